@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the bigKRLS() fit on MI355X, BASELINE.json's metric and configs.
 
-    python bench.py --gpus N --steps K --warmup W [--config C2|C3|C4|C5]
+    python bench.py --gpus N --steps K --warmup W [--config C2|C3|C4|C5] [--dump-outputs DIR] [--full]
 
 A step = one full bigKRLS() fit (kernel -> eigen -> lambda search -> coefficients ->
 variance matrices -> marginal effects). The default workload is configs[2] (C3), the
@@ -13,7 +13,15 @@ Neig=1024 which.derivatives=c(1,3,5)); --n/--p/--seed/--neig/--eigtrunc/--which-
 override single fields. Rank 0 prints ONE JSON line. For N > 1 the same fit is row-block
 partitioned over the ranks (strong scaling): see bigkrls_amd/dist.py.
 
-`roofline` is for the dominant kernel of the fit -- whichever of the profiled kernels takes
+A plain run sets up, warms up, times the K steps and prints the line: `value` (s per fit), `ms_per_step`,
+`phases_s` and the configuration. `--dump-outputs DIR` then also writes what the last timed fit returned as
+DIR/<name>.npy (float64; K and the variance matrices as a fixed, seeded sample of their entries), so that two builds
+can be compared output for output on the same inputs (with --gpus N > 1: rank 0's result, its row block of the N x N
+members, so only runs with the same N compare). `--full` adds everything else the benchmark measures: the
+per-kernel HIP-event sampling during the timed steps (`roofline`, `kernel_gemm`, `other_kernels`) and the CPU
+baseline. The sampling adds a few events to the timed fits, which is why a plain run leaves it off.
+
+`roofline` (--full) is for the dominant kernel of the fit -- whichever of the profiled kernels takes
 the most time on the critical path (dense path: the stage-1 band update / A22 V GEMMs, bulge
 chasing, or the one-stage symv; Neig << N: the K B_j product of the block Lanczos) --
 measured live with HIP events on the launch stream; the panel QR, which runs concurrently
@@ -21,9 +29,14 @@ on the look-ahead stream, is listed in `other_kernels`; `roofline.kernel_gemm` r
 Gaussian-kernel GEMM the metric names (time, TFLOP/s, HBM-write GB/s). The line is compact
 (< 5 KB: the driver keeps the tail of stdout); `--long-json` adds every entry's definition
 (DESIGN.md section 5 has them).
-`cpu_baseline` times the oracle's literal restatement of the reference on the host cores at
+`cpu_baseline` (--full) times the oracle's literal restatement of the reference on the host cores at
 the bench size (oracle/cpu_baseline.py, a child process started before the GPU is touched
-and released after the GPU timing; rank 0, N=1 only), bounded by --cpu-budget-s.
+and released after the GPU timing; rank 0, N=1 only), bounded by --cpu-budget-s (480 s: a --full
+run ends within 10 minutes). Within the budget it times the literal fit at the bench size in full up to
+dsyevd and the six timed probes, and as many derivative columns as fit (the rest at their mean). Where even
+that does not fit the host's cores, `value` is the full literal fit at N=2000 and the phases measured at the
+bench size are in `partial_phases_s` (the line's `sample` says which); --cpu-budget-s 880, the earlier
+default, gives such a host more time and the run then takes up to about 15 minutes.
 """
 import argparse
 import json
@@ -67,8 +80,17 @@ def parse():
                     help="comma-separated 1-based columns, e.g. 1,3,5")
     ap.add_argument("--cpu-n", type=int, default=None,
                     help="rows of the CPU-baseline sample (default: the bench N for C2/C3)")
-    ap.add_argument("--cpu-budget-s", type=float, default=880.0,
-                    help="wall-clock bound of the CPU baseline; what is measured until then is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel roofline figures (HIP-event sampling during the timed steps) and the "
+                         "CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed fit as DIR/<name>.npy (float64, at most 64 MB in all; "
+                         "with --gpus N > 1 rank 0's row block, comparable between runs with the same N)")
+    ap.add_argument("--cpu-budget-s", type=float, default=480.0,
+                    help="wall-clock bound of the CPU baseline (--full); what is measured until then is reported. "
+                         "The default keeps a --full run under 10 minutes; a host that cannot finish dsyevd and the "
+                         "timed probes at the bench size within it reports the N=2000 literal fit (880: the earlier "
+                         "default)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--force-dist", action="store_true",
                     help="route a single-GPU run through the row-block path (bigkrls_amd.dist) under an RCCL group "
@@ -79,6 +101,8 @@ def parse():
                     help="start the --gpus N rank processes, let them rendezvous over gloo on the CPU and build the "
                          "library's rank objects over host buffers -- no GPU, no fit: checks the launch path only")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     cfg = dict(CONFIGS[args.config])
     custom = False
     for key, val in (("n", args.n), ("p", args.p), ("seed", args.seed), ("neig", args.neig),
@@ -252,18 +276,19 @@ def compact_line(res):
     out = {k: v for k, v in res.items() if k not in ("roofline", "other_kernels", "kernel_gemm", "cpu_baseline", "config")}
     cfg = dict(res["config"])
     out["config"] = cfg
-    kg = res.get("kernel_gemm")
-    if kg:
-        kg = {k: v for k, v in kg.items() if k != "note"}
-    # `roofline` always exists in the line, and `kernel_gemm` -- half of BASELINE.json's metric -- always with it (also
-    # when no candidate kernel was sampled); a three-number copy stays at the top level for readers of older lines
-    out["roofline"] = _compact_entry(res["roofline"]) if res.get("roofline") else {}
-    out["roofline"]["kernel_gemm"] = kg
-    if out["roofline"].get("traffic") is not None:
-        out["roofline"]["traffic_source"] = res["roofline"].get("traffic_source", TRAFFIC_SOURCE)
-    if kg:
-        out["kernel_gemm"] = {k: kg[k] for k in ("tflops", "hbm_write_gbs", "ms") if k in kg}
-    out["other_kernels"] = [_compact_entry(e) for e in res.get("other_kernels", [])]
+    if "kernel_gemm" in res:                      # (--full)
+        kg = res["kernel_gemm"]
+        if kg:
+            kg = {k: v for k, v in kg.items() if k != "note"}
+        # `roofline` always exists in a --full line, and `kernel_gemm` -- half of BASELINE.json's metric -- always with it
+        # (also when no candidate kernel was sampled); a three-number copy stays at the top level for readers of older lines
+        out["roofline"] = _compact_entry(res["roofline"]) if res.get("roofline") else {}
+        out["roofline"]["kernel_gemm"] = kg
+        if out["roofline"].get("traffic") is not None:
+            out["roofline"]["traffic_source"] = res["roofline"].get("traffic_source", TRAFFIC_SOURCE)
+        if kg:
+            out["kernel_gemm"] = {k: kg[k] for k in ("tflops", "hbm_write_gbs", "ms") if k in kg}
+        out["other_kernels"] = [_compact_entry(e) for e in res.get("other_kernels", [])]
     cb = res.get("cpu_baseline")
     if cb:
         cb = dict(cb)
@@ -272,6 +297,54 @@ def compact_line(res):
         out["cpu_baseline"] = cb
     out["definitions"] = "DESIGN.md section 5"
     return out
+
+
+DUMP_SAMPLE = 1 << 19          # entries kept of a larger output (4 MB in float64)
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def _sample_positions(size):
+    """DUMP_SAMPLE sorted positions in [0, size), the same for the same size in every run."""
+    import numpy as np
+    return np.sort(np.random.default_rng(20240).choice(size, DUMP_SAMPLE, replace=False, shuffle=False))
+
+
+def dump_outputs(out, folder):
+    """`--dump-outputs`: every numeric member of the fit's result -- what a caller of the timed path receives -- as
+    folder/<name>.npy in float64. A member of more than DUMP_SAMPLE entries (K and the variance matrices, N x N in
+    HBM) is written as its entries at _sample_positions() of the column-major flattening. Members that are not
+    numeric (labels, None, the context) are left out."""
+    import numpy as np
+    from bigkrls_amd.device import DeviceMatrix
+
+    arrays = {}
+    for name, v in out.items():
+        if name.startswith("_") or v is None:
+            continue
+        if isinstance(v, DeviceMatrix):
+            size = v.nrow * v.ncol
+            if size <= DUMP_SAMPLE:
+                arrays[name] = v.to_numpy()
+                continue
+            ctx = v.ctx
+            with ctx.on_stream():
+                pos = ctx.torch.from_numpy(_sample_positions(size)).to(ctx.device)
+                picked = v.t.reshape(-1).index_select(0, pos)
+            arrays[name] = ctx.download(picked)
+            continue
+        a = np.asarray(v)
+        if a.dtype.kind not in "biuf":
+            continue
+        a = a.astype(np.float64)
+        arrays[name] = a.ravel(order="F")[_sample_positions(a.size)] if a.size > DUMP_SAMPLE else a
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes of outputs, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(folder, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(folder, name + ".npy"), a)
+    print(f"bench.py: {len(arrays)} outputs of the last timed fit written to {folder} ({total / 1e6:.1f} MB)",
+          file=sys.stderr)
 
 
 def _free_port():
@@ -415,7 +488,7 @@ def main():
     # ---- CPU-baseline child: started before anything here touches the GPU ------------------------
     cpu = None
     cpu_n = args.cpu_n if args.cpu_n is not None else (cfg["n"] if cfg["n"] <= 20000 else None)
-    if world == 1 and rank == 0 and not args.no_cpu_baseline and cpu_n is not None:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline and cpu_n is not None:
         cpu = CpuBaseline(cpu_n, cfg["p"], cfg["seed"], cfg["eigtrunc"], budget_s=args.cpu_budget_s)
 
     import numpy as np
@@ -452,7 +525,7 @@ def main():
         if cpu is not None:
             cpu.release()
             res["cpu_baseline"] = cpu.collect(args.cpu_budget_s)
-        elif world == 1 and not args.no_cpu_baseline:
+        elif args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = {
                 "value": None, "unit": "s per fit", "cores": os.cpu_count(), "kind": "port",
                 "sample": (f"not timed at N={cfg['n']}: the literal CPU path is infeasible at this size (dsyevd of a "
@@ -507,17 +580,19 @@ def run(args, cfg, world, rank, local_rank, np, torch, dist):
     for _ in range(args.warmup):
         out = one_fit({})
         del out
-    ctx.set_profile(True)
+    if args.full:
+        ctx.set_profile(True)
     phase_sum = {}
     barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
         T = {}
         out = one_fit(T)
         for k, v in T.items():
             phase_sum[k] = phase_sum.get(k, 0.0) + v
         lastkeeper, lam = out["lastkeeper"], out["lambda"]
-        del out
+        if not args.dump_outputs or i + 1 < args.steps:
+            del out
     barrier()
     dt = time.perf_counter() - t0
     if world > 1:
@@ -525,15 +600,20 @@ def run(args, cfg, world, rank, local_rank, np, torch, dist):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
     sec_per_fit = dt / args.steps
+    if args.dump_outputs:
+        if rank == 0:
+            dump_outputs(out, args.dump_outputs)
+        del out
 
-    prof = {name: ctx.get_profile(name) for name in
-            ("symv", "kernel_block", "trailing_update", "band_update", "band_update2", "band_update4", "band_av", "bulge_chase",
-             "panel_qr", "lanczos_kb", "lanczos_cgs2", "solveforc_probe", "deriv_rows", "yhat_gemv", "vcov_syrk")}
-    ctx.set_profile(False)
+    if args.full:
+        prof = {name: ctx.get_profile(name) for name in
+                ("symv", "kernel_block", "trailing_update", "band_update", "band_update2", "band_update4", "band_av",
+                 "bulge_chase", "panel_qr", "lanczos_kb", "lanczos_cgs2", "solveforc_probe", "deriv_rows", "yhat_gemv",
+                 "vcov_syrk")}
+        ctx.set_profile(False)
 
-    res = None
-    if rank == 0:
-        phases = {k: round(v / args.steps, 4) for k, v in phase_sum.items()}
+    full = {}
+    if rank == 0 and args.full:
         kb_ms, kb_flops, kb_n = prof["kernel_block"]
 
         STRIDE = 8   # the library brackets every 8th stage-1 panel (S1_PROF_STRIDE): totals are x8
@@ -759,6 +839,28 @@ def run(args, cfg, world, rank, local_rank, np, torch, dist):
             roof["fit_frac"] = round(fit_flops / sec_per_fit / (FP64_MFMA_PEAK_TFLOPS * 1e12), 4)
             roof["fit_frac_note"] = ("fit_frac = fit_flops / value / fp64 MFMA peak, fit_flops = " + fit_flops_note +
                                      "; the whole fit's wall-clock incl. everything that runs no MFMA")
+        full = {
+            "kernel_gemm": {
+                "gflops": round(kb_flops / (kb_ms / 1e3) / 1e9, 1) if kb_ms > 0 else None,
+                "tflops": round(kb_flops / (kb_ms / 1e3) / 1e12, 3) if kb_ms > 0 else None,
+                "frac_of_fp64_mfma_peak": round(kb_flops / (kb_ms / 1e3) / 1e12 / FP64_MFMA_PEAK_TFLOPS, 4) if kb_ms > 0 else None,
+                "hbm_write_gbs": round(8.0 * (kb_flops / (2.0 * p)) / 1e9 / (kb_ms / 1e3), 1) if kb_ms > 0 else None,
+                "frac_of_hbm_peak": round(8.0 * (kb_flops / (2.0 * p)) / 1e9 / (kb_ms / 1e3) / HBM_PEAK_GBS, 4) if kb_ms > 0 else None,
+                "ms": round(kb_ms / max(kb_n, 1), 4), "launches": kb_n,
+                "traffic": (round(8.0 * n * n * pmc_ratio("kernel_block_sym_kernel"), 0)
+                            if pmc_ratio("kernel_block_sym_kernel") else None),
+                "note": "kernel_block_sym_kernel: 2*N^2*P algorithmic flops per launch (the symmetric variant "
+                        "executes half of them and mirrors); for P <~ 40 the build is HBM-write bound (8 N^2 bytes, "
+                        "AI = P/4 flop/B), so the binding roofline is hbm_write_gbs / 8000"},
+            "roofline": roof,
+            "other_kernels": [c for c in cands if c["kernel"] != (roof or {}).get("kernel")] + extra,
+        }
+        if tu_ms > 0:
+            full["trailing_update"] = {"tflops": round(tu_flops / (tu_ms / 1e3) / 1e12, 3), "launches": tu_n}
+
+    res = None
+    if rank == 0:
+        phases = {k: round(v / args.steps, 4) for k, v in phase_sum.items()}
         res = {
             # BASELINE.json: "bigKRLS() fit wall-clock + kernel-GEMM fp64 GFLOP/s at N=20000,P=20";
             # `value` is the wall-clock half, `kernel_gemm.gflops` the GEMM half
@@ -786,23 +888,8 @@ def run(args, cfg, world, rank, local_rank, np, torch, dist):
                        "parallelism": ("1 GPU" if world == 1 and not args.force_dist
                                        else f"row-block x{world}, RCCL broadcast / all-gather")},
             "phases_s": phases,
-            "kernel_gemm": {
-                "gflops": round(kb_flops / (kb_ms / 1e3) / 1e9, 1) if kb_ms > 0 else None,
-                "tflops": round(kb_flops / (kb_ms / 1e3) / 1e12, 3) if kb_ms > 0 else None,
-                "frac_of_fp64_mfma_peak": round(kb_flops / (kb_ms / 1e3) / 1e12 / FP64_MFMA_PEAK_TFLOPS, 4) if kb_ms > 0 else None,
-                "hbm_write_gbs": round(8.0 * (kb_flops / (2.0 * p)) / 1e9 / (kb_ms / 1e3), 1) if kb_ms > 0 else None,
-                "frac_of_hbm_peak": round(8.0 * (kb_flops / (2.0 * p)) / 1e9 / (kb_ms / 1e3) / HBM_PEAK_GBS, 4) if kb_ms > 0 else None,
-                "ms": round(kb_ms / max(kb_n, 1), 4), "launches": kb_n,
-                "traffic": (round(8.0 * n * n * pmc_ratio("kernel_block_sym_kernel"), 0)
-                            if pmc_ratio("kernel_block_sym_kernel") else None),
-                "note": "kernel_block_sym_kernel: 2*N^2*P algorithmic flops per launch (the symmetric variant "
-                        "executes half of them and mirrors); for P <~ 40 the build is HBM-write bound (8 N^2 bytes, "
-                        "AI = P/4 flop/B), so the binding roofline is hbm_write_gbs / 8000"},
-            "roofline": roof,
-            "other_kernels": [c for c in cands if c["kernel"] != (roof or {}).get("kernel")] + extra,
         }
-        if tu_ms > 0:
-            res["trailing_update"] = {"tflops": round(tu_flops / (tu_ms / 1e3) / 1e12, 3), "launches": tu_n}
+        res.update(full)
     return res
 
 

@@ -27,6 +27,13 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 PORT_TAKEN = 97      # exit code of a rank whose rendezvous port was taken between the launcher's probe and its own bind
 
 
+def report(line):
+    """One write(2) per result line: the ranks share one log file, and with an unbuffered stdout print() writes the
+    text and its newline separately -- another rank's line can land between the two and hide both from the test."""
+    sys.stdout.flush()
+    os.write(1, (line + "\n").encode())
+
+
 def launcher():
     import socket
     import time
@@ -181,7 +188,7 @@ def worker():
         except BigKRLSError as e:
             msg = str(e)
             ok = e.code == ENOMEM and (("injected fault" in msg) if rank == fault_rank else ("another rank" in msg))
-        print(f"rank {rank}/{world} fault injected in rank {fault_rank}: {msg[:120]}" + (" OK" if ok else " MISMATCH"), flush=True)
+        report(f"rank {rank}/{world} fault injected in rank {fault_rank}: {msg[:120]}" + (" OK" if ok else " MISMATCH"))
         dist.barrier()
         bkdist.release_comms()
         dist.destroy_process_group()
@@ -202,8 +209,8 @@ def worker():
         everyone = [None] * world
         dist.all_gather_object(everyone, mine)
         replicas_ok = all(e == everyone[0] for e in everyone) and cnt["replica_diff"] == (1 if rank == ulp_rank else 0)
-        print(f"rank {rank}/{world} one-ulp deviation injected in rank {ulp_rank}: replicas "
-              f"{'bitwise identical' if all(e == everyone[0] for e in everyone) else 'DIFFER ' + repr(everyone)}, counters {cnt}", flush=True)
+        report(f"rank {rank}/{world} one-ulp deviation injected in rank {ulp_rank}: replicas "
+               f"{'bitwise identical' if all(e == everyone[0] for e in everyone) else 'DIFFER ' + repr(everyone)}, counters {cnt}")
     one = bk.bigKRLS(y, X, ctx=ctx, **kw)
 
     def rel(a, b):
@@ -227,9 +234,9 @@ def worker():
         vc = vc.to_numpy() if hasattr(vc, "to_numpy") else vc
         checks["vcov.est.c.cols"] = rel(out["vcov.est.c.cols"].to_numpy()[:, : r1 - r0], vc[:, r0:r1])
     ok = out["lastkeeper"] == one["lastkeeper"] and all(v < 1e-7 for v in checks.values()) and replicas_ok
-    print(f"rank {rank}/{world} N={n} P={p} neig={neig}: {dt:.2f} s lastkeeper {out['lastkeeper']} vs {one['lastkeeper']} "
-          + " ".join(f"{k}={v:.1e}" for k, v in checks.items())
-          + f" [redone={cnt['redone']} replayed={cnt['replayed']} replica_diff={cnt['replica_diff']}]" + (" OK" if ok else " MISMATCH"), flush=True)
+    report(f"rank {rank}/{world} N={n} P={p} neig={neig}: {dt:.2f} s lastkeeper {out['lastkeeper']} vs {one['lastkeeper']} "
+           + " ".join(f"{k}={v:.1e}" for k, v in checks.items())
+           + f" [redone={cnt['redone']} replayed={cnt['replayed']} replica_diff={cnt['replica_diff']}]" + (" OK" if ok else " MISMATCH"))
     dist.barrier()
     bkdist.release_comms()
     dist.destroy_process_group()

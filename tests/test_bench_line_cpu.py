@@ -1,6 +1,6 @@
-"""bench.py prints ONE compact JSON line: the driver keeps only the tail of stdout, so the line must stay small and
-carry BASELINE.json's second metric half -- the kernel GEMM -- inside `roofline`. Checked on a recorded long-form
-line of round 4 (profiles/r04/, a data file) without a GPU."""
+"""bench.py prints ONE compact JSON line: the driver keeps only the tail of stdout, so the line must stay small and,
+with --full, carry BASELINE.json's second metric half -- the kernel GEMM -- inside `roofline`. Checked on a recorded
+long-form line of round 4 (profiles/r04/, a data file) without a GPU."""
 import json
 import os
 import sys
@@ -89,3 +89,51 @@ def test_cpu_baseline_object_is_assembled_from_the_child_lines_and_fits_the_line
     long_form = json.load(open(os.path.join(ROOT, "profiles", "r04", "r04z_bench_C3_default_with_cpu_baseline.json")))
     long_form["cpu_baseline"] = res
     assert len(json.dumps(bench.compact_line(long_form))) < 6000
+
+
+def test_dump_outputs_writes_every_numeric_member_and_samples_the_large_ones(tmp_path):
+    """`--dump-outputs` on a result dict shaped like bigKRLS()'s (no GPU: a DeviceMatrix over a host tensor): float64
+    files for the numeric members only, a large member -- in HBM or on the host -- as its entries at the fixed sample
+    positions of its column-major flattening (the same positions for both), and the same files from two runs."""
+    import contextlib
+
+    import numpy as np
+    import torch
+
+    import bench
+    from bigkrls_amd.device import DeviceMatrix
+
+    class HostCtx:
+        device = torch.device("cpu")
+
+        def __init__(self):
+            self.torch = torch
+
+        def on_stream(self):
+            return contextlib.nullcontext()
+
+        def download(self, t):
+            return t.numpy().copy()
+
+    ctx = HostCtx()
+    nrow, ncol = 900, 800
+    big = DeviceMatrix(ctx, torch.arange(nrow * ncol, dtype=torch.float64).reshape(ncol, nrow))   # entry = its position
+    small = DeviceMatrix(ctx, torch.arange(6, dtype=torch.float64).reshape(2, 3))
+    host_big = np.arange(nrow * ncol, dtype=np.float64).reshape((nrow, ncol), order="F")                   # the same, on the host
+    out = {"K": big, "X": host_big, "vcov.est.c": small, "vcov.est.fitted": None, "coeffs": np.linspace(0.0, 1.0, 7),
+           "derivatives": np.ones((4, 2), order="F"), "lambda": 0.25, "lastkeeper": 3,
+           "binaryindicator": np.array([True, False]), "xlabs": ["x1", "x2"], "_ctx": ctx}
+    bench.dump_outputs(out, str(tmp_path / "a"))
+    bench.dump_outputs(out, str(tmp_path / "b"))
+    names = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert names == sorted(["K.npy", "X.npy", "vcov.est.c.npy", "coeffs.npy", "derivatives.npy", "lambda.npy", "lastkeeper.npy",
+                            "binaryindicator.npy"])
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b), f
+    k = np.load(tmp_path / "a" / "K.npy")
+    assert k.shape == (bench.DUMP_SAMPLE,) and np.array_equal(k, bench._sample_positions(nrow * ncol).astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "a" / "X.npy"), k)
+    assert np.array_equal(np.load(tmp_path / "a" / "vcov.est.c.npy"), small.to_numpy())
+    assert np.load(tmp_path / "a" / "lastkeeper.npy") == 3.0
+    assert sum((tmp_path / "a" / f).stat().st_size for f in names) < bench.DUMP_LIMIT_BYTES
