@@ -436,6 +436,67 @@ def predict(object: BigKRLS, newdata, se_pred=False, correct_SE=True, ytest=None
     return out
 
 
+def marginal_effects(object: BigKRLS, newdata, which_derivatives=None, ctx: Optional[Context] = None) -> dict:
+    """Marginal effects of a fitted model at new data points, without refitting: the pointwise derivatives
+    (u x |J|), their averages (1 x |J|) and the variances of the averages (1 x |J|; None when the object has no
+    vcov.est.c), in the original units and with the fit's definitions -- with newdata = X they are the fit's
+    `derivatives`, `avgderivatives` and `var.avgderivatives`. Binary training columns take the first difference
+    between their two training values, so newdata must hold one of those two values there. `which_derivatives`
+    (1-based) defaults to the object's own, or all columns. No counterpart in the reference (which computes the
+    marginal effects at the training rows only, R/bigKRLS.R:318-407). The numeric body is ONE call into the C ABI,
+    `bigkrls_marginal_effects`, which never forms the u x n test kernel."""
+    if not isinstance(object, BigKRLS):
+        raise TypeError("Object not of class 'bigKRLS'")
+    if "vcov.est.c.cols" in object or "rows" in object:
+        raise NotImplementedError("marginal_effects of a multi-GPU fit (sharded vcov.est.c.cols) is not supported; "
+                                  "refit on one GPU")
+    Xh = np.asfortranarray(np.asarray(object["X"], dtype=np.float64))
+    n, p = Xh.shape
+    nd_init = _as_host_matrix(newdata)
+    nd = np.array(nd_init, dtype=np.float64, order="F")
+    if nd.ndim != 2 or nd.shape[1] != p:
+        raise ValueError("ncol(newdata) differs from ncol(X) from fitted bigKRLS object")
+    u = nd.shape[0]
+    if u < 1:
+        raise ValueError("newdata has no rows")
+    if not np.all(np.isfinite(nd)):
+        raise ValueError("newdata contains missing or infinite values")
+    if which_derivatives is None:
+        which_derivatives = object.get("which.derivatives")
+    if which_derivatives is None:
+        which = list(range(1, p + 1))
+    else:
+        which = [int(i) for i in np.atleast_1d(which_derivatives)]
+        if not which or not all(1 <= i <= p for i in which):
+            raise ValueError("which.derivatives must index columns of X")
+    isbin = np.array([np.unique(Xh[:, j]).size == 2 for j in range(p)])          # the fit's rule (R/bigKRLS.R:242)
+    for j in sorted(set(i - 1 for i in which)):
+        if isbin[j]:
+            lo, hi = Xh[:, j].min(), Xh[:, j].max()
+            if not np.all((nd[:, j] == lo) | (nd[:, j] == hi)):
+                raise ValueError(f"newdata column {j + 1} is binary in the training data; its values must be "
+                                 f"one of the two training values ({lo:g}, {hi:g})")
+    ctx = ctx or object.get("_ctx") or default_context()
+    V = object.get("vcov.est.c")
+    Vd = None if V is None else (V if is_device_matrix(V) else ctx.from_numpy(np.asarray(V, dtype=np.float64)))
+    yv = np.ascontiguousarray(np.asarray(object["y"], dtype=np.float64).ravel())
+    coeffs = np.ascontiguousarray(np.asarray(object["coeffs"], dtype=np.float64).ravel())
+    which_arr = np.ascontiguousarray(which, dtype=np.int64)
+    nj = which_arr.size
+    D = np.empty((u, nj), dtype=np.float64, order="F")
+    avg = np.empty(nj)
+    var = np.empty(nj) if Vd is not None else None
+    _call_native("bigkrls_marginal_effects", ctx.handle, Xh.ctypes.data, n, p, yv.ctypes.data, coeffs.ctypes.data,
+                 float(object["sigma"]), which_arr.ctypes.data, nj, nd.ctypes.data, u,
+                 Vd.ptr if Vd is not None else None, D.ctypes.data, avg.ctypes.data,
+                 var.ctypes.data if var is not None else None)
+    xlabs = list(object.get("xlabs") or [f"x{i + 1}" for i in range(p)])
+    return {"derivatives": D, "avgderivatives": avg[None, :],
+            "var.avgderivatives": None if var is None else var[None, :],
+            "which.derivatives": which, "binaryindicator": isbin[which_arr - 1],
+            "xlabs": [xlabs[i - 1] for i in which], "newdata": nd_init}
+
+
 def _run_folds(jobs, contexts, fit_fn, predict_fn):
     """Run independent (train, test) jobs, one worker thread per context (== per GPU), and return
     the results in job order. Fold k goes to context k mod G: a fixed assignment, and because every

@@ -519,6 +519,13 @@ int bigkrls_dev_kernel_block(bigkrls_ctx* ctx, const double* A, int64_t u, int64
   return kernel_block(ctx, A, u, lda, B, v, ldb, p, sigma, out, ldo, diag_shift);
 }
 
+int bigkrls_dev_kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B,
+                                int64_t v, int64_t ldb, int64_t p, double sigma, const double* W, int64_t q,
+                                int64_t ldw, int trans, double* out, int64_t ldo) {
+  BK_TRY(check_ctx(ctx));
+  return kernel_contract(ctx, A, u, lda, B, v, ldb, p, sigma, W, q, ldw, trans, out, ldo);
+}
+
 int bigkrls_dev_gemm(bigkrls_ctx* ctx, int ta, int tb, int64_t m, int64_t n, int64_t k,
                      double alpha, const double* A, int64_t lda, const double* B, int64_t ldb,
                      double beta, double* C, int64_t ldc) {

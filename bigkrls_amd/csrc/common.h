@@ -190,6 +190,8 @@ enum Slot {
   SLOT_DIST_V = 41,        // ... column blocks of the variance matrices (same)
   SLOT_EIG_FLAGS = 42,     // completion flags of the persistent stage-2 back-transform's tasks
   SLOT_FIT_VERIFY = 43,    // the fit's check of a decomposition against K: Q r, Q (lambda o r), K Q r
+  SLOT_CONTRACT_PART = 44, // kernel_contract: partial sums of the loop splits
+  SLOT_ME_SMALL = 45,      // bigkrls_marginal_effects: standardised X and newdata, operands, products, D, S, V S
 };
 
 int ws_get(bigkrls_ctx* ctx, int slot, int64_t nbytes, void** out);
@@ -255,6 +257,12 @@ int gemm_nn_skinny48(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const do
 int kernel_block(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B,
                  int64_t v, int64_t ldb, int64_t p, double sigma, double* out, int64_t ldo,
                  int64_t diag_shift);
+
+// trans = 0: out (u x q, ldo) = K(A, B) W with W v x q; trans = 1: out (v x q, ldo) = K(A, B)' W with W u x q.
+// K(A, B) is kernel_block's kernel (diag_shift = -1), rebuilt tile by tile in registers and never stored.
+int kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
+                    int64_t ldb, int64_t p, double sigma, const double* W, int64_t q, int64_t ldw, int trans,
+                    double* out, int64_t ldo);
 
 int syrk_lower(bigkrls_ctx* ctx, int64_t m, int64_t k, double alpha, const double* A, int64_t lda,
                const double* B, int64_t ldb, double* C, int64_t ldc);

@@ -1851,4 +1851,241 @@ int kernel_block(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, cons
   return BIGKRLS_OK;
 }
 
+// ---------------------------------------------------------------------------
+// fused kernel contraction (marginal effects at new data points, csrc/margeff.hip)
+// ---------------------------------------------------------------------------
+// out (ns x q) = K(S, L) W with K(S, L)[s, l] = exp(-||S_s - L_l||^2 / sigma) and W (nl x q): the kernel tile is
+// rebuilt in registers and contracted at once, never written (flash-attention style). K(A, B)' = K(B, A), so
+// K(A, B) W (rows of A stationary, loop over B) and K(A, B)' W (rows of B stationary, loop over A) are this one kernel
+// with the roles of the operands swapped.
+// Each wave owns 64 stationary rows (4 MFMA tiles of 16) and 16 CT columns of W, and walks its share of the loop
+// rows 16 at a time:
+//   G = L_tile S_tile'  : mfma_f64_16x16x4(L, S), register r of lane holds (l = l0 + (lane >> 4) + 4 r, s = lane & 15)
+//   E = exp(-(|s|^2 + |l|^2 - 2 G) / sigma), the epilogue of kernel_block_wave_kernel, in place
+//   acc += E W_tile     : register r of E is the A operand of k-step r (A[row = lane & 15][k = lane >> 4] = E(s, l))
+// so neither the kernel tile nor a transpose of it touches LDS or memory. When the grid would leave compute units idle
+// (few stationary rows) the loop rows are split over several waves whose partial sums are added by
+// contract_reduce_kernel in a fixed order: no atomics, the result does not depend on scheduling.
+// KS > 0: P <= 4 KS and the stationary fragments stay in registers for the whole loop; KS == 0: any P, fragments
+// re-read (from L1 / L2) for every loop tile.
+constexpr int KC_MS = 4;   // 16-row stationary tiles per wave
+
+template <int KS, int CT>
+__global__ __launch_bounds__(NT) void kernel_contract_kernel(
+    const double* __restrict__ S, int64_t lds, int NS, const double* __restrict__ L, int64_t ldl, int NL, int P,
+    const double* __restrict__ nrm_s, const double* __restrict__ nrm_l, double neg_inv_sigma,
+    const double* __restrict__ W, int64_t ldw, int Q, double* __restrict__ out, int64_t ldo, int64_t split_stride,
+    int stiles, int nchunks, int nsplit, int ltiles, int64_t ntasks) {
+  __shared__ double etab[32];
+  if (threadIdx.x < 32) etab[threadIdx.x] = kExp2Tab32[threadIdx.x];
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w >= ntasks) return;
+  const int st = (int)(w % stiles);
+  const int cc = (int)((w / stiles) % nchunks);
+  const int sp = (int)(w / ((int64_t)stiles * nchunks));
+  const int s0 = st * 16 * KC_MS, c0 = cc * 16 * CT;
+  const int t_begin = (int)((int64_t)ltiles * sp / nsplit), t_end = (int)((int64_t)ltiles * (sp + 1) / nsplit);
+  const int lm = lane & 15, lk = lane >> 4;
+  const int steps = (P + 3) / 4;
+
+  int srow[KC_MS];
+  double ns[KC_MS];
+#pragma unroll
+  for (int m = 0; m < KC_MS; ++m) {
+    srow[m] = min(s0 + 16 * m + lm, NS - 1);
+    ns[m] = nrm_s[srow[m]];
+  }
+  // stationary fragments (k >= P zeroed: the loop side then reads a clamped, finite value)
+  double sf[KC_MS][KS > 0 ? KS : 1];
+  if (KS > 0) {
+#pragma unroll
+    for (int m = 0; m < KC_MS; ++m)
+#pragma unroll
+      for (int t = 0; t < (KS > 0 ? KS : 1); ++t) {
+        const int k = 4 * t + lk;
+        sf[m][t] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
+      }
+  }
+  d4 acc[KC_MS][CT];
+#pragma unroll
+  for (int m = 0; m < KC_MS; ++m)
+#pragma unroll
+    for (int c = 0; c < CT; ++c) acc[m][c] = (d4){0.0, 0.0, 0.0, 0.0};
+
+  for (int t = t_begin; t < t_end; ++t) {
+    const int l0 = t * 16;
+    const int lrow = min(l0 + lm, NL - 1);   // this lane's row of the L operand
+    double nl[4], wf[CT][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int l = l0 + lk + 4 * r;         // this lane's loop row in accumulator register r
+      nl[r] = nrm_l[min(l, NL - 1)];
+#pragma unroll
+      for (int c = 0; c < CT; ++c) {
+        const int col = c0 + 16 * c + lm;
+        wf[c][r] = (l < NL && col < Q) ? W[l + (int64_t)col * ldw] : 0.0;
+      }
+    }
+    d4 g[KC_MS];
+#pragma unroll
+    for (int m = 0; m < KC_MS; ++m) g[m] = (d4){0.0, 0.0, 0.0, 0.0};
+    if (KS > 0) {
+      double lf[KS > 0 ? KS : 1];
+#pragma unroll
+      for (int s = 0; s < (KS > 0 ? KS : 1); ++s) lf[s] = L[lrow + (int64_t)min(4 * s + lk, P - 1) * ldl];
+#pragma unroll
+      for (int s = 0; s < (KS > 0 ? KS : 1); ++s)
+#pragma unroll
+        for (int m = 0; m < KC_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sf[m][s], g[m], 0, 0, 0);
+    } else {
+      for (int s0k = 0; s0k < steps; s0k += 4) {
+        double lf[4], sg[KC_MS][4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const int k = 4 * (s0k + s) + lk;
+          lf[s] = L[lrow + (int64_t)min(k, P - 1) * ldl];
+#pragma unroll
+          for (int m = 0; m < KC_MS; ++m) sg[m][s] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+          for (int m = 0; m < KC_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sg[m][s], g[m], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < KC_MS; ++m) {
+      d4 e;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        double d2 = fma(-2.0, g[m][r], ns[m] + nl[r]);   // (kernel_block_wave_kernel's epilogue)
+        d2 = fmax(d2, 0.0);
+        e[r] = exp_nonpos_tab(d2 * neg_inv_sigma, etab);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < CT; ++c) acc[m][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(e[r], wf[c][r], acc[m][c], 0, 0, 0);
+    }
+  }
+  // acc[m][c] register r: (s = s0 + 16 m + (lane >> 4) + 4 r, col = c0 + 16 c + (lane & 15))
+  double* dst = out + (int64_t)sp * split_stride;
+#pragma unroll
+  for (int m = 0; m < KC_MS; ++m)
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+      const int col = c0 + 16 * c + lm;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int s = s0 + 16 * m + lk + 4 * r;
+        if (s < NS && col < Q) dst[s + (int64_t)col * ldo] = acc[m][c][r];
+      }
+    }
+}
+
+// out[s, c] = sum over the splits, in split order, of part[sp][s, c] (each ns x q, ld ns)
+__global__ void contract_reduce_kernel(int NS, int Q, int nsplit, const double* __restrict__ part,
+                                       double* __restrict__ out, int64_t ldo) {
+  const int64_t total = (int64_t)NS * Q, stride = total;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    double s = 0.0;
+    for (int k = 0; k < nsplit; ++k) s += part[(int64_t)k * stride + e];
+    out[(e % NS) + (e / NS) * ldo] = s;
+  }
+}
+
+int kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
+                    int64_t ldb, int64_t p, double sigma, const double* W, int64_t q, int64_t ldw, int trans,
+                    double* out, int64_t ldo) {
+  BK_REQUIRE(u > 0 && v > 0 && p > 0 && q > 0, "kernel_contract: bad dimensions");
+  BK_REQUIRE(u < (1ll << 31) && v < (1ll << 31) && p < (1ll << 20) && q < (1ll << 20), "kernel_contract: too large");
+  BK_REQUIRE(trans == 0 || trans == 1, "kernel_contract: trans must be 0 or 1");
+  BK_REQUIRE(sigma > 0.0, "kernel_contract: sigma must be > 0");
+  BK_REQUIRE(A && B && W && out, "kernel_contract: null pointer");
+  BK_REQUIRE(lda >= u && ldb >= v, "kernel_contract: leading dimension of A or B too small");
+  // trans = 0: stationary rows A, loop rows B; trans = 1: the reverse
+  const double* S = trans ? B : A;
+  const double* L = trans ? A : B;
+  const int64_t ns = trans ? v : u, nl = trans ? u : v;
+  const int64_t lds = trans ? ldb : lda, ldl = trans ? lda : ldb;
+  BK_REQUIRE(ldw >= nl && ldo >= ns, "kernel_contract: leading dimension of W or out too small");
+  void *pna = nullptr, *pnb = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_NORMS_A, u * sizeof(double), &pna));
+  BK_TRY(ws_get(ctx, SLOT_NORMS_B, v * sizeof(double), &pnb));
+  BK_TRY(row_sqnorms(ctx, A, u, p, lda, (double*)pna));
+  BK_TRY(row_sqnorms(ctx, B, v, p, ldb, (double*)pnb));
+  const double* nrm_s = (const double*)(trans ? pnb : pna);
+  const double* nrm_l = (const double*)(trans ? pna : pnb);
+
+  const int CT = q <= 16 ? 1 : (q <= 32 ? 2 : 4);
+  const int steps = (int)((p + 3) / 4);
+  const int ks = steps <= 8 ? steps : 0;
+  using KcFn = void (*)(const double*, int64_t, int, const double*, int64_t, int, int, const double*, const double*,
+                        double, const double*, int64_t, int, double*, int64_t, int64_t, int, int, int, int, int64_t);
+  KcFn fn = nullptr;
+#define BK_KCS(CTV)                                                                                                   \
+  switch (ks) {                                                                                                       \
+    case 1: fn = kernel_contract_kernel<1, CTV>; break;                                                               \
+    case 2: fn = kernel_contract_kernel<2, CTV>; break;                                                               \
+    case 3: fn = kernel_contract_kernel<3, CTV>; break;                                                               \
+    case 4: fn = kernel_contract_kernel<4, CTV>; break;                                                               \
+    case 5: fn = kernel_contract_kernel<5, CTV>; break;                                                               \
+    case 6: fn = kernel_contract_kernel<6, CTV>; break;                                                               \
+    case 7: fn = kernel_contract_kernel<7, CTV>; break;                                                               \
+    case 8: fn = kernel_contract_kernel<8, CTV>; break;                                                               \
+    default: fn = kernel_contract_kernel<0, CTV>; break;                                                              \
+  }
+  if (CT == 1) { BK_KCS(1) }
+  else if (CT == 2) { BK_KCS(2) }
+  else { BK_KCS(4) }
+#undef BK_KCS
+  const int64_t stiles = (ns + 16 * KC_MS - 1) / (16 * KC_MS);
+  const int64_t nchunks = (q + 16 * CT - 1) / (16 * CT);
+  const int64_t ltiles = (nl + 15) / 16;
+  // Loop splits against the wave slots the kernel can hold at once (2 or 3 per SIMD, by its registers): the time is
+  // about (rounds of resident waves) x (loop tiles per wave), so the split count minimises ceil(base s / slots) / s --
+  // a last round that is nearly empty costs as much as a full one (C3 shape: 313 tiles x 7 splits = 2191 waves on 2048
+  // slots took 1.36 ms). At most 64 splits, each at least 16 loop tiles (256 rows), all partial sums together at most
+  // 64 MB; fewer splits on a tie.
+  int cap = 0;
+  BK_TRY(resident_capacity(ctx, (const void*)fn, &cap, NT));
+  const int64_t slots = (int64_t)cap * (NT / 64);
+  const int64_t base = stiles * nchunks;
+  const int64_t max_split =
+      std::max<int64_t>(1, std::min<int64_t>({(int64_t)64, ltiles / 16, (64ll << 20) / (ns * q * (int64_t)sizeof(double))}));
+  int64_t nsplit = 1;
+  double best = (double)((base + slots - 1) / slots);
+  for (int64_t s = 2; s <= max_split; ++s) {
+    const double cost = (double)((base * s + slots - 1) / slots) / (double)s;
+    if (cost < best * 0.98) { best = cost; nsplit = s; }
+  }
+  const int64_t ntasks = base * nsplit;
+  BK_REQUIRE((ntasks + 3) / 4 < (1ll << 31), "kernel_contract: too many tiles");
+  double* dst = out;
+  int64_t ldd = ldo, split_stride = 0;
+  if (nsplit > 1) {
+    void* pp = nullptr;
+    BK_TRY(ws_get(ctx, SLOT_CONTRACT_PART, nsplit * ns * q * (int64_t)sizeof(double), &pp));
+    dst = (double*)pp;
+    ldd = ns;
+    split_stride = ns * q;
+  }
+  const dim3 grid((unsigned)((ntasks + 3) / 4));
+  BK_TRY(prof_begin(ctx, "kernel_contract", 2.0 * (double)u * (double)v * (double)(p + q)));
+  hipLaunchKernelGGL(fn, grid, dim3(NT), 0, ctx->stream, S, lds, (int)ns, L, ldl, (int)nl, (int)p, nrm_s, nrm_l,
+                     -1.0 / sigma, W, ldw, (int)q, dst, ldd, split_stride, (int)stiles, (int)nchunks, (int)nsplit,
+                     (int)ltiles, ntasks);
+  BK_CHECK_LAUNCH();
+  if (nsplit > 1) {
+    const int blocks = (int)std::min<int64_t>((ns * q + 255) / 256, 4096);
+    hipLaunchKernelGGL(contract_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (int)ns, (int)q, (int)nsplit,
+                       (const double*)dst, out, ldo);
+    BK_CHECK_LAUNCH();
+  }
+  BK_TRY(prof_end(ctx, "kernel_contract"));
+  return BIGKRLS_OK;
+}
+
 }  // namespace bk

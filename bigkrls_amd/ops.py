@@ -60,6 +60,22 @@ def bTempKernel(X_new: DeviceMatrix, X_old: DeviceMatrix, sigma: float) -> Devic
     return out
 
 
+def bKernelContract(A: DeviceMatrix, B: DeviceMatrix, W: DeviceMatrix, sigma: float, trans: int = 0) -> DeviceMatrix:
+    """trans=0: K(A, B) W (u x q); trans=1: K(A, B)' W (v x q), with K(A, B) bTempKernel's kernel, built tile by
+    tile in registers and never stored (bigkrls_dev_kernel_contract). No counterpart in the reference."""
+    ctx = A.ctx
+    if A.ncol != B.ncol:
+        raise ValueError("bKernelContract: column counts of A and B differ")
+    if trans not in (0, 1):
+        raise ValueError("bKernelContract: trans must be 0 or 1")
+    if W.nrow != (B.nrow if trans == 0 else A.nrow):
+        raise ValueError("bKernelContract: W has the wrong number of rows")
+    out = ctx.empty(A.nrow if trans == 0 else B.nrow, W.ncol)
+    _lib.call("bigkrls_dev_kernel_contract", ctx.handle, A.ptr, A.nrow, A.ld, B.ptr, B.nrow, B.ld, A.ncol,
+              float(sigma), W.ptr, W.ncol, W.ld, int(trans), out.ptr, out.ld)
+    return out
+
+
 # ---------------------------------------------------------------------------
 # eigen   (R/bigKRLS_Rcpp_functions.R:173-199)
 # ---------------------------------------------------------------------------

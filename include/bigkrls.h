@@ -196,6 +196,14 @@ int bigkrls_dev_kernel_block(bigkrls_ctx* ctx, const double* A, int64_t u, int64
                              const double* B, int64_t v, int64_t ldb, int64_t p, double sigma,
                              double* out, int64_t ldo, int64_t diag_shift);
 
+/* Fused kernel contraction: trans = 0: out (u x q, ldo) = K(A,B) W with W v x q (ldw);
+ * trans = 1: out (v x q, ldo) = K(A,B)' W with W u x q (ldw). K(A,B) is exactly bigkrls_dev_kernel_block's
+ * kernel with diag_shift = -1; it is rebuilt tile by tile in registers and never written to memory (extra
+ * device memory O((u + v) q), never O(u v)). Deterministic: two calls give bitwise identical results. */
+int bigkrls_dev_kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda,
+                                const double* B, int64_t v, int64_t ldb, int64_t p, double sigma,
+                                const double* W, int64_t q, int64_t ldw, int trans, double* out, int64_t ldo);
+
 /* C (m x n) = alpha * op(A) op(B) + beta * C ; transa/transb: 0 = N, 1 = T. */
 int bigkrls_dev_gemm(bigkrls_ctx* ctx, int transa, int transb, int64_t m, int64_t n, int64_t k,
                      double alpha, const double* A, int64_t lda, const double* B, int64_t ldb,
@@ -380,6 +388,20 @@ int bigkrls_predict(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, c
                     const double* h_coeffs, double sigma, const double* h_newdata, int64_t u,
                     const double* d_vcov_c, double neffective,
                     double* h_predicted, double* h_se_pred, double* d_newdataK, double* d_vcov_pred);
+
+/* Marginal effects of a fitted model at new data points (no counterpart in the reference, which computes them at
+ * the training rows only, R/bigKRLS.R:318-407). X (n x p), y, coeffs (n) and sigma are the fit's; newdata (u x p,
+ * host) is standardised with the TRAINING means and sds. h_which (1-based, n_which entries) selects the columns J;
+ * NULL: all p. Binary training columns (exactly two distinct values) take the first difference between the two
+ * training values; newdata must hold one of those two values in such a column (else BIGKRLS_EINVAL naming it).
+ * Outputs in the original units, like the fit's: h_derivatives (u x |J| column-major; may be NULL), h_avg (|J|), and,
+ * with d_vcov_c (the fit's n x n device-resident vcov.est.c, ld n) given, h_var (|J|) = the variance of each average;
+ * d_vcov_c NULL requires h_var NULL. With newdata = X the results equal the fit's derivatives, avgderivatives and
+ * var.avgderivatives. The u x n test kernel is never formed (bigkrls_dev_kernel_contract). */
+int bigkrls_marginal_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                             const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
+                             const double* h_newdata, int64_t u, const double* d_vcov_c, double* h_derivatives,
+                             double* h_avg, double* h_var);
 
 /* =============================================================================
  * Multi-GPU: one process per GPU, the collectives inside the library (the context's
