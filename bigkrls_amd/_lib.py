@@ -94,6 +94,7 @@ SIGNATURES = {
     # level 2
     "bigkrls_dev_kernel_block": [vp, vp, i64, i64, vp, i64, i64, i64, f64, vp, i64, i64],
     "bigkrls_dev_kernel_contract": [vp, vp, i64, i64, vp, i64, i64, i64, f64, vp, i64, i64, C.c_int, vp, i64],
+    "bigkrls_dev_quadform_diag": [vp, i64, i64, vp, i64, vp, i64, vp],
     "bigkrls_dev_gemm": [vp, C.c_int, C.c_int, i64, i64, i64, f64, vp, i64, vp, i64, f64, vp, i64],
     "bigkrls_dev_multdiag": [vp, vp, i64, i64, i64, vp, vp, i64],
     "bigkrls_dev_eigen": [vp, vp, i64, i64, i64, vp, i64, f64, vp, i64, pi64],
@@ -118,6 +119,7 @@ SIGNATURES = {
     # level 2, whole path
     "bigkrls_fit": [vp, vp, vp, i64, i64, C.POINTER(FitOptions), C.POINTER(FitOutputs)],
     "bigkrls_predict": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, f64, vp, vp, vp, vp],
+    "bigkrls_predict_pointwise": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, f64, vp, vp],
     "bigkrls_marginal_effects": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, vp, vp, vp, vp],
     # multi-GPU
     "bigkrls_comm_unique_id": [vp],

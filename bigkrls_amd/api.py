@@ -393,9 +393,13 @@ def summary(object: BigKRLS, degrees: str = "Neffective", probs=(0.05, 0.25, 0.5
 
 
 def predict(object: BigKRLS, newdata, se_pred=False, correct_SE=True, ytest=None,
-            ctx: Optional[Context] = None) -> BigKRLSPredicted:
+            ctx: Optional[Context] = None, matrices=True) -> BigKRLSPredicted:
     """predict.bigKRLS (R/bigKRLS.R:547-637); the numeric body (:590-621) is ONE call into the
-    C ABI, `bigkrls_predict` (include/bigkrls.h, csrc/fit.hip)."""
+    C ABI, `bigkrls_predict` (include/bigkrls.h, csrc/fit.hip).
+
+    matrices=False: the same `predicted` and `se.pred` through `bigkrls_predict_pointwise`, which takes the new
+    points in row blocks and never forms newdataK (u x n) or vcov.est.pred (u x u); both come back as None. Its
+    extra device memory stays near 1.1 GiB whatever the number of new points."""
     if not isinstance(object, BigKRLS):
         raise TypeError("Object not of class 'bigKRLS'")
     if se_pred and object.get("vcov.est.c") is None:
@@ -412,6 +416,9 @@ def predict(object: BigKRLS, newdata, se_pred=False, correct_SE=True, ytest=None
     yv = np.ascontiguousarray(np.asarray(object["y"], dtype=np.float64).ravel())
     coeffs = np.ascontiguousarray(np.asarray(object["coeffs"], dtype=np.float64).ravel())
     ypred = np.empty(u)
+    if not matrices:
+        return _predict_pointwise(object, ctx, Xh, nd, nd_init, yv, coeffs, ypred, se_pred, correct_SE, ytest,
+                                  bigmatrix_in)
     newdataK = ctx.empty(u, n)
     se = vcov_est_pred = Vd = None
     neff = -1.0
@@ -432,6 +439,28 @@ def predict(object: BigKRLS, newdata, se_pred=False, correct_SE=True, ytest=None
     out = BigKRLSPredicted(predicted=ypred, newdata=nd_init, newdataK=newdataK, ytest=ytest)
     out["se.pred"] = se
     out["vcov.est.pred"] = vcov_est_pred
+    out["has.big.matrices"] = bigmatrix_in
+    return out
+
+
+def _predict_pointwise(object, ctx, Xh, nd, nd_init, yv, coeffs, ypred, se_pred, correct_SE, ytest, bigmatrix_in):
+    """predict(..., matrices=False) after predict()'s own checks: one call into bigkrls_predict_pointwise."""
+    n, p = Xh.shape
+    u = nd.shape[0]
+    se = Vd = None
+    neff = -1.0
+    if se_pred:
+        V = object["vcov.est.c"]
+        Vd = V if is_device_matrix(V) else ctx.from_numpy(np.asarray(V))
+        se = np.empty(u)
+        if correct_SE and object.get("Neffective") is not None:                   # :610-611
+            neff = float(object["Neffective"])
+    _call_native("bigkrls_predict_pointwise", ctx.handle, Xh.ctypes.data, n, p, yv.ctypes.data, coeffs.ctypes.data,
+                 float(object["sigma"]), nd.ctypes.data, u, Vd.ptr if se_pred else None, neff,
+                 ypred.ctypes.data, se.ctypes.data if se_pred else None)
+    out = BigKRLSPredicted(predicted=ypred, newdata=nd_init, newdataK=None, ytest=ytest)
+    out["se.pred"] = se
+    out["vcov.est.pred"] = None
     out["has.big.matrices"] = bigmatrix_in
     return out
 

@@ -526,6 +526,12 @@ int bigkrls_dev_kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, in
   return kernel_contract(ctx, A, u, lda, B, v, ldb, p, sigma, W, q, ldw, trans, out, ldo);
 }
 
+int bigkrls_dev_quadform_diag(bigkrls_ctx* ctx, int64_t m, int64_t n, const double* A, int64_t lda, const double* V,
+                              int64_t ldv, double* out) {
+  BK_TRY(check_ctx(ctx));
+  return quadform_diag(ctx, m, n, A, lda, V, ldv, out);
+}
+
 int bigkrls_dev_gemm(bigkrls_ctx* ctx, int ta, int tb, int64_t m, int64_t n, int64_t k,
                      double alpha, const double* A, int64_t lda, const double* B, int64_t ldb,
                      double beta, double* C, int64_t ldc) {

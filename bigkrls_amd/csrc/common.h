@@ -65,7 +65,7 @@ struct bigkrls_ctx {
   bool side_is_main = false;   // BIGKRLS_NO_SIDE (diagnostics): side_stream is the main stream itself
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_pq = nullptr;
   // workspace slots: slot i is grown on demand and reused across calls
-  static constexpr int kSlots = 48;
+  static constexpr int kSlots = 50;
   void* ws[kSlots] = {nullptr};
   int64_t ws_bytes[kSlots] = {0};
   // pinned host scratch for small scalar read-backs
@@ -192,6 +192,9 @@ enum Slot {
   SLOT_FIT_VERIFY = 43,    // the fit's check of a decomposition against K: Q r, Q (lambda o r), K Q r
   SLOT_CONTRACT_PART = 44, // kernel_contract: partial sums of the loop splits
   SLOT_ME_SMALL = 45,      // bigkrls_marginal_effects: standardised X and newdata, operands, products, D, S, V S
+  SLOT_PP_SMALL = 46,      // bigkrls_predict_pointwise: standardised X, c, one block of newdata, yhat, diag
+  SLOT_PP_K = 47,          // ... one row block of the test kernel (at most 1 GiB)
+  SLOT_QF_PART = 48,       // quadform_diag: one partial per row, column tile and k split
 };
 
 int ws_get(bigkrls_ctx* ctx, int slot, int64_t nbytes, void** out);
@@ -263,6 +266,11 @@ int kernel_block(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, cons
 int kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
                     int64_t ldb, int64_t p, double sigma, const double* W, int64_t q, int64_t ldw, int trans,
                     double* out, int64_t ldo);
+
+// out (m) = diag(A V A'), i.e. out[i] = sum_j (A V)[i,j] A[i,j]; A m x n (lda), V n x n (ldv), V general. The product
+// A V is never stored; deterministic (fixed-order reduction of the per-tile partials).
+int quadform_diag(bigkrls_ctx* ctx, int64_t m, int64_t n, const double* A, int64_t lda, const double* V, int64_t ldv,
+                  double* out);
 
 int syrk_lower(bigkrls_ctx* ctx, int64_t m, int64_t k, double alpha, const double* A, int64_t lda,
                const double* B, int64_t ldb, double* C, int64_t ldc);

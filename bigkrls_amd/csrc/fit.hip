@@ -1014,4 +1014,79 @@ int bigkrls_predict(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, c
   return BIGKRLS_OK;
 }
 
+
+int bigkrls_predict_pointwise(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                              const double* h_coeffs, double sigma, const double* h_newdata, int64_t u,
+                              const double* d_vcov_c, double neff, double* h_predicted, double* h_se_pred) {
+  // bigkrls_predict's validation and standardisation; then row blocks of b new points: kernel_block, gemv, and for
+  // the SEs diag(Kn_b vcov.est.c Kn_b') (quadform_diag), the one entry of vcov.est.pred per point that se.pred needs.
+  BK_TRY(fit_check_ctx(ctx));
+  BK_REQUIRE(h_X && h_y && h_coeffs && h_newdata && h_predicted, "predict: null argument");
+  BK_REQUIRE(n > 1 && p > 0 && u > 0 && sigma > 0.0, "predict: bad dimensions or sigma");
+  const bool want_se = h_se_pred != nullptr;
+  if (want_se && !d_vcov_c) {
+    set_error("recompute bigKRLS object with bigKRLS(,vcov.est=TRUE) to compute standard errors");     // R/bigKRLS.R:553
+    return BIGKRLS_EINVAL;
+  }
+  // rows per block (include/bigkrls.h): the largest multiple of 128 whose b x n test-kernel block fits 1 GiB, at least
+  // 128, and no more than u
+  const int64_t b_rule = std::max<int64_t>(128, ((1ll << 30) / (n * (int64_t)sizeof(double))) / 128 * 128);
+  const int64_t b = std::min(b_rule, u);
+  hipStream_t st = ctx->stream;
+  const int64_t small_doubles = n * p + n + b * p + 2 * u + 64;
+  void* psmall = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_PP_SMALL, small_doubles * (int64_t)sizeof(double), &psmall));
+  double* q = (double*)psmall;
+  double* dX = q; q += n * p;
+  double* dc = q; q += n;
+  double* dZ = q; q += b * p;
+  double* dpred = q; q += u;
+  double* ddiag = q; q += u;
+  void* pk = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_PP_K, b * n * (int64_t)sizeof(double), &pk));
+  double* dKn = (double*)pk;
+  // pinned host: [Xs | c | Zs, block by block, each block's rows x p contiguous] uploaded, [yhat | diag] read back
+  double* pin = nullptr;
+  BK_HIP(hipStreamSynchronize(st));   // (the pinned buffer may be reallocated)
+  BK_TRY(pinned_get(ctx, n * p + n + u * p + 2 * u, &pin));
+  double* pz = pin + n * p + n;
+  double* pout = pz + u * p;
+  // standardise both with the TRAINING means and sds, as bigkrls_predict (R/bigKRLS.R:590-597)
+  for (int64_t j = 0; j < p; ++j) {
+    double m, s;
+    mean_sd(h_X + j * n, n, &m, &s);
+    if (s == 0.0) {
+      set_error("predict: a training column is constant");
+      return BIGKRLS_EINVAL;
+    }
+    const double* x = h_X + j * n;
+    double* xs = pin + j * n;
+    for (int64_t i = 0; i < n; ++i) xs[i] = (x[i] - m) / s;
+    const double* z = h_newdata + j * u;
+    for (int64_t r0 = 0; r0 < u; r0 += b) {
+      const int64_t rows = std::min(b, u - r0);
+      double* zs = pz + r0 * p + j * rows;
+      for (int64_t i = 0; i < rows; ++i) zs[i] = (z[r0 + i] - m) / s;
+    }
+  }
+  std::memcpy(pin + n * p, h_coeffs, (size_t)n * sizeof(double));
+  BK_HIP(hipMemcpyAsync(dX, pin, (size_t)(n * p + n) * sizeof(double), hipMemcpyHostToDevice, st));
+  for (int64_t r0 = 0; r0 < u; r0 += b) {
+    const int64_t rows = std::min(b, u - r0);
+    BK_HIP(hipMemcpyAsync(dZ, pz + r0 * p, (size_t)(rows * p) * sizeof(double), hipMemcpyHostToDevice, st));
+    BK_TRY(kernel_block(ctx, dZ, rows, rows, dX, n, n, p, sigma, dKn, rows, -1));                       // bTempKernel (:599)
+    BK_TRY(gemv(ctx, 0, rows, n, 1.0, dKn, rows, dc, 0.0, dpred + r0));                                // :601
+    if (want_se) BK_TRY(quadform_diag(ctx, rows, n, dKn, rows, d_vcov_c, n, ddiag + r0));               // diag of :608
+  }
+  if (want_se && neff > 0.0) BK_TRY(scale(ctx, u, std::sqrt((double)n / neff), ddiag));                // :610-611 (Q10)
+  double y_mean, y_sd;
+  mean_sd(h_y, n, &y_mean, &y_sd);
+  BK_HIP(hipMemcpyAsync(pout, dpred, (size_t)(want_se ? 2 * u : u) * sizeof(double), hipMemcpyDeviceToHost, st));
+  BK_HIP(hipStreamSynchronize(st));
+  for (int64_t i = 0; i < u; ++i) h_predicted[i] = pout[i] * y_sd + y_mean;                            // :621
+  if (h_se_pred)
+    for (int64_t i = 0; i < u; ++i) h_se_pred[i] = std::sqrt(pout[u + i]);                             // :613
+  return BIGKRLS_OK;
+}
+
 }  // extern "C"

@@ -2088,4 +2088,150 @@ int kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, c
   return BIGKRLS_OK;
 }
 
+
+// ---------------------------------------------------------------------------
+// diagonal of a quadratic form (pointwise predict, bigkrls_predict_pointwise in csrc/fit.hip)
+// ---------------------------------------------------------------------------
+// out[i] = sum_j (A V)[i,j] A[i,j] = diag(A V A'), A m x n, V n x n general (not assumed symmetric), both column-major.
+// The product A V runs through gemm_tile<false, false, BN> exactly as gemm_kernel does; only the epilogue differs. Each
+// lane multiplies its accumulators by A at the same (row, column) and sums over its columns; the four lanes that share
+// a row (lane >> 4) are added with shuffles and the two waves that share a row half through LDS, in a fixed order.
+// Each workgroup writes one partial per row: part[(z tiles_n + tn) M + row]. The dot with A is linear in the product,
+// so the k splits' partials are dotted and added like the column tiles' (quadform_reduce_kernel, fixed order: no
+// atomics, bitwise reproducible). Extra memory: splits x tiles_n x m doubles, never the m x n product.
+template <int BN>
+__global__ __launch_bounds__(NT, (gemm_occ<false, false, BN>())) void quadform_diag_kernel(
+    GemmOperands g, int tiles_m, int tiles_n, int k_chunk, double* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int ntile = tiles_m * tiles_n;
+  const int tid = xcd_remap(blockIdx.x, ntile);
+  const int tm = tid % tiles_m, tn = tid / tiles_m;
+  const int m0 = tm * BM, n0 = tn * BN;
+  const int z = blockIdx.y;
+  const int kbeg = z * k_chunk;
+  const int kend = min(g.K, kbeg + k_chunk);
+  d4 acc[4][BN / 32];
+  gemm_tile<false, false, BN, false, (BN <= GEMM_DEEP_BN && gemm_occ<false, false, BN>() <= GEMM_OCC)>(g, m0, n0, kbeg,
+                                                                                                       kend, smem, acc);
+  constexpr int NJ = BN / 32;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wm = (wave & 1) * 64, wn = (wave >> 1) * (BN / 2);
+  const int lm = lane & 15, lk = lane >> 4;
+  const int M = g.M, N = g.N;
+  // register r of acc[i][j] is (m0 + wm + 16 i + lm, n0 + wn + 16 j + lk + 4 r), as in acc_foreach; columns past N
+  // hold products with clamped (finite) operand columns and are weighted by 0, rows past M are never written
+  double s[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int m = m0 + wm + i * 16 + lm;
+    const double* arow = g.A + (m < M ? m : M - 1);
+    double a[NJ][4];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int n = n0 + wn + j * 16 + lk + 4 * r;
+        a[j][r] = n < N ? arow[(int64_t)n * g.lda] : 0.0;
+      }
+    double t = 0.0;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) t = fma(acc[i][j][r], a[j][r], t);
+    t += __shfl_xor(t, 16, 64);
+    t += __shfl_xor(t, 32, 64);
+    s[i] = t;
+  }
+  // gemm_tile ends on a barrier after its last LDS read; this one is for the early return of an empty k range
+  __syncthreads();
+  double* red = smem;   // [wave][64 rows of the wave's half]
+  if (lk == 0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) red[wave * 64 + i * 16 + lm] = s[i];
+  }
+  __syncthreads();
+  if (threadIdx.x < BM) {
+    const int r = threadIdx.x, h = r >> 6, rr = r & 63;       // waves h and h + 2 own rows [64 h, 64 h + 64)
+    const int m = m0 + r;
+    if (m < M) part[((int64_t)z * tiles_n + tn) * M + m] = red[h * 64 + rr] + red[(h + 2) * 64 + rr];
+  }
+}
+
+// out[i] = sum over q = z tiles_n + tn of part[q M + i], in the order q = 0, 1, ...
+__global__ void quadform_reduce_kernel(const double* __restrict__ part, int nparts, int M, double* __restrict__ out) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += gridDim.x * blockDim.x) {
+    const double* p = part + i;
+    double s = 0.0;
+    int q = 0;
+    for (; q + 4 <= nparts; q += 4) {   // four loads in flight, added in order
+      const double a0 = p[(int64_t)(q + 0) * M], a1 = p[(int64_t)(q + 1) * M];
+      const double a2 = p[(int64_t)(q + 2) * M], a3 = p[(int64_t)(q + 3) * M];
+      s += a0; s += a1; s += a2; s += a3;
+    }
+    for (; q < nparts; ++q) s += p[(int64_t)q * M];
+    out[i] = s;
+  }
+}
+
+template <int BN>
+static int launch_quadform_diag(bigkrls_ctx* ctx, const GemmOperands& g, double* out) {
+  const int tiles_m = (g.M + BM - 1) / BM;
+  const int tiles_n = (g.N + BN - 1) / BN;
+  const int ntile = tiles_m * tiles_n;
+  // split-K with launch_gemm's time model (rounds of the resident workgroups times k-steps per split, plus a cost per
+  // split). Per split the partials are one double per row and column tile, but the epilogue reads A's m x n again:
+  // 8 bytes per element of the product instead of the 16 of gemm's partial slabs.
+  int splits = 1;
+  if (ntile < 4096 && g.K >= 1024) {
+    const int maxs = std::min(64, std::max(1, g.K / 256));
+    const double per_split = 1.6e-6 * (double)g.M * (double)g.N + 0.2;
+    double best = 1e30;
+    constexpr int resident = 256 * gemm_occ<false, false, BN>();
+    for (int sp = 1; sp <= maxs; ++sp) {
+      const int rounds = (ntile * sp + resident - 1) / resident;
+      const double cost = 0.06 * rounds * ((double)g.K / sp) + per_split * sp;
+      if (cost < best - 1e-9) { best = cost; splits = sp; }
+    }
+  }
+  int k_chunk = ((g.K + splits - 1) / splits + BK - 1) / BK * BK;
+  if (k_chunk < BK) k_chunk = BK;
+  splits = (g.K + k_chunk - 1) / k_chunk;
+  if (splits < 1) splits = 1;
+  const int nparts = splits * tiles_n;
+  void* p = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_QF_PART, (int64_t)nparts * g.M * (int64_t)sizeof(double), &p));
+  auto kern = quadform_diag_kernel<BN>;
+  constexpr size_t smem = gemm_smem_bytes<false, false, BN>();
+  static_assert(smem >= 4 * 64 * sizeof(double), "quadform_diag_kernel: LDS too small for the row reduction");
+  BK_TRY(ensure_dyn_smem(ctx, (const void*)kern, smem));
+  hipLaunchKernelGGL(kern, dim3(ntile, splits), dim3(NT), smem, ctx->stream, g, tiles_m, tiles_n, k_chunk, (double*)p);
+  BK_CHECK_LAUNCH();
+  const int blocks = std::min((g.M + 255) / 256, 2048);
+  hipLaunchKernelGGL(quadform_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const double*)p, nparts, g.M,
+                     out);
+  BK_CHECK_LAUNCH();
+  return BIGKRLS_OK;
+}
+
+int quadform_diag(bigkrls_ctx* ctx, int64_t m, int64_t n, const double* A, int64_t lda, const double* V, int64_t ldv,
+                  double* out) {
+  BK_REQUIRE(m >= 0 && n >= 0, "quadform_diag: negative dimension");
+  BK_REQUIRE(m < (1ll << 31) && n < (1ll << 31), "quadform_diag: dimension too large");
+  if (m == 0) return BIGKRLS_OK;
+  BK_REQUIRE(out, "quadform_diag: null pointer");
+  if (n == 0) {   // empty sum
+    BK_HIP(hipMemsetAsync(out, 0, (size_t)m * sizeof(double), ctx->stream));
+    return BIGKRLS_OK;
+  }
+  BK_REQUIRE(A && V, "quadform_diag: null pointer");
+  BK_REQUIRE(lda >= m && ldv >= n, "quadform_diag: leading dimension of A or V too small");
+  GemmOperands g{A, V, lda, ldv, (int)m, (int)n, (int)n, nullptr};
+  BK_TRY(prof_begin(ctx, "quadform_diag", 2.0 * (double)m * (double)n * (double)n + 2.0 * (double)m * (double)n));
+  if (n <= 32) BK_TRY(launch_quadform_diag<32>(ctx, g, out));
+  else if (n <= 64) BK_TRY(launch_quadform_diag<64>(ctx, g, out));
+  else BK_TRY(launch_quadform_diag<128>(ctx, g, out));
+  BK_TRY(prof_end(ctx, "quadform_diag"));
+  return BIGKRLS_OK;
+}
+
 }  // namespace bk

@@ -76,6 +76,17 @@ def bKernelContract(A: DeviceMatrix, B: DeviceMatrix, W: DeviceMatrix, sigma: fl
     return out
 
 
+def bQuadformDiag(A: DeviceMatrix, V: DeviceMatrix) -> DeviceMatrix:
+    """diag(A V A') (m x 1) for A m x n and a general V n x n: out[i] = sum_j (A V)[i,j] A[i,j], without storing
+    A V (bigkrls_dev_quadform_diag). No counterpart in the reference."""
+    ctx = A.ctx
+    if V.nrow != A.ncol or V.ncol != A.ncol:
+        raise ValueError("bQuadformDiag: V must be ncol(A) x ncol(A)")
+    out = ctx.empty(A.nrow, 1)
+    _lib.call("bigkrls_dev_quadform_diag", ctx.handle, A.nrow, A.ncol, A.ptr, A.ld, V.ptr, V.ld, out.ptr)
+    return out
+
+
 # ---------------------------------------------------------------------------
 # eigen   (R/bigKRLS_Rcpp_functions.R:173-199)
 # ---------------------------------------------------------------------------

@@ -204,6 +204,13 @@ int bigkrls_dev_kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, in
                                 const double* B, int64_t v, int64_t ldb, int64_t p, double sigma,
                                 const double* W, int64_t q, int64_t ldw, int trans, double* out, int64_t ldo);
 
+/* Diagonal of a quadratic form: out[i] = sum_j (A V)[i,j] A[i,j] = diag(A V A')[i], A m x n (lda >= m),
+ * V n x n (ldv >= n), both column-major; V is general (not assumed symmetric). out has m entries. The m x n product
+ * is never stored (extra device memory: a few doubles per row and 128-column tile). Deterministic: two calls give
+ * bitwise identical results. */
+int bigkrls_dev_quadform_diag(bigkrls_ctx* ctx, int64_t m, int64_t n, const double* A, int64_t lda,
+                              const double* V, int64_t ldv, double* out);
+
 /* C (m x n) = alpha * op(A) op(B) + beta * C ; transa/transb: 0 = N, 1 = T. */
 int bigkrls_dev_gemm(bigkrls_ctx* ctx, int transa, int transb, int64_t m, int64_t n, int64_t k,
                      double alpha, const double* A, int64_t lda, const double* B, int64_t ldb,
@@ -388,6 +395,18 @@ int bigkrls_predict(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, c
                     const double* h_coeffs, double sigma, const double* h_newdata, int64_t u,
                     const double* d_vcov_c, double neffective,
                     double* h_predicted, double* h_se_pred, double* d_newdataK, double* d_vcov_pred);
+
+/* predict.bigKRLS without the u x n and u x u matrices: the same inputs, validation, error messages and outputs as
+ * bigkrls_predict (predicted, and se.pred when h_se_pred is given), for any number u of new points. The new points
+ * are taken in row blocks of b: b is the largest multiple of 128 with 8 b n <= 2^30 bytes (the b x n test-kernel
+ * block fits 1 GiB), at least 128, and min(b, u) rows are used when u is smaller (n = 20 000: b = 6 656). Per block:
+ * the test kernel, its product with the coefficients, and with d_vcov_c the diagonal of K_b vcov.est.c K_b'
+ * (bigkrls_dev_quadform_diag), times sqrt(n / neffective) when neffective > 0. Extra device memory:
+ * O((u + n) p) plus the block and the quadratic form's partials, about 1.1 GiB at most, whatever u is. */
+int bigkrls_predict_pointwise(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                              const double* h_coeffs, double sigma, const double* h_newdata, int64_t u,
+                              const double* d_vcov_c, double neffective,
+                              double* h_predicted, double* h_se_pred);
 
 /* Marginal effects of a fitted model at new data points (no counterpart in the reference, which computes them at
  * the training rows only, R/bigKRLS.R:318-407). X (n x p), y, coeffs (n) and sigma are the fit's; newdata (u x p,
