@@ -65,7 +65,7 @@ struct bigkrls_ctx {
   bool side_is_main = false;   // BIGKRLS_NO_SIDE (diagnostics): side_stream is the main stream itself
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_pq = nullptr;
   // workspace slots: slot i is grown on demand and reused across calls
-  static constexpr int kSlots = 50;
+  static constexpr int kSlots = 52;
   void* ws[kSlots] = {nullptr};
   int64_t ws_bytes[kSlots] = {0};
   // pinned host scratch for small scalar read-backs
@@ -195,6 +195,9 @@ enum Slot {
   SLOT_PP_SMALL = 46,      // bigkrls_predict_pointwise: standardised X, c, one block of newdata, yhat, diag
   SLOT_PP_K = 47,          // ... one row block of the test kernel (at most 1 GiB)
   SLOT_QF_PART = 48,       // quadform_diag: one partial per row, column tile and k split
+  SLOT_KB_SHIFT = 49,      // kernel_block / kernel_contract: the common shift of both operands (P doubles: column means of A)
+  SLOT_KB_A = 50,          // ... the shifted copy of A (u x P)
+  SLOT_KB_B = 51,          // ... the shifted copy of B (v x P) where B is not a row block of A
 };
 
 int ws_get(bigkrls_ctx* ctx, int slot, int64_t nbytes, void** out);
@@ -315,7 +318,9 @@ int multdiag(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t k, int64_t ld
              const double* diag, double* out, int64_t ldo);
 int diag_extract(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t lda, double* out);
 int scale(bigkrls_ctx* ctx, int64_t n, double alpha, double* x);
-int row_sqnorms(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t p, int64_t lda, double* out);
+int col_means(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t p, int64_t lda, double* out);
+int shift_rows_sqnorms(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t p, int64_t lda, const double* shift,
+                       double* out, double* norms);
 int copy_matrix(bigkrls_ctx* ctx, const double* A, int64_t m, int64_t n, int64_t lda, double* B,
                 int64_t ldb);
 

@@ -1719,6 +1719,43 @@ static int kb_nontemporal(int64_t rows, int64_t p) {
   return rows * p * (int64_t)sizeof(double) > (2ll << 20);    // 2 MB
 }
 
+// Operands of a kernel build moved by one common vector, with their squared row norms. exp(-|a - b|^2 / sigma) depends
+// on differences only, but |a|^2 + |b|^2 - 2 a.b cancels on data that are not centred (rows near 1e5: errors of 1e-5 in K),
+// so both operands are copied with the column means of A subtracted (col_means, shift_rows_sqnorms in vecops.hip:
+// O((u + v) p), no host synchronisation). A row block of A -- the same buffer for the symmetric build, B = A + c0 for
+// the column block of a rank -- is served from the copy of A, so it sees bitwise the same rows and norms.
+struct CentredOperands {
+  const double *A, *B, *na, *nb;
+  int64_t lda, ldb;
+};
+static int centre_operands(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
+                           int64_t ldb, int64_t p, CentredOperands* o) {
+  void *pna = nullptr, *pnb = nullptr, *psh = nullptr, *pa = nullptr, *pb = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_NORMS_A, u * sizeof(double), &pna));
+  BK_TRY(ws_get(ctx, SLOT_KB_SHIFT, p * sizeof(double), &psh));
+  BK_TRY(ws_get(ctx, SLOT_KB_A, u * p * (int64_t)sizeof(double), &pa));
+  BK_TRY(col_means(ctx, A, u, p, lda, (double*)psh));
+  BK_TRY(shift_rows_sqnorms(ctx, A, u, p, lda, (const double*)psh, (double*)pa, (double*)pna));
+  o->A = (const double*)pa;
+  o->na = (const double*)pna;
+  o->lda = u;
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(A), b0 = reinterpret_cast<uintptr_t>(B);
+  if (lda == ldb && b0 >= a0 && (b0 - a0) / sizeof(double) + (uint64_t)v <= (uint64_t)u) {
+    const int64_t r0 = (int64_t)((b0 - a0) / sizeof(double));
+    o->B = o->A + r0;
+    o->nb = o->na + r0;
+    o->ldb = u;
+    return BIGKRLS_OK;
+  }
+  BK_TRY(ws_get(ctx, SLOT_NORMS_B, v * sizeof(double), &pnb));
+  BK_TRY(ws_get(ctx, SLOT_KB_B, v * p * (int64_t)sizeof(double), &pb));
+  BK_TRY(shift_rows_sqnorms(ctx, B, v, p, ldb, (const double*)psh, (double*)pb, (double*)pnb));
+  o->B = (const double*)pb;
+  o->nb = (const double*)pnb;
+  o->ldb = v;
+  return BIGKRLS_OK;
+}
+
 int kernel_block(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B,
                  int64_t v, int64_t ldb, int64_t p, double sigma, double* out, int64_t ldo,
                  int64_t diag_shift) {
@@ -1727,11 +1764,13 @@ int kernel_block(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, cons
   BK_REQUIRE(sigma > 0.0, "kernel_block: sigma must be > 0");
   if (u == 0 || v == 0) return BIGKRLS_OK;
   BK_REQUIRE(A && B && out, "kernel_block: null pointer");
-  void *pna = nullptr, *pnb = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_NORMS_A, u * sizeof(double), &pna));
-  BK_TRY(ws_get(ctx, SLOT_NORMS_B, v * sizeof(double), &pnb));
-  BK_TRY(row_sqnorms(ctx, A, u, p, lda, (double*)pna));
-  BK_TRY(row_sqnorms(ctx, B, v, p, ldb, (double*)pnb));
+  BK_REQUIRE(lda >= u && ldb >= v, "kernel_block: leading dimension of A or B too small");
+  const bool sym = A == B && u == v && lda == ldb && diag_shift == 0;
+  // from here on A and B are the centred copies (the same buffer when they were the same buffer)
+  CentredOperands co;
+  BK_TRY(centre_operands(ctx, A, u, lda, B, v, ldb, p, &co));
+  A = co.A; lda = co.lda; B = co.B; ldb = co.ldb;
+  const double *pna = co.na, *pnb = co.nb;
   // one workgroup per 128 x 128 tile with the X panels in LDS where it beats the one-wave-per-32x32 kernels: P > 32
   // (measured, TFLOP/s tiled vs wave: N = 100 000, P = 50: 44.7 vs 38.5; N = 30 000, P = 50: 37.2 vs 33.9;
   //  N = 50 000, P = 20: 21.1 vs 20.7; N = 20 000, P = 20: 17.8 vs 19.9; BIGKRLS_KB=wave|tiled forces either)
@@ -1739,7 +1778,6 @@ int kernel_block(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, cons
     const char* e = getenv("BIGKRLS_KB");
     return e ? (std::string(e) == "tiled" ? 1 : (std::string(e) == "wave" ? -1 : 0)) : 0;
   }();
-  const bool sym = A == B && u == v && lda == ldb && diag_shift == 0;
   const bool big = u >= 1024 && v >= 1024;
   if (kb_force > 0 || (kb_force == 0 && big && p > 32)) {
     const int tiles_m = (int)((u + 127) / 128), tiles_n = (int)((v + 127) / 128);
@@ -2006,18 +2044,17 @@ int kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, c
   BK_REQUIRE(A && B && W && out, "kernel_contract: null pointer");
   BK_REQUIRE(lda >= u && ldb >= v, "kernel_contract: leading dimension of A or B too small");
   // trans = 0: stationary rows A, loop rows B; trans = 1: the reverse
-  const double* S = trans ? B : A;
-  const double* L = trans ? A : B;
   const int64_t ns = trans ? v : u, nl = trans ? u : v;
-  const int64_t lds = trans ? ldb : lda, ldl = trans ? lda : ldb;
   BK_REQUIRE(ldw >= nl && ldo >= ns, "kernel_contract: leading dimension of W or out too small");
-  void *pna = nullptr, *pnb = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_NORMS_A, u * sizeof(double), &pna));
-  BK_TRY(ws_get(ctx, SLOT_NORMS_B, v * sizeof(double), &pnb));
-  BK_TRY(row_sqnorms(ctx, A, u, p, lda, (double*)pna));
-  BK_TRY(row_sqnorms(ctx, B, v, p, ldb, (double*)pnb));
+  CentredOperands co;     // both operands moved by the column means of A (see centre_operands)
+  BK_TRY(centre_operands(ctx, A, u, lda, B, v, ldb, p, &co));
+  A = co.A; lda = co.lda; B = co.B; ldb = co.ldb;
+  const double *pna = co.na, *pnb = co.nb;
   const double* nrm_s = (const double*)(trans ? pnb : pna);
   const double* nrm_l = (const double*)(trans ? pna : pnb);
+  const double* S = trans ? B : A;
+  const double* L = trans ? A : B;
+  const int64_t lds = trans ? ldb : lda, ldl = trans ? lda : ldb;
 
   const int CT = q <= 16 ? 1 : (q <= 32 ? 2 : 4);
   const int steps = (int)((p + 3) / 4);

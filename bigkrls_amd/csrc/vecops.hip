@@ -202,24 +202,49 @@ int scale(bigkrls_ctx* ctx, int64_t n, double alpha, double* x) {
   return BIGKRLS_OK;
 }
 
-// ---- squared row norms of a column-major n x p matrix -------------------------
-__global__ void row_sqnorms_kernel(int n, int p, const double* __restrict__ A, int64_t lda,
-                                   double* __restrict__ out) {
+// ---- centring of the kernel builds' operands (kernel_block, kernel_contract in gemm.hip) --------------------------
+// The Gaussian kernel depends on differences of rows only, and the builds expand |a - b|^2 = |a|^2 + |b|^2 - 2 a.b: on
+// data far from the origin the three terms are huge and cancel. Both operands are therefore moved by one common vector,
+// the column means of A, before the norms and the products are taken.
+// out[c] = mean of column c: one workgroup per column, every thread sums a fixed set of rows and the partial sums are
+// combined in a fixed order (deterministic). Any vector near the data serves, so the rounding of the mean is harmless.
+__global__ __launch_bounds__(1024) void col_means_kernel(int n, const double* __restrict__ A, int64_t lda,
+                                                         double* __restrict__ out) {
+  __shared__ double sh[16];
+  const double* a = A + (int64_t)blockIdx.x * lda;
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 1024) s += a[i];
+  s = block_sum(s, sh);
+  if (threadIdx.x == 0) out[blockIdx.x] = s / (double)n;
+}
+
+int col_means(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t p, int64_t lda, double* out) {
+  if (n <= 0 || p <= 0) return BIGKRLS_OK;
+  hipLaunchKernelGGL(col_means_kernel, dim3((unsigned)p), dim3(1024), 0, ctx->stream, (int)n, A, lda, out);
+  BK_CHECK_LAUNCH();
+  return BIGKRLS_OK;
+}
+
+// out (n x p, leading dimension n) = A - 1 shift', norms[i] = |out[i, :]|^2 (one thread per row, the columns in order)
+__global__ void shift_rows_sqnorms_kernel(int n, int p, const double* __restrict__ A, int64_t lda,
+                                          const double* __restrict__ shift, double* __restrict__ out,
+                                          double* __restrict__ norms) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   double s = 0.0;
   for (int c = 0; c < p; ++c) {
-    const double v = A[i + (int64_t)c * lda];
+    const double v = A[i + (int64_t)c * lda] - shift[c];
+    out[i + (int64_t)c * n] = v;
     s += v * v;
   }
-  out[i] = s;
+  norms[i] = s;
 }
 
-int row_sqnorms(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t p, int64_t lda,
-                double* out) {
+int shift_rows_sqnorms(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t p, int64_t lda, const double* shift,
+                       double* out, double* norms) {
   if (n <= 0) return BIGKRLS_OK;
-  hipLaunchKernelGGL(row_sqnorms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                     ctx->stream, (int)n, (int)p, A, lda, out);
+  hipLaunchKernelGGL(shift_rows_sqnorms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (int)n,
+                     (int)p, A, lda, shift, out, norms);
   BK_CHECK_LAUNCH();
   return BIGKRLS_OK;
 }

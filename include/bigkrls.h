@@ -132,11 +132,13 @@ int bigkrls_event_elapsed_ms(void* ev_start, void* ev_stop, double* ms);
  * ========================================================================== */
 
 /* replaces BigGaussKernel(pA, pOut, sigma)            src/gauss_kernel.cpp:32-42
- * out[i,j] = exp(-sum_p (X[i,p]-X[j,p])^2 / sigma), n x n, diag == 1. */
+ * out[i,j] = exp(-sum_p (X[i,p]-X[j,p])^2 / sigma), n x n, diag == 1.
+ * X need not be centred: the column means are subtracted on the device before the norms and products are taken. */
 int bigkrls_gauss_kernel(const double* X, int64_t n, int64_t p, double sigma, double* out);
 
 /* replaces BigTempKernel(pA, pB, pOut, sigma)         src/temp_kernel.cpp:32-44
- * out[i,j] = exp(-||A_i - B_j||^2 / sigma), A is u x p, B is v x p, out u x v. */
+ * out[i,j] = exp(-||A_i - B_j||^2 / sigma), A is u x p, B is v x p, out u x v.
+ * A and B need not be centred: the column means of A are subtracted from both on the device. */
 int bigkrls_temp_kernel(const double* A, int64_t u, const double* B, int64_t v, int64_t p,
                         double sigma, double* out);
 
@@ -191,7 +193,10 @@ int bigkrls_neffective(const double* X, int64_t n, int64_t p, double* neff);
 /* General kernel block: out[i,j] = exp(-||A_i - B_j||^2/sigma), out is u x v with
  * leading dimension ldo. If diag_shift >= 0, entries with i == j + diag_shift are
  * set to exactly 1 (column block [c0,c1) of the symmetric n x n kernel:
- * A = X, B = X + c0, diag_shift = c0). Pass diag_shift = -1 for predict. */
+ * A = X, B = X + c0, diag_shift = c0). Pass diag_shift = -1 for predict.
+ * A and B need not be centred: both are copied with the column means of A subtracted (extra device memory
+ * O((u + v) p), no host synchronisation) before |a|^2 + |b|^2 - 2 a.b is formed; lda >= u and ldb >= v. A block B
+ * that lies inside A (same leading dimension) reads the copy of A, so every column block of one X sees the same rows. */
 int bigkrls_dev_kernel_block(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda,
                              const double* B, int64_t v, int64_t ldb, int64_t p, double sigma,
                              double* out, int64_t ldo, int64_t diag_shift);
@@ -199,7 +204,8 @@ int bigkrls_dev_kernel_block(bigkrls_ctx* ctx, const double* A, int64_t u, int64
 /* Fused kernel contraction: trans = 0: out (u x q, ldo) = K(A,B) W with W v x q (ldw);
  * trans = 1: out (v x q, ldo) = K(A,B)' W with W u x q (ldw). K(A,B) is exactly bigkrls_dev_kernel_block's
  * kernel with diag_shift = -1; it is rebuilt tile by tile in registers and never written to memory (extra
- * device memory O((u + v) q), never O(u v)). Deterministic: two calls give bitwise identical results. */
+ * device memory O((u + v) (p + q)), never O(u v)). Deterministic: two calls give bitwise identical results.
+ * A and B need not be centred (the column means of A are subtracted from both, as in bigkrls_dev_kernel_block). */
 int bigkrls_dev_kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda,
                                 const double* B, int64_t v, int64_t ldb, int64_t p, double sigma,
                                 const double* W, int64_t q, int64_t ldw, int trans, double* out, int64_t ldo);
