@@ -92,11 +92,12 @@ struct bigkrls_ctx {
   int64_t n_redone = 0, n_replayed = 0, n_replica_diff = 0;
   // set by the eigensolver beside an error code when what failed can only be a fault of the run on a finite symmetric
   // input (a block recurrence that does not hold against K, non-finite entries after the tridiagonalisation); read and
-  // cleared by the fit, which validated its input and redoes such a decomposition once (csrc/fit.hip)
+  // cleared by the fit, which validated its input and redoes such a decomposition once (Fit::soften, csrc/fit.hip)
   bool corrupt_run = false;
-  // set by the fit around a decomposition it is going to verify against K itself (ALL kept pairs, csrc/fit.hip): the
-  // block Lanczos then leaves out its own sample check of the last block of Ritz pairs against K (one more K-times-
-  // block product: 13 ms at N = 50 000, 50 ms at N = 100 000); not set for the redo after a failed check
+  // set by the fit around a decomposition it is going to verify against K itself (ALL kept pairs, csrc/fit.hip,
+  // Fit::verify_decomposition): the block Lanczos then leaves out its own sample check of the last block of Ritz pairs
+  // against K (one more K-times-block product: 13 ms at N = 50 000, 50 ms at N = 100 000); not set for the redo after a
+  // failed check
   bool caller_verifies = false;
   // device-side predicate of the next gemm() launches (kernel and split-K reduction return at once while *gemm_run_if
   // == 0): the T-factor chain of a stage-1 panel only runs when pq_chol left the panel to the Householder kernel
@@ -351,7 +352,7 @@ int deriv_var(bigkrls_ctx* ctx, const double* Q, int64_t n, int64_t k, int64_t l
 enum EigMode { EIG_FULL = 0, EIG_SETUP_ONLY = 1, EIG_RESUME = 2 };
 // Internal status (never crosses the C ABI): the watchdog of a persistent kernel fired in a decomposition whose
 // stage 1 was driven from outside (EIG_RESUME). The distributed fit agrees on it over the ranks and replays the
-// decomposition with the launch-per-step kernels on every rank (csrc/fit.hip); larger than every public code so
+// decomposition with the launch-per-step kernels on every rank (Fit::eigen_dist_dense, csrc/fit.hip); larger than every public code so
 // that the agreement (a MAX) prefers it to a rank-local OK.
 constexpr int BK_EWATCHDOG = 90;
 int eigen(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t lda, int64_t n_vals, double* vals,

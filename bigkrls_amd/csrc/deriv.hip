@@ -120,7 +120,7 @@ int deriv_rows(bigkrls_ctx* ctx, const double* Krows, int64_t n, int64_t n_rows,
                const double* extra, int64_t n_extra, double* extra_out) {
   // `extra` (n x n_extra, ld n): more operand columns for the same pass over K; K extra -> extra_out (n_rows x n_extra).
   // The fit sends the two +-1 combinations of its kept eigenvectors along: the check of the decomposition against K
-  // costs no pass over K of its own (csrc/fit.hip).
+  // costs no pass over K of its own (Fit::verify_deferred, csrc/fit.hip).
   BK_REQUIRE(n > 0 && n_rows > 0 && p > 0 && n < (1ll << 31) && p < (1 << 20),
              "deriv_rows: bad dimensions");
   BK_REQUIRE(row0 >= 0 && row0 + n_rows <= n, "deriv_rows: row block out of range");

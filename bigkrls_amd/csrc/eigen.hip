@@ -3074,7 +3074,7 @@ int eigen(bigkrls_ctx* ctx, const double* A, int64_t n64, int64_t lda, int64_t n
 #endif
       if (h_err1 != 0 && mode == EIG_RESUME) {
         set_error("eigen: watchdog of the register-resident panel QR fired during the distributed stage 1");
-        return BK_EWATCHDOG;     // the caller replays the decomposition on every rank (csrc/fit.hip)
+        return BK_EWATCHDOG;     // the caller replays the decomposition on every rank (Fit::eigen_dist_dense, csrc/fit.hip)
       }
       if (h_err1 != 0) return eigen_retry_without_resident(ctx, A, n64, lda, n_vals, vals, n_vecs_max, keep_thresh,
                                                            vecs, ldv, h_n_vecs, part_index, part_count);
@@ -3253,7 +3253,7 @@ int eigen(bigkrls_ctx* ctx, const double* A, int64_t n64, int64_t lda, int64_t n
 #ifdef BK_FAULT_INJECT
   // BIGKRLS_FAULT=eig_garbage (test build): the FIRST decomposition after the variable is set comes back with its
   // middle kept eigenvector scaled by 1.001 -- a wrong result without any error, the kind the fit's verification
-  // (csrc/fit.hip) exists for; =eig_garbage_always: every decomposition does
+  // (Fit::verify_decomposition, csrc/fit.hip) exists for; =eig_garbage_always: every decomposition does
   {
     static int garbage_calls = 0;
     const char* fault = getenv("BIGKRLS_FAULT");
@@ -3265,7 +3265,7 @@ int eigen(bigkrls_ctx* ctx, const double* A, int64_t n64, int64_t lda, int64_t n
       BK_TRY(scale(ctx, N, 1.001, vecs + (int64_t)gc * ldv));
     // BIGKRLS_FAULT=eig_swap / eig_swap_always: two kept eigenvectors exchanged -- every column still has norm 1, the
     // combinations Q r keep |Q r|^2 = k: only the comparison with K Q r (on one GPU deferred to the fit's pass over K
-    // for the marginal effects, csrc/fit.hip) can see it
+    // for the marginal effects, Fit::verify_deferred in csrc/fit.hip) can see it
     {
       static int swap_calls = 0;
       const bool sonce = fault && std::string(fault) == "eig_swap", salways = fault && std::string(fault) == "eig_swap_always";
@@ -3277,7 +3277,7 @@ int eigen(bigkrls_ctx* ctx, const double* A, int64_t n64, int64_t lda, int64_t n
     }
     // BIGKRLS_FAULT=vals_ulp (set in ONE rank's process): this rank's copy of the replicated eigenvalues differs from its
     // peers' in the last bit of one kept value -- a valid decomposition the fit's check against K lets through; the
-    // multi-GPU fit must still run its lambda search on identical values everywhere (csrc/fit.hip: rank 0's are broadcast)
+    // multi-GPU fit must still run its lambda search on identical values everywhere (Fit::fetch_and_agree_eigenvalues: rank 0's)
     if (fault && std::string(fault) == "vals_ulp" && nv > 1 && keep_thresh >= 0.0) {   // (not the inner solves of the Lanczos)
       fault_nudge_ulp<<<1, 1, 0, st>>>(vals + nv / 2);
       BK_HIP(hipGetLastError());

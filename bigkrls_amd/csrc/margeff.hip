@@ -18,43 +18,12 @@
 // group-sum algebra of deriv_finalize_kernel (csrc/deriv.hip): Kn1 and Kn0 differ from Kn only by the factors
 // E = exp(-(z1 - z0)^2 / sigma) and 1/E on the rows / columns of the other group. The variances are T = V S (gemm)
 // and column dots. Device memory: O((u + n)(p + q)) plus the loop splits' partials, never O(u n).
-#include "common.h"
+#include "hostprep.h"
 
-#include <algorithm>
-#include <cmath>
 #include <cstring>
 
 namespace bk {
 namespace {
-
-// mean and R's sd() (n - 1 denominator) of a column, as the fit computes them (csrc/fit.hip)
-void me_mean_sd(const double* x, int64_t n, double* mean, double* sd) {
-  long double s = 0.0L;
-  for (int64_t i = 0; i < n; ++i) s += x[i];
-  const long double m = s / (long double)n;
-  long double q = 0.0L;
-  for (int64_t i = 0; i < n; ++i) {
-    const long double dlt = (long double)x[i] - m;
-    q += dlt * dlt;
-  }
-  *mean = (double)m;
-  *sd = n > 1 ? (double)std::sqrt((double)(q / (long double)(n - 1))) : 0.0;
-}
-
-// exactly two distinct values (the fit's rule, R/bigKRLS.R:242)
-bool me_two_valued(const double* x, int64_t n, double* lo_out, double* hi_out) {
-  double lo = x[0], hi = x[0];
-  for (int64_t i = 1; i < n; ++i) {
-    lo = std::min(lo, x[i]);
-    hi = std::max(hi, x[i]);
-  }
-  *lo_out = lo;
-  *hi_out = hi;
-  if (lo == hi) return false;
-  for (int64_t i = 0; i < n; ++i)
-    if (x[i] != lo && x[i] != hi) return false;
-  return true;
-}
 
 // Per-column constants of the selected columns (device, 4 per column): is_binary, z0, z1 and the column index.
 struct MeCol {
@@ -141,11 +110,7 @@ int bigkrls_marginal_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int
                              const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
                              const double* h_newdata, int64_t u, const double* d_vcov_c, double* h_derivatives,
                              double* h_avg, double* h_var) {
-  if (!ctx) {
-    set_error("null context");
-    return BIGKRLS_EINVAL;
-  }
-  BK_HIP(hipSetDevice(ctx->device));
+  BK_TRY(check_ctx(ctx));
   BK_REQUIRE(h_X && h_y && h_coeffs && h_newdata && h_avg, "marginal_effects: null argument");
   BK_REQUIRE(n > 1 && p > 0 && u > 0 && n < (1ll << 31) && u < (1ll << 31), "marginal_effects: bad dimensions");
   BK_REQUIRE(sigma > 0.0 && std::isfinite(sigma), "marginal_effects: sigma must be a positive scalar");
@@ -167,9 +132,9 @@ int bigkrls_marginal_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int
   std::vector<double> x_mean(p), x_sd(p), lo(p), hi(p);
   std::vector<char> isbin(p);
   for (int64_t j = 0; j < p; ++j) {
-    me_mean_sd(h_X + j * n, n, &x_mean[j], &x_sd[j]);
+    mean_sd(h_X + j * n, n, &x_mean[j], &x_sd[j]);
     BK_REQUIRE(x_sd[j] > 0.0, "marginal_effects: training column " + std::to_string(j + 1) + " is constant");
-    isbin[j] = me_two_valued(h_X + j * n, n, &lo[j], &hi[j]);
+    isbin[j] = two_valued(h_X + j * n, n, &lo[j], &hi[j]);
   }
   for (int64_t i = 0; i < nj; ++i) {
     const int64_t j = cols[i];
@@ -181,7 +146,7 @@ int bigkrls_marginal_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int
                      " is binary in the training data; its values must be one of the two training values");
   }
   double y_mean, y_sd;
-  me_mean_sd(h_y, n, &y_mean, &y_sd);
+  mean_sd(h_y, n, &y_mean, &y_sd);
   BK_REQUIRE(y_sd > 0.0, "marginal_effects: y is a constant");
 
   // ---- device layout -------------------------------------------------------------------------------
@@ -215,9 +180,8 @@ int bigkrls_marginal_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int
     double* hBs = hB + n * q;
     MeCol* hcols = (MeCol*)(hBs + u * q);
     for (int64_t j = 0; j < p; ++j) {
-      const double m = x_mean[j], s = x_sd[j];
-      for (int64_t i = 0; i < n; ++i) hXs[j * n + i] = (h_X[j * n + i] - m) / s;
-      for (int64_t i = 0; i < u; ++i) hZs[j * u + i] = (h_newdata[j * u + i] - m) / s;
+      standardise_column(h_X + j * n, n, x_mean[j], x_sd[j], hXs + j * n);
+      standardise_column(h_newdata + j * u, u, x_mean[j], x_sd[j], hZs + j * u);
     }
     for (int64_t i = 0; i < n; ++i) hB[i] = h_coeffs[i];
     for (int64_t i = 0; i < u; ++i) hBs[i] = 1.0;
