@@ -50,7 +50,8 @@ class FitOutputs(C.Structure):
                 ("lastkeeper", i64), ("neig", i64), ("n_deriv", i64), ("n_probes", i64),
                 ("sigma", f64), ("lambda_", f64), ("Le", f64), ("Looe", f64), ("sigmasq", f64),
                 ("R2", f64), ("R2AME", f64), ("Neffective", f64), ("Neffective_acf", f64),
-                ("y_mean", f64), ("y_sd", f64), ("phase_s", f64 * 8)]
+                ("y_mean", f64), ("y_sd", f64), ("phase_s", f64 * 8),
+                ("d_vcov_q", vp), ("vcov_q_cols_max", i64), ("vcov_w", vp), ("vcov_q_cols", i64)]
 
 
 PHASES = ("h2d", "kernel", "eigen", "lambda", "coeffs", "vcov_c", "vcov_fitted", "derivatives")
@@ -95,6 +96,7 @@ SIGNATURES = {
     "bigkrls_dev_kernel_block": [vp, vp, i64, i64, vp, i64, i64, i64, f64, vp, i64, i64],
     "bigkrls_dev_kernel_contract": [vp, vp, i64, i64, vp, i64, i64, i64, f64, vp, i64, i64, C.c_int, vp, i64],
     "bigkrls_dev_quadform_diag": [vp, i64, i64, vp, i64, vp, i64, vp],
+    "bigkrls_dev_rowsumsq_weighted": [vp, i64, i64, vp, i64, vp, vp],
     "bigkrls_dev_gemm": [vp, C.c_int, C.c_int, i64, i64, i64, f64, vp, i64, vp, i64, f64, vp, i64],
     "bigkrls_dev_multdiag": [vp, vp, i64, i64, i64, vp, vp, i64],
     "bigkrls_dev_eigen": [vp, vp, i64, i64, i64, vp, i64, f64, vp, i64, pi64],
@@ -120,7 +122,10 @@ SIGNATURES = {
     "bigkrls_fit": [vp, vp, vp, i64, i64, C.POINTER(FitOptions), C.POINTER(FitOutputs)],
     "bigkrls_predict": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, f64, vp, vp, vp, vp],
     "bigkrls_predict_pointwise": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, f64, vp, vp],
+    "bigkrls_predict_factored": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, i64, vp, f64, vp, vp, vp, vp],
     "bigkrls_marginal_effects": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, vp, vp, vp, vp],
+    "bigkrls_marginal_effects_factored": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, vp, i64, i64, vp, vp, vp,
+                                          vp],
     # multi-GPU
     "bigkrls_comm_unique_id": [vp],
     "bigkrls_comm_create": [vp, i32, i32, vp, C.POINTER(vp)],

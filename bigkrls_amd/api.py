@@ -95,7 +95,8 @@ def bigKRLS(y=None, X=None, sigma=None, derivative=True, which_derivatives=None,
             model_subfolder_name=None, overwrite_existing=False, Ncores=None,
             acf=False, noisy=None, instructions=True, ctx: Optional[Context] = None,
             timings: Optional[Dict[str, float]] = None,
-            trace: Optional[list] = None, comm=None, keep_outputs: bool = True) -> BigKRLS:
+            trace: Optional[list] = None, comm=None, keep_outputs: bool = True,
+            vcov_form: str = "dense", max_factors: Optional[int] = None) -> BigKRLS:
     """Kernel-regularised least squares fit (R/bigKRLS.R:97-516).
 
     The numeric body -- validation of the data, standardisation, the five steps and the rescaling
@@ -114,6 +115,15 @@ def bigKRLS(y=None, X=None, sigma=None, derivative=True, which_derivatives=None,
     with the same y, X and arguments -- through `bigkrls_fit_dist`; the N x N outputs are then this rank's
     column blocks `K.cols`, `vcov.est.c.cols`, `vcov.est.fitted.cols` (n x (r1 - r0), rows `w["rows"]`),
     or not kept at all with keep_outputs=False.
+    `vcov_form`: how the variance of the coefficients is returned. "dense" (default): the N x N matrices
+    `vcov.est.c` and `vcov.est.fitted`. "factors": `vcov.est.Q` (a DeviceMatrix, N x lastkeeper: the kept
+    eigenvectors) and `vcov.est.w` (lastkeeper weights) with vcov.est.c = Q diag(w) Q' and vcov.est.fitted =
+    Q diag(w d^2) Q' (d = K.eigenvalues[:lastkeeper]); both matrices are None and K is the only N x N buffer of the
+    call. "both": all of them from one fit. predict() and marginal_effects() work from either form. With a
+    communicator every rank holds the whole Q and w, so a multi-GPU object with factors can be used downstream on any
+    single rank. The buffer for Q has `Neig` columns when Neig was given or nothing is truncated (eigtrunc 0),
+    otherwise `max_factors` (default min(N, 2048)); a fit that keeps more eigenpairs than that raises a ValueError --
+    factors are never truncated -- and the columns not needed are released after the call.
     """
     ctx = (comm.ctx if comm is not None else ctx) or default_context()
     if X is None or y is None:
@@ -154,6 +164,21 @@ def bigKRLS(y=None, X=None, sigma=None, derivative=True, which_derivatives=None,
     if Neig is not None and int(Neig) < 1:
         raise ValueError("Neig must be a positive integer")
     neig = min(n, int(Neig)) if Neig is not None else n                           # :194
+    if vcov_form not in ("dense", "factors", "both"):
+        raise ValueError('vcov_form must be "dense", "factors" or "both"')
+    if max_factors is not None and not (isinstance(max_factors, (int, np.integer)) and not isinstance(max_factors, bool)
+                                        and max_factors >= 1):
+        raise ValueError("max_factors must be a positive integer")
+    want_dense, want_factors = vcov_form != "factors", vcov_form != "dense"
+    if want_factors and not vcov_est:
+        raise ValueError('vcov_form = "factors" / "both" requires vcov_est = True')
+    qcap = 0
+    if want_factors:
+        eigtrunc_eff = (0.001 if n > 3000 else 0.0) if eigtrunc is None else float(eigtrunc)      # :195-201
+        if Neig is not None or eigtrunc_eff == 0.0:
+            qcap = neig
+        else:
+            qcap = min(neig, int(max_factors) if max_factors is not None else min(n, 2048))
     pd = 0 if not derivative else (p if which_derivatives is None else len(which_derivatives))
 
     opt = _lib.FitOptions()
@@ -198,20 +223,34 @@ def bigKRLS(y=None, X=None, sigma=None, derivative=True, which_derivatives=None,
         _call_native("bigkrls_fit_dist_rows", comm.handle, n, C.byref(opt), C.byref(a0), C.byref(a1))
         r0, r1 = int(a0.value), int(a1.value)
     ncols = r1 - r0                                                               # columns of K this process holds
-    K = vcovmatc = vcovmatyhat = None
+    K = vcovmatc = vcovmatyhat = Qf = wf = None
     if keep_outputs or comm is None:
         K = ctx.empty(n, max(ncols, 1))                                           # :434
         out.d_K = K.ptr
-        if vcov_est:
+        if vcov_est and want_dense:
             vcovmatc, vcovmatyhat = ctx.empty(n, max(ncols, 1)), ctx.empty(n, max(ncols, 1))
             out.d_vcov_c, out.d_vcov_fitted = vcovmatc.ptr, vcovmatyhat.ptr
+    if want_factors:                                                              # whole on every rank
+        Qf, wf = ctx.empty(n, qcap), np.zeros(qcap)
+        out.d_vcov_q, out.vcov_q_cols_max, out.vcov_w = Qf.ptr, qcap, wf.ctypes.data
 
     t_wall0 = time.perf_counter()
-    if comm is None:
-        _call_native("bigkrls_fit", ctx.handle, Xh.ctypes.data, yh.ctypes.data, n, p, C.byref(opt), C.byref(out))
-    else:
-        _call_native("bigkrls_fit_dist", comm.handle, Xh.ctypes.data, yh.ctypes.data, n, p, C.byref(opt), C.byref(out))
+    try:
+        if comm is None:
+            _call_native("bigkrls_fit", ctx.handle, Xh.ctypes.data, yh.ctypes.data, n, p, C.byref(opt), C.byref(out))
+        else:
+            _call_native("bigkrls_fit_dist", comm.handle, Xh.ctypes.data, yh.ctypes.data, n, p, C.byref(opt),
+                         C.byref(out))
+    except ValueError as e:
+        if want_factors and int(out.lastkeeper) > qcap:      # the library's capacity error (include/bigkrls.h)
+            raise ValueError(f"{e}: pass max_factors >= {int(out.lastkeeper)} (or vcov_form='dense')") from None
+        raise
     t_native = time.perf_counter() - t_wall0
+    if want_factors:
+        kq = int(out.vcov_q_cols)
+        if kq < qcap:                                         # keep the lastkeeper columns, release the rest
+            Qf = Qf.keep_first_cols(kq)
+            wf = wf[:kq].copy()
 
     if trace is not None:
         for i in range(min(int(out.n_probes), max_trace)):
@@ -243,16 +282,19 @@ def bigKRLS(y=None, X=None, sigma=None, derivative=True, which_derivatives=None,
         if keep_outputs:
             cut = (lambda m: m if ncols > 0 else None)
             w["K.cols"] = cut(K)
-            w["vcov.est.c.cols"] = cut(vcovmatc) if vcov_est else None
-            w["vcov.est.fitted.cols"] = cut(vcovmatyhat) if vcov_est else None
+            w["vcov.est.c.cols"] = cut(vcovmatc) if vcovmatc is not None else None
+            w["vcov.est.fitted.cols"] = cut(vcovmatyhat) if vcovmatyhat is not None else None
     else:
         w["K"] = K if return_big_squares else K.to_numpy()                        # :434
-        if vcov_est:
+        if vcovmatc is not None:
             w["vcov.est.c"] = vcovmatc if return_big_squares else vcovmatc.to_numpy()          # :438
             w["vcov.est.fitted"] = vcovmatyhat if return_big_squares else vcovmatyhat.to_numpy()   # :445
         else:
             w["vcov.est.c"] = None
             w["vcov.est.fitted"] = None
+    if want_factors:                                          # flat keys: save_bigKRLS / load_bigKRLS carry them as they are
+        w["vcov.est.Q"] = Qf
+        w["vcov.est.w"] = wf
     w["derivative.call"] = derivative
     if derivative:
         w["avgderivatives"] = avg[None, :]                                        # :400
@@ -392,17 +434,50 @@ def summary(object: BigKRLS, degrees: str = "Neffective", probs=(0.05, 0.25, 0.5
             "colnames": ["Estimate", "Std. Error", "t value", "Pr(>|t|)"], "n": n}
 
 
+def _vcov_choice(object, vcov):
+    """The form of vcov.est.c a post-fit call works from: "dense" (the N x N matrix), "factors" (vcov.est.Q and
+    vcov.est.w) or None (the object has neither). vcov=None prefers the dense matrix; "dense" / "factors" force a
+    form and raise when the object does not carry it."""
+    if vcov not in (None, "dense", "factors"):
+        raise ValueError('vcov must be None, "dense" or "factors"')
+    has_dense = object.get("vcov.est.c") is not None
+    has_factors = object.get("vcov.est.Q") is not None and object.get("vcov.est.w") is not None
+    if vcov == "dense" and not has_dense:
+        raise ValueError('the object has no vcov.est.c: refit with vcov_form="dense" or "both"')
+    if vcov == "factors" and not has_factors:
+        raise ValueError('the object has no vcov.est.Q / vcov.est.w: refit with vcov_form="factors" or "both"')
+    if vcov is None:
+        return "dense" if has_dense else ("factors" if has_factors else None)
+    return vcov
+
+
+def _factors(object, ctx):
+    """(Q on the device, w contiguous on the host) of an object that carries the factors of vcov.est.c."""
+    Q = object["vcov.est.Q"]
+    Qd = Q if is_device_matrix(Q) else ctx.from_numpy(np.asarray(Q, dtype=np.float64))
+    wv = np.ascontiguousarray(np.asarray(object["vcov.est.w"], dtype=np.float64).ravel())
+    if wv.size != Qd.ncol or Qd.nrow != np.asarray(object["X"]).shape[0]:
+        raise ValueError("vcov.est.Q must be nrow(X) x length(vcov.est.w)")
+    return Qd, wv
+
+
 def predict(object: BigKRLS, newdata, se_pred=False, correct_SE=True, ytest=None,
-            ctx: Optional[Context] = None, matrices=True) -> BigKRLSPredicted:
+            ctx: Optional[Context] = None, matrices=True, vcov: Optional[str] = None) -> BigKRLSPredicted:
     """predict.bigKRLS (R/bigKRLS.R:547-637); the numeric body (:590-621) is ONE call into the
     C ABI, `bigkrls_predict` (include/bigkrls.h, csrc/fit.hip).
 
     matrices=False: the same `predicted` and `se.pred` through `bigkrls_predict_pointwise`, which takes the new
     points in row blocks and never forms newdataK (u x n) or vcov.est.pred (u x u); both come back as None. Its
-    extra device memory stays near 1.1 GiB whatever the number of new points."""
+    extra device memory stays near 1.1 GiB whatever the number of new points.
+
+    vcov: the form of vcov.est.c the standard errors come from. None: the N x N matrix when the object has it, else
+    its factors (a fit with vcov_form="factors", on one GPU or several); "dense" / "factors" force one and raise a
+    ValueError when the object does not carry it. From the factors the numeric body is `bigkrls_predict_factored`:
+    se^2_i = sum_j w_j (newdataK Q)_ij^2, about n / lastkeeper times fewer flops than the product with the matrix."""
     if not isinstance(object, BigKRLS):
         raise TypeError("Object not of class 'bigKRLS'")
-    if se_pred and object.get("vcov.est.c") is None:
+    form = _vcov_choice(object, vcov)
+    if se_pred and form is None:
         raise ValueError("recompute bigKRLS object with bigKRLS(,vcov.est=TRUE) to compute standard errors")
     ctx = ctx or object.get("_ctx") or default_context()
     Xh = np.asfortranarray(np.asarray(object["X"], dtype=np.float64))
@@ -416,6 +491,9 @@ def predict(object: BigKRLS, newdata, se_pred=False, correct_SE=True, ytest=None
     yv = np.ascontiguousarray(np.asarray(object["y"], dtype=np.float64).ravel())
     coeffs = np.ascontiguousarray(np.asarray(object["coeffs"], dtype=np.float64).ravel())
     ypred = np.empty(u)
+    if se_pred and form == "factors":
+        return _predict_factored(object, ctx, Xh, nd, nd_init, yv, coeffs, ypred, correct_SE, ytest, bigmatrix_in,
+                                 matrices)
     if not matrices:
         return _predict_pointwise(object, ctx, Xh, nd, nd_init, yv, coeffs, ypred, se_pred, correct_SE, ytest,
                                   bigmatrix_in)
@@ -465,7 +543,33 @@ def _predict_pointwise(object, ctx, Xh, nd, nd_init, yv, coeffs, ypred, se_pred,
     return out
 
 
-def marginal_effects(object: BigKRLS, newdata, which_derivatives=None, ctx: Optional[Context] = None) -> dict:
+def _predict_factored(object, ctx, Xh, nd, nd_init, yv, coeffs, ypred, correct_SE, ytest, bigmatrix_in, matrices):
+    """predict(..., se_pred=True) from the factors of vcov.est.c after predict()'s own checks: one call into
+    bigkrls_predict_factored, with the two matrices as outputs (matrices=True) or in row blocks without them."""
+    n, p = Xh.shape
+    u = nd.shape[0]
+    Qd, wv = _factors(object, ctx)
+    newdataK = ctx.empty(u, n) if matrices else None
+    vcov_est_pred = ctx.empty(u, u) if matrices else None
+    se = np.empty(u)
+    neff = -1.0
+    if correct_SE and object.get("Neffective") is not None:                       # :610-611
+        neff = float(object["Neffective"])
+    _call_native("bigkrls_predict_factored", ctx.handle, Xh.ctypes.data, n, p, yv.ctypes.data, coeffs.ctypes.data,
+                 float(object["sigma"]), nd.ctypes.data, u, Qd.ptr, Qd.ld, Qd.ncol, wv.ctypes.data, neff,
+                 ypred.ctypes.data, se.ctypes.data, newdataK.ptr if matrices else None,
+                 vcov_est_pred.ptr if matrices else None)
+    if matrices and not bigmatrix_in:                                             # :623-626
+        vcov_est_pred, newdataK = vcov_est_pred.to_numpy(), newdataK.to_numpy()
+    out = BigKRLSPredicted(predicted=ypred, newdata=nd_init, newdataK=newdataK, ytest=ytest)
+    out["se.pred"] = se
+    out["vcov.est.pred"] = vcov_est_pred
+    out["has.big.matrices"] = bigmatrix_in
+    return out
+
+
+def marginal_effects(object: BigKRLS, newdata, which_derivatives=None, ctx: Optional[Context] = None,
+                     vcov: Optional[str] = None) -> dict:
     """Marginal effects of a fitted model at new data points, without refitting: the pointwise derivatives
     (u x |J|), their averages (1 x |J|) and the variances of the averages (1 x |J|; None when the object has no
     vcov.est.c), in the original units and with the fit's definitions -- with newdata = X they are the fit's
@@ -473,12 +577,15 @@ def marginal_effects(object: BigKRLS, newdata, which_derivatives=None, ctx: Opti
     between their two training values, so newdata must hold one of those two values there. `which_derivatives`
     (1-based) defaults to the object's own, or all columns. No counterpart in the reference (which computes the
     marginal effects at the training rows only, R/bigKRLS.R:318-407). The numeric body is ONE call into the C ABI,
-    `bigkrls_marginal_effects`, which never forms the u x n test kernel."""
+    `bigkrls_marginal_effects`, which never forms the u x n test kernel. `vcov` chooses the form of vcov.est.c the
+    variances come from, as in predict(): from the factors (`bigkrls_marginal_effects_factored`) the variance step is
+    the fit's own sum_k w_k (q_k's)^2, and a multi-GPU object that carries them is accepted."""
     if not isinstance(object, BigKRLS):
         raise TypeError("Object not of class 'bigKRLS'")
-    if "vcov.est.c.cols" in object or "rows" in object:
+    form = _vcov_choice(object, vcov)
+    if ("vcov.est.c.cols" in object or "rows" in object) and form != "factors":
         raise NotImplementedError("marginal_effects of a multi-GPU fit (sharded vcov.est.c.cols) is not supported; "
-                                  "refit on one GPU")
+                                  "refit on one GPU or with vcov_form=\"factors\"")
     Xh = np.asfortranarray(np.asarray(object["X"], dtype=np.float64))
     n, p = Xh.shape
     nd_init = _as_host_matrix(newdata)
@@ -506,19 +613,25 @@ def marginal_effects(object: BigKRLS, newdata, which_derivatives=None, ctx: Opti
                 raise ValueError(f"newdata column {j + 1} is binary in the training data; its values must be "
                                  f"one of the two training values ({lo:g}, {hi:g})")
     ctx = ctx or object.get("_ctx") or default_context()
-    V = object.get("vcov.est.c")
+    V = object.get("vcov.est.c") if form == "dense" else None
     Vd = None if V is None else (V if is_device_matrix(V) else ctx.from_numpy(np.asarray(V, dtype=np.float64)))
+    Qd, wv = _factors(object, ctx) if form == "factors" else (None, None)
     yv = np.ascontiguousarray(np.asarray(object["y"], dtype=np.float64).ravel())
     coeffs = np.ascontiguousarray(np.asarray(object["coeffs"], dtype=np.float64).ravel())
     which_arr = np.ascontiguousarray(which, dtype=np.int64)
     nj = which_arr.size
     D = np.empty((u, nj), dtype=np.float64, order="F")
     avg = np.empty(nj)
-    var = np.empty(nj) if Vd is not None else None
-    _call_native("bigkrls_marginal_effects", ctx.handle, Xh.ctypes.data, n, p, yv.ctypes.data, coeffs.ctypes.data,
-                 float(object["sigma"]), which_arr.ctypes.data, nj, nd.ctypes.data, u,
-                 Vd.ptr if Vd is not None else None, D.ctypes.data, avg.ctypes.data,
-                 var.ctypes.data if var is not None else None)
+    var = np.empty(nj) if form is not None else None
+    if form == "factors":
+        _call_native("bigkrls_marginal_effects_factored", ctx.handle, Xh.ctypes.data, n, p, yv.ctypes.data,
+                     coeffs.ctypes.data, float(object["sigma"]), which_arr.ctypes.data, nj, nd.ctypes.data, u,
+                     Qd.ptr, Qd.ld, Qd.ncol, wv.ctypes.data, D.ctypes.data, avg.ctypes.data, var.ctypes.data)
+    else:
+        _call_native("bigkrls_marginal_effects", ctx.handle, Xh.ctypes.data, n, p, yv.ctypes.data, coeffs.ctypes.data,
+                     float(object["sigma"]), which_arr.ctypes.data, nj, nd.ctypes.data, u,
+                     Vd.ptr if Vd is not None else None, D.ctypes.data, avg.ctypes.data,
+                     var.ctypes.data if var is not None else None)
     xlabs = list(object.get("xlabs") or [f"x{i + 1}" for i in range(p)])
     return {"derivatives": D, "avgderivatives": avg[None, :],
             "var.avgderivatives": None if var is None else var[None, :],

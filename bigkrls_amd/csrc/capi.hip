@@ -532,6 +532,12 @@ int bigkrls_dev_quadform_diag(bigkrls_ctx* ctx, int64_t m, int64_t n, const doub
   return quadform_diag(ctx, m, n, A, lda, V, ldv, out);
 }
 
+int bigkrls_dev_rowsumsq_weighted(bigkrls_ctx* ctx, int64_t m, int64_t k, const double* T, int64_t ldt,
+                                  const double* w, double* out) {
+  BK_TRY(check_ctx(ctx));
+  return rowsumsq_weighted(ctx, m, k, T, ldt, w, out);
+}
+
 int bigkrls_dev_gemm(bigkrls_ctx* ctx, int ta, int tb, int64_t m, int64_t n, int64_t k,
                      double alpha, const double* A, int64_t lda, const double* B, int64_t ldb,
                      double beta, double* C, int64_t ldc) {

@@ -180,7 +180,7 @@ enum Slot {
   SLOT_EIG_TBIG = 30,      // ... and their T factors
   SLOT_FIT_SMALL = 31,     // bigkrls_fit / bigkrls_predict: X, y, eigenvalues, c, yhat, D, S, ...
   SLOT_FIT_Q = 32,         // ... eigenvectors (n x Neig)
-  SLOT_FIT_M = 33,         // ... Q diag(w) / K_new V
+  SLOT_FIT_M = 33,         // ... Q diag(w) / K_new V / K_new Q and K_new Q diag(w)
   SLOT_FIT_K = 34,         // ... the kernel when the caller does not want it back
   SLOT_EIG_AGG = 35,       // stage 1: reflector blocks of the panel groups whose trailing update is pending
   SLOT_COMM_STAGE = 36,    // multi-GPU: send / receive staging of the row-block all-gathers
@@ -194,7 +194,7 @@ enum Slot {
   SLOT_CONTRACT_PART = 44, // kernel_contract: partial sums of the loop splits
   SLOT_ME_SMALL = 45,      // bigkrls_marginal_effects: standardised X and newdata, operands, products, D, S, V S
   SLOT_PP_SMALL = 46,      // bigkrls_predict_pointwise: standardised X, c, one block of newdata, yhat, diag
-  SLOT_PP_K = 47,          // ... one row block of the test kernel (at most 1 GiB)
+  SLOT_PP_K = 47,          // ... one row block of the test kernel, and its product with Q where the variance comes as factors (at most 1 GiB)
   SLOT_QF_PART = 48,       // quadform_diag: one partial per row, column tile and k split
   SLOT_KB_SHIFT = 49,      // kernel_block / kernel_contract: the common shift of both operands (P doubles: column means of A)
   SLOT_KB_A = 50,          // ... the shifted copy of A (u x P)
@@ -317,6 +317,9 @@ int gemv(bigkrls_ctx* ctx, int trans, int64_t m, int64_t n, double alpha, const 
 int dot_host(bigkrls_ctx* ctx, int64_t n, const double* x, const double* y, double* h_out);
 int multdiag(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t k, int64_t lda,
              const double* diag, double* out, int64_t ldo);
+// out[i] = sum_j w[j] T[i,j]^2, T m x k (ldt), w and out on the device; fixed summation order
+int rowsumsq_weighted(bigkrls_ctx* ctx, int64_t m, int64_t k, const double* T, int64_t ldt, const double* w,
+                      double* out);
 int diag_extract(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t lda, double* out);
 int scale(bigkrls_ctx* ctx, int64_t n, double alpha, double* x);
 int col_means(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t p, int64_t lda, double* out);
@@ -336,6 +339,22 @@ int lambda_search(bigkrls_ctx* ctx, const double* Q, int64_t n_rows, int64_t k, 
                   const double* d, const double* a, const double* h_vals_all, int64_t n_vals,
                   double L, double U, double tol, double* h_lambda, int64_t* h_nprobes,
                   double* h_trace, int64_t max_trace, bigkrls_comm* comm = nullptr, int64_t n_total = 0);
+
+// vcov.est.c as the entries behind predict() and marginal_effects() receive it (fit.hip, margeff.hip): the n x n matrix
+// (d_V, ld n), or its factors Q diag(w) Q' (d_Q n x k with leading dimension ldq, h_w the k weights on the host), or
+// neither. The dense and the factored entry of a pair differ in the variance step only.
+struct Vcov {
+  const double* d_V = nullptr;
+  const double* d_Q = nullptr;
+  int64_t ldq = 0, k = 0;
+  const double* h_w = nullptr;
+  static Vcov matrix(const double* d_vcov_c) { Vcov v; v.d_V = d_vcov_c; return v; }
+  static Vcov factors(const double* d_Q, int64_t ldq, int64_t k, const double* h_w) {
+    Vcov v; v.d_Q = d_Q; v.ldq = ldq; v.k = k; v.h_w = h_w; return v;
+  }
+  bool given() const { return d_V != nullptr || d_Q != nullptr; }
+  int64_t cols() const { return d_Q ? k : 0; }
+};
 
 // ---- deriv.hip ----------------------------------------------------------------
 int deriv_rows(bigkrls_ctx* ctx, const double* Krows, int64_t n, int64_t n_rows, int64_t ldk,

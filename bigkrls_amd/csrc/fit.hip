@@ -250,6 +250,11 @@ struct Fit {
     sigma = opt->sigma > 0.0 ? opt->sigma : (double)p;                                                   // :230
     if (derivative && !vcov_est)                                                                          // :239
       return fail("vcov.est is needed to get derivatives (derivative==TRUE requires vcov.est=TRUE).");
+    if (out->d_vcov_q) {                       // vcov.est.c handed out as its factors Q diag(w) Q'
+      if (!vcov_est) return fail("the factors of vcov.est.c require vcov.est = TRUE");
+      BK_REQUIRE(out->vcov_w && out->vcov_q_cols_max > 0, "fit: d_vcov_q needs vcov_w and vcov_q_cols_max > 0");
+      out->vcov_q_cols = 0;
+    }
     if (out->binaryindicator) {                                                                           // :242 (raw X)
       for_columns(p, n, [&](int64_t j) {
         double lo, hi;
@@ -645,6 +650,14 @@ struct Fit {
   int accept_decomposition() {
     BK_REQUIRE(lastkeeper > 0, "fit: no eigenpair passes the eigtrunc threshold");
     k = lastkeeper;
+    // the caller's room for the factors, checked before anything is computed with them: never silently truncated (the
+    // count is agreed between the ranks of a multi-GPU fit, so every rank returns this)
+    if (out->d_vcov_q && lastkeeper > out->vcov_q_cols_max) {
+      out->lastkeeper = lastkeeper;
+      return fail("fit: the decomposition keeps " + std::to_string((long long)lastkeeper) +
+                  " eigenpairs, the buffers for the factors of vcov.est.c hold " +
+                  std::to_string((long long)out->vcov_q_cols_max) + " columns");
+    }
     if (trace_on()) {
       BK_TRY(trace_host("R:fit_vals", vals.data(), neig, k));
       BK_TRY(trace_point(ctx, st, "R:fit_Q", dQ, n * k, dist_mode));
@@ -790,9 +803,28 @@ struct Fit {
     }
     // (one local stretch between the collectives of the coefficients and those of the derivative pass: its status is
     //  agreed at the end, so that a rank that fails here does not leave its peers waiting in the next all-gather)
-    if (vcov_est && (out->d_vcov_c || out->d_vcov_fitted)) return agreed(variance_matrices_local());
+    const bool matrices = vcov_est && (out->d_vcov_c || out->d_vcov_fitted);
+    if (matrices || out->d_vcov_q) return agreed(variance_outputs_local(matrices));
     timer.mark();
     timer.mark();
+    return BIGKRLS_OK;
+  }
+
+  int variance_outputs_local(bool matrices) {
+    if (out->d_vcov_q) BK_TRY(hand_out_factors());
+    if (matrices) return variance_matrices_local();
+    timer.mark();
+    timer.mark();
+    return BIGKRLS_OK;
+  }
+
+  // vcov.est.c = Q diag(w) Q' as its factors: the kept columns of dQ (replicated on every rank of a multi-GPU fit, so
+  // no exchange) and w_j = sd(y)^2 wv_j, the weights the fit itself uses times the rescaling of :438
+  int hand_out_factors() {
+    BK_TRY(copy_matrix(ctx, dQ, n, k, n, out->d_vcov_q, n));
+    const double sd2 = y_sd * y_sd;
+    for (int64_t i = 0; i < k; ++i) out->vcov_w[i] = sd2 * wv[i];
+    out->vcov_q_cols = k;
     return BIGKRLS_OK;
   }
 
@@ -969,7 +1001,7 @@ int fit_impl(bigkrls_ctx* ctx, bigkrls_comm* comm, const double* h_X, const doub
   return f.finish();
 }
 
-// ---- predict.bigKRLS() (R/bigKRLS.R:590-621): what the whole-matrix and the pointwise entry share ------------------
+// ---- predict.bigKRLS() (R/bigKRLS.R:590-621): what the whole-matrix and the pointwise entries share ----------------
 struct TrainMoments {
   std::vector<double> x_mean, x_sd;
   double y_mean = 0.0, y_sd = 0.0;
@@ -978,14 +1010,15 @@ struct TrainMoments {
 // the argument checks and the TRAINING means and sds both are standardised with (:590-597)
 int predict_prepare(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y, const double* h_coeffs,
                     double sigma, const double* h_newdata, int64_t u, const double* h_predicted, bool want_se,
-                    const double* d_vcov_c, TrainMoments* tm) {
+                    const Vcov& vc, TrainMoments* tm) {
   BK_TRY(check_ctx(ctx));
   BK_REQUIRE(h_X && h_y && h_coeffs && h_newdata && h_predicted, "predict: null argument");
   BK_REQUIRE(n > 1 && p > 0 && u > 0 && sigma > 0.0, "predict: bad dimensions or sigma");
-  if (want_se && !d_vcov_c) {
+  if (want_se && !vc.given()) {
     set_error("recompute bigKRLS object with bigKRLS(,vcov.est=TRUE) to compute standard errors");     // R/bigKRLS.R:553
     return BIGKRLS_EINVAL;
   }
+  if (vc.d_Q) BK_REQUIRE(vc.h_w && vc.k > 0 && vc.k <= n && vc.ldq >= n, "predict: bad factors of vcov.est.c");
   tm->x_mean.resize(p);
   tm->x_sd.resize(p);
   for (int64_t j = 0; j < p; ++j) {
@@ -1008,6 +1041,136 @@ int predict_finish(bigkrls_ctx* ctx, const double* dpred, int64_t u, bool want_s
   if (h_se_pred)
     for (int64_t i = 0; i < u; ++i) h_se_pred[i] = std::sqrt(pinned[u + i]);
   return BIGKRLS_OK;
+}
+
+// bigkrls_predict / bigkrls_predict_factored with a device output: the u x n test kernel as a whole
+int predict_whole(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y, const double* h_coeffs,
+                  double sigma, const double* h_newdata, int64_t u, const Vcov& vc, double neff, double* h_predicted,
+                  double* h_se_pred, double* d_newdataK, double* d_vcov_pred) {
+  const bool want_se = h_se_pred != nullptr || d_vcov_pred != nullptr;
+  TrainMoments tm;
+  BK_TRY(predict_prepare(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_newdata, u, h_predicted, want_se, vc, &tm));
+  hipStream_t st = ctx->stream;
+  const int64_t k = want_se ? vc.cols() : 0;
+  const int64_t small_doubles = n * p + u * p + n + k + 2 * u + 64;
+  void* psmall = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_FIT_SMALL, small_doubles * (int64_t)sizeof(double), &psmall));
+  double* q = (double*)psmall;
+  double* dX = q; q += n * p;
+  double* dN = q; q += u * p;
+  double* dc = q; q += n;
+  double* dw = q; q += k;
+  double* dpred = q; q += u;
+  double* ddiag = q; q += u;
+  double* dKn = d_newdataK;
+  if (!dKn) {
+    void* pk = nullptr;
+    BK_TRY(ws_get(ctx, SLOT_FIT_K, u * n * (int64_t)sizeof(double), &pk));
+    dKn = (double*)pk;
+  }
+  double* pin = nullptr;
+  BK_TRY(pinned_get(ctx, n * p + u * p + n + k + u, &pin));
+  for (int64_t j = 0; j < p; ++j) {
+    standardise_column(h_X + j * n, n, tm.x_mean[j], tm.x_sd[j], pin + j * n);
+    standardise_column(h_newdata + j * u, u, tm.x_mean[j], tm.x_sd[j], pin + n * p + j * u);
+  }
+  std::memcpy(pin + n * p + u * p, h_coeffs, (size_t)n * sizeof(double));
+  if (k > 0) std::memcpy(pin + n * p + u * p + n, vc.h_w, (size_t)k * sizeof(double));
+  BK_HIP(hipMemcpyAsync(dX, pin, (size_t)(n * p + u * p + n + k) * sizeof(double), hipMemcpyHostToDevice, st));
+  BK_TRY(kernel_block(ctx, dN, u, u, dX, n, n, p, sigma, dKn, u, -1));                                 // bTempKernel (:599)
+  BK_TRY(gemv(ctx, 0, u, n, 1.0, dKn, u, dc, 0.0, dpred));                                            // newdataK %*% coeffs (:601)
+  const double q10 = neff > 0.0 ? std::sqrt((double)n / neff) : 1.0;                                   // :610-611 (quirk Q10)
+  if (want_se && vc.d_V) {
+    const double vy = tm.y_sd * tm.y_sd;
+    void* pm = nullptr;
+    BK_TRY(ws_get(ctx, SLOT_FIT_M, (u * n + (d_vcov_pred ? 0 : u * u)) * (int64_t)sizeof(double), &pm));
+    double* dT = (double*)pm;
+    double* dVp = d_vcov_pred ? d_vcov_pred : dT + u * n;
+    // var(y) * tcrossprod(newdataK %*% (vcov.est.c * (1/var(y))), newdataK)   (:608)
+    BK_TRY(gemm(ctx, 0, 0, u, n, n, 1.0 / vy, dKn, u, vc.d_V, n, 0.0, dT, u));
+    BK_TRY(gemm(ctx, 0, 1, u, u, n, vy, dT, u, dKn, u, 0.0, dVp, u));
+    if (neff > 0.0) BK_TRY(scale(ctx, u * u, q10, dVp));
+    BK_TRY(diag_extract(ctx, dVp, u, u, ddiag));
+  } else if (want_se) {
+    // the same matrix from the factors: T = newdataK Q, vcov.est.pred = (T diag(w)) T', its diagonal sum_j w_j T_ij^2
+    void* pm = nullptr;
+    BK_TRY(ws_get(ctx, SLOT_FIT_M, (d_vcov_pred ? 2 : 1) * u * k * (int64_t)sizeof(double), &pm));
+    double* dT = (double*)pm;
+    BK_TRY(gemm(ctx, 0, 0, u, k, n, 1.0, dKn, u, vc.d_Q, vc.ldq, 0.0, dT, u));
+    BK_TRY(rowsumsq_weighted(ctx, u, k, dT, u, dw, ddiag));
+    if (neff > 0.0) BK_TRY(scale(ctx, u, q10, ddiag));
+    if (d_vcov_pred) {
+      double* dM = dT + u * k;
+      BK_TRY(multdiag(ctx, dT, u, k, u, dw, dM, u));
+      BK_TRY(gemm(ctx, 0, 1, u, u, k, q10, dM, u, dT, u, 0.0, d_vcov_pred, u));
+    }
+  }
+  return predict_finish(ctx, dpred, u, want_se, pin, tm, h_predicted, h_se_pred);
+}
+
+// rows per block of the pointwise entries (include/bigkrls.h): the largest multiple of 128 whose b x (n + k) doubles
+// -- the test-kernel block, and beside it its product with the k factor columns -- fit 1 GiB, at least 128
+int64_t pointwise_block_rows(int64_t n, int64_t k) {
+  return std::max<int64_t>(128, ((1ll << 30) / ((n + k) * (int64_t)sizeof(double))) / 128 * 128);
+}
+
+// bigkrls_predict_pointwise / bigkrls_predict_factored without device outputs: bigkrls_predict's validation and
+// standardisation; then row blocks of b new points: kernel_block, gemv, and for the SEs the one entry of vcov.est.pred
+// per point that se.pred needs -- diag(Kn_b vcov.est.c Kn_b') (quadform_diag), or from the factors T = Kn_b Q (gemm)
+// and sum_j w_j T_ij^2 (rowsumsq_weighted).
+int predict_blocks(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y, const double* h_coeffs,
+                   double sigma, const double* h_newdata, int64_t u, const Vcov& vc, double neff, double* h_predicted,
+                   double* h_se_pred) {
+  const bool want_se = h_se_pred != nullptr;
+  TrainMoments tm;
+  BK_TRY(predict_prepare(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_newdata, u, h_predicted, want_se, vc, &tm));
+  const int64_t k = want_se ? vc.cols() : 0;
+  const int64_t b = std::min(pointwise_block_rows(n, k), u);
+  hipStream_t st = ctx->stream;
+  const int64_t small_doubles = n * p + n + k + b * p + 2 * u + 64;
+  void* psmall = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_PP_SMALL, small_doubles * (int64_t)sizeof(double), &psmall));
+  double* q = (double*)psmall;
+  double* dX = q; q += n * p;
+  double* dc = q; q += n;
+  double* dw = q; q += k;
+  double* dZ = q; q += b * p;
+  double* dpred = q; q += u;
+  double* ddiag = q; q += u;
+  void* pk = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_PP_K, b * (n + k) * (int64_t)sizeof(double), &pk));
+  double* dKn = (double*)pk;
+  double* dT = dKn + b * n;
+  // pinned host: [Xs | c | w | Zs, block by block, each block's rows x p contiguous] uploaded, [yhat | diag] read back
+  double* pin = nullptr;
+  BK_HIP(hipStreamSynchronize(st));   // (the pinned buffer may be reallocated)
+  BK_TRY(pinned_get(ctx, n * p + n + k + u * p + 2 * u, &pin));
+  double* pz = pin + n * p + n + k;
+  double* pout = pz + u * p;
+  for (int64_t j = 0; j < p; ++j) {
+    standardise_column(h_X + j * n, n, tm.x_mean[j], tm.x_sd[j], pin + j * n);
+    for (int64_t r0 = 0; r0 < u; r0 += b) {
+      const int64_t rows = std::min(b, u - r0);
+      standardise_column(h_newdata + j * u + r0, rows, tm.x_mean[j], tm.x_sd[j], pz + r0 * p + j * rows);
+    }
+  }
+  std::memcpy(pin + n * p, h_coeffs, (size_t)n * sizeof(double));
+  if (k > 0) std::memcpy(pin + n * p + n, vc.h_w, (size_t)k * sizeof(double));
+  BK_HIP(hipMemcpyAsync(dX, pin, (size_t)(n * p + n + k) * sizeof(double), hipMemcpyHostToDevice, st));
+  for (int64_t r0 = 0; r0 < u; r0 += b) {
+    const int64_t rows = std::min(b, u - r0);
+    BK_HIP(hipMemcpyAsync(dZ, pz + r0 * p, (size_t)(rows * p) * sizeof(double), hipMemcpyHostToDevice, st));
+    BK_TRY(kernel_block(ctx, dZ, rows, rows, dX, n, n, p, sigma, dKn, rows, -1));                       // bTempKernel (:599)
+    BK_TRY(gemv(ctx, 0, rows, n, 1.0, dKn, rows, dc, 0.0, dpred + r0));                                // :601
+    if (want_se && vc.d_V) {
+      BK_TRY(quadform_diag(ctx, rows, n, dKn, rows, vc.d_V, n, ddiag + r0));                            // diag of :608
+    } else if (want_se) {
+      BK_TRY(gemm(ctx, 0, 0, rows, k, n, 1.0, dKn, rows, vc.d_Q, vc.ldq, 0.0, dT, rows));               // T = Kn_b Q
+      BK_TRY(rowsumsq_weighted(ctx, rows, k, dT, rows, dw, ddiag + r0));
+    }
+  }
+  if (want_se && neff > 0.0) BK_TRY(scale(ctx, u, std::sqrt((double)n / neff), ddiag));                // :610-611 (Q10)
+  return predict_finish(ctx, dpred, u, want_se, pout, tm, h_predicted, h_se_pred);
 }
 
 }  // namespace
@@ -1040,99 +1203,27 @@ int bigkrls_predict(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, c
                     const double* h_coeffs, double sigma, const double* h_newdata, int64_t u,
                     const double* d_vcov_c, double neff, double* h_predicted, double* h_se_pred,
                     double* d_newdataK, double* d_vcov_pred) {
-  const bool want_se = h_se_pred != nullptr || d_vcov_pred != nullptr;
-  TrainMoments tm;
-  BK_TRY(predict_prepare(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_newdata, u, h_predicted, want_se, d_vcov_c, &tm));
-  hipStream_t st = ctx->stream;
-  const int64_t small_doubles = n * p + u * p + n + 2 * u + 64;
-  void* psmall = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_FIT_SMALL, small_doubles * (int64_t)sizeof(double), &psmall));
-  double* q = (double*)psmall;
-  double* dX = q; q += n * p;
-  double* dN = q; q += u * p;
-  double* dc = q; q += n;
-  double* dpred = q; q += u;
-  double* ddiag = q; q += u;
-  double* dKn = d_newdataK;
-  if (!dKn) {
-    void* pk = nullptr;
-    BK_TRY(ws_get(ctx, SLOT_FIT_K, u * n * (int64_t)sizeof(double), &pk));
-    dKn = (double*)pk;
-  }
-  double* pin = nullptr;
-  BK_TRY(pinned_get(ctx, n * p + u * p + n + u, &pin));
-  for (int64_t j = 0; j < p; ++j) {
-    standardise_column(h_X + j * n, n, tm.x_mean[j], tm.x_sd[j], pin + j * n);
-    standardise_column(h_newdata + j * u, u, tm.x_mean[j], tm.x_sd[j], pin + n * p + j * u);
-  }
-  std::memcpy(pin + n * p + u * p, h_coeffs, (size_t)n * sizeof(double));
-  BK_HIP(hipMemcpyAsync(dX, pin, (size_t)(n * p + u * p + n) * sizeof(double), hipMemcpyHostToDevice, st));
-  BK_TRY(kernel_block(ctx, dN, u, u, dX, n, n, p, sigma, dKn, u, -1));                                 // bTempKernel (:599)
-  BK_TRY(gemv(ctx, 0, u, n, 1.0, dKn, u, dc, 0.0, dpred));                                            // newdataK %*% coeffs (:601)
-  if (want_se) {
-    const double vy = tm.y_sd * tm.y_sd;
-    void* pm = nullptr;
-    BK_TRY(ws_get(ctx, SLOT_FIT_M, (u * n + (d_vcov_pred ? 0 : u * u)) * (int64_t)sizeof(double), &pm));
-    double* dT = (double*)pm;
-    double* dVp = d_vcov_pred ? d_vcov_pred : dT + u * n;
-    // var(y) * tcrossprod(newdataK %*% (vcov.est.c * (1/var(y))), newdataK)   (:608)
-    BK_TRY(gemm(ctx, 0, 0, u, n, n, 1.0 / vy, dKn, u, d_vcov_c, n, 0.0, dT, u));
-    BK_TRY(gemm(ctx, 0, 1, u, u, n, vy, dT, u, dKn, u, 0.0, dVp, u));
-    if (neff > 0.0) BK_TRY(scale(ctx, u * u, std::sqrt((double)n / neff), dVp));                       // :610-611 (quirk Q10)
-    BK_TRY(diag_extract(ctx, dVp, u, u, ddiag));
-  }
-  return predict_finish(ctx, dpred, u, want_se, pin, tm, h_predicted, h_se_pred);
+  const Vcov vc = Vcov::matrix(d_vcov_c);
+  return predict_whole(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_newdata, u, vc, neff, h_predicted, h_se_pred, d_newdataK,
+                       d_vcov_pred);
 }
 
 int bigkrls_predict_pointwise(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
                               const double* h_coeffs, double sigma, const double* h_newdata, int64_t u,
                               const double* d_vcov_c, double neff, double* h_predicted, double* h_se_pred) {
-  // bigkrls_predict's validation and standardisation; then row blocks of b new points: kernel_block, gemv, and for
-  // the SEs diag(Kn_b vcov.est.c Kn_b') (quadform_diag), the one entry of vcov.est.pred per point that se.pred needs.
-  const bool want_se = h_se_pred != nullptr;
-  TrainMoments tm;
-  BK_TRY(predict_prepare(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_newdata, u, h_predicted, want_se, d_vcov_c, &tm));
-  // rows per block (include/bigkrls.h): the largest multiple of 128 whose b x n test-kernel block fits 1 GiB, at least
-  // 128, and no more than u
-  const int64_t b_rule = std::max<int64_t>(128, ((1ll << 30) / (n * (int64_t)sizeof(double))) / 128 * 128);
-  const int64_t b = std::min(b_rule, u);
-  hipStream_t st = ctx->stream;
-  const int64_t small_doubles = n * p + n + b * p + 2 * u + 64;
-  void* psmall = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_PP_SMALL, small_doubles * (int64_t)sizeof(double), &psmall));
-  double* q = (double*)psmall;
-  double* dX = q; q += n * p;
-  double* dc = q; q += n;
-  double* dZ = q; q += b * p;
-  double* dpred = q; q += u;
-  double* ddiag = q; q += u;
-  void* pk = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_PP_K, b * n * (int64_t)sizeof(double), &pk));
-  double* dKn = (double*)pk;
-  // pinned host: [Xs | c | Zs, block by block, each block's rows x p contiguous] uploaded, [yhat | diag] read back
-  double* pin = nullptr;
-  BK_HIP(hipStreamSynchronize(st));   // (the pinned buffer may be reallocated)
-  BK_TRY(pinned_get(ctx, n * p + n + u * p + 2 * u, &pin));
-  double* pz = pin + n * p + n;
-  double* pout = pz + u * p;
-  for (int64_t j = 0; j < p; ++j) {
-    standardise_column(h_X + j * n, n, tm.x_mean[j], tm.x_sd[j], pin + j * n);
-    for (int64_t r0 = 0; r0 < u; r0 += b) {
-      const int64_t rows = std::min(b, u - r0);
-      standardise_column(h_newdata + j * u + r0, rows, tm.x_mean[j], tm.x_sd[j], pz + r0 * p + j * rows);
-    }
-  }
-  std::memcpy(pin + n * p, h_coeffs, (size_t)n * sizeof(double));
-  BK_HIP(hipMemcpyAsync(dX, pin, (size_t)(n * p + n) * sizeof(double), hipMemcpyHostToDevice, st));
-  for (int64_t r0 = 0; r0 < u; r0 += b) {
-    const int64_t rows = std::min(b, u - r0);
-    BK_HIP(hipMemcpyAsync(dZ, pz + r0 * p, (size_t)(rows * p) * sizeof(double), hipMemcpyHostToDevice, st));
-    BK_TRY(kernel_block(ctx, dZ, rows, rows, dX, n, n, p, sigma, dKn, rows, -1));                       // bTempKernel (:599)
-    BK_TRY(gemv(ctx, 0, rows, n, 1.0, dKn, rows, dc, 0.0, dpred + r0));                                // :601
-    if (want_se) BK_TRY(quadform_diag(ctx, rows, n, dKn, rows, d_vcov_c, n, ddiag + r0));               // diag of :608
-  }
-  if (want_se && neff > 0.0) BK_TRY(scale(ctx, u, std::sqrt((double)n / neff), ddiag));                // :610-611 (Q10)
-  return predict_finish(ctx, dpred, u, want_se, pout, tm, h_predicted, h_se_pred);
+  const Vcov vc = Vcov::matrix(d_vcov_c);
+  return predict_blocks(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_newdata, u, vc, neff, h_predicted, h_se_pred);
+}
+
+int bigkrls_predict_factored(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                             const double* h_coeffs, double sigma, const double* h_newdata, int64_t u,
+                             const double* d_Q, int64_t ldq, int64_t k, const double* h_w, double neff,
+                             double* h_predicted, double* h_se_pred, double* d_newdataK, double* d_vcov_pred) {
+  const Vcov vc = Vcov::factors(d_Q, ldq, k, h_w);
+  if (d_newdataK || d_vcov_pred)
+    return predict_whole(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_newdata, u, vc, neff, h_predicted, h_se_pred,
+                         d_newdataK, d_vcov_pred);
+  return predict_blocks(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_newdata, u, vc, neff, h_predicted, h_se_pred);
 }
 
 }  // extern "C"

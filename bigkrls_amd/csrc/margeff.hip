@@ -17,7 +17,9 @@
 // q = 1 + |J|. D is a per-row finalise of R and Zs, s / a a per-row finalise of C and Xs; the binary columns use the
 // group-sum algebra of deriv_finalize_kernel (csrc/deriv.hip): Kn1 and Kn0 differ from Kn only by the factors
 // E = exp(-(z1 - z0)^2 / sigma) and 1/E on the rows / columns of the other group. The variances are T = V S (gemm)
-// and column dots. Device memory: O((u + n)(p + q)) plus the loop splits' partials, never O(u n).
+// and column dots, or -- bigkrls_marginal_effects_factored, V = Q diag(w) Q' given by its factors -- sum_k w_k (q_k'S_j)^2
+// (deriv_var, what the fit itself does); the two entries differ in that step only.
+// Device memory: O((u + n)(p + q)) plus the loop splits' partials, never O(u n).
 #include "hostprep.h"
 
 #include <cstring>
@@ -99,23 +101,19 @@ __global__ __launch_bounds__(256) void me_coldot_kernel(int n, const double* __r
   if (threadIdx.x == 0) out[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
-}  // namespace
-}  // namespace bk
-
-using namespace bk;
-
-extern "C" {
-
-int bigkrls_marginal_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
-                             const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
-                             const double* h_newdata, int64_t u, const double* d_vcov_c, double* h_derivatives,
-                             double* h_avg, double* h_var) {
+// both entries: vcov.est.c as the n x n matrix, as its factors, or not at all (no variances) -- Vcov, common.h
+int marginal_effects_impl(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                          const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
+                          const double* h_newdata, int64_t u, const Vcov& vc, double* h_derivatives, double* h_avg,
+                          double* h_var) {
   BK_TRY(check_ctx(ctx));
   BK_REQUIRE(h_X && h_y && h_coeffs && h_newdata && h_avg, "marginal_effects: null argument");
   BK_REQUIRE(n > 1 && p > 0 && u > 0 && n < (1ll << 31) && u < (1ll << 31), "marginal_effects: bad dimensions");
   BK_REQUIRE(sigma > 0.0 && std::isfinite(sigma), "marginal_effects: sigma must be a positive scalar");
-  BK_REQUIRE((d_vcov_c == nullptr) == (h_var == nullptr),
-             "marginal_effects: h_var is written exactly when d_vcov_c is given");
+  BK_REQUIRE(vc.given() == (h_var != nullptr),
+             "marginal_effects: h_var is written exactly when vcov.est.c (or its factors) is given");
+  if (vc.d_Q) BK_REQUIRE(vc.h_w && vc.k > 0 && vc.k <= n && vc.ldq >= n, "marginal_effects: bad factors of vcov.est.c");
+  const int64_t k = vc.cols();
   std::vector<int64_t> cols;
   if (h_which) {
     BK_REQUIRE(n_which > 0, "marginal_effects: which_derivatives is empty");
@@ -152,7 +150,7 @@ int bigkrls_marginal_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int
   // ---- device layout -------------------------------------------------------------------------------
   hipStream_t st = ctx->stream;
   const int64_t colw = (int64_t)((sizeof(MeCol) + 7) / 8);
-  const int64_t up_doubles = n * p + u * p + n * q + u * q + nj * colw;      // uploaded, in this order
+  const int64_t up_doubles = n * p + u * p + n * q + u * q + nj * colw + k;  // uploaded, in this order
   const int64_t small_doubles = up_doubles + u * q + n * q + u * nj + 2 * n * nj + nj + 64;
   void* psmall = nullptr;
   BK_TRY(ws_get(ctx, SLOT_ME_SMALL, small_doubles * (int64_t)sizeof(double), &psmall));
@@ -162,6 +160,7 @@ int bigkrls_marginal_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int
   double* dB = qd; qd += n * q;
   double* dBs = qd; qd += u * q;
   MeCol* dcols = (MeCol*)qd; qd += nj * colw;
+  double* dw = qd; qd += k;
   double* dR = qd; qd += u * q;
   double* dC = qd; qd += n * q;
   double* dD = qd; qd += u * nj;
@@ -203,6 +202,7 @@ int bigkrls_marginal_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int
       hcols[jj].z1 = (hi[j] - x_mean[j]) / x_sd[j];
       hcols[jj].col = (double)j;
     }
+    if (k > 0) std::memcpy((double*)hcols + nj * colw, vc.h_w, (size_t)k * sizeof(double));
     BK_HIP(hipMemcpyAsync(dXs, pin, (size_t)up_doubles * sizeof(double), hipMemcpyHostToDevice, st));
   }
 
@@ -217,15 +217,24 @@ int bigkrls_marginal_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int
   hipLaunchKernelGGL(me_cols_kernel, dim3(blocks), dim3(256), 0, st, (int)n, (int)nj, (const double*)dC,
                      (const double*)dXs, (const MeCol*)dcols, sigma, dS);
   BK_CHECK_LAUNCH();
-  if (d_vcov_c) {
-    BK_TRY(gemm(ctx, 0, 0, n, nj, n, 1.0, d_vcov_c, n, dS, n, 0.0, dT, n));          // T = vcov.est.c S
+  if (vc.d_V) {
+    BK_TRY(gemm(ctx, 0, 0, n, nj, n, 1.0, vc.d_V, n, dS, n, 0.0, dT, n));          // T = vcov.est.c S
     hipLaunchKernelGGL(me_coldot_kernel, dim3((unsigned)nj), dim3(256), 0, st, (int)n, (const double*)dS,
                        (const double*)dT, dvar);
     BK_CHECK_LAUNCH();
   }
+  // s'(vcov.est.c)s per column. From the factors it is the fit's own step, which returns synchronised with its result
+  // on the host (deriv_var stages it through the context's pinned buffer, the one `pin` points into: the upload above
+  // has completed by then, and nothing of `pin` is read again before it is overwritten below).
+  std::vector<double> qf((size_t)nj, 0.0);
+  if (vc.d_Q) {
+    const std::vector<double> ones((size_t)nj, 1.0);
+    BK_TRY(deriv_var(ctx, vc.d_Q, n, k, vc.ldq, dw, dS, nj, n, ones.data(), qf.data()));
+  }
   BK_HIP(hipMemcpyAsync(pin, dD, (size_t)(u * nj) * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (d_vcov_c) BK_HIP(hipMemcpyAsync(pin + u * nj, dvar, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (vc.d_V) BK_HIP(hipMemcpyAsync(pin + u * nj, dvar, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost, st));
   BK_HIP(hipStreamSynchronize(st));
+  if (vc.d_V) std::memcpy(qf.data(), pin + u * nj, (size_t)nj * sizeof(double));
 
   // ---- original units (R/bigKRLS.R:393-407): D sd(y)/sd(x_j), its column means, var (sd(y)/sd(x_j))^2 -----
   for (int64_t jj = 0; jj < nj; ++jj) {
@@ -248,10 +257,33 @@ int bigkrls_marginal_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int
       } else {
         scale = 4.0 / (sigma * sigma * ud * ud);
       }
-      h_var[jj] = scale * pin[u * nj + jj] / (x_sd[j] * x_sd[j]);
+      h_var[jj] = scale * qf[jj] / (x_sd[j] * x_sd[j]);
     }
   }
   return BIGKRLS_OK;
+}
+
+}  // namespace
+}  // namespace bk
+
+using namespace bk;
+
+extern "C" {
+
+int bigkrls_marginal_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                             const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
+                             const double* h_newdata, int64_t u, const double* d_vcov_c, double* h_derivatives,
+                             double* h_avg, double* h_var) {
+  return marginal_effects_impl(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_which, n_which, h_newdata, u,
+                               Vcov::matrix(d_vcov_c), h_derivatives, h_avg, h_var);
+}
+
+int bigkrls_marginal_effects_factored(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                                      const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
+                                      const double* h_newdata, int64_t u, const double* d_Q, int64_t ldq, int64_t k,
+                                      const double* h_w, double* h_derivatives, double* h_avg, double* h_var) {
+  return marginal_effects_impl(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_which, n_which, h_newdata, u,
+                               Vcov::factors(d_Q, ldq, k, h_w), h_derivatives, h_avg, h_var);
 }
 
 }  // extern "C"

@@ -174,6 +174,38 @@ int multdiag(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t k, int64_t ld
   return BIGKRLS_OK;
 }
 
+// ---- out[i] = sum_j w[j] T[i,j]^2 : the diagonal of T diag(w) T' ---------------
+// One thread per row walking the columns in order: a wave's loads are 64 consecutive doubles of one column, and the
+// sum of a row has one fixed order (no atomics: two calls give the same bits). With w >= 0 no term cancels.
+// 64-thread workgroups: the operand is short and wide (a row block of new points times the kept eigenvectors), so
+// small workgroups spread its few thousand rows over more compute units.
+__global__ __launch_bounds__(64) void rowsumsq_weighted_kernel(int m, int k, const double* __restrict__ T, int64_t ldt,
+                                                               const double* __restrict__ w,
+                                                               double* __restrict__ out) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= m) return;
+  const double* t = T + i;
+  double s = 0.0;
+#pragma unroll 8
+  for (int j = 0; j < k; ++j) {
+    const double v = t[(int64_t)j * ldt];
+    s = fma(w[j] * v, v, s);
+  }
+  out[i] = s;
+}
+
+int rowsumsq_weighted(bigkrls_ctx* ctx, int64_t m, int64_t k, const double* T, int64_t ldt, const double* w,
+                      double* out) {
+  BK_REQUIRE(m >= 0 && k >= 0 && m < (1ll << 31) && k < (1ll << 31), "rowsumsq_weighted: bad dimensions");
+  if (m == 0) return BIGKRLS_OK;
+  BK_REQUIRE(out != nullptr, "rowsumsq_weighted: null output");
+  BK_REQUIRE(k == 0 || (T && w && ldt >= m), "rowsumsq_weighted: null operand or ldt < m");
+  hipLaunchKernelGGL(rowsumsq_weighted_kernel, dim3((unsigned)((m + 63) / 64)), dim3(64), 0, ctx->stream, (int)m,
+                     (int)k, T, ldt, w, out);
+  BK_CHECK_LAUNCH();
+  return BIGKRLS_OK;
+}
+
 __global__ void diag_kernel(int n, const double* __restrict__ A, int64_t lda,
                             double* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

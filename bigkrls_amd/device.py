@@ -269,6 +269,28 @@ class DeviceMatrix:
         """View of columns [c0, c1) (contiguous in column-major storage)."""
         return DeviceMatrix(self.ctx, self.t[c0:c1])
 
+    def keep_first_cols(self, k: int) -> "DeviceMatrix":
+        """The first k columns in storage of their own, and this matrix's storage released (the handle must not be
+        used afterwards). A view would keep the whole buffer alive, and a device-to-device copy needs both buffers at
+        once; the columns go through the context's pinned staging buffer instead, so the device never holds more
+        than the original. Beyond the staging buffer's largest size the copy is made on the device."""
+        ctx, k = self.ctx, int(k)
+        m = k * self.nrow
+        with ctx.on_stream():
+            if m > _STAGE_MAX:
+                kept = self.t[:k].clone()
+                self.t = None
+                return DeviceMatrix(ctx, kept)
+            stage, _ = ctx._staging(m)
+            stage[:m].copy_(self.t[:k].reshape(-1), non_blocking=True)
+            ctx.torch.cuda.current_stream().synchronize()
+            shape = (k, self.nrow)
+            self.t = None                                      # the block goes back to the allocator before the next one
+            kept = ctx.torch.empty(shape, dtype=ctx.torch.float64, device=ctx.device)
+            kept.view(-1).copy_(stage[:m], non_blocking=True)
+            ctx.torch.cuda.current_stream().synchronize()      # (the staging buffer is free again)
+        return DeviceMatrix(ctx, kept)
+
     def to_numpy(self) -> np.ndarray:
         # (ncol, nrow) C order is (nrow, ncol) column-major: return the Fortran-ordered view
         with self.ctx.on_stream():

@@ -228,13 +228,17 @@ atexit.register(release_comms)
 def bigKRLS_dist(y, X, sigma=None, derivative=True, which_derivatives=None, Neig=None, eigtrunc=None,
                  lambda_=None, L=None, U=None, ctx: Optional[Context] = None, comm: Optional[Comm] = None,
                  timings: Optional[Dict[str, float]] = None, trace=None, keep_outputs=True,
-                 eigen_mode: Optional[str] = None, collectives: Optional[str] = None) -> BigKRLS:
+                 eigen_mode: Optional[str] = None, collectives: Optional[str] = None, vcov_form: str = "dense",
+                 max_factors: Optional[int] = None) -> BigKRLS:
     """bigKRLS() over the ranks of the default process group (every rank calls with the same y, X): one call into
     `bigkrls_fit_dist`. Every rank returns the same small outputs; N x N outputs stay sharded (`K.cols`,
     `vcov.est.c.cols`, `vcov.est.fitted.cols` hold this rank's column block, `rows` its row range).
     `eigen_mode`: None (the library's choice: block Lanczos with sharded products when N >= 16384 and Neig <= N/8,
     otherwise the dense path with stage 1 partitioned by column blocks), "krylov" / "dense" to force either,
-    "replicated" for the decomposition replicated on every rank (what tiny problems, n <= 256, always use)."""
+    "replicated" for the decomposition replicated on every rank (what tiny problems, n <= 256, always use).
+    `vcov_form` / `max_factors` as in bigKRLS(): with "factors" or "both" every rank also returns the whole
+    `vcov.est.Q` (N x lastkeeper, replicated by the eigensolver already: no further exchange) and `vcov.est.w`, which
+    predict(se_pred=True) and marginal_effects() accept on any single rank; the sharded matrices cannot serve them."""
     from .api import default_context
     if comm is None:
         comm = get_comm(ctx or default_context(), collectives)
@@ -244,7 +248,7 @@ def bigKRLS_dist(y, X, sigma=None, derivative=True, which_derivatives=None, Neig
             os.environ["BIGKRLS_DIST_EIGEN"] = eigen_mode
         return bigKRLS(y, X, sigma=sigma, derivative=derivative, which_derivatives=which_derivatives, Neig=Neig,
                        eigtrunc=eigtrunc, lambda_=lambda_, L=L, U=U, timings=timings, trace=trace, comm=comm,
-                       keep_outputs=keep_outputs, noisy=False)
+                       keep_outputs=keep_outputs, noisy=False, vcov_form=vcov_form, max_factors=max_factors)
     finally:
         if eigen_mode is not None:
             if saved is None:

@@ -87,6 +87,19 @@ def bQuadformDiag(A: DeviceMatrix, V: DeviceMatrix) -> DeviceMatrix:
     return out
 
 
+def bRowSumSqWeighted(T: DeviceMatrix, w) -> DeviceMatrix:
+    """out[i] = sum_j w[j] T[i,j]^2 (m x 1) = diag(T diag(w) T') for T m x k and k weights (a DeviceMatrix or a host
+    array): with T = A Q it is bQuadformDiag(A, Q diag(w) Q') from the factors (bigkrls_dev_rowsumsq_weighted). No
+    counterpart in the reference."""
+    ctx = T.ctx
+    dw = w if isinstance(w, DeviceMatrix) else ctx.from_numpy(np.asarray(w, dtype=np.float64).ravel())
+    if dw.nrow * dw.ncol != T.ncol:
+        raise ValueError("bRowSumSqWeighted: w must have ncol(T) entries")
+    out = ctx.empty(T.nrow, 1)
+    _lib.call("bigkrls_dev_rowsumsq_weighted", ctx.handle, T.nrow, T.ncol, T.ptr, T.ld, dw.ptr, out.ptr)
+    return out
+
+
 # ---------------------------------------------------------------------------
 # eigen   (R/bigKRLS_Rcpp_functions.R:173-199)
 # ---------------------------------------------------------------------------

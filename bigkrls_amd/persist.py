@@ -68,6 +68,7 @@ def read_big_matrix_text(path: str) -> np.ndarray:
         return np.asarray(m).reshape(-1, ncol)     # a single column or a single row is still a matrix
 
 _BIGKRLS_MATRICES = ["K", "X", "derivatives", "vcov.est.c", "vcov.est.fitted"]             # bLoad :337
+_FACTOR_MATRICES = ["vcov.est.Q"]      # bigKRLS(vcov_form="factors" / "both"): loaded when present, no NOTE when absent
 _PREDICTED_MATRICES = ["predicted", "se.pred", "vcov.est.pred", "newdata", "newdataK", "ytest"]   # :340
 _CLASSES = {"bigKRLS": BigKRLS, "bigKRLS_predicted": BigKRLSPredicted, "bigKRLS_CV": BigKRLSCV}
 
@@ -175,7 +176,7 @@ def _from_r(tree):
 
 
 _VECTOR_FIELDS = {"xlabs", "which.derivatives", "coeffs", "y", "yfitted", "yfitted.std", "K.eigenvalues",
-                  "binaryindicator", "predicted", "se.pred", "ytest", "devices", "dir", "folds",
+                  "vcov.est.w", "binaryindicator", "predicted", "se.pred", "ytest", "devices", "dir", "folds",
                   "R2_is", "R2_oos", "MSE_is", "MSE_oos", "R2AME_is", "R2AME_oos", "MSE_AME_is", "MSE_AME_oos"}
 
 
@@ -187,11 +188,11 @@ def _bload(obj, path: str, noisy: bool, ctx: Optional[Context], to_device: bool)
     if isinstance(obj.get("which.derivatives"), np.ndarray):
         obj["which.derivatives"] = [int(i) for i in obj["which.derivatives"]]
     files = os.listdir(path)
-    matrices = _BIGKRLS_MATRICES if isinstance(obj, BigKRLS) else _PREDICTED_MATRICES        # :336-343
+    matrices = _BIGKRLS_MATRICES + _FACTOR_MATRICES if isinstance(obj, BigKRLS) else _PREDICTED_MATRICES   # :336-343
     for name in matrices:
         txt, npy = name + ".txt", name + ".npy"
         if txt not in files and npy not in files:
-            if name not in obj and noisy:
+            if name not in obj and noisy and name not in _FACTOR_MATRICES:
                 print("NOTE:", name, "not found in .RData or in big matrix file,", txt, ".\n")
             continue
         if noisy:

@@ -217,6 +217,14 @@ int bigkrls_dev_kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, in
 int bigkrls_dev_quadform_diag(bigkrls_ctx* ctx, int64_t m, int64_t n, const double* A, int64_t lda,
                               const double* V, int64_t ldv, double* out);
 
+/* Weighted row sums of squares: out[i] = sum_j w[j] T[i,j]^2 = diag(T diag(w) T')[i], T m x k column-major
+ * (ldt >= m), w (k) and out (m) on the device. With T = A Q and V = Q diag(w) Q' this is diag(A V A'), the quantity of
+ * bigkrls_dev_quadform_diag, from the factors of V: 2 m n k flops for the product (bigkrls_dev_gemm) instead of
+ * 2 m n^2, and with w >= 0 a sum without cancellation. One thread per row, the columns in order: deterministic, two
+ * calls give bitwise identical results. k == 0 gives zeros; m == 0 does nothing. */
+int bigkrls_dev_rowsumsq_weighted(bigkrls_ctx* ctx, int64_t m, int64_t k, const double* T, int64_t ldt,
+                                  const double* w, double* out);
+
 /* C (m x n) = alpha * op(A) op(B) + beta * C ; transa/transb: 0 = N, 1 = T. */
 int bigkrls_dev_gemm(bigkrls_ctx* ctx, int transa, int transb, int64_t m, int64_t n, int64_t k,
                      double alpha, const double* A, int64_t lda, const double* B, int64_t ldb,
@@ -383,6 +391,20 @@ typedef struct bigkrls_fit_outputs {
   double y_mean, y_sd;
   double phase_s[8];         /* HIP-event seconds: h2d, kernel, eigen, lambda, coeffs, vcov_c,
                                 vcov_fitted, derivatives */
+  /* ---- vcov.est.c as its factors: vcov.est.c = Q diag(w) Q' with Q the lastkeeper kept eigenvectors and
+   *      w_j = sd(y)^2 sigmasq / (d_j + lambda)^2, the weights the fit itself uses (:299) in the units of d_vcov_c
+   *      (:438). 8 n lastkeeper bytes instead of 8 n^2; everything after the fit can work from them
+   *      (bigkrls_predict_factored, bigkrls_marginal_effects_factored). Requires options.vcov_est != 0; independent of
+   *      d_vcov_c / d_vcov_fitted, which may be NULL (neither matrix nor its scratch is then formed). The factors are
+   *      never truncated: if lastkeeper > vcov_q_cols_max the call returns BIGKRLS_EINVAL as soon as the decomposition
+   *      is accepted, the message names both numbers and `lastkeeper` is set. In bigkrls_fit_dist every rank receives
+   *      the whole n x lastkeeper Q (the eigenvectors are replicated there: no further exchange).
+   *      vcov.est.fitted = Q diag(w_j d_j^2) Q' (:307 with K Q = Q D): its weights are formed by the host from
+   *      `eigenvalues`. */
+  double* d_vcov_q;          /* caller-allocated DEVICE buffer, n x vcov_q_cols_max, ld n; NULL = not wanted */
+  int64_t vcov_q_cols_max;   /* its capacity in columns */
+  double* vcov_w;            /* caller-allocated host array, vcov_q_cols_max doubles: receives w */
+  int64_t vcov_q_cols;       /* written by the call: columns of Q / entries of w that are valid (= lastkeeper) */
 } bigkrls_fit_outputs;
 
 /* X is n x p column-major, y has n entries, both on the HOST (they are small: 8 n (p+1) bytes).
@@ -414,6 +436,27 @@ int bigkrls_predict_pointwise(bigkrls_ctx* ctx, const double* h_X, int64_t n, in
                               const double* d_vcov_c, double neffective,
                               double* h_predicted, double* h_se_pred);
 
+/* predict.bigKRLS from the factors of vcov.est.c (bigkrls_fit_outputs.d_vcov_q / vcov_w): d_Q is n x k on the device
+ * (ldq >= n), h_w the k weights on the host, vcov.est.c = Q diag(w) Q'. Validation, standardisation, error messages and
+ * the sqrt(n / neffective) factor are those of bigkrls_predict; d_Q NULL is "no vcov.est.c".
+ * With d_newdataK and d_vcov_pred both NULL it is the counterpart of bigkrls_predict_pointwise: row blocks of b new
+ * points, b the largest multiple of 128 with 8 b (n + k) <= 2^30 bytes (the b x n test-kernel block AND its b x k
+ * product with Q fit 1 GiB together), at least 128, min(b, u) rows when u is smaller (n = 20 000, k = 250:
+ * b = 6 528). Per block: the test kernel, its product with the coefficients, T = K_b Q (bigkrls_dev_gemm) and
+ * se^2_i = sum_j w_j T_ij^2 (bigkrls_dev_rowsumsq_weighted): 2 b n k flops where bigkrls_predict_pointwise spends
+ * 2 b n^2. Extra device memory: 8 b (n + k) <= 2^30 bytes for the block and T, 8 s b k bytes for the split-K partials
+ * of the product (s is the split count bigkrls_dev_gemm chooses for a b x k result: a handful while the tiles of T
+ * leave the GPU partly idle, 1 once they fill it, so the partials shrink relative to T as k grows) and
+ * 8 ((n + b) (2 p + 1) + 2 u + k) bytes of vectors and operand copies. n = 20 000, p = 20, k = 250 (b = 6 528,
+ * s <= 5): below 1.25 GiB for u up to millions of points.
+ * With d_newdataK (u x n) or d_vcov_pred (u x u) given it is the counterpart of bigkrls_predict: the whole test
+ * kernel, T = K_new Q (u x k), vcov.est.pred = (T diag(w)) T' and its diagonal from bigkrls_dev_rowsumsq_weighted;
+ * extra device memory 8 u (2 k + p) bytes beside the outputs (and 8 u n when d_newdataK is NULL). */
+int bigkrls_predict_factored(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                             const double* h_coeffs, double sigma, const double* h_newdata, int64_t u,
+                             const double* d_Q, int64_t ldq, int64_t k, const double* h_w, double neffective,
+                             double* h_predicted, double* h_se_pred, double* d_newdataK, double* d_vcov_pred);
+
 /* Marginal effects of a fitted model at new data points (no counterpart in the reference, which computes them at
  * the training rows only, R/bigKRLS.R:318-407). X (n x p), y, coeffs (n) and sigma are the fit's; newdata (u x p,
  * host) is standardised with the TRAINING means and sds. h_which (1-based, n_which entries) selects the columns J;
@@ -427,6 +470,15 @@ int bigkrls_marginal_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int
                              const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
                              const double* h_newdata, int64_t u, const double* d_vcov_c, double* h_derivatives,
                              double* h_avg, double* h_var);
+
+/* bigkrls_marginal_effects with vcov.est.c given by its factors (d_Q n x k on the device, ldq >= n; h_w the k weights
+ * on the host) in place of d_vcov_c: everything up to the variance step is shared, and that step is the fit's own
+ * var_j = scale_j sum_k w_k (q_k' s_j)^2 (bigkrls_dev_deriv_var) instead of the product vcov.est.c S and column
+ * dots: 2 n k |J| flops instead of 2 n^2 |J|. d_Q NULL requires h_var NULL. */
+int bigkrls_marginal_effects_factored(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                                      const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
+                                      const double* h_newdata, int64_t u, const double* d_Q, int64_t ldq, int64_t k,
+                                      const double* h_w, double* h_derivatives, double* h_avg, double* h_var);
 
 /* =============================================================================
  * Multi-GPU: one process per GPU, the collectives inside the library (the context's
@@ -473,8 +525,8 @@ int bigkrls_fit_dist_rows(bigkrls_comm* comm, int64_t n, const bigkrls_fit_optio
  * (Neig << N) or the dense path with stage 1 partitioned by column blocks, lambda search / coefficients / fitted
  * values / variance matrices / marginal effects work on the row block with one all-reduce or all-gather each.
  * Every rank receives the same small host outputs; the device outputs d_K, d_vcov_c, d_vcov_fitted are this rank's
- * COLUMN blocks (n x (r1 - r0), ld n). BIGKRLS_DIST_EIGEN=krylov|dense|replicated overrides the choice of the
- * eigensolver (development / tests). */
+ * COLUMN blocks (n x (r1 - r0), ld n); d_vcov_q / vcov_w (the factors of vcov.est.c) are whole on every rank.
+ * BIGKRLS_DIST_EIGEN=krylov|dense|replicated overrides the choice of the eigensolver (development / tests). */
 int bigkrls_fit_dist(bigkrls_comm* comm, const double* h_X, const double* h_y, int64_t n, int64_t p,
                      const bigkrls_fit_options* options, bigkrls_fit_outputs* out);
 
