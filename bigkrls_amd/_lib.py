@@ -36,7 +36,7 @@ class FitOptions(C.Structure):
     """bigkrls_fit_options (include/bigkrls.h)."""
     _fields_ = [("struct_bytes", i64), ("sigma", f64), ("lambda_", f64), ("L", f64), ("U", f64),
                 ("eigtrunc", f64), ("neig", i64), ("derivative", i32), ("vcov_est", i32), ("acf", i32),
-                ("reserved", i32), ("which_derivatives", pi64), ("n_which", i64)]
+                ("kernel_form", i32), ("which_derivatives", pi64), ("n_which", i64)]
 
 
 class FitOutputs(C.Structure):
@@ -101,6 +101,7 @@ SIGNATURES = {
     "bigkrls_dev_multdiag": [vp, vp, i64, i64, i64, vp, vp, i64],
     "bigkrls_dev_eigen": [vp, vp, i64, i64, i64, vp, i64, f64, vp, i64, pi64],
     "bigkrls_dev_eigen_part": [vp, vp, i64, i64, i64, vp, i64, f64, vp, i64, pi64, i32, i32],
+    "bigkrls_dev_eigen_implicit": [vp, vp, i64, i64, i64, f64, i64, vp, i64, f64, vp, i64, pi64],
     "bigkrls_dev_fill_random": [vp, vp, i64, C.c_uint32],
     "bigkrls_dev_cholqr2": [vp, vp, vp, i64, i64, vp, pi32, vp],
     "bigkrls_dev_lanczos_projected": [vp, vp, vp, i64, i64, vp],

@@ -96,7 +96,7 @@ def bigKRLS(y=None, X=None, sigma=None, derivative=True, which_derivatives=None,
             acf=False, noisy=None, instructions=True, ctx: Optional[Context] = None,
             timings: Optional[Dict[str, float]] = None,
             trace: Optional[list] = None, comm=None, keep_outputs: bool = True,
-            vcov_form: str = "dense", max_factors: Optional[int] = None) -> BigKRLS:
+            vcov_form: str = "dense", max_factors: Optional[int] = None, kernel: str = "stored") -> BigKRLS:
     """Kernel-regularised least squares fit (R/bigKRLS.R:97-516).
 
     The numeric body -- validation of the data, standardisation, the five steps and the rescaling
@@ -124,6 +124,12 @@ def bigKRLS(y=None, X=None, sigma=None, derivative=True, which_derivatives=None,
     single rank. The buffer for Q has `Neig` columns when Neig was given or nothing is truncated (eigtrunc 0),
     otherwise `max_factors` (default min(N, 2048)); a fit that keeps more eigenpairs than that raises a ValueError --
     factors are never truncated -- and the columns not needed are released after the call.
+    `kernel`: "stored" (default) builds the N x N kernel matrix; "implicit" never stores it -- every product with K
+    (the block Lanczos steps, the check of the decomposition, K c, the marginal-effects pass) rebuilds the kernel tiles
+    from X inside a fused contraction, so the fit holds no N x N buffer at all: O(N maxdim + N Neig) doubles with
+    maxdim = min(N/2, max(16 Neig, 4096)). It needs `Neig` with N >= 1024 and 4 Neig <= N (block Lanczos only: there is
+    no dense fallback), one GPU, and vcov_form="factors" whenever vcov_est is true. The object then has K = None and
+    w["kernel"] = "implicit"; predict(), marginal_effects(), summary() and save / load work on it unchanged.
     """
     ctx = (comm.ctx if comm is not None else ctx) or default_context()
     if X is None or y is None:
@@ -169,6 +175,23 @@ def bigKRLS(y=None, X=None, sigma=None, derivative=True, which_derivatives=None,
     if max_factors is not None and not (isinstance(max_factors, (int, np.integer)) and not isinstance(max_factors, bool)
                                         and max_factors >= 1):
         raise ValueError("max_factors must be a positive integer")
+    if kernel not in ("stored", "implicit"):
+        raise ValueError('kernel must be "stored" or "implicit"')
+    implicit = kernel == "implicit"
+    if implicit:
+        if comm is not None:
+            raise ValueError('kernel="implicit" runs on one GPU: drop comm, or use kernel="stored"')
+        if Neig is None:
+            raise ValueError('kernel="implicit" needs Neig (the block Lanczos computes the Neig largest eigenpairs): '
+                             'pass Neig <= N/4, or use kernel="stored"')
+        if n < 1024:
+            raise ValueError(f'kernel="implicit" needs N >= 1024 (N = {n}): use kernel="stored"')
+        if 4 * neig > n:
+            raise ValueError(f'kernel="implicit" needs 4 Neig <= N (Neig = {neig}, N = {n}): pass Neig <= {n // 4}, '
+                             'or use kernel="stored"')
+        if vcov_est and vcov_form != "factors":
+            raise ValueError('kernel="implicit" returns the variance as factors: pass vcov_form="factors" '
+                             '(or vcov_est=False, derivative=False)')
     want_dense, want_factors = vcov_form != "factors", vcov_form != "dense"
     if want_factors and not vcov_est:
         raise ValueError('vcov_form = "factors" / "both" requires vcov_est = True')
@@ -192,6 +215,7 @@ def bigKRLS(y=None, X=None, sigma=None, derivative=True, which_derivatives=None,
     opt.derivative = int(bool(derivative))
     opt.vcov_est = int(bool(vcov_est))
     opt.acf = int(bool(acf))
+    opt.kernel_form = 1 if implicit else 0
     which_arr = None
     if which_derivatives is not None:
         which_arr = np.ascontiguousarray(which_derivatives, dtype=np.int64)
@@ -224,7 +248,7 @@ def bigKRLS(y=None, X=None, sigma=None, derivative=True, which_derivatives=None,
         r0, r1 = int(a0.value), int(a1.value)
     ncols = r1 - r0                                                               # columns of K this process holds
     K = vcovmatc = vcovmatyhat = Qf = wf = None
-    if keep_outputs or comm is None:
+    if (keep_outputs or comm is None) and not implicit:
         K = ctx.empty(n, max(ncols, 1))                                           # :434
         out.d_K = K.ptr
         if vcov_est and want_dense:
@@ -285,7 +309,7 @@ def bigKRLS(y=None, X=None, sigma=None, derivative=True, which_derivatives=None,
             w["vcov.est.c.cols"] = cut(vcovmatc) if vcovmatc is not None else None
             w["vcov.est.fitted.cols"] = cut(vcovmatyhat) if vcovmatyhat is not None else None
     else:
-        w["K"] = K if return_big_squares else K.to_numpy()                        # :434
+        w["K"] = None if implicit else (K if return_big_squares else K.to_numpy())   # :434
         if vcovmatc is not None:
             w["vcov.est.c"] = vcovmatc if return_big_squares else vcovmatc.to_numpy()          # :438
             w["vcov.est.fitted"] = vcovmatyhat if return_big_squares else vcovmatyhat.to_numpy()   # :445
@@ -295,6 +319,8 @@ def bigKRLS(y=None, X=None, sigma=None, derivative=True, which_derivatives=None,
     if want_factors:                                          # flat keys: save_bigKRLS / load_bigKRLS carry them as they are
         w["vcov.est.Q"] = Qf
         w["vcov.est.w"] = wf
+    if implicit:                                              # (stored fits keep the member list they always had)
+        w["kernel"] = "implicit"
     w["derivative.call"] = derivative
     if derivative:
         w["avgderivatives"] = avg[None, :]                                        # :400

@@ -566,6 +566,15 @@ int bigkrls_dev_eigen_part(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t
                part_count);
 }
 
+int bigkrls_dev_eigen_implicit(bigkrls_ctx* ctx, const double* X, int64_t n, int64_t ldx, int64_t p, double sigma,
+                               int64_t n_vals, double* vals, int64_t n_vecs_max, double h_keep_thresh, double* vecs,
+                               int64_t ldv, int64_t* h_n_vecs) {
+  BK_TRY(check_ctx(ctx));
+  KernelOp kernel;
+  BK_TRY(kernel_op_prepare(ctx, X, n, ldx, p, sigma, &kernel));
+  return eigen_implicit(ctx, kernel, n_vals, vals, n_vecs_max, h_keep_thresh, vecs, ldv, h_n_vecs);
+}
+
 int bigkrls_dev_fill_random(bigkrls_ctx* ctx, double* p, int64_t count, uint32_t seed) {
   BK_TRY(check_ctx(ctx));
   return fill_random(ctx, p, count, seed);

@@ -65,7 +65,7 @@ struct bigkrls_ctx {
   bool side_is_main = false;   // BIGKRLS_NO_SIDE (diagnostics): side_stream is the main stream itself
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_pq = nullptr;
   // workspace slots: slot i is grown on demand and reused across calls
-  static constexpr int kSlots = 52;
+  static constexpr int kSlots = 54;
   void* ws[kSlots] = {nullptr};
   int64_t ws_bytes[kSlots] = {0};
   // pinned host scratch for small scalar read-backs
@@ -199,6 +199,8 @@ enum Slot {
   SLOT_KB_SHIFT = 49,      // kernel_block / kernel_contract: the common shift of both operands (P doubles: column means of A)
   SLOT_KB_A = 50,          // ... the shifted copy of A (u x P)
   SLOT_KB_B = 51,          // ... the shifted copy of B (v x P) where B is not a row block of A
+  SLOT_KOP_X = 52,         // implicit kernel operator (KernelOp): the centred copy of X (n x P)
+  SLOT_KOP_NORMS = 53,     // ... and its squared row norms
 };
 
 int ws_get(bigkrls_ctx* ctx, int slot, int64_t nbytes, void** out);
@@ -270,6 +272,26 @@ int kernel_block(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, cons
 int kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
                     int64_t ldb, int64_t p, double sigma, const double* W, int64_t q, int64_t ldw, int trans,
                     double* out, int64_t ldo);
+
+// The same for operands that are already centred (one common shift, see centre_operands in gemm.hip) and come with
+// their squared row norms: out (ns x q, ldo) = K(S, L) W, S the stationary rows (ns x p, lds), L the loop rows
+// (nl x p, ldl), W nl x q. More than 64 columns run through the wide kernel (profile name kernel_contract_wide).
+int kernel_contract_centred(bigkrls_ctx* ctx, const double* S, int64_t ns, int64_t lds, const double* nrm_s,
+                            const double* L, int64_t nl, int64_t ldl, const double* nrm_l, int64_t p, double sigma,
+                            const double* W, int64_t q, int64_t ldw, double* out, int64_t ldo);
+
+// K(X, X) as an operator: the kernel matrix of a fit that never stores it (kernel_form = 1). kernel_op_prepare centres
+// X once (workspace slots of its own); kernel_op_times is out (n x q, ldo) = K W, W n x q (ldw), by the fused contraction.
+// Its diagonal is exp(-max(d2, 0) / sigma) with d2 at rounding level, not the exact 1 of the stored build.
+struct KernelOp {
+  const double* Xc = nullptr;    // centred X, n x p, ld n
+  const double* nrm = nullptr;   // squared row norms of Xc
+  int64_t n = 0, p = 0;
+  double sigma = 0.0;
+};
+int kernel_op_prepare(bigkrls_ctx* ctx, const double* X, int64_t n, int64_t ldx, int64_t p, double sigma, KernelOp* op);
+int kernel_op_times(bigkrls_ctx* ctx, const KernelOp& op, const double* W, int64_t q, int64_t ldw, double* out,
+                    int64_t ldo);
 
 // out (m) = diag(A V A'), i.e. out[i] = sum_j (A V)[i,j] A[i,j]; A m x n (lda), V n x n (ldv), V general. The product
 // A V is never stored; deterministic (fixed-order reduction of the per-tile partials).
@@ -360,7 +382,8 @@ struct Vcov {
 int deriv_rows(bigkrls_ctx* ctx, const double* Krows, int64_t n, int64_t n_rows, int64_t ldk,
                int64_t row0, const double* X, int64_t p, int64_t ldx, const int32_t* h_is_binary,
                const double* c, double sigma, double* D, int64_t ldd, double* S, int64_t lds, double* kc_out = nullptr,
-               const double* extra = nullptr, int64_t n_extra = 0, double* extra_out = nullptr);
+               const double* extra = nullptr, int64_t n_extra = 0, double* extra_out = nullptr,
+               const KernelOp* kernel = nullptr);
 int deriv_var(bigkrls_ctx* ctx, const double* Q, int64_t n, int64_t k, int64_t ldq,
               const double* wv, const double* S, int64_t p, int64_t lds, const double* h_scale,
               double* h_var);
@@ -382,6 +405,10 @@ int eigen(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t lda, int64_t n_v
 int eigen_krylov_dist(bigkrls_comm* comm, const double* Kcols, int64_t n, int64_t r0, int64_t r1, int64_t nb,
                       int64_t n_vals, double* vals, int64_t n_vecs_max, double keep_thresh, double* vecs, int64_t ldv,
                       int64_t* h_n_vecs);
+// the n_vals largest pairs of K(X, X) by the block Lanczos on the operator (never a matrix): n >= 1024 and
+// 4 n_vals <= n, else BIGKRLS_EINVAL; no dense fall-through -- BIGKRLS_ENOCONV is returned
+int eigen_implicit(bigkrls_ctx* ctx, const KernelOp& kernel, int64_t n_vals, double* vals, int64_t n_vecs_max,
+                   double keep_thresh, double* vecs, int64_t ldv, int64_t* h_n_vecs);
 // Row-block distributed stage 1 (dense -> band), one call per panel step between the caller's
 // collectives; see include/bigkrls.h (bigkrls_dev_s1_*).
 int dist_s1_open(bigkrls_ctx* ctx, int64_t n);

@@ -117,14 +117,17 @@ __global__ void deriv_finalize_kernel(int n_rows, int p, int row0, const double*
 int deriv_rows(bigkrls_ctx* ctx, const double* Krows, int64_t n, int64_t n_rows, int64_t ldk,
                int64_t row0, const double* X, int64_t p, int64_t ldx, const int32_t* h_is_binary,
                const double* c, double sigma, double* D, int64_t ldd, double* S, int64_t lds, double* kc_out,
-               const double* extra, int64_t n_extra, double* extra_out) {
+               const double* extra, int64_t n_extra, double* extra_out, const KernelOp* kernel) {
   // `extra` (n x n_extra, ld n): more operand columns for the same pass over K; K extra -> extra_out (n_rows x n_extra).
   // The fit sends the two +-1 combinations of its kept eigenvectors along: the check of the decomposition against K
   // costs no pass over K of its own (Fit::verify_deferred, csrc/fit.hip).
   BK_REQUIRE(n > 0 && n_rows > 0 && p > 0 && n < (1ll << 31) && p < (1 << 20),
              "deriv_rows: bad dimensions");
   BK_REQUIRE(row0 >= 0 && row0 + n_rows <= n, "deriv_rows: row block out of range");
-  BK_REQUIRE(Krows && X && h_is_binary && c && D && S, "deriv_rows: null pointer");
+  // `kernel`: K is not stored -- the product with the whole K is the fused contraction on the operator (Krows unused);
+  // same operand matrix B, same finalise kernel
+  BK_REQUIRE((Krows || kernel) && X && h_is_binary && c && D && S, "deriv_rows: null pointer");
+  BK_REQUIRE(!kernel || (kernel->n == n && n_rows == n && row0 == 0), "deriv_rows: the kernel operator covers all rows");
   BK_REQUIRE(n_extra >= 0 && (n_extra == 0 || (extra && extra_out)), "deriv_rows: bad extra operand");
   const int64_t nb0 = 2 + 2 * p, nb = nb0 + n_extra;
   void *pb = nullptr, *pkb = nullptr, *pt = nullptr;
@@ -154,7 +157,9 @@ int deriv_rows(bigkrls_ctx* ctx, const double* Krows, int64_t n, int64_t n_rows,
   // (33 .. 48 operand columns -- P = 16 .. 23 -- on the 128 x 48 tile: the 128 x 64 tile of gemm() would run the MFMA
   //  units on up to a third of padding; BIGKRLS_DERIV48=0: the generic kernel, for cross-checks)
   static const bool use48 = [] { const char* e = getenv("BIGKRLS_DERIV48"); return !(e && e[0] == '0'); }();
-  if (n_rows == n && row0 == 0 && nb > 32 && nb <= 48 && n >= 4096 && use48)
+  if (kernel)
+    BK_TRY(kernel_op_times(ctx, *kernel, (const double*)pb, nb, n, (double*)pkb, n));
+  else if (n_rows == n && row0 == 0 && nb > 32 && nb <= 48 && n >= 4096 && use48)
     BK_TRY(gemm_nn_skinny48(ctx, n, nb, n, Krows, ldk, (const double*)pb, n, (double*)pkb, n));
   else if (n_rows == n && row0 == 0)
     BK_TRY(gemm(ctx, 0, 0, n, nb, n, 1.0, Krows, ldk, (const double*)pb, n, 0.0, (double*)pkb, n));

@@ -2197,9 +2197,12 @@ static thread_local std::string kry_diag;   // what the last block Lanczos did a
 // W (n x cols, ld n) = K B (n x cols, ld n): the only way the block Lanczos touches K. Single GPU: the whole matrix
 // A. Multi-GPU: this rank's column block Kcols = K[:, r0:r1] gives the rows r0:r1 of K B (K symmetric: Kcols' B),
 // one all-gather of the row blocks assembles the product on every rank ("Eigen, partial").
+// Implicit kernel (single GPU): no matrix at all -- K = K(X, X) as an operator, the product is the fused contraction
+// (kernel_op_times, csrc/gemm.hip).
 struct KTimes {
   const double* A = nullptr;
   int64_t lda = 0;
+  const KernelOp* kernel = nullptr;
   bigkrls_comm* comm = nullptr;
   const double* Kcols = nullptr;
   int64_t r0 = 0, r1 = 0, nb = 0;
@@ -2212,6 +2215,7 @@ struct KTimes {
 // the re-orthogonalisation, the Cholesky QR and the Ritz vectors work on the row blocks and all-reduce their small
 // Gram / coefficient matrices.
 static int k_times(bigkrls_ctx* ctx, const KTimes& op, int64_t n, double* B, int64_t cols, double* W) {
+  if (op.kernel) return kernel_op_times(ctx, *op.kernel, B, cols, n, W, n);
   if (!op.comm) return gemm(ctx, 0, 0, n, cols, n, 1.0, op.A, op.lda, B, n, 0.0, W, n);
   const int64_t nloc = op.r1 - op.r0;
   BK_TRY(comm_gather_rows(op.comm, B + op.r0, nloc, n, cols, op.nb, n, B, n));
@@ -2756,6 +2760,27 @@ int eigen_krylov_dist(bigkrls_comm* comm, const double* Kcols, int64_t n, int64_
   op.nb = nb;
   // every rank keeps all the kept eigenvector columns (part 0 of 1): the later passes work on row blocks of Q
   return eigen_krylov(comm->ctx, op, n, n_vals, vals, n_vecs_max, keep_thresh, vecs, ldv, h_n_vecs, 0, 1);
+}
+
+// The block Lanczos on a kernel matrix that is never stored. There is no matrix to hand to the dense path: what the
+// iteration cannot deliver is the caller's answer.
+int eigen_implicit(bigkrls_ctx* ctx, const KernelOp& kernel, int64_t n_vals, double* vals, int64_t n_vecs_max,
+                   double keep_thresh, double* vecs, int64_t ldv, int64_t* h_n_vecs) {
+  const int64_t n = kernel.n;
+  BK_REQUIRE(kernel.Xc && kernel.nrm && vals && n > 0 && n < (1ll << 30), "eigen (implicit kernel): bad arguments");
+  if (!(n >= 1024 && n_vals > 0 && 4 * n_vals <= n)) {
+    set_error("eigen (implicit kernel): the block Lanczos needs n >= 1024 and 4 n_vals <= n (n = " + std::to_string((long long)n) +
+              ", n_vals = " + std::to_string((long long)n_vals) + ")");
+    return BIGKRLS_EINVAL;
+  }
+  BK_REQUIRE(n_vecs_max >= 0 && n_vecs_max <= n, "eigen (implicit kernel): n_vecs_max out of range");
+  BK_REQUIRE(n_vecs_max == 0 || (vecs && ldv >= n), "eigen (implicit kernel): bad eigenvector buffer");
+  KTimes op;
+  op.kernel = &kernel;
+  const int rc = eigen_krylov(ctx, op, n, n_vals, vals, n_vecs_max, keep_thresh, vecs, ldv, h_n_vecs, 0, 1);
+  if (rc == BIGKRLS_ENOCONV)
+    set_error(std::string(bigkrls_last_error()) + " -- the implicit kernel form has no dense fallback: fit with kernel=\"stored\"");
+  return rc;
 }
 
 // Stage-1 state of a row-block distributed reduction, kept in the context between

@@ -137,6 +137,8 @@ struct Fit {
   int64_t neig = 0, pd = 0;
   double eigtrunc = 0.0, sigma = 0.0;
   bool derivative = false, vcov_est = false, acf = false;
+  bool implicit = false;                       // kernel_form = 1: K is never stored, `kop` stands in for dK
+  KernelOp kop;
   std::vector<int64_t> cols;                   // 0-based selected columns
   std::vector<double> x_mean, x_sd;
   double y_mean = 0.0, y_sd = 0.0;
@@ -210,6 +212,18 @@ struct Fit {
     }
     acf = opt->acf != 0 && p > 2;                                                                        // :192
     neig = (opt->neig > 0) ? std::min<int64_t>(n, opt->neig) : n;                                        // :194
+    if (opt->kernel_form != 0 && opt->kernel_form != 1) return fail("fit: kernel_form must be 0 (stored) or 1 (implicit)");
+    implicit = opt->kernel_form == 1;
+    if (implicit) {
+      if (comm) return fail("fit: the implicit kernel form runs on one GPU (bigkrls_fit), not in bigkrls_fit_dist");
+      if (out->d_K) return fail("fit: the implicit kernel form stores no kernel matrix: d_K must be NULL");
+      if (out->d_vcov_c || out->d_vcov_fitted)
+        return fail("fit: the implicit kernel form returns the variance as factors (d_vcov_q, vcov_w): d_vcov_c and d_vcov_fitted must be NULL");
+      if (opt->neig <= 0) return fail("fit: the implicit kernel form needs neig (block Lanczos for the neig largest pairs)");
+      if (n < 1024 || 4 * neig > n)
+        return fail("fit: the implicit kernel form needs n >= 1024 and 4 neig <= n (n = " + std::to_string((long long)n) +
+                    ", neig = " + std::to_string((long long)neig) + ")");
+    }
     eigtrunc = opt->eigtrunc;
     if (eigtrunc < 0.0 || std::isnan(eigtrunc)) eigtrunc = n > 3000 ? 0.001 : 0.0;                       // :195-201
     else if (eigtrunc > 1.0) return fail("eigtrunc must be between 0 (no truncation) and 1 (keep largest only).");
@@ -309,7 +323,7 @@ struct Fit {
     void* unused = nullptr;
     BK_TRY(ws_get(ctx, SLOT_FIT_SMALL, small_doubles * (int64_t)sizeof(double), psmall));
     BK_TRY(ws_get(ctx, SLOT_FIT_Q, n * neig * (int64_t)sizeof(double), pq));
-    if (!out->d_K)   // K: the whole matrix, or this rank's column block K[:, r0:r1) (n x nloc, ld n)
+    if (!out->d_K && !implicit)   // K: the whole matrix, or this rank's column block K[:, r0:r1) (n x nloc, ld n)
       BK_TRY(ws_get(ctx, comm ? SLOT_DIST_K : SLOT_FIT_K, n * std::max<int64_t>(nloc, 1) * (int64_t)sizeof(double), pk));
     if (comm && vcov_est && (out->d_vcov_c || out->d_vcov_fitted))   // Q diag(w) of the variance matrices, up front
       BK_TRY(ws_get(ctx, SLOT_FIT_M, n * neig * (int64_t)sizeof(double), &unused));
@@ -340,6 +354,11 @@ struct Fit {
 
   // ---- step 1: kernel (:262) ---------------------------------------------------------------------------------------
   int build_kernel() {
+    if (implicit) {   // no matrix: the centred copy of X and its norms, once for every product of the fit
+      BK_TRY(kernel_op_prepare(ctx, dX, n, n, p, sigma, &kop));
+      timer.mark();                                                         // kernel (about 0: the products land in `eigen`)
+      return BIGKRLS_OK;
+    }
     if (!comm) BK_TRY(kernel_block(ctx, dX, n, n, dX, n, n, p, sigma, dK, n, 0));
     else BK_TRY(agreed(nloc > 0 ? kernel_block(ctx, dX, n, n, dX + r0, nloc, n, p, sigma, dK, n, r0) : BIGKRLS_OK));   // K[:, r0:r1): no exchange
     timer.mark();                                                           // kernel
@@ -362,7 +381,10 @@ struct Fit {
     return fetch_and_agree_eigenvalues();
   }
 
-  int eigen_single() { return soften(eigen(ctx, dK, n, n, neig, dvals, neig, eigtrunc, dQ, n, &lastkeeper)); }
+  int eigen_single() {
+    if (implicit) return soften(eigen_implicit(ctx, kop, neig, dvals, neig, eigtrunc, dQ, n, &lastkeeper));
+    return soften(eigen(ctx, dK, n, n, neig, dvals, neig, eigtrunc, dQ, n, &lastkeeper));
+  }
 
   int eigen_dist_krylov() {
     return agreed(soften(eigen_krylov_dist(comm, dK, n, r0, r1, nb, neig, dvals, neig, eigtrunc, dQ, n, &lastkeeper)));
@@ -553,7 +575,8 @@ struct Fit {
     BK_HIP(hipMemcpyAsync(dC, hp, (size_t)(4 * kk) * sizeof(double), hipMemcpyHostToDevice, st));
     BK_TRY(gemm(ctx, 0, 0, n, 4, kk, 1.0, dQ, n, dC, kk, 0.0, dU, n));          // [U | L] = Q [R | Lambda R]  (dL follows dU)
     if (rows > 0 && !defer_k) {
-      if (!comm) BK_TRY(gemm(ctx, 0, 0, n, 2, n, 1.0, dK, n, dU, n, 0.0, dR, n));
+      if (implicit) BK_TRY(kernel_op_times(ctx, kop, dU, 2, n, dR, n));
+      else if (!comm) BK_TRY(gemm(ctx, 0, 0, n, 2, n, 1.0, dK, n, dU, n, 0.0, dR, n));
       else BK_TRY(gemm(ctx, 1, 0, rows, 2, n, 1.0, dK, n, dU, n, 0.0, dR, rows));
     }
     BK_HIP(hipStreamSynchronize(st));     // (the pinned buffer was the source of the upload)
@@ -757,7 +780,8 @@ struct Fit {
     BK_TRY(solveforc(ctx, dQ, n, k, n, dvals, da, lambda, dc, &Le));
     if (!one_pass_over_k()) {
       if (ctx->profile) BK_TRY(prof_begin(ctx, "yhat_gemv", 8.0 * (double)n * (double)n));
-      BK_TRY(gemv(ctx, 0, n, n, 1.0, dK, n, dc, 0.0, dyhat));                                            // yfitted = K c (full K)
+      if (implicit) BK_TRY(kernel_op_times(ctx, kop, dc, 1, n, dyhat, n));
+      else BK_TRY(gemv(ctx, 0, n, n, 1.0, dK, n, dc, 0.0, dyhat));                                       // yfitted = K c (full K)
       if (ctx->profile) BK_TRY(prof_end(ctx, "yhat_gemv"));
       return BIGKRLS_OK;
     }
@@ -765,7 +789,8 @@ struct Fit {
     if (ctx->profile) BK_TRY(prof_begin(ctx, "deriv_rows", 8.0 * (double)n * (double)n));
     BK_TRY(deriv_rows(ctx, dK, n, n, n, 0, dXe, pd, n, isbin.data(), dc, sigma, dD, n, dS, n, dyhat,     // + yfitted = K c (:291)
                       verify_pending ? dVU : (const double*)nullptr, verify_pending ? 2 : 0,
-                      verify_pending ? dVU + 4 * n : (double*)nullptr));                                // + K [u_1 u_2]
+                      verify_pending ? dVU + 4 * n : (double*)nullptr,                                  // + K [u_1 u_2]
+                      implicit ? &kop : (const KernelOp*)nullptr));
     if (ctx->profile) BK_TRY(prof_end(ctx, "deriv_rows"));
     return verify_pending ? verify_deferred() : (int)BIGKRLS_OK;
   }

@@ -2034,29 +2034,192 @@ __global__ void contract_reduce_kernel(int NS, int Q, int nsplit, const double* 
   }
 }
 
-int kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
-                    int64_t ldb, int64_t p, double sigma, const double* W, int64_t q, int64_t ldw, int trans,
-                    double* out, int64_t ldo) {
-  BK_REQUIRE(u > 0 && v > 0 && p > 0 && q > 0, "kernel_contract: bad dimensions");
-  BK_REQUIRE(u < (1ll << 31) && v < (1ll << 31) && p < (1ll << 20) && q < (1ll << 20), "kernel_contract: too large");
-  BK_REQUIRE(trans == 0 || trans == 1, "kernel_contract: trans must be 0 or 1");
-  BK_REQUIRE(sigma > 0.0, "kernel_contract: sigma must be > 0");
-  BK_REQUIRE(A && B && W && out, "kernel_contract: null pointer");
-  BK_REQUIRE(lda >= u && ldb >= v, "kernel_contract: leading dimension of A or B too small");
-  // trans = 0: stationary rows A, loop rows B; trans = 1: the reverse
-  const int64_t ns = trans ? v : u, nl = trans ? u : v;
-  BK_REQUIRE(ldw >= nl && ldo >= ns, "kernel_contract: leading dimension of W or out too small");
-  CentredOperands co;     // both operands moved by the column means of A (see centre_operands)
-  BK_TRY(centre_operands(ctx, A, u, lda, B, v, ldb, p, &co));
-  A = co.A; lda = co.lda; B = co.B; ldb = co.ldb;
-  const double *pna = co.na, *pnb = co.nb;
-  const double* nrm_s = (const double*)(trans ? pnb : pna);
-  const double* nrm_l = (const double*)(trans ? pna : pnb);
-  const double* S = trans ? B : A;
-  const double* L = trans ? A : B;
-  const int64_t lds = trans ? ldb : lda, ldl = trans ? lda : ldb;
+// The same contraction for more than 64 columns of W (the 128-column block of the block Lanczos on an implicit kernel,
+// csrc/eigen.hip): one wave builds a kernel tile ONCE and contracts it with up to 128 columns, where the kernel above
+// (CT <= 4) would rebuild every tile, exp included, once per 64 columns.
+// Tiling: KCW_MS = 2 stationary tiles (32 rows) x KCW_CT = 8 column tiles (128 columns) per wave. Registers per lane
+// (a double is two): accumulators 2 x 8 x 4 doubles = 128 (AGPRs), resident fragments sf 2 x KS <= 16 doubles = 32,
+// G / E 2 x 4 doubles = 16, one k-step of W 8 doubles = 16 (the compiler keeps two to three of the four in flight),
+// loop fragments, norms and addresses about 40: 230 to 256 of the 512 of the unified file, i.e. 2 waves per SIMD
+// (__launch_bounds__(NT, 2) holds the allocator to it). Four stationary tiles with 128 columns would take 256
+// registers for the accumulators alone and leave one wave per SIMD with nothing to cover the loads of W.
+// MFMA 16x16x4 per 32 x 16 kernel tile pair: 2 KS (<= 16) for G and 2 x 4 x 8 = 64 for the contraction.
+// Column tiles that lie wholly past q are skipped (wave-uniform), so a last chunk of q mod 128 columns costs its own
+// tiles only. Everything else -- operand layout, edge clamping, the epilogue, the fixed-order reduction of the loop
+// splits -- is kernel_contract_kernel's.
+constexpr int KCW_MS = 2;   // 16-row stationary tiles per wave
+constexpr int KCW_CT = 8;   // 16-column tiles of W per wave
 
-  const int CT = q <= 16 ? 1 : (q <= 32 ? 2 : 4);
+// FULL: the wave's 128 columns all exist (the Lanczos block): column tile c of W sits at the wave-uniform offset
+// 16 c ldw from one pointer per lane. Otherwise: a clamped column per tile, tiles wholly past q skipped.
+template <int KS, bool FULL>
+__device__ __forceinline__ void kcw_body(const double* __restrict__ S, int64_t lds, int NS, const double* __restrict__ L,
+                                         int64_t ldl, int NL, int P, const double* __restrict__ nrm_s,
+                                         const double* __restrict__ nrm_l, double neg_inv_sigma,
+                                         const double* __restrict__ W, int64_t ldw, int Q, double* __restrict__ dst,
+                                         int64_t ldo, int s0, int c0, int t_begin, int t_end, const double* etab) {
+  const int lane = threadIdx.x & 63;
+  const int lm = lane & 15, lk = lane >> 4;
+  const int steps = (P + 3) / 4;
+  const int nct = FULL ? KCW_CT : min(KCW_CT, (Q - c0 + 15) / 16);   // column tiles that hold a column (wave-uniform)
+
+  int srow[KCW_MS];
+  double ns[KCW_MS];
+#pragma unroll
+  for (int m = 0; m < KCW_MS; ++m) {
+    srow[m] = min(s0 + 16 * m + lm, NS - 1);
+    ns[m] = nrm_s[srow[m]];
+  }
+  // stationary fragments (k >= P zeroed: the loop side then reads a clamped, finite value)
+  double sf[KCW_MS][KS > 0 ? KS : 1];
+  if (KS > 0) {
+#pragma unroll
+    for (int m = 0; m < KCW_MS; ++m)
+#pragma unroll
+      for (int t = 0; t < (KS > 0 ? KS : 1); ++t) {
+        const int k = 4 * t + lk;
+        sf[m][t] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
+      }
+  }
+  d4 acc[KCW_MS][KCW_CT];
+#pragma unroll
+  for (int m = 0; m < KCW_MS; ++m)
+#pragma unroll
+    for (int c = 0; c < KCW_CT; ++c) acc[m][c] = (d4){0.0, 0.0, 0.0, 0.0};
+  // this lane's column of W in each column tile
+  const double* wbase = W + (int64_t)(c0 + lm) * ldw;
+  const int64_t wstep = 16 * ldw;
+
+  for (int t = t_begin; t < t_end; ++t) {
+    const int l0 = t * 16;
+    const int lrow = min(l0 + lm, NL - 1);   // this lane's row of the L operand
+    double nl[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) nl[r] = nrm_l[min(l0 + lk + 4 * r, NL - 1)];
+    d4 g[KCW_MS];
+#pragma unroll
+    for (int m = 0; m < KCW_MS; ++m) g[m] = (d4){0.0, 0.0, 0.0, 0.0};
+    if (KS > 0) {
+      double lf[KS > 0 ? KS : 1];
+#pragma unroll
+      for (int s = 0; s < (KS > 0 ? KS : 1); ++s) lf[s] = L[lrow + (int64_t)min(4 * s + lk, P - 1) * ldl];
+#pragma unroll
+      for (int s = 0; s < (KS > 0 ? KS : 1); ++s)
+#pragma unroll
+        for (int m = 0; m < KCW_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sf[m][s], g[m], 0, 0, 0);
+    } else {
+      for (int s0k = 0; s0k < steps; s0k += 4) {
+        double lf[4], sg[KCW_MS][4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const int k = 4 * (s0k + s) + lk;
+          lf[s] = L[lrow + (int64_t)min(k, P - 1) * ldl];
+#pragma unroll
+          for (int m = 0; m < KCW_MS; ++m) sg[m][s] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+          for (int m = 0; m < KCW_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sg[m][s], g[m], 0, 0, 0);
+      }
+    }
+    // E in place of G (kernel_block_wave_kernel's epilogue)
+#pragma unroll
+    for (int m = 0; m < KCW_MS; ++m)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        double d2 = fma(-2.0, g[m][r], ns[m] + nl[r]);
+        d2 = fmax(d2, 0.0);
+        g[m][r] = exp_nonpos_tab(d2 * neg_inv_sigma, etab);
+      }
+    // k-step r of the contraction: loop rows l0 + (lane >> 4) + 4 r, one k-step of W (8 doubles) at a time
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int l = l0 + lk + 4 * r;
+      const bool lok = l < NL;
+      const int lc = min(l, NL - 1);
+      double wf[KCW_CT];
+      if (FULL) {
+#pragma unroll
+        for (int c = 0; c < KCW_CT; ++c) {
+          const double v = wbase[c * wstep + lc];
+          wf[c] = lok ? v : 0.0;
+        }
+#pragma unroll
+        for (int c = 0; c < KCW_CT; ++c)
+#pragma unroll
+          for (int m = 0; m < KCW_MS; ++m)
+            acc[m][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(g[m][r], wf[c], acc[m][c], 0, 0, 0);
+      } else {
+#pragma unroll
+        for (int c = 0; c < KCW_CT; ++c) {
+          const int col = c0 + 16 * c + lm;      // (clamped: a column past q is weighted by 0; the address is
+          const double v = W[lc + (int64_t)min(col, Q - 1) * ldw];   //  recomputed to keep 8 pointers out of registers)
+          wf[c] = (lok && col < Q) ? v : 0.0;
+        }
+#pragma unroll
+        for (int c = 0; c < KCW_CT; ++c)
+          if (c < nct) {
+#pragma unroll
+            for (int m = 0; m < KCW_MS; ++m)
+              acc[m][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(g[m][r], wf[c], acc[m][c], 0, 0, 0);
+          }
+      }
+    }
+  }
+  // acc[m][c] register r: (s = s0 + 16 m + (lane >> 4) + 4 r, col = c0 + 16 c + (lane & 15))
+#pragma unroll
+  for (int m = 0; m < KCW_MS; ++m)
+#pragma unroll
+    for (int c = 0; c < KCW_CT; ++c) {
+      const int col = c0 + 16 * c + lm;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int s = s0 + 16 * m + lk + 4 * r;
+        if (s < NS && (FULL || col < Q)) dst[s + (int64_t)col * ldo] = acc[m][c][r];
+      }
+    }
+}
+
+template <int KS>
+__global__ __launch_bounds__(NT, 2) void kernel_contract_wide_kernel(
+    const double* __restrict__ S, int64_t lds, int NS, const double* __restrict__ L, int64_t ldl, int NL, int P,
+    const double* __restrict__ nrm_s, const double* __restrict__ nrm_l, double neg_inv_sigma,
+    const double* __restrict__ W, int64_t ldw, int Q, double* __restrict__ out, int64_t ldo, int64_t split_stride,
+    int stiles, int nchunks, int nsplit, int ltiles, int64_t ntasks) {
+  __shared__ double etab[32];
+  if (threadIdx.x < 32) etab[threadIdx.x] = kExp2Tab32[threadIdx.x];
+  __syncthreads();
+  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w >= ntasks) return;
+  const int st = (int)(w % stiles);
+  const int cc = (int)((w / stiles) % nchunks);
+  const int sp = (int)(w / ((int64_t)stiles * nchunks));
+  const int s0 = st * 16 * KCW_MS, c0 = cc * 16 * KCW_CT;
+  const int t_begin = (int)((int64_t)ltiles * sp / nsplit), t_end = (int)((int64_t)ltiles * (sp + 1) / nsplit);
+  double* dst = out + (int64_t)sp * split_stride;
+  if (c0 + 16 * KCW_CT <= Q)
+    kcw_body<KS, true>(S, lds, NS, L, ldl, NL, P, nrm_s, nrm_l, neg_inv_sigma, W, ldw, Q, dst, ldo, s0, c0, t_begin, t_end, etab);
+  else   // (with resident fragments the partial body would spill: it re-reads them like KS == 0)
+    kcw_body<0, false>(S, lds, NS, L, ldl, NL, P, nrm_s, nrm_l, neg_inv_sigma, W, ldw, Q, dst, ldo, s0, c0, t_begin, t_end, etab);
+}
+
+// out (ns x q, ldo) = K(S, L) W for operands that are already centred, with their squared row norms: what
+// kernel_contract runs after centre_operands, and what an implicit kernel operator (KernelOp) runs at every product.
+// q <= 64: kernel_contract_kernel; q > 64: kernel_contract_wide_kernel in chunks of 128 columns, profiled under its own
+// name. (Measured against the narrow kernel at q = 128: DESIGN.md section 4.)
+int kernel_contract_centred(bigkrls_ctx* ctx, const double* S, int64_t ns, int64_t lds, const double* nrm_s,
+                            const double* L, int64_t nl, int64_t ldl, const double* nrm_l, int64_t p, double sigma,
+                            const double* W, int64_t q, int64_t ldw, double* out, int64_t ldo) {
+  BK_REQUIRE(ns > 0 && nl > 0 && p > 0 && q > 0, "kernel_contract: bad dimensions");
+  BK_REQUIRE(ns < (1ll << 31) && nl < (1ll << 31) && p < (1ll << 20) && q < (1ll << 20), "kernel_contract: too large");
+  BK_REQUIRE(sigma > 0.0, "kernel_contract: sigma must be > 0");
+  BK_REQUIRE(S && L && nrm_s && nrm_l && W && out, "kernel_contract: null pointer");
+  BK_REQUIRE(lds >= ns && ldl >= nl && ldw >= nl && ldo >= ns, "kernel_contract: leading dimension too small");
+  const bool wide = q > 64;
+  const int CT = wide ? KCW_CT : (q <= 16 ? 1 : (q <= 32 ? 2 : 4));
+  const int MS = wide ? KCW_MS : KC_MS;
+  const char* pname = wide ? "kernel_contract_wide" : "kernel_contract";
   const int steps = (int)((p + 3) / 4);
   const int ks = steps <= 8 ? steps : 0;
   using KcFn = void (*)(const double*, int64_t, int, const double*, int64_t, int, int, const double*, const double*,
@@ -2074,11 +2237,24 @@ int kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, c
     case 8: fn = kernel_contract_kernel<8, CTV>; break;                                                               \
     default: fn = kernel_contract_kernel<0, CTV>; break;                                                              \
   }
-  if (CT == 1) { BK_KCS(1) }
+  if (wide) {
+    switch (ks) {
+      case 1: fn = kernel_contract_wide_kernel<1>; break;
+      case 2: fn = kernel_contract_wide_kernel<2>; break;
+      case 3: fn = kernel_contract_wide_kernel<3>; break;
+      case 4: fn = kernel_contract_wide_kernel<4>; break;
+      case 5: fn = kernel_contract_wide_kernel<5>; break;
+      case 6: fn = kernel_contract_wide_kernel<6>; break;
+      case 7: fn = kernel_contract_wide_kernel<7>; break;
+      case 8: fn = kernel_contract_wide_kernel<8>; break;
+      default: fn = kernel_contract_wide_kernel<0>; break;
+    }
+  }
+  else if (CT == 1) { BK_KCS(1) }
   else if (CT == 2) { BK_KCS(2) }
   else { BK_KCS(4) }
 #undef BK_KCS
-  const int64_t stiles = (ns + 16 * KC_MS - 1) / (16 * KC_MS);
+  const int64_t stiles = (ns + 16 * MS - 1) / (16 * MS);
   const int64_t nchunks = (q + 16 * CT - 1) / (16 * CT);
   const int64_t ltiles = (nl + 15) / 16;
   // Loop splits against the wave slots the kernel can hold at once (2 or 3 per SIMD, by its registers): the time is
@@ -2110,7 +2286,7 @@ int kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, c
     split_stride = ns * q;
   }
   const dim3 grid((unsigned)((ntasks + 3) / 4));
-  BK_TRY(prof_begin(ctx, "kernel_contract", 2.0 * (double)u * (double)v * (double)(p + q)));
+  BK_TRY(prof_begin(ctx, pname, 2.0 * (double)ns * (double)nl * (double)(p + q)));
   hipLaunchKernelGGL(fn, grid, dim3(NT), 0, ctx->stream, S, lds, (int)ns, L, ldl, (int)nl, (int)p, nrm_s, nrm_l,
                      -1.0 / sigma, W, ldw, (int)q, dst, ldd, split_stride, (int)stiles, (int)nchunks, (int)nsplit,
                      (int)ltiles, ntasks);
@@ -2121,8 +2297,53 @@ int kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, c
                        (const double*)dst, out, ldo);
     BK_CHECK_LAUNCH();
   }
-  BK_TRY(prof_end(ctx, "kernel_contract"));
+  BK_TRY(prof_end(ctx, pname));
   return BIGKRLS_OK;
+}
+
+int kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
+                    int64_t ldb, int64_t p, double sigma, const double* W, int64_t q, int64_t ldw, int trans,
+                    double* out, int64_t ldo) {
+  BK_REQUIRE(u > 0 && v > 0 && p > 0 && q > 0, "kernel_contract: bad dimensions");
+  BK_REQUIRE(u < (1ll << 31) && v < (1ll << 31) && p < (1ll << 20) && q < (1ll << 20), "kernel_contract: too large");
+  BK_REQUIRE(trans == 0 || trans == 1, "kernel_contract: trans must be 0 or 1");
+  BK_REQUIRE(sigma > 0.0, "kernel_contract: sigma must be > 0");
+  BK_REQUIRE(A && B && W && out, "kernel_contract: null pointer");
+  BK_REQUIRE(lda >= u && ldb >= v, "kernel_contract: leading dimension of A or B too small");
+  // trans = 0: stationary rows A, loop rows B; trans = 1: the reverse
+  const int64_t ns = trans ? v : u, nl = trans ? u : v;
+  BK_REQUIRE(ldw >= nl && ldo >= ns, "kernel_contract: leading dimension of W or out too small");
+  CentredOperands co;     // both operands moved by the column means of A (see centre_operands)
+  BK_TRY(centre_operands(ctx, A, u, lda, B, v, ldb, p, &co));
+  if (trans)
+    return kernel_contract_centred(ctx, co.B, v, co.ldb, co.nb, co.A, u, co.lda, co.na, p, sigma, W, q, ldw, out, ldo);
+  return kernel_contract_centred(ctx, co.A, u, co.lda, co.na, co.B, v, co.ldb, co.nb, p, sigma, W, q, ldw, out, ldo);
+}
+
+// ---- the kernel matrix of one data set as an operator (kernel = "implicit": csrc/eigen.hip, csrc/fit.hip) -----------
+// The centred copy of X and its squared row norms live in slots of their own, so that they survive every other kernel
+// build or contraction of the context until the next kernel_op_prepare.
+int kernel_op_prepare(bigkrls_ctx* ctx, const double* X, int64_t n, int64_t ldx, int64_t p, double sigma, KernelOp* op) {
+  BK_REQUIRE(X && op && n > 0 && p > 0 && ldx >= n && n < (1ll << 31) && p < (1ll << 20), "kernel operator: bad arguments");
+  BK_REQUIRE(sigma > 0.0, "kernel operator: sigma must be > 0");
+  void *px = nullptr, *pn = nullptr, *psh = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_KOP_X, n * p * (int64_t)sizeof(double), &px));
+  BK_TRY(ws_get(ctx, SLOT_KOP_NORMS, n * (int64_t)sizeof(double), &pn));
+  BK_TRY(ws_get(ctx, SLOT_KB_SHIFT, p * sizeof(double), &psh));
+  BK_TRY(col_means(ctx, X, n, p, ldx, (double*)psh));
+  BK_TRY(shift_rows_sqnorms(ctx, X, n, p, ldx, (const double*)psh, (double*)px, (double*)pn));
+  op->Xc = (const double*)px;
+  op->nrm = (const double*)pn;
+  op->n = n;
+  op->p = p;
+  op->sigma = sigma;
+  return BIGKRLS_OK;
+}
+
+int kernel_op_times(bigkrls_ctx* ctx, const KernelOp& op, const double* W, int64_t q, int64_t ldw, double* out,
+                    int64_t ldo) {
+  return kernel_contract_centred(ctx, op.Xc, op.n, op.n, op.nrm, op.Xc, op.n, op.n, op.nrm, op.p, op.sigma, W, q, ldw,
+                                 out, ldo);
 }
 
 

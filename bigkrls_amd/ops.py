@@ -140,6 +140,26 @@ def bEigen(A: DeviceMatrix, Neig: Optional[int] = None, eigtrunc: float = 0.0,
                        values_dev=vals)
 
 
+def bEigenImplicit(X: DeviceMatrix, sigma: Optional[float] = None, Neig: int = 0, eigtrunc: float = 0.0) -> Eigenobject:
+    """bEigen of bGaussKernel(X, sigma) without the matrix (bigkrls_dev_eigen_implicit): block Lanczos whose products
+    with K are fused contractions over X. X is the standardised N x P data; needs N >= 1024 and 4 Neig <= N, and has no
+    dense fallback (a spectrum the iteration does not resolve is an error)."""
+    ctx = X.ctx
+    n, p = X.nrow, X.ncol
+    sigma = float(p) if sigma is None else float(sigma)
+    Neig = int(Neig)
+    if not (1 <= Neig <= n):
+        raise ValueError("bEigenImplicit: Neig out of range")
+    vals = ctx.empty(Neig, 1)
+    vecs = ctx.empty(n, Neig)
+    nv = C.c_int64(0)
+    _lib.call("bigkrls_dev_eigen_implicit", ctx.handle, X.ptr, n, X.ld, p, sigma, Neig, vals.ptr, Neig,
+              float(eigtrunc), vecs.ptr, vecs.ld, C.byref(nv))
+    lastkeeper = int(nv.value)
+    return Eigenobject(values=vals.to_numpy().ravel(), lastkeeper=lastkeeper, vectors=vecs.cols(0, lastkeeper),
+                       values_dev=vals)
+
+
 # ---------------------------------------------------------------------------
 # solveforc / lambda search   (R/bigKRLS_Rcpp_functions.R:5-95)
 # ---------------------------------------------------------------------------

@@ -189,6 +189,8 @@ def _bload(obj, path: str, noisy: bool, ctx: Optional[Context], to_device: bool)
         obj["which.derivatives"] = [int(i) for i in obj["which.derivatives"]]
     files = os.listdir(path)
     matrices = _BIGKRLS_MATRICES + _FACTOR_MATRICES if isinstance(obj, BigKRLS) else _PREDICTED_MATRICES   # :336-343
+    if isinstance(obj, BigKRLS) and obj.get("kernel") == "implicit":
+        obj.setdefault("K", None)         # bigKRLS(kernel="implicit") has no kernel matrix: no K.txt, and no NOTE about it
     for name in matrices:
         txt, npy = name + ".txt", name + ".npy"
         if txt not in files and npy not in files:

@@ -257,6 +257,15 @@ int bigkrls_dev_eigen_part(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t
                            int64_t n_vecs_max, double h_keep_thresh, double* vecs, int64_t ldv,
                            int64_t* h_n_vecs, int32_t part_index, int32_t part_count);
 
+/* The same for the Gaussian kernel matrix K(X, X) of X (device, n x p, ldx; bandwidth sigma) WITHOUT the matrix: block
+ * Lanczos whose products K B_j are fused contractions (the kernel tile is rebuilt in registers, never stored). Needs
+ * n >= 1024 and 4 n_vals <= n (BIGKRLS_EINVAL otherwise). There is no dense fallback: BIGKRLS_ENOCONV is returned. The
+ * operator's diagonal is exp(-max(d2, 0) / sigma) with d2 at rounding level, not the exact 1 of bigkrls_dev_kernel_block. */
+int bigkrls_dev_eigen_implicit(bigkrls_ctx* ctx, const double* X, int64_t n, int64_t ldx, int64_t p, double sigma,
+                               int64_t n_vals, double* vals,
+                               int64_t n_vecs_max, double h_keep_thresh, double* vecs, int64_t ldv,
+                               int64_t* h_n_vecs);
+
 /* p[0 .. count) (device) = uniform values in [-0.5, 0.5) that depend on the element index and the seed only: the
  * start block of the block Lanczos, the same on every rank (seed 20240229 is the single-GPU library's). */
 int bigkrls_dev_fill_random(bigkrls_ctx* ctx, double* p, int64_t count, uint32_t seed);
@@ -353,7 +362,11 @@ typedef struct bigkrls_fit_options {
   int32_t derivative;        /* marginal effects (step 5)                       :321                */
   int32_t vcov_est;          /* variance matrices; derivative != 0 requires it  :239                */
   int32_t acf;               /* also BigNeffective(X), only when p > 2          :192, :412-416      */
-  int32_t reserved;
+  int32_t kernel_form;       /* 0: K stored (n x n on the device); 1: implicit -- K is never stored, every product
+                                with it is a fused contraction that rebuilds its tiles from X. Implicit needs
+                                neig > 0 with n >= 1024 and 4 neig <= n (block Lanczos, no dense fallback), one
+                                GPU (bigkrls_fit only), d_K = d_vcov_c = d_vcov_fitted = NULL: the variance comes
+                                as factors (d_vcov_q, vcov_w) or not at all. Other values: BIGKRLS_EINVAL          */
   const int64_t* which_derivatives;  /* 1-based like R; NULL: all columns       :206-215, :326      */
   int64_t n_which;
 } bigkrls_fit_options;
