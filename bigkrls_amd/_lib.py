@@ -98,6 +98,7 @@ SIGNATURES = {
     "bigkrls_dev_quadform_diag": [vp, i64, i64, vp, i64, vp, i64, vp],
     "bigkrls_dev_rowsumsq_weighted": [vp, i64, i64, vp, i64, vp, vp],
     "bigkrls_dev_gemm": [vp, C.c_int, C.c_int, i64, i64, i64, f64, vp, i64, vp, i64, f64, vp, i64],
+    "bigkrls_dev_gemm_modulated": [vp, i64, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, i64],
     "bigkrls_dev_multdiag": [vp, vp, i64, i64, i64, vp, vp, i64],
     "bigkrls_dev_eigen": [vp, vp, i64, i64, i64, vp, i64, f64, vp, i64, pi64],
     "bigkrls_dev_eigen_part": [vp, vp, i64, i64, i64, vp, i64, f64, vp, i64, pi64, i32, i32],
@@ -127,6 +128,7 @@ SIGNATURES = {
     "bigkrls_marginal_effects": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, vp, vp, vp, vp],
     "bigkrls_marginal_effects_factored": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, vp, i64, i64, vp, vp, vp,
                                           vp],
+    "bigkrls_marginal_effects_se": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, vp, vp, i64, i64, vp, i64, vp],
     # multi-GPU
     "bigkrls_comm_unique_id": [vp],
     "bigkrls_comm_create": [vp, i32, i32, vp, C.POINTER(vp)],

@@ -595,7 +595,7 @@ def _predict_factored(object, ctx, Xh, nd, nd_init, yv, coeffs, ypred, correct_S
 
 
 def marginal_effects(object: BigKRLS, newdata, which_derivatives=None, ctx: Optional[Context] = None,
-                     vcov: Optional[str] = None) -> dict:
+                     vcov: Optional[str] = None, se: bool = False, _block_rows: int = 0) -> dict:
     """Marginal effects of a fitted model at new data points, without refitting: the pointwise derivatives
     (u x |J|), their averages (1 x |J|) and the variances of the averages (1 x |J|; None when the object has no
     vcov.est.c), in the original units and with the fit's definitions -- with newdata = X they are the fit's
@@ -605,10 +605,21 @@ def marginal_effects(object: BigKRLS, newdata, which_derivatives=None, ctx: Opti
     marginal effects at the training rows only, R/bigKRLS.R:318-407). The numeric body is ONE call into the C ABI,
     `bigkrls_marginal_effects`, which never forms the u x n test kernel. `vcov` chooses the form of vcov.est.c the
     variances come from, as in predict(): from the factors (`bigkrls_marginal_effects_factored`) the variance step is
-    the fit's own sum_k w_k (q_k's)^2, and a multi-GPU object that carries them is accepted."""
+    the fit's own sum_k w_k (q_k's)^2, and a multi-GPU object that carries them is accepted.
+
+    se=True adds "se.derivatives" (u x |J|, the columns of "derivatives"): the standard error of every pointwise
+    derivative, sqrt(g' vcov.est.c g) / sd(x_j) for the weights g with derivative = g'c, from the same form of vcov.est.c
+    as "var.avgderivatives" (a second call, `bigkrls_marginal_effects_se`; everything else in the result is bitwise
+    what se=False returns). Binary columns carry the reference's factor 2 on the variance, as var.avgderivatives does,
+    so for a single new point se.derivatives[0, j]**2 == var.avgderivatives[0, j] in every column. The factors are the
+    fast form: 2 u n lastkeeper flops per column against 2 u n^2 from the matrix; the new points are taken in row blocks
+    of at most 1 GiB of test kernel either way. Raises the ValueError of predict(se_pred=True) when the object carries
+    neither form. With se=False the result has exactly the keys it always had."""
     if not isinstance(object, BigKRLS):
         raise TypeError("Object not of class 'bigKRLS'")
     form = _vcov_choice(object, vcov)
+    if se and form is None:
+        raise ValueError("recompute bigKRLS object with bigKRLS(,vcov.est=TRUE) to compute standard errors")
     if ("vcov.est.c.cols" in object or "rows" in object) and form != "factors":
         raise NotImplementedError("marginal_effects of a multi-GPU fit (sharded vcov.est.c.cols) is not supported; "
                                   "refit on one GPU or with vcov_form=\"factors\"")
@@ -659,10 +670,19 @@ def marginal_effects(object: BigKRLS, newdata, which_derivatives=None, ctx: Opti
                      Vd.ptr if Vd is not None else None, D.ctypes.data, avg.ctypes.data,
                      var.ctypes.data if var is not None else None)
     xlabs = list(object.get("xlabs") or [f"x{i + 1}" for i in range(p)])
-    return {"derivatives": D, "avgderivatives": avg[None, :],
-            "var.avgderivatives": None if var is None else var[None, :],
-            "which.derivatives": which, "binaryindicator": isbin[which_arr - 1],
-            "xlabs": [xlabs[i - 1] for i in which], "newdata": nd_init}
+    out = {"derivatives": D, "avgderivatives": avg[None, :],
+           "var.avgderivatives": None if var is None else var[None, :],
+           "which.derivatives": which, "binaryindicator": isbin[which_arr - 1],
+           "xlabs": [xlabs[i - 1] for i in which], "newdata": nd_init}
+    if se:
+        sed = np.empty((u, nj), dtype=np.float64, order="F")
+        _call_native("bigkrls_marginal_effects_se", ctx.handle, Xh.ctypes.data, n, p, yv.ctypes.data,
+                     coeffs.ctypes.data, float(object["sigma"]), which_arr.ctypes.data, nj, nd.ctypes.data, u,
+                     Vd.ptr if form == "dense" else None, Qd.ptr if form == "factors" else None,
+                     Qd.ld if form == "factors" else 0, Qd.ncol if form == "factors" else 0,
+                     wv.ctypes.data if form == "factors" else None, int(_block_rows), sed.ctypes.data)
+        out["se.derivatives"] = sed
+    return out
 
 
 def _run_folds(jobs, contexts, fit_fn, predict_fn):

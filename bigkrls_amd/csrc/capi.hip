@@ -545,6 +545,13 @@ int bigkrls_dev_gemm(bigkrls_ctx* ctx, int ta, int tb, int64_t m, int64_t n, int
   return gemm(ctx, ta, tb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc);
 }
 
+int bigkrls_dev_gemm_modulated(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda,
+                               const double* r, const double* t, const double* s, const double* B, int64_t ldb,
+                               double* C, int64_t ldc) {
+  BK_TRY(check_ctx(ctx));
+  return gemm_modulated(ctx, m, n, k, A, lda, r, t, s, B, ldb, C, ldc);
+}
+
 int bigkrls_dev_multdiag(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t k, int64_t lda,
                          const double* diag, double* out, int64_t ldo) {
   BK_TRY(check_ctx(ctx));

@@ -192,9 +192,10 @@ enum Slot {
   SLOT_EIG_FLAGS = 42,     // completion flags of the persistent stage-2 back-transform's tasks
   SLOT_FIT_VERIFY = 43,    // the fit's check of a decomposition against K: Q r, Q (lambda o r), K Q r
   SLOT_CONTRACT_PART = 44, // kernel_contract: partial sums of the loop splits
-  SLOT_ME_SMALL = 45,      // bigkrls_marginal_effects: standardised X and newdata, operands, products, D, S, V S
+  SLOT_ME_SMALL = 45,      // bigkrls_marginal_effects(_se): standardised X and newdata, operands, products, D, S, V S / r, t, s, se^2
   SLOT_PP_SMALL = 46,      // bigkrls_predict_pointwise: standardised X, c, one block of newdata, yhat, diag
-  SLOT_PP_K = 47,          // ... one row block of the test kernel, and its product with Q where the variance comes as factors (at most 1 GiB)
+  SLOT_PP_K = 47,          // ... one row block of the test kernel, and its product with Q where the variance comes as factors (at most 1 GiB);
+                           //     bigkrls_marginal_effects_se: the same block and product, or the block and its modulated copy
   SLOT_QF_PART = 48,       // quadform_diag: one partial per row, column tile and k split
   SLOT_KB_SHIFT = 49,      // kernel_block / kernel_contract: the common shift of both operands (P doubles: column means of A)
   SLOT_KB_A = 50,          // ... the shifted copy of A (u x P)
@@ -260,12 +261,24 @@ class PinnedStage {
 int gemm(bigkrls_ctx* ctx, int ta, int tb, int64_t m, int64_t n, int64_t k, double alpha,
          const double* A, int64_t lda, const double* B, int64_t ldb, double beta, double* C,
          int64_t ldc);
+// C (m x n, ldc) = (A o (r 1' + t s')) B: A m x k (lda) and B k x n (ldb) not transposed, r and t m entries, s k entries,
+// all on the device; C is overwritten. A is modulated in registers on its way to LDS, the modulated copy never stored.
+// gemm()'s tiles and deterministic split-K choice; with r = 1, t = 0 bitwise gemm(0, 0, .., 1.0, .., 0.0, ..).
+int gemm_modulated(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* r,
+                   const double* t, const double* s, const double* B, int64_t ldb, double* C, int64_t ldc);
 // C (m x n, n <= 48) = A (m x k) B (k x n), both not transposed: the 128 x 48 tile of the marginal-effects pass
 int gemm_nn_skinny48(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* B,
                      int64_t ldb, double* C, int64_t ldc);
 int kernel_block(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B,
                  int64_t v, int64_t ldb, int64_t p, double sigma, double* out, int64_t ldo,
                  int64_t diag_shift);
+// kernel_block's launch for operands that are already centred (one common shift) and come with their squared row
+// norms na (u) and nb (v); validated by the caller. sym: A and B are the same rows and the build is the symmetric one.
+// Every entry depends on its own two rows only, so a row block of A gives bitwise the rows of the whole build as long
+// as both take the same kernel (they do while v < 1024).
+int kernel_block_centred(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* na, const double* B,
+                         int64_t v, int64_t ldb, const double* nb, int64_t p, double sigma, double* out, int64_t ldo,
+                         int64_t diag_shift, bool sym = false);
 
 // trans = 0: out (u x q, ldo) = K(A, B) W with W v x q; trans = 1: out (v x q, ldo) = K(A, B)' W with W u x q.
 // K(A, B) is kernel_block's kernel (diag_shift = -1), rebuilt tile by tile in registers and never stored.

@@ -1133,12 +1133,6 @@ int predict_whole(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, con
   return predict_finish(ctx, dpred, u, want_se, pin, tm, h_predicted, h_se_pred);
 }
 
-// rows per block of the pointwise entries (include/bigkrls.h): the largest multiple of 128 whose b x (n + k) doubles
-// -- the test-kernel block, and beside it its product with the k factor columns -- fit 1 GiB, at least 128
-int64_t pointwise_block_rows(int64_t n, int64_t k) {
-  return std::max<int64_t>(128, ((1ll << 30) / ((n + k) * (int64_t)sizeof(double))) / 128 * 128);
-}
-
 // bigkrls_predict_pointwise / bigkrls_predict_factored without device outputs: bigkrls_predict's validation and
 // standardisation; then row blocks of b new points: kernel_block, gemv, and for the SEs the one entry of vcov.est.pred
 // per point that se.pred needs -- diag(Kn_b vcov.est.c Kn_b') (quadform_diag), or from the factors T = Kn_b Q (gemm)

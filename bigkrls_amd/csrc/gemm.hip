@@ -154,12 +154,22 @@ struct GemmOperands {
   const int* run_if = nullptr;  // optional device-side predicate (plain GEMM kernels only): nothing is done while *run_if == 0
 };
 
+// Optional modulation of a not-transposed A operand on its way to LDS (gemm_tile<.., MOD = true>, gemm_modulated):
+// op(A)(m, k) = A(m, k) (r[m] + t[m] s[k]); r and t have M entries, s has K.
+struct GemmMod {
+  const double* r;
+  const double* t;
+  const double* s;
+};
+
 // Computes the accumulators of the (m0, n0) block tile over k in [kbeg, kend).
 // TA/TB: operand is used transposed (op(A) = A' with A stored K x M, etc.).
-template <bool TA, bool TB, int BN, bool GATHER = false, bool DEEP = false>
+// MOD: the A operand is modulated (GemmMod) between its staging registers and LDS; off, `mod` is never read.
+template <bool TA, bool TB, int BN, bool GATHER = false, bool DEEP = false, bool MOD = false>
 __device__ __forceinline__ void gemm_tile(const GemmOperands& g, int m0, int n0, int kbeg,
                                           int kend, double* __restrict__ smem,
-                                          d4 (&acc)[4][BN / 32]) {
+                                          d4 (&acc)[4][BN / 32], const GemmMod* mod = nullptr) {
+  static_assert(!MOD || (!TA && !GATHER), "gemm_tile: the modulated A operand is not transposed and not gathered");
   constexpr int NJ = BN / 32;
   // A tile: op(A)(m,k). not transposed: A[m + k lda] -> contiguous along m.
   constexpr bool A_CONTIG = !TA;
@@ -215,12 +225,47 @@ __device__ __forceinline__ void gemm_tile(const GemmOperands& g, int m0, int n0,
     sb = 16 * g.ldb;
     ib = BK;
   }
+  // Modulated A (m-contiguous: this thread stages row m0 + tid % BM at the k rows tid / BM + (NT / BM) q of every
+  // k-tile): r and t of its row live in two registers; the tile's s values are loaded together with the tile (the same
+  // address over a wave: cached broadcast loads), clamped like the tile's own addresses, and the factor is applied in
+  // registers just before the LDS store (mod_apply) -- nothing sits between the global loads and the MFMAs.
+  constexpr int MQ = MOD ? BM / 16 : 1;
+  double mod_r = 0.0, mod_t = 0.0;
+  const double* ps = nullptr;
+  double rs[MQ];
+  if (MOD) {
+    const int gx = m0 + tid % BM;
+    const int gc = gx < g.M ? gx : g.M - 1;
+    mod_r = mod->r[gc];
+    mod_t = mod->t[gc];
+    ps = mod->s + kbeg + tid / BM;
+  }
+  auto mod_load = [&](int k0, double (&xs)[MQ]) {
+    constexpr int KS = NT / BM;
+    if (k0 + BK <= kend) {
+#pragma unroll
+      for (int q = 0; q < MQ; ++q) xs[q] = ps[q * KS];
+    } else {
+      const int kb = k0 + tid / BM;
+#pragma unroll
+      for (int q = 0; q < MQ; ++q) {
+        const int gk = kb + q * KS;
+        xs[q] = mod->s[gk < kend ? gk : kend - 1];
+      }
+    }
+    ps += BK;
+  };
+  auto mod_apply = [&](double (&xa)[BM / 16], const double (&xs)[MQ]) {
+#pragma unroll
+    for (int q = 0; q < MQ; ++q) xa[q] *= fma(mod_t, xs[q], mod_r);
+  };
   auto load_tiles = [&](int k0) {
     const bool full = k0 + BK <= kend;
     if (full && a_fast) tile_load_strided<BM>(pa, sa, ra);
     else tile_load<A_CONTIG, BM, GATHER>(g.A, g.lda, m0, k0, g.M, kend, ra, g.kidx);
     if (full && b_fast) tile_load_strided<BN>(pb, sb, rb);
     else tile_load<B_CONTIG, BN>(g.B, g.ldb, n0, k0, g.N, kend, rb);
+    if constexpr (MOD) mod_load(k0, rs);
     pa += ia;
     pb += ib;
   };
@@ -250,16 +295,19 @@ __device__ __forceinline__ void gemm_tile(const GemmOperands& g, int m0, int n0,
     // would have to hide.
     double ra2[BM / 16];
     double rb2[BN / 16];
-    auto load_into = [&](int k0, double (&xa)[BM / 16], double (&xb)[BN / 16]) {
+    double rs2[MQ];
+    auto load_into = [&](int k0, double (&xa)[BM / 16], double (&xb)[BN / 16], double (&xs)[MQ]) {
       const bool full = k0 + BK <= kend;
       if (full && a_fast) tile_load_strided<BM>(pa, sa, xa);
       else tile_load<A_CONTIG, BM, GATHER>(g.A, g.lda, m0, k0, g.M, kend, xa, g.kidx);
       if (full && b_fast) tile_load_strided<BN>(pb, sb, xb);
       else tile_load<B_CONTIG, BN>(g.B, g.ldb, n0, k0, g.N, kend, xb);
+      if constexpr (MOD) mod_load(k0, xs);
       pa += ia;
       pb += ib;
     };
-    auto stage = [&](int k0, int st, double (&xa)[BM / 16], double (&xb)[BN / 16]) {
+    auto stage = [&](int k0, int st, double (&xa)[BM / 16], double (&xb)[BN / 16], const double (&xs)[MQ]) {
+      if constexpr (MOD) mod_apply(xa, xs);
       if (k0 + BK > kend) {
         tile_zero_ktail<A_CONTIG, BM>(k0, kend, xa);
         tile_zero_ktail<B_CONTIG, BN>(k0, kend, xb);
@@ -267,27 +315,28 @@ __device__ __forceinline__ void gemm_tile(const GemmOperands& g, int m0, int n0,
       tile_store<A_CONTIG, BM>(smem + st * A_STAGE, xa);
       tile_store<B_CONTIG, BN>(smem + B_BASE + st * B_STAGE, xb);
     };
-    load_into(kbeg, ra, rb);
-    stage(kbeg, 0, ra, rb);
-    if (ntiles > 1) load_into(kbeg + BK, ra2, rb2);
+    load_into(kbeg, ra, rb, rs);
+    stage(kbeg, 0, ra, rb, rs);
+    if (ntiles > 1) load_into(kbeg + BK, ra2, rb2, rs2);
     __syncthreads();
     for (int t = 0; t < ntiles; t += 2) {
       // even tile t: LDS stage 0; tile t+1 waits in (ra2, rb2); tile t+2 loads into (ra, rb)
-      if (t + 2 < ntiles) load_into(kbeg + (t + 2) * BK, ra, rb);
+      if (t + 2 < ntiles) load_into(kbeg + (t + 2) * BK, ra, rb, rs);
       mfma_tile(0);
-      if (t + 1 < ntiles) stage(kbeg + (t + 1) * BK, 1, ra2, rb2);
+      if (t + 1 < ntiles) stage(kbeg + (t + 1) * BK, 1, ra2, rb2, rs2);
       __syncthreads();
       if (t + 1 >= ntiles) break;
       // odd tile t+1: LDS stage 1; tile t+2 waits in (ra, rb); tile t+3 loads into (ra2, rb2)
-      if (t + 3 < ntiles) load_into(kbeg + (t + 3) * BK, ra2, rb2);
+      if (t + 3 < ntiles) load_into(kbeg + (t + 3) * BK, ra2, rb2, rs2);
       mfma_tile(1);
-      if (t + 2 < ntiles) stage(kbeg + (t + 2) * BK, 0, ra, rb);
+      if (t + 2 < ntiles) stage(kbeg + (t + 2) * BK, 0, ra, rb, rs);
       __syncthreads();
     }
     return;
   }
 
   load_tiles(kbeg);
+  if constexpr (MOD) mod_apply(ra, rs);
   if (kbeg + BK > kend) {
     tile_zero_ktail<A_CONTIG, BM>(kbeg, kend, ra);
     tile_zero_ktail<B_CONTIG, BN>(kbeg, kend, rb);
@@ -302,6 +351,7 @@ __device__ __forceinline__ void gemm_tile(const GemmOperands& g, int m0, int n0,
     if (t + 1 < ntiles) load_tiles(k0);
     mfma_tile(cur);
     if (t + 1 < ntiles) {
+      if constexpr (MOD) mod_apply(ra, rs);
       if (k0 + BK > kend) {  // partial last tile: k rows past the end must contribute zeros
         tile_zero_ktail<A_CONTIG, BM>(k0, kend, ra);
         tile_zero_ktail<B_CONTIG, BN>(k0, kend, rb);
@@ -456,12 +506,10 @@ __global__ void splitk_reduce_kernel(const double* __restrict__ partial, int spl
   }
 }
 
+// The deterministic split-K choice of the plain GEMM kernels of one tile width (launch_gemm, launch_gemm_modulated):
+// the number of k slabs and the slab length, a multiple of BK.
 template <bool TA, bool TB, int BN>
-static int launch_gemm(bigkrls_ctx* ctx, const GemmOperands& g, double alpha, double beta,
-                       double* C, int64_t ldc) {
-  const int tiles_m = (g.M + BM - 1) / BM;
-  const int tiles_n = (g.N + BN - 1) / BN;
-  const int ntile = tiles_m * tiles_n;
+static void gemm_split_plan(const GemmOperands& g, int ntile, int* splits_out, int* k_chunk_out) {
   // split-K when the tile grid does not fill whole rounds of the GPU and K is long
   // The split count is chosen against the 512 workgroups the GPU holds at once (two per CU):
   // ntile * splits workgroups take ceil(ntile * splits / 512) rounds of K / splits k-steps each, plus
@@ -495,14 +543,33 @@ static int launch_gemm(bigkrls_ctx* ctx, const GemmOperands& g, double alpha, do
   if (k_chunk < BK) k_chunk = BK;
   splits = (g.K + k_chunk - 1) / k_chunk;
   if (splits < 1) splits = 1;
-  double* partial = nullptr;
+  *splits_out = splits;
+  *k_chunk_out = k_chunk;
+}
+
+// the slabs of the split-K partials (splits x M x N doubles); nullptr for a single split
+static int gemm_split_partials(bigkrls_ctx* ctx, const GemmOperands& g, int splits, double** partial) {
+  *partial = nullptr;
   if (splits > 1) {
     void* p = nullptr;
     // GEMMs issued on the look-ahead stream run concurrently with main-stream GEMMs: own partial buffer
     const int slot = (ctx->side_stream && (ctx->stream == ctx->side_stream || ctx->stream == ctx->bg_stream)) ? SLOT_SIDE_SPLITK : SLOT_GEMM_SPLITK;
     BK_TRY(ws_get(ctx, slot, (int64_t)splits * g.M * g.N * sizeof(double), &p));
-    partial = (double*)p;
+    *partial = (double*)p;
   }
+  return BIGKRLS_OK;
+}
+
+template <bool TA, bool TB, int BN>
+static int launch_gemm(bigkrls_ctx* ctx, const GemmOperands& g, double alpha, double beta,
+                       double* C, int64_t ldc) {
+  const int tiles_m = (g.M + BM - 1) / BM;
+  const int tiles_n = (g.N + BN - 1) / BN;
+  const int ntile = tiles_m * tiles_n;
+  int splits = 1, k_chunk = BK;
+  gemm_split_plan<TA, TB, BN>(g, ntile, &splits, &k_chunk);
+  double* partial = nullptr;
+  BK_TRY(gemm_split_partials(ctx, g, splits, &partial));
   auto kern = gemm_kernel<TA, TB, BN>;
   constexpr size_t smem = gemm_smem_bytes<TA, TB, BN>();
   BK_TRY(ensure_dyn_smem(ctx, (const void*)kern, smem));
@@ -558,6 +625,91 @@ int gemm(bigkrls_ctx* ctx, int ta, int tb, int64_t m, int64_t n, int64_t k, doub
   if (n <= 32) return dispatch_trans<32>(ctx, ta, tb, g, alpha, beta, C, ldc);
   if (n <= 64) return dispatch_trans<64>(ctx, ta, tb, g, alpha, beta, C, ldc);
   return dispatch_trans<128>(ctx, ta, tb, g, alpha, beta, C, ldc);
+}
+
+// ---------------------------------------------------------------------------
+// C (M x N) = (A o (r 1' + t s')) B, A and B not transposed: the plain N,N kernel of the same width with A modulated
+// on its way to LDS (gemm_tile<.., MOD>), so the modulated copy of A -- G_j = Kn o (r 1' + t s') of the pointwise
+// standard errors of the marginal effects, csrc/margeff.hip -- is never written. Same tiles, same occupancy, same k
+// pipeline and same split-K choice as gemm_kernel<false, false, BN>; the product is linear in the modulated operand,
+// so the splits' partials add in slab order as before (splitk_reduce_kernel: no atomics, bitwise reproducible).
+// With r = 1, t = 0 the factor is exactly 1 and the result is bitwise gemm()'s.
+// ---------------------------------------------------------------------------
+template <int BN>
+__global__ __launch_bounds__(NT, (gemm_occ<false, false, BN>())) void gemm_modulated_kernel(
+    GemmOperands g, GemmMod mod, double* __restrict__ C, int64_t ldc, int tiles_m, int tiles_n, int k_chunk,
+    double* __restrict__ partial) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int ntile = tiles_m * tiles_n;
+  const int tid = xcd_remap(blockIdx.x, ntile);
+  const int tm = tid % tiles_m, tn = tid / tiles_m;
+  const int m0 = tm * BM, n0 = tn * BN;
+  const int z = blockIdx.y;
+  const int kbeg = z * k_chunk;
+  const int kend = min(g.K, kbeg + k_chunk);
+  d4 acc[4][BN / 32];
+  gemm_tile<false, false, BN, false, (BN <= GEMM_DEEP_BN && gemm_occ<false, false, BN>() <= GEMM_OCC), true>(
+      g, m0, n0, kbeg, kend, smem, acc, &mod);
+  const int M = g.M, N = g.N;
+  if (partial != nullptr) {
+    double* P = partial + (int64_t)z * M * N;
+    acc_foreach<BN>(acc, m0, n0, [&](int m, int n, double v) {
+      if (m < M && n < N) P[(int64_t)m + (int64_t)n * M] = v;
+    });
+  } else {
+    acc_foreach<BN>(acc, m0, n0, [&](int m, int n, double v) {
+      if (m < M && n < N) C[(int64_t)m + (int64_t)n * ldc] = v;
+    });
+  }
+}
+
+template <int BN>
+static int launch_gemm_modulated(bigkrls_ctx* ctx, const GemmOperands& g, const GemmMod& mod, double* C, int64_t ldc) {
+  const int tiles_m = (g.M + BM - 1) / BM;
+  const int tiles_n = (g.N + BN - 1) / BN;
+  const int ntile = tiles_m * tiles_n;
+  int splits = 1, k_chunk = BK;
+  gemm_split_plan<false, false, BN>(g, ntile, &splits, &k_chunk);
+  double* partial = nullptr;
+  BK_TRY(gemm_split_partials(ctx, g, splits, &partial));
+  auto kern = gemm_modulated_kernel<BN>;
+  constexpr size_t smem = gemm_smem_bytes<false, false, BN>();
+  BK_TRY(ensure_dyn_smem(ctx, (const void*)kern, smem));
+  hipLaunchKernelGGL(kern, dim3(ntile, splits), dim3(NT), smem, ctx->stream, g, mod, C, ldc, tiles_m, tiles_n, k_chunk,
+                     partial);
+  BK_CHECK_LAUNCH();
+  if (splits > 1) {
+    const int64_t total = (int64_t)g.M * g.N;
+    const int blocks = (int)std::min<int64_t>((total + 255) / 256, 2048);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, partial, splits, g.M, g.N, 1.0,
+                       0.0, C, ldc, (const int*)nullptr);
+    BK_CHECK_LAUNCH();
+  }
+  return BIGKRLS_OK;
+}
+
+int gemm_modulated(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* r,
+                   const double* t, const double* s, const double* B, int64_t ldb, double* C, int64_t ldc) {
+  BK_REQUIRE(m >= 0 && n >= 0 && k >= 0, "gemm_modulated: negative dimension");
+  BK_REQUIRE(m < (1ll << 31) && n < (1ll << 31) && k < (1ll << 31), "gemm_modulated: dimension too large");
+  if (m == 0 || n == 0) return BIGKRLS_OK;
+  BK_REQUIRE(C && ldc >= m, "gemm_modulated: null C or ldc < m");
+  if (k == 0) {   // empty sum
+    const int blocks = (int)std::min<int64_t>((m * n + 255) / 256, 2048);
+    hipLaunchKernelGGL(scale_matrix_kernel, dim3(blocks), dim3(256), 0, ctx->stream, C, ldc, (int)m, (int)n, 0.0);
+    BK_CHECK_LAUNCH();
+    return BIGKRLS_OK;
+  }
+  BK_REQUIRE(A && B && r && t && s, "gemm_modulated: null pointer");
+  BK_REQUIRE(lda >= m && ldb >= k, "gemm_modulated: leading dimension of A or B too small");
+  const GemmOperands g{A, B, lda, ldb, (int)m, (int)n, (int)k, nullptr};
+  const GemmMod mod{r, t, s};
+  BK_TRY(prof_begin(ctx, "gemm_modulated", 2.0 * (double)m * (double)n * (double)k));
+  if (n <= 32) BK_TRY(launch_gemm_modulated<32>(ctx, g, mod, C, ldc));
+  else if (n <= 64) BK_TRY(launch_gemm_modulated<64>(ctx, g, mod, C, ldc));
+  else BK_TRY(launch_gemm_modulated<128>(ctx, g, mod, C, ldc));
+  BK_TRY(prof_end(ctx, "gemm_modulated"));
+  return BIGKRLS_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -1769,8 +1921,12 @@ int kernel_block(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, cons
   // from here on A and B are the centred copies (the same buffer when they were the same buffer)
   CentredOperands co;
   BK_TRY(centre_operands(ctx, A, u, lda, B, v, ldb, p, &co));
-  A = co.A; lda = co.lda; B = co.B; ldb = co.ldb;
-  const double *pna = co.na, *pnb = co.nb;
+  return kernel_block_centred(ctx, co.A, u, co.lda, co.na, co.B, v, co.ldb, co.nb, p, sigma, out, ldo, diag_shift, sym);
+}
+
+int kernel_block_centred(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* pna, const double* B,
+                         int64_t v, int64_t ldb, const double* pnb, int64_t p, double sigma, double* out, int64_t ldo,
+                         int64_t diag_shift, bool sym) {
   // one workgroup per 128 x 128 tile with the X panels in LDS where it beats the one-wave-per-32x32 kernels: P > 32
   // (measured, TFLOP/s tiled vs wave: N = 100 000, P = 50: 44.7 vs 38.5; N = 30 000, P = 50: 37.2 vs 33.9;
   //  N = 50 000, P = 20: 21.1 vs 20.7; N = 20 000, P = 20: 17.8 vs 19.9; BIGKRLS_KB=wave|tiled forces either)

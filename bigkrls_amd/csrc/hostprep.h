@@ -73,4 +73,11 @@ static inline void standardise_column(const double* src, int64_t rows, double me
   for (int64_t i = 0; i < rows; ++i) dst[i] = (src[i] - mean) / sd;
 }
 
+// rows per block of the pointwise entries (include/bigkrls.h): the largest multiple of 128 whose b x (n + k) doubles
+// -- the test-kernel block, and beside it its product with the k factor columns (or, k = n, a second block) -- fit
+// 1 GiB, at least 128
+static inline int64_t pointwise_block_rows(int64_t n, int64_t k) {
+  return std::max<int64_t>(128, ((1ll << 30) / ((n + k) * (int64_t)sizeof(double))) / 128 * 128);
+}
+
 }  // namespace bk

@@ -20,6 +20,18 @@
 // and column dots, or -- bigkrls_marginal_effects_factored, V = Q diag(w) Q' given by its factors -- sum_k w_k (q_k'S_j)^2
 // (deriv_var, what the fit itself does); the two entries differ in that step only.
 // Device memory: O((u + n)(p + q)) plus the loop splits' partials, never O(u n).
+//
+// bigkrls_marginal_effects_se(): the standard error of every D[i,j]. D[i,j] = g_ij' c is linear in c with the weights
+//   g_ij[k] = Kn[i,k] (r_i + t_i s_k)
+//   continuous j: s_k = Xs_kj, r_i = -(2/sigma) Zs_ij, t_i = 2/sigma
+//   binary j:     s_k = b_k;  h_i = 1: r_i = sd (1 - 1/E), t_i = sd (1/E - E);  h_i = 0: r_i = -sd (1 - E), t_i = sd (1/E - E)
+//                 (sd = 1/(z1 - z0); me_rows_kernel's sd (+-1) ((1 - E) Sc + (1 - 1/E) Oc) written per training row)
+// so Var(D[i,j]) = g_ij' V g_ij = sum_m w_m ((G_j Q)[i,m])^2 with G_j = Kn o (r 1' + t s') and V = Q diag(w) Q'. The new
+// points go in row blocks of the test kernel (at most 1 GiB, predict_blocks' rule, csrc/fit.hip); per block Kn_b is built
+// once and per column T = G_j Q comes from gemm_modulated (csrc/gemm.hip: G_j is never stored) and rowsumsq_weighted
+// writes column j of the result. With V as the n x n matrix G_j is stored beside the block and quadform_diag gives the
+// diagonal (2 u n^2 flops per column instead of 2 u n k). Original units: se = sqrt(f_j var) / sd(x_j), f_j = 2 for
+// binary columns (the reference's factor, as in var_j above): at u = 1, se^2 is var_j.
 #include "hostprep.h"
 
 #include <cstring>
@@ -101,20 +113,88 @@ __global__ __launch_bounds__(256) void me_coldot_kernel(int n, const double* __r
   if (threadIdx.x == 0) out[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
-// both entries: vcov.est.c as the n x n matrix, as its factors, or not at all (no variances) -- Vcov, common.h
-int marginal_effects_impl(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
-                          const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
-                          const double* h_newdata, int64_t u, const Vcov& vc, double* h_derivatives, double* h_avg,
-                          double* h_var) {
+// ---- pointwise standard errors ---------------------------------------------------------------------------------------
+// S (n x nj, ld n): s of every selected column -- Xs_kj, or the training group indicator (Xs == z1, as me_cols_kernel)
+__global__ void me_se_s_kernel(int n, int nj, const double* __restrict__ Xs, const MeCol* __restrict__ cols,
+                               double* __restrict__ S) {
+  const int64_t total = (int64_t)n * nj;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int k = (int)(e % n);
+    const MeCol cj = cols[e / n];
+    const double x = Xs[k + (int64_t)cj.col * n];
+    S[e] = cj.bin == 0.0 ? x : (x == cj.z1 ? 1.0 : 0.0);
+  }
+}
+
+// R, T (rows x nj, ld rows): r and t of one block of new points (Zs: the block's first row, ld ldz). The group of a new
+// point in a binary column is Zs == z1: newdata holds one of the two training values there (validated) and is
+// standardised by the expression that gives z1.
+__global__ void me_se_rt_kernel(int rows, int nj, const double* __restrict__ Zs, int64_t ldz,
+                                const MeCol* __restrict__ cols, double sigma, double* __restrict__ R,
+                                double* __restrict__ T) {
+  const int64_t total = (int64_t)rows * nj;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int i = (int)(e % rows);
+    const MeCol cj = cols[e / rows];
+    const double z = Zs[i + (int64_t)cj.col * ldz];
+    double r, t;
+    if (cj.bin == 0.0) {
+      r = (-2.0 / sigma) * z;
+      t = 2.0 / sigma;
+    } else {
+      const double sd = 1.0 / (cj.z1 - cj.z0);
+      const double phi = -1.0 / (sd * sd * sigma);
+      const double E = exp(phi), Einv = exp(-phi);
+      r = z == cj.z1 ? sd * (1.0 - Einv) : -sd * (1.0 - E);
+      t = sd * (Einv - E);
+    }
+    R[e] = r;
+    T[e] = t;
+  }
+}
+
+// G (rows x n, ld rows) = Kn o (r 1' + t s'), the factor as gemm_modulated forms it (dense vcov.est.c only)
+__global__ void me_se_modulate_kernel(int rows, int n, const double* __restrict__ Kn, const double* __restrict__ r,
+                                      const double* __restrict__ t, const double* __restrict__ s,
+                                      double* __restrict__ G) {
+  const int64_t total = (int64_t)rows * n;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int i = (int)(e % rows);
+    const int k = (int)(e / rows);
+    G[e] = Kn[e] * fma(t[i], s[k], r[i]);
+  }
+}
+
+// ---- what the entries share on the host ---------------------------------------------------------------------------------
+int me_check_args(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y, const double* h_coeffs,
+                  double sigma, const double* h_newdata, int64_t u, const void* h_out) {
   BK_TRY(check_ctx(ctx));
-  BK_REQUIRE(h_X && h_y && h_coeffs && h_newdata && h_avg, "marginal_effects: null argument");
+  BK_REQUIRE(h_X && h_y && h_coeffs && h_newdata && h_out, "marginal_effects: null argument");
   BK_REQUIRE(n > 1 && p > 0 && u > 0 && n < (1ll << 31) && u < (1ll << 31), "marginal_effects: bad dimensions");
   BK_REQUIRE(sigma > 0.0 && std::isfinite(sigma), "marginal_effects: sigma must be a positive scalar");
-  BK_REQUIRE(vc.given() == (h_var != nullptr),
-             "marginal_effects: h_var is written exactly when vcov.est.c (or its factors) is given");
+  return BIGKRLS_OK;
+}
+
+int me_check_factors(const Vcov& vc, int64_t n) {
   if (vc.d_Q) BK_REQUIRE(vc.h_w && vc.k > 0 && vc.k <= n && vc.ldq >= n, "marginal_effects: bad factors of vcov.est.c");
-  const int64_t k = vc.cols();
+  return BIGKRLS_OK;
+}
+
+// the selected columns (0-based), the training moments and the two-valued columns
+struct MePrep {
   std::vector<int64_t> cols;
+  std::vector<double> x_mean, x_sd, lo, hi;
+  std::vector<char> isbin;
+  double y_sd = 0.0;
+  MeCol col(int64_t jj) const {
+    const int64_t j = cols[jj];
+    return MeCol{isbin[j] ? 1.0 : 0.0, (lo[j] - x_mean[j]) / x_sd[j], (hi[j] - x_mean[j]) / x_sd[j], (double)j};
+  }
+};
+
+int me_prepare(const double* h_X, int64_t n, int64_t p, const double* h_y, const int64_t* h_which, int64_t n_which,
+               const double* h_newdata, int64_t u, MePrep* mp) {
+  std::vector<int64_t>& cols = mp->cols;
   if (h_which) {
     BK_REQUIRE(n_which > 0, "marginal_effects: which_derivatives is empty");
     for (int64_t i = 0; i < n_which; ++i) {
@@ -124,17 +204,17 @@ int marginal_effects_impl(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_
   } else {
     for (int64_t j = 0; j < p; ++j) cols.push_back(j);
   }
-  const int64_t nj = (int64_t)cols.size(), q = 1 + nj;
   for (int64_t i = 0; i < u * p; ++i)
     BK_REQUIRE(std::isfinite(h_newdata[i]), "marginal_effects: newdata contains missing or infinite values");
-  std::vector<double> x_mean(p), x_sd(p), lo(p), hi(p);
-  std::vector<char> isbin(p);
+  std::vector<double>&x_mean = mp->x_mean, &x_sd = mp->x_sd, &lo = mp->lo, &hi = mp->hi;
+  std::vector<char>& isbin = mp->isbin;
+  x_mean.resize(p); x_sd.resize(p); lo.resize(p); hi.resize(p); isbin.resize(p);
   for (int64_t j = 0; j < p; ++j) {
     mean_sd(h_X + j * n, n, &x_mean[j], &x_sd[j]);
     BK_REQUIRE(x_sd[j] > 0.0, "marginal_effects: training column " + std::to_string(j + 1) + " is constant");
     isbin[j] = two_valued(h_X + j * n, n, &lo[j], &hi[j]);
   }
-  for (int64_t i = 0; i < nj; ++i) {
+  for (size_t i = 0; i < cols.size(); ++i) {
     const int64_t j = cols[i];
     if (!isbin[j]) continue;
     const double* z = h_newdata + j * u;
@@ -143,9 +223,38 @@ int marginal_effects_impl(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_
                  "newdata column " + std::to_string(j + 1) +
                      " is binary in the training data; its values must be one of the two training values");
   }
-  double y_mean, y_sd;
-  mean_sd(h_y, n, &y_mean, &y_sd);
-  BK_REQUIRE(y_sd > 0.0, "marginal_effects: y is a constant");
+  double y_mean;
+  mean_sd(h_y, n, &y_mean, &mp->y_sd);
+  BK_REQUIRE(mp->y_sd > 0.0, "marginal_effects: y is a constant");
+  return BIGKRLS_OK;
+}
+
+// hXs (n x p), hZs (u x p): X and newdata standardised with the training means and sds, as bigkrls_predict
+void me_standardise(const MePrep& mp, const double* h_X, int64_t n, int64_t p, const double* h_newdata, int64_t u,
+                    double* hXs, double* hZs) {
+  for (int64_t j = 0; j < p; ++j) {
+    standardise_column(h_X + j * n, n, mp.x_mean[j], mp.x_sd[j], hXs + j * n);
+    standardise_column(h_newdata + j * u, u, mp.x_mean[j], mp.x_sd[j], hZs + j * u);
+  }
+}
+
+// both entries: vcov.est.c as the n x n matrix, as its factors, or not at all (no variances) -- Vcov, common.h
+int marginal_effects_impl(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                          const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
+                          const double* h_newdata, int64_t u, const Vcov& vc, double* h_derivatives, double* h_avg,
+                          double* h_var) {
+  BK_TRY(me_check_args(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_newdata, u, h_avg));
+  BK_REQUIRE(vc.given() == (h_var != nullptr),
+             "marginal_effects: h_var is written exactly when vcov.est.c (or its factors) is given");
+  BK_TRY(me_check_factors(vc, n));
+  const int64_t k = vc.cols();
+  MePrep mp;
+  BK_TRY(me_prepare(h_X, n, p, h_y, h_which, n_which, h_newdata, u, &mp));
+  const std::vector<int64_t>& cols = mp.cols;
+  const std::vector<double>&x_mean = mp.x_mean, &x_sd = mp.x_sd, &lo = mp.lo, &hi = mp.hi;
+  const std::vector<char>& isbin = mp.isbin;
+  const double y_sd = mp.y_sd;
+  const int64_t nj = (int64_t)cols.size(), q = 1 + nj;
 
   // ---- device layout -------------------------------------------------------------------------------
   hipStream_t st = ctx->stream;
@@ -178,10 +287,7 @@ int marginal_effects_impl(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_
     double* hB = hZs + u * p;
     double* hBs = hB + n * q;
     MeCol* hcols = (MeCol*)(hBs + u * q);
-    for (int64_t j = 0; j < p; ++j) {
-      standardise_column(h_X + j * n, n, x_mean[j], x_sd[j], hXs + j * n);
-      standardise_column(h_newdata + j * u, u, x_mean[j], x_sd[j], hZs + j * u);
-    }
+    me_standardise(mp, h_X, n, p, h_newdata, u, hXs, hZs);
     for (int64_t i = 0; i < n; ++i) hB[i] = h_coeffs[i];
     for (int64_t i = 0; i < u; ++i) hBs[i] = 1.0;
     for (int64_t jj = 0; jj < nj; ++jj) {
@@ -197,10 +303,7 @@ int marginal_effects_impl(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_
         for (int64_t i = 0; i < n; ++i) b[i] = hXs[j * n + i] * h_coeffs[i];
         std::memcpy(bs, hZs + j * u, (size_t)u * sizeof(double));
       }
-      hcols[jj].bin = isbin[j] ? 1.0 : 0.0;
-      hcols[jj].z0 = (lo[j] - x_mean[j]) / x_sd[j];
-      hcols[jj].z1 = (hi[j] - x_mean[j]) / x_sd[j];
-      hcols[jj].col = (double)j;
+      hcols[jj] = mp.col(jj);
     }
     if (k > 0) std::memcpy((double*)hcols + nj * colw, vc.h_w, (size_t)k * sizeof(double));
     BK_HIP(hipMemcpyAsync(dXs, pin, (size_t)up_doubles * sizeof(double), hipMemcpyHostToDevice, st));
@@ -263,6 +366,110 @@ int marginal_effects_impl(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_
   return BIGKRLS_OK;
 }
 
+// bigkrls_marginal_effects_se: vc is the matrix or the factors (exactly one, checked by the entry)
+int marginal_effects_se_impl(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                             const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
+                             const double* h_newdata, int64_t u, const Vcov& vc, int64_t block_rows, double* h_se) {
+  BK_TRY(me_check_args(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_newdata, u, h_se));
+  BK_REQUIRE(block_rows >= 0 && block_rows % 128 == 0, "marginal_effects_se: block_rows must be 0 or a multiple of 128");
+  BK_TRY(me_check_factors(vc, n));
+  const int64_t k = vc.cols();
+  MePrep mp;
+  BK_TRY(me_prepare(h_X, n, p, h_y, h_which, n_which, h_newdata, u, &mp));
+  const int64_t nj = (int64_t)mp.cols.size();
+  // rows per block: beside the b x n block of the test kernel, T = G_j Q (b x k) or the stored G_j (b x n)
+  const int64_t wide = vc.d_Q ? k : n;
+  const int64_t b = std::min(block_rows > 0 ? block_rows : pointwise_block_rows(n, wide), u);
+
+  // ---- device layout -------------------------------------------------------------------------------
+  hipStream_t st = ctx->stream;
+  const int64_t colw = (int64_t)((sizeof(MeCol) + 7) / 8);
+  const int64_t up_doubles = n * p + u * p + n + u + nj * colw + k;   // uploaded, in this order
+  const int64_t small_doubles = up_doubles + n * nj + 2 * b * nj + u * nj + 64;
+  void* psmall = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_ME_SMALL, small_doubles * (int64_t)sizeof(double), &psmall));
+  double* qd = (double*)psmall;
+  double* dXs = qd; qd += n * p;
+  double* dZs = qd; qd += u * p;
+  double* dnx = qd; qd += n;
+  double* dnz = qd; qd += u;
+  MeCol* dcols = (MeCol*)qd; qd += nj * colw;
+  double* dw = qd; qd += k;
+  double* dS = qd; qd += n * nj;
+  double* dR = qd; qd += b * nj;
+  double* dT = qd; qd += b * nj;
+  double* dse = qd; qd += u * nj;
+  void* pk = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_PP_K, b * (n + wide) * (int64_t)sizeof(double), &pk));
+  double* dKn = (double*)pk;
+  double* dP = dKn + b * n;   // T = G_j Q, or G_j
+
+  // ---- standardise, squared row norms (the training rows are centred by their standardisation: no further shift),
+  //      upload -----------------------------------------------------------------------------------------
+  double* pin = nullptr;
+  BK_HIP(hipStreamSynchronize(st));   // (the pinned buffer may be reallocated)
+  BK_TRY(pinned_get(ctx, std::max(up_doubles, u * nj), &pin));
+  {
+    double* hXs = pin;
+    double* hZs = hXs + n * p;
+    double* hnx = hZs + u * p;
+    double* hnz = hnx + n;
+    MeCol* hcols = (MeCol*)(hnz + u);
+    me_standardise(mp, h_X, n, p, h_newdata, u, hXs, hZs);
+    auto sqnorms = [p](const double* A, int64_t rows, double* out) {
+      for (int64_t i = 0; i < rows; ++i) out[i] = 0.0;
+      for (int64_t j = 0; j < p; ++j)
+        for (int64_t i = 0; i < rows; ++i) out[i] += A[j * rows + i] * A[j * rows + i];
+    };
+    sqnorms(hXs, n, hnx);
+    sqnorms(hZs, u, hnz);
+    for (int64_t jj = 0; jj < nj; ++jj) hcols[jj] = mp.col(jj);
+    if (k > 0) std::memcpy((double*)hcols + nj * colw, vc.h_w, (size_t)k * sizeof(double));
+    BK_HIP(hipMemcpyAsync(dXs, pin, (size_t)up_doubles * sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  int blocks = (int)std::min<int64_t>((n * nj + 255) / 256, 4096);
+  hipLaunchKernelGGL(me_se_s_kernel, dim3(blocks), dim3(256), 0, st, (int)n, (int)nj, (const double*)dXs,
+                     (const MeCol*)dcols, dS);
+  BK_CHECK_LAUNCH();
+
+  // ---- row blocks of the new points ---------------------------------------------------------------------
+  for (int64_t r0 = 0; r0 < u; r0 += b) {
+    const int64_t rows = std::min(b, u - r0);
+    BK_TRY(kernel_block_centred(ctx, dZs + r0, rows, u, dnz + r0, dXs, n, n, dnx, p, sigma, dKn, rows, -1));
+    blocks = (int)std::min<int64_t>((rows * nj + 255) / 256, 4096);
+    hipLaunchKernelGGL(me_se_rt_kernel, dim3(blocks), dim3(256), 0, st, (int)rows, (int)nj, (const double*)(dZs + r0),
+                       u, (const MeCol*)dcols, sigma, dR, dT);
+    BK_CHECK_LAUNCH();
+    for (int64_t jj = 0; jj < nj; ++jj) {
+      const double *r = dR + jj * rows, *t = dT + jj * rows, *s = dS + jj * n;
+      double* out = dse + jj * u + r0;
+      if (vc.d_Q) {
+        BK_TRY(gemm_modulated(ctx, rows, k, n, dKn, rows, r, t, s, vc.d_Q, vc.ldq, dP, rows));     // T = G_j Q
+        BK_TRY(rowsumsq_weighted(ctx, rows, k, dP, rows, dw, out));
+      } else {
+        blocks = (int)std::min<int64_t>((rows * n + 255) / 256, 8192);
+        hipLaunchKernelGGL(me_se_modulate_kernel, dim3(blocks), dim3(256), 0, st, (int)rows, (int)n,
+                           (const double*)dKn, r, t, s, dP);
+        BK_CHECK_LAUNCH();
+        BK_TRY(quadform_diag(ctx, rows, n, dP, rows, vc.d_V, n, out));                             // diag(G_j V G_j')
+      }
+    }
+  }
+  BK_HIP(hipMemcpyAsync(pin, dse, (size_t)(u * nj) * sizeof(double), hipMemcpyDeviceToHost, st));
+  BK_HIP(hipStreamSynchronize(st));
+
+  // ---- original units: the variance times (sd(y)/sd(x_j))^2 with V = vcov.est.c / sd(y)^2 -- sd(y)^2 cancels as in
+  //      marginal_effects_impl; the factor 2 of the binary columns; a quadratic form that rounds below zero is zero -----
+  for (int64_t jj = 0; jj < nj; ++jj) {
+    const int64_t j = mp.cols[jj];
+    const double scale = (mp.isbin[j] ? 2.0 : 1.0) / (mp.x_sd[j] * mp.x_sd[j]);
+    const double* v = pin + jj * u;
+    double* se = h_se + jj * u;
+    for (int64_t i = 0; i < u; ++i) se[i] = std::sqrt(std::max(scale * v[i], 0.0));
+  }
+  return BIGKRLS_OK;
+}
+
 }  // namespace
 }  // namespace bk
 
@@ -284,6 +491,16 @@ int bigkrls_marginal_effects_factored(bigkrls_ctx* ctx, const double* h_X, int64
                                       const double* h_w, double* h_derivatives, double* h_avg, double* h_var) {
   return marginal_effects_impl(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_which, n_which, h_newdata, u,
                                Vcov::factors(d_Q, ldq, k, h_w), h_derivatives, h_avg, h_var);
+}
+
+int bigkrls_marginal_effects_se(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                                const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
+                                const double* h_newdata, int64_t u, const double* d_vcov_c, const double* d_Q,
+                                int64_t ldq, int64_t k, const double* h_w, int64_t block_rows, double* h_se) {
+  BK_REQUIRE((d_vcov_c != nullptr) != (d_Q != nullptr),
+             "marginal_effects_se: exactly one of vcov.est.c and its factors must be given");
+  return marginal_effects_se_impl(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_which, n_which, h_newdata, u,
+                                  d_vcov_c ? Vcov::matrix(d_vcov_c) : Vcov::factors(d_Q, ldq, k, h_w), block_rows, h_se);
 }
 
 }  // extern "C"

@@ -100,6 +100,24 @@ def bRowSumSqWeighted(T: DeviceMatrix, w) -> DeviceMatrix:
     return out
 
 
+def bGemmModulated(A: DeviceMatrix, r, t, s, B: DeviceMatrix) -> DeviceMatrix:
+    """(A o (r 1' + t s')) B (m x n) for A m x k, B k x n, r and t with m entries and s with k (DeviceMatrix or host
+    arrays): out[i,j] = sum_l A[i,l] (r[i] + t[i] s[l]) B[l,j]. A is modulated on its way into the multiply and the
+    modulated copy is never stored (bigkrls_dev_gemm_modulated); with r = 1, t = 0 it is the plain product bitwise.
+    No counterpart in the reference."""
+    ctx = A.ctx
+    if B.nrow != A.ncol:
+        raise ValueError("bGemmModulated: B must have ncol(A) rows")
+    dev = [v if isinstance(v, DeviceMatrix) else ctx.from_numpy(np.asarray(v, dtype=np.float64).ravel()) for v in (r, t, s)]
+    for v, want, name in zip(dev, (A.nrow, A.nrow, A.ncol), "rts"):
+        if v.nrow * v.ncol != want or (v.ncol > 1 and v.nrow > 1):
+            raise ValueError(f"bGemmModulated: {name} must be a vector with {want} entries")
+    out = ctx.empty(A.nrow, B.ncol)
+    _lib.call("bigkrls_dev_gemm_modulated", ctx.handle, A.nrow, B.ncol, A.ncol, A.ptr, A.ld, dev[0].ptr, dev[1].ptr,
+              dev[2].ptr, B.ptr, B.ld, out.ptr, out.ld)
+    return out
+
+
 # ---------------------------------------------------------------------------
 # eigen   (R/bigKRLS_Rcpp_functions.R:173-199)
 # ---------------------------------------------------------------------------

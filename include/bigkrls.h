@@ -230,6 +230,17 @@ int bigkrls_dev_gemm(bigkrls_ctx* ctx, int transa, int transb, int64_t m, int64_
                      double alpha, const double* A, int64_t lda, const double* B, int64_t ldb,
                      double beta, double* C, int64_t ldc);
 
+/* Product with a modulated left operand: C (m x n, ldc >= m, overwritten) = (A o (r 1' + t s')) B, i.e.
+ * C[i,j] = sum_l A[i,l] (r[i] + t[i] s[l]) B[l,j]; A m x k (lda >= m) and B k x n (ldb >= k) column-major and not
+ * transposed, r and t (m) and s (k) on the device. The factor is applied to A in registers on its way to the
+ * multiply; the modulated copy of A is never written (no extra device memory beside bigkrls_dev_gemm's split-K
+ * partials). Tiles and split-K choice are bigkrls_dev_gemm's; deterministic, two calls give bitwise identical results,
+ * and with r = 1, t = 0 the result is bitwise that of bigkrls_dev_gemm(0, 0, m, n, k, 1.0, A, lda, B, ldb, 0.0, C, ldc).
+ * k == 0 gives zeros; m == 0 or n == 0 does nothing. */
+int bigkrls_dev_gemm_modulated(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda,
+                               const double* r, const double* t, const double* s, const double* B, int64_t ldb,
+                               double* C, int64_t ldc);
+
 /* out[:,i] = A[:,i]*diag[i] (diag on device). */
 int bigkrls_dev_multdiag(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t k, int64_t lda,
                          const double* diag, double* out, int64_t ldo);
@@ -492,6 +503,33 @@ int bigkrls_marginal_effects_factored(bigkrls_ctx* ctx, const double* h_X, int64
                                       const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
                                       const double* h_newdata, int64_t u, const double* d_Q, int64_t ldq, int64_t k,
                                       const double* h_w, double* h_derivatives, double* h_avg, double* h_var);
+
+/* Pointwise standard errors of the marginal effects: h_se (u x |J| column-major, the column order of h_derivatives)
+ * = the standard error of every derivative bigkrls_marginal_effects returns for the same inputs, in the original
+ * units. Validation, standardisation, binary detection and error messages are bigkrls_marginal_effects'. vcov.est.c
+ * comes as the n x n matrix (d_vcov_c, ld n) or as its factors (d_Q n x k, ldq >= n, on the device; h_w the k weights
+ * on the host): exactly one of d_vcov_c and d_Q is given, else BIGKRLS_EINVAL.
+ * In standardised units D[i,j] = g_ij' c with g_ij[l] = Kn[i,l] (r_i + t_i s_l) (continuous j: s = Xs[:,j],
+ * r_i = -(2/sigma) Zs_ij, t_i = 2/sigma; binary j: s = the training group indicator and r_i, t_i the two weights of
+ * the first difference for the group of new point i), so Var(D[i,j]) = g_ij' V g_ij and
+ *   se[i,j] = sqrt(f_j sum_m w_m ((G_j Q)[i,m])^2) / sd(x_j),   G_j = Kn o (r 1' + t s'),
+ * with f_j = 2 for binary columns (the reference's factor, src/bigderiv_v3.cpp:85, as in var.avgderivatives) and 1
+ * otherwise. With u = 1, se[0,j]^2 equals bigkrls_marginal_effects' h_var[j] for every column.
+ * The new points are taken in row blocks of b. From the factors b is bigkrls_predict_factored's: the largest multiple
+ * of 128 with 8 b (n + k) <= 2^30 bytes, at least 128; per block the test kernel once, and per column
+ * T = G_j Q (bigkrls_dev_gemm_modulated: G_j is never stored) and bigkrls_dev_rowsumsq_weighted: 2 u n k flops per
+ * column. From the matrix (the compatibility path) b is the largest multiple of 128 with 16 b n <= 2^30 bytes, at
+ * least 128; G_j is written beside the block and bigkrls_dev_quadform_diag gives the diagonal: 2 u n^2 flops per column,
+ * n / k times the factors' -- the factors are the fast form. block_rows = 0 chooses b as above; another value overrides
+ * it and must be a positive multiple of 128 (BIGKRLS_EINVAL otherwise). Every row's result is bitwise independent of b
+ * while the products take one k split (n < 1024); beyond that the split count follows the block's shape, as in
+ * bigkrls_dev_gemm, and blockings agree to rounding. Two calls with the same b are bitwise identical.
+ * Extra device memory: the block and T (or G_j), at most 1 GiB; the products' split partials; and
+ * 8 ((u + n) (p + 2 |J|) + u |J| + k) bytes of vectors -- independent of u beyond O(u (p + |J|)). */
+int bigkrls_marginal_effects_se(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                                const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
+                                const double* h_newdata, int64_t u, const double* d_vcov_c, const double* d_Q,
+                                int64_t ldq, int64_t k, const double* h_w, int64_t block_rows, double* h_se);
 
 /* =============================================================================
  * Multi-GPU: one process per GPU, the collectives inside the library (the context's
