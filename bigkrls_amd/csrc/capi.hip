@@ -228,9 +228,7 @@ int prof_end(bigkrls_ctx* ctx, const char* name, hipStream_t stream) {
 }
 
 static int prof_flush(bigkrls_ctx* ctx) {
-  BK_HIP(hipStreamSynchronize(ctx->stream));
-  if (ctx->side_stream) BK_HIP(hipStreamSynchronize(ctx->side_stream));
-  if (ctx->bg_stream) BK_HIP(hipStreamSynchronize(ctx->bg_stream));
+  BK_TRY(drain_streams(ctx));
   for (auto& e : ctx->prof) {
     for (auto& s : e.pending) {
       float ms = 0.f;

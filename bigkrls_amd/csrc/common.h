@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdlib.h>
 #include <string>
 #include <utility>
 #include <vector>
@@ -91,8 +92,9 @@ struct bigkrls_ctx {
   // replicated eigenvalues of this rank that were not rank 0's bit for bit (multi-GPU fits)
   int64_t n_redone = 0, n_replayed = 0, n_replica_diff = 0;
   // set by the eigensolver beside an error code when what failed can only be a fault of the run on a finite symmetric
-  // input (a block recurrence that does not hold against K, non-finite entries after the tridiagonalisation); read and
-  // cleared by the fit, which validated its input and redoes such a decomposition once (Fit::soften, csrc/fit.hip)
+  // input (a block recurrence that does not hold against K, non-finite entries after the tridiagonalisation); cleared on
+  // entry to eigen() (EIG_FULL), eigen_implicit and eigen_krylov_dist and where a Lanczos attempt is given up for the
+  // dense path; read and cleared by the fit, which validated its input and redoes such a decomposition once (Fit::soften)
   bool corrupt_run = false;
   // set by the fit around a decomposition it is going to verify against K itself (ALL kept pairs, csrc/fit.hip,
   // Fit::verify_decomposition): the block Lanczos then leaves out its own sample check of the last block of Ritz pairs
@@ -204,6 +206,15 @@ enum Slot {
   SLOT_KOP_NORMS = 53,     // ... and its squared row norms
 };
 
+// BIGKRLS_VERBOSE: progress and timing lines on stderr (read at every call: it may be switched while the process runs)
+static inline bool verbose() { return getenv("BIGKRLS_VERBOSE") != nullptr; }
+// everything the context has queued is done: the look-ahead, the background and the main stream
+static inline int drain_streams(bigkrls_ctx* ctx) {
+  if (ctx->side_stream) BK_HIP(hipStreamSynchronize(ctx->side_stream));
+  if (ctx->bg_stream) BK_HIP(hipStreamSynchronize(ctx->bg_stream));
+  BK_HIP(hipStreamSynchronize(ctx->stream));
+  return BIGKRLS_OK;
+}
 int ws_get(bigkrls_ctx* ctx, int slot, int64_t nbytes, void** out);
 bool ws_poison();                      // BIGKRLS_POISON (diagnostics): fresh workspace starts as all-ones bytes ...
 int ws_poison_all(bigkrls_ctx* ctx);   // ... and every slab is reset to them at the start of a fit
@@ -408,7 +419,8 @@ enum EigMode { EIG_FULL = 0, EIG_SETUP_ONLY = 1, EIG_RESUME = 2 };
 // Internal status (never crosses the C ABI): the watchdog of a persistent kernel fired in a decomposition whose
 // stage 1 was driven from outside (EIG_RESUME). The distributed fit agrees on it over the ranks and replays the
 // decomposition with the launch-per-step kernels on every rank (Fit::eigen_dist_dense, csrc/fit.hip); larger than every public code so
-// that the agreement (a MAX) prefers it to a rank-local OK.
+// that the agreement (a MAX) prefers it to a rank-local OK. EIG_FULL never returns it: there the same replay runs
+// inside the call (DenseEig::run / replay, csrc/eigen.hip, the one place that answers a fired watchdog).
 constexpr int BK_EWATCHDOG = 90;
 int eigen(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t lda, int64_t n_vals, double* vals,
           int64_t n_vecs_max, double keep_thresh, double* vecs, int64_t ldv, int64_t* h_n_vecs,

@@ -329,7 +329,8 @@ int eigen_dense_dist(bigkrls_comm* comm, double* A, int64_t n, int64_t nb, int64
   }
   BK_TRY(comm_agree(comm, status));
   // stage 2, divide & conquer and this rank's slice of the back-transform; a fired watchdog of a persistent kernel
-  // (this rank's or another's) comes back as BK_EWATCHDOG on EVERY rank: the caller replays the decomposition
+  // (this rank's or another's; EIG_RESUME reports it, it does not replay: DenseEig::run, csrc/eigen.hip) comes back as
+  // BK_EWATCHDOG on EVERY rank, with nothing of the call left running on the look-ahead stream: the caller replays
   int64_t nv = 0;
   void* pq = nullptr;
   status = eigen(ctx, nullptr, n, n, neig, dvals, neig, eigtrunc, dQ, n, &nv, rank, world, EIG_RESUME);

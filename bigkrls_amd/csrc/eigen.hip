@@ -1320,13 +1320,13 @@ int divide_conquer(bigkrls_ctx* ctx, int n, const std::vector<double>& hd,
         BK_TRY(trace_point(ctx, st, "R:dc_leaf_Q", Q0, N * N, nleaf));
       }
     }
-    if (getenv("BIGKRLS_VERBOSE"))
+    if (verbose())
       fprintf(stderr, "[bigkrls]   d&c leaves: %6d of up to %d rows (QL) %8.2f ms\n", nleaf, leaf_max,
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_leaf).count());
   }
 
   int64_t nv_final = 0;
-  const bool verbose = getenv("BIGKRLS_VERBOSE") != nullptr;
+  const bool verbose = bk::verbose();
   std::vector<LazyLevel> lazy_levels(lazy ? Dl + 1 : 0);   // indexed by depth
   std::vector<double> bf, bl, yf, yl;                      // boundary rows of the current frontier / of a level
   double* stash = nullptr;
@@ -2365,7 +2365,7 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
         std::memcpy(hp, Rtmp.data(), (size_t)b * b * sizeof(double));
         BK_HIP(hipMemcpyAsync(dBall + (int64_t)steps * b * b, hp, (size_t)b * b * sizeof(double), hipMemcpyHostToDevice, st));
         BK_HIP(hipStreamSynchronize(st));
-        if (getenv("BIGKRLS_VERBOSE")) fprintf(stderr, "[bigkrls] block Lanczos step %d: ill-conditioned block (pivot ratio %.1e) re-orthogonalised\n", steps, piv[0] / piv[1]);
+        if (verbose()) fprintf(stderr, "[bigkrls] block Lanczos step %d: ill-conditioned block (pivot ratio %.1e) re-orthogonalised\n", steps, piv[0] / piv[1]);
       }
     }
     // The Krylov space is invariant to working precision when the new block is nothing but rounding: its largest
@@ -2401,7 +2401,7 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
           std::fill(Rtmp.begin(), Rtmp.end(), 0.0);
           BK_HIP(hipMemsetAsync(dBall + (int64_t)steps * b * b, 0, (size_t)b * b * sizeof(double), st));
           piv[1] = 0.0;       // (nothing of this step counts as a direction of a Krylov block)
-          if (getenv("BIGKRLS_VERBOSE"))
+          if (verbose())
             fprintf(stderr, "[bigkrls] block Lanczos step %d: invariant subspace of %lld columns (|W| = %.1e): continued with a random block\n",
                     steps, (long long)((steps + 1) * b), wfro);
         }
@@ -2518,7 +2518,7 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
         Resid r = residuals(th.data(), Ylast.data());
         double worst = r.worst, theta1 = std::fabs(th[0]);
         BK_TRY(agree_worst(worst, theta1));
-        if (getenv("BIGKRLS_VERBOSE"))
+        if (verbose())
           fprintf(stderr, "[bigkrls] block Lanczos estimate: steps=%d (compressed from %d: %lld instead of %lld) worst=%.3e converged=%lld of %lld theta0=%.4e\n",
                   steps, full_steps, (long long)mc, (long long)m, worst, (long long)r.n_conv, (long long)k, th[0]);
         {
@@ -2549,7 +2549,7 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
         Resid r = residuals(theta.data(), Ylast.data());
         double worst = r.worst, theta1 = std::fabs(theta[0]);
         BK_TRY(agree_worst(worst, theta1));
-        if (getenv("BIGKRLS_VERBOSE"))
+        if (verbose())
           fprintf(stderr, "[bigkrls] block Lanczos check: steps=%d worst=%.3e worst(kept)=%.3e converged=%lld of %lld theta0=%.4e\n",
                   steps, worst, r.worst_kept, (long long)r.n_conv, (long long)k, theta[0]);
         {
@@ -2587,7 +2587,7 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
     BK_HIP(hipMemcpyAsync(B + (int64_t)steps * b * n, W, n * b * sizeof(double), hipMemcpyDeviceToDevice, st));
     dim = (int64_t)(steps + 1) * b;
   }
-  if (getenv("BIGKRLS_VERBOSE")) fprintf(stderr, "[bigkrls] block Lanczos: n=%lld k=%lld steps=%d dim=%lld converged=%d\n", (long long)n, (long long)k, steps, (long long)dim, (int)converged);
+  if (verbose()) fprintf(stderr, "[bigkrls] block Lanczos: n=%lld k=%lld steps=%d dim=%lld converged=%d\n", (long long)n, (long long)k, steps, (long long)dim, (int)converged);
 #ifdef BK_FAULT_INJECT
   {
     const char* fault = getenv("BIGKRLS_FAULT");   // BIGKRLS_FAULT=noconv (test build): pretend the iteration stalled
@@ -2646,7 +2646,7 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
     BK_HIP(hipStreamSynchronize(st));
     double rmax = 0.0;
     for (int64_t i = 0; i < bs; ++i) rmax = std::max(rmax, std::sqrt(std::max(hp[i], 0.0)));
-    if (getenv("BIGKRLS_VERBOSE"))
+    if (verbose())
       fprintf(stderr, "[bigkrls] block Lanczos: true residual of the last %lld pairs %.3e (tolerance %.3e)\n", (long long)bs,
               rmax, tol * std::fabs(theta[0]));
     {
@@ -2724,34 +2724,11 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
   return BIGKRLS_OK;
 }
 
-// The watchdog of a persistent kernel (pq_resident / bc_resident) fired: its workgroups were not
-// co-resident, e.g. because another process or stream held part of the GPU. A is untouched, so the
-// decomposition is redone once, in the same call, with the launch-per-step kernels (no spinning).
-static int eigen_retry_without_resident(bigkrls_ctx* ctx, const double* A, int64_t n64, int64_t lda,
-                                        int64_t n_vals, double* vals, int64_t n_vecs_max, double keep_thresh,
-                                        double* vecs, int64_t ldv, int64_t* h_n_vecs, int part_index,
-                                        int part_count) {
-  if (ctx->side_stream) (void)hipStreamSynchronize(ctx->side_stream);   // look-ahead work still queued
-  if (ctx->bg_stream) (void)hipStreamSynchronize(ctx->bg_stream);
-  (void)hipStreamSynchronize(ctx->stream);
-  if (ctx->no_resident) {
-    set_error("eigen: watchdog of a persistent kernel fired although none should have been launched");
-    return BIGKRLS_EHIP;
-  }
-  if (getenv("BIGKRLS_VERBOSE"))
-    fprintf(stderr, "[bigkrls] eigen: persistent-kernel watchdog fired; retrying with per-step launches\n");
-  ctx->n_replayed++;
-  ctx->no_resident = true;
-  const int rc = eigen(ctx, A, n64, lda, n_vals, vals, n_vecs_max, keep_thresh, vecs, ldv, h_n_vecs, part_index,
-                       part_count, EIG_FULL);
-  ctx->no_resident = false;
-  return rc;
-}
-
 int eigen_krylov_dist(bigkrls_comm* comm, const double* Kcols, int64_t n, int64_t r0, int64_t r1, int64_t nb,
                       int64_t n_vals, double* vals, int64_t n_vecs_max, double keep_thresh, double* vecs, int64_t ldv,
                       int64_t* h_n_vecs) {
   BK_REQUIRE(comm && comm->ctx && (Kcols || r1 <= r0) && vals && n_vals > 0 && n_vals <= n, "eigen_krylov_dist: bad arguments");
+  comm->ctx->corrupt_run = false;
   KTimes op;
   op.comm = comm;
   op.Kcols = Kcols;
@@ -2775,6 +2752,7 @@ int eigen_implicit(bigkrls_ctx* ctx, const KernelOp& kernel, int64_t n_vals, dou
   }
   BK_REQUIRE(n_vecs_max >= 0 && n_vecs_max <= n, "eigen (implicit kernel): n_vecs_max out of range");
   BK_REQUIRE(n_vecs_max == 0 || (vecs && ldv >= n), "eigen (implicit kernel): bad eigenvector buffer");
+  ctx->corrupt_run = false;
   KTimes op;
   op.kernel = &kernel;
   const int rc = eigen_krylov(ctx, op, n, n_vals, vals, n_vecs_max, keep_thresh, vecs, ldv, h_n_vecs, 0, 1);
@@ -2790,6 +2768,13 @@ struct DistS1 {
   int n = 0;
   bool panel_pending = false;   // a panel factorisation is running on the look-ahead stream (ev_join marks its end)
   int agg_mode = 0;             // panels per trailing update the ranks agreed on: 4 (groups of four, then pairs), 2 (pairs), 0 (none)
+};
+
+// wall-clock of the host between two points, for the BIGKRLS_VERBOSE lines: ms() since the start or the last lap()
+struct Stopwatch {
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+  double lap() { const double m = ms(); t0 = std::chrono::steady_clock::now(); return m; }
 };
 
 // The stage-1 panel loop as a captured hipGraph (round 6; OPT-IN, off by default). The loop has no host synchronisation
@@ -2831,14 +2816,10 @@ static int stage1_run(bigkrls_ctx* ctx, double* W, int n, double* taus1, const S
     }
     st = ctx->graph_stream;
   }
-  const bool verbose = getenv("BIGKRLS_VERBOSE") != nullptr;
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-    return std::chrono::duration<double, std::milli>(b - a).count();
-  };
+  const bool verbose = bk::verbose();
   const bool hit = gmode != 1 && ctx->s1_graph_exec && ctx->s1_graph_n == n && ctx->s1_graph_gen == ctx->ws_generation &&
                    ctx->s1_graph_W == (const void*)W;
-  const auto t0 = now();
+  Stopwatch sw;
   if (!hit) {
     if (ctx->s1_graph_exec) {
       BK_HIP(hipStreamSynchronize(user));
@@ -2860,7 +2841,7 @@ static int stage1_run(bigkrls_ctx* ctx, double* W, int n, double* taus1, const S
       set_error(std::string("stage 1: stream capture failed: ") + hipGetErrorString(ec));
       return BIGKRLS_EHIP;
     }
-    const auto t1 = now();
+    const double ms_capture = sw.lap();
     hipGraphExec_t exec = nullptr;
     const hipError_t ei = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
     size_t nnodes = 0;
@@ -2875,10 +2856,10 @@ static int stage1_run(bigkrls_ctx* ctx, double* W, int n, double* taus1, const S
     ctx->s1_graph_gen = ctx->ws_generation;
     ctx->s1_graph_W = (const void*)W;
     if (verbose)
-      fprintf(stderr, "[bigkrls]   stage 1 as a graph: %zu nodes, capture %.2f ms, instantiate %.2f ms\n", nnodes, ms(t0, t1),
-              ms(t1, now()));
+      fprintf(stderr, "[bigkrls]   stage 1 as a graph: %zu nodes, capture %.2f ms, instantiate %.2f ms\n", nnodes, ms_capture,
+              sw.lap());
   }
-  const auto t2 = now();
+  sw = Stopwatch();
   if (st != user) {                  // everything queued on the default stream so far comes first ...
     BK_HIP(hipEventRecord(ctx->ev_graph, user));
     BK_HIP(hipStreamWaitEvent(st, ctx->ev_graph, 0));
@@ -2889,13 +2870,554 @@ static int stage1_run(bigkrls_ctx* ctx, double* W, int n, double* taus1, const S
     BK_HIP(hipStreamWaitEvent(user, ctx->ev_graph, 0));
   }
   if (verbose) {
-    const auto t3 = now();
+    const double ms_call = sw.ms();
     BK_HIP(hipStreamSynchronize(user));
-    fprintf(stderr, "[bigkrls]   stage 1 as a graph: launch call %.2f ms, launch to completion %.2f ms%s\n", ms(t2, t3),
-            ms(t2, now()), hit ? " (cached executable graph)" : "");
+    fprintf(stderr, "[bigkrls]   stage 1 as a graph: launch call %.2f ms, launch to completion %.2f ms%s\n", ms_call,
+            sw.ms(), hit ? " (cached executable graph)" : "");
   }
   return BIGKRLS_OK;
 }
+
+// ---------------------------------------------------------------------------
+// The dense decomposition: one call's arguments and what its phases share, and the phases in the order they run
+// (DenseEig::phases). EIG_SETUP_ONLY leaves after the layout (hand_to_dist), EIG_RESUME skips stage 1. Two rules:
+//  - A persistent kernel's watchdog word is read by read_watchdog() alone; a fired one comes back as WD_FIRED and
+//    becomes the call's answer at ONE place (run): BK_EWATCHDOG under EIG_RESUME, the replay in this call otherwise.
+//  - Once fork_lookahead() has queued work on the look-ahead stream against this call's workspace, no exit leaves it
+//    running: success waits for it on the main stream (join_lookahead, then finish's synchronisation); every other
+//    exit -- each BK_TRY / BK_HIP of the phases, the NaN check, a fired watchdog -- goes through run(), which
+//    synchronises the stream the work went to.
+// ---------------------------------------------------------------------------
+namespace {
+
+struct EigArgs {
+  bigkrls_ctx* ctx;
+  const double* A;
+  int64_t N, lda, n_vals;
+  double* vals;
+  int64_t n_vecs_max;
+  double keep_thresh;
+  double* vecs;
+  int64_t ldv;
+  int64_t* h_n_vecs;
+  int part_index, part_count, mode;
+};
+
+// the persistent kernels with a watchdog word: what EIG_RESUME reports when it fired, and the BIGKRLS_FAULT value
+// (test build) that makes the first attempt read it as fired
+struct Watchdog { const char* resume_error; const char* fault; };
+constexpr Watchdog WD_STAGE1{"eigen: watchdog of the register-resident panel QR fired during the distributed stage 1", "watchdog"};
+constexpr Watchdog WD_STAGE2{"eigen: watchdog of the LDS-resident bulge chasing fired after the distributed stage 1", nullptr};
+constexpr Watchdog WD_BT2{"eigen: watchdog of the persistent stage-2 back-transform fired after the distributed stage 1", "watchdog_bt2"};
+constexpr int WD_FIRED = -1;   // status of a phase whose watchdog read came back non-zero; never leaves DenseEig::run
+
+struct DenseEig : EigArgs {
+  const int n;
+  const hipStream_t st;
+  // BIGKRLS_VERBOSE: wall-clock of each phase on stderr (adds a stream synchronisation per phase)
+  const bool talk = verbose();
+  Stopwatch phase;
+  // ---- workspace (carve_workspace): the matrix, the one-stage path's panels and vectors, the U slot
+  double *W = nullptr, *P1 = nullptr, *P2 = nullptr, *d = nullptr, *e = nullptr, *tau = nullptr, *scratch = nullptr;
+  double* U = nullptr;
+  SymvWs sw{};
+  // ... and of the two-stage path: stage 1, its reflector scales, the band, stage 2's sweep offsets and reflectors
+  bool two_stage = false;
+  Stage1Ws s1{};
+  double *taus1 = nullptr, *AB = nullptr, *VV = nullptr, *TT = nullptr;
+  int64_t* d_soff = nullptr;
+  // ---- what is precomputed for the back-transforms beside the divide & conquer (fork_lookahead)
+  std::vector<int64_t> bt2_toff;      // T-factor slot offsets of the stage-2 back-transform's task groups
+  double* bt2_T = nullptr;
+  int64_t* bt2_dtoff = nullptr;
+  int* bt2_err = nullptr;             // watchdog word of the persistent stage-2 back-transform (when it ran)
+  Bt1Plan bt1;                        // merged block reflectors of the stage-1 back-transform
+  double *bt1_V = nullptr, *bt1_T = nullptr, *bt1_G = nullptr;
+  int64_t LT1 = 0;
+  bool lookahead_queued = false;      // work of this call may still be running on pre_stream()
+  // ---- the tridiagonal matrix and the solution (host)
+  std::vector<double> hd, he, vals_desc;
+  std::vector<int> src_cols;
+  double* Qfin = nullptr;
+  int nv = 0;
+  const Watchdog* fired = nullptr;
+
+  explicit DenseEig(const EigArgs& a) : EigArgs(a), n((int)a.N), st(a.ctx->stream) {}
+
+  void tick(const char* name) {
+    if (!talk) return;
+    (void)hipStreamSynchronize(st);
+    fprintf(stderr, "[bigkrls] eigen n=%d: %-28s %8.2f ms\n", n, name, phase.lap());
+  }
+
+  // (BIGKRLS_BG=1, an A/B switch: what is precomputed for the back-transforms goes to a lowest-priority stream instead
+  //  of the high-priority look-ahead stream. Measured slower: C3 0.4029-0.4043 vs 0.4009-0.4012 s, same box
+  //  (profiles/r06/r06g_bg_stream_ab_*.log) -- the merged blocks then finish late behind the stage-2 back-transform)
+  hipStream_t pre_stream() const {
+    static const bool bg = [] { const char* e = getenv("BIGKRLS_BG"); return e && e[0] == '1'; }();
+    return bg ? ctx->bg_stream : ctx->side_stream;
+  }
+
+  // ---- Neig << N: block Lanczos (the reference switches to eigs_sym for Neig < N, src/eigen.cpp:18-22);
+  // BIGKRLS_EIGK=dense keeps the dense path, =krylov forces the iterative one when Neig <= N/4. *go_dense is set when
+  // the decomposition is (still) the dense path's to do; otherwise the returned status is the call's.
+  int route_krylov(bool* go_dense) {
+    *go_dense = false;
+    const char* ek = getenv("BIGKRLS_EIGK");
+    const std::string eigk = ek ? ek : "";
+    // (measured: N = 12 000, Neig = 512 dense 0.33 s vs 0.47 s; N = 50 000, Neig = 512 dense 6.9 s vs 0.88 s)
+    const bool small_k = n_vals * 8 <= N && N >= 16384;
+    if (eigk == "dense" || n_vals >= N || !(small_k || (eigk == "krylov" && n_vals * 4 <= N && N >= 1024))) {
+      *go_dense = true;
+      return BIGKRLS_OK;
+    }
+    KTimes whole;
+    whole.A = A;
+    whole.lda = lda;
+    const int rc = eigen_krylov(ctx, whole, N, n_vals, vals, n_vecs_max, keep_thresh, vecs, ldv, h_n_vecs, part_index,
+                                part_count);
+    // A spectrum the iteration does not resolve within its subspace limit (or a breakdown) is
+    // handed to the dense path in the same call -- A is untouched. Only an explicit
+    // BIGKRLS_EIGK=krylov reports the non-convergence.
+    if (rc != BIGKRLS_ENOCONV || eigk == "krylov") return rc;
+    // ... provided its workspace fits: W, Q0, Q1, U = 4 n^2 doubles beside what the caller holds (320 GB at
+    // n = 100 000). Otherwise the non-convergence is the answer, with what the iteration saw.
+    size_t free_b = 0, total_b = 0;
+    BK_HIP(hipMemGetInfo(&free_b, &total_b));
+#ifdef BK_FAULT_INJECT
+    if (const char* fault = getenv("BIGKRLS_FAULT_NOFIT")) {   // (test build) pretend the device is this full
+      if (atoi(fault) != 0) free_b = 0;
+    }
+#endif
+    int64_t held = 0;
+    for (int sl : {SLOT_EIG_A, SLOT_EIG_Q0, SLOT_EIG_Q1, SLOT_EIG_U}) held += std::min<int64_t>(ctx->ws_bytes[sl], N * N * 8);
+    // the Krylov workspace is released first if that is what it takes
+    int64_t kry = 0;
+    for (int sl : {SLOT_KRY_B, SLOT_KRY_W, SLOT_KRY_T, SLOT_KRY_Y}) kry += ctx->ws_bytes[sl];
+    const double need = 4.0 * 8.0 * (double)N * (double)N * 1.02 - (double)held;
+    if (need > (double)free_b + (double)kry) {
+      char buf[256];
+      snprintf(buf, sizeof buf,
+               "eigen: the block Lanczos did not converge within its subspace limit and the dense fallback does "
+               "not fit (needs %.1f GB more, %.1f GB free);", need / 1e9, ((double)free_b + (double)kry) / 1e9);
+      set_error(std::string(buf) + kry_diag);
+      return BIGKRLS_ENOCONV;
+    }
+    if (need > (double)free_b) {
+      for (int sl : {SLOT_KRY_B, SLOT_KRY_W, SLOT_KRY_T, SLOT_KRY_Y}) {
+        if (ctx->ws[sl]) { BK_HIP(hipStreamSynchronize(ctx->stream)); BK_HIP(hipFree(ctx->ws[sl])); ctx->ws[sl] = nullptr; ctx->ws_bytes[sl] = 0; }
+      }
+    }
+    if (talk) fprintf(stderr, "[bigkrls] block Lanczos did not converge: dense path;%s\n", kry_diag.c_str());
+    ctx->corrupt_run = false;   // (what the abandoned attempt flagged says nothing about the decomposition that follows)
+    *go_dense = true;
+    return BIGKRLS_OK;
+  }
+
+  // ---- the workspace of the reduction and of the stage-2 back-transform's T factors: sizes, slots, layout, then what a
+  // fresh decomposition starts from and the two small tables the device needs
+  int carve_workspace() {
+    // two-stage (band) reduction is the default above 4 panels; BIGKRLS_EIG=1stage forces the
+    // one-stage (symv) reduction (kept for small n and as a cross-check: the tests run both)
+    const char* eig_env = getenv("BIGKRLS_EIG");
+    two_stage = mode != EIG_FULL || (!(eig_env && std::string(eig_env) == "1stage") && n > 4 * S2_B);
+    // ---- sizes, in doubles. The tiled-symv partial buffers live in the (later) U slot of the divide & conquer
+    const int64_t sv_prow = (N / SV_CW + 2) * N, sv_pcol = 10 * N, sv_prow2 = (N / (SV_CW * 32) + 2) * N;
+    const int64_t u_doubles = std::max<int64_t>(N * N, sv_prow + sv_pcol + sv_prow2 + 16 * 2 * TRD_NB);
+    const int64_t nb64 = N * S2_B;
+    const int64_t maxb = (N + 255) / 256 + 2;
+    const int64_t nmail1 = 2 * maxb * 2 * S2_B;  // pq_resident: 2 buffers x workgroups x 64 word pairs
+    const int64_t nmail = nmail1 + 2 * 16 * 2 * S2_B;   // + 2 buffers x 16 group boxes
+    const int64_t npqc = PQC_MAIL_DOUBLES;   // pq_chol mailbox
+    const int64_t npart = 2 * maxb + 2 * maxb * S2_B + S2_B + S2_B * S2_B + 2 * N + nmail;
+    const int64_t ntall = (N / S2_B + 2) * S2_B * S2_B;
+    const int64_t nfpart = (N / (S1F_CHUNKS * S2_B) + 3) * S2_B * S2_B;   // partial V'Y blocks of the fused small products
+    const int64_t bt_doubles = 7 * nb64 + 8 * S2_B * S2_B + npart + ntall + nfpart + npqc + 2 * N /*taus1, scales1*/ +
+                               (int64_t)S2_LD * N /*AB*/ + N + 8 /*soff as int64*/;
+    const Stage2Plan plan = two_stage ? stage2_plan(n) : Stage2Plan();
+    // reflector blocks of the two panel groups whose trailing update is pending (stage1_to_band)
+    const bool agg = two_stage && mode != EIG_RESUME && n >= S1_AGG_MIN_M + 4 * S2_B;
+    const int64_t agg_blk = N * 4 * S2_B;
+    // T factors of the stage-2 back-transform tasks (BIGKRLS_BT2=seq: reflector-by-reflector kernel)
+    const char* bt2_env = getenv("BIGKRLS_BT2");
+    const bool bt2_wy = two_stage && n_vecs_max > 0 && n >= 3 && !(bt2_env && std::string(bt2_env) == "seq");
+    if (bt2_wy) bt2_toff = bt2_task_offsets(n);
+    const int64_t ntasks = bt2_wy ? bt2_toff.back() : 0;
+    // ---- slots
+    void *pW = nullptr, *pP = nullptr, *pV = nullptr, *pU = nullptr, *p2 = nullptr, *pvv = nullptr, *pt2 = nullptr, *pagg = nullptr;
+    BK_TRY(ws_get(ctx, SLOT_EIG_A, N * N * sizeof(double), &pW));
+    BK_TRY(ws_get(ctx, SLOT_EIG_PANEL, 4 * N * TRD_NB * sizeof(double), &pP));
+    BK_TRY(ws_get(ctx, SLOT_EIG_VEC, (5 * N + 4 * TRD_NB + 2 * ((N + 255) / 256 + 2)) * sizeof(double), &pV));
+    BK_TRY(ws_get(ctx, SLOT_EIG_U, u_doubles * sizeof(double), &pU));
+    if (two_stage) {
+      BK_TRY(ws_get(ctx, SLOT_EIG_BT, bt_doubles * sizeof(double), &p2));
+      BK_TRY(ws_get(ctx, SLOT_EIG_VV, (plan.nrefl * (S2_B + 1) + 16) * sizeof(double), &pvv));
+    }
+    if (bt2_wy)
+      BK_TRY(ws_get(ctx, SLOT_EIG_T2, (ntasks * BT2_G * BT2_G + (int64_t)bt2_toff.size() + 8) * (int64_t)sizeof(double), &pt2));
+    if (agg) BK_TRY(ws_get(ctx, SLOT_EIG_AGG, (4 * agg_blk + 3 * 4 * S2_B * S2_B) * (int64_t)sizeof(double), &pagg));
+    if (bt2_wy) BK_TRY(side_stream_get(ctx));
+    // ---- layout
+    W = (double*)pW;
+    P1 = (double*)pP;
+    P2 = P1 + 2 * N * TRD_NB;
+    d = (double*)pV;
+    e = d + N;
+    tau = e + N;
+    scratch = tau + N;
+    U = (double*)pU;
+    sw = SymvWs{U, U + sv_prow, U + sv_prow + sv_pcol, U + sv_prow + sv_pcol + sv_prow2};
+    if (two_stage) {
+      double* q = (double*)p2;
+      s1.Vp = q; q += nb64;
+      s1.Y = q; q += nb64;
+      s1.Y2 = q; q += nb64;
+      s1.PZ1 = q; q += 2 * nb64;
+      s1.PZ2 = q; q += 2 * nb64;
+      s1.small = q; q += 8 * S2_B * S2_B;
+      s1.part = q; q += npart;
+      s1.mail = s1.part + (npart - nmail);
+      s1.mail2 = s1.mail + nmail1;
+      s1.err = (int*)scratch;
+      s1.Tall = q; q += ntall;
+      s1.fpart = q; q += nfpart;
+      s1.pqc = q; q += npqc;
+      s1.fallback = (int*)scratch + 4;
+      taus1 = q; q += 2 * N;
+      AB = q; q += (int64_t)S2_LD * N;
+      d_soff = (int64_t*)q;
+      VV = (double*)pvv;
+      TT = VV + plan.nrefl * S2_B;
+    }
+    if (bt2_wy) {
+      bt2_T = (double*)pt2;
+      bt2_dtoff = (int64_t*)(bt2_T + ntasks * BT2_G * BT2_G);
+    }
+    if (agg) {
+      double* qa = (double*)pagg;
+      s1.aggPZ1[0] = qa; s1.aggPZ2[0] = qa + agg_blk; s1.aggPZ1[1] = qa + 2 * agg_blk; s1.aggPZ2[1] = qa + 3 * agg_blk;
+      s1.aggC = qa + 4 * agg_blk;
+      s1.aggLd = N;
+    }
+    // ---- contents
+    if (mode == EIG_FULL) BK_TRY(copy_matrix(ctx, A, N, N, lda, W, N));
+    BK_HIP(hipMemsetAsync(d, 0, 3 * N * sizeof(double), st));
+    if (two_stage && mode != EIG_RESUME) {   // (a resumed decomposition keeps the watchdog word of its stage 1)
+      BK_HIP(hipMemsetAsync(s1.mail, 0, nmail * sizeof(double), st));
+      BK_HIP(hipMemsetAsync(s1.err, 0, sizeof(int), st));
+      BK_HIP(hipMemsetAsync(s1.pqc, 0, npqc * sizeof(double), st));
+      BK_HIP(hipMemsetAsync(s1.fallback, 0, sizeof(int), st));
+      BK_HIP(hipMemsetAsync(taus1, 0, 2 * N * sizeof(double), st));
+    }
+    if (two_stage) {
+      // (through the pinned upload arena, sized here for the whole decomposition so that it is not reallocated later;
+      //  the task offsets are not read before bt2_build_t, which ev_fork orders behind everything queued here)
+      const size_t soff_bytes = plan.soff.size() * sizeof(int64_t), toff_bytes = bt2_toff.size() * sizeof(int64_t);
+      PinnedStage up(ctx);
+      BK_TRY(up.reserve(std::max(dc_stage_bytes(n), soff_bytes + toff_bytes + 4096)));
+      BK_TRY(up.put(d_soff, plan.soff.data(), soff_bytes));
+      BK_TRY(up.put(bt2_dtoff, bt2_toff.data(), toff_bytes));
+    }
+    return BIGKRLS_OK;
+  }
+
+  // merged block reflectors of the stage-1 back-transform (BIGKRLS_BT1=panel: one panel per step)
+  int carve_bt1() {
+    const char* bt1_env = getenv("BIGKRLS_BT1");
+    if (!two_stage || n_vecs_max <= 0 || (bt1_env && std::string(bt1_env) == "panel")) return BIGKRLS_OK;
+    LT1 = bt1_grp_for(n) * S2_B;
+    bt1 = bt1_plan(n);
+    void *pvb = nullptr, *ptb = nullptr;
+    BK_TRY(ws_get(ctx, SLOT_EIG_VBIG, (bt1.vtotal + 16) * (int64_t)sizeof(double), &pvb));
+    // per group: the merged T (LT x LT), its Gram matrix (LT x LT), the recurrence's scratch (LT x 64); then the group table
+    const int64_t ng1 = (int64_t)bt1.k0.size();
+    BK_TRY(ws_get(ctx, SLOT_EIG_TBIG,
+                  (ng1 * (2 * LT1 * LT1 + LT1 * S2_B) + 16) * (int64_t)sizeof(double) + (ng1 + 1) * (int64_t)sizeof(Bt1Group),
+                  &ptb));
+    bt1_V = (double*)pvb;
+    bt1_T = (double*)ptb;
+    bt1_G = bt1_T + ng1 * LT1 * LT1;
+    return side_stream_get(ctx);
+  }
+
+  // EIG_SETUP_ONLY: the distributed stage 1 drives the panel steps itself (bigkrls_dev_s1_*): hand it the layout
+  int hand_to_dist() {
+    if (ctx->dist_s1 && ctx->dist_s1_free) ctx->dist_s1_free(ctx->dist_s1);
+    DistS1* ds = new DistS1();
+    ds->n = n;
+    ctx->dist_s1 = ds;
+    ctx->dist_s1_free = [](void* p) { delete (DistS1*)p; };
+    BK_TRY(ds->ops.init(ctx, W, n, taus1, s1));
+    BK_HIP(hipStreamSynchronize(st));   // (the arena slice the sweep offsets were uploaded from is free again)
+    return BIGKRLS_OK;
+  }
+
+  // The one read of a persistent kernel's watchdog word (a stream synchronisation): WD_FIRED when it is set
+  int read_watchdog(const int* word, const Watchdog& which) {
+    int h_err = 0;
+    PinnedFetch pf(ctx, 1);
+    BK_TRY(pf.add(&h_err, word, sizeof(int)));
+    BK_TRY(pf.finish());
+#ifdef BK_FAULT_INJECT
+    // BIGKRLS_FAULT=watchdog / watchdog_bt2 (test build): pretend the watchdog fired on the first attempt
+    const char* fault = getenv("BIGKRLS_FAULT");
+    if (fault && which.fault && std::string(fault) == which.fault && !ctx->no_resident) h_err = 1;
+#endif
+    if (h_err == 0) return BIGKRLS_OK;
+    fired = &which;
+    return WD_FIRED;
+  }
+
+  // ---- A (or the band a distributed stage 1 left in W) -> d, e on the device
+  int reduce_to_tridiagonal() {
+    if (!two_stage) {
+      if (n >= 2) return tridiagonalize(ctx, W, n, d, e, tau, P1, P2, scratch, sw);
+      BK_HIP(hipMemcpyAsync(d, W, sizeof(double), hipMemcpyDeviceToDevice, st));
+      return BIGKRLS_OK;
+    }
+    tick("setup + copy");
+    if (mode == EIG_FULL) BK_TRY(stage1_run(ctx, W, n, taus1, s1));
+    if (mode == EIG_FULL && talk && s1.pqc) {
+      double nfb = 0.0;
+      PinnedFetch pfb(ctx, 1);       // (never a device -> pageable copy: the runtime would pin / unpin the page)
+      BK_TRY(pfb.add(&nfb, s1.pqc + PQC_OFF_SLICES + PQC_NG + 32, sizeof(double)));
+      BK_TRY(pfb.finish());
+      fprintf(stderr, "[bigkrls]   panels left to the Householder kernel by pq_chol: %d\n", (int)nfb);
+    }
+    // the register-resident panel QR: checked before stage 2 consumes the band
+    BK_TRY(read_watchdog(s1.err, WD_STAGE1));
+    tick("stage 1 (dense -> band)");
+    int blocks = (int)std::min<int64_t>(((int64_t)S2_LD * N + 255) / 256, 8192);
+    hipLaunchKernelGGL(s1_extract_band, dim3(blocks), dim3(256), 0, st, (const double*)W, n, AB);
+    BK_CHECK_LAUNCH();
+    if (trace_on()) BK_TRY(trace_point(ctx, st, "R:eig_band", AB, (int64_t)S2_LD * N, mode));
+    // progress flags / error word of the persistent bulge-chasing kernel: the (unused here)
+    // tau and scratch vectors of the one-stage path
+    int* bc_err = (int*)scratch;
+    BK_TRY(stage2_to_tridiag(ctx, AB, n, d_soff, VV, TT, d, e, (int*)tau, bc_err));
+    BK_TRY(fork_lookahead());
+    BK_TRY(read_watchdog(bc_err, WD_STAGE2));
+    tick("stage 2 (band -> tridiagonal)");
+    return BIGKRLS_OK;
+  }
+
+  // What the back-transforms need beyond the reflectors, built on the look-ahead stream from the output of stages 1
+  // and 2 while the main stream goes on with the divide & conquer
+  int fork_lookahead() {
+    if (bt2_T != nullptr) {
+      // on the look-ahead stream, behind the bulge chasing (queued now, while it runs: issuing the ~900 launches of the
+      // merged blocks below takes the host 4 ms): they are not needed before the divide & conquer has finished
+      hipStream_t side = pre_stream();
+      BK_HIP(hipEventRecord(ctx->ev_fork, st));          // the bulge chasing is done
+      lookahead_queued = true;
+      BK_HIP(hipStreamWaitEvent(side, ctx->ev_fork, 0));
+      const int ngroups = (int)bt2_toff.size() - 1, ntmax = (n - 2) / S2_B + 1;
+      BK_TRY(ensure_dyn_smem(ctx, (const void*)bt2_build_t, BT2T_SMEM));
+      hipLaunchKernelGGL(bt2_build_t, dim3((unsigned)(((int64_t)ntmax * ngroups + 3) / 4)), dim3(256), BT2T_SMEM, side, n,
+                         (const int64_t*)d_soff, (const double*)VV, (const double*)TT, (const int64_t*)bt2_dtoff, bt2_T,
+                         ntmax, ngroups);
+      BK_CHECK_LAUNCH();
+      BK_HIP(hipEventRecord(ctx->ev_join2, side));       // what the stage-2 back-transform waits for
+    }
+    if (bt1_V != nullptr) {
+      // The merged block reflectors of the stage-1 back-transform, on the look-ahead stream BEHIND the T factors above
+      // (round 6): after the bulge chasing (its workgroups fill every CU's LDS; sharing the GPU only slows it down),
+      // beside the divide & conquer -- and, since that takes 17 ms at N = 20 000 and these launches 20, beside the first
+      // milliseconds of the stage-2 back-transform, which no longer waits for them: only the stage-1 back-transform does.
+      BK_HIP(hipEventRecord(ctx->ev_fork, st));
+      lookahead_queued = true;
+      BK_HIP(hipStreamWaitEvent(pre_stream(), ctx->ev_fork, 0));
+      const int64_t ng1 = (int64_t)bt1.k0.size();
+      double* bt1_tmp = bt1_G + ng1 * LT1 * LT1;
+      Bt1Group* d_groups = (Bt1Group*)(bt1_tmp + ng1 * LT1 * S2_B + 8);
+      BK_TRY(bt1_precompute(ctx, W, n, taus1, s1.Tall, bt1, bt1_V, bt1_T, bt1_G, bt1_tmp, d_groups, pre_stream()));
+      BK_HIP(hipEventRecord(ctx->ev_join, pre_stream()));
+    }
+    return BIGKRLS_OK;
+  }
+
+  int fetch_and_check_tridiagonal() {
+    hd.resize(n);
+    he.resize(n);
+    PinnedFetch pf(ctx, 2 * N);
+    BK_TRY(pf.add(hd.data(), d, N * sizeof(double)));
+    BK_TRY(pf.add(he.data(), e, N * sizeof(double)));
+    BK_TRY(pf.finish());
+    for (int i = 0; i < n; ++i)
+      if (!std::isfinite(hd[i]) || (i < n - 1 && !std::isfinite(he[i]))) {
+        set_error("eigen: non-finite entries after tridiagonalisation (NaN/Inf in the input?)");
+        ctx->corrupt_run = true;
+        return BIGKRLS_EINVAL;
+      }
+    if (trace_on()) {
+      BK_TRY(trace_host("R:eig_d", hd.data(), n, mode));
+      BK_TRY(trace_host("R:eig_e", he.data(), n - 1, mode));
+    }
+    return BIGKRLS_OK;
+  }
+
+  // ---- divide & conquer; the values and the kept columns of the tridiagonal matrix's eigenvectors to the caller's buffers
+  int solve() {
+    void *pQ0 = nullptr, *pQ1 = nullptr;
+    BK_TRY(ws_get(ctx, SLOT_EIG_Q0, N * N * sizeof(double), &pQ0));
+    BK_TRY(ws_get(ctx, SLOT_EIG_Q1, N * N * sizeof(double), &pQ1));
+    BK_TRY(divide_conquer(ctx, n, hd, he, (double*)pQ0, (double*)pQ1, U, n_vals, n_vecs_max, keep_thresh, vals_desc,
+                          src_cols, &Qfin));
+    tick("divide & conquer");
+    if (trace_on()) BK_TRY(trace_host("R:eig_vals", vals_desc.data(), n_vals, (int64_t)src_cols.size()));
+    PinnedStage up(ctx);      // (the divide & conquer ended with a synchronisation: the arena is free)
+    BK_TRY(up.reserve((size_t)n_vals * sizeof(double) + (size_t)n * sizeof(int) + 4096));
+    BK_TRY(up.put(vals, vals_desc.data(), n_vals * sizeof(double)));
+    nv = (int)src_cols.size();
+    if (h_n_vecs) *h_n_vecs = nv;
+    if (nv == 0 || n_vecs_max <= 0) return BIGKRLS_OK;
+    void* pidx = nullptr;
+    BK_TRY(ws_get(ctx, SLOT_EIG_INT, (int64_t)10 * n * sizeof(int), &pidx));
+    int* d_src = (int*)pidx;
+    BK_TRY(up.put(d_src, src_cols.data(), nv * sizeof(int)));
+    int blocks = (int)std::min<int64_t>((N * nv + 255) / 256, 8192);
+    hipLaunchKernelGGL(gather_cols, dim3(blocks), dim3(256), 0, st, n, nv, (const int*)d_src, (const double*)Qfin, N, vecs,
+                       ldv);
+    BK_CHECK_LAUNCH();
+    return BIGKRLS_OK;
+  }
+
+  // Multi-GPU: every rank runs the (replicated) reduction and divide & conquer, but
+  // back-transforms only its own slice of the kept eigenvector columns; the other columns are
+  // returned as zeros, so that an all-reduce (sum) over the ranks assembles Q exactly.
+  int back_transform_slice() {
+    if (nv == 0 || n_vecs_max <= 0) return BIGKRLS_OK;
+    const int pc0 = (int)((int64_t)nv * part_index / part_count);
+    const int pc1 = (int)((int64_t)nv * (part_index + 1) / part_count);
+    if (pc0 > 0) BK_HIP(hipMemsetAsync(vecs, 0, (size_t)pc0 * ldv * sizeof(double), st));
+    if (pc1 < nv) BK_HIP(hipMemsetAsync(vecs + (int64_t)pc1 * ldv, 0, (size_t)(nv - pc1) * ldv * sizeof(double), st));
+    double* pvecs = vecs + (int64_t)pc0 * ldv;
+    const int pnv = pc1 - pc0;
+    if (pnv <= 0) return BIGKRLS_OK;
+    if (!two_stage) return back_transform(ctx, W, n, tau, pvecs, ldv, pnv);
+    tick("gather kept columns");
+    if (bt2_T != nullptr) BK_HIP(hipStreamWaitEvent(st, ctx->ev_join2, 0));
+    // (the watchdog word of the bulge chasing, read back as zero above, now serves the persistent back-transform)
+    bt2_err = (bt2_T != nullptr) ? (int*)scratch : nullptr;
+    BK_TRY(back_transform_stage2(ctx, n, d_soff, VV, TT, pvecs, ldv, pnv, bt2_dtoff, bt2_T,
+                                 bt2_toff.empty() ? 0 : bt2_toff.back(), bt2_err));
+    tick("back-transform stage 2");
+    void* pw12 = nullptr;
+    const int64_t bt1_w = (int64_t)bt1_grp_for(n) * S2_B;
+    BK_TRY(ws_get(ctx, SLOT_EIG_Z, 2 * bt1_w * pnv * sizeof(double), &pw12));
+    if (bt1_V != nullptr) {
+      BK_HIP(hipStreamWaitEvent(st, ctx->ev_join, 0));
+      BK_TRY(back_transform_stage1_grouped(ctx, n, bt1, bt1_V, bt1_T, pvecs, ldv, pnv, (double*)pw12,
+                                           (double*)pw12 + bt1_w * pnv));
+    } else {
+      BK_TRY(back_transform_stage1(ctx, W, n, taus1, pvecs, ldv, pnv, s1.Vp, s1.Tall, (double*)pw12,
+                                   (double*)pw12 + (int64_t)S2_B * pnv));
+    }
+    tick("back-transform stage 1");
+    return BIGKRLS_OK;
+  }
+
+  // the successful end of the look-ahead work, also when no column was back-transformed: the main stream waits for it
+  int join_lookahead() {
+    if (bt2_T != nullptr) BK_HIP(hipStreamWaitEvent(st, ctx->ev_join2, 0));
+    if (bt1_V != nullptr) BK_HIP(hipStreamWaitEvent(st, ctx->ev_join, 0));
+    return BIGKRLS_OK;
+  }
+
+  // the test build's wrong results without an error (the read-backs of read_watchdog and route_krylov's full device
+  // are the other hooks); nothing in the shipped library
+  int inject_faults() {
+#ifdef BK_FAULT_INJECT
+    // BIGKRLS_FAULT=eig_garbage (test build): the FIRST decomposition after the variable is set comes back with its
+    // middle kept eigenvector scaled by 1.001 -- a wrong result without any error, the kind the fit's verification
+    // (Fit::verify_decomposition, csrc/fit.hip) exists for; =eig_garbage_always: every decomposition does
+    static int garbage_calls = 0;
+    const char* fault = getenv("BIGKRLS_FAULT");
+    const bool once = fault && std::string(fault) == "eig_garbage", always = fault && std::string(fault) == "eig_garbage_always";
+    if (!once && !always) garbage_calls = 0;
+    // (a column the fit's check samples: the middle kept one; in a multi-GPU fit the last one, owned by the last rank)
+    const int gc = part_count == 1 ? nv / 2 : nv - 1;
+    if ((always || (once && garbage_calls++ == 0)) && nv > 0 && n_vecs_max > 0 && part_index == part_count - 1)
+      BK_TRY(scale(ctx, N, 1.001, vecs + (int64_t)gc * ldv));
+    // BIGKRLS_FAULT=eig_swap / eig_swap_always: two kept eigenvectors exchanged -- every column still has norm 1, the
+    // combinations Q r keep |Q r|^2 = k: only the comparison with K Q r (on one GPU deferred to the fit's pass over K
+    // for the marginal effects, Fit::verify_deferred in csrc/fit.hip) can see it
+    static int swap_calls = 0;
+    const bool sonce = fault && std::string(fault) == "eig_swap", salways = fault && std::string(fault) == "eig_swap_always";
+    if (!sonce && !salways) swap_calls = 0;
+    if ((salways || (sonce && swap_calls++ == 0)) && nv > 3 && n_vecs_max > 0 && part_count == 1 && keep_thresh >= 0.0) {
+      fault_swap_cols<<<(N + 255) / 256, 256, 0, st>>>(vecs + (int64_t)(nv / 2) * ldv, vecs + (int64_t)(nv / 2 + 1) * ldv, (int)N);
+      BK_HIP(hipGetLastError());
+    }
+    // BIGKRLS_FAULT=vals_ulp (set in ONE rank's process): this rank's copy of the replicated eigenvalues differs from its
+    // peers' in the last bit of one kept value -- a valid decomposition the fit's check against K lets through; the
+    // multi-GPU fit must still run its lambda search on identical values everywhere (Fit::fetch_and_agree_eigenvalues: rank 0's)
+    if (fault && std::string(fault) == "vals_ulp" && nv > 1 && keep_thresh >= 0.0) {   // (not the inner solves of the Lanczos)
+      fault_nudge_ulp<<<1, 1, 0, st>>>(vals + nv / 2);
+      BK_HIP(hipGetLastError());
+    }
+#endif
+    return BIGKRLS_OK;
+  }
+
+  int finish() {
+    if (trace_on() && nv > 0 && n_vecs_max > 0) {
+      const int tc0 = (int)((int64_t)nv * part_index / part_count), tc1 = (int)((int64_t)nv * (part_index + 1) / part_count);
+      if (tc1 > tc0 && ldv == N) BK_TRY(trace_point(ctx, st, "L:eig_Qpart", vecs + (int64_t)tc0 * ldv, (int64_t)(tc1 - tc0) * ldv, tc0));
+    }
+    // the persistent stage-2 back-transform: Z is garbage if its watchdog fired. Either way the main stream, which has
+    // waited for the look-ahead work, is synchronised
+    if (bt2_err != nullptr) BK_TRY(read_watchdog(bt2_err, WD_BT2));
+    else BK_HIP(hipStreamSynchronize(st));
+    lookahead_queued = false;
+    return BIGKRLS_OK;
+  }
+
+  int phases() {
+    BK_TRY(carve_workspace());
+    if (mode == EIG_SETUP_ONLY) return hand_to_dist();
+    BK_TRY(carve_bt1());
+    BK_TRY(reduce_to_tridiagonal());
+    BK_TRY(fetch_and_check_tridiagonal());
+    BK_TRY(solve());
+    BK_TRY(back_transform_slice());
+    BK_TRY(join_lookahead());
+    BK_TRY(inject_faults());
+    return finish();
+  }
+
+  // The watchdog of a persistent kernel (pq_resident / bc_resident / the stage-2 back-transform) fired: its workgroups
+  // were not co-resident, e.g. because another process or stream held part of the GPU. A is untouched, so the
+  // decomposition is redone once, in the same call, with the launch-per-step kernels (no spinning).
+  int replay() {
+    (void)drain_streams(ctx);
+    if (ctx->no_resident) {
+      set_error("eigen: watchdog of a persistent kernel fired although none should have been launched");
+      return BIGKRLS_EHIP;
+    }
+    if (talk) fprintf(stderr, "[bigkrls] eigen: persistent-kernel watchdog fired; retrying with per-step launches\n");
+    ctx->n_replayed++;
+    ctx->no_resident = true;
+    const int rc = DenseEig(static_cast<const EigArgs&>(*this)).run();
+    ctx->no_resident = false;
+    return rc;
+  }
+
+  int run() {
+    phase = Stopwatch();
+    const int rc = phases();
+    if (lookahead_queued) (void)hipStreamSynchronize(pre_stream());   // (every exit but the successful one)
+    lookahead_queued = false;
+    if (rc != WD_FIRED) return rc;
+    if (mode == EIG_RESUME) {
+      set_error(fired->resume_error);
+      return BK_EWATCHDOG;     // the caller replays the decomposition on every rank (Fit::eigen_dist_dense, csrc/fit.hip)
+    }
+    return replay();
+  }
+};
+
+}  // namespace
 
 int eigen(bigkrls_ctx* ctx, const double* A, int64_t n64, int64_t lda, int64_t n_vals, double* vals,
           int64_t n_vecs_max, double keep_thresh, double* vecs, int64_t ldv, int64_t* h_n_vecs,
@@ -2909,432 +3431,15 @@ int eigen(bigkrls_ctx* ctx, const double* A, int64_t n64, int64_t lda, int64_t n
     BK_REQUIRE(n_vecs_max == 0 || (vecs && ldv >= n64), "eigen: bad eigenvector buffer");
   }
   if (mode != EIG_FULL) BK_REQUIRE(n64 > 4 * S2_B, "eigen: the distributed dense path needs n > 256");
+  DenseEig dense(EigArgs{ctx, A, n64, lda, n_vals, vals, n_vecs_max, keep_thresh, vecs, ldv, h_n_vecs, part_index,
+                         part_count, mode});
   if (mode == EIG_FULL) {
-    // Neig << N: block Lanczos (the reference switches to eigs_sym for Neig < N, src/eigen.cpp:18-22);
-    // BIGKRLS_EIGK=dense keeps the dense path, =krylov forces the iterative one when Neig <= N/4
-    const char* ek = getenv("BIGKRLS_EIGK");
-    const std::string mode = ek ? ek : "";
-    // (measured: N = 12 000, Neig = 512 dense 0.33 s vs 0.47 s; N = 50 000, Neig = 512 dense 6.9 s vs 0.88 s)
-    const bool small_k = n_vals * 8 <= n64 && n64 >= 16384;
-    if (mode != "dense" && n_vals < n64 && (small_k || (mode == "krylov" && n_vals * 4 <= n64 && n64 >= 1024))) {
-      KTimes whole;
-      whole.A = A;
-      whole.lda = lda;
-      const int rc = eigen_krylov(ctx, whole, n64, n_vals, vals, n_vecs_max, keep_thresh, vecs, ldv, h_n_vecs,
-                                  part_index, part_count);
-      // A spectrum the iteration does not resolve within its subspace limit (or a breakdown) is
-      // handed to the dense path in the same call -- A is untouched. Only an explicit
-      // BIGKRLS_EIGK=krylov reports the non-convergence.
-      if (rc != BIGKRLS_ENOCONV || mode == "krylov") return rc;
-      // ... provided its workspace fits: W, Q0, Q1, U = 4 n^2 doubles beside what the caller holds (320 GB at
-      // n = 100 000). Otherwise the non-convergence is the answer, with what the iteration saw.
-      {
-        size_t free_b = 0, total_b = 0;
-        BK_HIP(hipMemGetInfo(&free_b, &total_b));
-#ifdef BK_FAULT_INJECT
-        if (const char* fault = getenv("BIGKRLS_FAULT_NOFIT")) {   // (test build) pretend the device is this full
-          if (atoi(fault) != 0) free_b = 0;
-        }
-#endif
-        int64_t held = 0;
-        for (int sl : {SLOT_EIG_A, SLOT_EIG_Q0, SLOT_EIG_Q1, SLOT_EIG_U}) held += std::min<int64_t>(ctx->ws_bytes[sl], n64 * n64 * 8);
-        // the Krylov workspace is released first if that is what it takes
-        int64_t kry = 0;
-        for (int sl : {SLOT_KRY_B, SLOT_KRY_W, SLOT_KRY_T, SLOT_KRY_Y}) kry += ctx->ws_bytes[sl];
-        const double need = 4.0 * 8.0 * (double)n64 * (double)n64 * 1.02 - (double)held;
-        if (need > (double)free_b + (double)kry) {
-          char buf[256];
-          snprintf(buf, sizeof buf,
-                   "eigen: the block Lanczos did not converge within its subspace limit and the dense fallback does "
-                   "not fit (needs %.1f GB more, %.1f GB free);", need / 1e9, ((double)free_b + (double)kry) / 1e9);
-          set_error(std::string(buf) + kry_diag);
-          return BIGKRLS_ENOCONV;
-        }
-        if (need > (double)free_b) {
-          for (int sl : {SLOT_KRY_B, SLOT_KRY_W, SLOT_KRY_T, SLOT_KRY_Y}) {
-            if (ctx->ws[sl]) { BK_HIP(hipStreamSynchronize(ctx->stream)); BK_HIP(hipFree(ctx->ws[sl])); ctx->ws[sl] = nullptr; ctx->ws_bytes[sl] = 0; }
-          }
-        }
-      }
-      if (getenv("BIGKRLS_VERBOSE"))
-        fprintf(stderr, "[bigkrls] block Lanczos did not converge: dense path;%s\n", kry_diag.c_str());
-    }
+    ctx->corrupt_run = false;   // (the flag speaks of this decomposition only: see common.h)
+    bool go_dense = false;
+    const int rc = dense.route_krylov(&go_dense);
+    if (!go_dense) return rc;
   }
-  const int n = (int)n64;
-  const int64_t N = n;
-  hipStream_t st = ctx->stream;
-  // BIGKRLS_VERBOSE: wall-clock of each phase on stderr (adds a stream synchronisation per phase)
-  const bool verbose = getenv("BIGKRLS_VERBOSE") != nullptr;
-  auto t_phase = std::chrono::steady_clock::now();
-  auto tick = [&](const char* name) {
-    if (!verbose) return;
-    (void)hipStreamSynchronize(st);
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[bigkrls] eigen n=%d: %-28s %8.2f ms\n", n, name,
-            std::chrono::duration<double, std::milli>(now - t_phase).count());
-    t_phase = now;
-  };
-  void *pW = nullptr, *pQ0 = nullptr, *pQ1 = nullptr, *pU = nullptr, *pP = nullptr, *pV = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_EIG_A, N * N * sizeof(double), &pW));
-  BK_TRY(ws_get(ctx, SLOT_EIG_PANEL, 4 * N * TRD_NB * sizeof(double), &pP));
-  BK_TRY(ws_get(ctx, SLOT_EIG_VEC, (5 * N + 4 * TRD_NB + 2 * ((N + 255) / 256 + 2)) * sizeof(double), &pV));
-  double* W = (double*)pW;
-  double* P1 = (double*)pP;
-  double* P2 = P1 + 2 * N * TRD_NB;
-  double* d = (double*)pV;
-  double* e = d + N;
-  double* tau = e + N;
-  double* scratch = tau + N;
-  if (mode == EIG_FULL) BK_TRY(copy_matrix(ctx, A, N, N, lda, W, N));
-  BK_HIP(hipMemsetAsync(d, 0, 3 * N * sizeof(double), st));
-  // tiled-symv partial buffers live in the (later) U slot of the divide & conquer
-  const int64_t sv_prow = (N / SV_CW + 2) * N, sv_pcol = 10 * N, sv_prow2 = (N / (SV_CW * 32) + 2) * N;
-  const int64_t u_doubles = std::max<int64_t>(N * N, sv_prow + sv_pcol + sv_prow2 + 16 * 2 * TRD_NB);
-  BK_TRY(ws_get(ctx, SLOT_EIG_U, u_doubles * sizeof(double), &pU));
-  SymvWs sw{(double*)pU, (double*)pU + sv_prow, (double*)pU + sv_prow + sv_pcol,
-            (double*)pU + sv_prow + sv_pcol + sv_prow2};
-  // two-stage (band) reduction is the default above 4 panels; BIGKRLS_EIG=1stage forces the
-  // one-stage (symv) reduction (kept for small n and as a cross-check: the tests run both)
-  const char* eig_env = getenv("BIGKRLS_EIG");
-  const bool two_stage = mode != EIG_FULL || (!(eig_env && std::string(eig_env) == "1stage") && n > 4 * S2_B);
-  double *taus1 = nullptr, *AB = nullptr, *VV = nullptr, *TT = nullptr;
-  int64_t* d_soff = nullptr;
-  std::vector<int64_t> bt2_toff;      // (source of an asynchronous copy: lives until the function returns)
-  double* bt2_T = nullptr;
-  int64_t* bt2_dtoff = nullptr;
-  int* bt2_err = nullptr;             // watchdog word of the persistent stage-2 back-transform (when it ran)
-  Bt1Plan bt1;
-  double *bt1_V = nullptr, *bt1_T = nullptr;
-  Stage1Ws s1{};
-  if (two_stage) {
-    const int64_t nb64 = N * S2_B;
-    void *p2 = nullptr, *pvv = nullptr;
-    const int64_t maxb = (N + 255) / 256 + 2;
-    const int64_t nmail1 = 2 * maxb * 2 * S2_B;  // pq_resident: 2 buffers x workgroups x 64 word pairs
-    const int64_t nmail = nmail1 + 2 * 16 * 2 * S2_B;   // + 2 buffers x 16 group boxes
-    const int64_t npqc = PQC_MAIL_DOUBLES;   // pq_chol mailbox
-    const int64_t npart = 2 * maxb + 2 * maxb * S2_B + S2_B + S2_B * S2_B + 2 * N + nmail;
-    const int64_t ntall = (N / S2_B + 2) * S2_B * S2_B;
-    const int64_t nfpart = (N / (S1F_CHUNKS * S2_B) + 3) * S2_B * S2_B;   // partial V'Y blocks of the fused small products
-    const int64_t need = 7 * nb64 + 8 * S2_B * S2_B + npart + ntall + nfpart + npqc + 2 * N /*taus1, scales1*/ +
-                         (int64_t)S2_LD * N /*AB*/ + N + 8 /*soff as int64*/;
-    BK_TRY(ws_get(ctx, SLOT_EIG_BT, need * sizeof(double), &p2));
-    double* q = (double*)p2;
-    s1.Vp = q; q += nb64;
-    s1.Y = q; q += nb64;
-    s1.Y2 = q; q += nb64;
-    s1.PZ1 = q; q += 2 * nb64;
-    s1.PZ2 = q; q += 2 * nb64;
-    s1.small = q; q += 8 * S2_B * S2_B;
-    s1.part = q; q += npart;
-    s1.mail = s1.part + (npart - nmail);
-    s1.mail2 = s1.mail + nmail1;
-    s1.err = (int*)scratch;
-    if (mode != EIG_RESUME) {   // (a resumed decomposition keeps the watchdog word of its stage 1)
-      BK_HIP(hipMemsetAsync(s1.mail, 0, nmail * sizeof(double), st));
-      BK_HIP(hipMemsetAsync(s1.err, 0, sizeof(int), st));
-    }
-    s1.Tall = q; q += ntall;
-    s1.fpart = q; q += nfpart;
-    s1.pqc = q; q += npqc;
-    s1.fallback = (int*)scratch + 4;
-    if (mode != EIG_RESUME) {
-      BK_HIP(hipMemsetAsync(s1.pqc, 0, npqc * sizeof(double), st));
-      BK_HIP(hipMemsetAsync(s1.fallback, 0, sizeof(int), st));
-    }
-    taus1 = q; q += 2 * N;
-    AB = q; q += (int64_t)S2_LD * N;
-    d_soff = (int64_t*)q;
-    Stage2Plan plan = stage2_plan(n);
-    BK_TRY(ws_get(ctx, SLOT_EIG_VV, (plan.nrefl * (S2_B + 1) + 16) * sizeof(double), &pvv));
-    VV = (double*)pvv;
-    TT = VV + plan.nrefl * S2_B;
-    {
-      // (through the pinned upload arena, sized here for the whole decomposition so that it is not reallocated later)
-      PinnedStage up(ctx);
-      BK_TRY(up.reserve(std::max(dc_stage_bytes(n), plan.soff.size() * sizeof(int64_t) + 4096)));
-      BK_TRY(up.put(d_soff, plan.soff.data(), plan.soff.size() * sizeof(int64_t)));
-    }
-    if (mode != EIG_RESUME) BK_HIP(hipMemsetAsync(taus1, 0, 2 * N * sizeof(double), st));
-    if ((mode == EIG_FULL || mode == EIG_SETUP_ONLY) && n >= S1_AGG_MIN_M + 4 * S2_B) {
-      // reflector blocks of the two panel groups whose trailing update is pending (stage1_to_band)
-      void* pagg = nullptr;
-      const int64_t blk = N * 4 * S2_B;
-      BK_TRY(ws_get(ctx, SLOT_EIG_AGG, (4 * blk + 3 * 4 * S2_B * S2_B) * (int64_t)sizeof(double), &pagg));
-      double* qa = (double*)pagg;
-      s1.aggPZ1[0] = qa; s1.aggPZ2[0] = qa + blk; s1.aggPZ1[1] = qa + 2 * blk; s1.aggPZ2[1] = qa + 3 * blk;
-      s1.aggC = qa + 4 * blk;
-      s1.aggLd = N;
-    }
-    if (mode == EIG_SETUP_ONLY) {
-      // the distributed stage 1 drives the panel steps itself (bigkrls_dev_s1_*): hand it the layout
-      if (ctx->dist_s1 && ctx->dist_s1_free) ctx->dist_s1_free(ctx->dist_s1);
-      DistS1* ds = new DistS1();
-      ds->n = n;
-      ctx->dist_s1 = ds;
-      ctx->dist_s1_free = [](void* p) { delete (DistS1*)p; };
-      BK_TRY(ds->ops.init(ctx, W, n, taus1, s1));
-      BK_HIP(hipStreamSynchronize(st));   // plan.soff (host) was the source of an async copy
-      return BIGKRLS_OK;
-    }
-    tick("setup + copy");
-    if (mode == EIG_FULL) BK_TRY(stage1_run(ctx, W, n, taus1, s1));
-    if (mode == EIG_FULL && getenv("BIGKRLS_VERBOSE") && s1.pqc) {
-      double nfb = 0.0;
-      PinnedFetch pfb(ctx, 1);       // (never a device -> pageable copy: the runtime would pin / unpin the page)
-      BK_TRY(pfb.add(&nfb, s1.pqc + PQC_OFF_SLICES + PQC_NG + 32, sizeof(double)));
-      BK_TRY(pfb.finish());
-      fprintf(stderr, "[bigkrls]   panels left to the Householder kernel by pq_chol: %d\n", (int)nfb);
-    }
-    {
-      // watchdog word of the register-resident panel QR: checked before stage 2 consumes the band
-      int h_err1 = 0;
-      PinnedFetch pf1(ctx, 1);
-      BK_TRY(pf1.add(&h_err1, s1.err, sizeof(int)));
-      BK_TRY(pf1.finish());
-#ifdef BK_FAULT_INJECT
-      // BIGKRLS_FAULT=watchdog (test build): pretend the watchdog fired on the first attempt
-      const char* fault = getenv("BIGKRLS_FAULT");
-      if (fault && std::string(fault) == "watchdog" && !ctx->no_resident) h_err1 = 1;
-#endif
-      if (h_err1 != 0 && mode == EIG_RESUME) {
-        set_error("eigen: watchdog of the register-resident panel QR fired during the distributed stage 1");
-        return BK_EWATCHDOG;     // the caller replays the decomposition on every rank (Fit::eigen_dist_dense, csrc/fit.hip)
-      }
-      if (h_err1 != 0) return eigen_retry_without_resident(ctx, A, n64, lda, n_vals, vals, n_vecs_max, keep_thresh,
-                                                           vecs, ldv, h_n_vecs, part_index, part_count);
-    }
-    tick("stage 1 (dense -> band)");
-    int blocks = (int)std::min<int64_t>(((int64_t)S2_LD * N + 255) / 256, 8192);
-    hipLaunchKernelGGL(s1_extract_band, dim3(blocks), dim3(256), 0, st, (const double*)W, n, AB);
-    BK_CHECK_LAUNCH();
-    if (trace_on()) BK_TRY(trace_point(ctx, st, "R:eig_band", AB, (int64_t)S2_LD * N, mode));
-    // progress flags / error word of the persistent bulge-chasing kernel: the (unused here)
-    // tau and scratch vectors of the one-stage path
-    int* bc_err = (int*)scratch;
-    // merged block reflectors of the stage-1 back-transform (BIGKRLS_BT1=panel: one panel per step):
-    // built on the look-ahead stream from stage 1's output while the main stream goes on
-    const char* bt1_env = getenv("BIGKRLS_BT1");
-    const bool bt1_grouped = n_vecs_max > 0 && !(bt1_env && std::string(bt1_env) == "panel");
-    const int64_t LT1 = bt1_grp_for(n) * S2_B;
-    double* bt1_G = nullptr;
-    if (bt1_grouped) {
-      bt1 = bt1_plan(n);
-      void *pvb = nullptr, *ptb = nullptr;
-      BK_TRY(ws_get(ctx, SLOT_EIG_VBIG, (bt1.vtotal + 16) * (int64_t)sizeof(double), &pvb));
-      // per group: the merged T (LT x LT), its Gram matrix (LT x LT), the recurrence's scratch (LT x 64); then the group table
-      const int64_t ng1 = (int64_t)bt1.k0.size();
-      BK_TRY(ws_get(ctx, SLOT_EIG_TBIG,
-                    (ng1 * (2 * LT1 * LT1 + LT1 * S2_B) + 16) * (int64_t)sizeof(double) + (ng1 + 1) * (int64_t)sizeof(Bt1Group),
-                    &ptb));
-      bt1_V = (double*)pvb;
-      bt1_T = (double*)ptb;
-      bt1_G = bt1_T + ng1 * LT1 * LT1;
-      BK_TRY(side_stream_get(ctx));
-    }
-    BK_TRY(stage2_to_tridiag(ctx, AB, n, d_soff, VV, TT, d, e, (int*)tau, bc_err));
-    // (BIGKRLS_BG=1, an A/B switch: what is precomputed for the back-transforms goes to a lowest-priority stream instead
-    //  of the high-priority look-ahead stream. Measured slower: C3 0.4029-0.4043 vs 0.4009-0.4012 s, same box
-    //  (profiles/r06/r06g_bg_stream_ab_*.log) -- the merged blocks then finish late behind the stage-2 back-transform)
-    auto pre_stream = [&]() -> hipStream_t {
-      static const bool bg = [] { const char* e = getenv("BIGKRLS_BG"); return e && e[0] == '1'; }();
-      return bg ? ctx->bg_stream : ctx->side_stream;
-    };
-    // T factors of the stage-2 back-transform tasks (BIGKRLS_BT2=seq: reflector-by-reflector kernel)
-    const char* bt2_env = getenv("BIGKRLS_BT2");
-    if (n_vecs_max > 0 && n >= 3 && !(bt2_env && std::string(bt2_env) == "seq")) {
-      bt2_toff = bt2_task_offsets(n);
-      const int64_t ntasks = bt2_toff.back();
-      void* pt2 = nullptr;
-      BK_TRY(ws_get(ctx, SLOT_EIG_T2,
-                    (ntasks * BT2_G * BT2_G + (int64_t)bt2_toff.size() + 8) * (int64_t)sizeof(double), &pt2));
-      bt2_T = (double*)pt2;
-      bt2_dtoff = (int64_t*)(bt2_T + ntasks * BT2_G * BT2_G);
-      // on the look-ahead stream, behind the bulge chasing (queued now, while it runs: issuing the ~900 launches of the
-      // merged blocks below takes the host 4 ms): they are not needed before the divide & conquer has finished
-      BK_TRY(side_stream_get(ctx));
-      hipStream_t side = pre_stream();
-      BK_HIP(hipEventRecord(ctx->ev_fork, st));          // the bulge chasing is done
-      BK_HIP(hipStreamWaitEvent(side, ctx->ev_fork, 0));
-      BK_HIP(hipMemcpyAsync(bt2_dtoff, bt2_toff.data(), bt2_toff.size() * sizeof(int64_t), hipMemcpyHostToDevice, side));
-      const int ngroups = (int)bt2_toff.size() - 1, ntmax = (n - 2) / S2_B + 1;
-      BK_TRY(ensure_dyn_smem(ctx, (const void*)bt2_build_t, BT2T_SMEM));
-      hipLaunchKernelGGL(bt2_build_t, dim3((unsigned)(((int64_t)ntmax * ngroups + 3) / 4)), dim3(256), BT2T_SMEM, side, n,
-                         (const int64_t*)d_soff, (const double*)VV, (const double*)TT, (const int64_t*)bt2_dtoff, bt2_T,
-                         ntmax, ngroups);
-      BK_CHECK_LAUNCH();
-      BK_HIP(hipEventRecord(ctx->ev_join2, side));       // what the stage-2 back-transform waits for
-    }
-    if (bt1_grouped) {
-      // The merged block reflectors of the stage-1 back-transform, on the look-ahead stream BEHIND the T factors above
-      // (round 6): after the bulge chasing (its workgroups fill every CU's LDS; sharing the GPU only slows it down),
-      // beside the divide & conquer -- and, since that takes 17 ms at N = 20 000 and these launches 20, beside the first
-      // milliseconds of the stage-2 back-transform, which no longer waits for them: only the stage-1 back-transform does.
-      BK_HIP(hipEventRecord(ctx->ev_fork, st));
-      BK_HIP(hipStreamWaitEvent(pre_stream(), ctx->ev_fork, 0));
-      {
-        const int64_t ng1 = (int64_t)bt1.k0.size();
-        double* bt1_tmp = bt1_G + ng1 * LT1 * LT1;
-        Bt1Group* d_groups = (Bt1Group*)(bt1_tmp + ng1 * LT1 * S2_B + 8);
-        BK_TRY(bt1_precompute(ctx, W, n, taus1, s1.Tall, bt1, bt1_V, bt1_T, bt1_G, bt1_tmp, d_groups, pre_stream()));
-      }
-      BK_HIP(hipEventRecord(ctx->ev_join, pre_stream()));
-    }
-    int h_err = 0;
-    PinnedFetch pf2(ctx, 1);
-    BK_TRY(pf2.add(&h_err, bc_err, sizeof(int)));
-    BK_TRY(pf2.finish());              // (also: plan.soff (host) was the source of an async copy)
-    tick("stage 2 (band -> tridiagonal)");
-    if (h_err != 0 && mode == EIG_RESUME) {
-      set_error("eigen: watchdog of the LDS-resident bulge chasing fired after the distributed stage 1");
-      return BK_EWATCHDOG;
-    }
-    if (h_err != 0)
-      return eigen_retry_without_resident(ctx, A, n64, lda, n_vals, vals, n_vecs_max, keep_thresh, vecs, ldv,
-                                          h_n_vecs, part_index, part_count);
-  } else if (n >= 2) {
-    BK_TRY(tridiagonalize(ctx, W, n, d, e, tau, P1, P2, scratch, sw));
-  } else {
-    BK_HIP(hipMemcpyAsync(d, W, sizeof(double), hipMemcpyDeviceToDevice, st));
-  }
-  std::vector<double> hd(n), he(n);
-  {
-    PinnedFetch pf(ctx, 2 * N);
-    BK_TRY(pf.add(hd.data(), d, N * sizeof(double)));
-    BK_TRY(pf.add(he.data(), e, N * sizeof(double)));
-    BK_TRY(pf.finish());
-  }
-  for (int i = 0; i < n; ++i)
-    if (!std::isfinite(hd[i]) || (i < n - 1 && !std::isfinite(he[i]))) {
-      set_error("eigen: non-finite entries after tridiagonalisation (NaN/Inf in the input?)");
-      ctx->corrupt_run = true;
-      return BIGKRLS_EINVAL;
-    }
-  if (trace_on()) {
-    BK_TRY(trace_host("R:eig_d", hd.data(), n, mode));
-    BK_TRY(trace_host("R:eig_e", he.data(), n - 1, mode));
-  }
-  BK_TRY(ws_get(ctx, SLOT_EIG_Q0, N * N * sizeof(double), &pQ0));
-  BK_TRY(ws_get(ctx, SLOT_EIG_Q1, N * N * sizeof(double), &pQ1));
-  std::vector<double> vals_desc;
-  std::vector<int> src_cols;
-  double* Qfin = nullptr;
-  BK_TRY(divide_conquer(ctx, n, hd, he, (double*)pQ0, (double*)pQ1, (double*)pU, n_vals,
-                        n_vecs_max, keep_thresh, vals_desc, src_cols, &Qfin));
-  tick("divide & conquer");
-  if (trace_on()) {
-    BK_TRY(trace_host("R:eig_vals", vals_desc.data(), n_vals, (int64_t)src_cols.size()));
-  }
-  PinnedStage up(ctx);      // (the divide & conquer ended with a synchronisation: the arena is free)
-  BK_TRY(up.reserve((size_t)n_vals * sizeof(double) + (size_t)n * sizeof(int) + 4096));
-  BK_TRY(up.put(vals, vals_desc.data(), n_vals * sizeof(double)));
-  const int nv = (int)src_cols.size();
-  if (h_n_vecs) *h_n_vecs = nv;
-  if (nv > 0 && n_vecs_max > 0) {
-    void* pidx = nullptr;
-    BK_TRY(ws_get(ctx, SLOT_EIG_INT, (int64_t)10 * n * sizeof(int), &pidx));
-    int* d_src = (int*)pidx;
-    BK_TRY(up.put(d_src, src_cols.data(), nv * sizeof(int)));
-    int blocks = (int)std::min<int64_t>((N * nv + 255) / 256, 8192);
-    hipLaunchKernelGGL(gather_cols, dim3(blocks), dim3(256), 0, st, n, nv, (const int*)d_src,
-                       (const double*)Qfin, N, vecs, ldv);
-    BK_CHECK_LAUNCH();
-    // Multi-GPU: every rank runs the (replicated) reduction and divide & conquer, but
-    // back-transforms only its own slice of the kept eigenvector columns; the other columns are
-    // returned as zeros, so that an all-reduce (sum) over the ranks assembles Q exactly.
-    const int pc0 = (int)((int64_t)nv * part_index / part_count);
-    const int pc1 = (int)((int64_t)nv * (part_index + 1) / part_count);
-    if (pc0 > 0) BK_HIP(hipMemsetAsync(vecs, 0, (size_t)pc0 * ldv * sizeof(double), st));
-    if (pc1 < nv) BK_HIP(hipMemsetAsync(vecs + (int64_t)pc1 * ldv, 0, (size_t)(nv - pc1) * ldv * sizeof(double), st));
-    double* pvecs = vecs + (int64_t)pc0 * ldv;
-    const int pnv = pc1 - pc0;
-    if (pnv > 0 && two_stage) {
-      tick("gather kept columns");
-      if (bt2_T != nullptr) BK_HIP(hipStreamWaitEvent(st, ctx->ev_join2, 0));
-      // (the watchdog word of the bulge chasing, read back as zero above, now serves the persistent back-transform)
-      bt2_err = (bt2_T != nullptr) ? (int*)scratch : nullptr;
-      BK_TRY(back_transform_stage2(ctx, n, d_soff, VV, TT, pvecs, ldv, pnv, bt2_dtoff, bt2_T,
-                                   bt2_toff.empty() ? 0 : bt2_toff.back(), bt2_err));
-      tick("back-transform stage 2");
-      void* pw12 = nullptr;
-      const int64_t bt1_w = (int64_t)bt1_grp_for(n) * S2_B;
-      BK_TRY(ws_get(ctx, SLOT_EIG_Z, 2 * bt1_w * pnv * sizeof(double), &pw12));
-      if (bt1_V != nullptr) {
-        BK_HIP(hipStreamWaitEvent(st, ctx->ev_join, 0));
-        BK_TRY(back_transform_stage1_grouped(ctx, n, bt1, bt1_V, bt1_T, pvecs, ldv, pnv, (double*)pw12,
-                                             (double*)pw12 + bt1_w * pnv));
-      }
-      else
-        BK_TRY(back_transform_stage1(ctx, W, n, taus1, pvecs, ldv, pnv, s1.Vp, s1.Tall, (double*)pw12,
-                                     (double*)pw12 + (int64_t)S2_B * pnv));
-      tick("back-transform stage 1");
-    } else if (pnv > 0) {
-      BK_TRY(back_transform(ctx, W, n, tau, pvecs, ldv, pnv));
-    }
-  }
-  // (also when no column was back-transformed: nothing of this call may still run on the look-ahead stream)
-  if (bt2_T != nullptr) BK_HIP(hipStreamWaitEvent(st, ctx->ev_join2, 0));
-  if (bt1_V != nullptr) BK_HIP(hipStreamWaitEvent(st, ctx->ev_join, 0));
-#ifdef BK_FAULT_INJECT
-  // BIGKRLS_FAULT=eig_garbage (test build): the FIRST decomposition after the variable is set comes back with its
-  // middle kept eigenvector scaled by 1.001 -- a wrong result without any error, the kind the fit's verification
-  // (Fit::verify_decomposition, csrc/fit.hip) exists for; =eig_garbage_always: every decomposition does
-  {
-    static int garbage_calls = 0;
-    const char* fault = getenv("BIGKRLS_FAULT");
-    const bool once = fault && std::string(fault) == "eig_garbage", always = fault && std::string(fault) == "eig_garbage_always";
-    if (!once && !always) garbage_calls = 0;
-    // (a column the fit's check samples: the middle kept one; in a multi-GPU fit the last one, owned by the last rank)
-    const int gc = part_count == 1 ? nv / 2 : nv - 1;
-    if ((always || (once && garbage_calls++ == 0)) && nv > 0 && n_vecs_max > 0 && part_index == part_count - 1)
-      BK_TRY(scale(ctx, N, 1.001, vecs + (int64_t)gc * ldv));
-    // BIGKRLS_FAULT=eig_swap / eig_swap_always: two kept eigenvectors exchanged -- every column still has norm 1, the
-    // combinations Q r keep |Q r|^2 = k: only the comparison with K Q r (on one GPU deferred to the fit's pass over K
-    // for the marginal effects, Fit::verify_deferred in csrc/fit.hip) can see it
-    {
-      static int swap_calls = 0;
-      const bool sonce = fault && std::string(fault) == "eig_swap", salways = fault && std::string(fault) == "eig_swap_always";
-      if (!sonce && !salways) swap_calls = 0;
-      if ((salways || (sonce && swap_calls++ == 0)) && nv > 3 && n_vecs_max > 0 && part_count == 1 && keep_thresh >= 0.0) {
-        fault_swap_cols<<<(N + 255) / 256, 256, 0, st>>>(vecs + (int64_t)(nv / 2) * ldv, vecs + (int64_t)(nv / 2 + 1) * ldv, (int)N);
-        BK_HIP(hipGetLastError());
-      }
-    }
-    // BIGKRLS_FAULT=vals_ulp (set in ONE rank's process): this rank's copy of the replicated eigenvalues differs from its
-    // peers' in the last bit of one kept value -- a valid decomposition the fit's check against K lets through; the
-    // multi-GPU fit must still run its lambda search on identical values everywhere (Fit::fetch_and_agree_eigenvalues: rank 0's)
-    if (fault && std::string(fault) == "vals_ulp" && nv > 1 && keep_thresh >= 0.0) {   // (not the inner solves of the Lanczos)
-      fault_nudge_ulp<<<1, 1, 0, st>>>(vals + nv / 2);
-      BK_HIP(hipGetLastError());
-    }
-  }
-#endif
-  if (trace_on() && nv > 0 && n_vecs_max > 0) {
-    const int tc0 = (int)((int64_t)nv * part_index / part_count), tc1 = (int)((int64_t)nv * (part_index + 1) / part_count);
-    if (tc1 > tc0 && ldv == N) BK_TRY(trace_point(ctx, st, "L:eig_Qpart", vecs + (int64_t)tc0 * ldv, (int64_t)(tc1 - tc0) * ldv, tc0));
-  }
-  if (bt2_err != nullptr) {
-    // watchdog word of the persistent stage-2 back-transform: Z is garbage if it fired -> the decomposition is redone
-    // with per-wavefront launches (by the caller's replay in the distributed fit)
-    int h_err3 = 0;
-    PinnedFetch pf3(ctx, 1);
-    BK_TRY(pf3.add(&h_err3, bt2_err, sizeof(int)));
-    BK_TRY(pf3.finish());
-#ifdef BK_FAULT_INJECT
-    const char* fault = getenv("BIGKRLS_FAULT");
-    if (fault && std::string(fault) == "watchdog_bt2" && !ctx->no_resident) h_err3 = 1;
-#endif
-    if (h_err3 != 0 && mode == EIG_RESUME) {
-      set_error("eigen: watchdog of the persistent stage-2 back-transform fired after the distributed stage 1");
-      return BK_EWATCHDOG;
-    }
-    if (h_err3 != 0)
-      return eigen_retry_without_resident(ctx, A, n64, lda, n_vals, vals, n_vecs_max, keep_thresh, vecs, ldv,
-                                          h_n_vecs, part_index, part_count);
-    return BIGKRLS_OK;
-  }
-  BK_HIP(hipStreamSynchronize(st));
-  return BIGKRLS_OK;
+  return dense.run();
 }
 
 // ---------------------------------------------------------------------------

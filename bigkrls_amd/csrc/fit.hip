@@ -114,7 +114,7 @@ bool verify_on() {
   return on;
 }
 
-bool report_redo() { return getenv("BIGKRLS_VERBOSE") || getenv("BIGKRLS_REPORT_REDO"); }
+bool report_redo() { return verbose() || getenv("BIGKRLS_REPORT_REDO"); }
 
 // One fit: what its phases share, and the phases, in the reference's order. Each returns a status; fit_impl runs them.
 // comm == nullptr is the single-GPU fit; with a communicator every N x N object is this rank's column block, and
@@ -397,7 +397,8 @@ struct Fit {
     // A fired watchdog of a persistent kernel (panel factorisation / bulge chasing: their workgroups must be
     // co-resident, and here they share the GPU with the collectives' kernels) is agreed on by all ranks inside
     // eigen_dense_dist and the decomposition is redone ONCE, on every rank, with the launch-per-step kernels --
-    // K[:, r0:r1) is untouched, so the replay starts from a fresh copy (the single-GPU eigen() does the same). The same
+    // K[:, r0:r1) is untouched, so the replay starts from a fresh copy (the single-GPU eigen() does the same inside its
+    // call, DenseEig::replay in csrc/eigen.hip: both drain the context's streams first, drain_streams). The same
     // replay answers ranks whose replicated decompositions did not come out identical (eigen_dense_dist).
     int rc_e = BIGKRLS_OK;
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -412,12 +413,10 @@ struct Fit {
       if (rc_e != BIGKRLS_OK) break;
       rc_e = eigen_dense_dist(comm, (double*)pa, n, nb, neig, eigtrunc, dvals, dQ, &lastkeeper);
       if (rc_e != BK_EWATCHDOG || attempt == 1 || ctx->no_resident) break;
-      if (getenv("BIGKRLS_VERBOSE"))
+      if (verbose())
         fprintf(stderr, "[bigkrls] rank %d: %s; replaying the distributed decomposition with per-step launches\n",
                 comm->rank, bigkrls_last_error());
-      if (ctx->side_stream) (void)hipStreamSynchronize(ctx->side_stream);
-      if (ctx->bg_stream) (void)hipStreamSynchronize(ctx->bg_stream);
-      (void)hipStreamSynchronize(st);
+      (void)drain_streams(ctx);
       ctx->n_replayed++;
       ctx->no_resident = true;
     }
@@ -685,7 +684,7 @@ struct Fit {
       BK_TRY(trace_host("R:fit_vals", vals.data(), neig, k));
       BK_TRY(trace_point(ctx, st, "R:fit_Q", dQ, n * k, dist_mode));
     }
-    if (getenv("BIGKRLS_VERBOSE")) {
+    if (verbose()) {
       // (equal lines on all ranks -- and Q'Q of the first and last kept columns; a column with a non-finite entry
       //  shows as nan)
       long double sv = 0.0L;
