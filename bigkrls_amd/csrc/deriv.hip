@@ -129,6 +129,10 @@ int deriv_rows(bigkrls_ctx* ctx, const double* Krows, int64_t n, int64_t n_rows,
   BK_REQUIRE((Krows || kernel) && X && h_is_binary && c && D && S, "deriv_rows: null pointer");
   BK_REQUIRE(!kernel || (kernel->n == n && n_rows == n && row0 == 0), "deriv_rows: the kernel operator covers all rows");
   BK_REQUIRE(n_extra >= 0 && (n_extra == 0 || (extra && extra_out)), "deriv_rows: bad extra operand");
+  // (a too-small leading dimension would read or write outside the caller's matrices without any error)
+  BK_REQUIRE(!Krows || kernel || ldk >= n, "deriv_rows: ldk < n");
+  BK_REQUIRE(ldx >= n, "deriv_rows: ldx < n");
+  BK_REQUIRE(ldd >= n_rows && lds >= n_rows, "deriv_rows: ldd or lds < n_rows");
   const int64_t nb0 = 2 + 2 * p, nb = nb0 + n_extra;
   void *pb = nullptr, *pkb = nullptr, *pt = nullptr;
   BK_TRY(ws_get(ctx, SLOT_DERIV_B, n * nb * sizeof(double), &pb));
@@ -203,6 +207,7 @@ int deriv_var(bigkrls_ctx* ctx, const double* Q, int64_t n, int64_t k, int64_t l
               double* h_var) {
   BK_REQUIRE(n > 0 && k > 0 && p > 0, "deriv_var: bad dimensions");
   BK_REQUIRE(Q && wv && S && h_scale && h_var, "deriv_var: null pointer");
+  BK_REQUIRE(ldq >= n && lds >= n, "deriv_var: ldq or lds < n");
   void* pt = nullptr;
   BK_TRY(ws_get(ctx, SLOT_DERIV_KB, (k * p + p) * sizeof(double), &pt));
   double* T = (double*)pt;
