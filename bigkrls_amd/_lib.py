@@ -103,6 +103,7 @@ SIGNATURES = {
     "bigkrls_dev_eigen": [vp, vp, i64, i64, i64, vp, i64, f64, vp, i64, pi64],
     "bigkrls_dev_eigen_part": [vp, vp, i64, i64, i64, vp, i64, f64, vp, i64, pi64, i32, i32],
     "bigkrls_dev_eigen_implicit": [vp, vp, i64, i64, i64, f64, i64, vp, i64, f64, vp, i64, pi64],
+    "bigkrls_dev_eigen_auto": [vp, vp, i64, i64, vp, i64, i64, f64, f64, i64, vp, vp, i64, pi64, pi64],
     "bigkrls_dev_fill_random": [vp, vp, i64, C.c_uint32],
     "bigkrls_dev_cholqr2": [vp, vp, vp, i64, i64, vp, pi32, vp],
     "bigkrls_dev_lanczos_projected": [vp, vp, vp, i64, i64, vp],
@@ -122,6 +123,7 @@ SIGNATURES = {
     "bigkrls_dev_neffective": [vp, vp, i64, i64, i64, vp],
     # level 2, whole path
     "bigkrls_fit": [vp, vp, vp, i64, i64, C.POINTER(FitOptions), C.POINTER(FitOutputs)],
+    "bigkrls_fit_auto": [vp, vp, vp, i64, i64, C.POINTER(FitOptions), i64, C.POINTER(FitOutputs)],
     "bigkrls_predict": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, f64, vp, vp, vp, vp],
     "bigkrls_predict_pointwise": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, f64, vp, vp],
     "bigkrls_predict_factored": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, i64, vp, f64, vp, vp, vp, vp],

@@ -130,6 +130,12 @@ def bigKRLS(y=None, X=None, sigma=None, derivative=True, which_derivatives=None,
     maxdim = min(N/2, max(16 Neig, 4096)). It needs `Neig` with N >= 1024 and 4 Neig <= N (block Lanczos only: there is
     no dense fallback), one GPU, and vcov_form="factors" whenever vcov_est is true. The object then has K = None and
     w["kernel"] = "implicit"; predict(), marginal_effects(), summary() and save / load work on it unchanged.
+    `Neig="auto"` (one GPU, N >= 1024, either kernel form): the block Lanczos finds the rank itself -- it grows its
+    subspace until the spectrum is resolved down to eigtrunc * lambda_1 and returns what a fit with
+    Neig = lastkeeper + 1 returns, so `K.eigenvalues` has lastkeeper + 1 entries. eigtrunc must be > 0 (the default is
+    0 for N <= 3000: pass one). The search is capped at min(N // 4, max_factors if given else 2048) pairs; a spectrum
+    with more eigenvalues above the threshold raises a ValueError. An eigenvalue of multiplicity above the block size
+    128 can be missed, as with a given Neig.
     """
     ctx = (comm.ctx if comm is not None else ctx) or default_context()
     if X is None or y is None:
@@ -167,9 +173,20 @@ def bigKRLS(y=None, X=None, sigma=None, derivative=True, which_derivatives=None,
         raise ValueError("U must be a positive scalar")
     if L is not None and not (np.isscalar(L) and L >= 0):
         raise ValueError("L must be a non-negative scalar")
-    if Neig is not None and int(Neig) < 1:
+    neig_auto = isinstance(Neig, str)
+    if neig_auto:
+        if Neig != "auto":
+            raise ValueError('Neig must be a positive integer or "auto"')
+        if comm is not None:
+            raise ValueError('Neig="auto" runs on one GPU: drop comm, or pass Neig')
+        if n < 1024:
+            raise ValueError(f'Neig="auto" needs N >= 1024 (N = {n}): pass Neig, or leave it out')
+        if ((0.001 if n > 3000 else 0.0) if eigtrunc is None else float(eigtrunc)) == 0.0:
+            raise ValueError('Neig="auto" finds the rank from eigtrunc, which is 0 here (the default for N <= 3000): '
+                             'pass eigtrunc > 0')
+    elif Neig is not None and int(Neig) < 1:
         raise ValueError("Neig must be a positive integer")
-    neig = min(n, int(Neig)) if Neig is not None else n                           # :194
+    neig = n if Neig is None else (n // 4 if neig_auto else min(n, int(Neig)))    # :194 (auto: the cap, see below)
     if vcov_form not in ("dense", "factors", "both"):
         raise ValueError('vcov_form must be "dense", "factors" or "both"')
     if max_factors is not None and not (isinstance(max_factors, (int, np.integer)) and not isinstance(max_factors, bool)
@@ -195,10 +212,12 @@ def bigKRLS(y=None, X=None, sigma=None, derivative=True, which_derivatives=None,
     want_dense, want_factors = vcov_form != "factors", vcov_form != "dense"
     if want_factors and not vcov_est:
         raise ValueError('vcov_form = "factors" / "both" requires vcov_est = True')
+    if neig_auto:                     # the cap of the rank search: the eigenvalue buffer and the factor buffer hold it
+        neig = min(n // 4, int(max_factors) if max_factors is not None else 2048)
     qcap = 0
     if want_factors:
         eigtrunc_eff = (0.001 if n > 3000 else 0.0) if eigtrunc is None else float(eigtrunc)      # :195-201
-        if Neig is not None or eigtrunc_eff == 0.0:
+        if Neig is not None or eigtrunc_eff == 0.0:       # (Neig="auto": neig is the cap)
             qcap = neig
         else:
             qcap = min(neig, int(max_factors) if max_factors is not None else min(n, 2048))
@@ -211,7 +230,7 @@ def bigKRLS(y=None, X=None, sigma=None, derivative=True, which_derivatives=None,
     opt.L = -1.0 if L is None else float(L)
     opt.U = -1.0 if U is None else float(U)
     opt.eigtrunc = -1.0 if eigtrunc is None else float(eigtrunc)
-    opt.neig = neig
+    opt.neig = 0 if neig_auto else neig             # (auto: ignored, the cap is bigkrls_fit_auto's own argument)
     opt.derivative = int(bool(derivative))
     opt.vcov_est = int(bool(vcov_est))
     opt.acf = int(bool(acf))
@@ -260,12 +279,18 @@ def bigKRLS(y=None, X=None, sigma=None, derivative=True, which_derivatives=None,
 
     t_wall0 = time.perf_counter()
     try:
-        if comm is None:
+        if neig_auto:
+            _call_native("bigkrls_fit_auto", ctx.handle, Xh.ctypes.data, yh.ctypes.data, n, p, C.byref(opt), neig,
+                         C.byref(out))
+        elif comm is None:
             _call_native("bigkrls_fit", ctx.handle, Xh.ctypes.data, yh.ctypes.data, n, p, C.byref(opt), C.byref(out))
         else:
             _call_native("bigkrls_fit_dist", comm.handle, Xh.ctypes.data, yh.ctypes.data, n, p, C.byref(opt),
                          C.byref(out))
     except ValueError as e:
+        if neig_auto and "kcap" in str(e):                   # the cap of the rank search (bigkrls_dev_eigen_auto)
+            raise ValueError(f'{e}: Neig="auto" searched up to {neig} pairs -- raise max_factors (at most N // 4 = '
+                             f'{n // 4}), or pass Neig') from None
         if want_factors and int(out.lastkeeper) > qcap:      # the library's capacity error (include/bigkrls.h)
             raise ValueError(f"{e}: pass max_factors >= {int(out.lastkeeper)} (or vcov_form='dense')") from None
         raise
@@ -280,7 +305,7 @@ def bigKRLS(y=None, X=None, sigma=None, derivative=True, which_derivatives=None,
         for i in range(min(int(out.n_probes), max_trace)):
             trace.append((float(tracebuf[2 * i]), float(tracebuf[2 * i + 1])))
     w["X"] = Xh
-    w["K.eigenvalues"] = vals                                                     # :268
+    w["K.eigenvalues"] = vals[:int(out.neig)].copy() if neig_auto else vals       # :268 (auto: lastkeeper + 1 values)
     w["lastkeeper"] = int(out.lastkeeper)                                         # :269
     w["Neffective"] = float(out.Neffective)                                       # :280
     if derivative:

@@ -580,6 +580,17 @@ int bigkrls_dev_eigen_implicit(bigkrls_ctx* ctx, const double* X, int64_t n, int
   return eigen_implicit(ctx, kernel, n_vals, vals, n_vecs_max, h_keep_thresh, vecs, ldv, h_n_vecs);
 }
 
+int bigkrls_dev_eigen_auto(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t lda, const double* X, int64_t ldx,
+                           int64_t p, double sigma, double h_keep_thresh, int64_t n_vals_max, double* vals, double* vecs,
+                           int64_t ldv, int64_t* h_n_vals, int64_t* h_n_vecs) {
+  BK_TRY(check_ctx(ctx));
+  BK_REQUIRE(h_n_vals && h_n_vecs, "eigen_auto: the counts are required");
+  if (A) return eigen_auto(ctx, A, n, lda, n_vals_max, vals, h_keep_thresh, vecs, ldv, h_n_vals, h_n_vecs);
+  KernelOp kernel;
+  BK_TRY(kernel_op_prepare(ctx, X, n, ldx, p, sigma, &kernel));
+  return eigen_implicit(ctx, kernel, n_vals_max, vals, n_vals_max, h_keep_thresh, vecs, ldv, h_n_vecs, true, h_n_vals);
+}
+
 int bigkrls_dev_fill_random(bigkrls_ctx* ctx, double* p, int64_t count, uint32_t seed) {
   BK_TRY(check_ctx(ctx));
   return fill_random(ctx, p, count, seed);

@@ -432,8 +432,15 @@ int eigen_krylov_dist(bigkrls_comm* comm, const double* Kcols, int64_t n, int64_
                       int64_t* h_n_vecs);
 // the n_vals largest pairs of K(X, X) by the block Lanczos on the operator (never a matrix): n >= 1024 and
 // 4 n_vals <= n, else BIGKRLS_EINVAL; no dense fall-through -- BIGKRLS_ENOCONV is returned
+// auto_rank: n_vals is the cap; the pairs down to keep_thresh lambda_1 (> 0) and one sentinel value below it are
+// returned, *h_n_vals values (BIGKRLS_EINVAL when the cap does not hold them)
 int eigen_implicit(bigkrls_ctx* ctx, const KernelOp& kernel, int64_t n_vals, double* vals, int64_t n_vecs_max,
-                   double keep_thresh, double* vecs, int64_t ldv, int64_t* h_n_vecs);
+                   double keep_thresh, double* vecs, int64_t ldv, int64_t* h_n_vecs, bool auto_rank = false,
+                   int64_t* h_n_vals = nullptr);
+// the same on a stored matrix: block Lanczos where it can run (n >= 1024, 4 kcap <= n), else -- or when it does not
+// converge -- the dense path with all values, of which the first lastkeeper + 1 are returned
+int eigen_auto(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t lda, int64_t kcap, double* vals, double keep_thresh,
+               double* vecs, int64_t ldv, int64_t* h_n_vals, int64_t* h_n_vecs);
 // Row-block distributed stage 1 (dense -> band), one call per panel step between the caller's
 // collectives; see include/bigkrls.h (bigkrls_dev_s1_*).
 int dist_s1_open(bigkrls_ctx* ctx, int64_t n);

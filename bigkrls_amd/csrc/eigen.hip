@@ -2235,13 +2235,27 @@ static int kry_agree_min(const KTimes& op, double* vals, int count) {
 // realistically differ between ranks); single GPU: the status itself
 static int kry_agree_status(const KTimes& op, int rc) { return op.comm ? comm_agree(op.comm, rc) : rc; }
 
+// Auto rank (auto_rank, keep_thresh = tau > 0 required): k is the CAP kcap, not the rank. The workspace is laid out as
+// a fixed run with k = kcap lays it out; the rank is found inside the one run, because the Krylov basis B_0, B_1, ...
+// does not depend on k. At every (full) check, with theta the descending Ritz values of T:
+//   c = #{theta_i >= tau theta_1},  k_eff = c + 1   (the kept pairs and one sentinel below the threshold)
+// and the run has converged when the residual estimates of the first k_eff pairs (and `dropped`) are <= tol theta_1
+// and the subspace has at least k_eff columns. Ritz values only grow with the subspace, so c only grows: c + 1 > kcap
+// with theta_1 converged is final (BIGKRLS_EINVAL). After convergence everything runs with k = k_eff: *h_n_vals =
+// k_eff values, *h_n_vecs = c vectors. The schedule of the checks depends on sizes and Ritz data only: the first
+// check where a fixed k = 128 has it, the later ones by steps_to_go with the current k_eff; no estimate checks.
+// `ke` below is that effective rank; in a fixed run ke == k throughout.
 static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t k, double* vals,
                         int64_t n_vecs_max, double keep_thresh, double* vecs, int64_t ldv,
-                        int64_t* h_n_vecs, int part_index, int part_count) {
+                        int64_t* h_n_vecs, int part_index, int part_count, bool auto_rank = false,
+                        int64_t* h_n_vals = nullptr) {
   hipStream_t st = ctx->stream;
   constexpr int b = 128;
   const double tol = 1e-10;
   kry_diag.clear();
+  if (auto_rank) BK_REQUIRE(keep_thresh > 0.0 && h_n_vals && !kop.comm, "eigen (Krylov, auto rank): needs keep_thresh > 0 and one GPU");
+  int64_t ke = auto_rank ? std::min<int64_t>(k, b) : k;
+  int n_checks = 0;
   const int64_t maxdim = std::min<int64_t>(n / 2 / b * b, std::max<int64_t>(16 * k, 4096) / b * b);
   const int maxsteps = (int)(maxdim / b);
   void *pB = nullptr, *pW = nullptr, *pC = nullptr, *pC2 = nullptr;
@@ -2302,11 +2316,11 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
   // subspace of 5k columns, or of 2.5k where a step costs more than such a check (sizes only: the schedule, and
   // with it the result, must not depend on timing)
   const double step_s_est = 2.0 * (double)n * (double)n * b / 50e12;
-  const bool check_is_cheap = 12e-6 * 4.0 * (double)k < step_s_est;
+  bool check_is_cheap = 12e-6 * 4.0 * (double)(auto_rank ? (int64_t)b : k) < step_s_est;   // (auto rank: follows k_eff)
   // (C4: the pairs converge at step 27, C5 at step 23; a first check at 4k / 2k columns -- step 16 in both -- sits on the
   //  plateau of the worst residual and only costs a dense eigensolve of T: 5k / 2.5k columns, step 20, leaves three
   //  checks at C4 (20, 25, 27) and two at C5 (20, 23) instead of four and three)
-  int next_check = (int)std::max<int64_t>(2, ((check_is_cheap ? 5 : 10) * k / 2 + b - 1) / b);
+  int next_check = (int)std::max<int64_t>(2, ((check_is_cheap ? 5 : 10) * (auto_rank ? (int64_t)b : k) / 2 + b - 1) / b);
   if (const char* fc = getenv("BIGKRLS_KRY_FIRST_CHECK")) next_check = std::max(2, atoi(fc));   // (development)
   while (true) {
     // ---- one block Lanczos step: W = K B_j, orthogonalised against every block so far (CGS2) ---
@@ -2381,7 +2395,7 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
     // beta of this step is zero (the new block is not coupled to the old ones).
     {
       const double wfro = std::sqrt(std::max(wnorm_sq, 0.0));
-      if (wmax_seen > 0.0 && wfro <= 1e-10 * wmax_seen && (int64_t)(steps + 1) * b < k && steps + 1 < maxsteps) {
+      if (wmax_seen > 0.0 && wfro <= 1e-10 * wmax_seen && (int64_t)(steps + 1) * b < ke && steps + 1 < maxsteps) {
         BK_TRY(fill_random(ctx, W, n * b, 20240229u + 7919u * (uint32_t)(steps + 1)));
         for (int pass = 0; pass < 2; ++pass) {
           BK_TRY(gram(B, dim, W, b, C));
@@ -2409,7 +2423,7 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
     }
     {
       const double wmax = std::sqrt(std::max(piv[1], 0.0));
-      if (!breakdown && !early_check_done && wmax <= 1e-6 * wmax_seen && (int64_t)(steps + 1) * b >= k) {
+      if (!breakdown && !early_check_done && wmax <= 1e-6 * wmax_seen && (int64_t)(steps + 1) * b >= ke) {
         next_check = std::min(next_check, steps + 1);      // (once: the checks after it follow their own forecasts)
         early_check_done = true;
       }
@@ -2428,7 +2442,7 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
       const std::vector<double>& beta = Rtmp;       // T[steps, steps - 1]: couples the last block to the next one
       // residuals |beta y_i[last block]| of the first k Ritz pairs of a projected problem whose eigenvectors end in the
       // b rows ylast (b x k, host)
-      struct Resid { double worst = 0.0, worst_kept = 0.0; int64_t n_conv = 0; };
+      struct Resid { double worst = 0.0, worst_kept = 0.0, first = 0.0; int64_t n_conv = 0; };
       auto residuals = [&](const double* th, const double* ylast) {
         Resid r;
         if (breakdown) {
@@ -2438,13 +2452,14 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
           r.worst = r.worst_kept = std::sqrt(std::max(wnorm_sq, 0.0));
           return r;
         }
-        for (int64_t i = 0; i < k; ++i) {
+        for (int64_t i = 0; i < ke; ++i) {
           double r2 = 0.0;
           for (int rr = 0; rr < b; ++rr) {
             double sacc = 0.0;
             for (int c = rr; c < b; ++c) sacc += beta[rr + (size_t)c * b] * ylast[c + (size_t)i * b];
             r2 += sacc * sacc;
           }
+          if (i == 0) r.first = std::sqrt(r2);
           r.worst = std::max(r.worst, std::sqrt(r2));
           if (std::sqrt(r2) <= tol * std::fabs(th[0])) ++r.n_conv;
           if (keep_thresh >= 0.0 && th[i] >= keep_thresh * th[0]) r.worst_kept = std::max(r.worst_kept, std::sqrt(r2));
@@ -2457,16 +2472,18 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
       std::vector<double> Ylast((size_t)b * k), th;
       auto solve_projected = [&](double* dT, int64_t mm, double* dvalsT) -> int {
         int64_t nvY = 0;
+        // (auto rank: the subspace of an early check can be narrower than the cap -- as many vectors as there are)
+        const int64_t kv = auto_rank ? std::min<int64_t>(k, mm) : k;
         // (replicated, but after a fault one rank's copy may fail where its peers' do not: agreed, so nobody leaves alone)
-        BK_TRY(kry_agree_status(kop, eigen(ctx, dT, mm, mm, mm, dvalsT, k, -1.0, (double*)pY, mm, &nvY, 0, 1, EIG_FULL)));
+        BK_TRY(kry_agree_status(kop, eigen(ctx, dT, mm, mm, mm, dvalsT, kv, -1.0, (double*)pY, mm, &nvY, 0, 1, EIG_FULL)));
         double* hp = nullptr;
         BK_TRY(pinned_get(ctx, mm + (int64_t)b * k, &hp));
         BK_HIP(hipMemcpyAsync(hp, dvalsT, mm * sizeof(double), hipMemcpyDeviceToHost, st));
         BK_HIP(hipMemcpy2DAsync(hp + mm, b * sizeof(double), (double*)pY + (mm - b), mm * sizeof(double),
-                                b * sizeof(double), k, hipMemcpyDeviceToHost, st));
+                                b * sizeof(double), kv, hipMemcpyDeviceToHost, st));
         BK_HIP(hipStreamSynchronize(st));
         th.assign(hp, hp + mm);
-        std::memcpy(Ylast.data(), hp + mm, (size_t)b * k * sizeof(double));
+        std::memcpy(Ylast.data(), hp + mm, (size_t)b * kv * sizeof(double));
         return BIGKRLS_OK;
       };
       auto agree_worst = [&](double& worst, double& theta1) -> int {
@@ -2496,13 +2513,13 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
       // never come back, so it cannot replace the full check (its converged set can miss wanted eigenvalues,
       // tools/experiments/DEAD_ENDS.md): it only says where the next FULL check goes, and a full check follows at
       // once should it report convergence.
-      if (m < k) {      // (a breakdown before the subspace had k columns: nothing to decompose -- the dense path)
+      if (m < ke) {     // (a breakdown before the subspace had k columns: nothing to decompose -- the dense path)
         dim = m;
         break;
       }
       bool full = true;
       const int64_t mc = k + (int64_t)(steps - full_steps) * b;
-      if (next_is_estimate && !last && full_steps > 0 && 2 * mc <= m && !getenv("BIGKRLS_KRY_NOEST")) {
+      if (!auto_rank && next_is_estimate && !last && full_steps > 0 && 2 * mc <= m && !getenv("BIGKRLS_KRY_NOEST")) {
         void* pT = nullptr;
         {
           int rc = ws_get(ctx, SLOT_KRY_T, (mc * mc + mc) * sizeof(double), &pT);
@@ -2546,9 +2563,29 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
         BK_CHECK_LAUNCH();
         BK_TRY(solve_projected(dT, m, dvalsT));
         theta = th;
+        ++n_checks;
+        // auto rank: the rank this check asks for. need > cap: the residuals below are those of the first `cap` pairs
+        // (theta_1's among them: the cap error waits for it); need > m: the subspace is still too narrow.
+        int64_t need = 0;
+        if (auto_rank) {
+          int64_t c = 0;
+          while (c < m && theta[c] >= keep_thresh * theta[0]) ++c;
+          need = c + 1;
+          ke = std::min<int64_t>(std::min<int64_t>(need, k), m);
+          check_is_cheap = 12e-6 * 4.0 * (double)ke < step_s_est;
+        }
         Resid r = residuals(theta.data(), Ylast.data());
         double worst = r.worst, theta1 = std::fabs(theta[0]);
         BK_TRY(agree_worst(worst, theta1));
+        if (auto_rank && need > k && !breakdown && std::max(r.first, dropped) <= tol * theta1) {
+          char buf[320];
+          snprintf(buf, sizeof buf, "eigen (Krylov, auto rank): more than kcap = %lld eigenvalues reach the threshold: theta_kcap / theta_1 = %.3e "
+                                    "is still above keep_thresh = %.3e (raise the cap, or give the rank)", (long long)k,
+                   theta[k - 1] / theta[0], keep_thresh);
+          set_error(buf);
+          return BIGKRLS_EINVAL;
+        }
+        if (auto_rank && need > ke) worst = std::max(worst, 2.0 * tol * theta1);   // (not converged whatever the first ke pairs say)
         if (verbose())
           fprintf(stderr, "[bigkrls] block Lanczos check: steps=%d worst=%.3e worst(kept)=%.3e converged=%lld of %lld theta0=%.4e\n",
                   steps, worst, r.worst_kept, (long long)r.n_conv, (long long)k, theta[0]);
@@ -2562,11 +2599,12 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
           dim = m;
           break;
         }
-        const int inc = steps_to_go(worst, theta1);
+        int inc = steps_to_go(worst, theta1);
+        if (auto_rank && need > m) inc = std::max<int>(inc, (int)((std::min<int64_t>(need, k) - m + b - 1) / b));   // (columns first)
         next_check = steps + inc;
         // what the estimate at next_check needs of this check: the k Ritz values and C = beta Y[last block rows, :]
         // (b x k), the coupling of the Ritz vectors to the next block -- kept on the device behind the blocks of T
-        next_is_estimate = inc >= 4;
+        next_is_estimate = inc >= 4 && !auto_rank;
         full_steps = steps;
         if (next_is_estimate) {
           double* hp = nullptr;
@@ -2588,13 +2626,14 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
     dim = (int64_t)(steps + 1) * b;
   }
   if (verbose()) fprintf(stderr, "[bigkrls] block Lanczos: n=%lld k=%lld steps=%d dim=%lld converged=%d\n", (long long)n, (long long)k, steps, (long long)dim, (int)converged);
+  if (verbose() && auto_rank) fprintf(stderr, "[bigkrls] block Lanczos (auto rank): cap=%lld rank=%lld checks=%d\n", (long long)k, (long long)ke, n_checks);
 #ifdef BK_FAULT_INJECT
   {
     const char* fault = getenv("BIGKRLS_FAULT");   // BIGKRLS_FAULT=noconv (test build): pretend the iteration stalled
     if (fault && std::string(fault) == "noconv") converged = false;
   }
 #endif
-  if (!converged && dim < k) {
+  if (!converged && dim < ke) {
     set_error("eigen (Krylov): breakdown with a subspace smaller than the number of requested pairs (a kernel of lower "
               "numerical rank than Neig: the dense path decomposes it -- taken automatically on one GPU; "
               "bigkrls_fit_dist: eigen_mode \"dense\")");
@@ -2612,10 +2651,10 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
   // which is what every call did before (BIGKRLS_KRY_REFINE=1 still forces it).
   double* Q = W;                        // n x k (W, W2 are n x max(b,k))
   double* KQ = W2;
-  if (nr > 0) BK_TRY(gemm(ctx, 0, 0, nr, k, dim, 1.0, B + ro, n, (double*)pY, dim, 0.0, Q + ro, n));
+  if (nr > 0) BK_TRY(gemm(ctx, 0, 0, nr, ke, dim, 1.0, B + ro, n, (double*)pY, dim, 0.0, Q + ro, n));
   double* dH = dA + b * b;              // k x k + 2k
   double* dvalsH = dH + k * k;
-  std::vector<double> hv(theta.begin(), theta.begin() + k);     // Ritz values of T, descending
+  std::vector<double> hv(theta.begin(), theta.begin() + ke);     // Ritz values of T, descending
   bool refine = false;
   {
     const char* rf = getenv("BIGKRLS_KRY_REFINE");
@@ -2630,7 +2669,7 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
     BK_TRY(ws_get(ctx, SLOT_KRY_T, (dim * dim + dim) * sizeof(double), &pT));
     dvals_final = (const double*)pT + dim * dim;
   } else if (!refine) {
-    const int64_t bs = std::min<int64_t>(k, b), c0 = k - bs;
+    const int64_t bs = std::min<int64_t>(ke, b), c0 = ke - bs;
     // theta of T sits at the head of SLOT_KRY_T's value vector (device): dvalsT of the last check
     void* pT = nullptr;
     BK_TRY(ws_get(ctx, SLOT_KRY_T, (dim * dim + dim) * sizeof(double), &pT));
@@ -2669,31 +2708,32 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
   }
   void* pZ = nullptr;
   if (refine) {
-    BK_TRY(k_times(ctx, kop, n, Q, k, KQ));
-    BK_TRY(gram(Q, k, KQ, k, dH));
+    BK_TRY(k_times(ctx, kop, n, Q, ke, KQ));
+    BK_TRY(gram(Q, ke, KQ, ke, dH));
     BK_TRY(ws_get(ctx, SLOT_KRY_Y, std::max<int64_t>(dim * k, k * k) * sizeof(double), &pZ));
     int64_t nvZ = 0;
-    BK_TRY(eigen(ctx, dH, k, k, k, dvalsH, k, -1.0, (double*)pZ, k, &nvZ, 0, 1, EIG_FULL));
+    BK_TRY(eigen(ctx, dH, ke, ke, ke, dvalsH, ke, -1.0, (double*)pZ, ke, &nvZ, 0, 1, EIG_FULL));
     {
-      PinnedFetch pf(ctx, k);
-      BK_TRY(pf.add(hv.data(), dvalsH, k * sizeof(double)));
+      PinnedFetch pf(ctx, ke);
+      BK_TRY(pf.add(hv.data(), dvalsH, ke * sizeof(double)));
       BK_TRY(pf.finish());
     }
     dvals_final = dvalsH;
   }
-  BK_HIP(hipMemcpyAsync(vals, dvals_final, k * sizeof(double), hipMemcpyDeviceToDevice, st));
+  BK_HIP(hipMemcpyAsync(vals, dvals_final, ke * sizeof(double), hipMemcpyDeviceToDevice, st));
   int64_t nv = 0;
   if (keep_thresh >= 0.0) {
-    for (int64_t i = 0; i < k; ++i)
+    for (int64_t i = 0; i < ke; ++i)
       if (hv[i] >= keep_thresh * hv[0]) nv = i + 1;     // max(which(values >= eigtrunc * values[1]))
   } else {
-    nv = k;
+    nv = ke;
   }
   nv = std::min<int64_t>(nv, n_vecs_max);
   if (h_n_vecs) *h_n_vecs = nv;
+  if (auto_rank) *h_n_vals = ke;
   if (nv > 0) {
     if (nr > 0) {
-      if (refine) BK_TRY(gemm(ctx, 0, 0, nr, nv, k, 1.0, Q + ro, n, (double*)pZ, k, 0.0, vecs + ro, ldv));
+      if (refine) BK_TRY(gemm(ctx, 0, 0, nr, nv, ke, 1.0, Q + ro, n, (double*)pZ, ke, 0.0, vecs + ro, ldv));
       else BK_TRY(copy_matrix(ctx, Q + ro, nr, nv, n, vecs + ro, ldv));
     }
     // every rank returns all rows of the kept eigenvectors (the later passes of the fit read row blocks of Q but
@@ -2742,7 +2782,7 @@ int eigen_krylov_dist(bigkrls_comm* comm, const double* Kcols, int64_t n, int64_
 // The block Lanczos on a kernel matrix that is never stored. There is no matrix to hand to the dense path: what the
 // iteration cannot deliver is the caller's answer.
 int eigen_implicit(bigkrls_ctx* ctx, const KernelOp& kernel, int64_t n_vals, double* vals, int64_t n_vecs_max,
-                   double keep_thresh, double* vecs, int64_t ldv, int64_t* h_n_vecs) {
+                   double keep_thresh, double* vecs, int64_t ldv, int64_t* h_n_vecs, bool auto_rank, int64_t* h_n_vals) {
   const int64_t n = kernel.n;
   BK_REQUIRE(kernel.Xc && kernel.nrm && vals && n > 0 && n < (1ll << 30), "eigen (implicit kernel): bad arguments");
   if (!(n >= 1024 && n_vals > 0 && 4 * n_vals <= n)) {
@@ -2752,10 +2792,13 @@ int eigen_implicit(bigkrls_ctx* ctx, const KernelOp& kernel, int64_t n_vals, dou
   }
   BK_REQUIRE(n_vecs_max >= 0 && n_vecs_max <= n, "eigen (implicit kernel): n_vecs_max out of range");
   BK_REQUIRE(n_vecs_max == 0 || (vecs && ldv >= n), "eigen (implicit kernel): bad eigenvector buffer");
+  if (auto_rank)
+    BK_REQUIRE(h_n_vals && keep_thresh > 0.0 && keep_thresh <= 1.0 && n_vecs_max == n_vals,
+               "eigen (implicit kernel, auto rank): needs 0 < keep_thresh <= 1 and room for n_vals eigenvectors");
   ctx->corrupt_run = false;
   KTimes op;
   op.kernel = &kernel;
-  const int rc = eigen_krylov(ctx, op, n, n_vals, vals, n_vecs_max, keep_thresh, vecs, ldv, h_n_vecs, 0, 1);
+  const int rc = eigen_krylov(ctx, op, n, n_vals, vals, n_vecs_max, keep_thresh, vecs, ldv, h_n_vecs, 0, 1, auto_rank, h_n_vals);
   if (rc == BIGKRLS_ENOCONV)
     set_error(std::string(bigkrls_last_error()) + " -- the implicit kernel form has no dense fallback: fit with kernel=\"stored\"");
   return rc;
@@ -2901,6 +2944,9 @@ struct EigArgs {
   int64_t ldv;
   int64_t* h_n_vecs;
   int part_index, part_count, mode;
+  // auto rank (eigen_auto): n_vals is the cap of the block Lanczos and *h_n_vals receives the number of values written
+  bool auto_rank = false;
+  int64_t* h_n_vals = nullptr;
 };
 
 // the persistent kernels with a watchdog word: what EIG_RESUME reports when it fired, and the BIGKRLS_FAULT value
@@ -2966,7 +3012,8 @@ struct DenseEig : EigArgs {
     const char* ek = getenv("BIGKRLS_EIGK");
     const std::string eigk = ek ? ek : "";
     // (measured: N = 12 000, Neig = 512 dense 0.33 s vs 0.47 s; N = 50 000, Neig = 512 dense 6.9 s vs 0.88 s)
-    const bool small_k = n_vals * 8 <= N && N >= 16384;
+    // (auto rank: no rank to compare the costs with -- the iteration is tried wherever it can run)
+    const bool small_k = auto_rank ? (n_vals * 4 <= N && N >= 1024) : (n_vals * 8 <= N && N >= 16384);
     if (eigk == "dense" || n_vals >= N || !(small_k || (eigk == "krylov" && n_vals * 4 <= N && N >= 1024))) {
       *go_dense = true;
       return BIGKRLS_OK;
@@ -2975,7 +3022,7 @@ struct DenseEig : EigArgs {
     whole.A = A;
     whole.lda = lda;
     const int rc = eigen_krylov(ctx, whole, N, n_vals, vals, n_vecs_max, keep_thresh, vecs, ldv, h_n_vecs, part_index,
-                                part_count);
+                                part_count, auto_rank, h_n_vals);
     // A spectrum the iteration does not resolve within its subspace limit (or a breakdown) is
     // handed to the dense path in the same call -- A is untouched. Only an explicit
     // BIGKRLS_EIGK=krylov reports the non-convergence.
@@ -3440,6 +3487,51 @@ int eigen(bigkrls_ctx* ctx, const double* A, int64_t n64, int64_t lda, int64_t n
     if (!go_dense) return rc;
   }
   return dense.run();
+}
+
+// Auto rank on a stored matrix: the pairs down to keep_thresh lambda_1 and one sentinel value below it, at most kcap
+// values (vals holds kcap doubles, vecs kcap columns). The block Lanczos finds the rank inside its one run wherever it
+// can run (n >= 1024, 4 kcap <= n); what it does not resolve (BIGKRLS_ENOCONV), and every other shape, goes to the dense
+// path as a fixed-rank call does: all n values with keep_thresh, of which the first lastkeeper + 1 are returned.
+int eigen_auto(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t lda, int64_t kcap, double* vals, double keep_thresh,
+               double* vecs, int64_t ldv, int64_t* h_n_vals, int64_t* h_n_vecs) {
+  BK_REQUIRE(A && vals && vecs && h_n_vals && h_n_vecs && n > 0 && n < (1ll << 30) && lda >= n && ldv >= n,
+             "eigen (auto rank): bad arguments");
+  BK_REQUIRE(kcap >= 1 && kcap <= n, "eigen (auto rank): the cap must be between 1 and n");
+  BK_REQUIRE(keep_thresh > 0.0 && keep_thresh <= 1.0, "eigen (auto rank): needs 0 < keep_thresh <= 1");
+  ctx->corrupt_run = false;
+  {
+    DenseEig first(EigArgs{ctx, A, n, lda, kcap, vals, kcap, keep_thresh, vecs, ldv, h_n_vecs, 0, 1, EIG_FULL, true, h_n_vals});
+    bool go_dense = false;
+    const int rc = first.route_krylov(&go_dense);
+    if (!go_dense) return rc;
+  }
+  void* pv = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_KRY_C, n * (int64_t)sizeof(double), &pv));     // (the dense path does not touch this slot)
+  int64_t nv = 0;
+  BK_TRY(DenseEig(EigArgs{ctx, A, n, lda, n, (double*)pv, kcap, keep_thresh, vecs, ldv, &nv, 0, 1, EIG_FULL}).run());
+  std::vector<double> hv((size_t)n);
+  {
+    PinnedFetch pf(ctx, n);
+    BK_TRY(pf.add(hv.data(), (const double*)pv, n * sizeof(double)));
+    BK_TRY(pf.finish());
+  }
+  int64_t c = 0;
+  for (int64_t i = 0; i < n; ++i)
+    if (hv[i] >= keep_thresh * hv[0]) c = i + 1;     // max(which(values >= eigtrunc * values[1]))
+  if (c + 1 > kcap) {
+    char buf[320];
+    snprintf(buf, sizeof buf, "eigen (auto rank): more than kcap = %lld eigenvalues reach the threshold: lambda_kcap / lambda_1 = %.3e "
+                              "is still above keep_thresh = %.3e (raise the cap, or give the rank)", (long long)kcap,
+             hv[kcap - 1] / hv[0], keep_thresh);
+    set_error(buf);
+    return BIGKRLS_EINVAL;
+  }
+  BK_HIP(hipMemcpyAsync(vals, pv, (size_t)(c + 1) * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  BK_HIP(hipStreamSynchronize(ctx->stream));
+  *h_n_vals = c + 1;
+  *h_n_vecs = std::min<int64_t>(nv, c);
+  return BIGKRLS_OK;
 }
 
 // ---------------------------------------------------------------------------

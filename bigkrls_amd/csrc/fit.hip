@@ -13,6 +13,7 @@
 #include <limits>
 
 namespace bk {
+
 namespace {
 
 const double kNaN = std::numeric_limits<double>::quiet_NaN();
@@ -135,6 +136,8 @@ struct Fit {
   hipStream_t st = nullptr;
   // ---- validated options and the moments of the raw data
   int64_t neig = 0, pd = 0;
+  bool neig_auto = false;                      // bigkrls_fit_auto: the eigensolver finds the rank, neig is the cap until it has (decompose)
+  int64_t neig_max = 0, neig_cap = 0;
   double eigtrunc = 0.0, sigma = 0.0;
   bool derivative = false, vcov_est = false, acf = false;
   bool implicit = false;                       // kernel_form = 1: K is never stored, `kop` stands in for dK
@@ -212,6 +215,7 @@ struct Fit {
     }
     acf = opt->acf != 0 && p > 2;                                                                        // :192
     neig = (opt->neig > 0) ? std::min<int64_t>(n, opt->neig) : n;                                        // :194
+    if (neig_auto) neig = neig_cap = std::max<int64_t>(neig_max, 1);          // (checked below, with eigtrunc)
     if (opt->kernel_form != 0 && opt->kernel_form != 1) return fail("fit: kernel_form must be 0 (stored) or 1 (implicit)");
     implicit = opt->kernel_form == 1;
     if (implicit) {
@@ -219,7 +223,7 @@ struct Fit {
       if (out->d_K) return fail("fit: the implicit kernel form stores no kernel matrix: d_K must be NULL");
       if (out->d_vcov_c || out->d_vcov_fitted)
         return fail("fit: the implicit kernel form returns the variance as factors (d_vcov_q, vcov_w): d_vcov_c and d_vcov_fitted must be NULL");
-      if (opt->neig <= 0) return fail("fit: the implicit kernel form needs neig (block Lanczos for the neig largest pairs)");
+      if (opt->neig <= 0 && !neig_auto) return fail("fit: the implicit kernel form needs neig (block Lanczos for the neig largest pairs)");
       if (n < 1024 || 4 * neig > n)
         return fail("fit: the implicit kernel form needs n >= 1024 and 4 neig <= n (n = " + std::to_string((long long)n) +
                     ", neig = " + std::to_string((long long)neig) + ")");
@@ -227,6 +231,13 @@ struct Fit {
     eigtrunc = opt->eigtrunc;
     if (eigtrunc < 0.0 || std::isnan(eigtrunc)) eigtrunc = n > 3000 ? 0.001 : 0.0;                       // :195-201
     else if (eigtrunc > 1.0) return fail("eigtrunc must be between 0 (no truncation) and 1 (keep largest only).");
+    if (neig_auto) {
+      if (!(eigtrunc > 0.0))
+        return fail("fit: bigkrls_fit_auto finds the rank from eigtrunc, which must be > 0 (unset, it is 0 for n <= 3000): pass eigtrunc");
+      if (n < 1024 || neig_max < 1 || 4 * neig_max > n)
+        return fail("fit: bigkrls_fit_auto needs n >= 1024 and 1 <= neig_max <= n / 4 (n = " + std::to_string((long long)n) +
+                    ", neig_max = " + std::to_string((long long)neig_max) + ")");
+    }
     derivative = opt->derivative != 0;
     vcov_est = opt->vcov_est != 0;
     if (opt->which_derivatives != nullptr) {                                                              // :206-215
@@ -382,6 +393,14 @@ struct Fit {
   }
 
   int eigen_single() {
+    if (neig_auto) {      // the buffers hold neig_cap values / columns; from here on neig is what the eigensolver returned
+      neig = neig_cap;
+      int64_t found = 0;
+      const int rc = implicit ? eigen_implicit(ctx, kop, neig_cap, dvals, neig_cap, eigtrunc, dQ, n, &lastkeeper, true, &found)
+                              : eigen_auto(ctx, dK, n, n, neig_cap, dvals, eigtrunc, dQ, n, &found, &lastkeeper);
+      if (rc == BIGKRLS_OK) neig = found;
+      return soften(rc);
+    }
     if (implicit) return soften(eigen_implicit(ctx, kop, neig, dvals, neig, eigtrunc, dQ, n, &lastkeeper));
     return soften(eigen(ctx, dK, n, n, neig, dvals, neig, eigtrunc, dQ, n, &lastkeeper));
   }
@@ -999,8 +1018,10 @@ struct Fit {
 // which failed the fit's checks (a fault of the run). Every decision in the loop is taken on
 // statuses that the ranks of a multi-GPU fit have agreed, so all of them take the same turn.
 int fit_impl(bigkrls_ctx* ctx, bigkrls_comm* comm, const double* h_X, const double* h_y, int64_t n, int64_t p,
-             const bigkrls_fit_options* opt, bigkrls_fit_outputs* out) {
+             const bigkrls_fit_options* opt, bigkrls_fit_outputs* out, bool neig_auto = false, int64_t neig_max = 0) {
   Fit f(ctx, comm, h_X, h_y, n, p, opt, out);
+  f.neig_auto = neig_auto;
+  f.neig_max = neig_max;
   BK_TRY(f.validate());
   BK_TRY(f.plan_and_allocate());
   BK_TRY(f.standardise_upload());
@@ -1201,6 +1222,11 @@ extern "C" {
 int bigkrls_fit(bigkrls_ctx* ctx, const double* h_X, const double* h_y, int64_t n, int64_t p,
                 const bigkrls_fit_options* opt, bigkrls_fit_outputs* out) {
   return fit_impl(ctx, nullptr, h_X, h_y, n, p, opt, out);
+}
+
+int bigkrls_fit_auto(bigkrls_ctx* ctx, const double* h_X, const double* h_y, int64_t n, int64_t p,
+                     const bigkrls_fit_options* opt, int64_t neig_max, bigkrls_fit_outputs* out) {
+  return fit_impl(ctx, nullptr, h_X, h_y, n, p, opt, out, true, neig_max);
 }
 
 int bigkrls_fit_dist_rows(bigkrls_comm* comm, int64_t n, const bigkrls_fit_options* opt, int64_t* r0, int64_t* r1) {

@@ -178,6 +178,36 @@ def bEigenImplicit(X: DeviceMatrix, sigma: Optional[float] = None, Neig: int = 0
                        values_dev=vals)
 
 
+def bEigenAuto(X: DeviceMatrix, sigma: Optional[float] = None, eigtrunc: float = 0.001, max_pairs: Optional[int] = None,
+               K: Optional[DeviceMatrix] = None) -> Eigenobject:
+    """bEigen without a rank (bigkrls_dev_eigen_auto): the block Lanczos grows its subspace until the spectrum is
+    resolved down to eigtrunc * lambda_1 (eigtrunc > 0) and returns what Neig = lastkeeper + 1 would: lastkeeper + 1
+    values -- the last one below the threshold -- and lastkeeper vectors. `K`: the stored kernel matrix (X, sigma are
+    then not used; the dense path takes over where the iteration does not converge); without it the operator built
+    from the standardised N x P data X, as in bEigenImplicit. `max_pairs` caps the search (default min(N // 4, 2048));
+    a spectrum with more eigenvalues above the threshold is an error."""
+    src = K if K is not None else X
+    ctx, n = src.ctx, src.nrow
+    if K is not None and K.ncol != n:
+        raise ValueError("bEigenAuto: K must be square")
+    if not (0.0 < float(eigtrunc) <= 1.0):
+        raise ValueError("bEigenAuto: eigtrunc must be in (0, 1]")
+    cap = min(n // 4, 2048) if max_pairs is None else int(max_pairs)
+    if not (1 <= cap <= n):
+        raise ValueError("bEigenAuto: max_pairs out of range")
+    p = 0 if X is None else X.ncol
+    sigma = float(p) if sigma is None else float(sigma)
+    vals = ctx.empty(cap, 1)
+    vecs = ctx.empty(n, cap)
+    nvals, nv = C.c_int64(0), C.c_int64(0)
+    _lib.call("bigkrls_dev_eigen_auto", ctx.handle, K.ptr if K is not None else None, n, K.ld if K is not None else n,
+              X.ptr if X is not None else None, X.ld if X is not None else n, p, sigma, float(eigtrunc), cap, vals.ptr,
+              vecs.ptr, vecs.ld, C.byref(nvals), C.byref(nv))
+    lastkeeper = int(nv.value)
+    return Eigenobject(values=vals.to_numpy().ravel()[:int(nvals.value)].copy(), lastkeeper=lastkeeper,
+                       vectors=vecs.cols(0, lastkeeper), values_dev=vals)
+
+
 # ---------------------------------------------------------------------------
 # solveforc / lambda search   (R/bigKRLS_Rcpp_functions.R:5-95)
 # ---------------------------------------------------------------------------

@@ -277,6 +277,22 @@ int bigkrls_dev_eigen_implicit(bigkrls_ctx* ctx, const double* X, int64_t n, int
                                int64_t n_vecs_max, double h_keep_thresh, double* vecs, int64_t ldv,
                                int64_t* h_n_vecs);
 
+/* Auto rank: the eigenpairs down to h_keep_thresh * lambda_1 (0 < h_keep_thresh <= 1 required) without a rank given.
+ * A != NULL: the stored matrix A (n x n, lda; X, ldx, p, sigma are ignored). A == NULL: the Gaussian kernel of X as an
+ * operator, as in bigkrls_dev_eigen_implicit. The block Lanczos grows its subspace until the Ritz values are resolved
+ * down to the threshold: with c = #{theta_i >= h_keep_thresh theta_1} it stops when the first c + 1 pairs -- the kept
+ * ones and one sentinel below the threshold -- have converged, and returns what a call with n_vals = c + 1 returns:
+ * *h_n_vals = c + 1 values in vals, *h_n_vecs = c eigenvectors in vecs. n_vals_max is the cap: vals holds n_vals_max
+ * doubles, vecs n_vals_max columns, and the workspace is that of a fixed run with n_vals = n_vals_max. More than
+ * n_vals_max - 1 eigenvalues at or above the threshold: BIGKRLS_EINVAL, the message names the cap, the ratio
+ * theta_cap / theta_1 reached and the threshold. Operator: n >= 1024 and 4 n_vals_max <= n, no dense fallback
+ * (BIGKRLS_ENOCONV). Stored: the iteration is tried whenever n >= 1024 and 4 n_vals_max <= n; otherwise, and where it does
+ * not converge, the dense path decomposes A with all values and the first c + 1 are returned. An eigenvalue whose
+ * multiplicity exceeds the block size (128) can be missed, as with a given rank. */
+int bigkrls_dev_eigen_auto(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t lda, const double* X, int64_t ldx,
+                           int64_t p, double sigma, double h_keep_thresh, int64_t n_vals_max, double* vals, double* vecs,
+                           int64_t ldv, int64_t* h_n_vals, int64_t* h_n_vecs);
+
 /* p[0 .. count) (device) = uniform values in [-0.5, 0.5) that depend on the element index and the seed only: the
  * start block of the block Lanczos, the same on every rank (seed 20240229 is the single-GPU library's). */
 int bigkrls_dev_fill_random(bigkrls_ctx* ctx, double* p, int64_t count, uint32_t seed);
@@ -385,7 +401,7 @@ typedef struct bigkrls_fit_options {
 typedef struct bigkrls_fit_outputs {
   int64_t struct_bytes;      /* sizeof(bigkrls_fit_outputs); checked */
   /* ---- caller-allocated host arrays; NULL = not wanted ---------------------------------------- */
-  double* eigenvalues;       /* neig values, descending; ALL are returned (quirk Q5)   :268         */
+  double* eigenvalues;       /* neig values (bigkrls_fit_auto: room for neig_max), descending; ALL are returned (quirk Q5) :268 */
   double* coeffs;            /* n                                                       :420         */
   double* yfitted;           /* n, original units                                       :428         */
   double* yfitted_std;       /* n, K c in standardised units                            :291         */
@@ -436,6 +452,17 @@ typedef struct bigkrls_fit_outputs {
  * message text in bigkrls_last_error(). */
 int bigkrls_fit(bigkrls_ctx* ctx, const double* h_X, const double* h_y, int64_t n, int64_t p,
                 const bigkrls_fit_options* options, bigkrls_fit_outputs* out);
+
+/* bigkrls_fit with the rank found by the fit (bigkrls_dev_eigen_auto) instead of given: options.neig is ignored, the
+ * eigensolver keeps the pairs down to eigtrunc * lambda_1 and one value below it. Needs eigtrunc > 0 after the default
+ * rule (n <= 3000 with eigtrunc unset, or eigtrunc = 0: BIGKRLS_EINVAL), n >= 1024 and 1 <= neig_max <= n / 4; there is
+ * no multi-GPU form. neig_max is the cap of the rank search: outputs.eigenvalues must hold neig_max doubles (and
+ * d_vcov_q, if wanted, at most neig_max - 1 columns are written), outputs.neig = lastkeeper + 1 is the number of values
+ * written, and Neffective, the lambda bounds and the search use those values, as they use the `neig` values of a fit
+ * with the rank given. More than neig_max - 1 eigenvalues at or above the threshold: BIGKRLS_EINVAL. The options and
+ * outputs structs are those of bigkrls_fit, unchanged. */
+int bigkrls_fit_auto(bigkrls_ctx* ctx, const double* h_X, const double* h_y, int64_t n, int64_t p,
+                     const bigkrls_fit_options* options, int64_t neig_max, bigkrls_fit_outputs* outputs);
 
 /* predict.bigKRLS (R/bigKRLS.R:590-621): newdata (u x p, host) is standardised with the TRAINING
  * means and sds, the u x n test kernel is built, predicted = K_new c sd(y) + mean(y).
