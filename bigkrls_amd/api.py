@@ -710,6 +710,123 @@ def marginal_effects(object: BigKRLS, newdata, which_derivatives=None, ctx: Opti
     return out
 
 
+def partial_dependence(object: BigKRLS, which=None, grid=20, newdata=None, se: bool = True, correct_SE: bool = True,
+                       vcov: Optional[str] = None, ctx: Optional[Context] = None) -> dict:
+    """Partial dependence of the fitted outcome on one predictor at a time: for every column j of `which` (1-based;
+    default: the object's which.derivatives, else all columns) and every grid value v, the mean over the reference rows
+    of the prediction with x_j set to v, with its standard error -- the curve of the expected outcome against x_j and its
+    confidence band. For a binary training column the grid is exactly its two training values (lo, hi), and
+    "first.difference" / "se.first.difference" are pd(hi) - pd(lo) and its standard error. No counterpart in the
+    reference. The numeric body is ONE call into the C ABI, `bigkrls_partial_dependence`: the Gaussian kernel factorises
+    over the columns, so all curves come from one fused O(u n) pass (`bigkrls_dev_kernel_loo_colsums`) instead of one
+    predict() on u rewritten rows per grid value; neither a u x n nor a u x u matrix is formed.
+
+    grid: an int G >= 2 (np.linspace(min, max, G) of the training column) or a list of arrays aligned with `which`; an
+    explicit grid for a binary column must hold its two training values only. newdata: the reference rows (u x p,
+    standardised with the training moments); None: the training rows. Column j of them is never read for column j's
+    curve. se / vcov: as in marginal_effects(); correct_SE: as in predict(). Returns a dict: "which", "xlabs",
+    "binaryindicator", "grid", "pd", "se.pd", "vcov.pd" (lists over the columns; the last two None without a variance),
+    "first.difference", "se.first.difference" (1 x |J|, NaN for continuous columns; the second None without a
+    variance) and "newdata"."""
+    if not isinstance(object, BigKRLS):
+        raise TypeError("Object not of class 'bigKRLS'")
+    form = _vcov_choice(object, vcov)
+    if not se:
+        form = None
+    if se and form is None:
+        raise ValueError("recompute bigKRLS object with bigKRLS(,vcov.est=TRUE) to compute standard errors")
+    if se and ("vcov.est.c.cols" in object or "rows" in object) and form != "factors":
+        raise NotImplementedError("marginal_effects of a multi-GPU fit (sharded vcov.est.c.cols) is not supported; "
+                                  "refit on one GPU or with vcov_form=\"factors\"")
+    Xh = np.asfortranarray(np.asarray(object["X"], dtype=np.float64))
+    n, p = Xh.shape
+    nd_init = nd = None
+    if newdata is not None:
+        nd_init = _as_host_matrix(newdata)
+        nd = np.array(nd_init, dtype=np.float64, order="F")
+        if nd.ndim != 2 or nd.shape[1] != p:
+            raise ValueError("ncol(newdata) differs from ncol(X) from fitted bigKRLS object")
+        if nd.shape[0] < 1:
+            raise ValueError("newdata has no rows")
+        if not np.all(np.isfinite(nd)):
+            raise ValueError("newdata contains missing or infinite values")
+    if which is None:
+        which = object.get("which.derivatives")
+    if which is None:
+        which = list(range(1, p + 1))
+    else:
+        which = [int(i) for i in np.atleast_1d(which)]
+        if not which or not all(1 <= i <= p for i in which):
+            raise ValueError("which.derivatives must index columns of X")
+    isbin = np.array([np.unique(Xh[:, j]).size == 2 for j in range(p)])          # the fit's rule (R/bigKRLS.R:242)
+    explicit = not isinstance(grid, (int, np.integer))
+    if explicit:
+        grid = list(grid)
+        if len(grid) != len(which):
+            raise ValueError("grid must be an integer or a list with one array per column of which")
+    elif grid < 2:
+        raise ValueError("grid must be at least 2")
+    grids = []
+    for idx, i in enumerate(which):
+        j = i - 1
+        lo, hi = Xh[:, j].min(), Xh[:, j].max()
+        if explicit:
+            g = np.ascontiguousarray(np.asarray(grid[idx], dtype=np.float64).ravel())
+            if g.size < 1 or not np.all(np.isfinite(g)):
+                raise ValueError(f"the grid of column {i} must hold at least one finite value")
+            if isbin[j] and not np.all((g == lo) | (g == hi)):
+                raise ValueError(f"grid column {i} is binary in the training data; its values must be "
+                                 f"one of the two training values ({lo:g}, {hi:g})")
+        if isbin[j]:
+            g = np.array([lo, hi])
+        elif not explicit:
+            g = np.linspace(lo, hi, int(grid))
+        grids.append(g)
+    ctx = ctx or object.get("_ctx") or default_context()
+    V = object.get("vcov.est.c") if form == "dense" else None
+    Vd = None if V is None else (V if is_device_matrix(V) else ctx.from_numpy(np.asarray(V, dtype=np.float64)))
+    Qd, wv = _factors(object, ctx) if form == "factors" else (None, None)
+    yv = np.ascontiguousarray(np.asarray(object["y"], dtype=np.float64).ravel())
+    coeffs = np.ascontiguousarray(np.asarray(object["coeffs"], dtype=np.float64).ravel())
+    which_arr = np.ascontiguousarray(which, dtype=np.int64)
+    nj = which_arr.size
+    sizes = np.array([g.size for g in grids], dtype=np.int64)
+    off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(sizes)]), dtype=np.int64)
+    cov_off = np.concatenate([[0], np.cumsum(sizes * sizes)])
+    flat = np.ascontiguousarray(np.concatenate(grids))
+    total = int(off[-1])
+    pd = np.empty(total)
+    sev = np.empty(total) if se else None
+    cov = np.empty(int(cov_off[-1])) if se else None
+    neff = -1.0
+    if se and correct_SE and object.get("Neffective") is not None:                # predict(): R/bigKRLS.R:610-611
+        neff = float(object["Neffective"])
+    _call_native("bigkrls_partial_dependence", ctx.handle, Xh.ctypes.data, n, p, yv.ctypes.data, coeffs.ctypes.data,
+                 float(object["sigma"]), which_arr.ctypes.data, nj, nd.ctypes.data if nd is not None else None,
+                 nd.shape[0] if nd is not None else n, flat.ctypes.data, off.ctypes.data,
+                 Vd.ptr if form == "dense" else None, Qd.ptr if form == "factors" else None,
+                 Qd.ld if form == "factors" else 0, Qd.ncol if form == "factors" else 0,
+                 wv.ctypes.data if form == "factors" else None, neff, pd.ctypes.data,
+                 sev.ctypes.data if se else None, cov.ctypes.data if se else None)
+    cut = lambda v: [v[off[i]:off[i + 1]] for i in range(nj)]
+    covs = None
+    if se:
+        covs = [cov[cov_off[i]:cov_off[i + 1]].reshape(sizes[i], sizes[i], order="F") for i in range(nj)]
+    bin_sel = isbin[which_arr - 1]
+    fd = np.full((1, nj), np.nan)
+    sefd = np.full((1, nj), np.nan) if se else None
+    for i in range(nj):
+        if bin_sel[i]:
+            fd[0, i] = pd[off[i] + 1] - pd[off[i]]
+            if se:
+                c = covs[i]
+                sefd[0, i] = np.sqrt(max(c[0, 0] + c[1, 1] - 2.0 * c[0, 1], 0.0))
+    xlabs = list(object.get("xlabs") or [f"x{i + 1}" for i in range(p)])
+    return {"which": which, "xlabs": [xlabs[i - 1] for i in which], "binaryindicator": bin_sel, "grid": grids,
+            "pd": cut(pd), "se.pd": cut(sev) if se else None, "vcov.pd": covs, "first.difference": fd,
+            "se.first.difference": sefd, "newdata": nd_init}
+
+
 def _run_folds(jobs, contexts, fit_fn, predict_fn):
     """Run independent (train, test) jobs, one worker thread per context (== per GPU), and return
     the results in job order. Fold k goes to context k mod G: a fixed assignment, and because every

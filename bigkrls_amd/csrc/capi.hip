@@ -524,6 +524,13 @@ int bigkrls_dev_kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, in
   return kernel_contract(ctx, A, u, lda, B, v, ldb, p, sigma, W, q, ldw, trans, out, ldo);
 }
 
+int bigkrls_dev_kernel_loo_colsums(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B,
+                                   int64_t v, int64_t ldb, int64_t p, double sigma, const int64_t* h_cols,
+                                   int64_t n_cols, double* out, int64_t ldo) {
+  BK_TRY(check_ctx(ctx));
+  return kernel_loo_colsums(ctx, A, u, lda, B, v, ldb, p, sigma, h_cols, n_cols, out, ldo);
+}
+
 int bigkrls_dev_quadform_diag(bigkrls_ctx* ctx, int64_t m, int64_t n, const double* A, int64_t lda, const double* V,
                               int64_t ldv, double* out) {
   BK_TRY(check_ctx(ctx));

@@ -66,7 +66,7 @@ struct bigkrls_ctx {
   bool side_is_main = false;   // BIGKRLS_NO_SIDE (diagnostics): side_stream is the main stream itself
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_pq = nullptr;
   // workspace slots: slot i is grown on demand and reused across calls
-  static constexpr int kSlots = 54;
+  static constexpr int kSlots = 57;
   void* ws[kSlots] = {nullptr};
   int64_t ws_bytes[kSlots] = {0};
   // pinned host scratch for small scalar read-backs
@@ -204,6 +204,9 @@ enum Slot {
   SLOT_KB_B = 51,          // ... the shifted copy of B (v x P) where B is not a row block of A
   SLOT_KOP_X = 52,         // implicit kernel operator (KernelOp): the centred copy of X (n x P)
   SLOT_KOP_NORMS = 53,     // ... and its squared row norms
+  SLOT_LOO_PART = 54,      // kernel_loo_colsums: partial sums of the loop splits
+  SLOT_PD_SMALL = 55,      // bigkrls_partial_dependence: standardised X and newdata, c, w, the grids, M, pd, variances
+  SLOT_PD_A = 56,          // ... one column's A_j (G_j x n, at most 1 GiB), its product with Q or vcov.est.c, the covariance
 };
 
 // BIGKRLS_VERBOSE: progress and timing lines on stderr (read at every call: it may be switched while the process runs)
@@ -296,6 +299,13 @@ int kernel_block_centred(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t l
 int kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
                     int64_t ldb, int64_t p, double sigma, const double* W, int64_t q, int64_t ldw, int trans,
                     double* out, int64_t ldo);
+
+// out (v x n_cols, ldo): out[l, jj] = sum_i exp(-(||A_i - B_l||^2 - (A[i,c] - B[l,c])^2) / sigma), c = h_cols[jj] (host,
+// 0-based): the column sums of K(A, B) with column c left out of the distance, all selected columns in one fused pass
+// (the rows of B stationary, the rows of A the loop). Operands as kernel_contract's; deterministic.
+int kernel_loo_colsums(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
+                       int64_t ldb, int64_t p, double sigma, const int64_t* h_cols, int64_t n_cols, double* out,
+                       int64_t ldo);
 
 // The same for operands that are already centred (one common shift, see centre_operands in gemm.hip) and come with
 // their squared row norms: out (ns x q, ldo) = K(S, L) W, S the stationary rows (ns x p, lds), L the loop rows

@@ -2476,6 +2476,274 @@ int kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, c
   return kernel_contract_centred(ctx, co.A, u, co.lda, co.na, co.B, v, co.ldb, co.nb, p, sigma, W, q, ldw, out, ldo);
 }
 
+// ---------------------------------------------------------------------------
+// fused leave-one-column-out column sums (partial dependence, csrc/pdep.hip)
+// ---------------------------------------------------------------------------
+// out[l, jj] = sum_i exp(-(||A_i - B_l||^2 - (A[i,c] - B[l,c])^2) / sigma), c = cols[jj]: the column sums of the kernel
+// of the two operands with column c left out of the distance, for every selected column in ONE pass. The unfused route
+// is one kernel_contract(trans = 1, W = ones) per column on copies of the operands without that column: it rebuilds the
+// Gram tile per column and spends 16 MFMAs per tile on a contraction with a vector of ones.
+// kernel_contract_kernel's frame: a wave owns 64 stationary rows (rows of B, KL_MS = 4 MFMA tiles) and KL_CW selected
+// columns and walks its share of the loop rows (rows of A) 16 at a time:
+//   G = L_tile S_tile'              mfma_f64_16x16x4(L, S): register r of a lane is (l = l0 + (lane >> 4) + 4 r, s = lane & 15)
+//   d2 = max(|s|^2 + |l|^2 - 2 G, 0)  ONCE per tile, in place of G
+//   per selected column: dj = L[l,c] - S[s,c],  e = exp(-max(d2 - dj^2, 0) / sigma),  acc[m][j] += e
+// The leave-out exponent is evaluated directly: K exp(+dj^2 / sigma) would be 0 * inf for rows that are far apart in
+// column c alone. Nothing is contracted by MFMA: a lane adds its own 4 loop rows per tile (one short chain, then one add
+// into the accumulator, so the accumulator's chain is nl / 16 long), and the four lane groups of a register (lane >> 4)
+// are added with shuffles after the loop. Loop rows past nl are weighted by 0 (mk), stationary rows past ns are computed
+// on a clamped row and not written. Loop splits and their fixed-order reduction (contract_reduce_kernel) as
+// kernel_contract: no atomics, two calls are bitwise identical.
+// Chunk width, registers per lane (a double is two; 512 in the unified file, 256 at two waves per SIMD, which
+// __launch_bounds__(NT, 2) holds the allocator to): accumulators 4 x KL_CW doubles and the stationary rows' selected-column
+// values, resident for the whole loop, 4 x KL_CW doubles: 16 KL_CW registers; resident Gram fragments sf 4 x KS <= 32
+// doubles = 64; d2 16 doubles = 32; the loop rows' values of the column in work and of the next one 8 doubles = 16;
+// masks, norms, row indices and addresses about 40; the temporaries of the exponentials in flight about 30. KL_CW = 8:
+// 128 + 64 + 32 + 16 + 40 + 30 = 310 > 256 at P = 32 (KS = 8), 286 at P = 20 -- one wave per SIMD, or spills inside the
+// loop. KL_CW = 4: 64 + 64 + 32 + 16 + 40 + 30 = 246 (P = 32), 222 (P = 20) -- the compiler reports 251 (KS = 8), 236
+// (KS = 5), 229 (KS = 0), no scratch: two waves per SIMD, the second wave's exponentials (fp64 VALU) covering the first
+// one's loads and MFMAs. The price of the narrower chunk is the Gram tile:
+// it is rebuilt per chunk, 4 KS MFMAs (<= 32) per 64 x 16 tile against 4 x 16 x KL_CW exponentials of ~30 fp64
+// instructions each -- with KL_CW = 4 still below a tenth of the wave's issue slots.
+// The selected columns travel as a kernel argument (at most KL_GROUP per launch, more columns: more launches), so the
+// host's list needs no device copy and no synchronisation.
+constexpr int KL_MS = 4;       // 16-row stationary tiles per wave
+constexpr int KL_CW = 4;       // selected columns per wave (the chunk width)
+constexpr int KL_GROUP = 64;   // selected columns per launch
+struct LooCols {
+  int c[KL_GROUP];
+};
+
+template <int KS>
+__global__ __launch_bounds__(NT, 2) void kernel_loo_colsums_kernel(
+    const double* __restrict__ S, int64_t lds, int NS, const double* __restrict__ L, int64_t ldl, int NL, int P,
+    const double* __restrict__ nrm_s, const double* __restrict__ nrm_l, double neg_inv_sigma, LooCols cols, int NC,
+    double* __restrict__ out, int64_t ldo, int64_t split_stride, int stiles, int nchunks, int nsplit, int ltiles,
+    int64_t ntasks) {
+  __shared__ double etab[32];
+  if (threadIdx.x < 32) etab[threadIdx.x] = kExp2Tab32[threadIdx.x];
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w >= ntasks) return;
+  const int st = (int)(w % stiles);
+  const int cc = (int)((w / stiles) % nchunks);
+  const int sp = (int)(w / ((int64_t)stiles * nchunks));
+  const int s0 = st * 16 * KL_MS;
+  // the chunks share the columns evenly (widths differ by at most one, none above KL_CW)
+  const int c0 = (int)((int64_t)NC * cc / nchunks), ncw = (int)((int64_t)NC * (cc + 1) / nchunks) - c0;
+  const int t_begin = (int)((int64_t)ltiles * sp / nsplit), t_end = (int)((int64_t)ltiles * (sp + 1) / nsplit);
+  const int lm = lane & 15, lk = lane >> 4;
+  const int steps = (P + 3) / 4;
+
+  int srow[KL_MS];
+  double ns[KL_MS];
+#pragma unroll
+  for (int m = 0; m < KL_MS; ++m) {
+    srow[m] = min(s0 + 16 * m + lm, NS - 1);
+    ns[m] = nrm_s[srow[m]];
+  }
+  // stationary fragments (k >= P zeroed: the loop side then reads a clamped, finite value)
+  double sf[KL_MS][KS > 0 ? KS : 1];
+  if (KS > 0) {
+#pragma unroll
+    for (int m = 0; m < KL_MS; ++m)
+#pragma unroll
+      for (int t = 0; t < (KS > 0 ? KS : 1); ++t) {
+        const int k = 4 * t + lk;
+        sf[m][t] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
+      }
+  }
+  // the chunk's columns (wave-uniform; one past the chunk's end repeats its last column and is never accumulated) and
+  // the stationary rows' values in them
+  int64_t coff[KL_CW];
+  double sc[KL_MS][KL_CW], acc[KL_MS][KL_CW];
+#pragma unroll
+  for (int j = 0; j < KL_CW; ++j) {
+    const int col = cols.c[c0 + min(j, ncw - 1)];
+    coff[j] = (int64_t)col * ldl;
+#pragma unroll
+    for (int m = 0; m < KL_MS; ++m) {
+      sc[m][j] = S[srow[m] + (int64_t)col * lds];
+      acc[m][j] = 0.0;
+    }
+  }
+
+  for (int t = t_begin; t < t_end; ++t) {
+    const int l0 = t * 16;
+    const int lrow = min(l0 + lm, NL - 1);   // this lane's row of the L operand
+    const double* lp[4];                      // this lane's loop row in accumulator register r
+    double nl[4], mk[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int l = l0 + lk + 4 * r;
+      lp[r] = L + min(l, NL - 1);
+      nl[r] = nrm_l[min(l, NL - 1)];
+      mk[r] = l < NL ? 1.0 : 0.0;
+    }
+    double lv[4];                             // the loop rows' values in the first column: in flight behind the MFMAs
+#pragma unroll
+    for (int r = 0; r < 4; ++r) lv[r] = lp[r][coff[0]];
+    d4 g[KL_MS];
+#pragma unroll
+    for (int m = 0; m < KL_MS; ++m) g[m] = (d4){0.0, 0.0, 0.0, 0.0};
+    if (KS > 0) {
+      double lf[KS > 0 ? KS : 1];
+#pragma unroll
+      for (int s = 0; s < (KS > 0 ? KS : 1); ++s) lf[s] = L[lrow + (int64_t)min(4 * s + lk, P - 1) * ldl];
+#pragma unroll
+      for (int s = 0; s < (KS > 0 ? KS : 1); ++s)
+#pragma unroll
+        for (int m = 0; m < KL_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sf[m][s], g[m], 0, 0, 0);
+    } else {
+      for (int s0k = 0; s0k < steps; s0k += 4) {
+        double lf[4], sg[KL_MS][4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const int k = 4 * (s0k + s) + lk;
+          lf[s] = L[lrow + (int64_t)min(k, P - 1) * ldl];
+#pragma unroll
+          for (int m = 0; m < KL_MS; ++m) sg[m][s] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+          for (int m = 0; m < KL_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sg[m][s], g[m], 0, 0, 0);
+      }
+    }
+    // the squared distance over ALL columns in place of G, once per tile (kernel_block_wave_kernel's epilogue)
+#pragma unroll
+    for (int m = 0; m < KL_MS; ++m)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) g[m][r] = fmax(fma(-2.0, g[m][r], ns[m] + nl[r]), 0.0);
+#pragma unroll
+    for (int j = 0; j < KL_CW; ++j) {
+      if (j < ncw) {                          // (wave-uniform)
+        double lnext[4];
+        if (j + 1 < KL_CW) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) lnext[r] = lp[r][coff[j + 1]];
+        }
+#pragma unroll
+        for (int m = 0; m < KL_MS; ++m) {
+          double tsum = 0.0;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const double dj = lv[r] - sc[m][j];
+            const double x = fmax(fma(-dj, dj, g[m][r]), 0.0);
+            tsum = fma(exp_nonpos_tab(x * neg_inv_sigma, etab), mk[r], tsum);
+          }
+          acc[m][j] += tsum;
+        }
+        if (j + 1 < KL_CW) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) lv[r] = lnext[r];
+        }
+      }
+    }
+  }
+  // the four lane groups hold the sums over the loop rows l = (lane >> 4) mod 4 of the same stationary rows
+  double* dst = out + (int64_t)sp * split_stride;
+#pragma unroll
+  for (int j = 0; j < KL_CW; ++j)
+#pragma unroll
+    for (int m = 0; m < KL_MS; ++m) {
+      double a = acc[m][j];
+      a += __shfl_xor(a, 16, 64);
+      a += __shfl_xor(a, 32, 64);
+      const int s = s0 + 16 * m + lm;
+      if (lk == 0 && j < ncw && s < NS) dst[s + (int64_t)(c0 + j) * ldo] = a;
+    }
+}
+
+// out (ns x n_cols, ldo) for operands that are already centred, with their squared row norms: S the stationary rows
+// (the rows the sums belong to), L the loop rows (the rows summed over); h_cols on the host, 0-based, validated here.
+static int kernel_loo_colsums_centred(bigkrls_ctx* ctx, const double* S, int64_t ns, int64_t lds, const double* nrm_s,
+                                      const double* L, int64_t nl, int64_t ldl, const double* nrm_l, int64_t p,
+                                      double sigma, const int64_t* h_cols, int64_t n_cols, double* out, int64_t ldo) {
+  const int steps = (int)((p + 3) / 4);
+  const int ks = steps <= 8 ? steps : 0;
+  using KlFn = void (*)(const double*, int64_t, int, const double*, int64_t, int, int, const double*, const double*,
+                        double, LooCols, int, double*, int64_t, int64_t, int, int, int, int, int64_t);
+  KlFn fn = nullptr;
+  switch (ks) {
+    case 1: fn = kernel_loo_colsums_kernel<1>; break;
+    case 2: fn = kernel_loo_colsums_kernel<2>; break;
+    case 3: fn = kernel_loo_colsums_kernel<3>; break;
+    case 4: fn = kernel_loo_colsums_kernel<4>; break;
+    case 5: fn = kernel_loo_colsums_kernel<5>; break;
+    case 6: fn = kernel_loo_colsums_kernel<6>; break;
+    case 7: fn = kernel_loo_colsums_kernel<7>; break;
+    case 8: fn = kernel_loo_colsums_kernel<8>; break;
+    default: fn = kernel_loo_colsums_kernel<0>; break;
+  }
+  int cap = 0;
+  BK_TRY(resident_capacity(ctx, (const void*)fn, &cap, NT));
+  const int64_t slots = (int64_t)cap * (NT / 64);
+  const int64_t stiles = (ns + 16 * KL_MS - 1) / (16 * KL_MS);
+  const int64_t ltiles = (nl + 15) / 16;
+  for (int64_t g0 = 0; g0 < n_cols; g0 += KL_GROUP) {
+    const int64_t nc = std::min<int64_t>(KL_GROUP, n_cols - g0);
+    LooCols lc;
+    for (int64_t j = 0; j < KL_GROUP; ++j) lc.c[j] = (int)h_cols[g0 + std::min(j, nc - 1)];
+    const int64_t nchunks = (nc + KL_CW - 1) / KL_CW;
+    // loop splits: kernel_contract_centred's model (rounds of resident waves x loop tiles per wave) and limits
+    const int64_t base = stiles * nchunks;
+    const int64_t max_split =
+        std::max<int64_t>(1, std::min<int64_t>({(int64_t)64, ltiles / 16, (64ll << 20) / (ns * nc * (int64_t)sizeof(double))}));
+    int64_t nsplit = 1;
+    double best = (double)((base + slots - 1) / slots);
+    for (int64_t s = 2; s <= max_split; ++s) {
+      const double cost = (double)((base * s + slots - 1) / slots) / (double)s;
+      if (cost < best * 0.98) { best = cost; nsplit = s; }
+    }
+    const int64_t ntasks = base * nsplit;
+    BK_REQUIRE((ntasks + 3) / 4 < (1ll << 31), "kernel_loo_colsums: too many tiles");
+    double* og = out + g0 * ldo;
+    double* dst = og;
+    int64_t ldd = ldo, split_stride = 0;
+    if (nsplit > 1) {
+      void* pp = nullptr;
+      BK_TRY(ws_get(ctx, SLOT_LOO_PART, nsplit * ns * nc * (int64_t)sizeof(double), &pp));
+      dst = (double*)pp;
+      ldd = ns;
+      split_stride = ns * nc;
+    }
+    BK_TRY(prof_begin(ctx, "kernel_loo_colsums", (double)ns * (double)nl * (double)nc));
+    hipLaunchKernelGGL(fn, dim3((unsigned)((ntasks + 3) / 4)), dim3(NT), 0, ctx->stream, S, lds, (int)ns, L, ldl, (int)nl,
+                       (int)p, nrm_s, nrm_l, -1.0 / sigma, lc, (int)nc, dst, ldd, split_stride, (int)stiles, (int)nchunks,
+                       (int)nsplit, (int)ltiles, ntasks);
+    BK_CHECK_LAUNCH();
+    if (nsplit > 1) {
+      const int blocks = (int)std::min<int64_t>((ns * nc + 255) / 256, 4096);
+      hipLaunchKernelGGL(contract_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (int)ns, (int)nc, (int)nsplit,
+                         (const double*)dst, og, ldo);
+      BK_CHECK_LAUNCH();
+    }
+    BK_TRY(prof_end(ctx, "kernel_loo_colsums"));
+  }
+  return BIGKRLS_OK;
+}
+
+int kernel_loo_colsums(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
+                       int64_t ldb, int64_t p, double sigma, const int64_t* h_cols, int64_t n_cols, double* out,
+                       int64_t ldo) {
+  BK_REQUIRE(u > 0 && v > 0 && p > 0, "kernel_loo_colsums: bad dimensions");
+  BK_REQUIRE(u < (1ll << 31) && v < (1ll << 31) && p < (1ll << 20), "kernel_loo_colsums: too large");
+  BK_REQUIRE(sigma > 0.0, "kernel_loo_colsums: sigma must be > 0");
+  BK_REQUIRE(A && B && h_cols && out, "kernel_loo_colsums: null pointer");
+  BK_REQUIRE(lda >= u && ldb >= v, "kernel_loo_colsums: leading dimension of A or B too small");
+  BK_REQUIRE(ldo >= v, "kernel_loo_colsums: leading dimension of out too small");
+  BK_REQUIRE(n_cols >= 1 && n_cols < (1ll << 20), "kernel_loo_colsums: n_cols must be at least 1 (and below 2^20)");
+  for (int64_t j = 0; j < n_cols; ++j)
+    BK_REQUIRE(h_cols[j] >= 0 && h_cols[j] < p, "kernel_loo_colsums: column index " + std::to_string(h_cols[j]) +
+                                                    " outside [0, " + std::to_string(p) + ")");
+  CentredOperands co;     // both operands moved by the column means of A (see centre_operands)
+  BK_TRY(centre_operands(ctx, A, u, lda, B, v, ldb, p, &co));
+  // the rows of B are stationary, the rows of A the loop (kernel_contract's trans = 1)
+  return kernel_loo_colsums_centred(ctx, co.B, v, co.ldb, co.nb, co.A, u, co.lda, co.na, p, sigma, h_cols, n_cols, out, ldo);
+}
+
 // ---- the kernel matrix of one data set as an operator (kernel = "implicit": csrc/eigen.hip, csrc/fit.hip) -----------
 // The centred copy of X and its squared row norms live in slots of their own, so that they survive every other kernel
 // build or contraction of the context until the next kernel_op_prepare.

@@ -76,6 +76,20 @@ def bKernelContract(A: DeviceMatrix, B: DeviceMatrix, W: DeviceMatrix, sigma: fl
     return out
 
 
+def bKernelLooColsums(A: DeviceMatrix, B: DeviceMatrix, sigma: float, cols) -> DeviceMatrix:
+    """out (nrow(B) x len(cols)): out[l, jj] = sum_i exp(-(||A_i - B_l||^2 - (A[i,c] - B[l,c])^2) / sigma), c = cols[jj]
+    (0-based): the column sums of bTempKernel(A, B) with column c left out of the distance, all selected columns in one
+    fused pass (bigkrls_dev_kernel_loo_colsums). No counterpart in the reference."""
+    ctx = A.ctx
+    if A.ncol != B.ncol:
+        raise ValueError("bKernelLooColsums: column counts of A and B differ")
+    h_cols = np.ascontiguousarray(cols, dtype=np.int64).ravel()
+    out = ctx.empty(B.nrow, max(int(h_cols.size), 1))
+    _lib.call("bigkrls_dev_kernel_loo_colsums", ctx.handle, A.ptr, A.nrow, A.ld, B.ptr, B.nrow, B.ld, A.ncol,
+              float(sigma), h_cols.ctypes.data, int(h_cols.size), out.ptr, out.ld)
+    return out
+
+
 def bQuadformDiag(A: DeviceMatrix, V: DeviceMatrix) -> DeviceMatrix:
     """diag(A V A') (m x 1) for A m x n and a general V n x n: out[i] = sum_j (A V)[i,j] A[i,j], without storing
     A V (bigkrls_dev_quadform_diag). No counterpart in the reference."""

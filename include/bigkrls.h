@@ -100,7 +100,8 @@ int bigkrls_ctx_release_workspace(bigkrls_ctx* ctx);
  * k = 512, flops), "panel_qr" and "bulge_chase" (algorithmic bytes), "lanczos_kb" /
  * "lanczos_cgs2" (block-Lanczos step, flops), "symv" (one-stage path, bytes of the
  * lower triangle streamed), "solveforc_probe", "deriv_rows", "yhat_gemv" (algorithmic
- * bytes: 8 N K per probe, 8 N^2, 8 N^2), "vcov_syrk" (N (N + 1) K flops per matrix). */
+ * bytes: 8 N K per probe, 8 N^2, 8 N^2), "vcov_syrk" (N (N + 1) K flops per matrix),
+ * "kernel_loo_colsums" (u v n_cols exponentials). */
 int bigkrls_ctx_set_profile(bigkrls_ctx* ctx, int enable);
 int bigkrls_ctx_get_profile(bigkrls_ctx* ctx, const char* name, double* total_ms,
                             double* total_work, int64_t* launches);
@@ -209,6 +210,18 @@ int bigkrls_dev_kernel_block(bigkrls_ctx* ctx, const double* A, int64_t u, int64
 int bigkrls_dev_kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda,
                                 const double* B, int64_t v, int64_t ldb, int64_t p, double sigma,
                                 const double* W, int64_t q, int64_t ldw, int trans, double* out, int64_t ldo);
+
+/* Fused leave-one-column-out column sums: out (v x n_cols, ldo >= v),
+ *   out[l, jj] = sum_i exp(-(||A_i - B_l||^2 - (A[i,c] - B[l,c])^2) / sigma),   c = h_cols[jj] (host, 0-based),
+ * i.e. the column sums of bigkrls_dev_kernel_block's kernel K(A, B) with column c left out of the distance, for all
+ * selected columns in one pass (A u x p, B v x p as in bigkrls_dev_kernel_contract; what n_cols calls of it with
+ * trans = 1 and W = ones on copies of A and B without column c give, with the Gram tile shared between the columns).
+ * The leave-out exponent is formed directly, never as K exp(+(A[i,c] - B[l,c])^2 / sigma). Extra device memory
+ * O((u + v) (p + n_cols)), never O(u v). Deterministic: two calls give bitwise identical results. A and B need not
+ * be centred. A column index outside [0, p) or n_cols < 1 is BIGKRLS_EINVAL. */
+int bigkrls_dev_kernel_loo_colsums(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B,
+                                   int64_t v, int64_t ldb, int64_t p, double sigma, const int64_t* h_cols,
+                                   int64_t n_cols, double* out, int64_t ldo);
 
 /* Diagonal of a quadratic form: out[i] = sum_j (A V)[i,j] A[i,j] = diag(A V A')[i], A m x n (lda >= m),
  * V n x n (ldv >= n), both column-major; V is general (not assumed symmetric). out has m entries. The m x n product
@@ -557,6 +570,31 @@ int bigkrls_marginal_effects_se(bigkrls_ctx* ctx, const double* h_X, int64_t n, 
                                 const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
                                 const double* h_newdata, int64_t u, const double* d_vcov_c, const double* d_Q,
                                 int64_t ldq, int64_t k, const double* h_w, int64_t block_rows, double* h_se);
+
+/* Partial dependence of the fitted outcome on one predictor at a time, with its covariance over the grid (no
+ * counterpart in the reference). For every selected column j (h_which, 1-based, n_which entries; NULL: all p) and every
+ * raw grid value v of it (h_grid: the columns' grids concatenated, column jj's at h_grid_off[jj] .. h_grid_off[jj + 1],
+ * G_j >= 1 values each; T = h_grid_off[n_which] in all):
+ *   h_pd  = the mean over the reference rows of the prediction with column j set to v (original units),
+ *   h_se  = its standard error (T values; may be NULL),
+ *   h_cov = the G_j x G_j covariance of column j's curve, column-major, the columns' blocks one after the other
+ *           (sum_j G_j^2 doubles; may be NULL).
+ * The reference rows are h_newdata (u x p, host), standardised with the TRAINING means and sds; NULL: the training rows
+ * (u is then ignored). Column j of the reference rows is never read for column j's curve. Standardisation, validation
+ * and error messages follow bigkrls_marginal_effects. vcov.est.c comes as the n x n matrix (d_vcov_c, ld n) or as its
+ * factors (d_Q n x k on the device, ldq >= n; h_w the k weights on the host): at most one of them (else BIGKRLS_EINVAL);
+ * with neither, h_se and h_cov must be NULL. The variances carry bigkrls_predict's factor for neffective > 0, so with
+ * the same neffective h_se^2 is the mean of bigkrls_predict's vcov.est.pred over the rewritten rows.
+ * The Gaussian kernel factorises over the columns, so in standardised units pd_j(v) = mean(y) + sd(y) a_j(v)' c with
+ * a_j(v)[l] = (1/u) M[l,j] exp(-(vs - Xs[l,j])^2 / sigma) and M = bigkrls_dev_kernel_loo_colsums(Zs, Xs): ONE fused
+ * O(u n) pass for all columns; per column A_j (G_j x n) is written, pd = A_j c, and cov_j = (A_j Q diag(w)) (A_j Q)' or
+ * (A_j vcov.est.c) A_j', its diagonal from bigkrls_dev_rowsumsq_weighted or bigkrls_dev_quadform_diag.
+ * 8 G_j n <= 2^30 bytes (A_j fits 1 GiB unblocked), else BIGKRLS_EINVAL naming the column, G_j and the cap. */
+int bigkrls_partial_dependence(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                               const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
+                               const double* h_newdata, int64_t u, const double* h_grid, const int64_t* h_grid_off,
+                               const double* d_vcov_c, const double* d_Q, int64_t ldq, int64_t k, const double* h_w,
+                               double neffective, double* h_pd, double* h_se, double* h_cov);
 
 /* =============================================================================
  * Multi-GPU: one process per GPU, the collectives inside the library (the context's
