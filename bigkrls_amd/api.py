@@ -446,6 +446,8 @@ def summary(object: BigKRLS, degrees: str = "Neffective", probs=(0.05, 0.25, 0.5
         say("N Effective:", n)
     p = Xh.shape[1]
     say("R2:", round(float(object["R2"]), digits))
+    if object.get("vcov.type") not in (None, "classical"):
+        say("vcov:", object["vcov.type"])
     if object.get("derivatives") is None:                                         # :700-703
         say("\nrecompute with bigKRLS(..., derivative = TRUE) for estimates of marginal effects\n")
         return None
@@ -707,6 +709,107 @@ def marginal_effects(object: BigKRLS, newdata, which_derivatives=None, ctx: Opti
                      Qd.ld if form == "factors" else 0, Qd.ncol if form == "factors" else 0,
                      wv.ctypes.data if form == "factors" else None, int(_block_rows), sed.ctypes.data)
         out["se.derivatives"] = sed
+    return out
+
+
+ROBUST_TYPES = {"classical": 0, "HC0": 1, "HC1": 2, "HC2": 3, "HC3": 4, "CR0": 1, "CR1": 2}
+
+
+def _robust_plan(object, type, cluster):
+    """Everything robust_vcov() decides before it touches the library: the validated inputs, the native type code, the
+    scalar factor on the middle matrix, and the cluster labels mapped to 0 .. G - 1 (or None)."""
+    if not isinstance(object, BigKRLS):
+        raise TypeError("Object not of class 'bigKRLS'")
+    if type not in ROBUST_TYPES:
+        raise ValueError('type must be one of "classical", "HC0", "HC1", "HC2", "HC3", or "CR0", "CR1" with cluster')
+    if object.get("vcov.est.Q") is None or object.get("vcov.est.w") is None:
+        raise ValueError('the object has no vcov.est.Q / vcov.est.w: refit with vcov_form="factors" or "both"')
+    clustered = type.startswith("CR")
+    if clustered and cluster is None:
+        raise ValueError(f'type="{type}" needs cluster (one label per row)')
+    if cluster is not None and not clustered:
+        raise ValueError(f'cluster goes with type="CR0" or "CR1", not "{type}"')
+    n = np.asarray(object["X"]).shape[0]
+    k = len(np.asarray(object["vcov.est.w"]).ravel())
+    d = np.asarray(object["K.eigenvalues"], dtype=np.float64).ravel()
+    if tuple(getattr(object["vcov.est.Q"], "shape", ())) != (n, k):
+        raise ValueError("vcov.est.Q must be nrow(X) x length(vcov.est.w)")
+    if k < 1 or d.size < k:
+        raise ValueError("the object's K.eigenvalues do not cover its vcov.est.w")
+    for key in ("lambda", "y", "yfitted.std", "sigmasq", "Neffective"):
+        if object.get(key) is None:
+            raise ValueError(f"the object has no {key}")
+    labels = G = None
+    if clustered:
+        raw = list(cluster.tolist() if isinstance(cluster, np.ndarray) else cluster)
+        if len(raw) != n:
+            raise ValueError(f"cluster must have one label per row: {len(raw)} labels for N = {n}")
+        index = {}
+        labels = np.empty(n, dtype=np.int64)
+        for i, lab in enumerate(raw):                        # any hashable labels, numbered in order of appearance
+            labels[i] = index.setdefault(lab, len(index))
+        G = len(index)
+        if G < 2:
+            raise ValueError("cluster must hold at least 2 distinct labels")
+    if type == "classical":
+        scale = float(object["sigmasq"])
+    elif type == "HC1":
+        scale = n / float(object["Neffective"])
+    elif type == "CR1":
+        scale = G / (G - 1.0)
+    else:
+        scale = 1.0
+    yv = np.asarray(object["y"], dtype=np.float64).ravel()
+    y_sd = _sd(yv)
+    resid = np.ascontiguousarray((yv - yv.mean()) / y_sd - np.asarray(object["yfitted.std"], dtype=np.float64).ravel())
+    return {"n": n, "k": k, "d": np.ascontiguousarray(d[:k]), "code": ROBUST_TYPES[type], "scale": float(scale),
+            "labels": labels, "G": G, "y_sd": float(y_sd), "resid": resid}
+
+
+def robust_vcov(object: BigKRLS, type: str = "HC1", cluster=None, ctx: Optional[Context] = None) -> BigKRLS:
+    """Heteroskedasticity- or cluster-robust variance of the coefficients of a fitted model, without refitting and
+    without an N x N matrix: a NEW object whose `vcov.est.Q` / `vcov.est.w` are the factors of the sandwich
+    V_r = G diag(omega) G, G = Q diag(1 / (d + lambda)) Q' on the fit's kept eigenpairs, so that predict(se_pred=True),
+    marginal_effects(), marginal_effects(se=True), partial_dependence(), summary() and save_bigKRLS() work from it as
+    they do from a fit with vcov_form="factors". The input object is untouched. No counterpart in the reference.
+
+    type: "classical" (omega = sigmasq: the fit's own variance, rotated), "HC0" (e_i^2), "HC1" (HC0 times
+    N / Neffective, the package's degrees of freedom), "HC2" (e_i^2 / (1 - h_i)), "HC3" (e_i^2 / (1 - h_i)^2) with h the
+    leverages of the smoother K (K + lambda I)^-1; "CR0" / "CR1" with `cluster` (N hashable labels, at least 2 distinct):
+    the clustered middle sum_g s_g s_g', s_g the score sum of cluster g, CR1 times G / (G - 1).
+
+    The object must carry the factors (a fit with vcov_form="factors" or "both"; kernel="implicit", Neig="auto" and
+    multi-GPU objects do). The numeric body is ONE call into the C ABI, `bigkrls_vcov_robust`. In the result
+    `vcov.est.c` and `vcov.est.fitted` are None: the identity vcov.est.fitted = Q diag(w d^2) Q' does not hold for the
+    rotated factors, and standard errors of fitted values come from predict(obj, X, se_pred=True). `vcov.type` is the
+    type, `vcov.clusters` the number of clusters or None; with derivatives in the object `var.avgderivatives` (and
+    `.std`) are recomputed from the new factors, so summary() reports robust standard errors."""
+    plan = _robust_plan(object, type, cluster)
+    ctx = ctx or object.get("_ctx") or default_context()
+    n, k = plan["n"], plan["k"]
+    Qd, _ = _factors(object, ctx)                              # (raises unless Q is N x length(vcov.est.w))
+    Qout = ctx.empty(n, k)
+    wout = np.zeros(k)
+    labels = plan["labels"]
+    _call_native("bigkrls_vcov_robust", ctx.handle, n, k, Qd.ptr, Qd.ld, plan["d"].ctypes.data, float(object["lambda"]),
+                 plan["resid"].ctypes.data, plan["y_sd"], plan["scale"], plan["code"],
+                 labels.ctypes.data if labels is not None else None, plan["G"] or 0, Qout.ptr, Qout.ld,
+                 wout.ctypes.data)
+    out = BigKRLS(object)
+    for key in ("vcov.est.c.cols", "vcov.est.fitted.cols", "path", "model_subfolder_name"):
+        out.pop(key, None)
+    out["vcov.est.Q"], out["vcov.est.w"] = Qout, wout
+    out["vcov.est.c"] = out["vcov.est.fitted"] = None
+    out["vcov.type"], out["vcov.clusters"] = type, plan["G"]
+    out["_ctx"] = ctx
+    if object.get("derivatives") is not None:
+        me = marginal_effects(out, out["X"], ctx=ctx, vcov="factors")
+        var = np.asarray(me["var.avgderivatives"], dtype=np.float64)
+        out["var.avgderivatives"] = var
+        if object.get("var.avgderivatives.std") is not None:  # standardised units: the fit's g = sd(y) / sd(x_j), var = g^2 var.std
+            Xh = np.asarray(out["X"], dtype=np.float64)
+            g = plan["y_sd"] / np.array([_sd(Xh[:, j - 1]) for j in me["which.derivatives"]])
+            out["var.avgderivatives.std"] = var.ravel() / (g * g)
     return out
 
 

@@ -66,7 +66,7 @@ struct bigkrls_ctx {
   bool side_is_main = false;   // BIGKRLS_NO_SIDE (diagnostics): side_stream is the main stream itself
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_pq = nullptr;
   // workspace slots: slot i is grown on demand and reused across calls
-  static constexpr int kSlots = 57;
+  static constexpr int kSlots = 60;
   void* ws[kSlots] = {nullptr};
   int64_t ws_bytes[kSlots] = {0};
   // pinned host scratch for small scalar read-backs
@@ -207,6 +207,9 @@ enum Slot {
   SLOT_LOO_PART = 54,      // kernel_loo_colsums: partial sums of the loop splits
   SLOT_PD_SMALL = 55,      // bigkrls_partial_dependence: standardised X and newdata, c, w, the grids, M, pd, variances
   SLOT_PD_A = 56,          // ... one column's A_j (G_j x n, at most 1 GiB), its product with Q or vcov.est.c, the covariance
+  SLOT_RV_SMALL = 57,      // bigkrls_vcov_robust: g, d g, residuals, leverages, omega, M, S, U, theta, the cluster scores
+  SLOT_CS_PART = 58,       // cluster_scores: the sums of the pieces of clusters that span several 64-row chunks
+  SLOT_CS_INDEX = 59,      // ... the sort permutation, the rows' pieces, the pieces' destinations, the multi-piece clusters
 };
 
 // BIGKRLS_VERBOSE: progress and timing lines on stderr (read at every call: it may be switched while the process runs)
@@ -280,6 +283,10 @@ int gemm(bigkrls_ctx* ctx, int ta, int tb, int64_t m, int64_t n, int64_t k, doub
 // gemm()'s tiles and deterministic split-K choice; with r = 1, t = 0 bitwise gemm(0, 0, .., 1.0, .., 0.0, ..).
 int gemm_modulated(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* r,
                    const double* t, const double* s, const double* B, int64_t ldb, double* C, int64_t ldc);
+// M (k x k, ldm, overwritten) = A' diag(omega) A, A n x k (lda), omega n entries on the device. The weight is applied in
+// registers on the way to LDS (no weighted copy of A); lower tiles only, mirrored: exactly symmetric. Deterministic.
+int gram_weighted(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* A, int64_t lda, const double* omega, double* M,
+                  int64_t ldm);
 // C (m x n, n <= 48) = A (m x k) B (k x n), both not transposed: the 128 x 48 tile of the marginal-effects pass
 int gemm_nn_skinny48(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* B,
                      int64_t ldb, double* C, int64_t ldc);
@@ -383,6 +390,12 @@ int shift_rows_sqnorms(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t p, 
                        double* out, double* norms);
 int copy_matrix(bigkrls_ctx* ctx, const double* A, int64_t m, int64_t n, int64_t lda, double* B,
                 int64_t ldb);
+
+// ---- robust.hip ---------------------------------------------------------------
+// S (k x G, lds, overwritten): S[j, g] = sum over the rows i with h_cluster[i] == g of e[i] A[i, j]; A n x k (lda) and
+// e (n) on the device, the labels on the host. Deterministic (fixed-order segmented sums, no atomics).
+int cluster_scores(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* A, int64_t lda, const double* e,
+                   const int64_t* h_cluster, int64_t G, double* S, int64_t lds);
 
 // ---- solveforc.hip ------------------------------------------------------------
 int qty(bigkrls_ctx* ctx, const double* Q, int64_t n, int64_t k, int64_t ldq, const double* y,

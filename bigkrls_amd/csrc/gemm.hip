@@ -165,11 +165,15 @@ struct GemmMod {
 // Computes the accumulators of the (m0, n0) block tile over k in [kbeg, kend).
 // TA/TB: operand is used transposed (op(A) = A' with A stored K x M, etc.).
 // MOD: the A operand is modulated (GemmMod) between its staging registers and LDS; off, `mod` is never read.
-template <bool TA, bool TB, int BN, bool GATHER = false, bool DEEP = false, bool MOD = false>
+// WK: a transposed A operand (k-contiguous) is weighted along the contraction, op(A)(m, k) = A(k, m) wk[k], between its
+// staging registers and LDS (gram_weighted: A' diag(wk) B); off, `wk` is never read.
+template <bool TA, bool TB, int BN, bool GATHER = false, bool DEEP = false, bool MOD = false, bool WK = false>
 __device__ __forceinline__ void gemm_tile(const GemmOperands& g, int m0, int n0, int kbeg,
                                           int kend, double* __restrict__ smem,
-                                          d4 (&acc)[4][BN / 32], const GemmMod* mod = nullptr) {
+                                          d4 (&acc)[4][BN / 32], const GemmMod* mod = nullptr,
+                                          const double* __restrict__ wk = nullptr) {
   static_assert(!MOD || (!TA && !GATHER), "gemm_tile: the modulated A operand is not transposed and not gathered");
+  static_assert(!WK || (TA && !GATHER && !MOD), "gemm_tile: the k-weighted A operand is transposed, not gathered, not modulated");
   constexpr int NJ = BN / 32;
   // A tile: op(A)(m,k). not transposed: A[m + k lda] -> contiguous along m.
   constexpr bool A_CONTIG = !TA;
@@ -240,9 +244,16 @@ __device__ __forceinline__ void gemm_tile(const GemmOperands& g, int m0, int n0,
     mod_t = mod->t[gc];
     ps = mod->s + kbeg + tid / BM;
   }
+  // Weighted transposed A (k-contiguous: this thread stages the k row kbeg + (tid & 15) of every k-tile for BM / 16
+  // columns): one weight per thread and k-tile, loaded with the tile and clamped like the tile's own addresses.
+  if (WK) ps = wk + kbeg + (tid & 15);
   auto mod_load = [&](int k0, double (&xs)[MQ]) {
     constexpr int KS = NT / BM;
-    if (k0 + BK <= kend) {
+    if constexpr (WK) {
+      const int gk = k0 + (tid & 15);
+      const double* pw = (k0 + BK <= kend) ? ps : wk + (gk < kend ? gk : kend - 1);   // (one load, of a valid address)
+      xs[0] = *pw;
+    } else if (k0 + BK <= kend) {
 #pragma unroll
       for (int q = 0; q < MQ; ++q) xs[q] = ps[q * KS];
     } else {
@@ -256,8 +267,13 @@ __device__ __forceinline__ void gemm_tile(const GemmOperands& g, int m0, int n0,
     ps += BK;
   };
   auto mod_apply = [&](double (&xa)[BM / 16], const double (&xs)[MQ]) {
+    if constexpr (WK) {
 #pragma unroll
-    for (int q = 0; q < MQ; ++q) xa[q] *= fma(mod_t, xs[q], mod_r);
+      for (int q = 0; q < BM / 16; ++q) xa[q] *= xs[0];
+    } else {
+#pragma unroll
+      for (int q = 0; q < MQ; ++q) xa[q] *= fma(mod_t, xs[q], mod_r);
+    }
   };
   auto load_tiles = [&](int k0) {
     const bool full = k0 + BK <= kend;
@@ -265,7 +281,7 @@ __device__ __forceinline__ void gemm_tile(const GemmOperands& g, int m0, int n0,
     else tile_load<A_CONTIG, BM, GATHER>(g.A, g.lda, m0, k0, g.M, kend, ra, g.kidx);
     if (full && b_fast) tile_load_strided<BN>(pb, sb, rb);
     else tile_load<B_CONTIG, BN>(g.B, g.ldb, n0, k0, g.N, kend, rb);
-    if constexpr (MOD) mod_load(k0, rs);
+    if constexpr (MOD || WK) mod_load(k0, rs);
     pa += ia;
     pb += ib;
   };
@@ -302,12 +318,12 @@ __device__ __forceinline__ void gemm_tile(const GemmOperands& g, int m0, int n0,
       else tile_load<A_CONTIG, BM, GATHER>(g.A, g.lda, m0, k0, g.M, kend, xa, g.kidx);
       if (full && b_fast) tile_load_strided<BN>(pb, sb, xb);
       else tile_load<B_CONTIG, BN>(g.B, g.ldb, n0, k0, g.N, kend, xb);
-      if constexpr (MOD) mod_load(k0, xs);
+      if constexpr (MOD || WK) mod_load(k0, xs);
       pa += ia;
       pb += ib;
     };
     auto stage = [&](int k0, int st, double (&xa)[BM / 16], double (&xb)[BN / 16], const double (&xs)[MQ]) {
-      if constexpr (MOD) mod_apply(xa, xs);
+      if constexpr (MOD || WK) mod_apply(xa, xs);
       if (k0 + BK > kend) {
         tile_zero_ktail<A_CONTIG, BM>(k0, kend, xa);
         tile_zero_ktail<B_CONTIG, BN>(k0, kend, xb);
@@ -336,7 +352,7 @@ __device__ __forceinline__ void gemm_tile(const GemmOperands& g, int m0, int n0,
   }
 
   load_tiles(kbeg);
-  if constexpr (MOD) mod_apply(ra, rs);
+  if constexpr (MOD || WK) mod_apply(ra, rs);
   if (kbeg + BK > kend) {
     tile_zero_ktail<A_CONTIG, BM>(kbeg, kend, ra);
     tile_zero_ktail<B_CONTIG, BN>(kbeg, kend, rb);
@@ -351,7 +367,7 @@ __device__ __forceinline__ void gemm_tile(const GemmOperands& g, int m0, int n0,
     if (t + 1 < ntiles) load_tiles(k0);
     mfma_tile(cur);
     if (t + 1 < ntiles) {
-      if constexpr (MOD) mod_apply(ra, rs);
+      if constexpr (MOD || WK) mod_apply(ra, rs);
       if (k0 + BK > kend) {  // partial last tile: k rows past the end must contribute zeros
         tile_zero_ktail<A_CONTIG, BM>(k0, kend, ra);
         tile_zero_ktail<B_CONTIG, BN>(k0, kend, rb);
@@ -547,13 +563,17 @@ static void gemm_split_plan(const GemmOperands& g, int ntile, int* splits_out, i
   *k_chunk_out = k_chunk;
 }
 
+// GEMMs issued on the look-ahead stream run concurrently with main-stream GEMMs: own partial buffer
+static int gemm_split_slot(const bigkrls_ctx* ctx) {
+  return (ctx->side_stream && (ctx->stream == ctx->side_stream || ctx->stream == ctx->bg_stream)) ? SLOT_SIDE_SPLITK : SLOT_GEMM_SPLITK;
+}
+
 // the slabs of the split-K partials (splits x M x N doubles); nullptr for a single split
 static int gemm_split_partials(bigkrls_ctx* ctx, const GemmOperands& g, int splits, double** partial) {
   *partial = nullptr;
   if (splits > 1) {
     void* p = nullptr;
-    // GEMMs issued on the look-ahead stream run concurrently with main-stream GEMMs: own partial buffer
-    const int slot = (ctx->side_stream && (ctx->stream == ctx->side_stream || ctx->stream == ctx->bg_stream)) ? SLOT_SIDE_SPLITK : SLOT_GEMM_SPLITK;
+    const int slot = gemm_split_slot(ctx);
     BK_TRY(ws_get(ctx, slot, (int64_t)splits * g.M * g.N * sizeof(double), &p));
     *partial = (double*)p;
   }
@@ -709,6 +729,131 @@ int gemm_modulated(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const doub
   else if (n <= 64) BK_TRY(launch_gemm_modulated<64>(ctx, g, mod, C, ldc));
   else BK_TRY(launch_gemm_modulated<128>(ctx, g, mod, C, ldc));
   BK_TRY(prof_end(ctx, "gemm_modulated"));
+  return BIGKRLS_OK;
+}
+
+// ---------------------------------------------------------------------------
+// M (k x k) = A' diag(omega) A, A n x k column-major: the weighted Gram matrix of the sandwich variance
+// (csrc/robust.hip). The T,N form of gemm_tile has both operands contiguous along the contraction; the weight is
+// applied to the A-side tile in registers on its way to LDS (gemm_tile<.., WK>), so diag(omega) A is never written.
+// Only the tiles on or below the diagonal are computed (k <= 64: the one BN-wide tile; else 128 x 128 tiles), and of
+// those only the entries with row >= column are used: each is written to (i, j) and to (j, i), inside diagonal tiles
+// too, so the result is symmetric bit for bit. The contraction is n long against a handful of tiles, so it is split
+// over n by gemm_split_plan, taken over the computed tiles; the slabs (one 128 x BN block per tile and split) are
+// summed in slab order by gram_reduce_kernel: no atomics, two calls give the same bits.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void gram_tile_of(int t, int T, int* tm, int* tn) {   // column-major walk of the lower tile triangle
+  int c = 0, rem = t;
+  while (rem >= T - c) { rem -= T - c; ++c; }
+  *tn = c;
+  *tm = c + rem;
+}
+
+template <int BN>
+__global__ __launch_bounds__(NT, (gemm_occ<true, false, BN>())) void gram_weighted_kernel(
+    GemmOperands g, const double* __restrict__ omega, double* __restrict__ C, int64_t ldc, int T, int ntile, int k_chunk,
+    double* __restrict__ partial) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int t = xcd_remap(blockIdx.x, ntile);
+  int tm, tn;
+  gram_tile_of(t, T, &tm, &tn);
+  const int m0 = tm * BM, n0 = tn * BN;   // (T > 1 only with BN == BM)
+  const int z = blockIdx.y;
+  const int kbeg = z * k_chunk;
+  const int kend = min(g.K, kbeg + k_chunk);
+  d4 acc[4][BN / 32];
+  gemm_tile<true, false, BN, false, (BN <= GEMM_DEEP_BN), false, true>(g, m0, n0, kbeg, kend, smem, acc, nullptr, omega);
+  const int M = g.M;
+  if (partial != nullptr) {
+    double* P = partial + ((int64_t)z * ntile + t) * (BM * BN);
+    acc_foreach<BN>(acc, m0, n0, [&](int m, int n, double v) {
+      if (m < M && n < M && m >= n) P[(m - m0) + (n - n0) * BM] = v;
+    });
+  } else {
+    acc_foreach<BN>(acc, m0, n0, [&](int m, int n, double v) {
+      if (m < M && n < M && m >= n) {
+        C[(int64_t)m + (int64_t)n * ldc] = v;
+        C[(int64_t)n + (int64_t)m * ldc] = v;
+      }
+    });
+  }
+}
+
+// BM * bn / 256 workgroups per tile, all in grid.x (the tile count T (T + 1) / 2 passes the 65 535 of grid.y near
+// k = 46 000); the slabs of an entry in the fixed order z = 0, 1, ...
+__global__ void gram_reduce_kernel(const double* __restrict__ partial, int splits, int ntile, int T, int bn, int M,
+                                   double* __restrict__ C, int64_t ldc) {
+  const int per_tile = BM * bn;
+  const int wg_per_tile = per_tile / 256;
+  const int t = blockIdx.x / wg_per_tile;
+  int tm, tn;
+  gram_tile_of(t, T, &tm, &tn);
+  const int m0 = tm * BM, n0 = tn * bn;
+  const int64_t slab = (int64_t)ntile * per_tile;
+  {
+    const int e = (blockIdx.x % wg_per_tile) * 256 + threadIdx.x;
+    const int m = m0 + e % BM, n = n0 + e / BM;
+    if (m >= M || n >= M || m < n) return;
+    const double* p = partial + (int64_t)t * per_tile + e;
+    double s = 0.0;
+    int z = 0;
+    for (; z + 4 <= splits; z += 4) {
+      const double a0 = p[(int64_t)(z + 0) * slab], a1 = p[(int64_t)(z + 1) * slab];
+      const double a2 = p[(int64_t)(z + 2) * slab], a3 = p[(int64_t)(z + 3) * slab];
+      s += a0; s += a1; s += a2; s += a3;
+    }
+    for (; z < splits; ++z) s += p[(int64_t)z * slab];
+    C[(int64_t)m + (int64_t)n * ldc] = s;
+    C[(int64_t)n + (int64_t)m * ldc] = s;
+  }
+}
+
+template <int BN>
+static int launch_gram_weighted(bigkrls_ctx* ctx, const GemmOperands& g, const double* omega, double* C, int64_t ldc) {
+  const int T = (g.M + BN - 1) / BN;            // BN < BM only for g.M <= BN: one tile
+  BK_REQUIRE((int64_t)T * (T + 1) / 2 * (BM * BN / 256) < (1ll << 31), "gram_weighted: k too large (too many tiles)");
+  const int ntile = T * (T + 1) / 2;
+  int splits = 1, k_chunk = BK;
+  gemm_split_plan<true, false, BN>(g, ntile, &splits, &k_chunk);
+  double* partial = nullptr;
+  if (splits > 1) {
+    void* p = nullptr;
+    BK_TRY(ws_get(ctx, gemm_split_slot(ctx), (int64_t)splits * ntile * BM * BN * (int64_t)sizeof(double), &p));
+    partial = (double*)p;
+  }
+  auto kern = gram_weighted_kernel<BN>;
+  constexpr size_t smem = gemm_smem_bytes<true, false, BN>();
+  BK_TRY(ensure_dyn_smem(ctx, (const void*)kern, smem));
+  hipLaunchKernelGGL(kern, dim3(ntile, splits), dim3(NT), smem, ctx->stream, g, omega, C, ldc, T, ntile, k_chunk, partial);
+  BK_CHECK_LAUNCH();
+  if (splits > 1) {
+    hipLaunchKernelGGL(gram_reduce_kernel, dim3((unsigned)(ntile * (BM * BN / 256))), dim3(256), 0, ctx->stream, (const double*)partial,
+                       splits, ntile, T, BN, g.M, C, ldc);
+    BK_CHECK_LAUNCH();
+  }
+  return BIGKRLS_OK;
+}
+
+int gram_weighted(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* A, int64_t lda, const double* omega, double* M,
+                  int64_t ldm) {
+  BK_REQUIRE(n >= 0 && k >= 0, "gram_weighted: negative dimension");
+  BK_REQUIRE(n < (1ll << 31) && k < (1ll << 31), "gram_weighted: dimension too large");
+  if (k == 0) return BIGKRLS_OK;
+  BK_REQUIRE(M && ldm >= k, "gram_weighted: null M or leading dimension of M too small");
+  if (n == 0) {   // empty sum
+    const int blocks = (int)std::min<int64_t>((k * k + 255) / 256, 2048);
+    hipLaunchKernelGGL(scale_matrix_kernel, dim3(blocks), dim3(256), 0, ctx->stream, M, ldm, (int)k, (int)k, 0.0);
+    BK_CHECK_LAUNCH();
+    return BIGKRLS_OK;
+  }
+  BK_REQUIRE(A && omega, "gram_weighted: null pointer");
+  BK_REQUIRE(lda >= n, "gram_weighted: leading dimension of A too small");
+  const GemmOperands g{A, A, lda, lda, (int)k, (int)k, (int)n, nullptr};
+  BK_TRY(prof_begin(ctx, "gram_weighted", (double)n * (double)k * ((double)k + 1.0)));
+  if (k <= 32) BK_TRY(launch_gram_weighted<32>(ctx, g, omega, M, ldm));
+  else if (k <= 64) BK_TRY(launch_gram_weighted<64>(ctx, g, omega, M, ldm));
+  else BK_TRY(launch_gram_weighted<128>(ctx, g, omega, M, ldm));
+  BK_TRY(prof_end(ctx, "gram_weighted"));
   return BIGKRLS_OK;
 }
 

@@ -132,6 +132,39 @@ def bGemmModulated(A: DeviceMatrix, r, t, s, B: DeviceMatrix) -> DeviceMatrix:
     return out
 
 
+def bGramWeighted(A: DeviceMatrix, omega) -> DeviceMatrix:
+    """A' diag(omega) A (k x k) for A n x k and n weights (a DeviceMatrix or a host array). The weight is applied on the
+    way into the multiply, no weighted copy of A is stored, and the result is symmetric bit for bit
+    (bigkrls_dev_gram_weighted). No counterpart in the reference."""
+    ctx = A.ctx
+    dw = omega if isinstance(omega, DeviceMatrix) else ctx.from_numpy(np.asarray(omega, dtype=np.float64).ravel())
+    if dw.nrow * dw.ncol != A.nrow or (dw.ncol > 1 and dw.nrow > 1):
+        raise ValueError(f"bGramWeighted: omega must be a vector with {A.nrow} entries")
+    out = ctx.empty(A.ncol, A.ncol)
+    _lib.call("bigkrls_dev_gram_weighted", ctx.handle, A.nrow, A.ncol, A.ptr, A.ld, dw.ptr, out.ptr, out.ld)
+    return out
+
+
+def bClusterScores(A: DeviceMatrix, e, labels, G: int) -> DeviceMatrix:
+    """S (k x G): S[j, g] = sum of e[i] A[i, j] over the rows i with labels[i] == g, for A n x k, e with n entries (a
+    DeviceMatrix or a host array) and n integer labels in [0, G) in any order; an empty cluster gives a zero column
+    (bigkrls_dev_cluster_scores). No counterpart in the reference."""
+    ctx = A.ctx
+    de = e if isinstance(e, DeviceMatrix) else ctx.from_numpy(np.asarray(e, dtype=np.float64).ravel())
+    if de.nrow * de.ncol != A.nrow or (de.ncol > 1 and de.nrow > 1):
+        raise ValueError(f"bClusterScores: e must be a vector with {A.nrow} entries")
+    lab = np.ascontiguousarray(labels, dtype=np.int64).ravel()
+    if lab.size != A.nrow:
+        raise ValueError(f"bClusterScores: labels must have {A.nrow} entries")
+    G = int(G)
+    if G < 1:
+        raise ValueError("bClusterScores: G must be at least 1")
+    out = ctx.empty(A.ncol, G)
+    _lib.call("bigkrls_dev_cluster_scores", ctx.handle, A.nrow, A.ncol, A.ptr, A.ld, de.ptr, lab.ctypes.data, G,
+              out.ptr, out.ld)
+    return out
+
+
 # ---------------------------------------------------------------------------
 # eigen   (R/bigKRLS_Rcpp_functions.R:173-199)
 # ---------------------------------------------------------------------------

@@ -254,6 +254,26 @@ int bigkrls_dev_gemm_modulated(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k
                                const double* r, const double* t, const double* s, const double* B, int64_t ldb,
                                double* C, int64_t ldc);
 
+/* Weighted Gram matrix: M (k x k, ldm >= k, overwritten) = A' diag(omega) A, i.e. M[i,j] = sum_l omega[l] A[l,i] A[l,j];
+ * A n x k column-major (lda >= n), omega (n) on the device. The weight is applied to one operand in registers on its way
+ * to the multiply; no weighted copy of A is written. Only the 128 x 128 tiles on or below the diagonal are computed and
+ * every entry with row >= column is stored at (i, j) and (j, i), inside diagonal tiles too: M[i,j] == M[j,i] bit for bit.
+ * The contraction is split over n (bigkrls_dev_gemm's split rule over the computed tiles) and the slabs are added in a
+ * fixed order: deterministic, two calls give bitwise identical results. Extra device memory: the slabs,
+ * 8 s t 128^2 bytes for s splits and t computed tiles. k == 0 does nothing; n == 0 gives zeros. */
+int bigkrls_dev_gram_weighted(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* A, int64_t lda,
+                              const double* omega, double* M, int64_t ldm);
+
+/* Per-cluster score sums: S (k x G, lds >= k, overwritten), S[j,g] = sum over the rows i with h_cluster[i] == g of
+ * e[i] A[i,j]; A n x k column-major (lda >= n) and e (n) on the device, h_cluster (n labels in [0, G), any order) on
+ * the host. An empty cluster gives a zero column; a label outside [0, G) or G < 1 is BIGKRLS_EINVAL. The host sorts the
+ * labels (stable counting sort, uploaded once; rows that are already grouped are read without the permutation), the
+ * device adds every cluster's rows in an order that depends on the cluster sizes only: no floating-point atomics, two
+ * calls give bitwise identical results. Extra device memory: 8 n + 8 pieces bytes of indices and 8 k doubles per piece of
+ * a cluster that spans several 64-row chunks (at most n / 64 + G pieces). */
+int bigkrls_dev_cluster_scores(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* A, int64_t lda, const double* e,
+                               const int64_t* h_cluster, int64_t G, double* S, int64_t lds);
+
 /* out[:,i] = A[:,i]*diag[i] (diag on device). */
 int bigkrls_dev_multdiag(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t k, int64_t lda,
                          const double* diag, double* out, int64_t ldo);
@@ -595,6 +615,28 @@ int bigkrls_partial_dependence(bigkrls_ctx* ctx, const double* h_X, int64_t n, i
                                const double* h_newdata, int64_t u, const double* h_grid, const int64_t* h_grid_off,
                                const double* d_vcov_c, const double* d_Q, int64_t ldq, int64_t k, const double* h_w,
                                double neffective, double* h_pd, double* h_se, double* h_cov);
+
+/* Heteroskedasticity- or cluster-robust variance of the coefficients as factors (no counterpart in the reference).
+ * d_Q (n x k, ldq >= n, device) and h_d (k, host) are the kept eigenpairs of the fit, lambda its ridge parameter,
+ * h_resid (n, host) the residuals y - yfitted in standardised units, y_sd the standard deviation of y. With
+ * g_j = 1 / (d_j + lambda) and G = Q diag(g) Q', the result is V_r = sd(y)^2 scale G diag(omega) G in the units of the
+ * fit's vcov.est.c, returned as d_Qout (n x k, ldqo >= n, device; must not overlap d_Q) and h_wout (k, host, descending,
+ * >= 0): V_r = Qout diag(wout) Qout'. omega by type, with h_i = sum_j Q_ij^2 d_j g_j the leverages:
+ *   0 classical: omega_i = 1 (h_resid unused; scale = sigmasq reproduces the fit's own factors),
+ *   1 HC0: e_i^2,   2 HC1: e_i^2 (the caller passes scale = n / Neffective),
+ *   3 HC2: e_i^2 / (1 - h_i),   4 HC3: e_i^2 / (1 - h_i)^2; a leverage >= 1 is BIGKRLS_EINVAL naming the row.
+ * With h_cluster (n labels in [0, G), host; types 1 and 2 only) the middle is the clustered one,
+ * Q' diag(omega) Q -> S S' with S = bigkrls_dev_cluster_scores(Q, e); scale carries the caller's G / (G - 1).
+ * Steps: M = Q' diag(omega) Q (bigkrls_dev_gram_weighted) or S S'; S = diag(g) M diag(g), symmetrised; its k
+ * eigenpairs (theta, U) by bigkrls_dev_eigen, theta < 0 (rounding, or rank G < k) set to 0; Qout = Q U, wout =
+ * sd(y)^2 scale theta (the scalar stays outside the eigenproblem, so Qout does not depend on it). Workspace beyond the outputs: 3 k^2 + 3 n + k G doubles; bigkrls_dev_gram_weighted's slabs
+ * (8 s t 128^2 bytes); with clusters 8 n + 8 pieces bytes of indices and k doubles per piece of a cluster that spans
+ * several 64-row chunks, at most k (n / 64 + G) doubles -- n k / 64 above O(k^2 + n + k G); and what bigkrls_dev_eigen
+ * and bigkrls_dev_gemm take for a k x k problem and an n x k product.
+ * Deterministic: two calls give bitwise identical results. */
+int bigkrls_vcov_robust(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* d_Q, int64_t ldq, const double* h_d,
+                        double lambda, const double* h_resid, double y_sd, double scale, int32_t type,
+                        const int64_t* h_cluster, int64_t G, double* d_Qout, int64_t ldqo, double* h_wout);
 
 /* =============================================================================
  * Multi-GPU: one process per GPU, the collectives inside the library (the context's
