@@ -100,6 +100,7 @@ SIGNATURES = {
     "bigkrls_dev_rowsumsq_weighted": [vp, i64, i64, vp, i64, vp, vp],
     "bigkrls_dev_gemm": [vp, C.c_int, C.c_int, i64, i64, i64, f64, vp, i64, vp, i64, f64, vp, i64],
     "bigkrls_dev_gemm_modulated": [vp, i64, i64, i64, vp, i64, vp, vp, vp, vp, i64, vp, i64],
+    "bigkrls_dev_gemm_modulated2": [vp, i64, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, f64, vp, i64, vp, i64],
     "bigkrls_dev_gram_weighted": [vp, i64, i64, vp, i64, vp, vp, i64],
     "bigkrls_dev_cluster_scores": [vp, i64, i64, vp, i64, vp, vp, i64, vp, i64],
     "bigkrls_dev_multdiag": [vp, vp, i64, i64, i64, vp, vp, i64],
@@ -134,6 +135,8 @@ SIGNATURES = {
     "bigkrls_marginal_effects_factored": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, vp, i64, i64, vp, vp, vp,
                                           vp],
     "bigkrls_marginal_effects_se": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, vp, vp, i64, i64, vp, i64, vp],
+    "bigkrls_interaction_effects": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, vp, vp, i64, i64, vp, vp, vp, vp],
+    "bigkrls_interaction_effects_se": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, vp, vp, i64, i64, vp, i64, vp],
     "bigkrls_partial_dependence": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, vp, vp, vp, vp, i64, i64, vp, f64,
                                    vp, vp, vp],
     "bigkrls_vcov_robust": [vp, i64, i64, vp, i64, vp, f64, vp, f64, f64, i32, vp, i64, vp, i64, vp],

@@ -712,6 +712,113 @@ def marginal_effects(object: BigKRLS, newdata, which_derivatives=None, ctx: Opti
     return out
 
 
+def interaction_effects(object: BigKRLS, newdata=None, pairs=None, which=None, se: bool = False,
+                        vcov: Optional[str] = None, ctx: Optional[Context] = None, _block_rows: int = 0) -> dict:
+    """Interaction effects of a fitted model at new data points, without refitting: does the effect of x_j depend on
+    x_k? For every pair (j, k) the pointwise values "interactions" (u x m), their averages "avginteractions" (1 x m) and
+    the variances of the averages "var.avginteractions" (1 x m; None when the object has no vcov.est.c), in the original
+    units. Continuous x continuous: the cross-derivative d^2 yhat / dx_j dx_k (j = k: the second derivative); binary x
+    continuous: the derivative in x_k of the first difference in x_j; binary x binary (j != k): the second difference
+    over the two pairs of training values, divided by both gaps. A pair (j, j) on a binary column is not defined. The
+    Gaussian kernel gives all of them in closed form: the second-order operator is the product of marginal_effects'
+    first-order modulations (include/bigkrls.h, bigkrls_interaction_effects). No counterpart in the reference.
+
+    newdata=None: the training X. `pairs`: 1-based (j, k), each stored ordered (j <= k) in the result; the default is
+    every j <= k over `which` (default: the object's which.derivatives, or all columns) without the binary diagonals.
+    Binary columns of a pair must hold one of their two training values in newdata. `vcov` and the multi-GPU rule are
+    marginal_effects'. se=True adds "se.interactions" (u x m): the standard error of every pointwise value from the
+    same form of vcov.est.c (a second call, `bigkrls_interaction_effects_se`; the factors are the fast form:
+    2 u n lastkeeper flops per pair in one pass of bigkrls_dev_gemm_modulated2); everything else in the result is
+    bitwise what se=False returns. Variances carry the reference's factor 2 when a column of the pair is binary, so for
+    a single new point se.interactions[0, i]**2 == var.avginteractions[0, i] for every pair."""
+    if not isinstance(object, BigKRLS):
+        raise TypeError("Object not of class 'bigKRLS'")
+    form = _vcov_choice(object, vcov)
+    if se and form is None:
+        raise ValueError("recompute bigKRLS object with bigKRLS(,vcov.est=TRUE) to compute standard errors")
+    if ("vcov.est.c.cols" in object or "rows" in object) and form != "factors":
+        raise NotImplementedError("interaction_effects of a multi-GPU fit (sharded vcov.est.c.cols) is not supported; "
+                                  "refit on one GPU or with vcov_form=\"factors\"")
+    Xh = np.asfortranarray(np.asarray(object["X"], dtype=np.float64))
+    n, p = Xh.shape
+    nd_init = Xh if newdata is None else _as_host_matrix(newdata)
+    nd = np.array(nd_init, dtype=np.float64, order="F")
+    if nd.ndim != 2 or nd.shape[1] != p:
+        raise ValueError("ncol(newdata) differs from ncol(X) from fitted bigKRLS object")
+    u = nd.shape[0]
+    if u < 1:
+        raise ValueError("newdata has no rows")
+    if not np.all(np.isfinite(nd)):
+        raise ValueError("newdata contains missing or infinite values")
+    isbin = np.array([np.unique(Xh[:, j]).size == 2 for j in range(p)])          # the fit's rule (R/bigKRLS.R:242)
+    if pairs is None:
+        if which is None:
+            which = object.get("which.derivatives")
+        if which is None:
+            cols = list(range(1, p + 1))
+        else:
+            cols = sorted(set(int(i) for i in np.atleast_1d(which)))
+            if not cols or not all(1 <= i <= p for i in cols):
+                raise ValueError("which must index columns of X")
+        pairs = [(j, k) for a, j in enumerate(cols) for k in cols[a:] if not (j == k and isbin[j - 1])]
+        if not pairs:
+            raise ValueError("no pair is left: the only selected column is binary")
+    else:
+        if which is not None:
+            raise ValueError("give pairs or which, not both")
+        try:
+            pairs = [(int(j), int(k)) for j, k in pairs]
+        except (TypeError, ValueError):
+            raise ValueError("pairs must be a list of (j, k) column indices") from None
+        if not pairs:
+            raise ValueError("pairs is empty")
+    ordered = []
+    for j, k in pairs:
+        if not (1 <= j <= p and 1 <= k <= p):
+            raise ValueError(f"pair ({j}, {k}) must index columns of X")
+        j, k = min(j, k), max(j, k)
+        if j == k and isbin[j - 1]:
+            raise ValueError(f"pair ({j}, {k}) is not defined: column {j} is binary in the training data")
+        if (j, k) in ordered:
+            raise ValueError(f"pair ({j}, {k}) is given more than once")
+        ordered.append((j, k))
+    for j in sorted(set(c - 1 for pr in ordered for c in pr)):
+        if isbin[j]:
+            lo, hi = Xh[:, j].min(), Xh[:, j].max()
+            if not np.all((nd[:, j] == lo) | (nd[:, j] == hi)):
+                raise ValueError(f"newdata column {j + 1} is binary in the training data; its values must be "
+                                 f"one of the two training values ({lo:g}, {hi:g})")
+    ctx = ctx or object.get("_ctx") or default_context()
+    V = object.get("vcov.est.c") if form == "dense" else None
+    Vd = None if V is None else (V if is_device_matrix(V) else ctx.from_numpy(np.asarray(V, dtype=np.float64)))
+    Qd, wv = _factors(object, ctx) if form == "factors" else (None, None)
+    yv = np.ascontiguousarray(np.asarray(object["y"], dtype=np.float64).ravel())
+    coeffs = np.ascontiguousarray(np.asarray(object["coeffs"], dtype=np.float64).ravel())
+    pair_arr = np.ascontiguousarray(ordered, dtype=np.int64)                      # m x 2 row-major: pair after pair
+    m = len(ordered)
+    vals = np.empty((u, m), dtype=np.float64, order="F")
+    avg = np.empty(m)
+    var = np.empty(m) if form is not None else None
+    vcov_args = (Vd.ptr if form == "dense" else None, Qd.ptr if form == "factors" else None,
+                 Qd.ld if form == "factors" else 0, Qd.ncol if form == "factors" else 0,
+                 wv.ctypes.data if form == "factors" else None)
+    _call_native("bigkrls_interaction_effects", ctx.handle, Xh.ctypes.data, n, p, yv.ctypes.data, coeffs.ctypes.data,
+                 float(object["sigma"]), pair_arr.ctypes.data, m, nd.ctypes.data, u, *vcov_args, vals.ctypes.data,
+                 avg.ctypes.data, var.ctypes.data if var is not None else None)
+    xlabs = list(object.get("xlabs") or [f"x{i + 1}" for i in range(p)])
+    out = {"interactions": vals, "avginteractions": avg[None, :],
+           "var.avginteractions": None if var is None else var[None, :],
+           "pairs": ordered, "pairlabs": [f"{xlabs[j - 1]}:{xlabs[k - 1]}" for j, k in ordered],
+           "binaryindicator": isbin[pair_arr - 1], "newdata": nd_init}
+    if se:
+        sev = np.empty((u, m), dtype=np.float64, order="F")
+        _call_native("bigkrls_interaction_effects_se", ctx.handle, Xh.ctypes.data, n, p, yv.ctypes.data,
+                     coeffs.ctypes.data, float(object["sigma"]), pair_arr.ctypes.data, m, nd.ctypes.data, u, *vcov_args,
+                     int(_block_rows), sev.ctypes.data)
+        out["se.interactions"] = sev
+    return out
+
+
 ROBUST_TYPES = {"classical": 0, "HC0": 1, "HC1": 2, "HC2": 3, "HC3": 4, "CR0": 1, "CR1": 2}
 
 

@@ -557,6 +557,14 @@ int bigkrls_dev_gemm_modulated(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k
   return gemm_modulated(ctx, m, n, k, A, lda, r, t, s, B, ldb, C, ldc);
 }
 
+int bigkrls_dev_gemm_modulated2(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda,
+                                const double* r1, const double* t1, const double* s1, const double* r2,
+                                const double* t2, const double* s2, double d, const double* B, int64_t ldb, double* C,
+                                int64_t ldc) {
+  BK_TRY(check_ctx(ctx));
+  return gemm_modulated2(ctx, m, n, k, A, lda, r1, t1, s1, r2, t2, s2, d, B, ldb, C, ldc);
+}
+
 int bigkrls_dev_multdiag(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t k, int64_t lda,
                          const double* diag, double* out, int64_t ldo) {
   BK_TRY(check_ctx(ctx));

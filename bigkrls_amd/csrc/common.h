@@ -195,9 +195,11 @@ enum Slot {
   SLOT_FIT_VERIFY = 43,    // the fit's check of a decomposition against K: Q r, Q (lambda o r), K Q r
   SLOT_CONTRACT_PART = 44, // kernel_contract: partial sums of the loop splits
   SLOT_ME_SMALL = 45,      // bigkrls_marginal_effects(_se): standardised X and newdata, operands, products, D, S, V S / r, t, s, se^2
+                           //     bigkrls_interaction_effects(_se): the same for the pairs
   SLOT_PP_SMALL = 46,      // bigkrls_predict_pointwise: standardised X, c, one block of newdata, yhat, diag
   SLOT_PP_K = 47,          // ... one row block of the test kernel, and its product with Q where the variance comes as factors (at most 1 GiB);
-                           //     bigkrls_marginal_effects_se: the same block and product, or the block and its modulated copy
+                           //     bigkrls_marginal_effects_se, bigkrls_interaction_effects_se: the same block and product, or the
+                           //     block and its modulated copy
   SLOT_QF_PART = 48,       // quadform_diag: one partial per row, column tile and k split
   SLOT_KB_SHIFT = 49,      // kernel_block / kernel_contract: the common shift of both operands (P doubles: column means of A)
   SLOT_KB_A = 50,          // ... the shifted copy of A (u x P)
@@ -283,6 +285,11 @@ int gemm(bigkrls_ctx* ctx, int ta, int tb, int64_t m, int64_t n, int64_t k, doub
 // gemm()'s tiles and deterministic split-K choice; with r = 1, t = 0 bitwise gemm(0, 0, .., 1.0, .., 0.0, ..).
 int gemm_modulated(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* r,
                    const double* t, const double* s, const double* B, int64_t ldb, double* C, int64_t ldc);
+// C (m x n, ldc, overwritten) = (A o F) B with F[i,l] = fma(fma(t1[i], s1[l], r1[i]), fma(t2[i], s2[l], r2[i]), d):
+// gemm_modulated with two modulations and a constant; r1, t1, r2, t2 (m) and s1, s2 (k) on the device. Deterministic.
+int gemm_modulated2(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* r1,
+                    const double* t1, const double* s1, const double* r2, const double* t2, const double* s2, double d,
+                    const double* B, int64_t ldb, double* C, int64_t ldc);
 // M (k x k, ldm, overwritten) = A' diag(omega) A, A n x k (lda), omega n entries on the device. The weight is applied in
 // registers on the way to LDS (no weighted copy of A); lower tiles only, mirrored: exactly symmetric. Deterministic.
 int gram_weighted(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* A, int64_t lda, const double* omega, double* M,

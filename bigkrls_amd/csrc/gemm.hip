@@ -162,16 +162,29 @@ struct GemmMod {
   const double* s;
 };
 
+// Optional second modulation beside GemmMod (gemm_tile<.., MOD = true, .., MOD2 = true>, gemm_modulated2):
+// op(A)(m, k) = A(m, k) fma(fma(t[m], s[k], r[m]), fma(t2[m], s2[k], r2[m]), d); r2 and t2 have M entries, s2 has K.
+struct GemmMod2 {
+  const double* r2;
+  const double* t2;
+  const double* s2;
+  double d;
+};
+
 // Computes the accumulators of the (m0, n0) block tile over k in [kbeg, kend).
 // TA/TB: operand is used transposed (op(A) = A' with A stored K x M, etc.).
 // MOD: the A operand is modulated (GemmMod) between its staging registers and LDS; off, `mod` is never read.
+// MOD2 (with MOD): the factor is the product of two such modulations plus a constant (GemmMod2); off, `mod2` is never read.
 // WK: a transposed A operand (k-contiguous) is weighted along the contraction, op(A)(m, k) = A(k, m) wk[k], between its
 // staging registers and LDS (gram_weighted: A' diag(wk) B); off, `wk` is never read.
-template <bool TA, bool TB, int BN, bool GATHER = false, bool DEEP = false, bool MOD = false, bool WK = false>
+template <bool TA, bool TB, int BN, bool GATHER = false, bool DEEP = false, bool MOD = false, bool WK = false,
+          bool MOD2 = false>
 __device__ __forceinline__ void gemm_tile(const GemmOperands& g, int m0, int n0, int kbeg,
                                           int kend, double* __restrict__ smem,
                                           d4 (&acc)[4][BN / 32], const GemmMod* mod = nullptr,
-                                          const double* __restrict__ wk = nullptr) {
+                                          const double* __restrict__ wk = nullptr,
+                                          const GemmMod2* mod2 = nullptr) {
+  static_assert(!MOD2 || MOD, "gemm_tile: the second modulation comes with the first");
   static_assert(!MOD || (!TA && !GATHER), "gemm_tile: the modulated A operand is not transposed and not gathered");
   static_assert(!WK || (TA && !GATHER && !MOD), "gemm_tile: the k-weighted A operand is transposed, not gathered, not modulated");
   constexpr int NJ = BN / 32;
@@ -233,9 +246,13 @@ __device__ __forceinline__ void gemm_tile(const GemmOperands& g, int m0, int n0,
   // k-tile): r and t of its row live in two registers; the tile's s values are loaded together with the tile (the same
   // address over a wave: cached broadcast loads), clamped like the tile's own addresses, and the factor is applied in
   // registers just before the LDS store (mod_apply) -- nothing sits between the global loads and the MFMAs.
-  constexpr int MQ = MOD ? BM / 16 : 1;
-  double mod_r = 0.0, mod_t = 0.0;
+  // MOD2: r2, t2 of the row in two more registers, the tile's s2 values in the upper half of the same register set
+  // (xs[MQ1 + q] beside xs[q]), loaded and clamped with them; the s2 pointer is ps plus a fixed offset.
+  constexpr int MQ1 = MOD ? BM / 16 : 1;
+  constexpr int MQ = MOD2 ? 2 * MQ1 : MQ1;
+  double mod_r = 0.0, mod_t = 0.0, mod_r2 = 0.0, mod_t2 = 0.0, mod_d = 0.0;
   const double* ps = nullptr;
+  const double* ps2 = nullptr;
   double rs[MQ];
   if (MOD) {
     const int gx = m0 + tid % BM;
@@ -243,6 +260,16 @@ __device__ __forceinline__ void gemm_tile(const GemmOperands& g, int m0, int n0,
     mod_r = mod->r[gc];
     mod_t = mod->t[gc];
     ps = mod->s + kbeg + tid / BM;
+    if constexpr (MOD2) {
+      // (tid / BM is the same over a wave: said so, the s values of both modulations are scalar loads into scalar
+      //  registers -- the vector file is full with gemm_modulated's one set)
+      const int kb = __builtin_amdgcn_readfirstlane(tid / BM);
+      mod_r2 = mod2->r2[gc];
+      mod_t2 = mod2->t2[gc];
+      mod_d = mod2->d;
+      ps = mod->s + kbeg + kb;
+      ps2 = mod2->s2 + kbeg + kb;
+    }
   }
   // Weighted transposed A (k-contiguous: this thread stages the k row kbeg + (tid & 15) of every k-tile for BM / 16
   // columns): one weight per thread and k-tile, loaded with the tile and clamped like the tile's own addresses.
@@ -255,21 +282,31 @@ __device__ __forceinline__ void gemm_tile(const GemmOperands& g, int m0, int n0,
       xs[0] = *pw;
     } else if (k0 + BK <= kend) {
 #pragma unroll
-      for (int q = 0; q < MQ; ++q) xs[q] = ps[q * KS];
-    } else {
-      const int kb = k0 + tid / BM;
+      for (int q = 0; q < MQ1; ++q) xs[q] = ps[q * KS];
+      if constexpr (MOD2) {
 #pragma unroll
-      for (int q = 0; q < MQ; ++q) {
+        for (int q = 0; q < MQ1; ++q) xs[MQ1 + q] = ps2[q * KS];
+      }
+    } else {
+      const int kb = k0 + (MOD2 ? __builtin_amdgcn_readfirstlane(tid / BM) : tid / BM);
+#pragma unroll
+      for (int q = 0; q < MQ1; ++q) {
         const int gk = kb + q * KS;
         xs[q] = mod->s[gk < kend ? gk : kend - 1];
+        if constexpr (MOD2) xs[MQ1 + q] = mod2->s2[gk < kend ? gk : kend - 1];
       }
     }
     ps += BK;
+    if constexpr (MOD2) ps2 += BK;
   };
   auto mod_apply = [&](double (&xa)[BM / 16], const double (&xs)[MQ]) {
     if constexpr (WK) {
 #pragma unroll
       for (int q = 0; q < BM / 16; ++q) xa[q] *= xs[0];
+    } else if constexpr (MOD2) {
+#pragma unroll
+      for (int q = 0; q < MQ1; ++q)
+        xa[q] *= fma(fma(mod_t, xs[q], mod_r), fma(mod_t2, xs[MQ1 + q], mod_r2), mod_d);
     } else {
 #pragma unroll
       for (int q = 0; q < MQ; ++q) xa[q] *= fma(mod_t, xs[q], mod_r);
@@ -683,8 +720,10 @@ __global__ __launch_bounds__(NT, (gemm_occ<false, false, BN>())) void gemm_modul
   }
 }
 
-template <int BN>
-static int launch_gemm_modulated(bigkrls_ctx* ctx, const GemmOperands& g, const GemmMod& mod, double* C, int64_t ldc) {
+// launches gemm_modulated_kernel<BN> (mods: GemmMod) or gemm_modulated2_kernel<BN> (mods: GemmMod, GemmMod2)
+template <int BN, class Kern, class... Mods>
+static int launch_gemm_modulated(bigkrls_ctx* ctx, const GemmOperands& g, Kern kern, double* C, int64_t ldc,
+                                 const Mods&... mods) {
   const int tiles_m = (g.M + BM - 1) / BM;
   const int tiles_n = (g.N + BN - 1) / BN;
   const int ntile = tiles_m * tiles_n;
@@ -692,11 +731,10 @@ static int launch_gemm_modulated(bigkrls_ctx* ctx, const GemmOperands& g, const 
   gemm_split_plan<false, false, BN>(g, ntile, &splits, &k_chunk);
   double* partial = nullptr;
   BK_TRY(gemm_split_partials(ctx, g, splits, &partial));
-  auto kern = gemm_modulated_kernel<BN>;
   constexpr size_t smem = gemm_smem_bytes<false, false, BN>();
   BK_TRY(ensure_dyn_smem(ctx, (const void*)kern, smem));
-  hipLaunchKernelGGL(kern, dim3(ntile, splits), dim3(NT), smem, ctx->stream, g, mod, C, ldc, tiles_m, tiles_n, k_chunk,
-                     partial);
+  hipLaunchKernelGGL(kern, dim3(ntile, splits), dim3(NT), smem, ctx->stream, g, mods..., C, ldc, tiles_m, tiles_n,
+                     k_chunk, partial);
   BK_CHECK_LAUNCH();
   if (splits > 1) {
     const int64_t total = (int64_t)g.M * g.N;
@@ -725,10 +763,72 @@ int gemm_modulated(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const doub
   const GemmOperands g{A, B, lda, ldb, (int)m, (int)n, (int)k, nullptr};
   const GemmMod mod{r, t, s};
   BK_TRY(prof_begin(ctx, "gemm_modulated", 2.0 * (double)m * (double)n * (double)k));
-  if (n <= 32) BK_TRY(launch_gemm_modulated<32>(ctx, g, mod, C, ldc));
-  else if (n <= 64) BK_TRY(launch_gemm_modulated<64>(ctx, g, mod, C, ldc));
-  else BK_TRY(launch_gemm_modulated<128>(ctx, g, mod, C, ldc));
+  if (n <= 32) BK_TRY(launch_gemm_modulated<32>(ctx, g, gemm_modulated_kernel<32>, C, ldc, mod));
+  else if (n <= 64) BK_TRY(launch_gemm_modulated<64>(ctx, g, gemm_modulated_kernel<64>, C, ldc, mod));
+  else BK_TRY(launch_gemm_modulated<128>(ctx, g, gemm_modulated_kernel<128>, C, ldc, mod));
   BK_TRY(prof_end(ctx, "gemm_modulated"));
+  return BIGKRLS_OK;
+}
+
+// ---------------------------------------------------------------------------
+// C (M x N) = (A o F) B, F[i,l] = fma(fma(t1[i], s1[l], r1[i]), fma(t2[i], s2[l], r2[i]), d): gemm_modulated with the
+// product of two modulations plus a constant as the factor (gemm_tile<.., MOD, .., MOD2>), so the doubly modulated
+// copy of A -- G_jk = Kn o m_j o m_k - (2/sigma) delta_jk Kn of the pointwise standard errors of the interaction
+// effects, csrc/inteff.hip -- is never written. Tiles, occupancy, k pipeline and split-K choice are gemm_modulated's;
+// per thread two more row scalars and, per k-tile in flight, BM / 16 more s values live across the k loop.
+// With r2 = 1, t2 = 0, d = 0 the second factor is exactly 1 and the result is bitwise gemm_modulated's.
+// ---------------------------------------------------------------------------
+template <int BN>
+__global__ __launch_bounds__(NT, (gemm_occ<false, false, BN>())) void gemm_modulated2_kernel(
+    GemmOperands g, GemmMod mod, GemmMod2 mod2, double* __restrict__ C, int64_t ldc, int tiles_m, int tiles_n,
+    int k_chunk, double* __restrict__ partial) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int ntile = tiles_m * tiles_n;
+  const int tid = xcd_remap(blockIdx.x, ntile);
+  const int tm = tid % tiles_m, tn = tid / tiles_m;
+  const int m0 = tm * BM, n0 = tn * BN;
+  const int z = blockIdx.y;
+  const int kbeg = z * k_chunk;
+  const int kend = min(g.K, kbeg + k_chunk);
+  d4 acc[4][BN / 32];
+  gemm_tile<false, false, BN, false, (BN <= GEMM_DEEP_BN && gemm_occ<false, false, BN>() <= GEMM_OCC), true, false,
+            true>(g, m0, n0, kbeg, kend, smem, acc, &mod, nullptr, &mod2);
+  const int M = g.M, N = g.N;
+  if (partial != nullptr) {
+    double* P = partial + (int64_t)z * M * N;
+    acc_foreach<BN>(acc, m0, n0, [&](int m, int n, double v) {
+      if (m < M && n < N) P[(int64_t)m + (int64_t)n * M] = v;
+    });
+  } else {
+    acc_foreach<BN>(acc, m0, n0, [&](int m, int n, double v) {
+      if (m < M && n < N) C[(int64_t)m + (int64_t)n * ldc] = v;
+    });
+  }
+}
+
+int gemm_modulated2(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* r1,
+                    const double* t1, const double* s1, const double* r2, const double* t2, const double* s2, double d,
+                    const double* B, int64_t ldb, double* C, int64_t ldc) {
+  BK_REQUIRE(m >= 0 && n >= 0 && k >= 0, "gemm_modulated2: negative dimension");
+  BK_REQUIRE(m < (1ll << 31) && n < (1ll << 31) && k < (1ll << 31), "gemm_modulated2: dimension too large");
+  if (m == 0 || n == 0) return BIGKRLS_OK;
+  BK_REQUIRE(C && ldc >= m, "gemm_modulated2: null C or ldc < m");
+  if (k == 0) {   // empty sum
+    const int blocks = (int)std::min<int64_t>((m * n + 255) / 256, 2048);
+    hipLaunchKernelGGL(scale_matrix_kernel, dim3(blocks), dim3(256), 0, ctx->stream, C, ldc, (int)m, (int)n, 0.0);
+    BK_CHECK_LAUNCH();
+    return BIGKRLS_OK;
+  }
+  BK_REQUIRE(A && B && r1 && t1 && s1 && r2 && t2 && s2, "gemm_modulated2: null pointer");
+  BK_REQUIRE(lda >= m && ldb >= k, "gemm_modulated2: leading dimension of A or B too small");
+  const GemmOperands g{A, B, lda, ldb, (int)m, (int)n, (int)k, nullptr};
+  const GemmMod mod{r1, t1, s1};
+  const GemmMod2 mod2{r2, t2, s2, d};
+  BK_TRY(prof_begin(ctx, "gemm_modulated2", 2.0 * (double)m * (double)n * (double)k));
+  if (n <= 32) BK_TRY(launch_gemm_modulated<32>(ctx, g, gemm_modulated2_kernel<32>, C, ldc, mod, mod2));
+  else if (n <= 64) BK_TRY(launch_gemm_modulated<64>(ctx, g, gemm_modulated2_kernel<64>, C, ldc, mod, mod2));
+  else BK_TRY(launch_gemm_modulated<128>(ctx, g, gemm_modulated2_kernel<128>, C, ldc, mod, mod2));
+  BK_TRY(prof_end(ctx, "gemm_modulated2"));
   return BIGKRLS_OK;
 }
 

@@ -132,6 +132,25 @@ def bGemmModulated(A: DeviceMatrix, r, t, s, B: DeviceMatrix) -> DeviceMatrix:
     return out
 
 
+def bGemmModulated2(A: DeviceMatrix, r1, t1, s1, r2, t2, s2, B: DeviceMatrix, d: float = 0.0) -> DeviceMatrix:
+    """(A o F) B (m x n) with F[i,l] = (r1[i] + t1[i] s1[l]) (r2[i] + t2[i] s2[l]) + d for A m x k, B k x n, r1, t1, r2,
+    t2 with m entries and s1, s2 with k (DeviceMatrix or host arrays; s1 and s2 may be the same one): the product with a
+    doubly modulated left operand in one pass, the modulated copy never stored (bigkrls_dev_gemm_modulated2); with
+    r2 = 1, t2 = 0, d = 0 it is bGemmModulated(A, r1, t1, s1, B) bitwise. No counterpart in the reference."""
+    ctx = A.ctx
+    if B.nrow != A.ncol:
+        raise ValueError("bGemmModulated2: B must have ncol(A) rows")
+    dev = [v if isinstance(v, DeviceMatrix) else ctx.from_numpy(np.asarray(v, dtype=np.float64).ravel())
+           for v in (r1, t1, s1, r2, t2, s2)]
+    for v, want, name in zip(dev, (A.nrow, A.nrow, A.ncol) * 2, ("r1", "t1", "s1", "r2", "t2", "s2")):
+        if v.nrow * v.ncol != want or (v.ncol > 1 and v.nrow > 1):
+            raise ValueError(f"bGemmModulated2: {name} must be a vector with {want} entries")
+    out = ctx.empty(A.nrow, B.ncol)
+    _lib.call("bigkrls_dev_gemm_modulated2", ctx.handle, A.nrow, B.ncol, A.ncol, A.ptr, A.ld, dev[0].ptr, dev[1].ptr,
+              dev[2].ptr, dev[3].ptr, dev[4].ptr, dev[5].ptr, float(d), B.ptr, B.ld, out.ptr, out.ld)
+    return out
+
+
 def bGramWeighted(A: DeviceMatrix, omega) -> DeviceMatrix:
     """A' diag(omega) A (k x k) for A n x k and n weights (a DeviceMatrix or a host array). The weight is applied on the
     way into the multiply, no weighted copy of A is stored, and the result is symmetric bit for bit

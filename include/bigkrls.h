@@ -254,6 +254,22 @@ int bigkrls_dev_gemm_modulated(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k
                                const double* r, const double* t, const double* s, const double* B, int64_t ldb,
                                double* C, int64_t ldc);
 
+/* Product with a doubly modulated left operand: C (m x n, ldc >= m, overwritten) = (A o F) B with
+ *   F[i,l] = fma(fma(t1[i], s1[l], r1[i]), fma(t2[i], s2[l], r2[i]), d),
+ * i.e. C[i,j] = sum_l A[i,l] ((r1[i] + t1[i] s1[l]) (r2[i] + t2[i] s2[l]) + d) B[l,j]; A m x k (lda >= m) and B k x n
+ * (ldb >= k) column-major and not transposed, r1, t1, r2, t2 (m) and s1, s2 (k) on the device (s1 and s2 may be the
+ * same vector), d a host scalar. The factor is applied to A in registers on its way to the multiply; the modulated copy
+ * of A is never written (no extra device memory beside bigkrls_dev_gemm's split-K partials). What the two
+ * bigkrls_dev_gemm_modulated calls it replaces -- against B and against diag(s1) B -- spend twice over, it spends once:
+ * 2 m n k flops. Tiles and split-K choice are bigkrls_dev_gemm's; deterministic, two calls give bitwise identical
+ * results; with r2 = 1, t2 = 0, d = 0 the result is bitwise that of bigkrls_dev_gemm_modulated(.., r1, t1, s1, ..), and
+ * with r1 = 1, t1 = 0 as well that of bigkrls_dev_gemm(0, 0, m, n, k, 1.0, A, lda, B, ldb, 0.0, C, ldc).
+ * k == 0 gives zeros; m == 0 or n == 0 does nothing. */
+int bigkrls_dev_gemm_modulated2(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda,
+                                const double* r1, const double* t1, const double* s1, const double* r2,
+                                const double* t2, const double* s2, double d, const double* B, int64_t ldb, double* C,
+                                int64_t ldc);
+
 /* Weighted Gram matrix: M (k x k, ldm >= k, overwritten) = A' diag(omega) A, i.e. M[i,j] = sum_l omega[l] A[l,i] A[l,j];
  * A n x k column-major (lda >= n), omega (n) on the device. The weight is applied to one operand in registers on its way
  * to the multiply; no weighted copy of A is written. Only the 128 x 128 tiles on or below the diagonal are computed and
@@ -590,6 +606,48 @@ int bigkrls_marginal_effects_se(bigkrls_ctx* ctx, const double* h_X, int64_t n, 
                                 const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
                                 const double* h_newdata, int64_t u, const double* d_vcov_c, const double* d_Q,
                                 int64_t ldq, int64_t k, const double* h_w, int64_t block_rows, double* h_se);
+
+/* Interaction effects of a fitted model at new data points: does the effect of x_j depend on x_k? (No counterpart in
+ * the reference.) X, y, coeffs, sigma, newdata and u as in bigkrls_marginal_effects. h_pairs holds m pairs of 1-based
+ * column indices, column-major (pair i is h_pairs[2 i], h_pairs[2 i + 1]); a pair is taken ordered (j <= k), and output
+ * column i belongs to pair i. In standardised units, with the first-order modulation m_j(i,l) = r_j[i] + t_j[i] s_j[l] of
+ * bigkrls_marginal_effects_se (continuous j: s = Xs[:,j], r = -(2/sigma) Zs[:,j], t = 2/sigma; binary j: s the training
+ * group indicator, r and t the two first-difference weights), the Gaussian kernel factorises over the columns and
+ *   G_jk = Kn o m_j o m_k - (2/sigma) delta_jk Kn,      I[i,(j,k)] = G_jk[i,:] c:
+ * continuous x continuous the cross-derivative d^2 yhat / dx_j dx_k (j = k: the second derivative), binary x continuous
+ * the derivative in x_k of the first difference in x_j, binary x binary (j != k) the second difference
+ * (yhat_11 - yhat_10 - yhat_01 + yhat_00) / ((z1 - z0)_j (z1 - z0)_k). Original units: times sd(y) / (sd(x_j) sd(x_k)).
+ * Outputs: h_interactions (u x m column-major; may be NULL), h_avg (m) the column means, and h_var (m) the variance of
+ * each mean, a'V a with a = (1/u) 1'G_jk, times f_jk = 2 when a column of the pair is binary (the reference's factor,
+ * src/bigderiv_v3.cpp:85, applied once) and 1 otherwise. vcov.est.c comes as the n x n matrix (d_vcov_c, ld n) or as
+ * its factors (d_Q n x k on the device, ldq >= n; h_w the k weights on the host), at most one of them; with neither,
+ * h_var must be NULL. Validation and its messages are bigkrls_marginal_effects' (finite newdata, binary columns of a
+ * pair hold one of the two training values, constant training column); in addition a pair index outside [1, p], a pair
+ * (j, j) on a binary column and a pair given twice (after ordering) are BIGKRLS_EINVAL, each naming the pair.
+ * The u x n test kernel is never formed: two bigkrls_dev_kernel_contract calls of width q = 1 + |J'| + m (J' the columns
+ * that occur in a pair) and a per-row finalise each. Extra device memory: O((u + n)(p + q)) and the contractions'
+ * partials. */
+int bigkrls_interaction_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                                const double* h_coeffs, double sigma, const int64_t* h_pairs, int64_t m,
+                                const double* h_newdata, int64_t u, const double* d_vcov_c, const double* d_Q,
+                                int64_t ldq, int64_t k, const double* h_w, double* h_interactions, double* h_avg,
+                                double* h_var);
+
+/* Pointwise standard errors of the interaction effects: h_se (u x m column-major, the columns of h_interactions) with
+ *   Var(I[i,(j,k)]) = G_jk[i,:] V G_jk[i,:]',      se = sqrt(f_jk Var) sd(y) / (sd(x_j) sd(x_k)),
+ * G_jk, f_jk, pairs, validation and messages as bigkrls_interaction_effects; exactly one of d_vcov_c and d_Q is given
+ * (else BIGKRLS_EINVAL). With u = 1, se[0,i]^2 equals bigkrls_interaction_effects' h_var[i] for every pair. The new
+ * points are taken in row blocks by bigkrls_marginal_effects_se's rules (from the factors 8 b (n + k) <= 2^30 bytes,
+ * from the matrix 16 b n <= 2^30, b a multiple of 128 and at least 128; block_rows = 0, or a positive multiple of 128
+ * that overrides b). Per block the test kernel once; per pair, from the factors T = G_jk Q
+ * (bigkrls_dev_gemm_modulated2: G_jk is never stored) and bigkrls_dev_rowsumsq_weighted, 2 u n k flops per pair; from
+ * the matrix (the compatibility path) G_jk is written beside the block, with the same fma expression, and
+ * bigkrls_dev_quadform_diag gives the diagonal. Every row's result is bitwise independent of b while the products take
+ * one k split (n < 1024); two calls with the same b are bitwise identical. */
+int bigkrls_interaction_effects_se(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                                   const double* h_coeffs, double sigma, const int64_t* h_pairs, int64_t m,
+                                   const double* h_newdata, int64_t u, const double* d_vcov_c, const double* d_Q,
+                                   int64_t ldq, int64_t k, const double* h_w, int64_t block_rows, double* h_se);
 
 /* Partial dependence of the fitted outcome on one predictor at a time, with its covariance over the grid (no
  * counterpart in the reference). For every selected column j (h_which, 1-based, n_which entries; NULL: all p) and every
