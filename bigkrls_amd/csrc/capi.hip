@@ -626,6 +626,12 @@ int bigkrls_dev_cholqr2(bigkrls_ctx* ctx, double* W, double* tmp, int64_t n, int
   return rc;
 }
 
+int bigkrls_dev_panel_factor(bigkrls_ctx* ctx, double* P, int64_t ld, int64_t m, double* Vw, double* V, double* T,
+                             double* Tfold, double* tau, int32_t* h_fallback) {
+  BK_TRY(check_ctx(ctx));
+  return panel_factor(ctx, P, ld, m, Vw, V, T, Tfold, tau, h_fallback);
+}
+
 int bigkrls_dev_copy_matrix(bigkrls_ctx* ctx, const double* src, int64_t m, int64_t n, int64_t lds,
                             double* dst, int64_t ldd) {
   BK_TRY(check_ctx(ctx));

@@ -473,6 +473,8 @@ int eigen_auto(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t lda, int64_
                double* vecs, int64_t ldv, int64_t* h_n_vals, int64_t* h_n_vecs);
 // Row-block distributed stage 1 (dense -> band), one call per panel step between the caller's
 // collectives; see include/bigkrls.h (bigkrls_dev_s1_*).
+int panel_factor(bigkrls_ctx* ctx, double* P, int64_t ld, int64_t m, double* Vw, double* V, double* T, double* Tfold,
+                 double* tau, int32_t* h_fallback);
 int dist_s1_open(bigkrls_ctx* ctx, int64_t n);
 int dist_s1_panel(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* strip);
 int dist_s1_av(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* Acols, int64_t lda, int64_t ncols,

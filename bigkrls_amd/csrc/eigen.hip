@@ -3079,7 +3079,7 @@ struct DenseEig : EigArgs {
     const int64_t npart = 2 * maxb + 2 * maxb * S2_B + S2_B + S2_B * S2_B + 2 * N + nmail;
     const int64_t ntall = (N / S2_B + 2) * S2_B * S2_B;
     const int64_t nfpart = (N / (S1F_CHUNKS * S2_B) + 3) * S2_B * S2_B;   // partial V'Y blocks of the fused small products
-    const int64_t bt_doubles = 7 * nb64 + 8 * S2_B * S2_B + npart + ntall + nfpart + npqc + 2 * N /*taus1, scales1*/ +
+    const int64_t bt_doubles = 8 * nb64 + S2_B * S2_B /* Vw, Tfold: the split panel factorisation */ + 8 * S2_B * S2_B + npart + ntall + nfpart + npqc + 2 * N /*taus1, scales1*/ +
                                (int64_t)S2_LD * N /*AB*/ + N + 8 /*soff as int64*/;
     const Stage2Plan plan = two_stage ? stage2_plan(n) : Stage2Plan();
     // reflector blocks of the two panel groups whose trailing update is pending (stage1_to_band)
@@ -3117,6 +3117,8 @@ struct DenseEig : EigArgs {
     if (two_stage) {
       double* q = (double*)p2;
       s1.Vp = q; q += nb64;
+      s1.Vw = q; q += nb64;
+      s1.Tfold = q; q += S2_B * S2_B;
       s1.Y = q; q += nb64;
       s1.Y2 = q; q += nb64;
       s1.PZ1 = q; q += 2 * nb64;
@@ -3625,7 +3627,7 @@ int dist_s1_av(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* Acols, int6
     BK_HIP(hipMemsetAsync(Ypart, 0, (size_t)(ldy * S2_B) * sizeof(double), ctx->stream));
     return BIGKRLS_OK;
   }
-  return gemm(ctx, 0, 0, m, S2_B, ncols, 1.0, Acols, lda, ds->ops.ws.Vp + row0, m, 0.0, Ypart, ldy);
+  return gemm(ctx, 0, 0, m, S2_B, ncols, 1.0, Acols, lda, ds->ops.Vw((int)k) + row0, m, 0.0, Ypart, ldy);
 }
 
 // the thin products of panel k from the gathered Y = A22 V: PZ1 = [V | Z], PZ2 = [Z | V]
@@ -3711,7 +3713,7 @@ int dist_s1_thin_group(bigkrls_ctx* ctx, int64_t n, int64_t k, double* Y, int64_
   const int64_t ldg = ds->ops.ws.aggLd;
   if (j > 0) {        // Y -= U (U'^T V) over the j pending blocks: their update has not reached the column blocks yet
     double* C = ds->ops.ws.aggC;
-    BK_TRY(gemm(ctx, 1, 0, 2 * b * j, b, m, 1.0, PZ2 + off, ldg, ds->ops.ws.Vp, m, 0.0, C, 2 * b * j));
+    BK_TRY(gemm(ctx, 1, 0, 2 * b * j, b, m, 1.0, PZ2 + off, ldg, ds->ops.Vw((int)k), m, 0.0, C, 2 * b * j));
     BK_TRY(gemm(ctx, 0, 0, m, b, 2 * b * j, -1.0, PZ1 + off, ldg, C, 2 * b * j, 1.0, Y, m));
   }
   const int64_t roff = off + (int64_t)j * 2 * b * ldg;
@@ -3768,6 +3770,60 @@ int dist_s1_put(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* strip, int
   BK_REQUIRE(strip && k >= 0 && ncols > 0 && k + ncols <= n, "s1_put: bad arguments");
   BK_TRY(dist_s1_wait_panel(ctx, ds));
   return copy_matrix(ctx, strip, n - k, ncols, n - k, ds->ops.W + k + k * n, n);
+}
+
+// One stage-1 panel factorisation on its own (exposed for tests): S1Ops::panel_qr and build_T, i.e. head -> Householder
+// kernel's slot -> tail (the one-kernel form under BIGKRLS_PQ=fused), on the context's otherwise idle stream with a
+// workspace of its own. The panel is block column 0 of an imagined (m + 64)-row matrix whose sub-diagonal block is P.
+int panel_factor(bigkrls_ctx* ctx, double* P, int64_t ld, int64_t m, double* Vw, double* V, double* T, double* Tfold,
+                 double* tau, int32_t* h_fallback) {
+  const int b = S2_B;
+  BK_REQUIRE(P && Vw && V && T && Tfold && tau && h_fallback && m >= 2 * b && m <= (int64_t)PQC_MAXWG * 256 && ld >= m,
+             "panel_factor: bad arguments (128 <= m <= 20 480 rows, ld >= m)");
+  const int n = (int)m + b;
+  const int64_t maxb = (n + 255) / 256 + 2;
+  const int64_t nmail1 = 2 * maxb * 2 * S2_B, nmail = nmail1 + 2 * 16 * 2 * S2_B;
+  const int64_t npart = 2 * maxb + 2 * maxb * S2_B + S2_B + S2_B * S2_B + 2 * n + nmail;
+  void* pw = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_EIG_MISC, (8 * b * b + npart + PQC_MAIL_DOUBLES + 2 * n + 16) * (int64_t)sizeof(double), &pw));
+  hipStream_t st = ctx->stream;
+  Stage1Ws ws{};
+  double* q = (double*)pw;
+  ws.Vp = V; ws.Vw = Vw; ws.Tfold = Tfold; ws.Tall = T;
+  ws.small = q; q += 8 * b * b;
+  ws.part = q; q += npart;
+  ws.mail = ws.part + (npart - nmail);
+  ws.mail2 = ws.mail + nmail1;
+  ws.pqc = q; q += PQC_MAIL_DOUBLES;
+  double* taus = q; q += 2 * n;
+  ws.err = (int*)q;
+  ws.fallback = ws.err + 4;
+  BK_HIP(hipMemsetAsync(ws.mail, 0, nmail * sizeof(double), st));
+  BK_HIP(hipMemsetAsync(ws.pqc, 0, PQC_MAIL_DOUBLES * sizeof(double), st));
+  BK_HIP(hipMemsetAsync(taus, 0, (2 * n + 16) * sizeof(double), st));
+  S1Ops ops;
+  BK_TRY(ops.init(ctx, P - b, n, taus, ws));
+  ops.N = ld;
+  BK_REQUIRE(ops.chol_panel(0), "panel_factor: the register-resident factorisation is not available (BIGKRLS_PQ, co-residency)");
+  BK_TRY(ops.panel_qr(0, st));
+  BK_TRY(ops.build_T(0, st));
+  if (!ops.split_panel(0)) {     // the one-kernel form: W-space is V-space
+    BK_HIP(hipMemcpyAsync(Vw, V, (size_t)m * b * sizeof(double), hipMemcpyDeviceToDevice, st));
+    BK_HIP(hipMemcpyAsync(Tfold, T, (size_t)b * b * sizeof(double), hipMemcpyDeviceToDevice, st));
+  }
+  BK_HIP(hipMemcpyAsync(tau, taus, b * sizeof(double), hipMemcpyDeviceToDevice, st));
+  int flags[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  {
+    PinnedFetch pf(ctx, 8);
+    BK_TRY(pf.add(flags, ws.err, sizeof flags));
+    BK_TRY(pf.finish());
+  }
+  if (flags[0] != 0) {
+    set_error("panel_factor: the watchdog of the panel factorisation fired");
+    return BIGKRLS_EHIP;
+  }
+  *h_fallback = flags[4];
+  return BIGKRLS_OK;
 }
 
 }  // namespace bk

@@ -564,6 +564,10 @@ __global__ __launch_bounds__(256, 1) void pq_resident(double* __restrict__ P, in
 // diagonal ratio below PQC_RATIO or a second-pass Gram matrix far from I make every workgroup leave the panel
 // untouched and raise *fallback: the launch of pq_resident that follows does the panel then (and returns at once
 // otherwise).
+// The big product A22 V that follows a factorisation on the critical path of stage 1 does not need the reconstruction:
+// W = Q - [S; 0] = [L U; Q2] = V U gives A22 V T = (A22 W)(U^-1 T). So the kernel is split (pq_chol<true>, the HEAD: the
+// two CholeskyQR passes, W left for the product; pq_tail, the TAIL: V, R, tau, T and U^-1 T beside that product);
+// pq_chol<false> is the one-kernel form (BIGKRLS_PQ=fused).
 // ---------------------------------------------------------------------------
 // trailing-matrix height down to which stage 1 aggregates two panels per update (stage1_to_band): where the update,
 // not the panel factorisation beside it, is the longer launch -- 14 848 with the 64-exchange Householder kernel,
@@ -764,12 +768,77 @@ __device__ __forceinline__ bool pqc_wait_flags(const unsigned long long* flag, i
 constexpr int64_t PQC_OFF_SLICES = (int64_t)PQC_MAXWG * PQC_NG;
 constexpr int64_t PQC_OFF_QTOP = PQC_OFF_SLICES + PQC_NG + 256;
 constexpr int64_t PQC_OFF_FLAGS = PQC_OFF_QTOP + PQC_NG;
-constexpr int64_t PQC_MAIL_DOUBLES = PQC_OFF_FLAGS + 2 * PQC_MAXWG + 16;
+// ... and what the head of the split factorisation leaves for its tail (pq_tail): L \ U of Q1 - S in the top-block area,
+// the product R2 R1, then S and the reciprocals of U's diagonal
+constexpr int64_t PQC_OFF_RPROD = PQC_OFF_FLAGS + 2 * PQC_MAXWG + 16;
+constexpr int64_t PQC_OFF_SINV = PQC_OFF_RPROD + PQC_NG;
+constexpr int64_t PQC_MAIL_DOUBLES = PQC_OFF_SINV + 2 * S2_B;
+
+// The T factor of the block reflector from the reconstruction itself: with Q1 - S = L U and V1 = L one has
+// (I - V T V')[I; 0] = Q S  <=>  Q1 S - I = -L T L'  <=>  T = -U S L^-T (same paper). Row i of X = T solves X L' = -U S on
+// its own: x_c = -U_ic S_c - sum_{k < c} x_k L_ck, so the 64 rows go to 64 groups of four lanes (16 rows per wave), lane q
+// of a group keeping the x_k with k = q (mod 4) and the group's partial sums folded by two quad exchanges per column
+// (~2 us for one workgroup). FOLD: also the right-hand side -S instead of -U S, which gives U^-1 T = -S L^-T: the factor
+// that takes Y2 = A22 W, W = V U = Q - [S; 0], to Y = A22 V T (the split factorisation, pq_tail) -- the same recurrence,
+// its loads of L shared, its chains independent of the first one's. LU: L \ U in LDS (row stride PQC_LD). Both are
+// written column-major with the zeros below the diagonal, the layout bt_build_t writes.
+template <bool WITH_T, bool FOLD>
+__device__ __forceinline__ void pqc_t_factor(const double* __restrict__ LU, const double* __restrict__ sS,
+                                             double* __restrict__ Tout, double* __restrict__ Tfold) {
+  constexpr int B = S2_B, LD = PQC_LD;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int ti = 16 * wave + (lane >> 2), q = lane & 3;
+  const double* Lq = LU + q;                 // L[c][4 j + q] = Lq[c * LD + 4 j]
+  const double* Ui = LU + ti * LD;           // U[ti][c], c >= ti
+  double x[B / 4], xf[B / 4];
+#pragma unroll
+  for (int j = 0; j < B / 4; ++j) { x[j] = 0.0; xf[j] = 0.0; }
+#pragma unroll
+  for (int c = 0; c < B; ++c) {
+    double a4[4] = {0.0, 0.0, 0.0, 0.0};     // (four chains: sixteen dependent multiply-adds per column cost ~6 us in all)
+    double f4[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int j = 0; j < B / 4; ++j) {
+      if (4 * j < c) {                                             // (static)
+        const double l = Lq[c * LD + 4 * j];
+        const double lm = (4 * j + q < c) ? l : 0.0;               // entries k >= c of row c hold U, not L
+        if (WITH_T) a4[j & 3] = fma(x[j], lm, a4[j & 3]);
+        if (FOLD) f4[j & 3] = fma(xf[j], lm, f4[j & 3]);
+      }
+    }
+    if (WITH_T) {
+      double acc = (a4[0] + a4[1]) + (a4[2] + a4[3]);
+      acc += dpp_move<0xB1>(acc);              // lane ^ 1
+      acc += dpp_move<0x4E>(acc);              // lane ^ 2
+      const double bic = (c >= ti) ? -Ui[c] * sS[c] : 0.0;
+      const double xc = bic - acc;
+      if (q == (c & 3)) {
+        x[c >> 2] = xc;
+        Tout[ti + B * c] = xc;
+      }
+    }
+    if (FOLD) {
+      double acc = (f4[0] + f4[1]) + (f4[2] + f4[3]);
+      acc += dpp_move<0xB1>(acc);
+      acc += dpp_move<0x4E>(acc);
+      const double xc = ((c == ti) ? -sS[c] : 0.0) - acc;
+      if (q == (c & 3)) {
+        xf[c >> 2] = xc;
+        Tfold[ti + B * c] = xc;
+      }
+    }
+  }
+}
 
 // (launch bounds of TWO workgroups per CU and the LDS arrays as dynamic shared memory, whose size the compiler does
 //  not know: 256 registers per lane, vector and accumulation registers together -- with
 //  more (the compiler parks values in accumulation registers when it may use 512) a workgroup no longer fits beside a
 //  wave of the trailing update and starts only when a CU has emptied completely: the kernel then lasts as long as the update)
+// SPLIT: the HEAD of the split factorisation -- the two CholeskyQR passes only. Each thread leaves its row of Q in Vp (here:
+// the buffer the big product A22 (.) reads), workgroup 0 factorises its own top block Q1 - S = L U behind its row stores
+// (no broadcast, nobody waits for it), subtracts S from the diagonal of the top block -- Vp then holds W = Q - [S; 0] =
+// V U -- and publishes L \ U, S and 1 / diag(U); the last workgroup publishes R2 R1. pq_tail does the rest beside A22 W.
+template <bool SPLIT>
 __global__ __launch_bounds__(256, 2) void pq_chol(double* __restrict__ P, int64_t ld, int m,
                                                   double* __restrict__ taus, double* __restrict__ scales,
                                                   double* __restrict__ Vp, double* __restrict__ mail,
@@ -803,6 +872,12 @@ __global__ __launch_bounds__(256, 2) void pq_chol(double* __restrict__ P, int64_
     const unsigned pstride = (unsigned)ld * 8u;
 #pragma unroll
     for (int c = 0; c < B; ++c) { const double v = *(const double*)((const char*)P + offp); p[c] = valid ? v : 0.0; offp += pstride; }
+    // (the head: the selected values made opaque -- otherwise the compiler keeps the loaded ones as well, for the stores
+    //  of park() under `valid`, and the two copies of the row do not fit into 256 registers)
+    if constexpr (SPLIT) {
+#pragma unroll
+      for (int c = 0; c < B; ++c) asm volatile("" : "+v"(p[c]));
+    }
   }
   if (tid == 0) { s_bad = 0; s_fail = 0; }
   const int bi = tid >> 4, bj = tid & 15;          // this thread's 4 x 4 block of a 64 x 64 matrix
@@ -857,11 +932,107 @@ __global__ __launch_bounds__(256, 2) void pq_chol(double* __restrict__ P, int64_
     for (int c = 0; c < B; ++c) { const double v = *(const double*)((const char*)Vp + off); p[c] = valid ? v : 0.0; off += cstride; }
   };
 
+  // ---- Q1 - S = L U, right-looking, by the whole workgroup (4 x 4 blocks in registers as in the Cholesky passes; the
+  //      current column and row go through LDS); S in sS, the reciprocal pivots in sInv (visible after a barrier) ------
+  auto lu_q1 = [&](double (&blkv)[4][4]) {
+    // two columns and rows (j, j + 1) per step and barrier
+    for (int jb = 0; jb < B / 4; ++jb) {
+#pragma unroll
+      for (int jp = 0; jp < 2; ++jp) {
+        const int jj = 2 * jp, j = 4 * jb + jj;
+        double* cb0 = sLU[(jb * 2 + jp) & 1][0];
+        double* cb1 = sLU[(jb * 2 + jp) & 1][1];
+        double* rb0 = sLU[(jb * 2 + jp) & 1][2];
+        double* rb1 = sLU[(jb * 2 + jp) & 1][3];
+        if (bj == jb) {
+#pragma unroll
+          for (int a = 0; a < 4; ++a) { cb0[4 * bi + a] = blkv[a][jj]; cb1[4 * bi + a] = blkv[a][jj + 1]; }
+        }
+        if (bi == jb) {
+#pragma unroll
+          for (int b2 = 0; b2 < 4; ++b2) { rb0[4 * bj + b2] = blkv[jj][b2]; rb1[4 * bj + b2] = blkv[jj + 1][b2]; }
+        }
+        __syncthreads();
+        const double a00 = cb0[j];
+        const double s0 = (a00 >= 0.0) ? -1.0 : 1.0;
+        const double p0 = a00 - s0, p0inv = pqc_rcp(p0);         // |p0| = 1 + |a00|
+        const double l10 = cb0[j + 1] * p0inv, u01 = rb0[j + 1];
+        const double a11 = cb1[j + 1] - l10 * u01;
+        const double s1 = (a11 >= 0.0) ? -1.0 : 1.0;
+        const double p1 = a11 - s1, p1inv = pqc_rcp(p1);
+        double li0[4], li1[4], uc0[4], uc1[4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+          const int i = 4 * bi + a, c = 4 * bj + a;
+          const double r0 = cb0[i], r1 = cb1[i], q0 = rb0[c], q1 = rb1[c];
+          const double t0 = r0 * p0inv;
+          const double t1 = (r1 - t0 * u01) * p1inv, u1 = q1 - l10 * q0;
+          li0[a] = (i > j) ? t0 : 0.0;
+          li1[a] = (i > j + 1) ? t1 : 0.0;
+          uc0[a] = (c > j) ? q0 : 0.0;
+          uc1[a] = (c > j + 1) ? u1 : 0.0;
+        }
+        const bool ocol = (bj == jb);
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+          const int i = 4 * bi + a;
+#pragma unroll
+          for (int b2 = 0; b2 < 4; ++b2) {
+            double v = blkv[a][b2] - (li0[a] * uc0[b2] + li1[a] * uc1[b2]);
+            if (b2 == jj) v = (ocol && i > j) ? li0[a] : ((ocol && i == j) ? p0 : v);
+            if (b2 == jj + 1) v = (ocol && i > j + 1) ? li1[a] : ((ocol && i == j + 1) ? p1 : v);
+            blkv[a][b2] = v;
+          }
+        }
+        if (tid == 0) { sS[j] = s0; sS[j + 1] = s1; sInv[j] = p0inv; sInv[j + 1] = p1inv; }
+      }
+    }
+    __syncthreads();
+  };
+  // ---- R2 R1 on and above the diagonal: thread (bi, bj), bi <= bj, forms its 4 x 4 block from the upper triangles of
+  //      sM[1] (R2) and sM[0] (R1) --------------------------------------------------------------------------------------
+  auto r_product = [&](double (&rr)[4][4]) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b2 = 0; b2 < 4; ++b2) rr[a][b2] = 0.0;
+    for (int kb = bi; kb <= bj; ++kb) {       // 4 x 4 blocks of R2 (rows of this thread) and R1 (its columns)
+      double x2[4][4], x1[4][4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          x2[a][u] = sM[1][(4 * bi + a) * LD + 4 * kb + u];      // R2[i][k]
+          x1[u][a] = sM[0][(4 * kb + u) * LD + 4 * bj + a];      // R1[k][c]
+        }
+      if (kb == bi) {                         // below the diagonal of R2 the array holds L2
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            if (u < a) x2[a][u] = 0.0;
+      }
+      if (kb == bj) {                         // ... and below that of R1, L1
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int a = 0; a < 4; ++a)
+            if (u > a) x1[u][a] = 0.0;
+      }
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b2 = 0; b2 < 4; ++b2)
+#pragma unroll
+          for (int u = 0; u < 4; ++u) rr[a][b2] += x2[a][u] * x1[u][b2];
+    }
+  };
+
   // stage 0, 1: the two CholeskyQR passes (p <- p R^-1); stage 2: the Householder reconstruction (p <- (p - S e_r) U^-1).
   // Each ends in the same substitution over the rows in registers with an upper triangular 64 x 64 factor in LDS
   // (sInv[c]: reciprocal of its diagonal).
 #pragma unroll
-  for (int stage = 0; stage < 3; ++stage) {
+  for (int stage = 0; stage < (SPLIT ? 2 : 3); ++stage) {
     double* M = sM[stage & 1];
     if (stage < 2) {
       // ---- partial Gram matrix of this workgroup's rows on the f64 MFMA units: 64 rows staged in LDS at a time; wave w
@@ -1097,67 +1268,14 @@ __global__ __launch_bounds__(256, 2) void pq_chol(double* __restrict__ P, int64_
       load_block_to_lds(qtop, sA);
       __syncthreads();
       PQC_PHASE(10)
-      // ---- Q1 - S = L U, right-looking, by the whole workgroup (4 x 4 blocks in registers as above; the current
-      //      column and row go through LDS); L and U back in place ------------------------------------------------
+      // ---- Q1 - S = L U; L and U back in place ----------------------------------------------------------------------
       {
         double blkv[4][4];
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
           for (int b2 = 0; b2 < 4; ++b2) blkv[a][b2] = sA[(4 * bi + a) * LD + 4 * bj + b2];
-        // two columns and rows (j, j + 1) per step and barrier
-        for (int jb = 0; jb < B / 4; ++jb) {
-#pragma unroll
-          for (int jp = 0; jp < 2; ++jp) {
-            const int jj = 2 * jp, j = 4 * jb + jj;
-            double* cb0 = sLU[(jb * 2 + jp) & 1][0];
-            double* cb1 = sLU[(jb * 2 + jp) & 1][1];
-            double* rb0 = sLU[(jb * 2 + jp) & 1][2];
-            double* rb1 = sLU[(jb * 2 + jp) & 1][3];
-            if (bj == jb) {
-#pragma unroll
-              for (int a = 0; a < 4; ++a) { cb0[4 * bi + a] = blkv[a][jj]; cb1[4 * bi + a] = blkv[a][jj + 1]; }
-            }
-            if (bi == jb) {
-#pragma unroll
-              for (int b2 = 0; b2 < 4; ++b2) { rb0[4 * bj + b2] = blkv[jj][b2]; rb1[4 * bj + b2] = blkv[jj + 1][b2]; }
-            }
-            __syncthreads();
-            const double a00 = cb0[j];
-            const double s0 = (a00 >= 0.0) ? -1.0 : 1.0;
-            const double p0 = a00 - s0, p0inv = pqc_rcp(p0);         // |p0| = 1 + |a00|
-            const double l10 = cb0[j + 1] * p0inv, u01 = rb0[j + 1];
-            const double a11 = cb1[j + 1] - l10 * u01;
-            const double s1 = (a11 >= 0.0) ? -1.0 : 1.0;
-            const double p1 = a11 - s1, p1inv = pqc_rcp(p1);
-            double li0[4], li1[4], uc0[4], uc1[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-              const int i = 4 * bi + a, c = 4 * bj + a;
-              const double r0 = cb0[i], r1 = cb1[i], q0 = rb0[c], q1 = rb1[c];
-              const double t0 = r0 * p0inv;
-              const double t1 = (r1 - t0 * u01) * p1inv, u1 = q1 - l10 * q0;
-              li0[a] = (i > j) ? t0 : 0.0;
-              li1[a] = (i > j + 1) ? t1 : 0.0;
-              uc0[a] = (c > j) ? q0 : 0.0;
-              uc1[a] = (c > j + 1) ? u1 : 0.0;
-            }
-            const bool ocol = (bj == jb);
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-              const int i = 4 * bi + a;
-#pragma unroll
-              for (int b2 = 0; b2 < 4; ++b2) {
-                double v = blkv[a][b2] - (li0[a] * uc0[b2] + li1[a] * uc1[b2]);
-                if (b2 == jj) v = (ocol && i > j) ? li0[a] : ((ocol && i == j) ? p0 : v);
-                if (b2 == jj + 1) v = (ocol && i > j + 1) ? li1[a] : ((ocol && i == j + 1) ? p1 : v);
-                blkv[a][b2] = v;
-              }
-            }
-            if (tid == 0) { sS[j] = s0; sS[j + 1] = s1; sInv[j] = p0inv; sInv[j + 1] = p1inv; }
-          }
-        }
-        __syncthreads();
+        lu_q1(blkv);
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -1165,44 +1283,10 @@ __global__ __launch_bounds__(256, 2) void pq_chol(double* __restrict__ P, int64_
       }
       __syncthreads();
       PQC_PHASE(11)
-      // R = S (R2 R1) on and above the diagonal of the top block (workgroup 0 holds those rows): thread (bi, bj),
-      // bi <= bj, forms its 4 x 4 block from the upper triangles of sM[1] (R2) and sM[0] (R1)
+      // R = S (R2 R1) on and above the diagonal of the top block (workgroup 0 holds those rows)
       if (blk == 0 && bi <= bj) {
         double rr[4][4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-          for (int b2 = 0; b2 < 4; ++b2) rr[a][b2] = 0.0;
-        for (int kb = bi; kb <= bj; ++kb) {       // 4 x 4 blocks of R2 (rows of this thread) and R1 (its columns)
-          double x2[4][4], x1[4][4];
-#pragma unroll
-          for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              x2[a][u] = sM[1][(4 * bi + a) * LD + 4 * kb + u];      // R2[i][k]
-              x1[u][a] = sM[0][(4 * kb + u) * LD + 4 * bj + a];      // R1[k][c]
-            }
-          if (kb == bi) {                         // below the diagonal of R2 the array holds L2
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-              for (int u = 0; u < 4; ++u)
-                if (u < a) x2[a][u] = 0.0;
-          }
-          if (kb == bj) {                         // ... and below that of R1, L1
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-              for (int a = 0; a < 4; ++a)
-                if (u > a) x1[u][a] = 0.0;
-          }
-#pragma unroll
-          for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b2 = 0; b2 < 4; ++b2)
-#pragma unroll
-              for (int u = 0; u < 4; ++u) rr[a][b2] += x2[a][u] * x1[u][b2];
-        }
+        r_product(rr);
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -1221,6 +1305,46 @@ __global__ __launch_bounds__(256, 2) void pq_chol(double* __restrict__ P, int64_
     pqc_solve(p, stage < 2 ? M : sA, sInv);
     __syncthreads();
     PQC_PHASE(5 + 4 * stage)
+  }
+  if constexpr (SPLIT) {
+    // ---- the head's results: Q, then (workgroup 0, behind its row stores) the top block's factors and the patch Q1 - S --
+    // (the row leaves the registers first: beside it the products and the factorisation below would spill)
+    park();
+    if (blk == 0 && wave == 0) {
+#pragma unroll
+      for (int c = 0; c < B; ++c) sA[lane * LD + c] = p[c];
+    }
+    if (blk == np - 1 && bi <= bj) {
+      double rr[4][4];
+      r_product(rr);
+      double* rprod = mail + PQC_OFF_RPROD;
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b2 = 0; b2 < 4; ++b2) {
+          const int i = 4 * bi + a, c = 4 * bj + b2;
+          if (i <= c) rprod[i * B + c] = rr[a][b2];
+        }
+    }
+    PQC_PHASE(10)
+    if (blk != 0) return;
+    __syncthreads();
+    const double qd = sA[lane * (LD + 1)];     // Q1_ii for thread i < 64
+    double blkv[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int b2 = 0; b2 < 4; ++b2) blkv[a][b2] = sA[(4 * bi + a) * LD + 4 * bj + b2];
+    lu_q1(blkv);
+    store_block(qtop, blkv);
+    if (tid < B) {
+      double* sinv = mail + PQC_OFF_SINV;
+      sinv[tid] = sS[tid];
+      sinv[B + tid] = sInv[tid];
+      Vp[tid + (int64_t)tid * m] = qd - sS[tid];      // (m >= 64: this thread's own row, behind its own store of Q1_ii)
+    }
+    if (tid == 0) *fallback = 0;
+    return;
   }
   // ---- results --------------------------------------------------------------------------------------------------------
   if (blk == 0 && tid == 0) *fallback = 0;
@@ -1241,48 +1365,104 @@ __global__ __launch_bounds__(256, 2) void pq_chol(double* __restrict__ P, int64_
       offp += pstride;
     }
   }
-  // ---- the T factor of the block reflector, H_1 ... H_64 = I - V T V', from the reconstruction itself (round 6):
-  //      with Q1 - S = L U and V1 = L one has (I - V T V')[I; 0] = Q S  <=>  Q1 S - I = -L T L'  <=>  T = -U S L^-T
-  //      (same paper). Row i of X = T solves X L' = -U S on its own: x_c = -U_ic S_c - sum_{k < c} x_k L_ck, so the 64
-  //      rows go to 64 groups of four lanes (16 rows per wave), lane q of a group keeping the x_k with k = q (mod 4) and
-  //      the group's partial sums folded by two quad exchanges per column -- ~2 us in workgroup 0 behind its stores,
-  //      instead of the chain V'V (split-K GEMM) -> slab reduction -> dlarft recurrence behind the kernel (69 us at
-  //      m = 2 500, on the critical path of every panel below m ~ 6 000). T is written column-major with its zeros below
-  //      the diagonal, the layout bt_build_t writes; a panel left to the Householder kernel (s_bad above: this point is
-  //      not reached) gets its T from that chain, which S1Ops::build_T launches behind a device-side predicate.
-  if (Tout != nullptr && blk == 0) {
-    const int ti = 16 * wave + (lane >> 2), q = lane & 3;
-    const double* Lq = sA + q;                 // L[c][4 j + q] = Lq[c * LD + 4 j]
-    const double* Ui = sA + ti * LD;           // U[ti][c], c >= ti
-    double x[B / 4];
+  // ---- the T factor of the block reflector, H_1 ... H_64 = I - V T V', from the reconstruction itself (pqc_t_factor):
+  //      ~2 us in workgroup 0 behind its stores, instead of the chain V'V (split-K GEMM) -> slab reduction -> dlarft
+  //      recurrence behind the kernel (69 us at m = 2 500, on the critical path of every panel below m ~ 6 000). A panel
+  //      left to the Householder kernel (s_bad above: this point is not reached) gets its T from that chain, which
+  //      S1Ops::build_T launches behind a device-side predicate.
+  if (Tout != nullptr && blk == 0) pqc_t_factor<true, false>(sA, sS, Tout, nullptr);
+}
+
+// ---------------------------------------------------------------------------
+// The TAIL of the split factorisation: the Householder reconstruction from what pq_chol<true> left -- W = Q - [S; 0] in
+// Vw, L \ U, S, 1 / diag(U) and R2 R1 in the mailbox. A plain kernel with no waits between workgroups, launched behind
+// the head (and the Householder kernel's slot) while A22 W runs. Workgroup k < gridDim.x - 1: thread t solves its row of
+// V = W U^-1 (the top block comes out as L) and stores it to V and, below the diagonal, into the panel. The LAST
+// workgroup, beside them: R = S (R2 R1), tau, T = -U S L^-T (write_T) and Tfold = U^-1 T = -S L^-T, which takes A22 W to
+// Y = A22 V T (s1_fused_yt). A panel the head left to the Householder kernel (*fallback != 0) has its V in Vw already:
+// copied to V, and T -- built by the chain S1Ops::build_T launches in front of this kernel -- to Tfold.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pq_tail(double* __restrict__ P, int64_t ld, int m, double* __restrict__ taus,
+                                               double* __restrict__ scales, const double* __restrict__ Vw,
+                                               double* __restrict__ V, const double* __restrict__ mail,
+                                               const int* __restrict__ fallback, double* __restrict__ T, int write_T,
+                                               double* __restrict__ Tfold) {
+  constexpr int B = S2_B, LD = PQC_LD;
+  __shared__ double sU[B * LD];
+  __shared__ double sInv[B], sS[B];
+  const int tid = threadIdx.x, blk = blockIdx.x;
+  const bool rows = blk < (int)gridDim.x - 1;
+  const int r = blk * 256 + tid;
+  const bool valid = rows && r < m;
+  const unsigned cstride = (unsigned)m * 8u;
+  if (*fallback != 0) {     // uniform, and the same in every workgroup
+    if (valid) {
+      unsigned off = (unsigned)r * 8u;
+#pragma unroll 8
+      for (int c = 0; c < B; ++c) { *(double*)((char*)V + off) = *(const double*)((const char*)Vw + off); off += cstride; }
+    }
+    if (!rows && write_T)
+      for (int e = tid; e < PQC_NG; e += 256) Tfold[e] = T[e];
+    return;
+  }
+  const double* lu = mail + PQC_OFF_QTOP;
 #pragma unroll
-    for (int j = 0; j < B / 4; ++j) x[j] = 0.0;
+  for (int u = 0; u < PQC_NG / 256; ++u) {
+    const int e = tid + 256 * u;
+    sU[(e >> 6) * LD + (e & 63)] = lu[e];
+  }
+  if (tid < B) { sS[tid] = mail[PQC_OFF_SINV + tid]; sInv[tid] = mail[PQC_OFF_SINV + B + tid]; }
+  if (rows) {
+    double p[B];
+    {
+      unsigned off = valid ? (unsigned)r * 8u : 0u;
 #pragma unroll
-    for (int c = 0; c < B; ++c) {
-      double a4[4] = {0.0, 0.0, 0.0, 0.0};     // (four chains: sixteen dependent multiply-adds per column cost ~6 us in all)
+      for (int c = 0; c < B; ++c) { const double v = *(const double*)((const char*)Vw + off); p[c] = valid ? v : 0.0; off += cstride; }
+    }
+    __syncthreads();
+    pqc_solve(p, sU, sInv);
+    if (valid) {
+      unsigned off = (unsigned)r * 8u, offp = (unsigned)r * 8u;
+      asm volatile("" : "+v"(off), "+v"(offp));
+      const unsigned pstride = (unsigned)ld * 8u;
 #pragma unroll
-      for (int j = 0; j < B / 4; ++j) {
-        if (4 * j < c) {                                             // (static)
-          const double l = Lq[c * LD + 4 * j];
-          a4[j & 3] = fma(x[j], (4 * j + q < c) ? l : 0.0, a4[j & 3]);   // entries k >= c of row c hold U, not L
-        }
-      }
-      double acc = (a4[0] + a4[1]) + (a4[2] + a4[3]);
-      acc += dpp_move<0xB1>(acc);              // lane ^ 1
-      acc += dpp_move<0x4E>(acc);              // lane ^ 2
-      const double bic = (c >= ti) ? -Ui[c] * sS[c] : 0.0;
-      const double xc = bic - acc;
-      if (q == (c & 3)) {
-        x[c >> 2] = xc;
-        Tout[ti + B * c] = xc;
+      for (int c = 0; c < B; ++c) {
+        const double v = (r < c) ? 0.0 : ((r == c) ? 1.0 : p[c]);
+        *(double*)((char*)V + off) = v;
+        if (r > c) *(double*)((char*)P + offp) = p[c];
+        off += cstride;
+        offp += pstride;
       }
     }
+    return;
   }
+  __syncthreads();
+  if (tid < B) {
+    taus[tid] = -sU[tid * LD + tid] * sS[tid];
+    scales[tid] = 1.0;
+  }
+  {
+    const double* rprod = mail + PQC_OFF_RPROD;
+#pragma unroll
+    for (int u = 0; u < PQC_NG / 256; ++u) {
+      const int e = tid + 256 * u, i = e >> 6, c = e & 63;     // (consecutive threads: consecutive entries of a row of R2 R1)
+      if (i <= c && i < m) P[i + (int64_t)c * ld] = sS[i] * rprod[e];
+    }
+  }
+  if (write_T) pqc_t_factor<true, true>(sU, sS, T, Tfold);
+  else pqc_t_factor<false, true>(sU, sS, nullptr, Tfold);
+}
+
+// Tfold = T for a panel the split factorisation left to the Householder kernel (V is then the operand of A22 (.) itself)
+__global__ void pq_tfold_copy(const double* __restrict__ T, double* __restrict__ Tfold, const int* __restrict__ run_if) {
+  if (*run_if == 0) return;
+  for (int e = threadIdx.x; e < S2_B * S2_B; e += blockDim.x) Tfold[e] = T[e];
 }
 
 #ifdef BK_PQC_PROF
-// development build only (tools/pqc_bench.sh): pq_chol on a random m x 64 panel, `reps` launches; returns the mean
-// launch time in microseconds (`stop_after` is ignored: the phase is a compile-time choice, PQC_STOP)
+// development build only (tools/pqc_bench.sh): the panel factorisation on a random m x 64 panel, `reps` launches; returns
+// the mean launch time in microseconds. `which` = 0: the head of the split factorisation (pq_chol<true>; its phase is a
+// compile-time choice, PQC_STOP), 1: the tail (pq_tail) behind one launch of the head, 2: the one-kernel form
 __global__ void pqc_fill(double* p, int64_t n, unsigned seed) {
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
     unsigned x = (unsigned)e * 2654435761u + seed; x ^= x >> 15; x *= 2246822519u; x ^= x >> 13;
@@ -1291,14 +1471,16 @@ __global__ void pqc_fill(double* p, int64_t n, unsigned seed) {
 }
 }  // anonymous namespace
 }  // namespace bk
-extern "C" __attribute__((visibility("default"))) int bk_pqc_bench(bigkrls_ctx* ctx, int m, int reps, int stop_after,
+extern "C" __attribute__((visibility("default"))) int bk_pqc_bench(bigkrls_ctx* ctx, int m, int reps, int which,
                                                                    double* us, double* dbg_out) {
   using namespace bk;
   hipStream_t st = ctx->stream;
-  hipFuncSetAttribute((const void*)pq_chol, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PQC_SMEM);
-  double *P, *P0, *Vp, *mail, *tau;
+  hipFuncSetAttribute((const void*)pq_chol<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PQC_SMEM);
+  hipFuncSetAttribute((const void*)pq_chol<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PQC_SMEM);
+  double *P, *P0, *Vp, *Vw, *mail, *tau, *Tt;
   int* flags;
   hipMalloc(&P, (size_t)m * 64 * 8); hipMalloc(&P0, (size_t)m * 64 * 8); hipMalloc(&Vp, (size_t)m * 64 * 8);
+  hipMalloc(&Vw, (size_t)m * 64 * 8); hipMalloc(&Tt, 2 * 4096 * 8);
   hipMalloc(&mail, PQC_MAIL_DOUBLES * 8); hipMalloc(&tau, 256 * 8); hipMalloc(&flags, 64);
   hipMemsetAsync(mail, 0, PQC_MAIL_DOUBLES * 8, st); hipMemsetAsync(flags, 0, 64, st);
   pqc_fill<<<512, 256, 0, st>>>(P0, (int64_t)m * 64, 7u);
@@ -1323,9 +1505,19 @@ extern "C" __attribute__((visibility("default"))) int bk_pqc_bench(bigkrls_ctx* 
     hipStreamSynchronize(st);
     if (load) hipStreamSynchronize(ctx->stream);
     if (load) syrk_mirror(ctx, m, 128, -1.0, L1, m, L1 + (size_t)m * 128, m, L0, m, 0, -1, true);
+    if (which == 1)
+      hipLaunchKernelGGL(pq_chol<true>, dim3((m + 255) / 256), dim3(256), PQC_SMEM, st, P, (int64_t)m, m, tau, tau + 64, Vw,
+                         mail, (r + 2) * 8 + 1, flags, flags + 4, (double*)nullptr);
     hipEventRecord(e0, st);
-    hipLaunchKernelGGL(pq_chol, dim3((m + 255) / 256), dim3(256), PQC_SMEM, st, P, (int64_t)m, m, tau, tau + 64, Vp, mail,
-                       (r + 2) * 8 + 1, flags, flags + 4, (double*)nullptr);
+    if (which == 0)
+      hipLaunchKernelGGL(pq_chol<true>, dim3((m + 255) / 256), dim3(256), PQC_SMEM, st, P, (int64_t)m, m, tau, tau + 64, Vw,
+                         mail, (r + 2) * 8 + 1, flags, flags + 4, (double*)nullptr);
+    else if (which == 1)
+      hipLaunchKernelGGL(pq_tail, dim3((m + 255) / 256 + 1), dim3(256), 0, st, P, (int64_t)m, m, tau, tau + 64, (const double*)Vw,
+                         Vp, (const double*)mail, (const int*)(flags + 4), Tt, 1, Tt + 4096);
+    else
+      hipLaunchKernelGGL(pq_chol<false>, dim3((m + 255) / 256), dim3(256), PQC_SMEM, st, P, (int64_t)m, m, tau, tau + 64, Vp,
+                         mail, (r + 2) * 8 + 1, flags, flags + 4, (double*)nullptr);
     hipEventRecord(e1, st);
     hipEventSynchronize(e1);
     float ms; hipEventElapsedTime(&ms, e0, e1);
@@ -1339,7 +1531,7 @@ extern "C" __attribute__((visibility("default"))) int bk_pqc_bench(bigkrls_ctx* 
   }
   int h[8]; hipMemcpy(h, flags, 32, hipMemcpyDeviceToHost);
   if (load) { hipStreamSynchronize(ctx->stream); hipStreamSynchronize(s2); hipFree(L0); hipFree(L1); hipStreamDestroy(s2); }
-  hipFree(P); hipFree(P0); hipFree(Vp); hipFree(mail); hipFree(tau); hipFree(flags);
+  hipFree(P); hipFree(P0); hipFree(Vp); hipFree(Vw); hipFree(Tt); hipFree(mail); hipFree(tau); hipFree(flags);
   return h[0] * 100 + h[4];     // watchdog word, fallback word
 }
 namespace bk {
@@ -1754,6 +1946,8 @@ __global__ void s1_gate(const unsigned long long* __restrict__ cnt, unsigned lon
 }
 struct Stage1Ws {
   double* Vp;     // m x b
+  double* Vw = nullptr;     // m x b: W = V U = Q - [S; 0] of the split panel factorisation, the operand of A22 (.)
+  double* Tfold = nullptr;  // b x b: U^-1 T of the current panel (Y = (A22 W) Tfold)
   double* Y;      // m x b
   double* Y2;     // m x b
   double* PZ1;    // m x 2b
@@ -1786,6 +1980,11 @@ struct S1Ops {
   int64_t N = 0;
   int maxb = 0, pq_cap = 1;
   bool pq_chol_on = true;
+  // The split factorisation (default; BIGKRLS_PQ=fused: the one-kernel form): panel_qr launches the head (pq_chol<true>),
+  // which leaves W = V U in ws.Vw -- all that A22 (.) needs -- and build_T the tail (pq_tail: V, R, tau, T, Tfold), which
+  // then runs beside that product. Per panel: Vw(k) is the operand of A22 (.) and of the correction factors U'^T (.) that
+  // act on its result, Tyt(k) the factor that takes the product to Y; everything else reads V and T.
+  bool pq_split = true;
   bool pq_steps = false, fused_small = true, fused_panel = true;
   size_t yt_smem = 0, z_smem = 0;
   double *normA = nullptr, *normB = nullptr, *dotA = nullptr, *dotB = nullptr, *betas = nullptr, *Rrow = nullptr;
@@ -1828,11 +2027,13 @@ struct S1Ops {
     // (workgroups exchange partial sums through global mailboxes) when all its workgroups can be
     // co-resident, else one launch per column. BIGKRLS_PQ=steps forces the latter.
     BK_TRY(resident_capacity(ctx, (const void*)pq_resident, &pq_cap));
-    BK_TRY(ensure_dyn_smem(ctx, (const void*)pq_chol, PQC_SMEM));
+    BK_TRY(ensure_dyn_smem(ctx, (const void*)pq_chol<false>, PQC_SMEM));
     const char* pq_env = getenv("BIGKRLS_PQ");
     pq_steps = ctx->no_resident || (pq_env && std::string(pq_env) == "steps");
     // BIGKRLS_PQ=householder: the 64-exchange Householder kernel for every panel (cross-check of pq_chol)
     pq_chol_on = !(pq_env && std::string(pq_env) == "householder");
+    pq_split = pq_chol_on && !pq_steps && ws.Vw != nullptr && ws.Tfold != nullptr && !(pq_env && std::string(pq_env) == "fused");
+    BK_TRY(ensure_dyn_smem(ctx, (const void*)pq_chol<true>, PQC_SMEM));
     // BIGKRLS_S1=gemm: the panel's small products as separate GEMMs (cross-check of the fused kernels)
     const char* s1_env = getenv("BIGKRLS_S1");
     fused_small = !(s1_env && std::string(s1_env) == "gemm");
@@ -1854,6 +2055,14 @@ struct S1Ops {
   bool resident_qr(int k) const { return !pq_steps && (n - k - S2_B + 255) / 256 <= std::min(pq_cap, 80); }
   bool has_panel(int k) const { return k + S2_B < n && n - k - S2_B > 1; }
   double* Tof(int k) const { return ws.Tall + (int64_t)(k / S2_B) * S2_B * S2_B; }
+  // the panels pq_chol takes: register-resident, at most PQC_MAXWG workgroups, at least 2 b rows
+  bool chol_panel(int k) const {
+    const int m = n - k - S2_B;
+    return resident_qr(k) && pq_chol_on && ws.pqc != nullptr && (m + 255) / 256 <= PQC_MAXWG && m >= 2 * S2_B;
+  }
+  bool split_panel(int k) const { return pq_split && chol_panel(k); }
+  double* Vw(int k) const { return split_panel(k) ? ws.Vw : ws.Vp; }
+  const double* Tyt(int k) const { return split_panel(k) ? ws.Tfold : Tof(k); }
 
   int panel_qr(int k, hipStream_t ps) {
     const int b = S2_B;
@@ -1879,12 +2088,16 @@ struct S1Ops {
       const bool samp = ctx->profile && (k / b) % S1_PROF_STRIDE == 0;
       if (samp) BK_TRY(prof_begin(ctx, "panel_qr", 24.0 * (double)m * pw, ps));
       const int npq = (m + 255) / 256;
-      const bool chol = pq_chol_on && ws.pqc != nullptr && npq <= PQC_MAXWG && m >= 2 * b;
+      const bool chol = chol_panel(k), split = split_panel(k);
       static const int pqc_dbg = [] { const char* e = getenv("BIGKRLS_PQC_DEBUG"); return e ? atoi(e) : 0; }();
       if (chol && (pqc_dbg & 1)) BK_HIP(hipDeviceSynchronize());     // debug: nothing runs beside the kernel
       if (chol) {
-        hipLaunchKernelGGL(pq_chol, dim3(npq), dim3(256), PQC_SMEM, ps, P, N, m, taus1 + k, taus1 + n + k, ws.Vp, ws.pqc,
-                           (k / b) * 8 + 1, ws.err, ws.fallback, t_in_pq ? Tof(k) : (double*)nullptr PQC_PROF_VAL(0));
+        if (split)
+          hipLaunchKernelGGL(pq_chol<true>, dim3(npq), dim3(256), PQC_SMEM, ps, P, N, m, taus1 + k, taus1 + n + k, ws.Vw,
+                             ws.pqc, (k / b) * 8 + 1, ws.err, ws.fallback, (double*)nullptr PQC_PROF_VAL(0));
+        else
+          hipLaunchKernelGGL(pq_chol<false>, dim3(npq), dim3(256), PQC_SMEM, ps, P, N, m, taus1 + k, taus1 + n + k, ws.Vp,
+                             ws.pqc, (k / b) * 8 + 1, ws.err, ws.fallback, t_in_pq ? Tof(k) : (double*)nullptr PQC_PROF_VAL(0));
         pq_started += (unsigned long long)npq;
         t_from_pq_k = t_in_pq ? k : -1;
       }
@@ -1918,8 +2131,9 @@ struct S1Ops {
         BK_HIP(hipMemcpy(dbg, ws.pqc + PQC_OFF_SLICES + PQC_NG, sizeof(dbg), hipMemcpyDeviceToHost));
         if (fb) fprintf(stderr, "[bigkrls] pq_chol left panel k=%d (m=%d) to the Householder kernel: pass 0 bad=%g dmin=%.3e dmax=%.3e; pass 1 bad=%g dmin=%.3e dmax=%.3e\n", k, m, dbg[0], dbg[1], dbg[2], dbg[8], dbg[9], dbg[10]);
       }
+      // (a split panel left to this kernel: its V goes where A22 (.) reads, pq_tail copies it to ws.Vp)
       hipLaunchKernelGGL(pq_resident, dim3(npq), dim3(256), 0, ps, P, N, m, taus1 + k,
-                         taus1 + n + k, ws.Vp, ws.mail, ws.mail2, (k / b) * S2_B + 1, ws.err,
+                         taus1 + n + k, split ? ws.Vw : ws.Vp, ws.mail, ws.mail2, (k / b) * S2_B + 1, ws.err,
                          chol ? (const int*)ws.fallback : (const int*)nullptr);
       if (samp) BK_TRY(prof_end(ctx, "panel_qr", ps));
       BK_CHECK_LAUNCH();
@@ -1962,17 +2176,32 @@ struct S1Ops {
     const int b = S2_B;
     const int m = n - k - b;
     double* T = Tof(k);
+    const bool split = split_panel(k);
     // pq_chol has written T itself unless it left the panel to the Householder kernel: the chain then runs behind the
     // device-side predicate *ws.fallback != 0 (three launches that return at once otherwise)
     const int* pred = (t_from_pq_k == k && ws.fallback != nullptr) ? (const int*)ws.fallback : (const int*)nullptr;
+    // The tail of the split factorisation (V, R, tau, T and Tfold; for a panel that fell back the copies of V and T) goes
+    // BEHIND the predicated chain, whose operand is then ws.Vw -- V itself whenever the chain does anything -- so that
+    // nothing but the tail stands between the head and what waits for this stream; with BIGKRLS_S1_TPQ=0 the chain
+    // always runs, on the tail's V, and Tfold = T is a launch of its own for a panel that fell back.
+    auto tail = [&](bool write_T) {
+      hipLaunchKernelGGL(pq_tail, dim3((m + 255) / 256 + 1), dim3(256), 0, ps, W + (k + b) + (int64_t)k * N, N, m, taus1 + k,
+                         taus1 + n + k, (const double*)ws.Vw, ws.Vp, (const double*)ws.pqc, (const int*)ws.fallback, T,
+                         write_T ? 1 : 0, ws.Tfold);
+    };
+    if (split && pred == nullptr) tail(false);
+    const double* Vchain = (split && pred != nullptr) ? ws.Vw : ws.Vp;
     hipStream_t saved = ctx->stream;
     ctx->stream = ps;
     ctx->gemm_run_if = pred;
-    const int rc = gemm(ctx, 1, 0, b, b, m, 1.0, ws.Vp, m, ws.Vp, m, 0.0, G, b);
+    const int rc = gemm(ctx, 1, 0, b, b, m, 1.0, Vchain, m, Vchain, m, 0.0, G, b);
     ctx->gemm_run_if = nullptr;
     ctx->stream = saved;
     BK_TRY(rc);
     hipLaunchKernelGGL(bt_build_t, dim3(1), dim3(256), 0, ps, (const double*)G, b, (const double*)(taus1 + k), T, pred);
+    if (split && pred != nullptr) tail(true);
+    else if (split)
+      hipLaunchKernelGGL(pq_tfold_copy, dim3(1), dim3(256), 0, ps, (const double*)T, ws.Tfold, (const int*)ws.fallback);
     BK_CHECK_LAUNCH();
     return BIGKRLS_OK;
   }
@@ -1992,7 +2221,7 @@ struct S1Ops {
     double* T = Tof(k);
     if (fused_small) {
       const int nblk = (m + S1F_CHUNKS * S2_B - 1) / (S1F_CHUNKS * S2_B);
-      hipLaunchKernelGGL(s1_fused_yt, dim3(nblk), dim3(256), yt_smem, st, (const double*)Y2, (const double*)T,
+      hipLaunchKernelGGL(s1_fused_yt, dim3(nblk), dim3(256), yt_smem, st, (const double*)Y2, Tyt(k),
                          (const double*)ws.Vp, m, ws.Y, ws.fpart);                   // Y = A22 V T, partial V'Y
       hipLaunchKernelGGL(s1_fused_s, dim3(pw), dim3(256), 0, st, (const double*)ws.fpart, nblk,
                          (const double*)T, S);                                       // S = T'V'Y
@@ -2002,7 +2231,7 @@ struct S1Ops {
     } else {
       BK_REQUIRE(pz1 == ws.PZ1 && ldpz == m, "stage 1: separate small products write the compact buffers only");
       const int blocks = (int)std::min<int64_t>(((int64_t)m * pw + 255) / 256, 4096);
-      BK_TRY(gemm(ctx, 0, 0, m, pw, pw, 1.0, Y2, m, T, pw, 0.0, ws.Y, m));            // Y = A22 V T
+      BK_TRY(gemm(ctx, 0, 0, m, pw, pw, 1.0, Y2, m, Tyt(k), pw, 0.0, ws.Y, m));            // Y = A22 V T
       BK_TRY(gemm(ctx, 1, 0, pw, pw, m, 1.0, ws.Vp, m, ws.Y, m, 0.0, S0, pw));        // V'Y
       BK_TRY(gemm(ctx, 1, 0, pw, pw, pw, 1.0, T, pw, S0, pw, 0.0, S, pw));            // S = T'V'Y
       BK_TRY(gemm(ctx, 0, 0, m, pw, pw, 1.0, ws.Vp, m, S, pw, 0.0, Y2, m));           // V S
@@ -2113,7 +2342,7 @@ int stage1_to_band(bigkrls_ctx* ctx, double* W, int n, double* taus1, const Stag
           double* A22 = W + (k + b) + (int64_t)(k + b) * N;
           const bool samp = ctx->profile && (k / b) % S1_PROF_STRIDE == 0;
           if (samp) BK_TRY(prof_begin(ctx, "band_av", 2.0 * (double)m * (double)m * b));
-          BK_TRY(gemm(ctx, 0, 0, m, b, m, 1.0, A22, N, ws.Vp, m, 0.0, ws.Y2, m));     // (stale A22) V
+          BK_TRY(gemm(ctx, 0, 0, m, b, m, 1.0, A22, N, ops.Vw(k), m, 0.0, ws.Y2, m));     // (stale A22) W
           if (samp) BK_TRY(prof_end(ctx, "band_av"));
           if (t_pending) {
             BK_HIP(hipStreamWaitEvent(st, ctx->ev_join2, 0));
@@ -2134,7 +2363,7 @@ int stage1_to_band(bigkrls_ctx* ctx, double* W, int n, double* taus1, const Stag
           if (j < 3) {
             hipStream_t saved = ctx->stream;
             ctx->stream = side;
-            const int rc = gemm(ctx, 1, 0, 2 * b * (j + 1), b, mn, 1.0, PZ2q + off + b, ldg, ws.Vp, mn, 0.0, Cfull,
+            const int rc = gemm(ctx, 1, 0, 2 * b * (j + 1), b, mn, 1.0, PZ2q + off + b, ldg, ops.Vw(k + b), mn, 0.0, Cfull,
                                 2 * b * (j + 1));
             ctx->stream = saved;
             BK_TRY(rc);
@@ -2165,7 +2394,7 @@ int stage1_to_band(bigkrls_ctx* ctx, double* W, int n, double* taus1, const Stag
         double* A22 = W + (k + b) + (int64_t)(k + b) * N;
         const bool samp = ctx->profile && (k / b) % S1_PROF_STRIDE == 0;
         if (samp) BK_TRY(prof_begin(ctx, "band_av", 2.0 * (double)m * (double)m * b));
-        BK_TRY(gemm(ctx, 0, 0, m, b, m, 1.0, A22, N, ws.Vp, m, 0.0, ws.Y2, m));     // (stale A22) V
+        BK_TRY(gemm(ctx, 0, 0, m, b, m, 1.0, A22, N, ops.Vw(k), m, 0.0, ws.Y2, m));     // (stale A22) W
         if (samp) BK_TRY(prof_end(ctx, "band_av"));
         if (t_pending) {
           BK_HIP(hipStreamWaitEvent(st, ctx->ev_join2, 0));   // T factor and the correction factors
@@ -2194,20 +2423,21 @@ int stage1_to_band(bigkrls_ctx* ctx, double* W, int n, double* taus1, const Stag
         BK_HIP(hipEventRecord(ctx->ev_join, side));
         BK_TRY(ops.build_T(k + b, side));
         {
-          // correction factors of the next step: U'^T V_{next} (and its part over R1)
+          // correction factors of the next step: U'^T W_{next} (and its part over R1) -- they act on Y2 = A22 W_{next}, which
+          // Tfold takes to Y as a whole (W = V U row by row, so the part over R1 is in the same space)
           hipStream_t saved = ctx->stream;
           ctx->stream = side;
           int rc = BIGKRLS_OK;
           if (half == 0) {
-            rc = gemm(ctx, 1, 0, 2 * b, b, mn, 1.0, PZ2g + b, ldg, ws.Vp, mn, 0.0, Ca, 2 * b);
+            rc = gemm(ctx, 1, 0, 2 * b, b, mn, 1.0, PZ2g + b, ldg, ops.Vw(k + b), mn, 0.0, Ca, 2 * b);
           } else {
             const int ncol64 = (mn + 63) / 64;
             const int J1 = std::min(std::max((int)(ncol64 * 0.2929 + 0.5), 1), ncol64 - 1);
             c1 = (k + 2 * b) + 64 * J1;
             const int64_t r1n = 64 * (int64_t)J1;
-            rc = gemm(ctx, 1, 0, 4 * b, b, mn, 1.0, PZ2g + 2 * b, ldg, ws.Vp, mn, 0.0, Cfull, 4 * b);
+            rc = gemm(ctx, 1, 0, 4 * b, b, mn, 1.0, PZ2g + 2 * b, ldg, ops.Vw(k + b), mn, 0.0, Cfull, 4 * b);
             if (rc == BIGKRLS_OK)
-              rc = gemm(ctx, 1, 0, 4 * b, b, mn - r1n, 1.0, PZ2g + 2 * b + r1n, ldg, ws.Vp + r1n, mn, 0.0, CR1, 4 * b);
+              rc = gemm(ctx, 1, 0, 4 * b, b, mn - r1n, 1.0, PZ2g + 2 * b + r1n, ldg, ops.Vw(k + b) + r1n, mn, 0.0, CR1, 4 * b);
           }
           ctx->stream = saved;
           BK_TRY(rc);
@@ -2265,7 +2495,7 @@ int stage1_to_band(bigkrls_ctx* ctx, double* W, int n, double* taus1, const Stag
     BK_TRY(fine("R:s1_tau", taus1 + k, pw, k));
     const bool samp = ctx->profile && (k / b) % S1_PROF_STRIDE == 0;   // HIP-event sampling: every 8th panel
     if (samp) BK_TRY(prof_begin(ctx, "band_av", 2.0 * (double)m * (double)m * pw));
-    BK_TRY(gemm(ctx, 0, 0, m, pw, m, 1.0, A22, N, ws.Vp, m, 0.0, ws.Y2, m));       // A22 V
+    BK_TRY(gemm(ctx, 0, 0, m, pw, m, 1.0, A22, N, ops.Vw(k), m, 0.0, ws.Y2, m));       // A22 W
     if (samp) BK_TRY(prof_end(ctx, "band_av"));
     if (t_pending) {   // the T factor was built on the look-ahead stream, concurrently with A22 V
       BK_HIP(hipStreamWaitEvent(st, ctx->ev_join2, 0));
@@ -2318,7 +2548,9 @@ int stage1_to_band(bigkrls_ctx* ctx, double* W, int n, double* taus1, const Stag
     // each of its two stream changes cost 12-15 us (from the end of a kernel on one stream to the start of its
     // dependant on the other; profiles/r05/r05b_C2_panel_chain_timeline.log). So the chain stays on the main stream --
     // the factorisation (which now writes its T factor itself) starts right behind s1_fused_z, A22 V right behind it --
-    // and the trailing update moves to the look-ahead stream, joined before A22 V reads the matrix.
+    // and the trailing update moves to the look-ahead stream, joined before A22 V reads the matrix. The tail of the split
+    // factorisation follows the update there (behind ev_pq): the update is the shorter of the two launches, so the tail
+    // starts with A22 W and ends before s1_fused_yt needs V and Tfold wherever that product is the longer one.
     static const int swap_m = [] { const char* e = getenv("BIGKRLS_S1_SWAP_M"); return e ? atoi(e) : S1_SWAP_M; }();
     if (has_panel(k + b) && panel_in_z && m - pw < swap_m && !ctx->side_is_main) {
       const bool narrow = true;
@@ -2338,7 +2570,7 @@ int stage1_to_band(bigkrls_ctx* ctx, double* W, int n, double* taus1, const Stag
       BK_TRY(ops.panel_qr(k + b, st));
       BK_HIP(hipEventRecord(ctx->ev_pq, st));
       BK_HIP(hipStreamWaitEvent(side, ctx->ev_pq, 0));
-      BK_TRY(ops.build_T(k + b, side));               // (returns at once on the device unless the panel fell back)
+      BK_TRY(ops.build_T(k + b, side));               // (the factorisation's tail, beside A22 W; the T chain of a panel that fell back)
       BK_HIP(hipEventRecord(ctx->ev_join2, side));
       t_pending = true;
       BK_HIP(hipStreamWaitEvent(st, ctx->ev_join, 0));

@@ -353,6 +353,15 @@ int bigkrls_dev_fill_random(bigkrls_ctx* ctx, double* p, int64_t count, uint32_t
  * src/eigen.cpp:18-22). */
 int bigkrls_dev_cholqr2(bigkrls_ctx* ctx, double* W, double* tmp, int64_t n, int64_t b, double* h_R,
                         int32_t* h_breakdown, double* d_R);
+/* One panel factorisation of the dense eigensolver's stage 1 (exposed for tests): the m x 64 panel P (device,
+ * column-major, ld; 128 <= m <= 20 480) is factorised by CholeskyQR2 + Householder reconstruction as the reduction does
+ * it -- head, the Householder kernel's slot, tail; the one-kernel form under BIGKRLS_PQ=fused. On return P holds R on
+ * and above the diagonal of its top block and V below it; V (m x 64, ld m) the unit lower trapezoidal reflector block;
+ * T (64 x 64) the upper triangular factor of H = I - V T V'; tau (64) its diagonal; Vw (m x 64, ld m) the operand
+ * W = V U of the big product of stage 1 and Tfold (64 x 64) = U^-1 T, so that W Tfold = V T (Vw = V and Tfold = T for
+ * the one-kernel form and for a panel left to the Householder kernel, which *h_fallback = 1 reports). */
+int bigkrls_dev_panel_factor(bigkrls_ctx* ctx, double* P, int64_t ld, int64_t m, double* Vw, double* V, double* T,
+                             double* Tfold, double* tau, int32_t* h_fallback);
 /* d_T (device, m x m column-major, m = steps b) = the block-tridiagonal projected matrix of a block Lanczos run:
  * diagonal blocks 0.5 (A_j + A_j') from d_A_blocks (steps blocks of b x b), sub-diagonal blocks beta_{j+1} (upper
  * triangular) from d_beta_blocks (steps - 1 blocks are read), super-diagonal blocks their transposes. */
