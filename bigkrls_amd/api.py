@@ -1037,6 +1037,129 @@ def partial_dependence(object: BigKRLS, which=None, grid=20, newdata=None, se: b
             "se.first.difference": sefd, "newdata": nd_init}
 
 
+def conditional_effects(object: BigKRLS, effect, along, grid=20, newdata=None, se: bool = True,
+                        vcov: Optional[str] = None, ctx: Optional[Context] = None) -> dict:
+    """Marginal effects along a moderator: how does the effect of x_j change with x_k? For every pair (j, k) of `effect`
+    x `along` (1-based ints or lists; all combinations) and every grid value v of x_k, the mean over the reference rows
+    of the marginal effect of x_j evaluated with x_k set to v -- the derivative for a continuous x_j (k == j: the slope
+    of the partial-dependence curve), the first difference between its two training values for a binary x_j -- with its
+    standard error and the covariance over the grid: the curve, its confidence band, and a test of "is the effect at
+    high x_k different from the effect at low x_k" ("contrast"). For every pair and every v the value and variance are
+    `avgderivatives` and `var.avgderivatives` of marginal_effects() on the reference rows with column k set to v, in its
+    units and with its factor 2 on the variances of a binary x_j. No counterpart in the reference. The numeric body is
+    ONE call into the C ABI, `bigkrls_conditional_effects`: the Gaussian kernel factorises over the columns, so all
+    curves come from one fused O(u n) pass (`bigkrls_dev_kernel_loo_moments`) instead of one marginal_effects() on u
+    rewritten rows per grid value.
+
+    grid: an int G >= 2 (np.linspace(min, max, G) of the moderator's training column) or a list with one array per
+    pair; a binary moderator always gets its two training values, and an explicit grid for it must hold only those.
+    newdata: the reference rows (u x p); None: the training rows. Column k of them is never read, nor column j for a
+    binary x_j. A pair (j, j) on a binary column is not defined. se / vcov and the multi-GPU rule: as in
+    marginal_effects() and partial_dependence(). Returns a dict: "pairs", "xlabs" (pairs of labels), "binary.effect",
+    "binary.moderator", "grid", "ce", "se.ce", "vcov.ce" (lists over the pairs; the last two None without a variance),
+    "contrast" = ce(last grid value) - ce(first) and "se.contrast" from the covariance (1 x m; the second None without a
+    variance), and "newdata"."""
+    if not isinstance(object, BigKRLS):
+        raise TypeError("Object not of class 'bigKRLS'")
+    form = _vcov_choice(object, vcov)
+    if not se:
+        form = None
+    if se and form is None:
+        raise ValueError("recompute bigKRLS object with bigKRLS(,vcov.est=TRUE) to compute standard errors")
+    if se and ("vcov.est.c.cols" in object or "rows" in object) and form != "factors":
+        raise NotImplementedError("conditional_effects of a multi-GPU fit (sharded vcov.est.c.cols) is not supported; "
+                                  "refit on one GPU or with vcov_form=\"factors\"")
+    Xh = np.asfortranarray(np.asarray(object["X"], dtype=np.float64))
+    n, p = Xh.shape
+    nd_init = nd = None
+    if newdata is not None:
+        nd_init = _as_host_matrix(newdata)
+        nd = np.array(nd_init, dtype=np.float64, order="F")
+        if nd.ndim != 2 or nd.shape[1] != p:
+            raise ValueError("ncol(newdata) differs from ncol(X) from fitted bigKRLS object")
+        if nd.shape[0] < 1:
+            raise ValueError("newdata has no rows")
+        if not np.all(np.isfinite(nd)):
+            raise ValueError("newdata contains missing or infinite values")
+
+    def columns(arg, name):
+        try:
+            cols = [int(i) for i in np.atleast_1d(arg)]
+        except (TypeError, ValueError):
+            raise ValueError(f"{name} must be a column index or a list of column indices") from None
+        if not cols or not all(1 <= i <= p for i in cols):
+            raise ValueError(f"{name} must index columns of X")
+        return cols
+    effects, alongs = columns(effect, "effect"), columns(along, "along")
+    isbin = np.array([np.unique(Xh[:, j]).size == 2 for j in range(p)])          # the fit's rule (R/bigKRLS.R:242)
+    pairs = []
+    for j in effects:
+        for k in alongs:
+            if j == k and isbin[j - 1]:
+                raise ValueError(f"pair ({j}, {k}) is not defined: column {j} is binary in the training data")
+            if (j, k) in pairs:
+                raise ValueError(f"pair ({j}, {k}) is given more than once")
+            pairs.append((j, k))
+    explicit = not isinstance(grid, (int, np.integer))
+    if explicit:
+        grid = list(grid)
+        if len(grid) != len(pairs):
+            raise ValueError("grid must be an integer or a list with one array per pair (effect x along)")
+    elif grid < 2:
+        raise ValueError("grid must be at least 2")
+    grids = []
+    for idx, (j, k) in enumerate(pairs):
+        lo, hi = Xh[:, k - 1].min(), Xh[:, k - 1].max()
+        if explicit:
+            g = np.ascontiguousarray(np.asarray(grid[idx], dtype=np.float64).ravel())
+            if g.size < 1 or not np.all(np.isfinite(g)):
+                raise ValueError(f"the grid of pair ({j}, {k}) must hold at least one finite value")
+            if isbin[k - 1] and not np.all((g == lo) | (g == hi)):
+                raise ValueError(f"the grid of pair ({j}, {k}): column {k} is binary in the training data; its values "
+                                 f"must be one of the two training values ({lo:g}, {hi:g})")
+        if isbin[k - 1]:
+            g = np.array([lo, hi])
+        elif not explicit:
+            g = np.linspace(lo, hi, int(grid))
+        grids.append(g)
+    ctx = ctx or object.get("_ctx") or default_context()
+    V = object.get("vcov.est.c") if form == "dense" else None
+    Vd = None if V is None else (V if is_device_matrix(V) else ctx.from_numpy(np.asarray(V, dtype=np.float64)))
+    Qd, wv = _factors(object, ctx) if form == "factors" else (None, None)
+    yv = np.ascontiguousarray(np.asarray(object["y"], dtype=np.float64).ravel())
+    coeffs = np.ascontiguousarray(np.asarray(object["coeffs"], dtype=np.float64).ravel())
+    pair_arr = np.ascontiguousarray(pairs, dtype=np.int64)                        # m x 2 row-major: pair after pair
+    m = len(pairs)
+    sizes = np.array([g.size for g in grids], dtype=np.int64)
+    off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(sizes)]), dtype=np.int64)
+    cov_off = np.concatenate([[0], np.cumsum(sizes * sizes)])
+    flat = np.ascontiguousarray(np.concatenate(grids))
+    total = int(off[-1])
+    ce = np.empty(total)
+    sev = np.empty(total) if se else None
+    cov = np.empty(int(cov_off[-1])) if se else None
+    _call_native("bigkrls_conditional_effects", ctx.handle, Xh.ctypes.data, n, p, yv.ctypes.data, coeffs.ctypes.data,
+                 float(object["sigma"]), pair_arr.ctypes.data, m, nd.ctypes.data if nd is not None else None,
+                 nd.shape[0] if nd is not None else n, flat.ctypes.data, off.ctypes.data,
+                 Vd.ptr if form == "dense" else None, Qd.ptr if form == "factors" else None,
+                 Qd.ld if form == "factors" else 0, Qd.ncol if form == "factors" else 0,
+                 wv.ctypes.data if form == "factors" else None, ce.ctypes.data,
+                 sev.ctypes.data if se else None, cov.ctypes.data if se else None)
+    cut = lambda v: [v[off[i]:off[i + 1]] for i in range(m)]
+    covs = None
+    if se:
+        covs = [cov[cov_off[i]:cov_off[i + 1]].reshape(sizes[i], sizes[i], order="F") for i in range(m)]
+    contrast = np.array([[ce[off[i + 1] - 1] - ce[off[i]] for i in range(m)]])
+    secon = None
+    if se:
+        secon = np.array([[np.sqrt(max(c[0, 0] + c[-1, -1] - 2.0 * c[0, -1], 0.0)) for c in covs]])
+    xlabs = list(object.get("xlabs") or [f"x{i + 1}" for i in range(p)])
+    return {"pairs": pairs, "xlabs": [(xlabs[j - 1], xlabs[k - 1]) for j, k in pairs],
+            "binary.effect": isbin[pair_arr[:, 0] - 1], "binary.moderator": isbin[pair_arr[:, 1] - 1], "grid": grids,
+            "ce": cut(ce), "se.ce": cut(sev) if se else None, "vcov.ce": covs, "contrast": contrast,
+            "se.contrast": secon, "newdata": nd_init}
+
+
 def _run_folds(jobs, contexts, fit_fn, predict_fn):
     """Run independent (train, test) jobs, one worker thread per context (== per GPU), and return
     the results in job order. Fold k goes to context k mod G: a fixed assignment, and because every

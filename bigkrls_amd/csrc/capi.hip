@@ -531,6 +531,13 @@ int bigkrls_dev_kernel_loo_colsums(bigkrls_ctx* ctx, const double* A, int64_t u,
   return kernel_loo_colsums(ctx, A, u, lda, B, v, ldb, p, sigma, h_cols, n_cols, out, ldo);
 }
 
+int bigkrls_dev_kernel_loo_moments(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B,
+                                   int64_t v, int64_t ldb, int64_t p, double sigma, const int64_t* h_entries,
+                                   int64_t n_entries, double* out, int64_t ldo) {
+  BK_TRY(check_ctx(ctx));
+  return kernel_loo_moments(ctx, A, u, lda, B, v, ldb, p, sigma, h_entries, n_entries, out, ldo);
+}
+
 int bigkrls_dev_quadform_diag(bigkrls_ctx* ctx, int64_t m, int64_t n, const double* A, int64_t lda, const double* V,
                               int64_t ldv, double* out) {
   BK_TRY(check_ctx(ctx));

@@ -206,9 +206,11 @@ enum Slot {
   SLOT_KB_B = 51,          // ... the shifted copy of B (v x P) where B is not a row block of A
   SLOT_KOP_X = 52,         // implicit kernel operator (KernelOp): the centred copy of X (n x P)
   SLOT_KOP_NORMS = 53,     // ... and its squared row norms
-  SLOT_LOO_PART = 54,      // kernel_loo_colsums: partial sums of the loop splits
+  SLOT_LOO_PART = 54,      // kernel_loo_colsums, kernel_loo_moments: partial sums of the loop splits (and a launch's columns
+                           //     before they are scattered to the caller's order)
   SLOT_PD_SMALL = 55,      // bigkrls_partial_dependence: standardised X and newdata, c, w, the grids, M, pd, variances
-  SLOT_PD_A = 56,          // ... one column's A_j (G_j x n, at most 1 GiB), its product with Q or vcov.est.c, the covariance
+                           //     bigkrls_conditional_effects: the same for the pairs
+  SLOT_PD_A = 56,          // ... one column's (pair's) A_j (G_j x n, at most 1 GiB), its product with Q or vcov.est.c, the covariance
   SLOT_RV_SMALL = 57,      // bigkrls_vcov_robust: g, d g, residuals, leverages, omega, M, S, U, theta, the cluster scores
   SLOT_CS_PART = 58,       // cluster_scores: the sums of the pieces of clusters that span several 64-row chunks
   SLOT_CS_INDEX = 59,      // ... the sort permutation, the rows' pieces, the pieces' destinations, the multi-piece clusters
@@ -319,6 +321,14 @@ int kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, c
 // (the rows of B stationary, the rows of A the loop). Operands as kernel_contract's; deterministic.
 int kernel_loo_colsums(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
                        int64_t ldb, int64_t p, double sigma, const int64_t* h_cols, int64_t n_cols, double* out,
+                       int64_t ldo);
+
+// out (v x n_entries, ldo): out[l, e] = sum_i wgt exp(-max(d2(i,l) - dc^2 - [kind = 2] dj^2, 0) / sigma) for the entries
+// (kind, c, j) of h_entries (host, 3 x n_entries column-major, 0-based columns): kind 0: wgt = 1 (kernel_loo_colsums'
+// quantity); kind 1: wgt = B[l,j] - A[i,j]; kind 2: wgt = 1, columns c and j both left out. One fused pass for all
+// entries, results in the caller's entry order. Operands as kernel_contract's; deterministic.
+int kernel_loo_moments(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
+                       int64_t ldb, int64_t p, double sigma, const int64_t* h_entries, int64_t n_entries, double* out,
                        int64_t ldo);
 
 // The same for operands that are already centred (one common shift, see centre_operands in gemm.hip) and come with

@@ -2989,6 +2989,349 @@ int kernel_loo_colsums(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda
   return kernel_loo_colsums_centred(ctx, co.B, v, co.ldb, co.nb, co.A, u, co.lda, co.na, p, sigma, h_cols, n_cols, out, ldo);
 }
 
+// ---------------------------------------------------------------------------
+// fused leave-out moments (conditional effects, csrc/condeff.hip)
+// ---------------------------------------------------------------------------
+// out[l, e] = sum_i wgt exp(-max(d2(i,l) - dc^2 - [kind = 2] dj^2, 0) / sigma), dc = A[i,c] - B[l,c], dj = A[i,j] - B[l,j],
+// for entries e = (kind, c, j):  kind 0: wgt = 1 (kernel_loo_colsums' quantity);  kind 1: wgt = B[l,j] - A[i,j];
+// kind 2: wgt = 1 and column j left out as well. kernel_loo_colsums_kernel's frame (64 stationary rows per wave, loop
+// rows 16 at a time, d2 once per tile, lane-group shuffles after the loop, loop splits through contract_reduce_kernel),
+// with the chunk redefined: the host sorts the entries by c and a chunk holds up to CW entries of ONE c, so
+//   base = max(d2 - dc^2, 0)                        once per chunk and row pair,
+//   e01  = exp(-base / sigma)                       once for ALL kind-0 and kind-1 entries of the chunk,
+//   kind 0: acc += e01;   kind 1: acc += e01 (S[s,j] - L[l,j])   -- one fused multiply-add on e01, no further exp;
+//   kind 2: acc += exp(-max(base - dj^2, 0) / sigma)             -- its own exponential.
+// max(max(a, 0) - b, 0) = max(a - b, 0) for b >= 0, so clamping base first changes nothing. The exponents are formed
+// directly (never K exp(+dc^2 / sigma)); the weight is the difference of the two centred copies, translation invariant
+// (S_j M0 - sum L_j e would cancel where the rows are close in column j). The kinds are wave-uniform (kernel argument).
+// Registers per lane beside kernel_loo_colsums_kernel's: the stationary and loop values of column c (4 + 4 doubles) and
+// the loop rows' values of all CW entry columns, loaded behind the MFMAs (4 CW doubles instead of 8). The
+// compiler's figures per KS and the chunk width they led to: DESIGN.md section 4, "Conditional effects".
+constexpr int KM_CW = 3;       // entries per wave (the chunk width) ...
+constexpr int KM_CW_KS8 = 2;   // ... and with KS = 8 (29 <= P <= 32), where the resident fragments leave room for two
+struct LooMomentEntries {
+  int c[KL_GROUP];           // the column every entry leaves out (one value per chunk)
+  int j[KL_GROUP];           // kind 1: the weight's column; kind 2: the second column left out; kind 0: c again
+  int kind[KL_GROUP];
+  int begin[KL_GROUP + 1];   // chunk cc holds the launch's entries [begin[cc], begin[cc + 1])
+};
+struct LooMomentDest {
+  int d[KL_GROUP];           // the caller's column of every entry of the launch
+};
+
+template <int KS, int CW>
+__global__ __launch_bounds__(NT, 2) void kernel_loo_moments_kernel(
+    const double* __restrict__ S, int64_t lds, int NS, const double* __restrict__ L, int64_t ldl, int NL, int P,
+    const double* __restrict__ nrm_s, const double* __restrict__ nrm_l, double neg_inv_sigma, LooMomentEntries ent,
+    double* __restrict__ out, int64_t ldo, int64_t split_stride, int stiles, int nchunks, int nsplit, int ltiles,
+    int64_t ntasks) {
+  __shared__ double etab[32];
+  if (threadIdx.x < 32) etab[threadIdx.x] = kExp2Tab32[threadIdx.x];
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w >= ntasks) return;
+  const int st = (int)(w % stiles);
+  const int cc = (int)((w / stiles) % nchunks);
+  const int sp = (int)(w / ((int64_t)stiles * nchunks));
+  const int s0 = st * 16 * KL_MS;
+  const int e0 = ent.begin[cc], ncw = ent.begin[cc + 1] - e0;   // (1 <= ncw <= CW)
+  const int t_begin = (int)((int64_t)ltiles * sp / nsplit), t_end = (int)((int64_t)ltiles * (sp + 1) / nsplit);
+  const int lm = lane & 15, lk = lane >> 4;
+  const int steps = (P + 3) / 4;
+
+  int srow[KL_MS];
+  double ns[KL_MS];
+#pragma unroll
+  for (int m = 0; m < KL_MS; ++m) {
+    srow[m] = min(s0 + 16 * m + lm, NS - 1);
+    ns[m] = nrm_s[srow[m]];
+  }
+  // stationary fragments (k >= P zeroed: the loop side then reads a clamped, finite value)
+  double sf[KL_MS][KS > 0 ? KS : 1];
+  if (KS > 0) {
+#pragma unroll
+    for (int m = 0; m < KL_MS; ++m)
+#pragma unroll
+      for (int t = 0; t < (KS > 0 ? KS : 1); ++t) {
+        const int k = 4 * t + lk;
+        sf[m][t] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
+      }
+  }
+  // the chunk's column c and its entries (wave-uniform; a slot past the chunk's end has kind -1 and is never
+  // accumulated), and the stationary rows' values in their columns
+  const int ccol = ent.c[e0];
+  const int64_t coffc = (int64_t)ccol * ldl;
+  double scv[KL_MS];
+#pragma unroll
+  for (int m = 0; m < KL_MS; ++m) scv[m] = S[srow[m] + (int64_t)ccol * lds];
+  int kind[CW];
+  int64_t joff[CW];
+  double sj[KL_MS][CW], acc[KL_MS][CW];
+  bool has01 = false;
+#pragma unroll
+  for (int j = 0; j < CW; ++j) {
+    const int e = e0 + min(j, ncw - 1);
+    kind[j] = j < ncw ? ent.kind[e] : -1;
+    has01 = has01 || kind[j] == 0 || kind[j] == 1;
+    const int col = ent.j[e];
+    joff[j] = (int64_t)col * ldl;
+#pragma unroll
+    for (int m = 0; m < KL_MS; ++m) {
+      sj[m][j] = S[srow[m] + (int64_t)col * lds];
+      acc[m][j] = 0.0;
+    }
+  }
+
+  for (int t = t_begin; t < t_end; ++t) {
+    const int l0 = t * 16;
+    const int lrow = min(l0 + lm, NL - 1);   // this lane's row of the L operand
+    const double* lp[4];                      // this lane's loop row in accumulator register r
+    double nl[4], mk[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int l = l0 + lk + 4 * r;
+      lp[r] = L + min(l, NL - 1);
+      nl[r] = nrm_l[min(l, NL - 1)];
+      mk[r] = l < NL ? 1.0 : 0.0;
+    }
+    double lc[4], lv[CW][4];               // the loop rows' values in column c and in the entries' columns:
+#pragma unroll                                // in flight behind the MFMAs
+    for (int r = 0; r < 4; ++r) lc[r] = lp[r][coffc];
+#pragma unroll
+    for (int j = 0; j < CW; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) lv[j][r] = lp[r][joff[j]];
+    d4 g[KL_MS];
+#pragma unroll
+    for (int m = 0; m < KL_MS; ++m) g[m] = (d4){0.0, 0.0, 0.0, 0.0};
+    if (KS > 0) {
+      double lf[KS > 0 ? KS : 1];
+#pragma unroll
+      for (int s = 0; s < (KS > 0 ? KS : 1); ++s) lf[s] = L[lrow + (int64_t)min(4 * s + lk, P - 1) * ldl];
+#pragma unroll
+      for (int s = 0; s < (KS > 0 ? KS : 1); ++s)
+#pragma unroll
+        for (int m = 0; m < KL_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sf[m][s], g[m], 0, 0, 0);
+    } else {
+      for (int s0k = 0; s0k < steps; s0k += 4) {
+        double lf[4], sg[KL_MS][4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const int k = 4 * (s0k + s) + lk;
+          lf[s] = L[lrow + (int64_t)min(k, P - 1) * ldl];
+#pragma unroll
+          for (int m = 0; m < KL_MS; ++m) sg[m][s] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+          for (int m = 0; m < KL_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sg[m][s], g[m], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < KL_MS; ++m) {
+      double tsum[CW];
+#pragma unroll
+      for (int j = 0; j < CW; ++j) tsum[j] = 0.0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        // the squared distance over all columns (kernel_loo_colsums_kernel's), then without column c
+        const double d2 = fmax(fma(-2.0, g[m][r], ns[m] + nl[r]), 0.0);
+        const double dc = lc[r] - scv[m];
+        const double base = fmax(fma(-dc, dc, d2), 0.0);
+        double e01 = 0.0;
+        if (has01) e01 = exp_nonpos_tab(base * neg_inv_sigma, etab) * mk[r];   // (wave-uniform)
+#pragma unroll
+        for (int j = 0; j < CW; ++j) {
+          if (kind[j] == 0) {                   // (wave-uniform, as the two below)
+            tsum[j] += e01;
+          } else if (kind[j] == 1) {
+            tsum[j] = fma(e01, sj[m][j] - lv[j][r], tsum[j]);
+          } else if (kind[j] == 2) {
+            const double dj = lv[j][r] - sj[m][j];
+            const double x = fmax(fma(-dj, dj, base), 0.0);
+            tsum[j] = fma(exp_nonpos_tab(x * neg_inv_sigma, etab), mk[r], tsum[j]);
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < CW; ++j) acc[m][j] += tsum[j];
+    }
+  }
+  // the four lane groups hold the sums over the loop rows l = (lane >> 4) mod 4 of the same stationary rows
+  double* dst = out + (int64_t)sp * split_stride;
+#pragma unroll
+  for (int j = 0; j < CW; ++j)
+#pragma unroll
+    for (int m = 0; m < KL_MS; ++m) {
+      double a = acc[m][j];
+      a += __shfl_xor(a, 16, 64);
+      a += __shfl_xor(a, 32, 64);
+      const int s = s0 + 16 * m + lm;
+      if (lk == 0 && j < ncw && s < NS) dst[s + (int64_t)(e0 + j) * ldo] = a;
+    }
+}
+
+// out[s, dest.d[blockIdx.y]] = src[s, blockIdx.y]: a launch's columns (sorted by c) to the caller's entry order
+__global__ void loo_moments_scatter_kernel(int NS, const double* __restrict__ src, LooMomentDest dest,
+                                           double* __restrict__ out, int64_t ldo) {
+  const int e = blockIdx.y;
+  double* o = out + (int64_t)dest.d[e] * ldo;
+  const double* s = src + (int64_t)e * NS;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < NS; i += gridDim.x * blockDim.x) o[i] = s[i];
+}
+
+__global__ void loo_moments_fill_kernel(int NS, double value, double* __restrict__ o) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < NS; i += gridDim.x * blockDim.x) o[i] = value;
+}
+
+int kernel_loo_moments(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
+                       int64_t ldb, int64_t p, double sigma, const int64_t* h_entries, int64_t n_entries, double* out,
+                       int64_t ldo) {
+  BK_REQUIRE(u > 0 && v > 0 && p > 0, "kernel_loo_moments: bad dimensions");
+  BK_REQUIRE(u < (1ll << 31) && v < (1ll << 31) && p < (1ll << 20), "kernel_loo_moments: too large");
+  BK_REQUIRE(sigma > 0.0, "kernel_loo_moments: sigma must be > 0");
+  BK_REQUIRE(A && B && h_entries && out, "kernel_loo_moments: null pointer");
+  BK_REQUIRE(lda >= u && ldb >= v, "kernel_loo_moments: leading dimension of A or B too small");
+  BK_REQUIRE(ldo >= v, "kernel_loo_moments: leading dimension of out too small");
+  BK_REQUIRE(n_entries >= 1 && n_entries < (1ll << 20), "kernel_loo_moments: n_entries must be at least 1 (and below 2^20)");
+  for (int64_t e = 0; e < n_entries; ++e) {
+    const int64_t kind = h_entries[3 * e], c = h_entries[3 * e + 1], j = h_entries[3 * e + 2];
+    const std::string where = "kernel_loo_moments: entry " + std::to_string(e) + " (kind " + std::to_string(kind) +
+                              ", c " + std::to_string(c) + ", j " + std::to_string(j) + "): ";
+    BK_REQUIRE(kind >= 0 && kind <= 2, where + "unknown kind");
+    BK_REQUIRE(c >= 0 && c < p, where + "column c outside [0, " + std::to_string(p) + ")");
+    if (kind != 0) {
+      BK_REQUIRE(j >= 0 && j < p, where + "column j outside [0, " + std::to_string(p) + ")");
+      BK_REQUIRE(j != c, where + "j must differ from c");
+    }
+  }
+  // An entry that leaves out every column (kind 0 at p = 1, kind 2 at p = 2) has the exponent 0 in every term: its sums
+  // are u, written as such (from the Gram tile the exponent would be rounding noise, and the sum u only to ~1e-16).
+  // The others in the order of their c (stable): a chunk is a run of up to cw entries of one c.
+  std::vector<int64_t> order;
+  order.reserve((size_t)n_entries);
+  for (int64_t e = 0; e < n_entries; ++e) {
+    const int64_t kind = h_entries[3 * e];
+    if ((kind == 0 && p == 1) || (kind == 2 && p == 2)) {
+      const int blocks = (int)std::min<int64_t>((v + 255) / 256, 1024);
+      hipLaunchKernelGGL(loo_moments_fill_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (int)v, (double)u, out + e * ldo);
+      BK_CHECK_LAUNCH();
+    } else {
+      order.push_back(e);
+    }
+  }
+  if (order.empty()) return BIGKRLS_OK;
+  std::stable_sort(order.begin(), order.end(),
+                   [h_entries](int64_t a, int64_t b) { return h_entries[3 * a + 1] < h_entries[3 * b + 1]; });
+  const int64_t n_sorted = (int64_t)order.size();
+
+  CentredOperands co;     // both operands moved by the column means of A (see centre_operands)
+  BK_TRY(centre_operands(ctx, A, u, lda, B, v, ldb, p, &co));
+  // the rows of B are stationary, the rows of A the loop (kernel_contract's trans = 1)
+  const double *S = co.B, *L = co.A, *nrm_s = co.nb, *nrm_l = co.na;
+  const int64_t ns = v, nl = u, lds = co.ldb, ldl = co.lda;
+  const int steps = (int)((p + 3) / 4);
+  const int ks = steps <= 8 ? steps : 0;
+  const int64_t cw = ks == 8 ? KM_CW_KS8 : KM_CW;
+  using KmFn = void (*)(const double*, int64_t, int, const double*, int64_t, int, int, const double*, const double*,
+                        double, LooMomentEntries, double*, int64_t, int64_t, int, int, int, int, int64_t);
+  KmFn fn = nullptr;
+  switch (ks) {
+    case 1: fn = kernel_loo_moments_kernel<1, KM_CW>; break;
+    case 2: fn = kernel_loo_moments_kernel<2, KM_CW>; break;
+    case 3: fn = kernel_loo_moments_kernel<3, KM_CW>; break;
+    case 4: fn = kernel_loo_moments_kernel<4, KM_CW>; break;
+    case 5: fn = kernel_loo_moments_kernel<5, KM_CW>; break;
+    case 6: fn = kernel_loo_moments_kernel<6, KM_CW>; break;
+    case 7: fn = kernel_loo_moments_kernel<7, KM_CW>; break;
+    case 8: fn = kernel_loo_moments_kernel<8, KM_CW_KS8>; break;
+    default: fn = kernel_loo_moments_kernel<0, KM_CW>; break;
+  }
+  int cap = 0;
+  BK_TRY(resident_capacity(ctx, (const void*)fn, &cap, NT));
+  const int64_t slots = (int64_t)cap * (NT / 64);
+  const int64_t stiles = (ns + 16 * KL_MS - 1) / (16 * KL_MS);
+  const int64_t ltiles = (nl + 15) / 16;
+  for (int64_t g0 = 0; g0 < n_sorted; g0 += KL_GROUP) {
+    const int64_t nc = std::min<int64_t>(KL_GROUP, n_sorted - g0);
+    LooMomentEntries le;
+    LooMomentDest dest;
+    bool in_place = true;   // the launch's columns are consecutive columns of out, in order
+    for (int64_t i = 0; i < KL_GROUP; ++i) {
+      const int64_t e = order[(size_t)(g0 + std::min(i, nc - 1))];
+      le.kind[i] = (int)h_entries[3 * e];
+      le.c[i] = (int)h_entries[3 * e + 1];
+      le.j[i] = le.kind[i] == 0 ? le.c[i] : (int)h_entries[3 * e + 2];
+      dest.d[i] = (int)e;
+      if (i < nc && e != order[(size_t)g0] + i) in_place = false;
+    }
+    // chunks: every run of one c, split evenly into pieces of at most cw entries; the exponentials per row pair
+    int64_t nchunks = 0, nexp = 0;
+    for (int64_t r0 = 0; r0 < nc;) {
+      int64_t r1 = r0 + 1;
+      while (r1 < nc && le.c[r1] == le.c[r0]) ++r1;
+      const int64_t len = r1 - r0, pieces = (len + cw - 1) / cw;
+      for (int64_t q = 0; q < pieces; ++q) {
+        const int64_t b0 = r0 + len * q / pieces, b1 = r0 + len * (q + 1) / pieces;
+        le.begin[nchunks++] = (int)b0;
+        bool has01 = false;
+        for (int64_t i = b0; i < b1; ++i) {
+          if (le.kind[i] == 2) ++nexp; else has01 = true;
+        }
+        if (has01) ++nexp;
+      }
+      r0 = r1;
+    }
+    for (int64_t i = nchunks; i <= KL_GROUP; ++i) le.begin[i] = (int)nc;
+    // loop splits: kernel_contract_centred's model (rounds of resident waves x loop tiles per wave) and limits
+    const int64_t base = stiles * nchunks;
+    const int64_t max_split =
+        std::max<int64_t>(1, std::min<int64_t>({(int64_t)64, ltiles / 16, (64ll << 20) / (ns * nc * (int64_t)sizeof(double))}));
+    int64_t nsplit = 1;
+    double best = (double)((base + slots - 1) / slots);
+    for (int64_t s = 2; s <= max_split; ++s) {
+      const double cost = (double)((base * s + slots - 1) / slots) / (double)s;
+      if (cost < best * 0.98) { best = cost; nsplit = s; }
+    }
+    const int64_t ntasks = base * nsplit;
+    BK_REQUIRE((ntasks + 3) / 4 < (1ll << 31), "kernel_loo_moments: too many tiles");
+    // the partial sums of the splits, and behind them the launch's columns where they are scattered afterwards
+    const int64_t part_doubles = nsplit > 1 ? nsplit * ns * nc : 0, tmp_doubles = in_place ? 0 : ns * nc;
+    double *part = nullptr, *tmp = nullptr;
+    if (part_doubles + tmp_doubles > 0) {
+      void* pp = nullptr;
+      BK_TRY(ws_get(ctx, SLOT_LOO_PART, (part_doubles + tmp_doubles) * (int64_t)sizeof(double), &pp));
+      part = (double*)pp;
+      tmp = part + part_doubles;
+    }
+    double* og = in_place ? out + order[(size_t)g0] * ldo : tmp;   // where the launch's columns end up first
+    const int64_t ldg = in_place ? ldo : ns;
+    double* dst = nsplit > 1 ? part : og;
+    const int64_t ldd = nsplit > 1 ? ns : ldg, split_stride = nsplit > 1 ? ns * nc : 0;
+    BK_TRY(prof_begin(ctx, "kernel_loo_moments", (double)ns * (double)nl * (double)nexp));
+    hipLaunchKernelGGL(fn, dim3((unsigned)((ntasks + 3) / 4)), dim3(NT), 0, ctx->stream, S, lds, (int)ns, L, ldl, (int)nl,
+                       (int)p, nrm_s, nrm_l, -1.0 / sigma, le, dst, ldd, split_stride, (int)stiles, (int)nchunks,
+                       (int)nsplit, (int)ltiles, ntasks);
+    BK_CHECK_LAUNCH();
+    if (nsplit > 1) {
+      const int blocks = (int)std::min<int64_t>((ns * nc + 255) / 256, 4096);
+      hipLaunchKernelGGL(contract_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (int)ns, (int)nc, (int)nsplit,
+                         (const double*)part, og, ldg);
+      BK_CHECK_LAUNCH();
+    }
+    if (!in_place) {
+      const int blocks = (int)std::min<int64_t>((ns + 255) / 256, 1024);
+      hipLaunchKernelGGL(loo_moments_scatter_kernel, dim3(blocks, (unsigned)nc), dim3(256), 0, ctx->stream, (int)ns,
+                         (const double*)tmp, dest, out, ldo);
+      BK_CHECK_LAUNCH();
+    }
+    BK_TRY(prof_end(ctx, "kernel_loo_moments"));
+  }
+  return BIGKRLS_OK;
+}
+
 // ---- the kernel matrix of one data set as an operator (kernel = "implicit": csrc/eigen.hip, csrc/fit.hip) -----------
 // The centred copy of X and its squared row norms live in slots of their own, so that they survive every other kernel
 // build or contraction of the context until the next kernel_op_prepare.

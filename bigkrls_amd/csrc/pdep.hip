@@ -14,8 +14,9 @@
 // elementwise kernel writes A_j (G_j x n, the rows a_j(v_g)'), pd = A_j c (gemv), and the variance is
 //   factors Vc = Q diag(w) Q': T = A_j Q (gemm), diag = sum_m w_m T_gm^2 (rowsumsq_weighted), cov = (T diag(w)) T'
 //   matrix:                    diag(A_j Vc A_j') (quadform_diag),                              cov = (A_j Vc) A_j'
-// O(G n k) or O(G n^2) per column. Column j of the reference sample is never read for column j's curve.
+// O(G n k) or O(G n^2) per column (curve_tail, curvetail.h). Column j of the reference sample is never read for column j's curve.
 // Device memory: O((u + n)(p + |J|)) plus the loop splits' partials, and per column A_j (at most 1 GiB) with its product.
+#include "curvetail.h"
 #include "hostprep.h"
 
 #include <cstring>
@@ -159,23 +160,7 @@ int bigkrls_partial_dependence(bigkrls_ctx* ctx, const double* h_X, int64_t n, i
     hipLaunchKernelGGL(pd_rows_kernel, dim3(blocks), dim3(256), 0, st, (int)G, (int)n, (const double*)(dM + jj * n),
                        (const double*)(dXs + j * n), (const double*)(dvs + g0), -1.0 / sigma, 1.0 / (double)u, dA);
     BK_CHECK_LAUNCH();
-    BK_TRY(gemv(ctx, 0, G, n, 1.0, dA, G, dc, 0.0, dpd + g0));                                    // A_j c
-    if (!want_var) continue;
-    if (vc.d_Q) {
-      double* dTw = dP + G * kq;
-      BK_TRY(gemm(ctx, 0, 0, G, kq, n, 1.0, dA, G, vc.d_Q, vc.ldq, 0.0, dP, G));                  // T = A_j Q
-      BK_TRY(rowsumsq_weighted(ctx, G, kq, dP, G, dw, dvar + g0));
-      if (h_cov) {
-        BK_TRY(multdiag(ctx, dP, G, kq, G, dw, dTw, G));
-        BK_TRY(gemm(ctx, 0, 1, G, G, kq, 1.0, dTw, G, dP, G, 0.0, dcov_j, G));                    // (T diag(w)) T'
-      }
-    } else {
-      BK_TRY(quadform_diag(ctx, G, n, dA, G, vc.d_V, n, dvar + g0));                              // diag(A_j Vc A_j')
-      if (h_cov) {
-        BK_TRY(gemm(ctx, 0, 0, G, n, n, 1.0, dA, G, vc.d_V, n, 0.0, dP, G));
-        BK_TRY(gemm(ctx, 0, 1, G, G, n, 1.0, dP, G, dA, G, 0.0, dcov_j, G));                      // (A_j Vc) A_j'
-      }
-    }
+    BK_TRY(curve_tail(ctx, vc, want_var, G, n, kq, dA, dP, dc, dw, dpd + g0, dvar + g0, h_cov ? dcov_j : nullptr));
     if (h_cov) dcov_j += G * G;
   }
   BK_HIP(hipMemcpyAsync(pin, dpd, (size_t)down_doubles * sizeof(double), hipMemcpyDeviceToHost, st));

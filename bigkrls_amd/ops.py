@@ -90,6 +90,25 @@ def bKernelLooColsums(A: DeviceMatrix, B: DeviceMatrix, sigma: float, cols) -> D
     return out
 
 
+def bKernelLooMoments(A: DeviceMatrix, B: DeviceMatrix, sigma: float, entries) -> DeviceMatrix:
+    """out (nrow(B) x len(entries)) for entries (kind, c, j) with 0-based columns: out[l, e] = sum_i wgt
+    exp(-max(d2(i,l) - dc^2 - [kind = 2] dj^2, 0) / sigma) with dc = A[i,c] - B[l,c], dj = A[i,j] - B[l,j]; kind 0: wgt = 1
+    (bKernelLooColsums' quantity, j ignored), kind 1: wgt = B[l,j] - A[i,j], kind 2: wgt = 1 with columns c and j both left
+    out of the distance. All entries in one fused pass (bigkrls_dev_kernel_loo_moments). No counterpart in the reference."""
+    ctx = A.ctx
+    if A.ncol != B.ncol:
+        raise ValueError("bKernelLooMoments: column counts of A and B differ")
+    h = np.asarray(entries, dtype=np.int64)
+    if h.size and (h.ndim != 2 or h.shape[1] != 3):
+        raise ValueError("bKernelLooMoments: entries must be a list of (kind, c, j)")
+    h = np.ascontiguousarray(h.reshape(-1, 3))                # row-major e x 3 == column-major 3 x e
+    out = ctx.empty(B.nrow, max(int(h.shape[0]), 1))
+    _lib.call("bigkrls_dev_kernel_loo_moments", ctx.handle, A.ptr, A.nrow, A.ld, B.ptr, B.nrow, B.ld, A.ncol,
+              float(sigma), h.ctypes.data if h.size else np.zeros(3, dtype=np.int64).ctypes.data, int(h.shape[0]),
+              out.ptr, out.ld)
+    return out
+
+
 def bQuadformDiag(A: DeviceMatrix, V: DeviceMatrix) -> DeviceMatrix:
     """diag(A V A') (m x 1) for A m x n and a general V n x n: out[i] = sum_j (A V)[i,j] A[i,j], without storing
     A V (bigkrls_dev_quadform_diag). No counterpart in the reference."""

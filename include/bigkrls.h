@@ -101,7 +101,8 @@ int bigkrls_ctx_release_workspace(bigkrls_ctx* ctx);
  * "lanczos_cgs2" (block-Lanczos step, flops), "symv" (one-stage path, bytes of the
  * lower triangle streamed), "solveforc_probe", "deriv_rows", "yhat_gemv" (algorithmic
  * bytes: 8 N K per probe, 8 N^2, 8 N^2), "vcov_syrk" (N (N + 1) K flops per matrix),
- * "kernel_loo_colsums" (u v n_cols exponentials). */
+ * "kernel_loo_colsums" (u v n_cols exponentials), "kernel_loo_moments" (u v E exponentials, E per
+ * row pair: one per chunk with a kind-0 or kind-1 entry plus one per kind-2 entry). */
 int bigkrls_ctx_set_profile(bigkrls_ctx* ctx, int enable);
 int bigkrls_ctx_get_profile(bigkrls_ctx* ctx, const char* name, double* total_ms,
                             double* total_work, int64_t* launches);
@@ -222,6 +223,23 @@ int bigkrls_dev_kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, in
 int bigkrls_dev_kernel_loo_colsums(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B,
                                    int64_t v, int64_t ldb, int64_t p, double sigma, const int64_t* h_cols,
                                    int64_t n_cols, double* out, int64_t ldo);
+
+/* Fused leave-out moments: out (v x n_entries, ldo >= v). h_entries (host) is 3 x n_entries column-major, entry e =
+ * (kind, c, j) with 0-based columns, and with dc = A[i,c] - B[l,c], dj = A[i,j] - B[l,j], d2 = ||A_i - B_l||^2:
+ *   out[l, e] = sum_i wgt exp(-max(d2 - dc^2 - [kind = 2] dj^2, 0) / sigma)
+ *   kind 0: wgt = 1, j ignored (bigkrls_dev_kernel_loo_colsums' quantity);   kind 1: wgt = B[l,j] - A[i,j], j != c;
+ *   kind 2: wgt = 1, columns c and j both left out of the distance, j != c.
+ * One pass for all entries: the entries are sorted by c (stable) and those of one c share the Gram tile and
+ * d2 - dc^2; the kind-0 and kind-1 entries of a chunk share ONE exponential (a kind-1 entry is one fused multiply-add
+ * on it), a kind-2 entry takes its own. The exponents are formed directly, never as K exp(+dc^2 / sigma); the weight is
+ * the difference of the centred copies of the operands, never B_j M0 - sum A_j e. An entry that leaves out every column
+ * (kind 0 at p = 1, kind 2 at p = 2) gives exactly u. Results are in the caller's entry order. Extra device memory
+ * O((u + v) (p + n_entries)), never O(u v); no atomics; deterministic: two calls give bitwise identical results. A and B
+ * need not be centred. An unknown kind, a column outside [0, p), j = c for kinds 1 and 2, or n_entries < 1 is
+ * BIGKRLS_EINVAL naming the entry. Profile name "kernel_loo_moments". */
+int bigkrls_dev_kernel_loo_moments(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B,
+                                   int64_t v, int64_t ldb, int64_t p, double sigma, const int64_t* h_entries,
+                                   int64_t n_entries, double* out, int64_t ldo);
 
 /* Diagonal of a quadratic form: out[i] = sum_j (A V)[i,j] A[i,j] = diag(A V A')[i], A m x n (lda >= m),
  * V n x n (ldv >= n), both column-major; V is general (not assumed symmetric). out has m entries. The m x n product
@@ -682,6 +700,32 @@ int bigkrls_partial_dependence(bigkrls_ctx* ctx, const double* h_X, int64_t n, i
                                const double* h_newdata, int64_t u, const double* h_grid, const int64_t* h_grid_off,
                                const double* d_vcov_c, const double* d_Q, int64_t ldq, int64_t k, const double* h_w,
                                double neffective, double* h_pd, double* h_se, double* h_cov);
+
+/* Conditional effects: the marginal effect of x_j along a moderator x_k, with its covariance over the grid (no
+ * counterpart in the reference). h_pairs is 2 x m column-major, 1-based: pair i = (effect j, moderator k). For every pair
+ * and every raw grid value v of x_k (h_grid: the pairs' grids concatenated, pair i's at h_grid_off[i] .. h_grid_off[i + 1],
+ * G_i >= 1 values each; T = h_grid_off[m] in all):
+ *   h_ce  = the mean over the reference rows of the marginal effect of x_j with column k set to v (original units):
+ *           the derivative for a continuous j (k = j: the slope of the partial-dependence curve), the first difference
+ *           between its two training values over their gap for a binary j,
+ *   h_se  = its standard error (T values; may be NULL),
+ *   h_cov = the G_i x G_i covariance of pair i's curve, column-major, the pairs' blocks one after the other
+ *           (sum_i G_i^2 doubles; may be NULL).
+ * They are avgderivatives and var.avgderivatives of bigkrls_marginal_effects on the reference rows with column k set to
+ * v, in its units and with its factor 2 on the variances of a binary j. Reference rows, grids, value and covariance
+ * layouts, the forms of vcov.est.c and the cap 8 G_i n <= 2^30 bytes are bigkrls_partial_dependence's, per pair instead of
+ * per column; column k of the reference rows is never read, nor column j for a binary j. BIGKRLS_EINVAL naming the pair:
+ * a pair (j, j) on a binary column, a pair given twice, an index outside [1, p], a grid value of a binary moderator
+ * that is not one of its two training values, a grid above the cap.
+ * In standardised units CE_jk(v) = a_jk(v)' c with a_jk(v)[l] = E_k(v)[l] times a moment of the test kernel with column
+ * k left out (csrc/condeff.hip): ONE fused O(u n) pass bigkrls_dev_kernel_loo_moments(Zs, Xs) for all pairs (kind 1 for
+ * a continuous j != k, kind 0 for j = k, kind 2 for a binary j; deduplicated); per pair A_jk (G_i x n) is written and the
+ * values, variances and covariance come from bigkrls_partial_dependence's tail. */
+int bigkrls_conditional_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                                const double* h_coeffs, double sigma, const int64_t* h_pairs, int64_t m,
+                                const double* h_newdata, int64_t u, const double* h_grid, const int64_t* h_grid_off,
+                                const double* d_vcov_c, const double* d_Q, int64_t ldq, int64_t k, const double* h_w,
+                                double* h_ce, double* h_se, double* h_cov);
 
 /* Heteroskedasticity- or cluster-robust variance of the coefficients as factors (no counterpart in the reference).
  * d_Q (n x k, ldq >= n, device) and h_d (k, host) are the kept eigenpairs of the fit, lambda its ridge parameter,
