@@ -95,6 +95,7 @@ SIGNATURES = {
     # level 2
     "bigkrls_dev_kernel_block": [vp, vp, i64, i64, vp, i64, i64, i64, f64, vp, i64, i64],
     "bigkrls_dev_kernel_contract": [vp, vp, i64, i64, vp, i64, i64, i64, f64, vp, i64, i64, C.c_int, vp, i64],
+    "bigkrls_dev_kernel_contract_grouped": [vp, vp, i64, i64, vp, i64, i64, i64, f64, vp, i64, i64, vp, i64, vp, i64],
     "bigkrls_dev_kernel_loo_colsums": [vp, vp, i64, i64, vp, i64, i64, i64, f64, vp, i64, vp, i64],
     "bigkrls_dev_kernel_loo_moments": [vp, vp, i64, i64, vp, i64, i64, i64, f64, vp, i64, vp, i64],
     "bigkrls_dev_quadform_diag": [vp, i64, i64, vp, i64, vp, i64, vp],
@@ -143,6 +144,8 @@ SIGNATURES = {
                                    vp, vp, vp],
     "bigkrls_conditional_effects": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp,
                                     vp],
+    "bigkrls_group_effects": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, vp, i64, vp, vp, i64, i64, vp, vp, vp,
+                              vp],
     "bigkrls_vcov_robust": [vp, i64, i64, vp, i64, vp, f64, vp, f64, f64, i32, vp, i64, vp, i64, vp],
     # multi-GPU
     "bigkrls_comm_unique_id": [vp],

@@ -397,6 +397,78 @@ def _betacf(a: float, b: float, x: float) -> float:
     return h
 
 
+def _chi2_sf(x: float, df: float) -> float:
+    """P(X > x) for a chi-square with df degrees of freedom (R: pchisq(x, df, lower.tail=FALSE)): the regularised upper
+    incomplete gamma function Q(df/2, x/2) -- the series of P below a + 1, the continued fraction of Q (modified Lentz)
+    above, the common factor exp(-x + a log x - lgamma(a)) formed in logs so that a large x underflows to 0. df = 2 is
+    exp(-x/2) itself."""
+    if not np.isfinite(df) or not df > 0 or x != x:
+        return float("nan")
+    if x <= 0.0:
+        return 1.0
+    a, z = 0.5 * df, 0.5 * x
+    if a == 1.0:
+        return math.exp(-z)
+    if z == float("inf"):
+        return 0.0
+    front = math.exp(-z + a * math.log(z) - math.lgamma(a))
+    if z < a + 1.0:
+        term = total = 1.0 / a
+        ap = a
+        for _ in range(10000):
+            ap += 1.0
+            term *= z / ap
+            total += term
+            if abs(term) < abs(total) * 1e-17:
+                break
+        return min(max(1.0 - front * total, 0.0), 1.0)
+    tiny = 1e-300
+    b = z + 1.0 - a
+    c = 1.0 / tiny
+    d = 1.0 / (b if abs(b) > tiny else tiny)
+    h = d
+    for i in range(1, 10000):
+        an = -i * (i - a)
+        b += 2.0
+        d = an * d + b
+        d = 1.0 / (d if abs(d) > tiny else tiny)
+        c = b + an / c
+        c = c if abs(c) > tiny else tiny
+        delta = d * c
+        h *= delta
+        if abs(delta - 1.0) < 1e-16:
+            break
+    return min(max(front * h, 0.0), 1.0)
+
+
+def _wald(theta, Sigma, reference_index: int):
+    """Wald test of H0: all entries of theta are equal, theta ~ N(., Sigma). With C the (G - 1) x G differences against
+    entry `reference_index`: (C theta)' pinv(C Sigma C') (C theta), the pseudo-inverse from the symmetric eigenpairs above
+    max eigenvalue x (G - 1) x machine epsilon; df = the rank used, p = the upper chi-square tail. Returns
+    (statistic, df, p); G = 1, or a covariance of rank 0, gives (0, 0, nan). Host only."""
+    theta = np.asarray(theta, dtype=np.float64).ravel()
+    Sigma = np.asarray(Sigma, dtype=np.float64)
+    G = theta.size
+    if Sigma.shape != (G, G):
+        raise ValueError("Sigma must be length(theta) x length(theta)")
+    if not 0 <= int(reference_index) < G:
+        raise ValueError("reference_index must index theta")
+    if G < 2:
+        return 0.0, 0, float("nan")
+    Cm = np.delete(np.eye(G), int(reference_index), axis=0)
+    Cm[:, int(reference_index)] = -1.0
+    d = Cm @ theta
+    Vd = Cm @ Sigma @ Cm.T
+    w, U = np.linalg.eigh(0.5 * (Vd + Vd.T))
+    keep = w > max(w.max(), 0.0) * (G - 1) * np.finfo(np.float64).eps
+    df = int(keep.sum())
+    if df == 0:
+        return 0.0, 0, float("nan")
+    z = U[:, keep].T @ d
+    stat = float(np.sum(z * z / w[keep]))
+    return stat, df, _chi2_sf(stat, df)
+
+
 def _pt_upper(t: float, df: float) -> float:
     """P(T > t) for Student's t with df degrees of freedom, t >= 0 (R: pt(t, df, lower.tail=FALSE)):
     0.5 I_x(df/2, 1/2) with x = df / (df + t^2)."""
@@ -1158,6 +1230,142 @@ def conditional_effects(object: BigKRLS, effect, along, grid=20, newdata=None, s
             "binary.effect": isbin[pair_arr[:, 0] - 1], "binary.moderator": isbin[pair_arr[:, 1] - 1], "grid": grids,
             "ce": cut(ce), "se.ce": cut(sev) if se else None, "vcov.ce": covs, "contrast": contrast,
             "se.contrast": secon, "newdata": nd_init}
+
+
+def _group_labels(by, nd, bins):
+    """(groups, labels) of group_effects(): `by` as u labels (groups = np.unique(by)), or as a 1-based column index of nd:
+    the column's distinct values, or with bins=B its quantile bins
+    np.digitize(col, np.quantile(col, np.linspace(0, 1, B + 1))[1:-1], right=True), empty bins dropped, reported by their
+    (lo, hi] edges. labels: int64 indices into groups. Host only."""
+    u, p = nd.shape
+    if isinstance(by, (int, np.integer)) and not isinstance(by, (bool, np.bool_)):
+        if not 1 <= int(by) <= p:
+            raise ValueError("by must index a column of newdata (1-based) or hold one label per row")
+        col = nd[:, int(by) - 1]
+        if bins is None:
+            groups, labels = np.unique(col, return_inverse=True)
+            return list(groups), np.ascontiguousarray(labels.ravel(), dtype=np.int64)
+        if not isinstance(bins, (int, np.integer)) or isinstance(bins, (bool, np.bool_)) or bins < 1:
+            raise ValueError("bins must be a positive integer")
+        edges = np.quantile(col, np.linspace(0.0, 1.0, int(bins) + 1))
+        raw = np.digitize(col, edges[1:-1], right=True)
+        used, labels = np.unique(raw, return_inverse=True)
+        groups = [(float(edges[b]), float(edges[b + 1])) for b in used]
+        return groups, np.ascontiguousarray(labels.ravel(), dtype=np.int64)
+    if bins is not None:
+        raise ValueError("bins applies only when by is a column index")
+    arr = np.asarray(by)
+    if arr.ndim == 2 and 1 in arr.shape:
+        arr = arr.ravel()
+    if arr.ndim != 1 or arr.size != u:
+        raise ValueError(f"by must hold one label per row of newdata ({u}); it has shape {np.asarray(by).shape}")
+    groups, labels = np.unique(arr, return_inverse=True)
+    return list(groups), np.ascontiguousarray(labels.ravel(), dtype=np.int64)
+
+
+def group_effects(object: BigKRLS, by, newdata=None, which_derivatives=None, bins=None, reference=None,
+                  vcov: Optional[str] = None, ctx: Optional[Context] = None) -> dict:
+    """Average marginal effects by subgroup, with their joint covariance and a test of heterogeneity: does the effect of
+    x_j differ between the groups of the rows actually observed? For every group g of `by` and every selected column j,
+    "ame"[g, j] is the mean of marginal_effects()'s derivatives over the rows of the group; "vcov.ame" is the joint
+    covariance of all of them (index jj * G + g: the groups of one variable are adjacent), so that differences between
+    groups and joint statements over several variables have standard errors. Every diagonal entry is
+    marginal_effects(object, newdata[rows of g])["var.avgderivatives"], binary columns with the reference's factor 2
+    (carried as sqrt(2) per side off the diagonal, which keeps the matrix positive semi-definite). No counterpart in
+    the reference. The numeric body is ONE call into the C ABI, `bigkrls_group_effects`: the column side of all groups
+    comes from one grouped fused contraction (`bigkrls_dev_kernel_contract_grouped`) and the covariance from the factors
+    of vcov.est.c (or the matrix) on the device; nothing N x N reaches the host.
+
+    newdata defaults to the training X. by: one label per row (any sortable dtype; the groups are np.unique(by)), or a
+    1-based column index of newdata: its distinct values, or with bins=B its B quantile bins (empty bins dropped;
+    "groups" then holds the (lo, hi] edges). reference: a group label (default: the first group). which_derivatives,
+    vcov and the multi-GPU rule: as in marginal_effects(). G * |J| may be at most 4096.
+
+    Returns a dict: "groups", "n" (rows per group), "ame" (G x |J|), "se.ame", "vcov.ame", "diff" and "se.diff" (each
+    group minus the reference, per variable; the reference row is 0), "wald" = {"statistic", "df", "p"} (each of length
+    |J|; H0: the group AMEs of x_j are all equal, see _wald; G = 1 gives 0, 0, nan), "reference", "derivatives" (u x |J|),
+    "which.derivatives", "binaryindicator", "xlabs", "newdata". Without a variance form on the object "se.ame",
+    "vcov.ame", "se.diff" and "wald" are None."""
+    if not isinstance(object, BigKRLS):
+        raise TypeError("Object not of class 'bigKRLS'")
+    form = _vcov_choice(object, vcov)
+    if ("vcov.est.c.cols" in object or "rows" in object) and form != "factors":
+        raise NotImplementedError("group_effects of a multi-GPU fit (sharded vcov.est.c.cols) is not supported; "
+                                  "refit on one GPU or with vcov_form=\"factors\"")
+    Xh = np.asfortranarray(np.asarray(object["X"], dtype=np.float64))
+    n, p = Xh.shape
+    nd_init = Xh if newdata is None else _as_host_matrix(newdata)
+    nd = np.array(nd_init, dtype=np.float64, order="F")
+    if nd.ndim != 2 or nd.shape[1] != p:
+        raise ValueError("ncol(newdata) differs from ncol(X) from fitted bigKRLS object")
+    u = nd.shape[0]
+    if u < 1:
+        raise ValueError("newdata has no rows")
+    if not np.all(np.isfinite(nd)):
+        raise ValueError("newdata contains missing or infinite values")
+    if which_derivatives is None:
+        which_derivatives = object.get("which.derivatives")
+    if which_derivatives is None:
+        which = list(range(1, p + 1))
+    else:
+        which = [int(i) for i in np.atleast_1d(which_derivatives)]
+        if not which or not all(1 <= i <= p for i in which):
+            raise ValueError("which.derivatives must index columns of X")
+    isbin = np.array([np.unique(Xh[:, j]).size == 2 for j in range(p)])          # the fit's rule (R/bigKRLS.R:242)
+    for j in sorted(set(i - 1 for i in which)):
+        if isbin[j]:
+            lo, hi = Xh[:, j].min(), Xh[:, j].max()
+            if not np.all((nd[:, j] == lo) | (nd[:, j] == hi)):
+                raise ValueError(f"newdata column {j + 1} is binary in the training data; its values must be "
+                                 f"one of the two training values ({lo:g}, {hi:g})")
+    groups, labels = _group_labels(by, nd, bins)
+    G, nj = len(groups), len(which)
+    if G < 1:
+        raise ValueError("by gives no group")
+    if reference is None:
+        ref = 0
+    else:
+        hits = [i for i, g in enumerate(groups)
+                if np.shape(g) == np.shape(reference) and bool(np.all(np.asarray(g) == np.asarray(reference)))]
+        if not hits:
+            raise ValueError(f"reference {reference!r} is not one of the groups {groups!r}")
+        ref = hits[0]
+    if G * nj > 4096:
+        raise ValueError(f"{G} groups x {nj} columns = {G * nj} average effects: the covariance is (G |J|)^2 doubles on "
+                         "the host and G |J| may be at most 4096; use fewer groups (bins=) or which_derivatives")
+    ctx = ctx or object.get("_ctx") or default_context()
+    V = object.get("vcov.est.c") if form == "dense" else None
+    Vd = None if V is None else (V if is_device_matrix(V) else ctx.from_numpy(np.asarray(V, dtype=np.float64)))
+    Qd, wv = _factors(object, ctx) if form == "factors" else (None, None)
+    yv = np.ascontiguousarray(np.asarray(object["y"], dtype=np.float64).ravel())
+    coeffs = np.ascontiguousarray(np.asarray(object["coeffs"], dtype=np.float64).ravel())
+    which_arr = np.ascontiguousarray(which, dtype=np.int64)
+    D = np.empty((u, nj), dtype=np.float64, order="F")
+    ame = np.empty((G, nj), dtype=np.float64, order="F")
+    cov = np.empty((G * nj, G * nj), dtype=np.float64, order="F") if form is not None else None
+    _call_native("bigkrls_group_effects", ctx.handle, Xh.ctypes.data, n, p, yv.ctypes.data, coeffs.ctypes.data,
+                 float(object["sigma"]), which_arr.ctypes.data, nj, nd.ctypes.data, u, labels.ctypes.data, G,
+                 Vd.ptr if form == "dense" else None, Qd.ptr if form == "factors" else None,
+                 Qd.ld if form == "factors" else 0, Qd.ncol if form == "factors" else 0,
+                 wv.ctypes.data if form == "factors" else None, D.ctypes.data, ame.ctypes.data,
+                 cov.ctypes.data if cov is not None else None)
+    diff = ame - ame[ref:ref + 1, :]
+    se_ame = se_diff = wald = None
+    if cov is not None:
+        se_ame = np.sqrt(np.maximum(np.diag(cov), 0.0)).reshape(nj, G).T
+        se_diff = np.zeros((G, nj))
+        stats, dfs, ps = np.zeros(nj), np.zeros(nj, dtype=np.int64), np.full(nj, np.nan)
+        for jj in range(nj):
+            Sj = cov[jj * G:(jj + 1) * G, jj * G:(jj + 1) * G]
+            se_diff[:, jj] = np.sqrt(np.maximum(np.diag(Sj) + Sj[ref, ref] - 2.0 * Sj[:, ref], 0.0))
+            se_diff[ref, jj] = 0.0
+            stats[jj], dfs[jj], ps[jj] = _wald(ame[:, jj], Sj, ref)
+        wald = {"statistic": stats, "df": dfs, "p": ps}
+    xlabs = list(object.get("xlabs") or [f"x{i + 1}" for i in range(p)])
+    return {"groups": groups, "n": np.bincount(labels, minlength=G), "ame": ame, "se.ame": se_ame, "vcov.ame": cov,
+            "diff": diff, "se.diff": se_diff, "wald": wald, "reference": groups[ref], "derivatives": D,
+            "which.derivatives": which, "binaryindicator": isbin[which_arr - 1],
+            "xlabs": [xlabs[i - 1] for i in which], "newdata": nd_init}
 
 
 def _run_folds(jobs, contexts, fit_fn, predict_fn):

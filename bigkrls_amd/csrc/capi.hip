@@ -377,6 +377,8 @@ int bigkrls_ctx_destroy(bigkrls_ctx* ctx) {
   if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
   if (ctx->h_plan) (void)hipHostFree(ctx->h_plan);
+  if (ctx->h_kcg) (void)hipHostFree(ctx->h_kcg);
+  if (ctx->ev_kcg) (void)hipEventDestroy(ctx->ev_kcg);
   for (hipEvent_t e : ctx->prof_pool) (void)hipEventDestroy(e);
   if (ctx->side_stream && !ctx->side_is_main) (void)hipStreamDestroy(ctx->side_stream);
   if (ctx->bg_stream && !ctx->side_is_main) (void)hipStreamDestroy(ctx->bg_stream);
@@ -522,6 +524,13 @@ int bigkrls_dev_kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, in
                                 int64_t ldw, int trans, double* out, int64_t ldo) {
   BK_TRY(check_ctx(ctx));
   return kernel_contract(ctx, A, u, lda, B, v, ldb, p, sigma, W, q, ldw, trans, out, ldo);
+}
+
+int bigkrls_dev_kernel_contract_grouped(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B,
+                                        int64_t v, int64_t ldb, int64_t p, double sigma, const double* W, int64_t q,
+                                        int64_t ldw, const int64_t* h_group, int64_t G, double* out, int64_t ldo) {
+  BK_TRY(check_ctx(ctx));
+  return kernel_contract_grouped(ctx, A, u, lda, B, v, ldb, p, sigma, W, q, ldw, h_group, G, out, ldo);
 }
 
 int bigkrls_dev_kernel_loo_colsums(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B,

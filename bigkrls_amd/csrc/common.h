@@ -66,7 +66,7 @@ struct bigkrls_ctx {
   bool side_is_main = false;   // BIGKRLS_NO_SIDE (diagnostics): side_stream is the main stream itself
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_pq = nullptr;
   // workspace slots: slot i is grown on demand and reused across calls
-  static constexpr int kSlots = 60;
+  static constexpr int kSlots = 62;
   void* ws[kSlots] = {nullptr};
   int64_t ws_bytes[kSlots] = {0};
   // pinned host scratch for small scalar read-backs
@@ -81,6 +81,11 @@ struct bigkrls_ctx {
   // ... and the small pinned buffer the group table of the stage-1 back-transform's precompute is uploaded from
   char* h_plan = nullptr;
   int64_t h_plan_bytes = 0;
+  // ... and the one the tables of kernel_contract_grouped (csrc/gemm.hip) are uploaded from, with the event recorded behind
+  // the upload: the next call waits for that event, not for the stream, before it overwrites the buffer
+  char* h_kcg = nullptr;
+  int64_t h_kcg_bytes = 0;
+  hipEvent_t ev_kcg = nullptr;
   // optional HIP-event sampling of named kernels (bench.py roofline numbers)
   bool profile = false;
   struct ProfSample { hipEvent_t e0, e1; double work; };
@@ -214,6 +219,8 @@ enum Slot {
   SLOT_RV_SMALL = 57,      // bigkrls_vcov_robust: g, d g, residuals, leverages, omega, M, S, U, theta, the cluster scores
   SLOT_CS_PART = 58,       // cluster_scores: the sums of the pieces of clusters that span several 64-row chunks
   SLOT_CS_INDEX = 59,      // ... the sort permutation, the rows' pieces, the pieces' destinations, the multi-piece clusters
+  SLOT_KCG_PART = 60,      // kernel_contract_grouped: partial sums of the groups that are cut into several segments
+  SLOT_KCG_GATHER = 61,    // ... the segment table, the sort permutation and the copies of A's rows, their norms and W in group order
 };
 
 // BIGKRLS_VERBOSE: progress and timing lines on stderr (read at every call: it may be switched while the process runs)
@@ -315,6 +322,19 @@ int kernel_block_centred(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t l
 int kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
                     int64_t ldb, int64_t p, double sigma, const double* W, int64_t q, int64_t ldw, int trans,
                     double* out, int64_t ldo);
+
+// out (v x G q, ldo): columns [g q, (g + 1) q) = K(A[rows with h_group == g], B)' W[those rows], all groups in one launch
+// (the rows of B stationary, a group's rows of A the loop: kernel_contract's trans = 1 per group). h_group: u host labels
+// in [0, G), any order. K is kernel_block's kernel, centred by the column means of all of A. Deterministic.
+int kernel_contract_grouped(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
+                            int64_t ldb, int64_t p, double sigma, const double* W, int64_t q, int64_t ldw,
+                            const int64_t* h_group, int64_t G, double* out, int64_t ldo);
+// ... for operands that are already centred and come with their squared row norms (kernel_contract_centred's contract):
+// S the stationary rows (v x p, lds), L the loop rows (u x p, ldl) with the labels, W u x q
+int kernel_contract_grouped_centred(bigkrls_ctx* ctx, const double* S, int64_t v, int64_t lds, const double* nrm_s,
+                                    const double* L, int64_t u, int64_t ldl, const double* nrm_l, int64_t p, double sigma,
+                                    const double* W, int64_t q, int64_t ldw, const int64_t* h_group, int64_t G,
+                                    double* out, int64_t ldo);
 
 // out (v x n_cols, ldo): out[l, jj] = sum_i exp(-(||A_i - B_l||^2 - (A[i,c] - B[l,c])^2) / sigma), c = h_cols[jj] (host,
 // 0-based): the column sums of K(A, B) with column c left out of the distance, all selected columns in one fused pass

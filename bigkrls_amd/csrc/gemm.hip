@@ -22,6 +22,7 @@
 // dimension of C and every 16 lanes store one 128-byte segment.
 #include "common.h"
 #include <algorithm>
+#include <cstring>
 
 namespace bk {
 
@@ -2719,6 +2720,400 @@ int kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, c
   if (trans)
     return kernel_contract_centred(ctx, co.B, v, co.ldb, co.nb, co.A, u, co.lda, co.na, p, sigma, W, q, ldw, out, ldo);
   return kernel_contract_centred(ctx, co.A, u, co.lda, co.na, co.B, v, co.ldb, co.nb, p, sigma, W, q, ldw, out, ldo);
+}
+
+// ---------------------------------------------------------------------------
+// grouped fused kernel contraction (group effects, csrc/grpeff.hip)
+// ---------------------------------------------------------------------------
+// out[:, g q .. (g + 1) q) = K(S, L[rows of group g])  W[rows of group g] for all groups in ONE launch: the loop rows come
+// sorted by group, and a device-side table cuts them into segments (l_begin, l_end, group, partial slot). The frame is
+// kernel_contract_kernel's, registers included -- 64 stationary rows per wave, 16 loop rows per step, MFMA /
+// exp_nonpos_tab / MFMA --; what differs is the task, (stationary tile, column chunk, segment) in place of (tile, chunk,
+// split), and the loop tiles, which start at l_begin (not at a multiple of 16) and are masked by l < l_end (not by NL).
+// A segment that is a whole group stores into out; the segments of a longer group store into their slots of `part`
+// (each NS x Q, ld NS) and contract_grouped_reduce_kernel adds them in segment order.
+struct KcgSeg {
+  int l_begin, l_end, group, slot;   // slot < 0: the group's only segment
+};
+
+template <int KS, int CT>
+__global__ __launch_bounds__(NT) void kernel_contract_grouped_kernel(
+    const double* __restrict__ S, int64_t lds, int NS, const double* __restrict__ L, int64_t ldl, int P,
+    const double* __restrict__ nrm_s, const double* __restrict__ nrm_l, double neg_inv_sigma,
+    const double* __restrict__ W, int64_t ldw, int Q, double* __restrict__ out, int64_t ldo, double* __restrict__ part,
+    const KcgSeg* __restrict__ segs, int stiles, int nchunks, int64_t ntasks) {
+  __shared__ double etab[32];
+  if (threadIdx.x < 32) etab[threadIdx.x] = kExp2Tab32[threadIdx.x];
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w >= ntasks) return;
+  const int st = (int)(w % stiles);
+  const int cc = (int)((w / stiles) % nchunks);
+  const KcgSeg sg = segs[w / ((int64_t)stiles * nchunks)];
+  const int s0 = st * 16 * KC_MS, c0 = cc * 16 * CT;
+  const int l_end = sg.l_end, l_last = sg.l_end - 1;
+  const int lm = lane & 15, lk = lane >> 4;
+  const int steps = (P + 3) / 4;
+
+  int srow[KC_MS];
+  double ns[KC_MS];
+#pragma unroll
+  for (int m = 0; m < KC_MS; ++m) {
+    srow[m] = min(s0 + 16 * m + lm, NS - 1);
+    ns[m] = nrm_s[srow[m]];
+  }
+  // stationary fragments (k >= P zeroed: the loop side then reads a clamped, finite value)
+  double sf[KC_MS][KS > 0 ? KS : 1];
+  if (KS > 0) {
+#pragma unroll
+    for (int m = 0; m < KC_MS; ++m)
+#pragma unroll
+      for (int t = 0; t < (KS > 0 ? KS : 1); ++t) {
+        const int k = 4 * t + lk;
+        sf[m][t] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
+      }
+  }
+  d4 acc[KC_MS][CT];
+#pragma unroll
+  for (int m = 0; m < KC_MS; ++m)
+#pragma unroll
+    for (int c = 0; c < CT; ++c) acc[m][c] = (d4){0.0, 0.0, 0.0, 0.0};
+
+  for (int l0 = sg.l_begin; l0 < l_end; l0 += 16) {
+    const int lrow = min(l0 + lm, l_last);   // this lane's row of the L operand (clamped inside the segment)
+    double nl[4], wf[CT][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int l = l0 + lk + 4 * r;         // this lane's loop row in accumulator register r
+      nl[r] = nrm_l[min(l, l_last)];
+#pragma unroll
+      for (int c = 0; c < CT; ++c) {
+        const int col = c0 + 16 * c + lm;
+        wf[c][r] = (l < l_end && col < Q) ? W[l + (int64_t)col * ldw] : 0.0;
+      }
+    }
+    d4 g[KC_MS];
+#pragma unroll
+    for (int m = 0; m < KC_MS; ++m) g[m] = (d4){0.0, 0.0, 0.0, 0.0};
+    if (KS > 0) {
+      double lf[KS > 0 ? KS : 1];
+#pragma unroll
+      for (int s = 0; s < (KS > 0 ? KS : 1); ++s) lf[s] = L[lrow + (int64_t)min(4 * s + lk, P - 1) * ldl];
+#pragma unroll
+      for (int s = 0; s < (KS > 0 ? KS : 1); ++s)
+#pragma unroll
+        for (int m = 0; m < KC_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sf[m][s], g[m], 0, 0, 0);
+    } else {
+      for (int s0k = 0; s0k < steps; s0k += 4) {
+        double lf[4], sgf[KC_MS][4];
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const int k = 4 * (s0k + s) + lk;
+          lf[s] = L[lrow + (int64_t)min(k, P - 1) * ldl];
+#pragma unroll
+          for (int m = 0; m < KC_MS; ++m) sgf[m][s] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+          for (int m = 0; m < KC_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sgf[m][s], g[m], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < KC_MS; ++m) {
+      d4 e;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        double d2 = fma(-2.0, g[m][r], ns[m] + nl[r]);   // (kernel_block_wave_kernel's epilogue)
+        d2 = fmax(d2, 0.0);
+        e[r] = exp_nonpos_tab(d2 * neg_inv_sigma, etab);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < CT; ++c) acc[m][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(e[r], wf[c][r], acc[m][c], 0, 0, 0);
+    }
+  }
+  // acc[m][c] register r: (s = s0 + 16 m + (lane >> 4) + 4 r, col = c0 + 16 c + (lane & 15))
+  double* dst = sg.slot < 0 ? out + (int64_t)sg.group * Q * ldo : part + (int64_t)sg.slot * NS * Q;
+  const int64_t ldd = sg.slot < 0 ? ldo : (int64_t)NS;
+#pragma unroll
+  for (int m = 0; m < KC_MS; ++m)
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+      const int col = c0 + 16 * c + lm;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int s = s0 + 16 * m + lk + 4 * r;
+        if (s < NS && col < Q) dst[s + (int64_t)col * ldd] = acc[m][c][r];
+      }
+    }
+}
+
+// the groups of several segments, and the empty ones (count 0): multi[3 i ..] = (group, first slot, segments);
+// out[:, group's columns] = the sum of the group's slots in segment order (blockIdx.y strides over the entries)
+__global__ void contract_grouped_reduce_kernel(int NS, int Q, int nmulti, const int* __restrict__ multi,
+                                               const double* __restrict__ part, double* __restrict__ out, int64_t ldo) {
+  const int64_t total = (int64_t)NS * Q;
+  for (int i = blockIdx.y; i < nmulti; i += gridDim.y) {
+    const int g = multi[3 * i], first = multi[3 * i + 1], cnt = multi[3 * i + 2];
+    const double* p0 = part + (int64_t)first * total;
+    double* o = out + (int64_t)g * Q * ldo;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+      double s = 0.0;
+      for (int k = 0; k < cnt; ++k) s += p0[(int64_t)k * total + e];
+      o[(e % NS) + (e / NS) * ldo] = s;
+    }
+  }
+}
+
+// A table of at most KCG_INLINE_SEGS segments and KCG_INLINE_MULTI multi-segment (or empty) groups travels as a kernel
+// argument and is stored by this kernel: a host-to-device copy of a few hundred bytes costs more on the stream (20 to
+// 50 us between the centring kernels and the pass) than the launch does.
+constexpr int KCG_INLINE_SEGS = 160, KCG_INLINE_MULTI = 32;
+struct KcgInline {
+  KcgSeg s[KCG_INLINE_SEGS];
+  int m[3 * KCG_INLINE_MULTI];
+};
+__global__ void contract_table_kernel(KcgInline t, int nseg, int nm3, KcgSeg* __restrict__ segs, int* __restrict__ multi) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nseg) segs[i] = t.s[i];
+  if (i < nm3) multi[i] = t.m[i];
+}
+
+// the loop rows in group order: Lg[r, :] = L[perm[r], :], ng[r] = nrm[perm[r]], Wg[r, :] = W[perm[r], :]
+__global__ void contract_gather_kernel(int U, int P, int Q, const int* __restrict__ perm, const double* __restrict__ L,
+                                       int64_t ldl, const double* __restrict__ nrm, const double* __restrict__ W,
+                                       int64_t ldw, double* __restrict__ Lg, double* __restrict__ ng,
+                                       double* __restrict__ Wg) {
+  const int64_t total = (int64_t)U * (P + Q + 1);
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int r = (int)(e % U);
+    const int c = (int)(e / U);
+    const int src = perm[r];
+    if (c < P) Lg[r + (int64_t)c * U] = L[src + (int64_t)c * ldl];
+    else if (c < P + Q) Wg[r + (int64_t)(c - P) * U] = W[src + (int64_t)(c - P) * ldw];
+    else ng[r] = nrm[src];
+  }
+}
+
+// For operands that are already centred and come with their squared row norms (kernel_contract_centred's contract): S the
+// stationary rows (v x p, lds), L the loop rows (u x p, ldl) with the labels h_group, W u x q.
+int kernel_contract_grouped_centred(bigkrls_ctx* ctx, const double* S, int64_t v, int64_t lds, const double* nrm_s,
+                                    const double* L, int64_t u, int64_t ldl, const double* nrm_l, int64_t p, double sigma,
+                                    const double* W, int64_t q, int64_t ldw, const int64_t* h_group, int64_t G,
+                                    double* out, int64_t ldo) {
+  BK_REQUIRE(u > 0 && v > 0 && p > 0 && q > 0, "kernel_contract_grouped: bad dimensions");
+  BK_REQUIRE(u < (1ll << 31) && v < (1ll << 31) && p < (1ll << 20) && q < (1ll << 20), "kernel_contract_grouped: too large");
+  BK_REQUIRE(sigma > 0.0, "kernel_contract_grouped: sigma must be > 0");
+  BK_REQUIRE(S && L && nrm_s && nrm_l && W && out && h_group, "kernel_contract_grouped: null pointer");
+  BK_REQUIRE(lds >= v && ldl >= u && ldw >= u && ldo >= v, "kernel_contract_grouped: leading dimension too small");
+  BK_REQUIRE(G * q < (1ll << 31) && v * q < (1ll << 40), "kernel_contract_grouped: out too large");
+  BK_REQUIRE(G >= 1, "kernel_contract_grouped: G must be at least 1: the label of row 1 is outside [0, G)");
+  hipStream_t st = ctx->stream;
+
+  // ---- stable counting sort (cluster_scores' rule): the rows of one group in their original order -------------------
+  // Rows that are already grouped (labels that never decrease) are recognised first, in a pass without the counters'
+  // store-to-load chains: their offsets are the places where the label changes and nothing is permuted. (The host works
+  // while the device centres the operands; at u = 20 000 the counting passes take longer than that and would show.)
+  std::vector<int64_t> off((size_t)G + 1, 0);
+  std::vector<int32_t> perm;
+  bool identity = h_group[0] >= 0 && h_group[u - 1] < G;
+  {
+    int64_t decreases = 0;
+    for (int64_t i = 1; i < u; ++i) decreases += h_group[i] < h_group[i - 1];
+    identity = identity && decreases == 0;
+  }
+  if (identity) {
+    int64_t prev = -1;
+    for (int64_t i = 0; i < u; ++i) {
+      const int64_t g = h_group[i];
+      if (g == prev) continue;
+      for (int64_t gg = prev + 1; gg <= g; ++gg) off[(size_t)gg] = i;
+      prev = g;
+    }
+    for (int64_t gg = prev + 1; gg <= G; ++gg) off[(size_t)gg] = u;
+  } else {
+    for (int64_t i = 0; i < u; ++i) {
+      BK_REQUIRE(h_group[i] >= 0 && h_group[i] < G, "kernel_contract_grouped: the label of row " + std::to_string(i + 1) +
+                                                        " is outside [0, G)");
+      ++off[(size_t)h_group[i] + 1];
+    }
+    for (int64_t g = 0; g < G; ++g) off[(size_t)g + 1] += off[(size_t)g];
+    perm.resize((size_t)u);
+    std::vector<int64_t> pos(off.begin(), off.end() - 1);
+    for (int64_t i = 0; i < u; ++i) perm[(size_t)(pos[(size_t)h_group[i]]++)] = (int32_t)i;
+  }
+
+  // ---- the kernel ---------------------------------------------------------------------------------------------------
+  const int CT = q <= 16 ? 1 : (q <= 32 ? 2 : 4);
+  const int steps = (int)((p + 3) / 4);
+  const int ks = steps <= 8 ? steps : 0;
+  using KcgFn = void (*)(const double*, int64_t, int, const double*, int64_t, int, const double*, const double*, double,
+                         const double*, int64_t, int, double*, int64_t, double*, const KcgSeg*, int, int, int64_t);
+  KcgFn fn = nullptr;
+#define BK_KCG(CTV)                                                                                                   \
+  switch (ks) {                                                                                                       \
+    case 1: fn = kernel_contract_grouped_kernel<1, CTV>; break;                                                       \
+    case 2: fn = kernel_contract_grouped_kernel<2, CTV>; break;                                                       \
+    case 3: fn = kernel_contract_grouped_kernel<3, CTV>; break;                                                       \
+    case 4: fn = kernel_contract_grouped_kernel<4, CTV>; break;                                                       \
+    case 5: fn = kernel_contract_grouped_kernel<5, CTV>; break;                                                       \
+    case 6: fn = kernel_contract_grouped_kernel<6, CTV>; break;                                                       \
+    case 7: fn = kernel_contract_grouped_kernel<7, CTV>; break;                                                       \
+    case 8: fn = kernel_contract_grouped_kernel<8, CTV>; break;                                                       \
+    default: fn = kernel_contract_grouped_kernel<0, CTV>; break;                                                      \
+  }
+  if (CT == 1) { BK_KCG(1) }
+  else if (CT == 2) { BK_KCG(2) }
+  else { BK_KCG(4) }
+#undef BK_KCG
+  const int64_t stiles = (v + 16 * KC_MS - 1) / (16 * KC_MS);
+  const int64_t nchunks = (q + 16 * CT - 1) / (16 * CT);
+
+  // ---- the segments ---------------------------------------------------------------------------------------------------
+  // kernel_contract_centred's model over all groups together: the time is about (rounds of resident waves) x (loop tiles
+  // of the longest part). A candidate s cuts the largest group (lt_max loop tiles) into s equal parts and every group
+  // into parts of about that length, s_g = ceil(lt_g s / lt_max), each part at least 16 loop tiles (s_g <= lt_g / 16) and
+  // at most 64 parts per group; the slots of the groups with s_g > 1 hold at most 64 MB; s minimises
+  // ceil(base sum_g s_g / slots) / s, fewer parts on a tie (a gain below 2 % does not count). With G = 1 this is
+  // kernel_contract_centred's split rule, cuts included: part k of a group is its loop tiles [lt k / s, lt (k + 1) / s).
+  int cap = 0;
+  BK_TRY(resident_capacity(ctx, (const void*)fn, &cap, NT));
+  const int64_t slots = (int64_t)cap * (NT / 64);
+  const int64_t base = stiles * nchunks;
+  const int64_t slot_cap = (64ll << 20) / (v * q * (int64_t)sizeof(double));
+  int64_t lt_max = 0, nonempty = 0;
+  for (int64_t g = 0; g < G; ++g) {
+    const int64_t ng = off[(size_t)g + 1] - off[(size_t)g];
+    lt_max = std::max(lt_max, (ng + 15) / 16);
+    nonempty += ng > 0;
+  }
+  auto parts_of = [&](int64_t g, int64_t s) {
+    const int64_t lt = (off[(size_t)g + 1] - off[(size_t)g] + 15) / 16;
+    const int64_t most = std::max<int64_t>(1, std::min<int64_t>(64, lt / 16));
+    return std::min(most, std::max<int64_t>(1, (lt * s + lt_max - 1) / lt_max));
+  };
+  const int64_t max_split = std::max<int64_t>(1, std::min<int64_t>(64, lt_max / 16));
+  int64_t nsplit = 1;
+  double best = (double)((base * nonempty + slots - 1) / slots);
+  for (int64_t s = 2; s <= max_split; ++s) {
+    int64_t nseg = 0, nslots = 0;
+    for (int64_t g = 0; g < G; ++g) {
+      if (off[(size_t)g + 1] == off[(size_t)g]) continue;
+      const int64_t sg = parts_of(g, s);
+      nseg += sg;
+      if (sg > 1) nslots += sg;
+    }
+    if (nslots > slot_cap) break;   // (the slots grow with s)
+    const double cost = (double)((base * nseg + slots - 1) / slots) / (double)s;
+    if (cost < best * 0.98) { best = cost; nsplit = s; }
+  }
+  std::vector<KcgSeg> segs;
+  std::vector<int32_t> multi;   // (group, first slot, segments) of the groups that are not one segment
+  int64_t nslots = 0;
+  for (int64_t g = 0; g < G; ++g) {
+    const int64_t b = off[(size_t)g], t = off[(size_t)g + 1];
+    if (b == t) {
+      multi.insert(multi.end(), {(int32_t)g, 0, 0});
+      continue;
+    }
+    const int64_t lt = (t - b + 15) / 16, sg = parts_of(g, nsplit);
+    if (sg > 1) multi.insert(multi.end(), {(int32_t)g, (int32_t)nslots, (int32_t)sg});
+    for (int64_t k = 0; k < sg; ++k) {
+      const int64_t t0 = lt * k / sg, t1 = lt * (k + 1) / sg;
+      segs.push_back(KcgSeg{(int)(b + 16 * t0), (int)std::min(b + 16 * t1, t), (int)g, sg > 1 ? (int)nslots++ : -1});
+    }
+  }
+  const int64_t nseg = (int64_t)segs.size(), nmulti = (int64_t)multi.size() / 3;
+  const int64_t ntasks = base * nseg;
+  BK_REQUIRE((ntasks + 3) / 4 < (1ll << 31), "kernel_contract_grouped: too many tiles");
+
+  // ---- the table, the permutation and the gathered rows ---------------------------------------------------------------------
+  const int64_t b_seg = nseg * (int64_t)sizeof(KcgSeg), b_mu = (nmulti * 12 + 15) / 16 * 16;
+  const int64_t b_perm = identity ? 0 : (u * 4 + 15) / 16 * 16, b_idx = b_seg + b_mu + b_perm;
+  const int64_t gather_doubles = identity ? 0 : u * (p + q + 1);
+  void* pg = nullptr;
+  void* ppart = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_KCG_GATHER, b_idx + gather_doubles * (int64_t)sizeof(double) + 64, &pg));
+  BK_TRY(ws_get(ctx, SLOT_KCG_PART, std::max<int64_t>(nslots, 1) * v * q * (int64_t)sizeof(double), &ppart));
+  char* dbase = (char*)pg;
+  const KcgSeg* d_segs = (const KcgSeg*)dbase;
+  const int* d_multi = (const int*)(dbase + b_seg);
+  const int* d_perm = (const int*)(dbase + b_seg + b_mu);
+  double* dLg = (double*)(dbase + b_idx);
+  double* dng = dLg + u * p;
+  double* dWg = dng + u;
+  const bool inline_table = nseg <= KCG_INLINE_SEGS && nmulti <= KCG_INLINE_MULTI;
+  if (inline_table) {
+    KcgInline t;
+    std::memcpy(t.s, segs.data(), (size_t)b_seg);
+    if (nmulti > 0) std::memcpy(t.m, multi.data(), (size_t)nmulti * 12);
+    hipLaunchKernelGGL(contract_table_kernel, dim3(1), dim3(256), 0, st, t, (int)nseg, (int)(3 * nmulti),
+                       (KcgSeg*)dbase, (int*)(dbase + b_seg));
+    BK_CHECK_LAUNCH();
+  }
+  if (!inline_table || !identity) {
+    // a pinned buffer of this function's own, guarded by an event behind the upload: waiting for the STREAM here (the
+    // context's shared pinned buffer would need it) leaves the device idle between the centring kernels and the pass,
+    // 4 % of the whole call at u = v = 20 000
+    if (ctx->ev_kcg) BK_HIP(hipEventSynchronize(ctx->ev_kcg));   // (the previous call's upload has left the buffer)
+    else BK_HIP(hipEventCreateWithFlags(&ctx->ev_kcg, hipEventDisableTiming));
+    if (ctx->h_kcg_bytes < b_idx) {
+      if (ctx->h_kcg) BK_HIP(hipHostFree(ctx->h_kcg));
+      ctx->h_kcg = nullptr;
+      ctx->h_kcg_bytes = 0;
+      BK_HIP(hipHostMalloc((void**)&ctx->h_kcg, (size_t)b_idx + 4096, hipHostMallocDefault));
+      ctx->h_kcg_bytes = b_idx + 4096;
+    }
+    char* hb = ctx->h_kcg;
+    const int64_t from = inline_table ? b_seg + b_mu : 0;      // (the table is already there: the permutation alone)
+    if (!inline_table) {
+      std::memcpy(hb, segs.data(), (size_t)b_seg);
+      if (nmulti > 0) std::memcpy(hb + b_seg, multi.data(), (size_t)nmulti * 12);
+    }
+    if (!identity) std::memcpy(hb + b_seg + b_mu, perm.data(), (size_t)u * 4);
+    BK_HIP(hipMemcpyAsync(dbase + from, hb + from, (size_t)(b_idx - from), hipMemcpyHostToDevice, st));
+    BK_HIP(hipEventRecord(ctx->ev_kcg, st));
+  }
+  const double *Lp = L, *nlp = nrm_l, *Wp = W;
+  int64_t ldlp = ldl, ldwp = ldw;
+  BK_TRY(prof_begin(ctx, "kernel_contract_grouped", 2.0 * (double)u * (double)v * (double)(p + q)));
+  if (!identity) {
+    const int blocks = (int)std::min<int64_t>((u * (p + q + 1) + 255) / 256, 8192);
+    hipLaunchKernelGGL(contract_gather_kernel, dim3(blocks), dim3(256), 0, st, (int)u, (int)p, (int)q, d_perm, L, ldl, nrm_l,
+                       W, ldw, dLg, dng, dWg);
+    BK_CHECK_LAUNCH();
+    Lp = dLg; nlp = dng; Wp = dWg;
+    ldlp = u; ldwp = u;
+  }
+  hipLaunchKernelGGL(fn, dim3((unsigned)((ntasks + 3) / 4)), dim3(NT), 0, st, S, lds, (int)v, Lp, ldlp, (int)p, nrm_s,
+                     nlp, -1.0 / sigma, Wp, ldwp, (int)q, out, ldo, (double*)ppart, d_segs, (int)stiles, (int)nchunks,
+                     ntasks);
+  BK_CHECK_LAUNCH();
+  if (nmulti > 0) {
+    const dim3 grid((unsigned)std::min<int64_t>((v * q + 255) / 256, 1024), (unsigned)std::min<int64_t>(nmulti, 1024));
+    hipLaunchKernelGGL(contract_grouped_reduce_kernel, grid, dim3(256), 0, st, (int)v, (int)q, (int)nmulti, d_multi,
+                       (const double*)ppart, out, ldo);
+    BK_CHECK_LAUNCH();
+  }
+  BK_TRY(prof_end(ctx, "kernel_contract_grouped"));
+  return BIGKRLS_OK;
+}
+
+int kernel_contract_grouped(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
+                            int64_t ldb, int64_t p, double sigma, const double* W, int64_t q, int64_t ldw,
+                            const int64_t* h_group, int64_t G, double* out, int64_t ldo) {
+  BK_REQUIRE(u > 0 && v > 0 && p > 0 && q > 0, "kernel_contract_grouped: bad dimensions");
+  BK_REQUIRE(u < (1ll << 31) && v < (1ll << 31) && p < (1ll << 20) && q < (1ll << 20), "kernel_contract_grouped: too large");
+  BK_REQUIRE(A && B && W && out && h_group, "kernel_contract_grouped: null pointer");
+  BK_REQUIRE(lda >= u && ldb >= v, "kernel_contract_grouped: leading dimension of A or B too small");
+  // (the labels are checked by the centred entry, on the host while the device centres the operands)
+  CentredOperands co;     // both operands moved by the column means of A (see centre_operands)
+  BK_TRY(centre_operands(ctx, A, u, lda, B, v, ldb, p, &co));
+  return kernel_contract_grouped_centred(ctx, co.B, v, co.ldb, co.nb, co.A, u, co.lda, co.na, p, sigma, W, q, ldw, h_group,
+                                         G, out, ldo);
 }
 
 // ---------------------------------------------------------------------------

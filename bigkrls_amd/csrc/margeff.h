@@ -1,7 +1,8 @@
 // What the post-estimation entries on the modulation m_j(i,l) = r_j[i] + t_j[i] s_j[l] share (csrc/margeff.hip: the
 // marginal effects and their standard errors; csrc/inteff.hip: the interaction effects): the per-column constants, the
-// r / t / s kernels, the column dots, the argument checks and the host-side preparation. Internal and header-only: every
-// user compiles it inside its own translation unit (anonymous namespace), nothing here joins the exported symbols.
+// row- and column-side finalise of the two contractions (also csrc/grpeff.hip: the group effects), the r / t / s
+// kernels, the column dots, the argument checks and the host-side preparation. Internal and header-only: every user
+// compiles it inside its own translation unit (anonymous namespace), nothing here joins the exported symbols.
 #pragma once
 #include "hostprep.h"
 
@@ -68,6 +69,65 @@ __global__ void me_se_rt_kernel(int rows, int nj, const double* __restrict__ Zs,
     }
     R[e] = r;
     T[e] = t;
+  }
+}
+
+// D (u x nj, ld u): row side. R (u x q, ld u) = Kn B, Zs (u x p, ld u), Bs (u x q) = B* (its binary columns are the
+// newdata group indicators h_j).
+__global__ void me_rows_kernel(int u, int nj, const double* __restrict__ R, const double* __restrict__ Zs,
+                               const double* __restrict__ Bs, const MeCol* __restrict__ cols, double sigma,
+                               double* __restrict__ D) {
+  const int64_t total = (int64_t)u * nj;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int i = (int)(e % u);
+    const int jj = (int)(e / u);
+    const MeCol cj = cols[jj];
+    const double Kc = R[i];
+    const double Kvc = R[(int64_t)(1 + jj) * u + i];
+    double dv;
+    if (cj.bin == 0.0) {
+      const double z = Zs[i + (int64_t)cj.col * u];
+      dv = (-2.0 / sigma) * (z * Kc - Kvc);
+    } else {
+      const double sd = 1.0 / (cj.z1 - cj.z0);
+      const double phi = -1.0 / (sd * sd * sigma);
+      const double E = exp(phi), Einv = exp(-phi);
+      const bool hi = Bs[(int64_t)(1 + jj) * u + i] != 0.0;
+      const double Sc = hi ? Kvc : Kc - Kvc;     // over the training rows of the point's own group
+      const double Oc = hi ? Kc - Kvc : Kvc;     // ... and of the other one
+      dv = sd * (hi ? 1.0 : -1.0) * ((1.0 - E) * Sc + (1.0 - Einv) * Oc);
+    }
+    D[e] = dv;
+  }
+}
+
+// S: column side. C (n x q, ld n) = Kn' B*, Xs (n x p, ld n). s_k for continuous columns, a_k for binary ones (training
+// group of k: Xs == z1, the fit's own test, csrc/deriv.hip). Column jj is written at S + jj s_col. blockIdx.y is a group
+// of new points (csrc/grpeff.hip): its block of C starts at c_group doubles per group, its columns of S at s_group; one
+// set of new points (csrc/margeff.hip) is gridDim.y = 1, s_col = n.
+__global__ void me_cols_kernel(int n, int nj, const double* __restrict__ Cm, const double* __restrict__ Xs,
+                               const MeCol* __restrict__ cols, double sigma, double* __restrict__ S, int64_t c_group,
+                               int64_t s_col, int64_t s_group) {
+  const int64_t total = (int64_t)n * nj;
+  Cm += (int64_t)blockIdx.y * c_group;
+  S += (int64_t)blockIdx.y * s_group;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int k = (int)(e % n);
+    const int jj = (int)(e / n);
+    const MeCol cj = cols[jj];
+    const double T = Cm[k];                                  // sum_i Kn[i,k]
+    const double H = Cm[(int64_t)(1 + jj) * n + k];          // sum_i Kn[i,k] Zs_ij, or over the new points with h = 1
+    const double x = Xs[k + (int64_t)cj.col * n];
+    double sv;
+    if (cj.bin == 0.0) {
+      sv = H - x * T;
+    } else {
+      const double sd = 1.0 / (cj.z1 - cj.z0);
+      const double phi = -1.0 / (sd * sd * sigma);
+      const double E = exp(phi), Einv = exp(-phi);
+      sv = (x == cj.z1) ? (1.0 - E) * H + (Einv - 1.0) * (T - H) : (1.0 - Einv) * H + (E - 1.0) * (T - H);
+    }
+    S[k + (int64_t)jj * s_col] = sv;
   }
 }
 

@@ -37,60 +37,6 @@
 namespace bk {
 namespace {
 
-// D (u x nj, ld u): row side. R (u x q, ld u) = Kn B, Zs (u x p, ld u), Bs (u x q) = B* (its binary columns are the
-// newdata group indicators h_j).
-__global__ void me_rows_kernel(int u, int nj, const double* __restrict__ R, const double* __restrict__ Zs,
-                               const double* __restrict__ Bs, const MeCol* __restrict__ cols, double sigma,
-                               double* __restrict__ D) {
-  const int64_t total = (int64_t)u * nj;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-    const int i = (int)(e % u);
-    const int jj = (int)(e / u);
-    const MeCol cj = cols[jj];
-    const double Kc = R[i];
-    const double Kvc = R[(int64_t)(1 + jj) * u + i];
-    double dv;
-    if (cj.bin == 0.0) {
-      const double z = Zs[i + (int64_t)cj.col * u];
-      dv = (-2.0 / sigma) * (z * Kc - Kvc);
-    } else {
-      const double sd = 1.0 / (cj.z1 - cj.z0);
-      const double phi = -1.0 / (sd * sd * sigma);
-      const double E = exp(phi), Einv = exp(-phi);
-      const bool hi = Bs[(int64_t)(1 + jj) * u + i] != 0.0;
-      const double Sc = hi ? Kvc : Kc - Kvc;     // over the training rows of the point's own group
-      const double Oc = hi ? Kc - Kvc : Kvc;     // ... and of the other one
-      dv = sd * (hi ? 1.0 : -1.0) * ((1.0 - E) * Sc + (1.0 - Einv) * Oc);
-    }
-    D[e] = dv;
-  }
-}
-
-// S (n x nj, ld n): column side. C (n x q, ld n) = Kn' B*, Xs (n x p, ld n). s_k for continuous columns, a_k for
-// binary ones (training group of k: Xs == z1, the fit's own test, csrc/deriv.hip).
-__global__ void me_cols_kernel(int n, int nj, const double* __restrict__ Cm, const double* __restrict__ Xs,
-                               const MeCol* __restrict__ cols, double sigma, double* __restrict__ S) {
-  const int64_t total = (int64_t)n * nj;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-    const int k = (int)(e % n);
-    const int jj = (int)(e / n);
-    const MeCol cj = cols[jj];
-    const double T = Cm[k];                                  // sum_i Kn[i,k]
-    const double H = Cm[(int64_t)(1 + jj) * n + k];          // sum_i Kn[i,k] Zs_ij, or over the new points with h = 1
-    const double x = Xs[k + (int64_t)cj.col * n];
-    double sv;
-    if (cj.bin == 0.0) {
-      sv = H - x * T;
-    } else {
-      const double sd = 1.0 / (cj.z1 - cj.z0);
-      const double phi = -1.0 / (sd * sd * sigma);
-      const double E = exp(phi), Einv = exp(-phi);
-      sv = (x == cj.z1) ? (1.0 - E) * H + (Einv - 1.0) * (T - H) : (1.0 - Einv) * H + (E - 1.0) * (T - H);
-    }
-    S[e] = sv;
-  }
-}
-
 // ---- pointwise standard errors (s, r and t: me_se_s_kernel, me_se_rt_kernel, margeff.h) ------------------------------
 // G (rows x n, ld rows) = Kn o (r 1' + t s'), the factor as gemm_modulated forms it (dense vcov.est.c only)
 __global__ void me_se_modulate_kernel(int rows, int n, const double* __restrict__ Kn, const double* __restrict__ r,
@@ -184,7 +130,7 @@ int marginal_effects_impl(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_
   BK_CHECK_LAUNCH();
   blocks = (int)std::min<int64_t>((n * nj + 255) / 256, 4096);
   hipLaunchKernelGGL(me_cols_kernel, dim3(blocks), dim3(256), 0, st, (int)n, (int)nj, (const double*)dC,
-                     (const double*)dXs, (const MeCol*)dcols, sigma, dS);
+                     (const double*)dXs, (const MeCol*)dcols, sigma, dS, (int64_t)0, n, (int64_t)0);
   BK_CHECK_LAUNCH();
   if (vc.d_V) {
     BK_TRY(gemm(ctx, 0, 0, n, nj, n, 1.0, vc.d_V, n, dS, n, 0.0, dT, n));          // T = vcov.est.c S

@@ -76,6 +76,28 @@ def bKernelContract(A: DeviceMatrix, B: DeviceMatrix, W: DeviceMatrix, sigma: fl
     return out
 
 
+def bKernelContractGrouped(A: DeviceMatrix, B: DeviceMatrix, W: DeviceMatrix, sigma: float, labels, G: int) -> DeviceMatrix:
+    """out (nrow(B) x G ncol(W)): the block of columns [g q, (g + 1) q) is K(A[labels == g], B)' W[labels == g], i.e.
+    bKernelContract(trans=1) on the rows of every group, all groups in one fused launch; K is bTempKernel(A, B)'s kernel
+    (centred by the column means of all of A). labels: nrow(A) integers in [0, G) in any order; an empty group gives zero
+    columns (bigkrls_dev_kernel_contract_grouped). No counterpart in the reference."""
+    ctx = A.ctx
+    if A.ncol != B.ncol:
+        raise ValueError("bKernelContractGrouped: column counts of A and B differ")
+    if W.nrow != A.nrow:
+        raise ValueError("bKernelContractGrouped: W has the wrong number of rows")
+    lab = np.ascontiguousarray(labels, dtype=np.int64).ravel()
+    if lab.size != A.nrow:
+        raise ValueError(f"bKernelContractGrouped: labels must have {A.nrow} entries")
+    G = int(G)
+    if G < 1:
+        raise ValueError("bKernelContractGrouped: G must be at least 1")
+    out = ctx.empty(B.nrow, G * W.ncol)
+    _lib.call("bigkrls_dev_kernel_contract_grouped", ctx.handle, A.ptr, A.nrow, A.ld, B.ptr, B.nrow, B.ld, A.ncol,
+              float(sigma), W.ptr, W.ncol, W.ld, lab.ctypes.data, G, out.ptr, out.ld)
+    return out
+
+
 def bKernelLooColsums(A: DeviceMatrix, B: DeviceMatrix, sigma: float, cols) -> DeviceMatrix:
     """out (nrow(B) x len(cols)): out[l, jj] = sum_i exp(-(||A_i - B_l||^2 - (A[i,c] - B[l,c])^2) / sigma), c = cols[jj]
     (0-based): the column sums of bTempKernel(A, B) with column c left out of the distance, all selected columns in one

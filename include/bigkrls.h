@@ -212,6 +212,24 @@ int bigkrls_dev_kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, in
                                 const double* B, int64_t v, int64_t ldb, int64_t p, double sigma,
                                 const double* W, int64_t q, int64_t ldw, int trans, double* out, int64_t ldo);
 
+/* Grouped fused kernel contraction: out (v x G q, ldo >= v); the block of columns [g q, (g + 1) q) holds
+ *   K(A[rows with h_group == g], B)' W[those rows],
+ * i.e. what bigkrls_dev_kernel_contract(trans = 1) gives on the rows of one group, for all G groups in ONE launch.
+ * K is exactly bigkrls_dev_kernel_block's kernel: the column means of ALL of A are subtracted from both operands.
+ * A u x p (lda >= u), B v x p (ldb >= v), W u x q (ldw >= u) on the device; h_group (u labels in [0, G), any order) on
+ * the host. The host sorts the labels (stable counting sort; rows that are not already grouped are gathered into a copy
+ * of A and W in group order) and cuts every group into segments of loop rows: equal parts by the cost model of
+ * bigkrls_dev_kernel_contract's split rule (rounds of resident waves x loop tiles per wave, over all groups together),
+ * a part at least 16 loop tiles unless the group is smaller, the partial sums at most 64 MB. A wave takes 64 rows of
+ * B, a chunk of 16 / 32 / 64 columns (any q) and one segment; a group of one segment is written straight into out,
+ * the segments of a longer group are added by a second kernel in segment order: no atomics, the layout depends on the
+ * group sizes only, two calls give bitwise identical results. An empty group gives zero columns. The u x v kernel is
+ * never stored; extra device memory O(u (p + q)) plus the partials. A label outside [0, G) or G < 1 is BIGKRLS_EINVAL
+ * naming the row. Profile name "kernel_contract_grouped", work 2 u v (p + q). */
+int bigkrls_dev_kernel_contract_grouped(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B,
+                                        int64_t v, int64_t ldb, int64_t p, double sigma, const double* W, int64_t q,
+                                        int64_t ldw, const int64_t* h_group, int64_t G, double* out, int64_t ldo);
+
 /* Fused leave-one-column-out column sums: out (v x n_cols, ldo >= v),
  *   out[l, jj] = sum_i exp(-(||A_i - B_l||^2 - (A[i,c] - B[l,c])^2) / sigma),   c = h_cols[jj] (host, 0-based),
  * i.e. the column sums of bigkrls_dev_kernel_block's kernel K(A, B) with column c left out of the distance, for all
@@ -726,6 +744,33 @@ int bigkrls_conditional_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, 
                                 const double* h_newdata, int64_t u, const double* h_grid, const int64_t* h_grid_off,
                                 const double* d_vcov_c, const double* d_Q, int64_t ldq, int64_t k, const double* h_w,
                                 double* h_ce, double* h_se, double* h_cov);
+
+/* Average marginal effects by subgroup with their joint covariance (no counterpart in the reference). X, y, coeffs,
+ * sigma, h_which, newdata and u as in bigkrls_marginal_effects (validation, standardisation, binary columns and error
+ * messages are its own); h_group holds u labels in [0, G) (host, any order; a label outside, or G < 1, is BIGKRLS_EINVAL
+ * naming the row). Outputs, original units:
+ *   h_derivatives (u x |J| column-major; may be NULL): the pointwise effects, bigkrls_marginal_effects',
+ *   h_ame (G x |J| column-major): ame[g, jj] = the mean of column jj of the derivatives over the rows of group g (an
+ *         empty group: NaN),
+ *   h_cov ((G |J|) x (G |J|) column-major, entry index e = jj G + g: the groups of one variable are adjacent): the joint
+ *         covariance of all of them. Written exactly when vcov.est.c is given -- as the n x n matrix (d_vcov_c, ld n)
+ *         or as its factors (d_Q n x k on the device, ldq >= n; h_w the k weights on the host), at most one of the two;
+ *         with neither h_cov must be NULL.
+ * In standardised units ame_e = sd(y) a_e S_e' c, where S_e (n) is bigkrls_marginal_effects' column-side vector s / a of
+ * variable jj over the rows of group g, and a_e = -(2 / sigma) / (n_g sd(x_j)) for a continuous column,
+ * +1 / ((z1 - z0) n_g sd(x_j)) for a binary one. cov[e, f] = a_e a_f S_e' V S_f with V = vcov.est.c (sd(y) cancels), and
+ * a binary entry carries a further sqrt(2) -- the reference's factor 2 on the variance (src/bigderiv_v3.cpp:85), one
+ * square root per side -- so that every diagonal entry is bigkrls_marginal_effects' h_var on the group's rows and the
+ * matrix stays positive semi-definite. The rows and columns of an empty group are zero.
+ * The row side is bigkrls_marginal_effects' (R = Kn B, a per-row finalise); the column side is ONE
+ * bigkrls_dev_kernel_contract_grouped (C_g = K(Z[g], X)' B*[g] for all groups), a finalise into S (n x G |J|), and
+ * M = S' V S: from the factors T = Q' S (bigkrls_dev_gemm) and M = T' diag(w) T (bigkrls_dev_gram_weighted), from the
+ * matrix P = V S and M = S' P. Device memory O(n G (1 + |J|)), never O(u n). */
+int bigkrls_group_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                          const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
+                          const double* h_newdata, int64_t u, const int64_t* h_group, int64_t G,
+                          const double* d_vcov_c, const double* d_Q, int64_t ldq, int64_t k, const double* h_w,
+                          double* h_derivatives, double* h_ame, double* h_cov);
 
 /* Heteroskedasticity- or cluster-robust variance of the coefficients as factors (no counterpart in the reference).
  * d_Q (n x k, ldq >= n, device) and h_d (k, host) are the kept eigenpairs of the fit, lambda its ridge parameter,
