@@ -23,6 +23,7 @@
 #include "common.h"
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 
 namespace bk {
 
@@ -2298,16 +2299,154 @@ int kernel_block_centred(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t l
 // rebuilt in registers and contracted at once, never written (flash-attention style). K(A, B)' = K(B, A), so
 // K(A, B) W (rows of A stationary, loop over B) and K(A, B)' W (rows of B stationary, loop over A) are this one kernel
 // with the roles of the operands swapped.
-// Each wave owns 64 stationary rows (4 MFMA tiles of 16) and 16 CT columns of W, and walks its share of the loop
-// rows 16 at a time:
+//
+// The frame of the tile kernels (kt_*), shared by this kernel, its wide and grouped forms and the two leave-out kernels
+// further down: a wave owns MS stationary tiles of 16 rows and a chunk of columns, and walks its share of the loop rows
+// 16 at a time:
 //   G = L_tile S_tile'  : mfma_f64_16x16x4(L, S), register r of lane holds (l = l0 + (lane >> 4) + 4 r, s = lane & 15)
-//   E = exp(-(|s|^2 + |l|^2 - 2 G) / sigma), the epilogue of kernel_block_wave_kernel, in place
+//   d2 = max(|s|^2 + |l|^2 - 2 G, 0), the epilogue of kernel_block_wave_kernel, in place
+// and what a kernel does with d2 is its own: here
+//   E = exp(-d2 / sigma)
 //   acc += E W_tile     : register r of E is the A operand of k-step r (A[row = lane & 15][k = lane >> 4] = E(s, l))
-// so neither the kernel tile nor a transpose of it touches LDS or memory. When the grid would leave compute units idle
-// (few stationary rows) the loop rows are split over several waves whose partial sums are added by
-// contract_reduce_kernel in a fixed order: no atomics, the result does not depend on scheduling.
+// so neither the kernel tile nor a transpose of it touches LDS or memory. Rows past an operand's end are read from its
+// last row (clamped) and masked or not written by the kernel. When the grid would leave compute units idle (few
+// stationary rows) the loop rows are split over several waves whose partial sums are added by contract_reduce_kernel in
+// a fixed order: no atomics, the result does not depend on scheduling.
 // KS > 0: P <= 4 KS and the stationary fragments stay in registers for the whole loop; KS == 0: any P, fragments
 // re-read (from L1 / L2) for every loop tile.
+
+// exp_nonpos_tab's table in LDS (every thread of the block, before a wave without a task leaves)
+__device__ __forceinline__ void kt_exp_table(double* etab) {
+  if (threadIdx.x < 32) etab[threadIdx.x] = kExp2Tab32[threadIdx.x];
+  __syncthreads();
+}
+
+// The task of a wave: stationary tile group st (fastest), column chunk cc, and `part`, a loop split or a segment.
+struct KtTask {
+  int st, cc;
+  int64_t part;
+};
+__device__ __forceinline__ bool kt_task(KtTask& k, int stiles, int nchunks, int64_t ntasks) {
+  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w >= ntasks) return false;
+  k.st = (int)(w % stiles);
+  k.cc = (int)((w / stiles) % nchunks);
+  k.part = w / ((int64_t)stiles * nchunks);
+  return true;
+}
+// loop split sp of nsplit walks the loop tiles [kt_split_begin(sp), kt_split_begin(sp + 1))
+__device__ __forceinline__ int kt_split_begin(int ltiles, int sp, int nsplit) { return (int)((int64_t)ltiles * sp / nsplit); }
+
+// column k of the stationary row srow; k >= P zeroed: the loop side then reads a clamped, finite value
+__device__ __forceinline__ double kt_fragment(const double* S, int64_t lds, int srow, int k, int P) {
+  return k < P ? S[srow + (int64_t)k * lds] : 0.0;
+}
+
+// This lane's stationary rows (clamped), their squared norms and, with KS > 0, their resident fragments.
+template <int MS, int KS>
+__device__ __forceinline__ void kt_stationary(int (&srow)[MS], double (&ns)[MS], double (&sf)[MS][KS > 0 ? KS : 1],
+                                              const double* __restrict__ S, int64_t lds, int NS,
+                                              const double* __restrict__ nrm_s, int P, int s0) {
+  const int lane = threadIdx.x & 63, lm = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int m = 0; m < MS; ++m) {
+    srow[m] = min(s0 + 16 * m + lm, NS - 1);
+    ns[m] = nrm_s[srow[m]];
+  }
+  if (KS > 0) {
+#pragma unroll
+    for (int m = 0; m < MS; ++m)
+#pragma unroll
+      for (int t = 0; t < (KS > 0 ? KS : 1); ++t) {
+        const int k = 4 * t + lk;
+        sf[m][t] = kt_fragment(S, lds, srow[m], k, P);
+      }
+  }
+}
+
+// g[m] = L_tile S_tile(m)' for the loop tile whose row `lrow` this lane feeds (MFMA chains in s-then-m order).
+// The trip counts ms = MS and ks = max(KS, 1) come BY REFERENCE, from two locals of the kernel: the compiler
+// optimises a callee before it inlines it, and with counts it knows it unrolls these loops here, on their own, where the
+// kernel's own loops are unrolled after its local arrays have become vectors. The two orders give the same operations in
+// another instruction order, and the register allocator then lands elsewhere: of the 27 kernel_contract_kernel
+// instantiations (no minimum wave count in their launch bounds) 8 changed occupancy, hence the loop splits and the bits.
+// Counts behind a reference are unknown until the call is inlined, and the loops unroll in the kernel as they did when
+// the code stood there ("The shared frame", has both resource tables).
+template <int MS, int KS>
+__device__ __forceinline__ void kt_gram(d4 (&g)[MS], const int (&srow)[MS], const double (&sf)[MS][KS > 0 ? KS : 1],
+                                        const double* __restrict__ S, int64_t lds, const double* __restrict__ L,
+                                        int64_t ldl, int lrow, int P, const int& ms, const int& ks) {
+  const int lk = (threadIdx.x & 63) >> 4;
+#pragma unroll
+  for (int m = 0; m < ms; ++m) g[m] = (d4){0.0, 0.0, 0.0, 0.0};
+  if (KS > 0) {
+    double lf[KS > 0 ? KS : 1];
+#pragma unroll
+    for (int s = 0; s < ks; ++s) lf[s] = L[lrow + (int64_t)min(4 * s + lk, P - 1) * ldl];
+#pragma unroll
+    for (int s = 0; s < ks; ++s)
+#pragma unroll
+      for (int m = 0; m < ms; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sf[m][s], g[m], 0, 0, 0);
+  } else {
+    const int steps = (P + 3) / 4;
+    for (int s0k = 0; s0k < steps; s0k += 4) {
+      double lf[4], sg[MS][4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const int k = 4 * (s0k + s) + lk;
+        lf[s] = L[lrow + (int64_t)min(k, P - 1) * ldl];
+#pragma unroll
+        for (int m = 0; m < ms; ++m) sg[m][s] = kt_fragment(S, lds, srow[m], k, P);
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int m = 0; m < ms; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sg[m][s], g[m], 0, 0, 0);
+    }
+  }
+}
+
+// the squared distance from an entry of the Gram tile and the two squared norms
+__device__ __forceinline__ double kt_dist2(double g, double ns, double nl) { return fmax(fma(-2.0, g, ns + nl), 0.0); }
+
+// MFMA accumulators to memory: acc[m][c] register r is (s = s0 + 16 m + (lane >> 4) + 4 r, col = c0 + 16 c + (lane & 15));
+// ALLCOLS: every column of the chunk exists.
+template <int MS, int CT, bool ALLCOLS>
+__device__ __forceinline__ void kt_store_tiles(const d4 (&acc)[MS][CT], double* __restrict__ dst, int64_t ld, int s0,
+                                               int c0, int NS, int Q) {
+  const int lane = threadIdx.x & 63, lm = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int m = 0; m < MS; ++m)
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+      const int col = c0 + 16 * c + lm;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int s = s0 + 16 * m + lk + 4 * r;
+        if (s < NS && (ALLCOLS || col < Q)) dst[s + (int64_t)col * ld] = acc[m][c][r];
+      }
+    }
+}
+
+// Per-lane sums to memory: the four lane groups (lane >> 4) hold the sums over the loop rows l = (lane >> 4) mod 4 of
+// the same stationary rows s0 + 16 m + (lane & 15); they are added with shuffles and group 0 stores column c0 + j, j < ncw.
+template <int MS, int CW>
+__device__ __forceinline__ void kt_store_lane_sums(const double (&acc)[MS][CW], double* __restrict__ dst, int64_t ld,
+                                                   int s0, int c0, int ncw, int NS) {
+  const int lane = threadIdx.x & 63, lm = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int j = 0; j < CW; ++j)
+#pragma unroll
+    for (int m = 0; m < MS; ++m) {
+      double a = acc[m][j];
+      a += __shfl_xor(a, 16, 64);
+      a += __shfl_xor(a, 32, 64);
+      const int s = s0 + 16 * m + lm;
+      if (lk == 0 && j < ncw && s < NS) dst[s + (int64_t)(c0 + j) * ld] = a;
+    }
+}
+
+// Each wave of kernel_contract_kernel owns 64 stationary rows (4 MFMA tiles of 16) and 16 CT columns of W.
 constexpr int KC_MS = 4;   // 16-row stationary tiles per wave
 
 template <int KS, int CT>
@@ -2317,37 +2456,18 @@ __global__ __launch_bounds__(NT) void kernel_contract_kernel(
     const double* __restrict__ W, int64_t ldw, int Q, double* __restrict__ out, int64_t ldo, int64_t split_stride,
     int stiles, int nchunks, int nsplit, int ltiles, int64_t ntasks) {
   __shared__ double etab[32];
-  if (threadIdx.x < 32) etab[threadIdx.x] = kExp2Tab32[threadIdx.x];
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (w >= ntasks) return;
-  const int st = (int)(w % stiles);
-  const int cc = (int)((w / stiles) % nchunks);
-  const int sp = (int)(w / ((int64_t)stiles * nchunks));
-  const int s0 = st * 16 * KC_MS, c0 = cc * 16 * CT;
-  const int t_begin = (int)((int64_t)ltiles * sp / nsplit), t_end = (int)((int64_t)ltiles * (sp + 1) / nsplit);
-  const int lm = lane & 15, lk = lane >> 4;
-  const int steps = (P + 3) / 4;
+  kt_exp_table(etab);
+  KtTask k;
+  if (!kt_task(k, stiles, nchunks, ntasks)) return;
+  const int sp = (int)k.part;
+  const int s0 = k.st * 16 * KC_MS, c0 = k.cc * 16 * CT;
+  const int t_begin = kt_split_begin(ltiles, sp, nsplit), t_end = kt_split_begin(ltiles, sp + 1, nsplit);
+  const int lane = threadIdx.x & 63, lm = lane & 15, lk = lane >> 4;
 
   int srow[KC_MS];
-  double ns[KC_MS];
-#pragma unroll
-  for (int m = 0; m < KC_MS; ++m) {
-    srow[m] = min(s0 + 16 * m + lm, NS - 1);
-    ns[m] = nrm_s[srow[m]];
-  }
-  // stationary fragments (k >= P zeroed: the loop side then reads a clamped, finite value)
-  double sf[KC_MS][KS > 0 ? KS : 1];
-  if (KS > 0) {
-#pragma unroll
-    for (int m = 0; m < KC_MS; ++m)
-#pragma unroll
-      for (int t = 0; t < (KS > 0 ? KS : 1); ++t) {
-        const int k = 4 * t + lk;
-        sf[m][t] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
-      }
-  }
+  double ns[KC_MS], sf[KC_MS][KS > 0 ? KS : 1];
+  kt_stationary<KC_MS, KS>(srow, ns, sf, S, lds, NS, nrm_s, P, s0);
+  const int ms = KC_MS, ks = KS > 0 ? KS : 1;   // kt_gram's trip counts (by reference: see there)
   d4 acc[KC_MS][CT];
 #pragma unroll
   for (int m = 0; m < KC_MS; ++m)
@@ -2369,60 +2489,19 @@ __global__ __launch_bounds__(NT) void kernel_contract_kernel(
       }
     }
     d4 g[KC_MS];
-#pragma unroll
-    for (int m = 0; m < KC_MS; ++m) g[m] = (d4){0.0, 0.0, 0.0, 0.0};
-    if (KS > 0) {
-      double lf[KS > 0 ? KS : 1];
-#pragma unroll
-      for (int s = 0; s < (KS > 0 ? KS : 1); ++s) lf[s] = L[lrow + (int64_t)min(4 * s + lk, P - 1) * ldl];
-#pragma unroll
-      for (int s = 0; s < (KS > 0 ? KS : 1); ++s)
-#pragma unroll
-        for (int m = 0; m < KC_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sf[m][s], g[m], 0, 0, 0);
-    } else {
-      for (int s0k = 0; s0k < steps; s0k += 4) {
-        double lf[4], sg[KC_MS][4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int k = 4 * (s0k + s) + lk;
-          lf[s] = L[lrow + (int64_t)min(k, P - 1) * ldl];
-#pragma unroll
-          for (int m = 0; m < KC_MS; ++m) sg[m][s] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-          for (int m = 0; m < KC_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sg[m][s], g[m], 0, 0, 0);
-      }
-    }
+    kt_gram<KC_MS, KS>(g, srow, sf, S, lds, L, ldl, lrow, P, ms, ks);
 #pragma unroll
     for (int m = 0; m < KC_MS; ++m) {
       d4 e;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        double d2 = fma(-2.0, g[m][r], ns[m] + nl[r]);   // (kernel_block_wave_kernel's epilogue)
-        d2 = fmax(d2, 0.0);
-        e[r] = exp_nonpos_tab(d2 * neg_inv_sigma, etab);
-      }
+      for (int r = 0; r < 4; ++r) e[r] = exp_nonpos_tab(kt_dist2(g[m][r], ns[m], nl[r]) * neg_inv_sigma, etab);
 #pragma unroll
       for (int r = 0; r < 4; ++r)
 #pragma unroll
         for (int c = 0; c < CT; ++c) acc[m][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(e[r], wf[c][r], acc[m][c], 0, 0, 0);
     }
   }
-  // acc[m][c] register r: (s = s0 + 16 m + (lane >> 4) + 4 r, col = c0 + 16 c + (lane & 15))
-  double* dst = out + (int64_t)sp * split_stride;
-#pragma unroll
-  for (int m = 0; m < KC_MS; ++m)
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-      const int col = c0 + 16 * c + lm;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int s = s0 + 16 * m + lk + 4 * r;
-        if (s < NS && col < Q) dst[s + (int64_t)col * ldo] = acc[m][c][r];
-      }
-    }
+  kt_store_tiles<KC_MS, CT, false>(acc, out + (int64_t)sp * split_stride, ldo, s0, c0, NS, Q);
 }
 
 // out[s, c] = sum over the splits, in split order, of part[sp][s, c] (each ns x q, ld ns)
@@ -2447,8 +2526,7 @@ __global__ void contract_reduce_kernel(int NS, int Q, int nsplit, const double* 
 // registers for the accumulators alone and leave one wave per SIMD with nothing to cover the loads of W.
 // MFMA 16x16x4 per 32 x 16 kernel tile pair: 2 KS (<= 16) for G and 2 x 4 x 8 = 64 for the contraction.
 // Column tiles that lie wholly past q are skipped (wave-uniform), so a last chunk of q mod 128 columns costs its own
-// tiles only. Everything else -- operand layout, edge clamping, the epilogue, the fixed-order reduction of the loop
-// splits -- is kernel_contract_kernel's.
+// tiles only. Everything else is the frame (kt_*).
 constexpr int KCW_MS = 2;   // 16-row stationary tiles per wave
 constexpr int KCW_CT = 8;   // 16-column tiles of W per wave
 
@@ -2462,27 +2540,12 @@ __device__ __forceinline__ void kcw_body(const double* __restrict__ S, int64_t l
                                          int64_t ldo, int s0, int c0, int t_begin, int t_end, const double* etab) {
   const int lane = threadIdx.x & 63;
   const int lm = lane & 15, lk = lane >> 4;
-  const int steps = (P + 3) / 4;
   const int nct = FULL ? KCW_CT : min(KCW_CT, (Q - c0 + 15) / 16);   // column tiles that hold a column (wave-uniform)
 
   int srow[KCW_MS];
-  double ns[KCW_MS];
-#pragma unroll
-  for (int m = 0; m < KCW_MS; ++m) {
-    srow[m] = min(s0 + 16 * m + lm, NS - 1);
-    ns[m] = nrm_s[srow[m]];
-  }
-  // stationary fragments (k >= P zeroed: the loop side then reads a clamped, finite value)
-  double sf[KCW_MS][KS > 0 ? KS : 1];
-  if (KS > 0) {
-#pragma unroll
-    for (int m = 0; m < KCW_MS; ++m)
-#pragma unroll
-      for (int t = 0; t < (KS > 0 ? KS : 1); ++t) {
-        const int k = 4 * t + lk;
-        sf[m][t] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
-      }
-  }
+  double ns[KCW_MS], sf[KCW_MS][KS > 0 ? KS : 1];
+  kt_stationary<KCW_MS, KS>(srow, ns, sf, S, lds, NS, nrm_s, P, s0);
+  const int ms = KCW_MS, ks = KS > 0 ? KS : 1;   // kt_gram's trip counts (by reference: see there)
   d4 acc[KCW_MS][KCW_CT];
 #pragma unroll
   for (int m = 0; m < KCW_MS; ++m)
@@ -2499,41 +2562,12 @@ __device__ __forceinline__ void kcw_body(const double* __restrict__ S, int64_t l
 #pragma unroll
     for (int r = 0; r < 4; ++r) nl[r] = nrm_l[min(l0 + lk + 4 * r, NL - 1)];
     d4 g[KCW_MS];
-#pragma unroll
-    for (int m = 0; m < KCW_MS; ++m) g[m] = (d4){0.0, 0.0, 0.0, 0.0};
-    if (KS > 0) {
-      double lf[KS > 0 ? KS : 1];
-#pragma unroll
-      for (int s = 0; s < (KS > 0 ? KS : 1); ++s) lf[s] = L[lrow + (int64_t)min(4 * s + lk, P - 1) * ldl];
-#pragma unroll
-      for (int s = 0; s < (KS > 0 ? KS : 1); ++s)
-#pragma unroll
-        for (int m = 0; m < KCW_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sf[m][s], g[m], 0, 0, 0);
-    } else {
-      for (int s0k = 0; s0k < steps; s0k += 4) {
-        double lf[4], sg[KCW_MS][4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int k = 4 * (s0k + s) + lk;
-          lf[s] = L[lrow + (int64_t)min(k, P - 1) * ldl];
-#pragma unroll
-          for (int m = 0; m < KCW_MS; ++m) sg[m][s] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-          for (int m = 0; m < KCW_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sg[m][s], g[m], 0, 0, 0);
-      }
-    }
-    // E in place of G (kernel_block_wave_kernel's epilogue)
+    kt_gram<KCW_MS, KS>(g, srow, sf, S, lds, L, ldl, lrow, P, ms, ks);
+    // E in place of G
 #pragma unroll
     for (int m = 0; m < KCW_MS; ++m)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        double d2 = fma(-2.0, g[m][r], ns[m] + nl[r]);
-        d2 = fmax(d2, 0.0);
-        g[m][r] = exp_nonpos_tab(d2 * neg_inv_sigma, etab);
-      }
+      for (int r = 0; r < 4; ++r) g[m][r] = exp_nonpos_tab(kt_dist2(g[m][r], ns[m], nl[r]) * neg_inv_sigma, etab);
     // k-step r of the contraction: loop rows l0 + (lane >> 4) + 4 r, one k-step of W (8 doubles) at a time
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -2569,18 +2603,7 @@ __device__ __forceinline__ void kcw_body(const double* __restrict__ S, int64_t l
       }
     }
   }
-  // acc[m][c] register r: (s = s0 + 16 m + (lane >> 4) + 4 r, col = c0 + 16 c + (lane & 15))
-#pragma unroll
-  for (int m = 0; m < KCW_MS; ++m)
-#pragma unroll
-    for (int c = 0; c < KCW_CT; ++c) {
-      const int col = c0 + 16 * c + lm;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int s = s0 + 16 * m + lk + 4 * r;
-        if (s < NS && (FULL || col < Q)) dst[s + (int64_t)col * ldo] = acc[m][c][r];
-      }
-    }
+  kt_store_tiles<KCW_MS, KCW_CT, FULL>(acc, dst, ldo, s0, c0, NS, Q);
 }
 
 template <int KS>
@@ -2590,20 +2613,90 @@ __global__ __launch_bounds__(NT, 2) void kernel_contract_wide_kernel(
     const double* __restrict__ W, int64_t ldw, int Q, double* __restrict__ out, int64_t ldo, int64_t split_stride,
     int stiles, int nchunks, int nsplit, int ltiles, int64_t ntasks) {
   __shared__ double etab[32];
-  if (threadIdx.x < 32) etab[threadIdx.x] = kExp2Tab32[threadIdx.x];
-  __syncthreads();
-  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (w >= ntasks) return;
-  const int st = (int)(w % stiles);
-  const int cc = (int)((w / stiles) % nchunks);
-  const int sp = (int)(w / ((int64_t)stiles * nchunks));
-  const int s0 = st * 16 * KCW_MS, c0 = cc * 16 * KCW_CT;
-  const int t_begin = (int)((int64_t)ltiles * sp / nsplit), t_end = (int)((int64_t)ltiles * (sp + 1) / nsplit);
+  kt_exp_table(etab);
+  KtTask k;
+  if (!kt_task(k, stiles, nchunks, ntasks)) return;
+  const int sp = (int)k.part;
+  const int s0 = k.st * 16 * KCW_MS, c0 = k.cc * 16 * KCW_CT;
+  const int t_begin = kt_split_begin(ltiles, sp, nsplit), t_end = kt_split_begin(ltiles, sp + 1, nsplit);
   double* dst = out + (int64_t)sp * split_stride;
   if (c0 + 16 * KCW_CT <= Q)
     kcw_body<KS, true>(S, lds, NS, L, ldl, NL, P, nrm_s, nrm_l, neg_inv_sigma, W, ldw, Q, dst, ldo, s0, c0, t_begin, t_end, etab);
   else   // (with resident fragments the partial body would spill: it re-reads them like KS == 0)
     kcw_body<0, false>(S, lds, NS, L, ldl, NL, P, nrm_s, nrm_l, neg_inv_sigma, W, ldw, Q, dst, ldo, s0, c0, t_begin, t_end, etab);
+}
+
+// ---- the host side of the frame ----
+// The KS of the tile kernels for p columns: the MFMA steps of the Gram tile where the fragments fit (p <= 32), else 0.
+static int ks_of(int64_t p) {
+  const int steps = (int)((p + 3) / 4);
+  return steps <= 8 ? steps : 0;
+}
+// f(std::integral_constant<int, KS>()) for a runtime ks in 0..8
+template <class F>
+static auto with_ks(int ks, F&& f) {
+  switch (ks) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 3: return f(std::integral_constant<int, 3>());
+    case 4: return f(std::integral_constant<int, 4>());
+    case 5: return f(std::integral_constant<int, 5>());
+    case 6: return f(std::integral_constant<int, 6>());
+    case 7: return f(std::integral_constant<int, 7>());
+    case 8: return f(std::integral_constant<int, 8>());
+    default: return f(std::integral_constant<int, 0>());
+  }
+}
+// the waves of a tile kernel that the device holds at once (2 or 3 per SIMD, by the kernel's registers)
+static int wave_slots(bigkrls_ctx* ctx, const void* fn, int64_t* slots) {
+  int cap = 0;
+  BK_TRY(resident_capacity(ctx, fn, &cap, NT));
+  *slots = (int64_t)cap * (NT / 64);
+  return BIGKRLS_OK;
+}
+// Loop splits against the wave slots: the time is about (rounds of resident waves) x (loop tiles per wave), so the split
+// count minimises ceil(base s / slots) / s for `base` tasks per split -- a last round that is nearly empty costs as much
+// as a full one (C3 shape: 313 tiles x 7 splits = 2191 waves on 2048 slots took 1.36 ms). At most 64 splits, each at
+// least 16 loop tiles (256 rows), all partial sums together at most 64 MB; fewer splits on a tie (a gain below 2 % does
+// not count).
+static int64_t plan_loop_splits(int64_t base, int64_t slots, int64_t ltiles, int64_t bytes_per_split) {
+  const int64_t max_split = std::max<int64_t>(1, std::min<int64_t>({(int64_t)64, ltiles / 16, (64ll << 20) / bytes_per_split}));
+  int64_t nsplit = 1;
+  double best = (double)((base + slots - 1) / slots);
+  for (int64_t s = 2; s <= max_split; ++s) {
+    const double cost = (double)((base * s + slots - 1) / slots) / (double)s;
+    if (cost < best * 0.98) { best = cost; nsplit = s; }
+  }
+  return nsplit;
+}
+// One launch over nsplit loop splits and what follows it. launch(dst, ldd, split_stride) starts the tile kernel: a single
+// split stores the ns x nc result where it belongs; several store their partial sums (each ns x nc, ld ns) into the
+// workspace slot, and contract_reduce_kernel adds them in split order. The result belongs in out (ld ldo), or with
+// out == nullptr in a buffer behind the partial sums (ld ns) that *staged returns.
+template <class Launch>
+static int launch_loop_splits(bigkrls_ctx* ctx, int slot, int64_t nsplit, int64_t ns, int64_t nc, double* out, int64_t ldo,
+                              double** staged, Launch&& launch) {
+  const int64_t part_doubles = nsplit > 1 ? nsplit * ns * nc : 0, staged_doubles = out ? 0 : ns * nc;
+  double* part = nullptr;
+  if (part_doubles + staged_doubles > 0) {
+    void* pp = nullptr;
+    BK_TRY(ws_get(ctx, slot, (part_doubles + staged_doubles) * (int64_t)sizeof(double), &pp));
+    part = (double*)pp;
+  }
+  if (!out) {
+    out = *staged = part + part_doubles;
+    ldo = ns;
+  }
+  if (nsplit == 1) BK_TRY(launch(out, ldo, (int64_t)0));
+  else BK_TRY(launch(part, ns, ns * nc));
+  BK_CHECK_LAUNCH();
+  if (nsplit > 1) {
+    const int blocks = (int)std::min<int64_t>((ns * nc + 255) / 256, 4096);
+    hipLaunchKernelGGL(contract_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (int)ns, (int)nc, (int)nsplit,
+                       (const double*)part, out, ldo);
+    BK_CHECK_LAUNCH();
+  }
+  return BIGKRLS_OK;
 }
 
 // out (ns x q, ldo) = K(S, L) W for operands that are already centred, with their squared row norms: what
@@ -2622,83 +2715,31 @@ int kernel_contract_centred(bigkrls_ctx* ctx, const double* S, int64_t ns, int64
   const int CT = wide ? KCW_CT : (q <= 16 ? 1 : (q <= 32 ? 2 : 4));
   const int MS = wide ? KCW_MS : KC_MS;
   const char* pname = wide ? "kernel_contract_wide" : "kernel_contract";
-  const int steps = (int)((p + 3) / 4);
-  const int ks = steps <= 8 ? steps : 0;
   using KcFn = void (*)(const double*, int64_t, int, const double*, int64_t, int, int, const double*, const double*,
                         double, const double*, int64_t, int, double*, int64_t, int64_t, int, int, int, int, int64_t);
-  KcFn fn = nullptr;
-#define BK_KCS(CTV)                                                                                                   \
-  switch (ks) {                                                                                                       \
-    case 1: fn = kernel_contract_kernel<1, CTV>; break;                                                               \
-    case 2: fn = kernel_contract_kernel<2, CTV>; break;                                                               \
-    case 3: fn = kernel_contract_kernel<3, CTV>; break;                                                               \
-    case 4: fn = kernel_contract_kernel<4, CTV>; break;                                                               \
-    case 5: fn = kernel_contract_kernel<5, CTV>; break;                                                               \
-    case 6: fn = kernel_contract_kernel<6, CTV>; break;                                                               \
-    case 7: fn = kernel_contract_kernel<7, CTV>; break;                                                               \
-    case 8: fn = kernel_contract_kernel<8, CTV>; break;                                                               \
-    default: fn = kernel_contract_kernel<0, CTV>; break;                                                              \
-  }
-  if (wide) {
-    switch (ks) {
-      case 1: fn = kernel_contract_wide_kernel<1>; break;
-      case 2: fn = kernel_contract_wide_kernel<2>; break;
-      case 3: fn = kernel_contract_wide_kernel<3>; break;
-      case 4: fn = kernel_contract_wide_kernel<4>; break;
-      case 5: fn = kernel_contract_wide_kernel<5>; break;
-      case 6: fn = kernel_contract_wide_kernel<6>; break;
-      case 7: fn = kernel_contract_wide_kernel<7>; break;
-      case 8: fn = kernel_contract_wide_kernel<8>; break;
-      default: fn = kernel_contract_wide_kernel<0>; break;
-    }
-  }
-  else if (CT == 1) { BK_KCS(1) }
-  else if (CT == 2) { BK_KCS(2) }
-  else { BK_KCS(4) }
-#undef BK_KCS
+  const KcFn fn = with_ks(ks_of(p), [&](auto ks) -> KcFn {
+    constexpr int KS = decltype(ks)::value;
+    if (wide) return kernel_contract_wide_kernel<KS>;
+    if (CT == 1) return kernel_contract_kernel<KS, 1>;
+    if (CT == 2) return kernel_contract_kernel<KS, 2>;
+    return kernel_contract_kernel<KS, 4>;
+  });
   const int64_t stiles = (ns + 16 * MS - 1) / (16 * MS);
   const int64_t nchunks = (q + 16 * CT - 1) / (16 * CT);
   const int64_t ltiles = (nl + 15) / 16;
-  // Loop splits against the wave slots the kernel can hold at once (2 or 3 per SIMD, by its registers): the time is
-  // about (rounds of resident waves) x (loop tiles per wave), so the split count minimises ceil(base s / slots) / s --
-  // a last round that is nearly empty costs as much as a full one (C3 shape: 313 tiles x 7 splits = 2191 waves on 2048
-  // slots took 1.36 ms). At most 64 splits, each at least 16 loop tiles (256 rows), all partial sums together at most
-  // 64 MB; fewer splits on a tie.
-  int cap = 0;
-  BK_TRY(resident_capacity(ctx, (const void*)fn, &cap, NT));
-  const int64_t slots = (int64_t)cap * (NT / 64);
-  const int64_t base = stiles * nchunks;
-  const int64_t max_split =
-      std::max<int64_t>(1, std::min<int64_t>({(int64_t)64, ltiles / 16, (64ll << 20) / (ns * q * (int64_t)sizeof(double))}));
-  int64_t nsplit = 1;
-  double best = (double)((base + slots - 1) / slots);
-  for (int64_t s = 2; s <= max_split; ++s) {
-    const double cost = (double)((base * s + slots - 1) / slots) / (double)s;
-    if (cost < best * 0.98) { best = cost; nsplit = s; }
-  }
-  const int64_t ntasks = base * nsplit;
+  int64_t slots = 0;
+  BK_TRY(wave_slots(ctx, (const void*)fn, &slots));
+  const int64_t nsplit = plan_loop_splits(stiles * nchunks, slots, ltiles, ns * q * (int64_t)sizeof(double));
+  const int64_t ntasks = stiles * nchunks * nsplit;
   BK_REQUIRE((ntasks + 3) / 4 < (1ll << 31), "kernel_contract: too many tiles");
-  double* dst = out;
-  int64_t ldd = ldo, split_stride = 0;
-  if (nsplit > 1) {
-    void* pp = nullptr;
-    BK_TRY(ws_get(ctx, SLOT_CONTRACT_PART, nsplit * ns * q * (int64_t)sizeof(double), &pp));
-    dst = (double*)pp;
-    ldd = ns;
-    split_stride = ns * q;
-  }
-  const dim3 grid((unsigned)((ntasks + 3) / 4));
-  BK_TRY(prof_begin(ctx, pname, 2.0 * (double)ns * (double)nl * (double)(p + q)));
-  hipLaunchKernelGGL(fn, grid, dim3(NT), 0, ctx->stream, S, lds, (int)ns, L, ldl, (int)nl, (int)p, nrm_s, nrm_l,
-                     -1.0 / sigma, W, ldw, (int)q, dst, ldd, split_stride, (int)stiles, (int)nchunks, (int)nsplit,
-                     (int)ltiles, ntasks);
-  BK_CHECK_LAUNCH();
-  if (nsplit > 1) {
-    const int blocks = (int)std::min<int64_t>((ns * q + 255) / 256, 4096);
-    hipLaunchKernelGGL(contract_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (int)ns, (int)q, (int)nsplit,
-                       (const double*)dst, out, ldo);
-    BK_CHECK_LAUNCH();
-  }
+  BK_TRY(launch_loop_splits(ctx, SLOT_CONTRACT_PART, nsplit, ns, q, out, ldo, nullptr,
+                            [&](double* dst, int64_t ldd, int64_t split_stride) -> int {
+    BK_TRY(prof_begin(ctx, pname, 2.0 * (double)ns * (double)nl * (double)(p + q)));
+    hipLaunchKernelGGL(fn, dim3((unsigned)((ntasks + 3) / 4)), dim3(NT), 0, ctx->stream, S, lds, (int)ns, L, ldl, (int)nl,
+                       (int)p, nrm_s, nrm_l, -1.0 / sigma, W, ldw, (int)q, dst, ldd, split_stride, (int)stiles,
+                       (int)nchunks, (int)nsplit, (int)ltiles, ntasks);
+    return BIGKRLS_OK;
+  }));
   BK_TRY(prof_end(ctx, pname));
   return BIGKRLS_OK;
 }
@@ -2726,10 +2767,10 @@ int kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, c
 // grouped fused kernel contraction (group effects, csrc/grpeff.hip)
 // ---------------------------------------------------------------------------
 // out[:, g q .. (g + 1) q) = K(S, L[rows of group g])  W[rows of group g] for all groups in ONE launch: the loop rows come
-// sorted by group, and a device-side table cuts them into segments (l_begin, l_end, group, partial slot). The frame is
-// kernel_contract_kernel's, registers included -- 64 stationary rows per wave, 16 loop rows per step, MFMA /
-// exp_nonpos_tab / MFMA --; what differs is the task, (stationary tile, column chunk, segment) in place of (tile, chunk,
-// split), and the loop tiles, which start at l_begin (not at a multiple of 16) and are masked by l < l_end (not by NL).
+// sorted by group, and a device-side table cuts them into segments (l_begin, l_end, group, partial slot). The kernel is
+// kernel_contract_kernel, registers included; what differs is the task, (stationary tile, column chunk, segment) in place
+// of (tile, chunk, split), and the loop tiles, which start at l_begin (not at a multiple of 16) and are masked by
+// l < l_end (not by NL).
 // A segment that is a whole group stores into out; the segments of a longer group store into their slots of `part`
 // (each NS x Q, ld NS) and contract_grouped_reduce_kernel adds them in segment order.
 struct KcgSeg {
@@ -2743,37 +2784,18 @@ __global__ __launch_bounds__(NT) void kernel_contract_grouped_kernel(
     const double* __restrict__ W, int64_t ldw, int Q, double* __restrict__ out, int64_t ldo, double* __restrict__ part,
     const KcgSeg* __restrict__ segs, int stiles, int nchunks, int64_t ntasks) {
   __shared__ double etab[32];
-  if (threadIdx.x < 32) etab[threadIdx.x] = kExp2Tab32[threadIdx.x];
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (w >= ntasks) return;
-  const int st = (int)(w % stiles);
-  const int cc = (int)((w / stiles) % nchunks);
-  const KcgSeg sg = segs[w / ((int64_t)stiles * nchunks)];
-  const int s0 = st * 16 * KC_MS, c0 = cc * 16 * CT;
+  kt_exp_table(etab);
+  KtTask k;
+  if (!kt_task(k, stiles, nchunks, ntasks)) return;
+  const KcgSeg sg = segs[k.part];
+  const int s0 = k.st * 16 * KC_MS, c0 = k.cc * 16 * CT;
   const int l_end = sg.l_end, l_last = sg.l_end - 1;
-  const int lm = lane & 15, lk = lane >> 4;
-  const int steps = (P + 3) / 4;
+  const int lane = threadIdx.x & 63, lm = lane & 15, lk = lane >> 4;
 
   int srow[KC_MS];
-  double ns[KC_MS];
-#pragma unroll
-  for (int m = 0; m < KC_MS; ++m) {
-    srow[m] = min(s0 + 16 * m + lm, NS - 1);
-    ns[m] = nrm_s[srow[m]];
-  }
-  // stationary fragments (k >= P zeroed: the loop side then reads a clamped, finite value)
-  double sf[KC_MS][KS > 0 ? KS : 1];
-  if (KS > 0) {
-#pragma unroll
-    for (int m = 0; m < KC_MS; ++m)
-#pragma unroll
-      for (int t = 0; t < (KS > 0 ? KS : 1); ++t) {
-        const int k = 4 * t + lk;
-        sf[m][t] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
-      }
-  }
+  double ns[KC_MS], sf[KC_MS][KS > 0 ? KS : 1];
+  kt_stationary<KC_MS, KS>(srow, ns, sf, S, lds, NS, nrm_s, P, s0);
+  const int ms = KC_MS, ks = KS > 0 ? KS : 1;   // kt_gram's trip counts (by reference: see there)
   d4 acc[KC_MS][CT];
 #pragma unroll
   for (int m = 0; m < KC_MS; ++m)
@@ -2794,61 +2816,20 @@ __global__ __launch_bounds__(NT) void kernel_contract_grouped_kernel(
       }
     }
     d4 g[KC_MS];
-#pragma unroll
-    for (int m = 0; m < KC_MS; ++m) g[m] = (d4){0.0, 0.0, 0.0, 0.0};
-    if (KS > 0) {
-      double lf[KS > 0 ? KS : 1];
-#pragma unroll
-      for (int s = 0; s < (KS > 0 ? KS : 1); ++s) lf[s] = L[lrow + (int64_t)min(4 * s + lk, P - 1) * ldl];
-#pragma unroll
-      for (int s = 0; s < (KS > 0 ? KS : 1); ++s)
-#pragma unroll
-        for (int m = 0; m < KC_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sf[m][s], g[m], 0, 0, 0);
-    } else {
-      for (int s0k = 0; s0k < steps; s0k += 4) {
-        double lf[4], sgf[KC_MS][4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int k = 4 * (s0k + s) + lk;
-          lf[s] = L[lrow + (int64_t)min(k, P - 1) * ldl];
-#pragma unroll
-          for (int m = 0; m < KC_MS; ++m) sgf[m][s] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-          for (int m = 0; m < KC_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sgf[m][s], g[m], 0, 0, 0);
-      }
-    }
+    kt_gram<KC_MS, KS>(g, srow, sf, S, lds, L, ldl, lrow, P, ms, ks);
 #pragma unroll
     for (int m = 0; m < KC_MS; ++m) {
       d4 e;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        double d2 = fma(-2.0, g[m][r], ns[m] + nl[r]);   // (kernel_block_wave_kernel's epilogue)
-        d2 = fmax(d2, 0.0);
-        e[r] = exp_nonpos_tab(d2 * neg_inv_sigma, etab);
-      }
+      for (int r = 0; r < 4; ++r) e[r] = exp_nonpos_tab(kt_dist2(g[m][r], ns[m], nl[r]) * neg_inv_sigma, etab);
 #pragma unroll
       for (int r = 0; r < 4; ++r)
 #pragma unroll
         for (int c = 0; c < CT; ++c) acc[m][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(e[r], wf[c][r], acc[m][c], 0, 0, 0);
     }
   }
-  // acc[m][c] register r: (s = s0 + 16 m + (lane >> 4) + 4 r, col = c0 + 16 c + (lane & 15))
   double* dst = sg.slot < 0 ? out + (int64_t)sg.group * Q * ldo : part + (int64_t)sg.slot * NS * Q;
-  const int64_t ldd = sg.slot < 0 ? ldo : (int64_t)NS;
-#pragma unroll
-  for (int m = 0; m < KC_MS; ++m)
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-      const int col = c0 + 16 * c + lm;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int s = s0 + 16 * m + lk + 4 * r;
-        if (s < NS && col < Q) dst[s + (int64_t)col * ldd] = acc[m][c][r];
-      }
-    }
+  kt_store_tiles<KC_MS, CT, false>(acc, dst, sg.slot < 0 ? ldo : (int64_t)NS, s0, c0, NS, Q);
 }
 
 // the groups of several segments, and the empty ones (count 0): multi[3 i ..] = (group, first slot, segments);
@@ -2948,40 +2929,26 @@ int kernel_contract_grouped_centred(bigkrls_ctx* ctx, const double* S, int64_t v
 
   // ---- the kernel ---------------------------------------------------------------------------------------------------
   const int CT = q <= 16 ? 1 : (q <= 32 ? 2 : 4);
-  const int steps = (int)((p + 3) / 4);
-  const int ks = steps <= 8 ? steps : 0;
   using KcgFn = void (*)(const double*, int64_t, int, const double*, int64_t, int, const double*, const double*, double,
                          const double*, int64_t, int, double*, int64_t, double*, const KcgSeg*, int, int, int64_t);
-  KcgFn fn = nullptr;
-#define BK_KCG(CTV)                                                                                                   \
-  switch (ks) {                                                                                                       \
-    case 1: fn = kernel_contract_grouped_kernel<1, CTV>; break;                                                       \
-    case 2: fn = kernel_contract_grouped_kernel<2, CTV>; break;                                                       \
-    case 3: fn = kernel_contract_grouped_kernel<3, CTV>; break;                                                       \
-    case 4: fn = kernel_contract_grouped_kernel<4, CTV>; break;                                                       \
-    case 5: fn = kernel_contract_grouped_kernel<5, CTV>; break;                                                       \
-    case 6: fn = kernel_contract_grouped_kernel<6, CTV>; break;                                                       \
-    case 7: fn = kernel_contract_grouped_kernel<7, CTV>; break;                                                       \
-    case 8: fn = kernel_contract_grouped_kernel<8, CTV>; break;                                                       \
-    default: fn = kernel_contract_grouped_kernel<0, CTV>; break;                                                      \
-  }
-  if (CT == 1) { BK_KCG(1) }
-  else if (CT == 2) { BK_KCG(2) }
-  else { BK_KCG(4) }
-#undef BK_KCG
+  const KcgFn fn = with_ks(ks_of(p), [&](auto ks) -> KcgFn {
+    constexpr int KS = decltype(ks)::value;
+    if (CT == 1) return kernel_contract_grouped_kernel<KS, 1>;
+    if (CT == 2) return kernel_contract_grouped_kernel<KS, 2>;
+    return kernel_contract_grouped_kernel<KS, 4>;
+  });
   const int64_t stiles = (v + 16 * KC_MS - 1) / (16 * KC_MS);
   const int64_t nchunks = (q + 16 * CT - 1) / (16 * CT);
 
   // ---- the segments ---------------------------------------------------------------------------------------------------
-  // kernel_contract_centred's model over all groups together: the time is about (rounds of resident waves) x (loop tiles
+  // plan_loop_splits' model over all groups together: the time is about (rounds of resident waves) x (loop tiles
   // of the longest part). A candidate s cuts the largest group (lt_max loop tiles) into s equal parts and every group
   // into parts of about that length, s_g = ceil(lt_g s / lt_max), each part at least 16 loop tiles (s_g <= lt_g / 16) and
   // at most 64 parts per group; the slots of the groups with s_g > 1 hold at most 64 MB; s minimises
   // ceil(base sum_g s_g / slots) / s, fewer parts on a tie (a gain below 2 % does not count). With G = 1 this is
-  // kernel_contract_centred's split rule, cuts included: part k of a group is its loop tiles [lt k / s, lt (k + 1) / s).
-  int cap = 0;
-  BK_TRY(resident_capacity(ctx, (const void*)fn, &cap, NT));
-  const int64_t slots = (int64_t)cap * (NT / 64);
+  // plan_loop_splits' rule, cuts included: part k of a group is its loop tiles [lt k / s, lt (k + 1) / s).
+  int64_t slots = 0;
+  BK_TRY(wave_slots(ctx, (const void*)fn, &slots));
   const int64_t base = stiles * nchunks;
   const int64_t slot_cap = (64ll << 20) / (v * q * (int64_t)sizeof(double));
   int64_t lt_max = 0, nonempty = 0;
@@ -3123,10 +3090,8 @@ int kernel_contract_grouped(bigkrls_ctx* ctx, const double* A, int64_t u, int64_
 // of the two operands with column c left out of the distance, for every selected column in ONE pass. The unfused route
 // is one kernel_contract(trans = 1, W = ones) per column on copies of the operands without that column: it rebuilds the
 // Gram tile per column and spends 16 MFMAs per tile on a contraction with a vector of ones.
-// kernel_contract_kernel's frame: a wave owns 64 stationary rows (rows of B, KL_MS = 4 MFMA tiles) and KL_CW selected
-// columns and walks its share of the loop rows (rows of A) 16 at a time:
-//   G = L_tile S_tile'              mfma_f64_16x16x4(L, S): register r of a lane is (l = l0 + (lane >> 4) + 4 r, s = lane & 15)
-//   d2 = max(|s|^2 + |l|^2 - 2 G, 0)  ONCE per tile, in place of G
+// The frame (kt_*) with 64 stationary rows (rows of B, KL_MS = 4 MFMA tiles) and a chunk of KL_CW selected columns per
+// wave; d2 is kept, ONCE per tile, in place of G, and then
 //   per selected column: dj = L[l,c] - S[s,c],  e = exp(-max(d2 - dj^2, 0) / sigma),  acc[m][j] += e
 // The leave-out exponent is evaluated directly: K exp(+dj^2 / sigma) would be 0 * inf for rows that are far apart in
 // column c alone. Nothing is contracted by MFMA: a lane adds its own 4 loop rows per tile (one short chain, then one add
@@ -3161,39 +3126,20 @@ __global__ __launch_bounds__(NT, 2) void kernel_loo_colsums_kernel(
     double* __restrict__ out, int64_t ldo, int64_t split_stride, int stiles, int nchunks, int nsplit, int ltiles,
     int64_t ntasks) {
   __shared__ double etab[32];
-  if (threadIdx.x < 32) etab[threadIdx.x] = kExp2Tab32[threadIdx.x];
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (w >= ntasks) return;
-  const int st = (int)(w % stiles);
-  const int cc = (int)((w / stiles) % nchunks);
-  const int sp = (int)(w / ((int64_t)stiles * nchunks));
-  const int s0 = st * 16 * KL_MS;
+  kt_exp_table(etab);
+  KtTask k;
+  if (!kt_task(k, stiles, nchunks, ntasks)) return;
+  const int sp = (int)k.part, cc = k.cc;
+  const int s0 = k.st * 16 * KL_MS;
   // the chunks share the columns evenly (widths differ by at most one, none above KL_CW)
   const int c0 = (int)((int64_t)NC * cc / nchunks), ncw = (int)((int64_t)NC * (cc + 1) / nchunks) - c0;
-  const int t_begin = (int)((int64_t)ltiles * sp / nsplit), t_end = (int)((int64_t)ltiles * (sp + 1) / nsplit);
-  const int lm = lane & 15, lk = lane >> 4;
-  const int steps = (P + 3) / 4;
+  const int t_begin = kt_split_begin(ltiles, sp, nsplit), t_end = kt_split_begin(ltiles, sp + 1, nsplit);
+  const int lane = threadIdx.x & 63, lm = lane & 15, lk = lane >> 4;
 
   int srow[KL_MS];
-  double ns[KL_MS];
-#pragma unroll
-  for (int m = 0; m < KL_MS; ++m) {
-    srow[m] = min(s0 + 16 * m + lm, NS - 1);
-    ns[m] = nrm_s[srow[m]];
-  }
-  // stationary fragments (k >= P zeroed: the loop side then reads a clamped, finite value)
-  double sf[KL_MS][KS > 0 ? KS : 1];
-  if (KS > 0) {
-#pragma unroll
-    for (int m = 0; m < KL_MS; ++m)
-#pragma unroll
-      for (int t = 0; t < (KS > 0 ? KS : 1); ++t) {
-        const int k = 4 * t + lk;
-        sf[m][t] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
-      }
-  }
+  double ns[KL_MS], sf[KL_MS][KS > 0 ? KS : 1];
+  kt_stationary<KL_MS, KS>(srow, ns, sf, S, lds, NS, nrm_s, P, s0);
+  const int ms = KL_MS, ks = KS > 0 ? KS : 1;   // kt_gram's trip counts (by reference: see there)
   // the chunk's columns (wave-uniform; one past the chunk's end repeats its last column and is never accumulated) and
   // the stationary rows' values in them
   int64_t coff[KL_CW];
@@ -3225,37 +3171,12 @@ __global__ __launch_bounds__(NT, 2) void kernel_loo_colsums_kernel(
 #pragma unroll
     for (int r = 0; r < 4; ++r) lv[r] = lp[r][coff[0]];
     d4 g[KL_MS];
-#pragma unroll
-    for (int m = 0; m < KL_MS; ++m) g[m] = (d4){0.0, 0.0, 0.0, 0.0};
-    if (KS > 0) {
-      double lf[KS > 0 ? KS : 1];
-#pragma unroll
-      for (int s = 0; s < (KS > 0 ? KS : 1); ++s) lf[s] = L[lrow + (int64_t)min(4 * s + lk, P - 1) * ldl];
-#pragma unroll
-      for (int s = 0; s < (KS > 0 ? KS : 1); ++s)
-#pragma unroll
-        for (int m = 0; m < KL_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sf[m][s], g[m], 0, 0, 0);
-    } else {
-      for (int s0k = 0; s0k < steps; s0k += 4) {
-        double lf[4], sg[KL_MS][4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int k = 4 * (s0k + s) + lk;
-          lf[s] = L[lrow + (int64_t)min(k, P - 1) * ldl];
-#pragma unroll
-          for (int m = 0; m < KL_MS; ++m) sg[m][s] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-          for (int m = 0; m < KL_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sg[m][s], g[m], 0, 0, 0);
-      }
-    }
-    // the squared distance over ALL columns in place of G, once per tile (kernel_block_wave_kernel's epilogue)
+    kt_gram<KL_MS, KS>(g, srow, sf, S, lds, L, ldl, lrow, P, ms, ks);
+    // the squared distance over ALL columns in place of G, once per tile
 #pragma unroll
     for (int m = 0; m < KL_MS; ++m)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) g[m][r] = fmax(fma(-2.0, g[m][r], ns[m] + nl[r]), 0.0);
+      for (int r = 0; r < 4; ++r) g[m][r] = kt_dist2(g[m][r], ns[m], nl[r]);
 #pragma unroll
     for (int j = 0; j < KL_CW; ++j) {
       if (j < ncw) {                          // (wave-uniform)
@@ -3282,18 +3203,7 @@ __global__ __launch_bounds__(NT, 2) void kernel_loo_colsums_kernel(
       }
     }
   }
-  // the four lane groups hold the sums over the loop rows l = (lane >> 4) mod 4 of the same stationary rows
-  double* dst = out + (int64_t)sp * split_stride;
-#pragma unroll
-  for (int j = 0; j < KL_CW; ++j)
-#pragma unroll
-    for (int m = 0; m < KL_MS; ++m) {
-      double a = acc[m][j];
-      a += __shfl_xor(a, 16, 64);
-      a += __shfl_xor(a, 32, 64);
-      const int s = s0 + 16 * m + lm;
-      if (lk == 0 && j < ncw && s < NS) dst[s + (int64_t)(c0 + j) * ldo] = a;
-    }
+  kt_store_lane_sums<KL_MS, KL_CW>(acc, out + (int64_t)sp * split_stride, ldo, s0, c0, ncw, NS);
 }
 
 // out (ns x n_cols, ldo) for operands that are already centred, with their squared row norms: S the stationary rows
@@ -3301,25 +3211,11 @@ __global__ __launch_bounds__(NT, 2) void kernel_loo_colsums_kernel(
 static int kernel_loo_colsums_centred(bigkrls_ctx* ctx, const double* S, int64_t ns, int64_t lds, const double* nrm_s,
                                       const double* L, int64_t nl, int64_t ldl, const double* nrm_l, int64_t p,
                                       double sigma, const int64_t* h_cols, int64_t n_cols, double* out, int64_t ldo) {
-  const int steps = (int)((p + 3) / 4);
-  const int ks = steps <= 8 ? steps : 0;
   using KlFn = void (*)(const double*, int64_t, int, const double*, int64_t, int, int, const double*, const double*,
                         double, LooCols, int, double*, int64_t, int64_t, int, int, int, int, int64_t);
-  KlFn fn = nullptr;
-  switch (ks) {
-    case 1: fn = kernel_loo_colsums_kernel<1>; break;
-    case 2: fn = kernel_loo_colsums_kernel<2>; break;
-    case 3: fn = kernel_loo_colsums_kernel<3>; break;
-    case 4: fn = kernel_loo_colsums_kernel<4>; break;
-    case 5: fn = kernel_loo_colsums_kernel<5>; break;
-    case 6: fn = kernel_loo_colsums_kernel<6>; break;
-    case 7: fn = kernel_loo_colsums_kernel<7>; break;
-    case 8: fn = kernel_loo_colsums_kernel<8>; break;
-    default: fn = kernel_loo_colsums_kernel<0>; break;
-  }
-  int cap = 0;
-  BK_TRY(resident_capacity(ctx, (const void*)fn, &cap, NT));
-  const int64_t slots = (int64_t)cap * (NT / 64);
+  const KlFn fn = with_ks(ks_of(p), [](auto ks) -> KlFn { return kernel_loo_colsums_kernel<decltype(ks)::value>; });
+  int64_t slots = 0;
+  BK_TRY(wave_slots(ctx, (const void*)fn, &slots));
   const int64_t stiles = (ns + 16 * KL_MS - 1) / (16 * KL_MS);
   const int64_t ltiles = (nl + 15) / 16;
   for (int64_t g0 = 0; g0 < n_cols; g0 += KL_GROUP) {
@@ -3327,39 +3223,17 @@ static int kernel_loo_colsums_centred(bigkrls_ctx* ctx, const double* S, int64_t
     LooCols lc;
     for (int64_t j = 0; j < KL_GROUP; ++j) lc.c[j] = (int)h_cols[g0 + std::min(j, nc - 1)];
     const int64_t nchunks = (nc + KL_CW - 1) / KL_CW;
-    // loop splits: kernel_contract_centred's model (rounds of resident waves x loop tiles per wave) and limits
-    const int64_t base = stiles * nchunks;
-    const int64_t max_split =
-        std::max<int64_t>(1, std::min<int64_t>({(int64_t)64, ltiles / 16, (64ll << 20) / (ns * nc * (int64_t)sizeof(double))}));
-    int64_t nsplit = 1;
-    double best = (double)((base + slots - 1) / slots);
-    for (int64_t s = 2; s <= max_split; ++s) {
-      const double cost = (double)((base * s + slots - 1) / slots) / (double)s;
-      if (cost < best * 0.98) { best = cost; nsplit = s; }
-    }
-    const int64_t ntasks = base * nsplit;
+    const int64_t nsplit = plan_loop_splits(stiles * nchunks, slots, ltiles, ns * nc * (int64_t)sizeof(double));
+    const int64_t ntasks = stiles * nchunks * nsplit;
     BK_REQUIRE((ntasks + 3) / 4 < (1ll << 31), "kernel_loo_colsums: too many tiles");
-    double* og = out + g0 * ldo;
-    double* dst = og;
-    int64_t ldd = ldo, split_stride = 0;
-    if (nsplit > 1) {
-      void* pp = nullptr;
-      BK_TRY(ws_get(ctx, SLOT_LOO_PART, nsplit * ns * nc * (int64_t)sizeof(double), &pp));
-      dst = (double*)pp;
-      ldd = ns;
-      split_stride = ns * nc;
-    }
-    BK_TRY(prof_begin(ctx, "kernel_loo_colsums", (double)ns * (double)nl * (double)nc));
-    hipLaunchKernelGGL(fn, dim3((unsigned)((ntasks + 3) / 4)), dim3(NT), 0, ctx->stream, S, lds, (int)ns, L, ldl, (int)nl,
-                       (int)p, nrm_s, nrm_l, -1.0 / sigma, lc, (int)nc, dst, ldd, split_stride, (int)stiles, (int)nchunks,
-                       (int)nsplit, (int)ltiles, ntasks);
-    BK_CHECK_LAUNCH();
-    if (nsplit > 1) {
-      const int blocks = (int)std::min<int64_t>((ns * nc + 255) / 256, 4096);
-      hipLaunchKernelGGL(contract_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (int)ns, (int)nc, (int)nsplit,
-                         (const double*)dst, og, ldo);
-      BK_CHECK_LAUNCH();
-    }
+    BK_TRY(launch_loop_splits(ctx, SLOT_LOO_PART, nsplit, ns, nc, out + g0 * ldo, ldo, nullptr,
+                              [&](double* dst, int64_t ldd, int64_t split_stride) -> int {
+      BK_TRY(prof_begin(ctx, "kernel_loo_colsums", (double)ns * (double)nl * (double)nc));
+      hipLaunchKernelGGL(fn, dim3((unsigned)((ntasks + 3) / 4)), dim3(NT), 0, ctx->stream, S, lds, (int)ns, L, ldl,
+                         (int)nl, (int)p, nrm_s, nrm_l, -1.0 / sigma, lc, (int)nc, dst, ldd, split_stride, (int)stiles,
+                         (int)nchunks, (int)nsplit, (int)ltiles, ntasks);
+      return BIGKRLS_OK;
+    }));
     BK_TRY(prof_end(ctx, "kernel_loo_colsums"));
   }
   return BIGKRLS_OK;
@@ -3389,9 +3263,8 @@ int kernel_loo_colsums(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda
 // ---------------------------------------------------------------------------
 // out[l, e] = sum_i wgt exp(-max(d2(i,l) - dc^2 - [kind = 2] dj^2, 0) / sigma), dc = A[i,c] - B[l,c], dj = A[i,j] - B[l,j],
 // for entries e = (kind, c, j):  kind 0: wgt = 1 (kernel_loo_colsums' quantity);  kind 1: wgt = B[l,j] - A[i,j];
-// kind 2: wgt = 1 and column j left out as well. kernel_loo_colsums_kernel's frame (64 stationary rows per wave, loop
-// rows 16 at a time, d2 once per tile, lane-group shuffles after the loop, loop splits through contract_reduce_kernel),
-// with the chunk redefined: the host sorts the entries by c and a chunk holds up to CW entries of ONE c, so
+// kind 2: wgt = 1 and column j left out as well. kernel_loo_colsums_kernel's use of the frame (d2 once per tile,
+// lane-group sums) with the chunk redefined: the host sorts the entries by c and a chunk holds up to CW entries of ONE c, so
 //   base = max(d2 - dc^2, 0)                        once per chunk and row pair,
 //   e01  = exp(-base / sigma)                       once for ALL kind-0 and kind-1 entries of the chunk,
 //   kind 0: acc += e01;   kind 1: acc += e01 (S[s,j] - L[l,j])   -- one fused multiply-add on e01, no further exp;
@@ -3421,38 +3294,19 @@ __global__ __launch_bounds__(NT, 2) void kernel_loo_moments_kernel(
     double* __restrict__ out, int64_t ldo, int64_t split_stride, int stiles, int nchunks, int nsplit, int ltiles,
     int64_t ntasks) {
   __shared__ double etab[32];
-  if (threadIdx.x < 32) etab[threadIdx.x] = kExp2Tab32[threadIdx.x];
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (w >= ntasks) return;
-  const int st = (int)(w % stiles);
-  const int cc = (int)((w / stiles) % nchunks);
-  const int sp = (int)(w / ((int64_t)stiles * nchunks));
-  const int s0 = st * 16 * KL_MS;
-  const int e0 = ent.begin[cc], ncw = ent.begin[cc + 1] - e0;   // (1 <= ncw <= CW)
-  const int t_begin = (int)((int64_t)ltiles * sp / nsplit), t_end = (int)((int64_t)ltiles * (sp + 1) / nsplit);
-  const int lm = lane & 15, lk = lane >> 4;
-  const int steps = (P + 3) / 4;
+  kt_exp_table(etab);
+  KtTask k;
+  if (!kt_task(k, stiles, nchunks, ntasks)) return;
+  const int sp = (int)k.part;
+  const int s0 = k.st * 16 * KL_MS;
+  const int e0 = ent.begin[k.cc], ncw = ent.begin[k.cc + 1] - e0;   // (1 <= ncw <= CW)
+  const int t_begin = kt_split_begin(ltiles, sp, nsplit), t_end = kt_split_begin(ltiles, sp + 1, nsplit);
+  const int lane = threadIdx.x & 63, lm = lane & 15, lk = lane >> 4;
 
   int srow[KL_MS];
-  double ns[KL_MS];
-#pragma unroll
-  for (int m = 0; m < KL_MS; ++m) {
-    srow[m] = min(s0 + 16 * m + lm, NS - 1);
-    ns[m] = nrm_s[srow[m]];
-  }
-  // stationary fragments (k >= P zeroed: the loop side then reads a clamped, finite value)
-  double sf[KL_MS][KS > 0 ? KS : 1];
-  if (KS > 0) {
-#pragma unroll
-    for (int m = 0; m < KL_MS; ++m)
-#pragma unroll
-      for (int t = 0; t < (KS > 0 ? KS : 1); ++t) {
-        const int k = 4 * t + lk;
-        sf[m][t] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
-      }
-  }
+  double ns[KL_MS], sf[KL_MS][KS > 0 ? KS : 1];
+  kt_stationary<KL_MS, KS>(srow, ns, sf, S, lds, NS, nrm_s, P, s0);
+  const int ms = KL_MS, ks = KS > 0 ? KS : 1;   // kt_gram's trip counts (by reference: see there)
   // the chunk's column c and its entries (wave-uniform; a slot past the chunk's end has kind -1 and is never
   // accumulated), and the stationary rows' values in their columns
   const int ccol = ent.c[e0];
@@ -3498,32 +3352,7 @@ __global__ __launch_bounds__(NT, 2) void kernel_loo_moments_kernel(
 #pragma unroll
       for (int r = 0; r < 4; ++r) lv[j][r] = lp[r][joff[j]];
     d4 g[KL_MS];
-#pragma unroll
-    for (int m = 0; m < KL_MS; ++m) g[m] = (d4){0.0, 0.0, 0.0, 0.0};
-    if (KS > 0) {
-      double lf[KS > 0 ? KS : 1];
-#pragma unroll
-      for (int s = 0; s < (KS > 0 ? KS : 1); ++s) lf[s] = L[lrow + (int64_t)min(4 * s + lk, P - 1) * ldl];
-#pragma unroll
-      for (int s = 0; s < (KS > 0 ? KS : 1); ++s)
-#pragma unroll
-        for (int m = 0; m < KL_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sf[m][s], g[m], 0, 0, 0);
-    } else {
-      for (int s0k = 0; s0k < steps; s0k += 4) {
-        double lf[4], sg[KL_MS][4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const int k = 4 * (s0k + s) + lk;
-          lf[s] = L[lrow + (int64_t)min(k, P - 1) * ldl];
-#pragma unroll
-          for (int m = 0; m < KL_MS; ++m) sg[m][s] = k < P ? S[srow[m] + (int64_t)k * lds] : 0.0;
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-          for (int m = 0; m < KL_MS; ++m) g[m] = __builtin_amdgcn_mfma_f64_16x16x4f64(lf[s], sg[m][s], g[m], 0, 0, 0);
-      }
-    }
+    kt_gram<KL_MS, KS>(g, srow, sf, S, lds, L, ldl, lrow, P, ms, ks);
 #pragma unroll
     for (int m = 0; m < KL_MS; ++m) {
       double tsum[CW];
@@ -3531,8 +3360,8 @@ __global__ __launch_bounds__(NT, 2) void kernel_loo_moments_kernel(
       for (int j = 0; j < CW; ++j) tsum[j] = 0.0;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        // the squared distance over all columns (kernel_loo_colsums_kernel's), then without column c
-        const double d2 = fmax(fma(-2.0, g[m][r], ns[m] + nl[r]), 0.0);
+        // the squared distance over all columns, then without column c
+        const double d2 = kt_dist2(g[m][r], ns[m], nl[r]);
         const double dc = lc[r] - scv[m];
         const double base = fmax(fma(-dc, dc, d2), 0.0);
         double e01 = 0.0;
@@ -3554,18 +3383,7 @@ __global__ __launch_bounds__(NT, 2) void kernel_loo_moments_kernel(
       for (int j = 0; j < CW; ++j) acc[m][j] += tsum[j];
     }
   }
-  // the four lane groups hold the sums over the loop rows l = (lane >> 4) mod 4 of the same stationary rows
-  double* dst = out + (int64_t)sp * split_stride;
-#pragma unroll
-  for (int j = 0; j < CW; ++j)
-#pragma unroll
-    for (int m = 0; m < KL_MS; ++m) {
-      double a = acc[m][j];
-      a += __shfl_xor(a, 16, 64);
-      a += __shfl_xor(a, 32, 64);
-      const int s = s0 + 16 * m + lm;
-      if (lk == 0 && j < ncw && s < NS) dst[s + (int64_t)(e0 + j) * ldo] = a;
-    }
+  kt_store_lane_sums<KL_MS, CW>(acc, out + (int64_t)sp * split_stride, ldo, s0, e0, ncw, NS);
 }
 
 // out[s, dest.d[blockIdx.y]] = src[s, blockIdx.y]: a launch's columns (sorted by c) to the caller's entry order
@@ -3627,26 +3445,15 @@ int kernel_loo_moments(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda
   // the rows of B are stationary, the rows of A the loop (kernel_contract's trans = 1)
   const double *S = co.B, *L = co.A, *nrm_s = co.nb, *nrm_l = co.na;
   const int64_t ns = v, nl = u, lds = co.ldb, ldl = co.lda;
-  const int steps = (int)((p + 3) / 4);
-  const int ks = steps <= 8 ? steps : 0;
-  const int64_t cw = ks == 8 ? KM_CW_KS8 : KM_CW;
+  const int64_t cw = ks_of(p) == 8 ? KM_CW_KS8 : KM_CW;
   using KmFn = void (*)(const double*, int64_t, int, const double*, int64_t, int, int, const double*, const double*,
                         double, LooMomentEntries, double*, int64_t, int64_t, int, int, int, int, int64_t);
-  KmFn fn = nullptr;
-  switch (ks) {
-    case 1: fn = kernel_loo_moments_kernel<1, KM_CW>; break;
-    case 2: fn = kernel_loo_moments_kernel<2, KM_CW>; break;
-    case 3: fn = kernel_loo_moments_kernel<3, KM_CW>; break;
-    case 4: fn = kernel_loo_moments_kernel<4, KM_CW>; break;
-    case 5: fn = kernel_loo_moments_kernel<5, KM_CW>; break;
-    case 6: fn = kernel_loo_moments_kernel<6, KM_CW>; break;
-    case 7: fn = kernel_loo_moments_kernel<7, KM_CW>; break;
-    case 8: fn = kernel_loo_moments_kernel<8, KM_CW_KS8>; break;
-    default: fn = kernel_loo_moments_kernel<0, KM_CW>; break;
-  }
-  int cap = 0;
-  BK_TRY(resident_capacity(ctx, (const void*)fn, &cap, NT));
-  const int64_t slots = (int64_t)cap * (NT / 64);
+  const KmFn fn = with_ks(ks_of(p), [](auto ks) -> KmFn {
+    constexpr int KS = decltype(ks)::value;
+    return kernel_loo_moments_kernel<KS, KS == 8 ? KM_CW_KS8 : KM_CW>;
+  });
+  int64_t slots = 0;
+  BK_TRY(wave_slots(ctx, (const void*)fn, &slots));
   const int64_t stiles = (ns + 16 * KL_MS - 1) / (16 * KL_MS);
   const int64_t ltiles = (nl + 15) / 16;
   for (int64_t g0 = 0; g0 < n_sorted; g0 += KL_GROUP) {
@@ -3680,42 +3487,19 @@ int kernel_loo_moments(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda
       r0 = r1;
     }
     for (int64_t i = nchunks; i <= KL_GROUP; ++i) le.begin[i] = (int)nc;
-    // loop splits: kernel_contract_centred's model (rounds of resident waves x loop tiles per wave) and limits
-    const int64_t base = stiles * nchunks;
-    const int64_t max_split =
-        std::max<int64_t>(1, std::min<int64_t>({(int64_t)64, ltiles / 16, (64ll << 20) / (ns * nc * (int64_t)sizeof(double))}));
-    int64_t nsplit = 1;
-    double best = (double)((base + slots - 1) / slots);
-    for (int64_t s = 2; s <= max_split; ++s) {
-      const double cost = (double)((base * s + slots - 1) / slots) / (double)s;
-      if (cost < best * 0.98) { best = cost; nsplit = s; }
-    }
-    const int64_t ntasks = base * nsplit;
+    const int64_t nsplit = plan_loop_splits(stiles * nchunks, slots, ltiles, ns * nc * (int64_t)sizeof(double));
+    const int64_t ntasks = stiles * nchunks * nsplit;
     BK_REQUIRE((ntasks + 3) / 4 < (1ll << 31), "kernel_loo_moments: too many tiles");
-    // the partial sums of the splits, and behind them the launch's columns where they are scattered afterwards
-    const int64_t part_doubles = nsplit > 1 ? nsplit * ns * nc : 0, tmp_doubles = in_place ? 0 : ns * nc;
-    double *part = nullptr, *tmp = nullptr;
-    if (part_doubles + tmp_doubles > 0) {
-      void* pp = nullptr;
-      BK_TRY(ws_get(ctx, SLOT_LOO_PART, (part_doubles + tmp_doubles) * (int64_t)sizeof(double), &pp));
-      part = (double*)pp;
-      tmp = part + part_doubles;
-    }
-    double* og = in_place ? out + order[(size_t)g0] * ldo : tmp;   // where the launch's columns end up first
-    const int64_t ldg = in_place ? ldo : ns;
-    double* dst = nsplit > 1 ? part : og;
-    const int64_t ldd = nsplit > 1 ? ns : ldg, split_stride = nsplit > 1 ? ns * nc : 0;
-    BK_TRY(prof_begin(ctx, "kernel_loo_moments", (double)ns * (double)nl * (double)nexp));
-    hipLaunchKernelGGL(fn, dim3((unsigned)((ntasks + 3) / 4)), dim3(NT), 0, ctx->stream, S, lds, (int)ns, L, ldl, (int)nl,
-                       (int)p, nrm_s, nrm_l, -1.0 / sigma, le, dst, ldd, split_stride, (int)stiles, (int)nchunks,
-                       (int)nsplit, (int)ltiles, ntasks);
-    BK_CHECK_LAUNCH();
-    if (nsplit > 1) {
-      const int blocks = (int)std::min<int64_t>((ns * nc + 255) / 256, 4096);
-      hipLaunchKernelGGL(contract_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (int)ns, (int)nc, (int)nsplit,
-                         (const double*)part, og, ldg);
-      BK_CHECK_LAUNCH();
-    }
+    // the launch's columns go into out at once, or into a staging buffer and are scattered from there afterwards
+    double* tmp = nullptr;
+    BK_TRY(launch_loop_splits(ctx, SLOT_LOO_PART, nsplit, ns, nc, in_place ? out + order[(size_t)g0] * ldo : nullptr, ldo,
+                              &tmp, [&](double* dst, int64_t ldd, int64_t split_stride) -> int {
+      BK_TRY(prof_begin(ctx, "kernel_loo_moments", (double)ns * (double)nl * (double)nexp));
+      hipLaunchKernelGGL(fn, dim3((unsigned)((ntasks + 3) / 4)), dim3(NT), 0, ctx->stream, S, lds, (int)ns, L, ldl,
+                         (int)nl, (int)p, nrm_s, nrm_l, -1.0 / sigma, le, dst, ldd, split_stride, (int)stiles,
+                         (int)nchunks, (int)nsplit, (int)ltiles, ntasks);
+      return BIGKRLS_OK;
+    }));
     if (!in_place) {
       const int blocks = (int)std::min<int64_t>((ns + 255) / 256, 1024);
       hipLaunchKernelGGL(loo_moments_scatter_kernel, dim3(blocks, (unsigned)nc), dim3(256), 0, ctx->stream, (int)ns,
