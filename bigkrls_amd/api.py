@@ -586,6 +586,66 @@ def _factors(object, ctx):
     return Qd, wv
 
 
+def _effects_open(name, object, newdata, vcov, se, gated=False, default=None):
+    """The common opening of the post-estimation functions, up to what needs no device: the class check, the form of
+    vcov.est.c, the se-without-vcov error, the multi-GPU refusal (under `name`), X, newdata and the two-valued columns.
+    gated: without se no variance is computed at all (form None, a multi-GPU object accepted). default: what
+    newdata=None means -- None: not allowed, "training": X itself, "null": the native call takes a null pointer for the
+    training rows (nd_init and nd None, u = n). Returns Xh, n, p, nd_init, nd, u, isbin, form."""
+    if not isinstance(object, BigKRLS):
+        raise TypeError("Object not of class 'bigKRLS'")
+    form = _vcov_choice(object, vcov)
+    if gated and not se:
+        form = None
+    if se and form is None:
+        raise ValueError("recompute bigKRLS object with bigKRLS(,vcov.est=TRUE) to compute standard errors")
+    if (se or not gated) and ("vcov.est.c.cols" in object or "rows" in object) and form != "factors":
+        raise NotImplementedError(f"{name} of a multi-GPU fit (sharded vcov.est.c.cols) is not supported; "
+                                  "refit on one GPU or with vcov_form=\"factors\"")
+    Xh = np.asfortranarray(np.asarray(object["X"], dtype=np.float64))
+    n, p = Xh.shape
+    nd_init, nd, u = None, None, n
+    if newdata is not None or default != "null":
+        nd_init = Xh if newdata is None and default == "training" else _as_host_matrix(newdata)
+        nd = np.array(nd_init, dtype=np.float64, order="F")
+        if nd.ndim != 2 or nd.shape[1] != p:
+            raise ValueError("ncol(newdata) differs from ncol(X) from fitted bigKRLS object")
+        u = nd.shape[0]
+        if u < 1:
+            raise ValueError("newdata has no rows")
+        if not np.all(np.isfinite(nd)):
+            raise ValueError("newdata contains missing or infinite values")
+    isbin = np.array([np.unique(Xh[:, j]).size == 2 for j in range(p)])          # the fit's rule (R/bigKRLS.R:242)
+    return Xh, n, p, nd_init, nd, u, isbin, form
+
+
+def _effects_device(object, form, ctx, p):
+    """... and, after the function's own validation, what the native call takes: the context, vcov.est.c on the device in
+    the chosen form, y and the coefficients, the five vcov arguments of the C ABI (d_vcov_c, d_Q, ldq, k, h_w), the labels.
+    Returns ctx, Vd, Qd, wv, yv, coeffs, vcov_args, xlabs."""
+    ctx = ctx or object.get("_ctx") or default_context()
+    V = object.get("vcov.est.c") if form == "dense" else None
+    Vd = None if V is None else (V if is_device_matrix(V) else ctx.from_numpy(np.asarray(V, dtype=np.float64)))
+    Qd, wv = _factors(object, ctx) if form == "factors" else (None, None)
+    yv = np.ascontiguousarray(np.asarray(object["y"], dtype=np.float64).ravel())
+    coeffs = np.ascontiguousarray(np.asarray(object["coeffs"], dtype=np.float64).ravel())
+    vcov_args = (Vd.ptr if form == "dense" else None, Qd.ptr if form == "factors" else None,
+                 Qd.ld if form == "factors" else 0, Qd.ncol if form == "factors" else 0,
+                 wv.ctypes.data if form == "factors" else None)
+    xlabs = list(object.get("xlabs") or [f"x{i + 1}" for i in range(p)])
+    return ctx, Vd, Qd, wv, yv, coeffs, vcov_args, xlabs
+
+
+def _check_binary_newdata(Xh, nd, isbin, cols):
+    """newdata must hold one of the two training values in every binary column of cols (0-based, in this order)."""
+    for j in cols:
+        if isbin[j]:
+            lo, hi = Xh[:, j].min(), Xh[:, j].max()
+            if not np.all((nd[:, j] == lo) | (nd[:, j] == hi)):
+                raise ValueError(f"newdata column {j + 1} is binary in the training data; its values must be "
+                                 f"one of the two training values ({lo:g}, {hi:g})")
+
+
 def predict(object: BigKRLS, newdata, se_pred=False, correct_SE=True, ytest=None,
             ctx: Optional[Context] = None, matrices=True, vcov: Optional[str] = None) -> BigKRLSPredicted:
     """predict.bigKRLS (R/bigKRLS.R:547-637); the numeric body (:590-621) is ONE call into the
@@ -714,25 +774,7 @@ def marginal_effects(object: BigKRLS, newdata, which_derivatives=None, ctx: Opti
     fast form: 2 u n lastkeeper flops per column against 2 u n^2 from the matrix; the new points are taken in row blocks
     of at most 1 GiB of test kernel either way. Raises the ValueError of predict(se_pred=True) when the object carries
     neither form. With se=False the result has exactly the keys it always had."""
-    if not isinstance(object, BigKRLS):
-        raise TypeError("Object not of class 'bigKRLS'")
-    form = _vcov_choice(object, vcov)
-    if se and form is None:
-        raise ValueError("recompute bigKRLS object with bigKRLS(,vcov.est=TRUE) to compute standard errors")
-    if ("vcov.est.c.cols" in object or "rows" in object) and form != "factors":
-        raise NotImplementedError("marginal_effects of a multi-GPU fit (sharded vcov.est.c.cols) is not supported; "
-                                  "refit on one GPU or with vcov_form=\"factors\"")
-    Xh = np.asfortranarray(np.asarray(object["X"], dtype=np.float64))
-    n, p = Xh.shape
-    nd_init = _as_host_matrix(newdata)
-    nd = np.array(nd_init, dtype=np.float64, order="F")
-    if nd.ndim != 2 or nd.shape[1] != p:
-        raise ValueError("ncol(newdata) differs from ncol(X) from fitted bigKRLS object")
-    u = nd.shape[0]
-    if u < 1:
-        raise ValueError("newdata has no rows")
-    if not np.all(np.isfinite(nd)):
-        raise ValueError("newdata contains missing or infinite values")
+    Xh, n, p, nd_init, nd, u, isbin, form = _effects_open("marginal_effects", object, newdata, vcov, se)
     if which_derivatives is None:
         which_derivatives = object.get("which.derivatives")
     if which_derivatives is None:
@@ -741,19 +783,8 @@ def marginal_effects(object: BigKRLS, newdata, which_derivatives=None, ctx: Opti
         which = [int(i) for i in np.atleast_1d(which_derivatives)]
         if not which or not all(1 <= i <= p for i in which):
             raise ValueError("which.derivatives must index columns of X")
-    isbin = np.array([np.unique(Xh[:, j]).size == 2 for j in range(p)])          # the fit's rule (R/bigKRLS.R:242)
-    for j in sorted(set(i - 1 for i in which)):
-        if isbin[j]:
-            lo, hi = Xh[:, j].min(), Xh[:, j].max()
-            if not np.all((nd[:, j] == lo) | (nd[:, j] == hi)):
-                raise ValueError(f"newdata column {j + 1} is binary in the training data; its values must be "
-                                 f"one of the two training values ({lo:g}, {hi:g})")
-    ctx = ctx or object.get("_ctx") or default_context()
-    V = object.get("vcov.est.c") if form == "dense" else None
-    Vd = None if V is None else (V if is_device_matrix(V) else ctx.from_numpy(np.asarray(V, dtype=np.float64)))
-    Qd, wv = _factors(object, ctx) if form == "factors" else (None, None)
-    yv = np.ascontiguousarray(np.asarray(object["y"], dtype=np.float64).ravel())
-    coeffs = np.ascontiguousarray(np.asarray(object["coeffs"], dtype=np.float64).ravel())
+    _check_binary_newdata(Xh, nd, isbin, sorted(set(i - 1 for i in which)))
+    ctx, Vd, Qd, wv, yv, coeffs, vcov_args, xlabs = _effects_device(object, form, ctx, p)
     which_arr = np.ascontiguousarray(which, dtype=np.int64)
     nj = which_arr.size
     D = np.empty((u, nj), dtype=np.float64, order="F")
@@ -768,7 +799,6 @@ def marginal_effects(object: BigKRLS, newdata, which_derivatives=None, ctx: Opti
                      float(object["sigma"]), which_arr.ctypes.data, nj, nd.ctypes.data, u,
                      Vd.ptr if Vd is not None else None, D.ctypes.data, avg.ctypes.data,
                      var.ctypes.data if var is not None else None)
-    xlabs = list(object.get("xlabs") or [f"x{i + 1}" for i in range(p)])
     out = {"derivatives": D, "avgderivatives": avg[None, :],
            "var.avgderivatives": None if var is None else var[None, :],
            "which.derivatives": which, "binaryindicator": isbin[which_arr - 1],
@@ -777,9 +807,7 @@ def marginal_effects(object: BigKRLS, newdata, which_derivatives=None, ctx: Opti
         sed = np.empty((u, nj), dtype=np.float64, order="F")
         _call_native("bigkrls_marginal_effects_se", ctx.handle, Xh.ctypes.data, n, p, yv.ctypes.data,
                      coeffs.ctypes.data, float(object["sigma"]), which_arr.ctypes.data, nj, nd.ctypes.data, u,
-                     Vd.ptr if form == "dense" else None, Qd.ptr if form == "factors" else None,
-                     Qd.ld if form == "factors" else 0, Qd.ncol if form == "factors" else 0,
-                     wv.ctypes.data if form == "factors" else None, int(_block_rows), sed.ctypes.data)
+                     *vcov_args, int(_block_rows), sed.ctypes.data)
         out["se.derivatives"] = sed
     return out
 
@@ -803,26 +831,8 @@ def interaction_effects(object: BigKRLS, newdata=None, pairs=None, which=None, s
     2 u n lastkeeper flops per pair in one pass of bigkrls_dev_gemm_modulated2); everything else in the result is
     bitwise what se=False returns. Variances carry the reference's factor 2 when a column of the pair is binary, so for
     a single new point se.interactions[0, i]**2 == var.avginteractions[0, i] for every pair."""
-    if not isinstance(object, BigKRLS):
-        raise TypeError("Object not of class 'bigKRLS'")
-    form = _vcov_choice(object, vcov)
-    if se and form is None:
-        raise ValueError("recompute bigKRLS object with bigKRLS(,vcov.est=TRUE) to compute standard errors")
-    if ("vcov.est.c.cols" in object or "rows" in object) and form != "factors":
-        raise NotImplementedError("interaction_effects of a multi-GPU fit (sharded vcov.est.c.cols) is not supported; "
-                                  "refit on one GPU or with vcov_form=\"factors\"")
-    Xh = np.asfortranarray(np.asarray(object["X"], dtype=np.float64))
-    n, p = Xh.shape
-    nd_init = Xh if newdata is None else _as_host_matrix(newdata)
-    nd = np.array(nd_init, dtype=np.float64, order="F")
-    if nd.ndim != 2 or nd.shape[1] != p:
-        raise ValueError("ncol(newdata) differs from ncol(X) from fitted bigKRLS object")
-    u = nd.shape[0]
-    if u < 1:
-        raise ValueError("newdata has no rows")
-    if not np.all(np.isfinite(nd)):
-        raise ValueError("newdata contains missing or infinite values")
-    isbin = np.array([np.unique(Xh[:, j]).size == 2 for j in range(p)])          # the fit's rule (R/bigKRLS.R:242)
+    Xh, n, p, nd_init, nd, u, isbin, form = _effects_open("interaction_effects", object, newdata, vcov, se,
+                                                         default="training")
     if pairs is None:
         if which is None:
             which = object.get("which.derivatives")
@@ -854,30 +864,16 @@ def interaction_effects(object: BigKRLS, newdata=None, pairs=None, which=None, s
         if (j, k) in ordered:
             raise ValueError(f"pair ({j}, {k}) is given more than once")
         ordered.append((j, k))
-    for j in sorted(set(c - 1 for pr in ordered for c in pr)):
-        if isbin[j]:
-            lo, hi = Xh[:, j].min(), Xh[:, j].max()
-            if not np.all((nd[:, j] == lo) | (nd[:, j] == hi)):
-                raise ValueError(f"newdata column {j + 1} is binary in the training data; its values must be "
-                                 f"one of the two training values ({lo:g}, {hi:g})")
-    ctx = ctx or object.get("_ctx") or default_context()
-    V = object.get("vcov.est.c") if form == "dense" else None
-    Vd = None if V is None else (V if is_device_matrix(V) else ctx.from_numpy(np.asarray(V, dtype=np.float64)))
-    Qd, wv = _factors(object, ctx) if form == "factors" else (None, None)
-    yv = np.ascontiguousarray(np.asarray(object["y"], dtype=np.float64).ravel())
-    coeffs = np.ascontiguousarray(np.asarray(object["coeffs"], dtype=np.float64).ravel())
+    _check_binary_newdata(Xh, nd, isbin, sorted(set(c - 1 for pr in ordered for c in pr)))
+    ctx, Vd, Qd, wv, yv, coeffs, vcov_args, xlabs = _effects_device(object, form, ctx, p)
     pair_arr = np.ascontiguousarray(ordered, dtype=np.int64)                      # m x 2 row-major: pair after pair
     m = len(ordered)
     vals = np.empty((u, m), dtype=np.float64, order="F")
     avg = np.empty(m)
     var = np.empty(m) if form is not None else None
-    vcov_args = (Vd.ptr if form == "dense" else None, Qd.ptr if form == "factors" else None,
-                 Qd.ld if form == "factors" else 0, Qd.ncol if form == "factors" else 0,
-                 wv.ctypes.data if form == "factors" else None)
     _call_native("bigkrls_interaction_effects", ctx.handle, Xh.ctypes.data, n, p, yv.ctypes.data, coeffs.ctypes.data,
                  float(object["sigma"]), pair_arr.ctypes.data, m, nd.ctypes.data, u, *vcov_args, vals.ctypes.data,
                  avg.ctypes.data, var.ctypes.data if var is not None else None)
-    xlabs = list(object.get("xlabs") or [f"x{i + 1}" for i in range(p)])
     out = {"interactions": vals, "avginteractions": avg[None, :],
            "var.avginteractions": None if var is None else var[None, :],
            "pairs": ordered, "pairlabs": [f"{xlabs[j - 1]}:{xlabs[k - 1]}" for j, k in ordered],
@@ -1010,28 +1006,9 @@ def partial_dependence(object: BigKRLS, which=None, grid=20, newdata=None, se: b
     "binaryindicator", "grid", "pd", "se.pd", "vcov.pd" (lists over the columns; the last two None without a variance),
     "first.difference", "se.first.difference" (1 x |J|, NaN for continuous columns; the second None without a
     variance) and "newdata"."""
-    if not isinstance(object, BigKRLS):
-        raise TypeError("Object not of class 'bigKRLS'")
-    form = _vcov_choice(object, vcov)
-    if not se:
-        form = None
-    if se and form is None:
-        raise ValueError("recompute bigKRLS object with bigKRLS(,vcov.est=TRUE) to compute standard errors")
-    if se and ("vcov.est.c.cols" in object or "rows" in object) and form != "factors":
-        raise NotImplementedError("marginal_effects of a multi-GPU fit (sharded vcov.est.c.cols) is not supported; "
-                                  "refit on one GPU or with vcov_form=\"factors\"")
-    Xh = np.asfortranarray(np.asarray(object["X"], dtype=np.float64))
-    n, p = Xh.shape
-    nd_init = nd = None
-    if newdata is not None:
-        nd_init = _as_host_matrix(newdata)
-        nd = np.array(nd_init, dtype=np.float64, order="F")
-        if nd.ndim != 2 or nd.shape[1] != p:
-            raise ValueError("ncol(newdata) differs from ncol(X) from fitted bigKRLS object")
-        if nd.shape[0] < 1:
-            raise ValueError("newdata has no rows")
-        if not np.all(np.isfinite(nd)):
-            raise ValueError("newdata contains missing or infinite values")
+    # (the multi-GPU refusal has always named marginal_effects here)
+    Xh, n, p, nd_init, nd, u, isbin, form = _effects_open("marginal_effects", object, newdata, vcov, se, gated=True,
+                                                         default="null")
     if which is None:
         which = object.get("which.derivatives")
     if which is None:
@@ -1040,7 +1017,6 @@ def partial_dependence(object: BigKRLS, which=None, grid=20, newdata=None, se: b
         which = [int(i) for i in np.atleast_1d(which)]
         if not which or not all(1 <= i <= p for i in which):
             raise ValueError("which.derivatives must index columns of X")
-    isbin = np.array([np.unique(Xh[:, j]).size == 2 for j in range(p)])          # the fit's rule (R/bigKRLS.R:242)
     explicit = not isinstance(grid, (int, np.integer))
     if explicit:
         grid = list(grid)
@@ -1064,12 +1040,7 @@ def partial_dependence(object: BigKRLS, which=None, grid=20, newdata=None, se: b
         elif not explicit:
             g = np.linspace(lo, hi, int(grid))
         grids.append(g)
-    ctx = ctx or object.get("_ctx") or default_context()
-    V = object.get("vcov.est.c") if form == "dense" else None
-    Vd = None if V is None else (V if is_device_matrix(V) else ctx.from_numpy(np.asarray(V, dtype=np.float64)))
-    Qd, wv = _factors(object, ctx) if form == "factors" else (None, None)
-    yv = np.ascontiguousarray(np.asarray(object["y"], dtype=np.float64).ravel())
-    coeffs = np.ascontiguousarray(np.asarray(object["coeffs"], dtype=np.float64).ravel())
+    ctx, Vd, Qd, wv, yv, coeffs, vcov_args, xlabs = _effects_device(object, form, ctx, p)
     which_arr = np.ascontiguousarray(which, dtype=np.int64)
     nj = which_arr.size
     sizes = np.array([g.size for g in grids], dtype=np.int64)
@@ -1084,11 +1055,8 @@ def partial_dependence(object: BigKRLS, which=None, grid=20, newdata=None, se: b
     if se and correct_SE and object.get("Neffective") is not None:                # predict(): R/bigKRLS.R:610-611
         neff = float(object["Neffective"])
     _call_native("bigkrls_partial_dependence", ctx.handle, Xh.ctypes.data, n, p, yv.ctypes.data, coeffs.ctypes.data,
-                 float(object["sigma"]), which_arr.ctypes.data, nj, nd.ctypes.data if nd is not None else None,
-                 nd.shape[0] if nd is not None else n, flat.ctypes.data, off.ctypes.data,
-                 Vd.ptr if form == "dense" else None, Qd.ptr if form == "factors" else None,
-                 Qd.ld if form == "factors" else 0, Qd.ncol if form == "factors" else 0,
-                 wv.ctypes.data if form == "factors" else None, neff, pd.ctypes.data,
+                 float(object["sigma"]), which_arr.ctypes.data, nj, nd.ctypes.data if nd is not None else None, u,
+                 flat.ctypes.data, off.ctypes.data, *vcov_args, neff, pd.ctypes.data,
                  sev.ctypes.data if se else None, cov.ctypes.data if se else None)
     cut = lambda v: [v[off[i]:off[i + 1]] for i in range(nj)]
     covs = None
@@ -1103,7 +1071,6 @@ def partial_dependence(object: BigKRLS, which=None, grid=20, newdata=None, se: b
             if se:
                 c = covs[i]
                 sefd[0, i] = np.sqrt(max(c[0, 0] + c[1, 1] - 2.0 * c[0, 1], 0.0))
-    xlabs = list(object.get("xlabs") or [f"x{i + 1}" for i in range(p)])
     return {"which": which, "xlabs": [xlabs[i - 1] for i in which], "binaryindicator": bin_sel, "grid": grids,
             "pd": cut(pd), "se.pd": cut(sev) if se else None, "vcov.pd": covs, "first.difference": fd,
             "se.first.difference": sefd, "newdata": nd_init}
@@ -1131,28 +1098,8 @@ def conditional_effects(object: BigKRLS, effect, along, grid=20, newdata=None, s
     "binary.moderator", "grid", "ce", "se.ce", "vcov.ce" (lists over the pairs; the last two None without a variance),
     "contrast" = ce(last grid value) - ce(first) and "se.contrast" from the covariance (1 x m; the second None without a
     variance), and "newdata"."""
-    if not isinstance(object, BigKRLS):
-        raise TypeError("Object not of class 'bigKRLS'")
-    form = _vcov_choice(object, vcov)
-    if not se:
-        form = None
-    if se and form is None:
-        raise ValueError("recompute bigKRLS object with bigKRLS(,vcov.est=TRUE) to compute standard errors")
-    if se and ("vcov.est.c.cols" in object or "rows" in object) and form != "factors":
-        raise NotImplementedError("conditional_effects of a multi-GPU fit (sharded vcov.est.c.cols) is not supported; "
-                                  "refit on one GPU or with vcov_form=\"factors\"")
-    Xh = np.asfortranarray(np.asarray(object["X"], dtype=np.float64))
-    n, p = Xh.shape
-    nd_init = nd = None
-    if newdata is not None:
-        nd_init = _as_host_matrix(newdata)
-        nd = np.array(nd_init, dtype=np.float64, order="F")
-        if nd.ndim != 2 or nd.shape[1] != p:
-            raise ValueError("ncol(newdata) differs from ncol(X) from fitted bigKRLS object")
-        if nd.shape[0] < 1:
-            raise ValueError("newdata has no rows")
-        if not np.all(np.isfinite(nd)):
-            raise ValueError("newdata contains missing or infinite values")
+    Xh, n, p, nd_init, nd, u, isbin, form = _effects_open("conditional_effects", object, newdata, vcov, se, gated=True,
+                                                         default="null")
 
     def columns(arg, name):
         try:
@@ -1163,7 +1110,6 @@ def conditional_effects(object: BigKRLS, effect, along, grid=20, newdata=None, s
             raise ValueError(f"{name} must index columns of X")
         return cols
     effects, alongs = columns(effect, "effect"), columns(along, "along")
-    isbin = np.array([np.unique(Xh[:, j]).size == 2 for j in range(p)])          # the fit's rule (R/bigKRLS.R:242)
     pairs = []
     for j in effects:
         for k in alongs:
@@ -1194,12 +1140,7 @@ def conditional_effects(object: BigKRLS, effect, along, grid=20, newdata=None, s
         elif not explicit:
             g = np.linspace(lo, hi, int(grid))
         grids.append(g)
-    ctx = ctx or object.get("_ctx") or default_context()
-    V = object.get("vcov.est.c") if form == "dense" else None
-    Vd = None if V is None else (V if is_device_matrix(V) else ctx.from_numpy(np.asarray(V, dtype=np.float64)))
-    Qd, wv = _factors(object, ctx) if form == "factors" else (None, None)
-    yv = np.ascontiguousarray(np.asarray(object["y"], dtype=np.float64).ravel())
-    coeffs = np.ascontiguousarray(np.asarray(object["coeffs"], dtype=np.float64).ravel())
+    ctx, Vd, Qd, wv, yv, coeffs, vcov_args, xlabs = _effects_device(object, form, ctx, p)
     pair_arr = np.ascontiguousarray(pairs, dtype=np.int64)                        # m x 2 row-major: pair after pair
     m = len(pairs)
     sizes = np.array([g.size for g in grids], dtype=np.int64)
@@ -1211,11 +1152,8 @@ def conditional_effects(object: BigKRLS, effect, along, grid=20, newdata=None, s
     sev = np.empty(total) if se else None
     cov = np.empty(int(cov_off[-1])) if se else None
     _call_native("bigkrls_conditional_effects", ctx.handle, Xh.ctypes.data, n, p, yv.ctypes.data, coeffs.ctypes.data,
-                 float(object["sigma"]), pair_arr.ctypes.data, m, nd.ctypes.data if nd is not None else None,
-                 nd.shape[0] if nd is not None else n, flat.ctypes.data, off.ctypes.data,
-                 Vd.ptr if form == "dense" else None, Qd.ptr if form == "factors" else None,
-                 Qd.ld if form == "factors" else 0, Qd.ncol if form == "factors" else 0,
-                 wv.ctypes.data if form == "factors" else None, ce.ctypes.data,
+                 float(object["sigma"]), pair_arr.ctypes.data, m, nd.ctypes.data if nd is not None else None, u,
+                 flat.ctypes.data, off.ctypes.data, *vcov_args, ce.ctypes.data,
                  sev.ctypes.data if se else None, cov.ctypes.data if se else None)
     cut = lambda v: [v[off[i]:off[i + 1]] for i in range(m)]
     covs = None
@@ -1225,7 +1163,6 @@ def conditional_effects(object: BigKRLS, effect, along, grid=20, newdata=None, s
     secon = None
     if se:
         secon = np.array([[np.sqrt(max(c[0, 0] + c[-1, -1] - 2.0 * c[0, -1], 0.0)) for c in covs]])
-    xlabs = list(object.get("xlabs") or [f"x{i + 1}" for i in range(p)])
     return {"pairs": pairs, "xlabs": [(xlabs[j - 1], xlabs[k - 1]) for j, k in pairs],
             "binary.effect": isbin[pair_arr[:, 0] - 1], "binary.moderator": isbin[pair_arr[:, 1] - 1], "grid": grids,
             "ce": cut(ce), "se.ce": cut(sev) if se else None, "vcov.ce": covs, "contrast": contrast,
@@ -1286,23 +1223,8 @@ def group_effects(object: BigKRLS, by, newdata=None, which_derivatives=None, bin
     |J|; H0: the group AMEs of x_j are all equal, see _wald; G = 1 gives 0, 0, nan), "reference", "derivatives" (u x |J|),
     "which.derivatives", "binaryindicator", "xlabs", "newdata". Without a variance form on the object "se.ame",
     "vcov.ame", "se.diff" and "wald" are None."""
-    if not isinstance(object, BigKRLS):
-        raise TypeError("Object not of class 'bigKRLS'")
-    form = _vcov_choice(object, vcov)
-    if ("vcov.est.c.cols" in object or "rows" in object) and form != "factors":
-        raise NotImplementedError("group_effects of a multi-GPU fit (sharded vcov.est.c.cols) is not supported; "
-                                  "refit on one GPU or with vcov_form=\"factors\"")
-    Xh = np.asfortranarray(np.asarray(object["X"], dtype=np.float64))
-    n, p = Xh.shape
-    nd_init = Xh if newdata is None else _as_host_matrix(newdata)
-    nd = np.array(nd_init, dtype=np.float64, order="F")
-    if nd.ndim != 2 or nd.shape[1] != p:
-        raise ValueError("ncol(newdata) differs from ncol(X) from fitted bigKRLS object")
-    u = nd.shape[0]
-    if u < 1:
-        raise ValueError("newdata has no rows")
-    if not np.all(np.isfinite(nd)):
-        raise ValueError("newdata contains missing or infinite values")
+    Xh, n, p, nd_init, nd, u, isbin, form = _effects_open("group_effects", object, newdata, vcov, False,
+                                                         default="training")
     if which_derivatives is None:
         which_derivatives = object.get("which.derivatives")
     if which_derivatives is None:
@@ -1311,13 +1233,7 @@ def group_effects(object: BigKRLS, by, newdata=None, which_derivatives=None, bin
         which = [int(i) for i in np.atleast_1d(which_derivatives)]
         if not which or not all(1 <= i <= p for i in which):
             raise ValueError("which.derivatives must index columns of X")
-    isbin = np.array([np.unique(Xh[:, j]).size == 2 for j in range(p)])          # the fit's rule (R/bigKRLS.R:242)
-    for j in sorted(set(i - 1 for i in which)):
-        if isbin[j]:
-            lo, hi = Xh[:, j].min(), Xh[:, j].max()
-            if not np.all((nd[:, j] == lo) | (nd[:, j] == hi)):
-                raise ValueError(f"newdata column {j + 1} is binary in the training data; its values must be "
-                                 f"one of the two training values ({lo:g}, {hi:g})")
+    _check_binary_newdata(Xh, nd, isbin, sorted(set(i - 1 for i in which)))
     groups, labels = _group_labels(by, nd, bins)
     G, nj = len(groups), len(which)
     if G < 1:
@@ -1333,21 +1249,14 @@ def group_effects(object: BigKRLS, by, newdata=None, which_derivatives=None, bin
     if G * nj > 4096:
         raise ValueError(f"{G} groups x {nj} columns = {G * nj} average effects: the covariance is (G |J|)^2 doubles on "
                          "the host and G |J| may be at most 4096; use fewer groups (bins=) or which_derivatives")
-    ctx = ctx or object.get("_ctx") or default_context()
-    V = object.get("vcov.est.c") if form == "dense" else None
-    Vd = None if V is None else (V if is_device_matrix(V) else ctx.from_numpy(np.asarray(V, dtype=np.float64)))
-    Qd, wv = _factors(object, ctx) if form == "factors" else (None, None)
-    yv = np.ascontiguousarray(np.asarray(object["y"], dtype=np.float64).ravel())
-    coeffs = np.ascontiguousarray(np.asarray(object["coeffs"], dtype=np.float64).ravel())
+    ctx, Vd, Qd, wv, yv, coeffs, vcov_args, xlabs = _effects_device(object, form, ctx, p)
     which_arr = np.ascontiguousarray(which, dtype=np.int64)
     D = np.empty((u, nj), dtype=np.float64, order="F")
     ame = np.empty((G, nj), dtype=np.float64, order="F")
     cov = np.empty((G * nj, G * nj), dtype=np.float64, order="F") if form is not None else None
     _call_native("bigkrls_group_effects", ctx.handle, Xh.ctypes.data, n, p, yv.ctypes.data, coeffs.ctypes.data,
                  float(object["sigma"]), which_arr.ctypes.data, nj, nd.ctypes.data, u, labels.ctypes.data, G,
-                 Vd.ptr if form == "dense" else None, Qd.ptr if form == "factors" else None,
-                 Qd.ld if form == "factors" else 0, Qd.ncol if form == "factors" else 0,
-                 wv.ctypes.data if form == "factors" else None, D.ctypes.data, ame.ctypes.data,
+                 *vcov_args, D.ctypes.data, ame.ctypes.data,
                  cov.ctypes.data if cov is not None else None)
     diff = ame - ame[ref:ref + 1, :]
     se_ame = se_diff = wald = None
@@ -1361,7 +1270,6 @@ def group_effects(object: BigKRLS, by, newdata=None, which_derivatives=None, bin
             se_diff[ref, jj] = 0.0
             stats[jj], dfs[jj], ps[jj] = _wald(ame[:, jj], Sj, ref)
         wald = {"statistic": stats, "df": dfs, "p": ps}
-    xlabs = list(object.get("xlabs") or [f"x{i + 1}" for i in range(p)])
     return {"groups": groups, "n": np.bincount(labels, minlength=G), "ame": ame, "se.ame": se_ame, "vcov.ame": cov,
             "diff": diff, "se.diff": se_diff, "wald": wald, "reference": groups[ref], "derivatives": D,
             "which.derivatives": which, "binaryindicator": isbin[which_arr - 1],

@@ -200,11 +200,12 @@ enum Slot {
   SLOT_FIT_VERIFY = 43,    // the fit's check of a decomposition against K: Q r, Q (lambda o r), K Q r
   SLOT_CONTRACT_PART = 44, // kernel_contract: partial sums of the loop splits
   SLOT_ME_SMALL = 45,      // bigkrls_marginal_effects(_se): standardised X and newdata, operands, products, D, S, V S / r, t, s, se^2
-                           //     bigkrls_interaction_effects(_se): the same for the pairs
+                           //     bigkrls_interaction_effects(_se): the same for the pairs; bigkrls_group_effects: with D and M.
+                           //     Each entry declares its regions once (Layout, layout.h); me_se_frame (margeff.h) for both *_se
   SLOT_PP_SMALL = 46,      // bigkrls_predict_pointwise: standardised X, c, one block of newdata, yhat, diag
   SLOT_PP_K = 47,          // ... one row block of the test kernel, and its product with Q where the variance comes as factors (at most 1 GiB);
-                           //     bigkrls_marginal_effects_se, bigkrls_interaction_effects_se: the same block and product, or the
-                           //     block and its modulated copy
+                           //     me_se_frame (bigkrls_marginal_effects_se, bigkrls_interaction_effects_se): the same block and
+                           //     product, or the block and its modulated copy; bigkrls_group_effects: C and S of all groups
   SLOT_QF_PART = 48,       // quadform_diag: one partial per row, column tile and k split
   SLOT_KB_SHIFT = 49,      // kernel_block / kernel_contract: the common shift of both operands (P doubles: column means of A)
   SLOT_KB_A = 50,          // ... the shifted copy of A (u x P)
@@ -213,8 +214,8 @@ enum Slot {
   SLOT_KOP_NORMS = 53,     // ... and its squared row norms
   SLOT_LOO_PART = 54,      // kernel_loo_colsums, kernel_loo_moments: partial sums of the loop splits (and a launch's columns
                            //     before they are scattered to the caller's order)
-  SLOT_PD_SMALL = 55,      // bigkrls_partial_dependence: standardised X and newdata, c, w, the grids, M, pd, variances
-                           //     bigkrls_conditional_effects: the same for the pairs
+  SLOT_PD_SMALL = 55,      // curve_frame (curvetail.h; bigkrls_partial_dependence, bigkrls_conditional_effects): standardised X
+                           //     and newdata, c, w, the grids, the moments M, the values, variances and covariance blocks
   SLOT_PD_A = 56,          // ... one column's (pair's) A_j (G_j x n, at most 1 GiB), its product with Q or vcov.est.c, the covariance
   SLOT_RV_SMALL = 57,      // bigkrls_vcov_robust: g, d g, residuals, leverages, omega, M, S, U, theta, the cluster scores
   SLOT_CS_PART = 58,       // cluster_scores: the sums of the pieces of clusters that span several 64-row chunks

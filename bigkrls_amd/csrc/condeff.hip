@@ -20,9 +20,6 @@
 // never read, nor column j for a binary j.
 // Device memory: O((u + n)(p + entries)) plus the loop splits' partials, and per pair A_jk (at most 1 GiB) with its product.
 #include "curvetail.h"
-#include "hostprep.h"
-
-#include <cstring>
 
 namespace bk {
 namespace {
@@ -60,18 +57,9 @@ int bigkrls_conditional_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, 
                                 const double* h_newdata, int64_t u, const double* h_grid, const int64_t* h_grid_off,
                                 const double* d_vcov_c, const double* d_Q, int64_t ldq, int64_t k, const double* h_w,
                                 double* h_ce, double* h_se, double* h_cov) {
-  BK_TRY(check_ctx(ctx));
-  BK_REQUIRE(h_X && h_y && h_coeffs && h_pairs && h_grid && h_grid_off && h_ce, "conditional_effects: null argument");
-  if (!h_newdata) u = n;   // the reference sample is the training rows
-  BK_REQUIRE(n > 1 && p > 0 && u > 0 && n < (1ll << 31) && u < (1ll << 31), "conditional_effects: bad dimensions");
-  BK_REQUIRE(sigma > 0.0 && std::isfinite(sigma), "conditional_effects: sigma must be a positive scalar");
-  BK_REQUIRE(!(d_vcov_c && d_Q), "conditional_effects: at most one of vcov.est.c and its factors may be given");
-  const Vcov vc = d_vcov_c ? Vcov::matrix(d_vcov_c) : (d_Q ? Vcov::factors(d_Q, ldq, k, h_w) : Vcov());
-  BK_REQUIRE(vc.given() || (!h_se && !h_cov),
-             "conditional_effects: h_se and h_cov are written only when vcov.est.c (or its factors) is given");
-  if (vc.d_Q) BK_REQUIRE(vc.h_w && vc.k > 0 && vc.k <= n && vc.ldq >= n, "conditional_effects: bad factors of vcov.est.c");
-  const bool want_var = vc.given() && (h_se || h_cov);
-  const int64_t kq = want_var ? vc.cols() : 0;
+  CurveArgs ca;
+  BK_TRY(curve_check_args(ctx, "conditional_effects", h_X && h_y && h_coeffs && h_pairs && h_grid && h_grid_off && h_ce,
+                          n, p, h_newdata, &u, sigma, d_vcov_c, d_Q, ldq, k, h_w, h_se, h_cov, &ca));
 
   // ---- the pairs and their grids -----------------------------------------------------------------------------
   BK_REQUIRE(m > 0 && m < (1ll << 20), "conditional_effects: pairs is empty (or holds 2^20 pairs or more)");
@@ -85,25 +73,9 @@ int bigkrls_conditional_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, 
       BK_REQUIRE(h_pairs[2 * i2] != j || h_pairs[2 * i2 + 1] != kk,
                  "conditional_effects: " + pair_name(i) + " is given more than once");
   }
-  const int64_t gcap = (1ll << 30) / (8 * n);
-  BK_REQUIRE(h_grid_off[0] == 0, "conditional_effects: the grid offsets must start at 0");
-  int64_t gmax = 0, cov_doubles = 0;
-  for (int64_t i = 0; i < m; ++i) {
-    const int64_t G = h_grid_off[i + 1] - h_grid_off[i];
-    BK_REQUIRE(G >= 1, "conditional_effects: the grid of " + pair_name(i) + " is empty");
-    BK_REQUIRE(G <= gcap, "conditional_effects: the grid of " + pair_name(i) + " has " + std::to_string(G) +
-                              " values; at most " + std::to_string(gcap) + " fit the 1 GiB block (8 G n <= 2^30 bytes)");
-    gmax = std::max(gmax, G);
-    cov_doubles += G * G;
-  }
-  const int64_t T = h_grid_off[m];
-  BK_REQUIRE(T < (1ll << 31), "conditional_effects: too many grid values");
-  if (!h_cov) cov_doubles = 0;
-  for (int64_t i = 0; i < T; ++i)
-    BK_REQUIRE(std::isfinite(h_grid[i]), "conditional_effects: the grid contains missing or infinite values");
-  if (h_newdata)
-    for (int64_t i = 0; i < u * p; ++i)
-      BK_REQUIRE(std::isfinite(h_newdata[i]), "conditional_effects: newdata contains missing or infinite values");
+  CurvePlan cp;
+  BK_TRY(curve_plan("conditional_effects", n, p, m, h_grid, h_grid_off, h_cov != nullptr, h_newdata, u, pair_name, &cp));
+  const int64_t T = cp.T;
 
   // ---- the training moments and the two-valued columns (as bigkrls_marginal_effects) ---------------------------
   std::vector<double> x_mean((size_t)p), x_sd((size_t)p), lo((size_t)p), hi((size_t)p);
@@ -141,71 +113,25 @@ int bigkrls_conditional_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, 
   }
   const int64_t ne = (int64_t)entries.size() / 3;
 
-  // ---- device layout -----------------------------------------------------------------------------------------
-  hipStream_t st = ctx->stream;
-  const int64_t zs_doubles = h_newdata ? u * p : 0;
-  const int64_t up_doubles = n * p + zs_doubles + n + kq + T;   // uploaded, in this order
-  const int64_t down_doubles = 2 * T + cov_doubles;             // read back: the values, the variances, the covariance blocks
-  void* psmall = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_PD_SMALL, (up_doubles + n * ne + down_doubles + 64) * (int64_t)sizeof(double), &psmall));
-  double* qd = (double*)psmall;
-  double* dXs = qd; qd += n * p;
-  double* dZs = h_newdata ? qd : dXs; qd += zs_doubles;
-  double* dc = qd; qd += n;
-  double* dw = qd; qd += kq;
-  double* dvs = qd; qd += T;
-  double* dM = qd; qd += n * ne;
-  double* dce = qd; qd += T;
-  double* dvar = qd; qd += T;
-  double* dcov = qd; qd += cov_doubles;
-  // one pair's A_jk, and beside it T = A Q and T diag(w) (factors) or A vcov.est.c (matrix, only for the covariance)
-  const int64_t wide = !want_var ? 0 : (vc.d_Q ? 2 * kq : (h_cov ? n : 0));
-  void* pa = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_PD_A, gmax * (n + wide) * (int64_t)sizeof(double), &pa));
-  double* dA = (double*)pa;
-  double* dP = dA + gmax * n;
-
-  // ---- standardise (training means and sds, as bigkrls_predict), upload ---------------------------------------
-  double* pin = nullptr;
-  BK_HIP(hipStreamSynchronize(st));   // (the pinned buffer may be reallocated)
-  BK_TRY(pinned_get(ctx, std::max(up_doubles, down_doubles), &pin));
-  {
-    double* hXs = pin;
-    double* hZs = hXs + n * p;
-    double* hc = hZs + zs_doubles;
-    double* hw = hc + n;
-    double* hvs = hw + kq;
-    for (int64_t j = 0; j < p; ++j) {
-      standardise_column(h_X + j * n, n, x_mean[j], x_sd[j], hXs + j * n);
-      if (h_newdata) standardise_column(h_newdata + j * u, u, x_mean[j], x_sd[j], hZs + j * u);
-    }
-    std::memcpy(hc, h_coeffs, (size_t)n * sizeof(double));
-    if (kq > 0) std::memcpy(hw, vc.h_w, (size_t)kq * sizeof(double));
-    for (int64_t i = 0; i < m; ++i) {
-      const int64_t kk = h_pairs[2 * i + 1] - 1, g0 = h_grid_off[i];
-      standardise_column(h_grid + g0, h_grid_off[i + 1] - g0, x_mean[kk], x_sd[kk], hvs + g0);
-    }
-    BK_HIP(hipMemcpyAsync(dXs, pin, (size_t)up_doubles * sizeof(double), hipMemcpyHostToDevice, st));
-  }
-
-  // ---- the moments of all pairs in one fused pass, then pair by pair -------------------------------------------
-  BK_TRY(kernel_loo_moments(ctx, dZs, u, u, dXs, n, n, p, sigma, entries.data(), ne, dM, n));
-  double* dcov_i = dcov;
-  for (int64_t i = 0; i < m; ++i) {
-    const int64_t j = h_pairs[2 * i] - 1, kk = h_pairs[2 * i + 1] - 1, g0 = h_grid_off[i], G = h_grid_off[i + 1] - g0;
-    const int type = j == kk ? 1 : (isbin[j] ? 2 : 0);
-    const double z0 = (lo[j] - x_mean[j]) / x_sd[j], z1 = (hi[j] - x_mean[j]) / x_sd[j];   // (as standardise_column)
-    const double scale = type == 2 ? 1.0 / ((z1 - z0) * (double)u) : 2.0 / (sigma * (double)u);
-    const int blocks = (int)std::min<int64_t>((G * n + 255) / 256, 8192);
-    hipLaunchKernelGGL(ce_rows_kernel, dim3(blocks), dim3(256), 0, st, (int)G, (int)n, type,
-                       (const double*)(dM + entry_of[i] * n), (const double*)(dXs + kk * n), (const double*)(dXs + j * n),
-                       (const double*)(dvs + g0), -1.0 / sigma, scale, z0, z1, dA);
-    BK_CHECK_LAUNCH();
-    BK_TRY(curve_tail(ctx, vc, want_var, G, n, kq, dA, dP, dc, dw, dce + g0, dvar + g0, h_cov ? dcov_i : nullptr));
-    if (h_cov) dcov_i += G * G;
-  }
-  BK_HIP(hipMemcpyAsync(pin, dce, (size_t)down_doubles * sizeof(double), hipMemcpyDeviceToHost, st));
-  BK_HIP(hipStreamSynchronize(st));
+  // ---- the moments of all pairs in one fused pass, then pair by pair (curve_frame, curvetail.h) ------------------
+  const double* pin = nullptr;
+  BK_TRY(curve_frame(
+      ctx, h_X, n, p, h_coeffs, h_newdata, u, x_mean, x_sd, ca, h_cov != nullptr, cp, h_grid, h_grid_off, ne,
+      [&](int64_t i) { return h_pairs[2 * i + 1] - 1; },
+      [&](const double* dZs, const double* dXs, double* dM) {
+        return kernel_loo_moments(ctx, dZs, u, u, dXs, n, n, p, sigma, entries.data(), ne, dM, n);
+      },
+      [&](int64_t i, int64_t G, const double* dXs, const double* dvs, const double* dM, double* dA) -> int {
+        const int64_t j = h_pairs[2 * i] - 1, kk = h_pairs[2 * i + 1] - 1;
+        const int type = j == kk ? 1 : (isbin[j] ? 2 : 0);
+        const double z0 = (lo[j] - x_mean[j]) / x_sd[j], z1 = (hi[j] - x_mean[j]) / x_sd[j];   // (as standardise_column)
+        const double scale = type == 2 ? 1.0 / ((z1 - z0) * (double)u) : 2.0 / (sigma * (double)u);
+        hipLaunchKernelGGL(ce_rows_kernel, dim3(launch_blocks(G * n, 8192)), dim3(256), 0, ctx->stream, (int)G, (int)n,
+                           type, dM + entry_of[i] * n, dXs + kk * n, dXs + j * n, dvs, -1.0 / sigma, scale, z0, z1, dA);
+        BK_CHECK_LAUNCH();
+        return BIGKRLS_OK;
+      },
+      &pin));
 
   // ---- original units (bigkrls_marginal_effects'): values sd(y) / sd(x_j), variances 1 / sd(x_j)^2 on vcov.est.c in the
   //      fit's units; the factor 2 of a binary j; a form that rounds below zero is zero -----------------------------------

@@ -28,12 +28,12 @@ int bigkrls_group_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_
                           const double* h_newdata, int64_t u, const int64_t* h_group, int64_t G,
                           const double* d_vcov_c, const double* d_Q, int64_t ldq, int64_t k, const double* h_w,
                           double* h_derivatives, double* h_ame, double* h_cov) {
-  BK_TRY(me_check_args(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_newdata, u, h_ame));
-  BK_REQUIRE(!(d_vcov_c && d_Q), "group_effects: at most one of vcov.est.c and its factors may be given");
-  const Vcov vc = d_vcov_c ? Vcov::matrix(d_vcov_c) : (d_Q ? Vcov::factors(d_Q, ldq, k, h_w) : Vcov());
+  BK_TRY(effects_check_args(ctx, "marginal_effects", h_X && h_y && h_coeffs && h_newdata && h_ame, n, p, u, sigma));
+  Vcov vc;
+  BK_TRY(vcov_forms("group_effects", d_vcov_c, d_Q, ldq, k, h_w, false, &vc));
   BK_REQUIRE(vc.given() == (h_cov != nullptr),
              "group_effects: h_cov is written exactly when vcov.est.c (or its factors) is given");
-  BK_TRY(me_check_factors(vc, n));
+  BK_TRY(vcov_check_factors("marginal_effects", vc, n));
   BK_REQUIRE(h_group, "group_effects: null labels");
   for (int64_t i = 0; i < u; ++i)    // (G < 1: row 1 is named)
     BK_REQUIRE(h_group[i] >= 0 && h_group[i] < G,
@@ -48,26 +48,15 @@ int bigkrls_group_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_
   std::vector<int64_t> ng((size_t)G, 0);
   for (int64_t i = 0; i < u; ++i) ++ng[(size_t)h_group[i]];
 
-  // ---- device layout ----------------------------------------------------------------------------------------------
+  // ---- device layout (read back: D, then M) -----------------------------------------------------------------------
   hipStream_t st = ctx->stream;
   const bool want_cov = vc.given();
-  const int64_t colw = (int64_t)((sizeof(MeCol) + 7) / 8);
-  const int64_t up_doubles = n * p + u * p + n + u + n * q + u * q + nj * colw + kq;   // uploaded, in this order
-  const int64_t down_doubles = u * nj + (want_cov ? E * E : 0);                // read back: D, then M
-  void* psmall = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_ME_SMALL, (up_doubles + u * q + down_doubles + 64) * (int64_t)sizeof(double), &psmall));
-  double* qd = (double*)psmall;
-  double* dXs = qd; qd += n * p;
-  double* dZs = qd; qd += u * p;
-  double* dnx = qd; qd += n;
-  double* dnz = qd; qd += u;
-  double* dB = qd; qd += n * q;
-  double* dBs = qd; qd += u * q;
-  MeCol* dcols = (MeCol*)qd; qd += nj * colw;
-  double* dw = qd; qd += kq;
-  double* dR = qd; qd += u * q;
-  double* dD = qd; qd += u * nj;
-  double* dM = qd; qd += want_cov ? E * E : 0;
+  Layout L;
+  const Region Xs = L.up(n * p), Zs = L.up(u * p), nx = L.up(n), nz = L.up(u), B = L.up(n * q), Bs = L.up(u * q),
+               cols = L.up_records<MeCol>(nj), w = L.up(kq);
+  const Region R = L.dev(u * q), D = L.down(u * nj), M = L.down(want_cov ? E * E : 0);
+  BK_TRY(layout_device(ctx, SLOT_ME_SMALL, &L));
+  const MeCol* dcols = L.d<MeCol>(cols);
   // C (n x G q) and S (n x G |J|); C is dead once S is written: T = Q' S (k x G |J|) or P = V S (n x G |J|) take its place
   void* pbig = nullptr;
   double *dC = nullptr, *dS = nullptr;
@@ -79,75 +68,43 @@ int bigkrls_group_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_
 
   // ---- standardise (training means and sds, as bigkrls_predict), squared row norms, operands, upload. The training rows
   //      are centred by their standardisation, so the contractions take the operands as they are (as
-  //      marginal_effects_se_impl's kernel blocks do): no shift by a column mean, whose rounding would depend on the order
+  //      me_se_frame's kernel blocks do): no shift by a column mean, whose rounding would depend on the order
   //      of the rows -- the same rows in another order give the same bits ------------------------------------------------
-  double* pin = nullptr;
-  BK_HIP(hipStreamSynchronize(st));   // (the pinned buffer may be reallocated)
-  BK_TRY(pinned_get(ctx, std::max(up_doubles, down_doubles), &pin));
-  {
-    double* hXs = pin;
-    double* hZs = hXs + n * p;
-    double* hnx = hZs + u * p;
-    double* hnz = hnx + n;
-    double* hB = hnz + u;
-    double* hBs = hB + n * q;
-    MeCol* hcols = (MeCol*)(hBs + u * q);
-    me_standardise(mp, h_X, n, p, h_newdata, u, hXs, hZs);
-    auto sqnorms = [p](const double* A, int64_t rows, double* out) {
-      for (int64_t i = 0; i < rows; ++i) out[i] = 0.0;
-      for (int64_t j = 0; j < p; ++j)
-        for (int64_t i = 0; i < rows; ++i) out[i] += A[j * rows + i] * A[j * rows + i];
-    };
-    sqnorms(hXs, n, hnx);
-    sqnorms(hZs, u, hnz);
-    for (int64_t i = 0; i < n; ++i) hB[i] = h_coeffs[i];
-    for (int64_t i = 0; i < u; ++i) hBs[i] = 1.0;
-    for (int64_t jj = 0; jj < nj; ++jj) {
-      const int64_t j = mp.cols[jj];
-      const double* x = h_X + j * n;
-      const double* z = h_newdata + j * u;
-      double* b = hB + (1 + jj) * n;
-      double* bs = hBs + (1 + jj) * u;
-      if (mp.isbin[j]) {                                // group membership on the raw values
-        for (int64_t i = 0; i < n; ++i) b[i] = (x[i] == mp.hi[j] ? 1.0 : 0.0) * h_coeffs[i];
-        for (int64_t i = 0; i < u; ++i) bs[i] = z[i] == mp.hi[j] ? 1.0 : 0.0;
-      } else {
-        for (int64_t i = 0; i < n; ++i) b[i] = hXs[j * n + i] * h_coeffs[i];
-        std::memcpy(bs, hZs + j * u, (size_t)u * sizeof(double));
-      }
-      hcols[jj] = mp.col(jj);
-    }
-    if (kq > 0) std::memcpy((double*)hcols + nj * colw, vc.h_w, (size_t)kq * sizeof(double));
-    BK_HIP(hipMemcpyAsync(dXs, pin, (size_t)up_doubles * sizeof(double), hipMemcpyHostToDevice, st));
-  }
+  BK_TRY(layout_pinned(ctx, &L));
+  double* pin = L.pinned();
+  me_standardise(mp, h_X, n, p, h_newdata, u, L.h(Xs), L.h(Zs));
+  host_sqnorms(L.h(Xs), n, p, L.h(nx));
+  host_sqnorms(L.h(Zs), u, p, L.h(nz));
+  me_fill_operands(mp, h_X, n, h_newdata, u, h_coeffs, L.h(Xs), L.h(Zs), L.h(B), L.h(Bs));
+  me_stage_cols(mp, vc, L.h<MeCol>(cols), L.h(w));
+  BK_TRY(layout_upload(ctx, L));
 
   // ---- row side: the pointwise effects ---------------------------------------------------------------------------------
-  BK_TRY(kernel_contract_centred(ctx, dZs, u, u, dnz, dXs, n, n, dnx, p, sigma, dB, q, n, dR, u));    // R = Kn B
-  int blocks = (int)std::min<int64_t>((u * nj + 255) / 256, 4096);
-  hipLaunchKernelGGL(me_rows_kernel, dim3(blocks), dim3(256), 0, st, (int)u, (int)nj, (const double*)dR,
-                     (const double*)dZs, (const double*)dBs, (const MeCol*)dcols, sigma, dD);
+  BK_TRY(kernel_contract_centred(ctx, L.d(Zs), u, u, L.d(nz), L.d(Xs), n, n, L.d(nx), p, sigma, L.d(B), q, n, L.d(R),
+                                 u));                                                                  // R = Kn B
+  hipLaunchKernelGGL(me_rows_kernel, dim3(launch_blocks(u * nj, 4096)), dim3(256), 0, st, (int)u, (int)nj,
+                     (const double*)L.d(R), (const double*)L.d(Zs), (const double*)L.d(Bs), dcols, sigma, L.d(D));
   BK_CHECK_LAUNCH();
 
   // ---- column side, all groups at once; M = S' V S ----------------------------------------------------------------------
   if (want_cov) {
-    BK_TRY(kernel_contract_grouped_centred(ctx, dXs, n, n, dnx, dZs, u, u, dnz, p, sigma, dBs, q, u, h_group, G, dC,
-                                           n));                                                       // all C_g
-    const dim3 grid((unsigned)std::min<int64_t>((n * nj + 255) / 256, 1024), (unsigned)G);
-    hipLaunchKernelGGL(me_cols_kernel, grid, dim3(256), 0, st, (int)n, (int)nj, (const double*)dC, (const double*)dXs,
-                       (const MeCol*)dcols, sigma, dS, n * q, G * n, n);
+    BK_TRY(kernel_contract_grouped_centred(ctx, L.d(Xs), n, n, L.d(nx), L.d(Zs), u, u, L.d(nz), p, sigma, L.d(Bs), q, u,
+                                           h_group, G, dC, n));                                       // all C_g
+    const dim3 grid(launch_blocks(n * nj, 1024), (unsigned)G);
+    hipLaunchKernelGGL(me_cols_kernel, grid, dim3(256), 0, st, (int)n, (int)nj, (const double*)dC,
+                       (const double*)L.d(Xs), dcols, sigma, dS, n * q, G * n, n);
     BK_CHECK_LAUNCH();
     if (vc.d_Q) {
       BK_TRY(gemm(ctx, 1, 0, kq, E, n, 1.0, vc.d_Q, vc.ldq, dS, n, 0.0, dC, kq));      // T = Q' S
-      BK_TRY(gram_weighted(ctx, kq, E, dC, kq, dw, dM, E));                            // M = T' diag(w) T
+      BK_TRY(gram_weighted(ctx, kq, E, dC, kq, L.d(w), L.d(M), E));                    // M = T' diag(w) T
     } else {
       BK_TRY(gemm(ctx, 0, 0, n, E, n, 1.0, vc.d_V, n, dS, n, 0.0, dC, n));             // P = vcov.est.c S
-      BK_TRY(gemm(ctx, 1, 0, E, E, n, 1.0, dS, n, dC, n, 0.0, dM, E));                 // M = S' P
+      BK_TRY(gemm(ctx, 1, 0, E, E, n, 1.0, dS, n, dC, n, 0.0, L.d(M), E));             // M = S' P
     }
   }
   // (gemm and gram_weighted do not touch the context's pinned buffer, and the grouped contraction stages its tables
   // through one of its own: `pin` is still the buffer sized above, and the upload from it has completed by stream order)
-  BK_HIP(hipMemcpyAsync(pin, dD, (size_t)down_doubles * sizeof(double), hipMemcpyDeviceToHost, st));
-  BK_HIP(hipStreamSynchronize(st));
+  BK_TRY(layout_download(ctx, L));
 
   // ---- original units: D sd(y) / sd(x_j) (R/bigKRLS.R:393-407), its group means; cov[e, f] = a_e a_f M[e, f] -------------
   for (int64_t jj = 0; jj < nj; ++jj) {

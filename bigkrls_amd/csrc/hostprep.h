@@ -1,8 +1,11 @@
 // Host-side preparation shared by the whole-path entries (csrc/fit.hip, csrc/margeff.hip): the context check, column
-// moments as R computes them, the two-valued test and the standardisation. Header-only, so that every user compiles
-// the arithmetic with its own translation unit's flags; `static`, so that nothing here joins the exported symbols.
+// moments as R computes them, the two-valued test and the standardisation; for the post-estimation entries also their
+// argument checks, the two forms of vcov.est.c, and the packed layout (layout.h) bound to a workspace slot and the pinned
+// buffer. Header-only, so that every user compiles the arithmetic with its own translation unit's flags; `static`, so
+// that nothing here joins the exported symbols.
 #pragma once
 #include "common.h"
+#include "layout.h"
 
 #include <algorithm>
 #include <cmath>
@@ -78,6 +81,80 @@ static inline void standardise_column(const double* src, int64_t rows, double me
 // 1 GiB, at least 128
 static inline int64_t pointwise_block_rows(int64_t n, int64_t k) {
   return std::max<int64_t>(128, ((1ll << 30) / ((n + k) * (int64_t)sizeof(double))) / 128 * 128);
+}
+
+// ---- the post-estimation entries -----------------------------------------------------------------------------------
+// blocks of 256 threads for `total` elements of a grid-stride kernel, at most `cap`
+static inline unsigned launch_blocks(int64_t total, int64_t cap) {
+  return (unsigned)std::min<int64_t>((total + 255) / 256, cap);
+}
+
+// out[i] = ||A[i, :]||^2 of A (rows x p, ld rows), column after column
+static inline void host_sqnorms(const double* A, int64_t rows, int64_t p, double* out) {
+  for (int64_t i = 0; i < rows; ++i) out[i] = 0.0;
+  for (int64_t j = 0; j < p; ++j)
+    for (int64_t i = 0; i < rows; ++i) out[i] += A[j * rows + i] * A[j * rows + i];
+}
+
+// the context, the pointers (`pointers`: all that must not be null are not), the dimensions and sigma; u is the number
+// of new rows, n where newdata may be null and is
+static inline int effects_check_args(bigkrls_ctx* ctx, const char* who, bool pointers, int64_t n, int64_t p, int64_t u,
+                                     double sigma) {
+  BK_TRY(check_ctx(ctx));
+  BK_REQUIRE(pointers, std::string(who) + ": null argument");
+  BK_REQUIRE(n > 1 && p > 0 && u > 0 && n < (1ll << 31) && u < (1ll << 31), std::string(who) + ": bad dimensions");
+  BK_REQUIRE(sigma > 0.0 && std::isfinite(sigma), std::string(who) + ": sigma must be a positive scalar");
+  return BIGKRLS_OK;
+}
+
+// vcov.est.c as the n x n matrix, as its factors, or not at all (Vcov, common.h), from the arguments of an entry that
+// takes both forms
+static inline int vcov_forms(const char* who, const double* d_vcov_c, const double* d_Q, int64_t ldq, int64_t k,
+                             const double* h_w, bool required, Vcov* vc) {
+  BK_REQUIRE(!(d_vcov_c && d_Q), std::string(who) + ": at most one of vcov.est.c and its factors may be given");
+  BK_REQUIRE(!required || d_vcov_c || d_Q, std::string(who) + ": exactly one of vcov.est.c and its factors must be given");
+  *vc = d_vcov_c ? Vcov::matrix(d_vcov_c) : (d_Q ? Vcov::factors(d_Q, ldq, k, h_w) : Vcov());
+  return BIGKRLS_OK;
+}
+
+static inline int vcov_check_factors(const char* who, const Vcov& vc, int64_t n) {
+  if (vc.d_Q)
+    BK_REQUIRE(vc.h_w && vc.k > 0 && vc.k <= n && vc.ldq >= n, std::string(who) + ": bad factors of vcov.est.c");
+  return BIGKRLS_OK;
+}
+
+// the layout's slot ...
+static inline int layout_device(bigkrls_ctx* ctx, int slot, Layout* L) {
+  BK_REQUIRE(L->valid() && L->down_adjacent(), "internal: a packed layout is out of order");
+  void* base = nullptr;
+  BK_TRY(ws_get(ctx, slot, L->slot_doubles() * (int64_t)sizeof(double), &base));
+  L->bind_device(base);
+  return BIGKRLS_OK;
+}
+
+// ... its staging area in the context's pinned buffer, which also takes what is read back (`down_doubles`: at least
+// the layout's own) ...
+static inline int layout_pinned(bigkrls_ctx* ctx, Layout* L, int64_t down_doubles = 0) {
+  double* pin = nullptr;
+  BK_HIP(hipStreamSynchronize(ctx->stream));   // (the pinned buffer may be reallocated)
+  BK_TRY(pinned_get(ctx, std::max({L->up_doubles(), L->down_doubles(), down_doubles}), &pin));
+  L->bind_host(pin);
+  return BIGKRLS_OK;
+}
+
+// ... the ONE upload of everything staged, and the ONE read-back of the adjacent regions marked for it (to the start
+// of the pinned buffer, synchronised)
+static inline int layout_upload(bigkrls_ctx* ctx, const Layout& L) {
+  BK_HIP(hipMemcpyAsync(L.d(Region()), L.pinned(), (size_t)L.up_doubles() * sizeof(double), hipMemcpyHostToDevice,
+                        ctx->stream));
+  return BIGKRLS_OK;
+}
+
+static inline int layout_download(bigkrls_ctx* ctx, const Layout& L) {
+  BK_HIP(hipMemcpyAsync(L.pinned(), L.d(Region{L.down_off(), 0}), (size_t)L.down_doubles() * sizeof(double),
+                        hipMemcpyDeviceToHost, ctx->stream));
+  BK_HIP(hipStreamSynchronize(ctx->stream));
+  return BIGKRLS_OK;
 }
 
 }  // namespace bk

@@ -171,10 +171,10 @@ int interaction_effects_impl(bigkrls_ctx* ctx, const double* h_X, int64_t n, int
                              const double* h_coeffs, double sigma, const int64_t* h_pairs, int64_t m,
                              const double* h_newdata, int64_t u, const Vcov& vc, double* h_interactions, double* h_avg,
                              double* h_var) {
-  BK_TRY(me_check_args(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_newdata, u, h_avg));
+  BK_TRY(effects_check_args(ctx, "marginal_effects", h_X && h_y && h_coeffs && h_newdata && h_avg, n, p, u, sigma));
   BK_REQUIRE(vc.given() == (h_var != nullptr),
              "interaction_effects: h_var is written exactly when vcov.est.c (or its factors) is given");
-  BK_TRY(me_check_factors(vc, n));
+  BK_TRY(vcov_check_factors("marginal_effects", vc, n));
   const int64_t k = vc.cols();
   IePlan pl;
   BK_TRY(ie_plan_pairs(h_pairs, m, p, &pl));
@@ -185,86 +185,63 @@ int interaction_effects_impl(bigkrls_ctx* ctx, const double* h_X, int64_t n, int
 
   // ---- device layout -------------------------------------------------------------------------------
   hipStream_t st = ctx->stream;
-  const int64_t colw = (int64_t)((sizeof(MeCol) + 7) / 8);
-  const int64_t pairw = (m * (int64_t)sizeof(IePair) + 7) / 8;
-  const int64_t up_doubles = n * p + u * p + n + nj * colw + pairw + k;   // uploaded, in this order
-  const int64_t small_doubles = up_doubles + n * nj + 2 * u * nj + 2 * (n + u) * q + u * m + 2 * n * m + m + 64;
-  void* psmall = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_ME_SMALL, small_doubles * (int64_t)sizeof(double), &psmall));
-  double* qd = (double*)psmall;
-  double* dXs = qd; qd += n * p;
-  double* dZs = qd; qd += u * p;
-  double* dc = qd; qd += n;
-  MeCol* dcols = (MeCol*)qd; qd += nj * colw;
-  IePair* dpairs = (IePair*)qd; qd += pairw;
-  double* dw = qd; qd += k;
-  double* dS = qd; qd += n * nj;      // s of the training rows
-  double* dR = qd; qd += u * nj;      // r, t of the new points
-  double* dT = qd; qd += u * nj;
-  double* dB = qd; qd += n * q;       // operands and products of the two contractions
-  double* dBs = qd; qd += u * q;
-  double* dRm = qd; qd += u * q;
-  double* dCm = qd; qd += n * q;
-  double* dI = qd; qd += u * m;
-  double* dSv = qd; qd += n * m;
-  double* dTv = qd; qd += n * m;
-  double* dvar = qd; qd += m;
+  Layout L;
+  const Region Xs = L.up(n * p), Zs = L.up(u * p), c = L.up(n), cols = L.up_records<MeCol>(nj),
+               pairs = L.up_records<IePair>(m), w = L.up(k);
+  const Region S = L.dev(n * nj);                            // s of the training rows
+  const Region R = L.dev(u * nj), T = L.dev(u * nj);         // r, t of the new points
+  const Region B = L.dev(n * q), Bs = L.dev(u * q), Rm = L.dev(u * q), Cm = L.dev(n * q);   // operands and products
+  const Region I = L.dev(u * m), Sv = L.dev(n * m), Tv = L.dev(n * m), var = L.dev(m);
+  BK_TRY(layout_device(ctx, SLOT_ME_SMALL, &L));
+  const MeCol* dcols = L.d<MeCol>(cols);
+  const IePair* dpairs = L.d<IePair>(pairs);
 
   // ---- standardise (training means and sds), upload ----------------------------------------------------
-  double* pin = nullptr;
-  BK_HIP(hipStreamSynchronize(st));   // (the pinned buffer may be reallocated)
-  BK_TRY(pinned_get(ctx, std::max(up_doubles, u * m + m), &pin));
-  {
-    double* hXs = pin;
-    double* hZs = hXs + n * p;
-    double* hc = hZs + u * p;
-    MeCol* hcols = (MeCol*)(hc + n);
-    IePair* hpairs = (IePair*)((double*)hcols + nj * colw);
-    me_standardise(mp, h_X, n, p, h_newdata, u, hXs, hZs);
-    std::memcpy(hc, h_coeffs, (size_t)n * sizeof(double));
-    for (int64_t jj = 0; jj < nj; ++jj) hcols[jj] = mp.col(jj);
-    std::memset(hpairs, 0, (size_t)pairw * sizeof(double));
-    std::memcpy(hpairs, pl.pos.data(), (size_t)m * sizeof(IePair));
-    if (k > 0) std::memcpy((double*)hpairs + pairw, vc.h_w, (size_t)k * sizeof(double));
-    BK_HIP(hipMemcpyAsync(dXs, pin, (size_t)up_doubles * sizeof(double), hipMemcpyHostToDevice, st));
-  }
+  BK_TRY(layout_pinned(ctx, &L, u * m + m));
+  double* pin = L.pinned();
+  me_standardise(mp, h_X, n, p, h_newdata, u, L.h(Xs), L.h(Zs));
+  std::memcpy(L.h(c), h_coeffs, (size_t)n * sizeof(double));
+  std::memset(L.h(pairs), 0, (size_t)pairs.len * sizeof(double));
+  std::memcpy(L.h(pairs), pl.pos.data(), (size_t)m * sizeof(IePair));
+  me_stage_cols(mp, vc, L.h<MeCol>(cols), L.h(w));
+  BK_TRY(layout_upload(ctx, L));
 
   // ---- r, t, s of the selected columns; the operands; the two fused contractions and their finalise ---------
-  auto grid_for = [](int64_t total) { return dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)); };
-  hipLaunchKernelGGL(me_se_s_kernel, grid_for(n * nj), dim3(256), 0, st, (int)n, (int)nj, (const double*)dXs,
-                     (const MeCol*)dcols, dS);
+  auto grid_for = [](int64_t total) { return dim3(launch_blocks(total, 4096)); };
+  hipLaunchKernelGGL(me_se_s_kernel, grid_for(n * nj), dim3(256), 0, st, (int)n, (int)nj, (const double*)L.d(Xs), dcols,
+                     L.d(S));
   BK_CHECK_LAUNCH();
-  hipLaunchKernelGGL(me_se_rt_kernel, grid_for(u * nj), dim3(256), 0, st, (int)u, (int)nj, (const double*)dZs, u,
-                     (const MeCol*)dcols, sigma, dR, dT);
+  hipLaunchKernelGGL(me_se_rt_kernel, grid_for(u * nj), dim3(256), 0, st, (int)u, (int)nj, (const double*)L.d(Zs), u,
+                     dcols, sigma, L.d(R), L.d(T));
   BK_CHECK_LAUNCH();
-  hipLaunchKernelGGL(ie_operand_kernel, grid_for(n * q), dim3(256), 0, st, (int)n, (int)nj, (int)m, (const double*)dS,
-                     n, (const IePair*)dpairs, (const double*)dc, dB);
+  hipLaunchKernelGGL(ie_operand_kernel, grid_for(n * q), dim3(256), 0, st, (int)n, (int)nj, (int)m,
+                     (const double*)L.d(S), n, dpairs, (const double*)L.d(c), L.d(B));
   BK_CHECK_LAUNCH();
-  hipLaunchKernelGGL(ie_operand_kernel, grid_for(u * q), dim3(256), 0, st, (int)u, (int)nj, (int)m, (const double*)dR,
-                     u, (const IePair*)dpairs, (const double*)nullptr, dBs);
+  hipLaunchKernelGGL(ie_operand_kernel, grid_for(u * q), dim3(256), 0, st, (int)u, (int)nj, (int)m,
+                     (const double*)L.d(R), u, dpairs, (const double*)nullptr, L.d(Bs));
   BK_CHECK_LAUNCH();
-  BK_TRY(kernel_contract(ctx, dZs, u, u, dXs, n, n, p, sigma, dB, q, n, 0, dRm, u));    // R = Kn B
-  BK_TRY(kernel_contract(ctx, dZs, u, u, dXs, n, n, p, sigma, dBs, q, u, 1, dCm, n));   // C = Kn' B*
-  hipLaunchKernelGGL(ie_rows_kernel, grid_for(u * m), dim3(256), 0, st, (int)u, (int)nj, (int)m, (const double*)dRm,
-                     (const double*)dR, (const double*)dT, (const IePair*)dpairs, sigma, dI);
+  BK_TRY(kernel_contract(ctx, L.d(Zs), u, u, L.d(Xs), n, n, p, sigma, L.d(B), q, n, 0, L.d(Rm), u));    // R = Kn B
+  BK_TRY(kernel_contract(ctx, L.d(Zs), u, u, L.d(Xs), n, n, p, sigma, L.d(Bs), q, u, 1, L.d(Cm), n));   // C = Kn' B*
+  hipLaunchKernelGGL(ie_rows_kernel, grid_for(u * m), dim3(256), 0, st, (int)u, (int)nj, (int)m, (const double*)L.d(Rm),
+                     (const double*)L.d(R), (const double*)L.d(T), dpairs, sigma, L.d(I));
   BK_CHECK_LAUNCH();
-  hipLaunchKernelGGL(ie_cols_kernel, grid_for(n * m), dim3(256), 0, st, (int)n, (int)nj, (int)m, (const double*)dCm,
-                     (const double*)dS, (const double*)dT, u, (const IePair*)dpairs, sigma, dSv);
+  hipLaunchKernelGGL(ie_cols_kernel, grid_for(n * m), dim3(256), 0, st, (int)n, (int)nj, (int)m, (const double*)L.d(Cm),
+                     (const double*)L.d(S), (const double*)L.d(T), u, dpairs, sigma, L.d(Sv));
   BK_CHECK_LAUNCH();
   if (vc.d_V) {
-    BK_TRY(gemm(ctx, 0, 0, n, m, n, 1.0, vc.d_V, n, dSv, n, 0.0, dTv, n));          // T = vcov.est.c S
-    hipLaunchKernelGGL(me_coldot_kernel, dim3((unsigned)m), dim3(256), 0, st, (int)n, (const double*)dSv,
-                       (const double*)dTv, dvar);
+    BK_TRY(gemm(ctx, 0, 0, n, m, n, 1.0, vc.d_V, n, L.d(Sv), n, 0.0, L.d(Tv), n));          // T = vcov.est.c S
+    hipLaunchKernelGGL(me_coldot_kernel, dim3((unsigned)m), dim3(256), 0, st, (int)n, (const double*)L.d(Sv),
+                       (const double*)L.d(Tv), L.d(var));
     BK_CHECK_LAUNCH();
   }
   // s'(vcov.est.c)s per pair; from the factors the fit's own step (see marginal_effects_impl on the pinned buffer)
   std::vector<double> qf((size_t)m, 0.0);
   if (vc.d_Q) {
     const std::vector<double> ones((size_t)m, 1.0);
-    BK_TRY(deriv_var(ctx, vc.d_Q, n, k, vc.ldq, dw, dSv, m, n, ones.data(), qf.data()));
+    BK_TRY(deriv_var(ctx, vc.d_Q, n, k, vc.ldq, L.d(w), L.d(Sv), m, n, ones.data(), qf.data()));
   }
-  BK_HIP(hipMemcpyAsync(pin, dI, (size_t)(u * m) * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (vc.d_V) BK_HIP(hipMemcpyAsync(pin + u * m, dvar, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
+  BK_HIP(hipMemcpyAsync(pin, L.d(I), (size_t)(u * m) * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (vc.d_V) BK_HIP(hipMemcpyAsync(pin + u * m, L.d(var), (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
   BK_HIP(hipStreamSynchronize(st));
   if (vc.d_V) std::memcpy(qf.data(), pin + u * m, (size_t)m * sizeof(double));
 
@@ -289,116 +266,33 @@ int interaction_effects_impl(bigkrls_ctx* ctx, const double* h_X, int64_t n, int
 int interaction_effects_se_impl(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
                                 const double* h_coeffs, double sigma, const int64_t* h_pairs, int64_t m,
                                 const double* h_newdata, int64_t u, const Vcov& vc, int64_t block_rows, double* h_se) {
-  BK_TRY(me_check_args(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_newdata, u, h_se));
+  BK_TRY(effects_check_args(ctx, "marginal_effects", h_X && h_y && h_coeffs && h_newdata && h_se, n, p, u, sigma));
   BK_REQUIRE(block_rows >= 0 && block_rows % 128 == 0,
              "interaction_effects_se: block_rows must be 0 or a multiple of 128");
-  BK_TRY(me_check_factors(vc, n));
-  const int64_t k = vc.cols();
+  BK_TRY(vcov_check_factors("marginal_effects", vc, n));
   IePlan pl;
   BK_TRY(ie_plan_pairs(h_pairs, m, p, &pl));
   MePrep mp;
   BK_TRY(me_prepare(h_X, n, p, h_y, pl.which.data(), (int64_t)pl.which.size(), h_newdata, u, &mp));
   BK_TRY(ie_check_diagonals(pl, mp));
-  const int64_t nj = (int64_t)mp.cols.size();
-  // rows per block: beside the b x n block of the test kernel, T = G_jk Q (b x k) or the stored G_jk (b x n)
-  const int64_t wide = vc.d_Q ? k : n;
-  const int64_t b = std::min(block_rows > 0 ? block_rows : pointwise_block_rows(n, wide), u);
-
-  // ---- device layout -------------------------------------------------------------------------------
-  hipStream_t st = ctx->stream;
-  const int64_t colw = (int64_t)((sizeof(MeCol) + 7) / 8);
-  const int64_t up_doubles = n * p + u * p + n + u + nj * colw + k;   // uploaded, in this order
-  const int64_t small_doubles = up_doubles + n * nj + 2 * b * nj + u * m + 64;
-  void* psmall = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_ME_SMALL, small_doubles * (int64_t)sizeof(double), &psmall));
-  double* qd = (double*)psmall;
-  double* dXs = qd; qd += n * p;
-  double* dZs = qd; qd += u * p;
-  double* dnx = qd; qd += n;
-  double* dnz = qd; qd += u;
-  MeCol* dcols = (MeCol*)qd; qd += nj * colw;
-  double* dw = qd; qd += k;
-  double* dS = qd; qd += n * nj;
-  double* dR = qd; qd += b * nj;
-  double* dT = qd; qd += b * nj;
-  double* dse = qd; qd += u * m;
-  void* pk = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_PP_K, b * (n + wide) * (int64_t)sizeof(double), &pk));
-  double* dKn = (double*)pk;
-  double* dP = dKn + b * n;   // T = G_jk Q, or G_jk
-
-  // ---- standardise, squared row norms, upload (as marginal_effects_se_impl) ---------------------------------
-  double* pin = nullptr;
-  BK_HIP(hipStreamSynchronize(st));   // (the pinned buffer may be reallocated)
-  BK_TRY(pinned_get(ctx, std::max(up_doubles, u * m), &pin));
-  {
-    double* hXs = pin;
-    double* hZs = hXs + n * p;
-    double* hnx = hZs + u * p;
-    double* hnz = hnx + n;
-    MeCol* hcols = (MeCol*)(hnz + u);
-    me_standardise(mp, h_X, n, p, h_newdata, u, hXs, hZs);
-    auto sqnorms = [p](const double* A, int64_t rows, double* out) {
-      for (int64_t i = 0; i < rows; ++i) out[i] = 0.0;
-      for (int64_t j = 0; j < p; ++j)
-        for (int64_t i = 0; i < rows; ++i) out[i] += A[j * rows + i] * A[j * rows + i];
-    };
-    sqnorms(hXs, n, hnx);
-    sqnorms(hZs, u, hnz);
-    for (int64_t jj = 0; jj < nj; ++jj) hcols[jj] = mp.col(jj);
-    if (k > 0) std::memcpy((double*)hcols + nj * colw, vc.h_w, (size_t)k * sizeof(double));
-    BK_HIP(hipMemcpyAsync(dXs, pin, (size_t)up_doubles * sizeof(double), hipMemcpyHostToDevice, st));
-  }
-  int blocks = (int)std::min<int64_t>((n * nj + 255) / 256, 4096);
-  hipLaunchKernelGGL(me_se_s_kernel, dim3(blocks), dim3(256), 0, st, (int)n, (int)nj, (const double*)dXs,
-                     (const MeCol*)dcols, dS);
-  BK_CHECK_LAUNCH();
-
-  // ---- row blocks of the new points ---------------------------------------------------------------------
-  for (int64_t r0 = 0; r0 < u; r0 += b) {
-    const int64_t rows = std::min(b, u - r0);
-    BK_TRY(kernel_block_centred(ctx, dZs + r0, rows, u, dnz + r0, dXs, n, n, dnx, p, sigma, dKn, rows, -1));
-    blocks = (int)std::min<int64_t>((rows * nj + 255) / 256, 4096);
-    hipLaunchKernelGGL(me_se_rt_kernel, dim3(blocks), dim3(256), 0, st, (int)rows, (int)nj, (const double*)(dZs + r0),
-                       u, (const MeCol*)dcols, sigma, dR, dT);
-    BK_CHECK_LAUNCH();
-    for (int64_t i = 0; i < m; ++i) {
-      const IePair pr = pl.pos[(size_t)i];
-      const double *r1 = dR + pr.a * rows, *t1 = dT + pr.a * rows, *s1 = dS + pr.a * n;
-      const double *r2 = dR + pr.b * rows, *t2 = dT + pr.b * rows, *s2 = dS + pr.b * n;
-      const double d = pr.a == pr.b ? -2.0 / sigma : 0.0;
-      double* out = dse + i * u + r0;
-      if (vc.d_Q) {
-        BK_TRY(gemm_modulated2(ctx, rows, k, n, dKn, rows, r1, t1, s1, r2, t2, s2, d, vc.d_Q, vc.ldq, dP, rows));   // T = G_jk Q
-        BK_TRY(rowsumsq_weighted(ctx, rows, k, dP, rows, dw, out));
-      } else {
-        blocks = (int)std::min<int64_t>((rows * n + 255) / 256, 8192);
-        hipLaunchKernelGGL(ie_se_modulate_kernel, dim3(blocks), dim3(256), 0, st, (int)rows, (int)n, (const double*)dKn,
-                           r1, t1, s1, r2, t2, s2, d, dP);
-        BK_CHECK_LAUNCH();
-        BK_TRY(quadform_diag(ctx, rows, n, dP, rows, vc.d_V, n, out));                             // diag(G_jk V G_jk')
-      }
+  const int64_t k = vc.cols();
+  auto pair = [&](int64_t i, const SeBlock& b, double* out) -> int {
+    const IePair pr = pl.pos[(size_t)i];
+    const double *r1 = b.R + pr.a * b.rows, *t1 = b.T + pr.a * b.rows, *s1 = b.S + pr.a * n;
+    const double *r2 = b.R + pr.b * b.rows, *t2 = b.T + pr.b * b.rows, *s2 = b.S + pr.b * n;
+    const double d = pr.a == pr.b ? -2.0 / sigma : 0.0;
+    if (vc.d_Q) {
+      BK_TRY(gemm_modulated2(ctx, b.rows, k, n, b.Kn, b.rows, r1, t1, s1, r2, t2, s2, d, vc.d_Q, vc.ldq, b.P,
+                             b.rows));                                                                 // T = G_jk Q
+      return rowsumsq_weighted(ctx, b.rows, k, b.P, b.rows, b.w, out);
     }
-  }
-  BK_HIP(hipMemcpyAsync(pin, dse, (size_t)(u * m) * sizeof(double), hipMemcpyDeviceToHost, st));
-  BK_HIP(hipStreamSynchronize(st));
-
-  // ---- original units; a quadratic form that rounds below zero is zero -----------------------------------------
-  for (int64_t i = 0; i < m; ++i) {
-    const double scale = ie_var_scale(pl, mp, i);
-    const double* v = pin + i * u;
-    double* se = h_se + i * u;
-    for (int64_t r = 0; r < u; ++r) se[r] = std::sqrt(std::max(scale * v[r], 0.0));
-  }
-  return BIGKRLS_OK;
-}
-
-int ie_vcov(const char* who, const double* d_vcov_c, const double* d_Q, int64_t ldq, int64_t k, const double* h_w,
-            bool required, Vcov* vc) {
-  BK_REQUIRE(!(d_vcov_c && d_Q), std::string(who) + ": at most one of vcov.est.c and its factors may be given");
-  BK_REQUIRE(!required || d_vcov_c || d_Q, std::string(who) + ": exactly one of vcov.est.c and its factors must be given");
-  *vc = d_vcov_c ? Vcov::matrix(d_vcov_c) : (d_Q ? Vcov::factors(d_Q, ldq, k, h_w) : Vcov());
-  return BIGKRLS_OK;
+    hipLaunchKernelGGL(ie_se_modulate_kernel, dim3(launch_blocks(b.rows * n, 8192)), dim3(256), 0, ctx->stream,
+                       (int)b.rows, (int)n, b.Kn, r1, t1, s1, r2, t2, s2, d, b.P);
+    BK_CHECK_LAUNCH();
+    return quadform_diag(ctx, b.rows, n, b.P, b.rows, vc.d_V, n, out);                                 // diag(G_jk V G_jk')
+  };
+  return me_se_frame(ctx, mp, h_X, n, p, h_newdata, u, sigma, vc, block_rows, m, pair,
+                     [&](int64_t i) { return ie_var_scale(pl, mp, i); }, h_se);
 }
 
 }  // namespace
@@ -414,7 +308,7 @@ int bigkrls_interaction_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, 
                                 int64_t ldq, int64_t k, const double* h_w, double* h_interactions, double* h_avg,
                                 double* h_var) {
   Vcov vc;
-  BK_TRY(ie_vcov("interaction_effects", d_vcov_c, d_Q, ldq, k, h_w, false, &vc));
+  BK_TRY(vcov_forms("interaction_effects", d_vcov_c, d_Q, ldq, k, h_w, false, &vc));
   return interaction_effects_impl(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_pairs, m, h_newdata, u, vc, h_interactions,
                                   h_avg, h_var);
 }
@@ -424,7 +318,7 @@ int bigkrls_interaction_effects_se(bigkrls_ctx* ctx, const double* h_X, int64_t 
                                    const double* h_newdata, int64_t u, const double* d_vcov_c, const double* d_Q,
                                    int64_t ldq, int64_t k, const double* h_w, int64_t block_rows, double* h_se) {
   Vcov vc;
-  BK_TRY(ie_vcov("interaction_effects_se", d_vcov_c, d_Q, ldq, k, h_w, true, &vc));
+  BK_TRY(vcov_forms("interaction_effects_se", d_vcov_c, d_Q, ldq, k, h_w, true, &vc));
   return interaction_effects_se_impl(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_pairs, m, h_newdata, u, vc, block_rows,
                                      h_se);
 }

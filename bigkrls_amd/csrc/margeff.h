@@ -1,8 +1,9 @@
 // What the post-estimation entries on the modulation m_j(i,l) = r_j[i] + t_j[i] s_j[l] share (csrc/margeff.hip: the
 // marginal effects and their standard errors; csrc/inteff.hip: the interaction effects): the per-column constants, the
 // row- and column-side finalise of the two contractions (also csrc/grpeff.hip: the group effects), the r / t / s
-// kernels, the column dots, the argument checks and the host-side preparation. Internal and header-only: every user
-// compiles it inside its own translation unit (anonymous namespace), nothing here joins the exported symbols.
+// kernels, the column dots, the host-side preparation, the operands of the two contractions and the frame of the
+// pointwise standard errors. Internal and header-only: every user compiles it inside its own translation unit
+// (anonymous namespace), nothing here joins the exported symbols.
 #pragma once
 #include "hostprep.h"
 
@@ -131,20 +132,6 @@ __global__ void me_cols_kernel(int n, int nj, const double* __restrict__ Cm, con
   }
 }
 
-int me_check_args(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y, const double* h_coeffs,
-                  double sigma, const double* h_newdata, int64_t u, const void* h_out) {
-  BK_TRY(check_ctx(ctx));
-  BK_REQUIRE(h_X && h_y && h_coeffs && h_newdata && h_out, "marginal_effects: null argument");
-  BK_REQUIRE(n > 1 && p > 0 && u > 0 && n < (1ll << 31) && u < (1ll << 31), "marginal_effects: bad dimensions");
-  BK_REQUIRE(sigma > 0.0 && std::isfinite(sigma), "marginal_effects: sigma must be a positive scalar");
-  return BIGKRLS_OK;
-}
-
-int me_check_factors(const Vcov& vc, int64_t n) {
-  if (vc.d_Q) BK_REQUIRE(vc.h_w && vc.k > 0 && vc.k <= n && vc.ldq >= n, "marginal_effects: bad factors of vcov.est.c");
-  return BIGKRLS_OK;
-}
-
 // the selected columns (0-based), the training moments and the two-valued columns
 struct MePrep {
   std::vector<int64_t> cols;
@@ -201,6 +188,96 @@ void me_standardise(const MePrep& mp, const double* h_X, int64_t n, int64_t p, c
     standardise_column(h_X + j * n, n, mp.x_mean[j], mp.x_sd[j], hXs + j * n);
     standardise_column(h_newdata + j * u, u, mp.x_mean[j], mp.x_sd[j], hZs + j * u);
   }
+}
+
+// the per-column constants and the weights of the factors, into their staged regions
+void me_stage_cols(const MePrep& mp, const Vcov& vc, MeCol* hcols, double* hw) {
+  for (size_t jj = 0; jj < mp.cols.size(); ++jj) hcols[jj] = mp.col((int64_t)jj);
+  if (vc.cols() > 0) std::memcpy(hw, vc.h_w, (size_t)vc.cols() * sizeof(double));
+}
+
+// the operands of the two contractions: hB (n x q) = [c, {x_j o c | b_j o c}_j], hBs (u x q) = [1, {Zs_j | h_j}_j],
+// q = 1 + |J|; b_j / h_j: the group indicators of a binary column on the raw training / new values
+void me_fill_operands(const MePrep& mp, const double* h_X, int64_t n, const double* h_newdata, int64_t u,
+                      const double* h_coeffs, const double* hXs, const double* hZs, double* hB, double* hBs) {
+  for (int64_t i = 0; i < n; ++i) hB[i] = h_coeffs[i];
+  for (int64_t i = 0; i < u; ++i) hBs[i] = 1.0;
+  for (int64_t jj = 0; jj < (int64_t)mp.cols.size(); ++jj) {
+    const int64_t j = mp.cols[jj];
+    const double* x = h_X + j * n;
+    const double* z = h_newdata + j * u;
+    double* b = hB + (1 + jj) * n;
+    double* bs = hBs + (1 + jj) * u;
+    if (mp.isbin[j]) {                                // group membership on the raw values
+      for (int64_t i = 0; i < n; ++i) b[i] = (x[i] == mp.hi[j] ? 1.0 : 0.0) * h_coeffs[i];
+      for (int64_t i = 0; i < u; ++i) bs[i] = z[i] == mp.hi[j] ? 1.0 : 0.0;
+    } else {
+      for (int64_t i = 0; i < n; ++i) b[i] = hXs[j * n + i] * h_coeffs[i];
+      std::memcpy(bs, hZs + j * u, (size_t)u * sizeof(double));
+    }
+  }
+}
+
+// ---- the pointwise standard errors (bigkrls_marginal_effects_se, bigkrls_interaction_effects_se) -------------------
+// One row block of the new points as the per-item body sees it: Kn (rows x n, ld rows), r and t of the block's rows
+// (rows x nj, ld rows), s of the training rows (n x nj, ld n), the factors' weights, and P beside the block: rows x k
+// (factors) or rows x n (matrix) doubles.
+struct SeBlock {
+  int64_t rows;
+  const double *Kn, *R, *T, *S, *w;
+  double* P;
+};
+
+// After the entry's checks and me_prepare: the new points in row blocks of the test kernel (at most 1 GiB, or
+// block_rows), per block Kn_b once and body(i, block, out) for each of the nout items, which writes the block's
+// quadratic forms g' V g of item i to out (rows doubles); h_se[i] = sqrt(max(scale(i) var, 0)), a form that rounds
+// below zero being zero. vc is the matrix or the factors.
+template <class Body, class Scale>
+int me_se_frame(bigkrls_ctx* ctx, const MePrep& mp, const double* h_X, int64_t n, int64_t p, const double* h_newdata,
+                int64_t u, double sigma, const Vcov& vc, int64_t block_rows, int64_t nout, Body body, Scale scale,
+                double* h_se) {
+  const int64_t k = vc.cols(), nj = (int64_t)mp.cols.size();
+  // rows per block: beside the b x n block of the test kernel, T = G Q (b x k) or the stored G (b x n)
+  const int64_t wide = vc.d_Q ? k : n;
+  const int64_t b = std::min(block_rows > 0 ? block_rows : pointwise_block_rows(n, wide), u);
+
+  hipStream_t st = ctx->stream;
+  Layout L;
+  const Region Xs = L.up(n * p), Zs = L.up(u * p), nx = L.up(n), nz = L.up(u), cols = L.up_records<MeCol>(nj),
+               w = L.up(k);
+  const Region S = L.dev(n * nj), R = L.dev(b * nj), T = L.dev(b * nj), se = L.down(u * nout);
+  BK_TRY(layout_device(ctx, SLOT_ME_SMALL, &L));
+  void* pk = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_PP_K, b * (n + wide) * (int64_t)sizeof(double), &pk));
+  double* dKn = (double*)pk;
+
+  // standardise, squared row norms (the training rows are centred by their standardisation: no further shift), upload
+  BK_TRY(layout_pinned(ctx, &L));
+  me_standardise(mp, h_X, n, p, h_newdata, u, L.h(Xs), L.h(Zs));
+  host_sqnorms(L.h(Xs), n, p, L.h(nx));
+  host_sqnorms(L.h(Zs), u, p, L.h(nz));
+  me_stage_cols(mp, vc, L.h<MeCol>(cols), L.h(w));
+  BK_TRY(layout_upload(ctx, L));
+  hipLaunchKernelGGL(me_se_s_kernel, dim3(launch_blocks(n * nj, 4096)), dim3(256), 0, st, (int)n, (int)nj,
+                     (const double*)L.d(Xs), (const MeCol*)L.d<MeCol>(cols), L.d(S));
+  BK_CHECK_LAUNCH();
+
+  for (int64_t r0 = 0; r0 < u; r0 += b) {
+    const int64_t rows = std::min(b, u - r0);
+    BK_TRY(kernel_block_centred(ctx, L.d(Zs) + r0, rows, u, L.d(nz) + r0, L.d(Xs), n, n, L.d(nx), p, sigma, dKn, rows, -1));
+    hipLaunchKernelGGL(me_se_rt_kernel, dim3(launch_blocks(rows * nj, 4096)), dim3(256), 0, st, (int)rows, (int)nj,
+                       (const double*)(L.d(Zs) + r0), u, (const MeCol*)L.d<MeCol>(cols), sigma, L.d(R), L.d(T));
+    BK_CHECK_LAUNCH();
+    const SeBlock blk{rows, dKn, L.d(R), L.d(T), L.d(S), L.d(w), dKn + b * n};
+    for (int64_t i = 0; i < nout; ++i) BK_TRY(body(i, blk, L.d(se) + i * u + r0));
+  }
+  BK_TRY(layout_download(ctx, L));
+  for (int64_t i = 0; i < nout; ++i) {
+    const double sc = scale(i);
+    const double* v = L.pinned() + i * u;
+    for (int64_t r = 0; r < u; ++r) h_se[i * u + r] = std::sqrt(std::max(sc * v[r], 0.0));
+  }
+  return BIGKRLS_OK;
 }
 
 }  // namespace

@@ -55,87 +55,46 @@ int marginal_effects_impl(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_
                           const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
                           const double* h_newdata, int64_t u, const Vcov& vc, double* h_derivatives, double* h_avg,
                           double* h_var) {
-  BK_TRY(me_check_args(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_newdata, u, h_avg));
+  BK_TRY(effects_check_args(ctx, "marginal_effects", h_X && h_y && h_coeffs && h_newdata && h_avg, n, p, u, sigma));
   BK_REQUIRE(vc.given() == (h_var != nullptr),
              "marginal_effects: h_var is written exactly when vcov.est.c (or its factors) is given");
-  BK_TRY(me_check_factors(vc, n));
+  BK_TRY(vcov_check_factors("marginal_effects", vc, n));
   const int64_t k = vc.cols();
   MePrep mp;
   BK_TRY(me_prepare(h_X, n, p, h_y, h_which, n_which, h_newdata, u, &mp));
-  const std::vector<int64_t>& cols = mp.cols;
-  const std::vector<double>&x_mean = mp.x_mean, &x_sd = mp.x_sd, &lo = mp.lo, &hi = mp.hi;
-  const std::vector<char>& isbin = mp.isbin;
-  const double y_sd = mp.y_sd;
-  const int64_t nj = (int64_t)cols.size(), q = 1 + nj;
+  const int64_t nj = (int64_t)mp.cols.size(), q = 1 + nj;
 
   // ---- device layout -------------------------------------------------------------------------------
   hipStream_t st = ctx->stream;
-  const int64_t colw = (int64_t)((sizeof(MeCol) + 7) / 8);
-  const int64_t up_doubles = n * p + u * p + n * q + u * q + nj * colw + k;  // uploaded, in this order
-  const int64_t small_doubles = up_doubles + u * q + n * q + u * nj + 2 * n * nj + nj + 64;
-  void* psmall = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_ME_SMALL, small_doubles * (int64_t)sizeof(double), &psmall));
-  double* qd = (double*)psmall;
-  double* dXs = qd; qd += n * p;
-  double* dZs = qd; qd += u * p;
-  double* dB = qd; qd += n * q;
-  double* dBs = qd; qd += u * q;
-  MeCol* dcols = (MeCol*)qd; qd += nj * colw;
-  double* dw = qd; qd += k;
-  double* dR = qd; qd += u * q;
-  double* dC = qd; qd += n * q;
-  double* dD = qd; qd += u * nj;
-  double* dS = qd; qd += n * nj;
-  double* dT = qd; qd += n * nj;
-  double* dvar = qd; qd += nj;
+  Layout L;
+  const Region Xs = L.up(n * p), Zs = L.up(u * p), B = L.up(n * q), Bs = L.up(u * q), cols = L.up_records<MeCol>(nj),
+               w = L.up(k);
+  const Region R = L.dev(u * q), C = L.dev(n * q), D = L.dev(u * nj), S = L.dev(n * nj), T = L.dev(n * nj),
+               var = L.dev(nj);
+  BK_TRY(layout_device(ctx, SLOT_ME_SMALL, &L));
+  const MeCol* dcols = L.d<MeCol>(cols);
 
   // ---- standardise (training means and sds, as bigkrls_predict), operands, upload ---------------------
-  double* pin = nullptr;
-  BK_HIP(hipStreamSynchronize(st));   // (the pinned buffer may be reallocated)
-  BK_TRY(pinned_get(ctx, std::max(up_doubles, u * nj + nj), &pin));
-  {
-    double* hXs = pin;
-    double* hZs = hXs + n * p;
-    double* hB = hZs + u * p;
-    double* hBs = hB + n * q;
-    MeCol* hcols = (MeCol*)(hBs + u * q);
-    me_standardise(mp, h_X, n, p, h_newdata, u, hXs, hZs);
-    for (int64_t i = 0; i < n; ++i) hB[i] = h_coeffs[i];
-    for (int64_t i = 0; i < u; ++i) hBs[i] = 1.0;
-    for (int64_t jj = 0; jj < nj; ++jj) {
-      const int64_t j = cols[jj];
-      const double* x = h_X + j * n;
-      const double* z = h_newdata + j * u;
-      double* b = hB + (1 + jj) * n;
-      double* bs = hBs + (1 + jj) * u;
-      if (isbin[j]) {                                   // group membership on the raw values
-        for (int64_t i = 0; i < n; ++i) b[i] = (x[i] == hi[j] ? 1.0 : 0.0) * h_coeffs[i];
-        for (int64_t i = 0; i < u; ++i) bs[i] = z[i] == hi[j] ? 1.0 : 0.0;
-      } else {
-        for (int64_t i = 0; i < n; ++i) b[i] = hXs[j * n + i] * h_coeffs[i];
-        std::memcpy(bs, hZs + j * u, (size_t)u * sizeof(double));
-      }
-      hcols[jj] = mp.col(jj);
-    }
-    if (k > 0) std::memcpy((double*)hcols + nj * colw, vc.h_w, (size_t)k * sizeof(double));
-    BK_HIP(hipMemcpyAsync(dXs, pin, (size_t)up_doubles * sizeof(double), hipMemcpyHostToDevice, st));
-  }
+  BK_TRY(layout_pinned(ctx, &L, u * nj + nj));
+  double* pin = L.pinned();
+  me_standardise(mp, h_X, n, p, h_newdata, u, L.h(Xs), L.h(Zs));
+  me_fill_operands(mp, h_X, n, h_newdata, u, h_coeffs, L.h(Xs), L.h(Zs), L.h(B), L.h(Bs));
+  me_stage_cols(mp, vc, L.h<MeCol>(cols), L.h(w));
+  BK_TRY(layout_upload(ctx, L));
 
   // ---- the two fused contractions and their finalise -----------------------------------------------
-  BK_TRY(kernel_contract(ctx, dZs, u, u, dXs, n, n, p, sigma, dB, q, n, 0, dR, u));    // R = Kn B
-  BK_TRY(kernel_contract(ctx, dZs, u, u, dXs, n, n, p, sigma, dBs, q, u, 1, dC, n));   // C = Kn' B*
-  int blocks = (int)std::min<int64_t>((u * nj + 255) / 256, 4096);
-  hipLaunchKernelGGL(me_rows_kernel, dim3(blocks), dim3(256), 0, st, (int)u, (int)nj, (const double*)dR,
-                     (const double*)dZs, (const double*)dBs, (const MeCol*)dcols, sigma, dD);
+  BK_TRY(kernel_contract(ctx, L.d(Zs), u, u, L.d(Xs), n, n, p, sigma, L.d(B), q, n, 0, L.d(R), u));    // R = Kn B
+  BK_TRY(kernel_contract(ctx, L.d(Zs), u, u, L.d(Xs), n, n, p, sigma, L.d(Bs), q, u, 1, L.d(C), n));   // C = Kn' B*
+  hipLaunchKernelGGL(me_rows_kernel, dim3(launch_blocks(u * nj, 4096)), dim3(256), 0, st, (int)u, (int)nj,
+                     (const double*)L.d(R), (const double*)L.d(Zs), (const double*)L.d(Bs), dcols, sigma, L.d(D));
   BK_CHECK_LAUNCH();
-  blocks = (int)std::min<int64_t>((n * nj + 255) / 256, 4096);
-  hipLaunchKernelGGL(me_cols_kernel, dim3(blocks), dim3(256), 0, st, (int)n, (int)nj, (const double*)dC,
-                     (const double*)dXs, (const MeCol*)dcols, sigma, dS, (int64_t)0, n, (int64_t)0);
+  hipLaunchKernelGGL(me_cols_kernel, dim3(launch_blocks(n * nj, 4096)), dim3(256), 0, st, (int)n, (int)nj,
+                     (const double*)L.d(C), (const double*)L.d(Xs), dcols, sigma, L.d(S), (int64_t)0, n, (int64_t)0);
   BK_CHECK_LAUNCH();
   if (vc.d_V) {
-    BK_TRY(gemm(ctx, 0, 0, n, nj, n, 1.0, vc.d_V, n, dS, n, 0.0, dT, n));          // T = vcov.est.c S
-    hipLaunchKernelGGL(me_coldot_kernel, dim3((unsigned)nj), dim3(256), 0, st, (int)n, (const double*)dS,
-                       (const double*)dT, dvar);
+    BK_TRY(gemm(ctx, 0, 0, n, nj, n, 1.0, vc.d_V, n, L.d(S), n, 0.0, L.d(T), n));          // T = vcov.est.c S
+    hipLaunchKernelGGL(me_coldot_kernel, dim3((unsigned)nj), dim3(256), 0, st, (int)n, (const double*)L.d(S),
+                       (const double*)L.d(T), L.d(var));
     BK_CHECK_LAUNCH();
   }
   // s'(vcov.est.c)s per column. From the factors it is the fit's own step, which returns synchronised with its result
@@ -144,20 +103,20 @@ int marginal_effects_impl(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_
   std::vector<double> qf((size_t)nj, 0.0);
   if (vc.d_Q) {
     const std::vector<double> ones((size_t)nj, 1.0);
-    BK_TRY(deriv_var(ctx, vc.d_Q, n, k, vc.ldq, dw, dS, nj, n, ones.data(), qf.data()));
+    BK_TRY(deriv_var(ctx, vc.d_Q, n, k, vc.ldq, L.d(w), L.d(S), nj, n, ones.data(), qf.data()));
   }
-  BK_HIP(hipMemcpyAsync(pin, dD, (size_t)(u * nj) * sizeof(double), hipMemcpyDeviceToHost, st));
-  if (vc.d_V) BK_HIP(hipMemcpyAsync(pin + u * nj, dvar, (size_t)nj * sizeof(double), hipMemcpyDeviceToHost, st));
+  BK_HIP(hipMemcpyAsync(pin, L.d(D), (size_t)(u * nj) * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (vc.d_V) BK_HIP(hipMemcpyAsync(pin + u * nj, L.d(var), (size_t)nj * sizeof(double), hipMemcpyDeviceToHost, st));
   BK_HIP(hipStreamSynchronize(st));
   if (vc.d_V) std::memcpy(qf.data(), pin + u * nj, (size_t)nj * sizeof(double));
 
   // ---- original units (R/bigKRLS.R:393-407): D sd(y)/sd(x_j), its column means, var (sd(y)/sd(x_j))^2 -----
   for (int64_t jj = 0; jj < nj; ++jj) {
-    const int64_t j = cols[jj];
+    const int64_t j = mp.cols[jj];
     double* col = pin + jj * u;
     long double s = 0.0L;
     for (int64_t r = 0; r < u; ++r) {
-      col[r] = (y_sd * col[r]) / x_sd[j];
+      col[r] = (mp.y_sd * col[r]) / mp.x_sd[j];
       s += col[r];
     }
     h_avg[jj] = (double)(s / (long double)u);
@@ -166,120 +125,47 @@ int marginal_effects_impl(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_
       // sd(y)^2 cancels: V = vcov.est.c / sd(y)^2 in standardised units, (sd(y)/sd(x_j))^2 back to the original ones
       const double ud = (double)u;
       double scale;
-      if (isbin[j]) {
-        const double dz = (hi[j] - x_mean[j]) / x_sd[j] - (lo[j] - x_mean[j]) / x_sd[j];
+      if (mp.isbin[j]) {
+        const double dz = (mp.hi[j] - mp.x_mean[j]) / mp.x_sd[j] - (mp.lo[j] - mp.x_mean[j]) / mp.x_sd[j];
         scale = 2.0 / (dz * dz * ud * ud);
       } else {
         scale = 4.0 / (sigma * sigma * ud * ud);
       }
-      h_var[jj] = scale * qf[jj] / (x_sd[j] * x_sd[j]);
+      h_var[jj] = scale * qf[jj] / (mp.x_sd[j] * mp.x_sd[j]);
     }
   }
   return BIGKRLS_OK;
 }
 
-// bigkrls_marginal_effects_se: vc is the matrix or the factors (exactly one, checked by the entry)
+// bigkrls_marginal_effects_se: vc is the matrix or the factors (exactly one, checked by the entry). Original units: the
+// variance times (sd(y)/sd(x_j))^2 with V = vcov.est.c / sd(y)^2 -- sd(y)^2 cancels as in marginal_effects_impl; the
+// factor 2 of the binary columns.
 int marginal_effects_se_impl(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
                              const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
                              const double* h_newdata, int64_t u, const Vcov& vc, int64_t block_rows, double* h_se) {
-  BK_TRY(me_check_args(ctx, h_X, n, p, h_y, h_coeffs, sigma, h_newdata, u, h_se));
+  BK_TRY(effects_check_args(ctx, "marginal_effects", h_X && h_y && h_coeffs && h_newdata && h_se, n, p, u, sigma));
   BK_REQUIRE(block_rows >= 0 && block_rows % 128 == 0, "marginal_effects_se: block_rows must be 0 or a multiple of 128");
-  BK_TRY(me_check_factors(vc, n));
-  const int64_t k = vc.cols();
+  BK_TRY(vcov_check_factors("marginal_effects", vc, n));
   MePrep mp;
   BK_TRY(me_prepare(h_X, n, p, h_y, h_which, n_which, h_newdata, u, &mp));
-  const int64_t nj = (int64_t)mp.cols.size();
-  // rows per block: beside the b x n block of the test kernel, T = G_j Q (b x k) or the stored G_j (b x n)
-  const int64_t wide = vc.d_Q ? k : n;
-  const int64_t b = std::min(block_rows > 0 ? block_rows : pointwise_block_rows(n, wide), u);
-
-  // ---- device layout -------------------------------------------------------------------------------
-  hipStream_t st = ctx->stream;
-  const int64_t colw = (int64_t)((sizeof(MeCol) + 7) / 8);
-  const int64_t up_doubles = n * p + u * p + n + u + nj * colw + k;   // uploaded, in this order
-  const int64_t small_doubles = up_doubles + n * nj + 2 * b * nj + u * nj + 64;
-  void* psmall = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_ME_SMALL, small_doubles * (int64_t)sizeof(double), &psmall));
-  double* qd = (double*)psmall;
-  double* dXs = qd; qd += n * p;
-  double* dZs = qd; qd += u * p;
-  double* dnx = qd; qd += n;
-  double* dnz = qd; qd += u;
-  MeCol* dcols = (MeCol*)qd; qd += nj * colw;
-  double* dw = qd; qd += k;
-  double* dS = qd; qd += n * nj;
-  double* dR = qd; qd += b * nj;
-  double* dT = qd; qd += b * nj;
-  double* dse = qd; qd += u * nj;
-  void* pk = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_PP_K, b * (n + wide) * (int64_t)sizeof(double), &pk));
-  double* dKn = (double*)pk;
-  double* dP = dKn + b * n;   // T = G_j Q, or G_j
-
-  // ---- standardise, squared row norms (the training rows are centred by their standardisation: no further shift),
-  //      upload -----------------------------------------------------------------------------------------
-  double* pin = nullptr;
-  BK_HIP(hipStreamSynchronize(st));   // (the pinned buffer may be reallocated)
-  BK_TRY(pinned_get(ctx, std::max(up_doubles, u * nj), &pin));
-  {
-    double* hXs = pin;
-    double* hZs = hXs + n * p;
-    double* hnx = hZs + u * p;
-    double* hnz = hnx + n;
-    MeCol* hcols = (MeCol*)(hnz + u);
-    me_standardise(mp, h_X, n, p, h_newdata, u, hXs, hZs);
-    auto sqnorms = [p](const double* A, int64_t rows, double* out) {
-      for (int64_t i = 0; i < rows; ++i) out[i] = 0.0;
-      for (int64_t j = 0; j < p; ++j)
-        for (int64_t i = 0; i < rows; ++i) out[i] += A[j * rows + i] * A[j * rows + i];
-    };
-    sqnorms(hXs, n, hnx);
-    sqnorms(hZs, u, hnz);
-    for (int64_t jj = 0; jj < nj; ++jj) hcols[jj] = mp.col(jj);
-    if (k > 0) std::memcpy((double*)hcols + nj * colw, vc.h_w, (size_t)k * sizeof(double));
-    BK_HIP(hipMemcpyAsync(dXs, pin, (size_t)up_doubles * sizeof(double), hipMemcpyHostToDevice, st));
-  }
-  int blocks = (int)std::min<int64_t>((n * nj + 255) / 256, 4096);
-  hipLaunchKernelGGL(me_se_s_kernel, dim3(blocks), dim3(256), 0, st, (int)n, (int)nj, (const double*)dXs,
-                     (const MeCol*)dcols, dS);
-  BK_CHECK_LAUNCH();
-
-  // ---- row blocks of the new points ---------------------------------------------------------------------
-  for (int64_t r0 = 0; r0 < u; r0 += b) {
-    const int64_t rows = std::min(b, u - r0);
-    BK_TRY(kernel_block_centred(ctx, dZs + r0, rows, u, dnz + r0, dXs, n, n, dnx, p, sigma, dKn, rows, -1));
-    blocks = (int)std::min<int64_t>((rows * nj + 255) / 256, 4096);
-    hipLaunchKernelGGL(me_se_rt_kernel, dim3(blocks), dim3(256), 0, st, (int)rows, (int)nj, (const double*)(dZs + r0),
-                       u, (const MeCol*)dcols, sigma, dR, dT);
-    BK_CHECK_LAUNCH();
-    for (int64_t jj = 0; jj < nj; ++jj) {
-      const double *r = dR + jj * rows, *t = dT + jj * rows, *s = dS + jj * n;
-      double* out = dse + jj * u + r0;
-      if (vc.d_Q) {
-        BK_TRY(gemm_modulated(ctx, rows, k, n, dKn, rows, r, t, s, vc.d_Q, vc.ldq, dP, rows));     // T = G_j Q
-        BK_TRY(rowsumsq_weighted(ctx, rows, k, dP, rows, dw, out));
-      } else {
-        blocks = (int)std::min<int64_t>((rows * n + 255) / 256, 8192);
-        hipLaunchKernelGGL(me_se_modulate_kernel, dim3(blocks), dim3(256), 0, st, (int)rows, (int)n,
-                           (const double*)dKn, r, t, s, dP);
-        BK_CHECK_LAUNCH();
-        BK_TRY(quadform_diag(ctx, rows, n, dP, rows, vc.d_V, n, out));                             // diag(G_j V G_j')
-      }
+  const int64_t k = vc.cols();
+  auto column = [&](int64_t jj, const SeBlock& b, double* out) -> int {
+    const double *r = b.R + jj * b.rows, *t = b.T + jj * b.rows, *s = b.S + jj * n;
+    if (vc.d_Q) {
+      BK_TRY(gemm_modulated(ctx, b.rows, k, n, b.Kn, b.rows, r, t, s, vc.d_Q, vc.ldq, b.P, b.rows));     // T = G_j Q
+      return rowsumsq_weighted(ctx, b.rows, k, b.P, b.rows, b.w, out);
     }
-  }
-  BK_HIP(hipMemcpyAsync(pin, dse, (size_t)(u * nj) * sizeof(double), hipMemcpyDeviceToHost, st));
-  BK_HIP(hipStreamSynchronize(st));
-
-  // ---- original units: the variance times (sd(y)/sd(x_j))^2 with V = vcov.est.c / sd(y)^2 -- sd(y)^2 cancels as in
-  //      marginal_effects_impl; the factor 2 of the binary columns; a quadratic form that rounds below zero is zero -----
-  for (int64_t jj = 0; jj < nj; ++jj) {
+    hipLaunchKernelGGL(me_se_modulate_kernel, dim3(launch_blocks(b.rows * n, 8192)), dim3(256), 0, ctx->stream,
+                       (int)b.rows, (int)n, b.Kn, r, t, s, b.P);
+    BK_CHECK_LAUNCH();
+    return quadform_diag(ctx, b.rows, n, b.P, b.rows, vc.d_V, n, out);                                 // diag(G_j V G_j')
+  };
+  auto scale = [&](int64_t jj) {
     const int64_t j = mp.cols[jj];
-    const double scale = (mp.isbin[j] ? 2.0 : 1.0) / (mp.x_sd[j] * mp.x_sd[j]);
-    const double* v = pin + jj * u;
-    double* se = h_se + jj * u;
-    for (int64_t i = 0; i < u; ++i) se[i] = std::sqrt(std::max(scale * v[i], 0.0));
-  }
-  return BIGKRLS_OK;
+    return (mp.isbin[j] ? 2.0 : 1.0) / (mp.x_sd[j] * mp.x_sd[j]);
+  };
+  return me_se_frame(ctx, mp, h_X, n, p, h_newdata, u, sigma, vc, block_rows, (int64_t)mp.cols.size(), column, scale,
+                     h_se);
 }
 
 }  // namespace

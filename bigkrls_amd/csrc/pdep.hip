@@ -17,9 +17,6 @@
 // O(G n k) or O(G n^2) per column (curve_tail, curvetail.h). Column j of the reference sample is never read for column j's curve.
 // Device memory: O((u + n)(p + |J|)) plus the loop splits' partials, and per column A_j (at most 1 GiB) with its product.
 #include "curvetail.h"
-#include "hostprep.h"
-
-#include <cstring>
 
 namespace bk {
 namespace {
@@ -49,18 +46,9 @@ int bigkrls_partial_dependence(bigkrls_ctx* ctx, const double* h_X, int64_t n, i
                                const double* h_newdata, int64_t u, const double* h_grid, const int64_t* h_grid_off,
                                const double* d_vcov_c, const double* d_Q, int64_t ldq, int64_t k, const double* h_w,
                                double neffective, double* h_pd, double* h_se, double* h_cov) {
-  BK_TRY(check_ctx(ctx));
-  BK_REQUIRE(h_X && h_y && h_coeffs && h_grid && h_grid_off && h_pd, "partial_dependence: null argument");
-  if (!h_newdata) u = n;   // the reference sample is the training rows
-  BK_REQUIRE(n > 1 && p > 0 && u > 0 && n < (1ll << 31) && u < (1ll << 31), "partial_dependence: bad dimensions");
-  BK_REQUIRE(sigma > 0.0 && std::isfinite(sigma), "partial_dependence: sigma must be a positive scalar");
-  BK_REQUIRE(!(d_vcov_c && d_Q), "partial_dependence: at most one of vcov.est.c and its factors may be given");
-  const Vcov vc = d_vcov_c ? Vcov::matrix(d_vcov_c) : (d_Q ? Vcov::factors(d_Q, ldq, k, h_w) : Vcov());
-  BK_REQUIRE(vc.given() || (!h_se && !h_cov),
-             "partial_dependence: h_se and h_cov are written only when vcov.est.c (or its factors) is given");
-  if (vc.d_Q) BK_REQUIRE(vc.h_w && vc.k > 0 && vc.k <= n && vc.ldq >= n, "partial_dependence: bad factors of vcov.est.c");
-  const bool want_var = vc.given() && (h_se || h_cov);
-  const int64_t kq = want_var ? vc.cols() : 0;
+  CurveArgs ca;
+  BK_TRY(curve_check_args(ctx, "partial_dependence", h_X && h_y && h_coeffs && h_grid && h_grid_off && h_pd, n, p,
+                          h_newdata, &u, sigma, d_vcov_c, d_Q, ldq, k, h_w, h_se, h_cov, &ca));
 
   // ---- the selected columns and their grids ------------------------------------------------------------------
   std::vector<int64_t> cols;
@@ -74,25 +62,10 @@ int bigkrls_partial_dependence(bigkrls_ctx* ctx, const double* h_X, int64_t n, i
     for (int64_t j = 0; j < p; ++j) cols.push_back(j);
   }
   const int64_t nj = (int64_t)cols.size();
-  const int64_t gcap = (1ll << 30) / (8 * n);
-  BK_REQUIRE(h_grid_off[0] == 0, "partial_dependence: the grid offsets must start at 0");
-  int64_t gmax = 0, cov_doubles = 0;
-  for (int64_t jj = 0; jj < nj; ++jj) {
-    const int64_t G = h_grid_off[jj + 1] - h_grid_off[jj];
-    BK_REQUIRE(G >= 1, "partial_dependence: the grid of column " + std::to_string(cols[jj] + 1) + " is empty");
-    BK_REQUIRE(G <= gcap, "partial_dependence: the grid of column " + std::to_string(cols[jj] + 1) + " has " +
-                              std::to_string(G) + " values; at most " + std::to_string(gcap) +
-                              " fit the 1 GiB block (8 G n <= 2^30 bytes)");
-    gmax = std::max(gmax, G);
-    cov_doubles += G * G;
-  }
-  const int64_t T = h_grid_off[nj];
-  BK_REQUIRE(T < (1ll << 31), "partial_dependence: too many grid values");
-  if (!h_cov) cov_doubles = 0;
-  for (int64_t i = 0; i < T; ++i) BK_REQUIRE(std::isfinite(h_grid[i]), "partial_dependence: the grid contains missing or infinite values");
-  if (h_newdata)
-    for (int64_t i = 0; i < u * p; ++i)
-      BK_REQUIRE(std::isfinite(h_newdata[i]), "partial_dependence: newdata contains missing or infinite values");
+  CurvePlan cp;
+  BK_TRY(curve_plan("partial_dependence", n, p, nj, h_grid, h_grid_off, h_cov != nullptr, h_newdata, u,
+                    [&](int64_t jj) { return "column " + std::to_string(cols[jj] + 1); }, &cp));
+  const int64_t T = cp.T;
 
   // ---- the training moments (as bigkrls_marginal_effects) ----------------------------------------------------
   std::vector<double> x_mean((size_t)p), x_sd((size_t)p);
@@ -104,67 +77,21 @@ int bigkrls_partial_dependence(bigkrls_ctx* ctx, const double* h_X, int64_t n, i
   mean_sd(h_y, n, &y_mean, &y_sd);
   BK_REQUIRE(y_sd > 0.0, "partial_dependence: y is a constant");
 
-  // ---- device layout -----------------------------------------------------------------------------------------
-  hipStream_t st = ctx->stream;
-  const int64_t zs_doubles = h_newdata ? u * p : 0;
-  const int64_t up_doubles = n * p + zs_doubles + n + kq + T;   // uploaded, in this order
-  const int64_t down_doubles = 2 * T + cov_doubles;             // read back: pd, the variances, the covariance blocks
-  void* psmall = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_PD_SMALL, (up_doubles + n * nj + down_doubles + 64) * (int64_t)sizeof(double), &psmall));
-  double* qd = (double*)psmall;
-  double* dXs = qd; qd += n * p;
-  double* dZs = h_newdata ? qd : dXs; qd += zs_doubles;
-  double* dc = qd; qd += n;
-  double* dw = qd; qd += kq;
-  double* dvs = qd; qd += T;
-  double* dM = qd; qd += n * nj;
-  double* dpd = qd; qd += T;
-  double* dvar = qd; qd += T;
-  double* dcov = qd; qd += cov_doubles;
-  // one column's A_j, and beside it T = A_j Q and T diag(w) (factors) or A_j vcov.est.c (matrix, only for the covariance)
-  const int64_t wide = !want_var ? 0 : (vc.d_Q ? 2 * kq : (h_cov ? n : 0));
-  void* pa = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_PD_A, gmax * (n + wide) * (int64_t)sizeof(double), &pa));
-  double* dA = (double*)pa;
-  double* dP = dA + gmax * n;
-
-  // ---- standardise (training means and sds, as bigkrls_predict), upload ---------------------------------------
-  double* pin = nullptr;
-  BK_HIP(hipStreamSynchronize(st));   // (the pinned buffer may be reallocated)
-  BK_TRY(pinned_get(ctx, std::max(up_doubles, down_doubles), &pin));
-  {
-    double* hXs = pin;
-    double* hZs = hXs + n * p;
-    double* hc = hZs + zs_doubles;
-    double* hw = hc + n;
-    double* hvs = hw + kq;
-    for (int64_t j = 0; j < p; ++j) {
-      standardise_column(h_X + j * n, n, x_mean[j], x_sd[j], hXs + j * n);
-      if (h_newdata) standardise_column(h_newdata + j * u, u, x_mean[j], x_sd[j], hZs + j * u);
-    }
-    std::memcpy(hc, h_coeffs, (size_t)n * sizeof(double));
-    if (kq > 0) std::memcpy(hw, vc.h_w, (size_t)kq * sizeof(double));
-    for (int64_t jj = 0; jj < nj; ++jj) {
-      const int64_t j = cols[jj], g0 = h_grid_off[jj];
-      standardise_column(h_grid + g0, h_grid_off[jj + 1] - g0, x_mean[j], x_sd[j], hvs + g0);
-    }
-    BK_HIP(hipMemcpyAsync(dXs, pin, (size_t)up_doubles * sizeof(double), hipMemcpyHostToDevice, st));
-  }
-
-  // ---- M for all selected columns in one fused pass, then column by column ------------------------------------
-  BK_TRY(kernel_loo_colsums(ctx, dZs, u, u, dXs, n, n, p, sigma, cols.data(), nj, dM, n));
-  double* dcov_j = dcov;
-  for (int64_t jj = 0; jj < nj; ++jj) {
-    const int64_t j = cols[jj], g0 = h_grid_off[jj], G = h_grid_off[jj + 1] - g0;
-    const int blocks = (int)std::min<int64_t>((G * n + 255) / 256, 8192);
-    hipLaunchKernelGGL(pd_rows_kernel, dim3(blocks), dim3(256), 0, st, (int)G, (int)n, (const double*)(dM + jj * n),
-                       (const double*)(dXs + j * n), (const double*)(dvs + g0), -1.0 / sigma, 1.0 / (double)u, dA);
-    BK_CHECK_LAUNCH();
-    BK_TRY(curve_tail(ctx, vc, want_var, G, n, kq, dA, dP, dc, dw, dpd + g0, dvar + g0, h_cov ? dcov_j : nullptr));
-    if (h_cov) dcov_j += G * G;
-  }
-  BK_HIP(hipMemcpyAsync(pin, dpd, (size_t)down_doubles * sizeof(double), hipMemcpyDeviceToHost, st));
-  BK_HIP(hipStreamSynchronize(st));
+  // ---- M for all selected columns in one fused pass, then column by column (curve_frame, curvetail.h) ----------
+  const double* pin = nullptr;
+  BK_TRY(curve_frame(
+      ctx, h_X, n, p, h_coeffs, h_newdata, u, x_mean, x_sd, ca, h_cov != nullptr, cp, h_grid, h_grid_off, nj,
+      [&](int64_t jj) { return cols[jj]; },
+      [&](const double* dZs, const double* dXs, double* dM) {
+        return kernel_loo_colsums(ctx, dZs, u, u, dXs, n, n, p, sigma, cols.data(), nj, dM, n);
+      },
+      [&](int64_t jj, int64_t G, const double* dXs, const double* dvs, const double* dM, double* dA) -> int {
+        hipLaunchKernelGGL(pd_rows_kernel, dim3(launch_blocks(G * n, 8192)), dim3(256), 0, ctx->stream, (int)G, (int)n,
+                           dM + jj * n, dXs + cols[jj] * n, dvs, -1.0 / sigma, 1.0 / (double)u, dA);
+        BK_CHECK_LAUNCH();
+        return BIGKRLS_OK;
+      },
+      &pin));
 
   // ---- original units; bigkrls_predict's factor on the variance (quirk Q10); a form that rounds below zero is zero ----
   const double f = neffective > 0.0 ? std::sqrt((double)n / neffective) : 1.0;
@@ -172,7 +99,7 @@ int bigkrls_partial_dependence(bigkrls_ctx* ctx, const double* h_X, int64_t n, i
   if (h_se)
     for (int64_t i = 0; i < T; ++i) h_se[i] = std::sqrt(std::max(f * pin[T + i], 0.0));
   if (h_cov)
-    for (int64_t i = 0; i < cov_doubles; ++i) h_cov[i] = f * pin[2 * T + i];
+    for (int64_t i = 0; i < cp.cov_doubles; ++i) h_cov[i] = f * pin[2 * T + i];
   return BIGKRLS_OK;
 }
 
