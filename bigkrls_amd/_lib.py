@@ -113,6 +113,9 @@ SIGNATURES = {
     "bigkrls_dev_fill_random": [vp, vp, i64, C.c_uint32],
     "bigkrls_dev_cholqr2": [vp, vp, vp, i64, i64, vp, pi32, vp],
     "bigkrls_dev_panel_factor": [vp, vp, i64, i64, vp, vp, vp, vp, vp, pi32],
+    "bigkrls_dev_syr2k": [vp, C.c_int, i64, i64, f64, vp, i64, vp, i64, vp, i64, i64, i64, C.c_int],
+    "bigkrls_dev_gemm_skinny48": [vp, i64, i64, i64, vp, i64, vp, i64, vp, i64],
+    "bigkrls_dev_gemm_batched": [vp, i64, pi64, pi64, pi64, pi64, pi64, pi64, pi64, pi64, pi64, pi64, i64, i64],
     "bigkrls_dev_lanczos_projected": [vp, vp, vp, i64, i64, vp],
     "bigkrls_dev_copy_matrix": [vp, vp, i64, i64, i64, vp, i64],
     "bigkrls_dev_qty": [vp, vp, i64, i64, i64, vp, vp],

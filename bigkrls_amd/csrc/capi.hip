@@ -648,6 +648,65 @@ int bigkrls_dev_panel_factor(bigkrls_ctx* ctx, double* P, int64_t ld, int64_t m,
   return panel_factor(ctx, P, ld, m, Vw, V, T, Tfold, tau, h_fallback);
 }
 
+int bigkrls_dev_syr2k(bigkrls_ctx* ctx, int form, int64_t m, int64_t k, double alpha, const double* A, int64_t lda,
+                      const double* B, int64_t ldb, double* C, int64_t ldc, int64_t begin, int64_t end, int flags) {
+  BK_TRY(check_ctx(ctx));
+  BK_REQUIRE(form >= 0 && form <= 4, "dev_syr2k: unknown form (0 lower, 1 mirror, 2 mirror with 64-wide tiles, 3 columns, 4 set)");
+  BK_REQUIRE((flags & ~1) == 0 && (flags == 0 || form == 2), "dev_syr2k: unknown flag (bit 0, skip_first_column, with form 2 only)");
+  BK_REQUIRE(m >= 0 && k >= 0, "dev_syr2k: negative dimension");
+  BK_REQUIRE((A && B && C) || m == 0 || k == 0, "dev_syr2k: null pointer");
+  BK_REQUIRE(lda >= m && ldb >= m && ldc >= m, "dev_syr2k: leading dimension too small");
+  BK_REQUIRE(begin >= INT32_MIN && begin <= INT32_MAX && end >= INT32_MIN && end <= INT32_MAX, "dev_syr2k: range too large");
+  switch (form) {
+    case 0: return syrk_lower(ctx, m, k, alpha, A, lda, B, ldb, C, ldc);
+    case 1: return syrk_mirror(ctx, m, k, alpha, A, lda, B, ldb, C, ldc, (int)begin, (int)end, false, false);
+    case 2: return syrk_mirror(ctx, m, k, alpha, A, lda, B, ldb, C, ldc, (int)begin, (int)end, true, (flags & 1) != 0);
+    case 3: return syrk_mirror_cols(ctx, m, k, alpha, A, lda, B, ldb, C, ldc, (int)begin, (int)end);
+    default: return syrk_mirror_set(ctx, m, k, alpha, A, lda, B, ldb, C, ldc);
+  }
+}
+
+int bigkrls_dev_gemm_skinny48(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda,
+                              const double* B, int64_t ldb, double* C, int64_t ldc) {
+  BK_TRY(check_ctx(ctx));
+  BK_REQUIRE(m >= 0 && n >= 0 && k >= 0, "dev_gemm_skinny48: negative dimension");
+  BK_REQUIRE(A && B && C, "dev_gemm_skinny48: null pointer");
+  BK_REQUIRE(lda >= m && ldb >= k && ldc >= m, "dev_gemm_skinny48: leading dimension too small");
+  return gemm_nn_skinny48(ctx, m, n, k, A, lda, B, ldb, C, ldc);
+}
+
+int bigkrls_dev_gemm_batched(bigkrls_ctx* ctx, int64_t n_batch, const int64_t* h_m, const int64_t* h_n, const int64_t* h_k,
+                             const int64_t* h_A, const int64_t* h_lda, const int64_t* h_B, const int64_t* h_ldb,
+                             const int64_t* h_C, const int64_t* h_ldc, const int64_t* h_kidx, int64_t max_m, int64_t max_n) {
+  BK_TRY(check_ctx(ctx));
+  BK_REQUIRE(n_batch >= 0 && n_batch <= INT32_MAX && max_m >= 0 && max_m <= INT32_MAX && max_n >= 0 && max_n <= INT32_MAX,
+             "dev_gemm_batched: bad batch size or maximum dimension");
+  if (n_batch == 0) return BIGKRLS_OK;
+  BK_REQUIRE(h_m && h_n && h_k && h_A && h_lda && h_B && h_ldb && h_C && h_ldc && h_kidx, "dev_gemm_batched: null array");
+  std::vector<GemmDesc> gd((size_t)n_batch);
+  for (int64_t i = 0; i < n_batch; ++i) {
+    BK_REQUIRE(h_m[i] >= 0 && h_n[i] >= 0 && h_k[i] >= 0 && h_m[i] <= max_m && h_n[i] <= max_n && h_k[i] <= INT32_MAX,
+               "dev_gemm_batched: a problem's dimension is negative or above the maximum");
+    BK_REQUIRE(h_A[i] && h_B[i] && h_C[i], "dev_gemm_batched: null pointer");
+    BK_REQUIRE(h_lda[i] >= h_m[i] && h_ldb[i] >= h_k[i] && h_ldc[i] >= h_m[i], "dev_gemm_batched: leading dimension too small");
+    GemmDesc& g = gd[(size_t)i];
+    g.A = (const double*)(uintptr_t)h_A[i]; g.B = (const double*)(uintptr_t)h_B[i]; g.C = (double*)(uintptr_t)h_C[i];
+    g.lda = h_lda[i]; g.ldb = h_ldb[i]; g.ldc = h_ldc[i];
+    g.m = (int32_t)h_m[i]; g.n = (int32_t)h_n[i]; g.k = (int32_t)h_k[i];
+    g.pad = 0;
+    g.kidx = (const int*)(uintptr_t)h_kidx[i];
+  }
+  const size_t bytes = gd.size() * sizeof(GemmDesc);
+  void* d_gd = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_EIG_DESC, (int64_t)bytes, &d_gd));
+  PinnedStage stage(ctx);
+  BK_TRY(stage.reserve(bytes + 64));
+  BK_TRY(stage.put(d_gd, gd.data(), bytes));
+  BK_TRY(gemm_batched_nn(ctx, (const GemmDesc*)d_gd, (int)n_batch, (int)max_m, (int)max_n));
+  BK_HIP(hipStreamSynchronize(ctx->stream));   // the pinned slice and the descriptor slot are free again after this
+  return BIGKRLS_OK;
+}
+
 int bigkrls_dev_copy_matrix(bigkrls_ctx* ctx, const double* src, int64_t m, int64_t n, int64_t lds,
                             double* dst, int64_t ldd) {
   BK_TRY(check_ctx(ctx));

@@ -21,6 +21,7 @@
 // "B", so that the lane index (l&15) runs along the column-major-contiguous M
 // dimension of C and every 16 lanes store one 128-byte segment.
 #include "common.h"
+#include "syrkmap.h"
 #include <algorithm>
 #include <cstring>
 #include <type_traits>
@@ -445,17 +446,7 @@ constexpr size_t smem_bytes_nt(int bn) {   // op(A) = A, op(B) = B': both tiles 
   return (size_t)(2 * lds_stage_of(true, BM) + 2 * lds_stage_of(true, bn)) * sizeof(double);
 }
 
-// XCD-aware tile order: consecutive block ids round-robin over the 8 XCDs, so give
-// each XCD a contiguous run of tiles (neighbouring tiles share operand panels in
-// that XCD's L2). Bijective for any grid size.
-__device__ __forceinline__ int xcd_remap(int bid, int nblocks) {
-  const int nx = 8;
-  const int q = nblocks / nx, rem = nblocks % nx;
-  const int x = bid % nx, i = bid / nx;
-  // blocks of xcd x: q + (x < rem) of them
-  const int start = x * q + (x < rem ? x : rem);
-  return start + i;
-}
+// (xcd_remap, the XCD-aware tile order of every kernel here: csrc/syrkmap.h)
 
 // ---------------------------------------------------------------------------
 // plain GEMM kernels
@@ -1114,7 +1105,7 @@ __global__ __launch_bounds__(NT, GEMM_OCC) void syrk_lower_kernel(GemmOperands g
   gemm_tile<false, true, 128>(g, m0, n0, 0, g.K, smem, acc);
   const int M = g.M;
   acc_foreach<128>(acc, m0, n0, [&](int m, int n, double v) {
-    if (m < M && n < M) {
+    if (m < M && n < M && m >= n) {   // (a diagonal tile holds elements above the diagonal: not part of the update)
       const int64_t o = (int64_t)m + (int64_t)n * ldc;
       C[o] += alpha * v;
     }
@@ -1149,14 +1140,6 @@ extern "C" __attribute__((visibility("default"))) int bk_syrk_trace_set(unsigned
 #define BK_TRACE_STAMP(slot)
 #endif
 
-struct SyrkMap {
-  int tiles;            // 128-row tiles of the matrix
-  int c0, c1;           // BN-wide tile columns of this launch
-  int R, nband, band0;  // rows per band, number of bands, first band (absolute index)
-  int t_off;            // R == 0 only
-  int band_start[160];  // band b (relative) starts at sequence index band_start[b]; [nband] = number of tiles
-};
-
 #ifndef SYRK64_OCC
 #define SYRK64_OCC 3
 #endif
@@ -1178,43 +1161,8 @@ __global__ __launch_bounds__(NT, (BN == 64 ? SYRK64_OCC : GEMM_OCC)) void syrk_m
   // (profiles/r03/r03m_*, r06/r06b_gate_ab_C3.log: 0.4221 vs 0.4087 s); -DSYRK64_LDS_EXACT=0 builds two per CU.
   extern __shared__ __attribute__((aligned(16))) double smem[];
   constexpr int NJ = BN / 32;
-  constexpr int CPT = 128 / BN;   // tile columns per 128-wide column pair
-  const int tiles = map.tiles;
-  int tc, tm, p;
-  if (map.R == 0) {
-    const int t = blockIdx.x + map.t_off;
-    // lower-triangular tiles, column by column; columns come in groups of CPT that share their
-    // first row tile p: group p has CPT * (tiles - p) tiles and starts at CPT * (p tiles - p(p-1)/2)
-    p = (int)((2.0 * tiles + 1.0 - sqrt((2.0 * tiles + 1.0) * (2.0 * tiles + 1.0) - 8.0 * t / CPT)) * 0.5);
-    auto gstart = [&](int q) { return CPT * (q * tiles - q * (q - 1) / 2); };
-    while (p > 0 && gstart(p) > t) --p;
-    while (gstart(p + 1) <= t) ++p;
-    const int rem = t - gstart(p);
-    tc = CPT * p + rem / (tiles - p);          // tile column (BN wide)
-    tm = p + rem % (tiles - p);                // tile row (128 high)
-  } else {
-    const int sq = xcd_remap(blockIdx.x, gridDim.x);
-    int lo = 0, hi = map.nband;                // band_start[lo] <= sq < band_start[hi]
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (map.band_start[mid] <= sq) lo = mid; else hi = mid;
-    }
-    int sp = sq - map.band_start[lo];
-    const int r0 = (map.band0 + lo) * map.R, r1 = min(r0 + map.R, tiles);
-    // columns whose diagonal tile lies at or above r0 hold all r1 - r0 rows of the band ...
-    const int cfull = max(min(map.c1, CPT * (r0 + 1)), map.c0);
-    const int nfull = (cfull - map.c0) * (r1 - r0);
-    if (sp < nfull) {
-      tc = map.c0 + sp / (r1 - r0);
-      tm = r0 + sp % (r1 - r0);
-    } else {   // ... the columns through the band's diagonal corner hold the rows from their diagonal tile down
-      sp -= nfull;
-      tc = cfull;
-      while (sp >= r1 - tc / CPT) { sp -= r1 - tc / CPT; ++tc; }
-      tm = tc / CPT + sp;
-    }
-    p = tc / CPT;
-  }
+  const SyrkTile tile = syrk_map_decode<BN>(map, blockIdx.x, gridDim.x);   // csrc/syrkmap.h
+  const int tc = tile.tc, tm = tile.tm, p = tile.p;
   const int m0 = tm * BM, n0 = tc * BN;
   d4 acc[4][NJ];
   BK_TRACE_STAMP(0)
@@ -1311,41 +1259,13 @@ __global__ __launch_bounds__(NT, (BN == 64 ? SYRK64_OCC : GEMM_OCC)) void syrk_m
   BK_TRACE_STAMP(2)
 }
 
-// Host side of SyrkMap: the BN-wide columns [c0, c1) of the lower tile triangle (tile rows from the diagonal down).
-// rows_per_band == 0: the column-by-column order (development switch BIGKRLS_SYRK_ORDER=cols).
+// The map of a launch (csrc/syrkmap.h) with the two development switches: BIGKRLS_SYRK_ORDER=cols is the column-by-column
+// order, BIGKRLS_SYRK_R the rows per band.
 template <int SBN>
 static int64_t syrk_map_build(SyrkMap& mp, int tiles, int c0, int c1, int k) {
-  constexpr int CPT = 128 / SBN;
-  mp.tiles = tiles; mp.c0 = c0; mp.c1 = c1; mp.t_off = 0; mp.nband = 0; mp.band0 = 0;
   static const int order_cols = [] { const char* e = getenv("BIGKRLS_SYRK_ORDER"); return e && std::string(e) == "cols"; }();
   static const int r_env = [] { const char* e = getenv("BIGKRLS_SYRK_R"); return e ? atoi(e) : 0; }();
-  auto col_first = [&](int64_t c) -> int64_t {   // column-major index of the first tile of BN-wide column c
-    const int64_t q = c / CPT;
-    if (q >= tiles) return CPT * ((int64_t)tiles * tiles - (int64_t)tiles * (tiles - 1) / 2);
-    return CPT * (q * tiles - q * (q - 1) / 2) + (c % CPT) * (tiles - q);
-  };
-  const int64_t nt = col_first(c1) - col_first(c0);
-  if (order_cols || nt <= 0) {
-    mp.R = 0;
-    mp.t_off = (int)col_first(c0);
-    return nt;
-  }
-  // rows per band: the band's A panels (R x 128 x k doubles) take about 2 MB of the XCD's 4 MB L2
-  int R = r_env > 0 ? r_env : (int)std::min<int64_t>(32, std::max<int64_t>(2, (2 << 20) / ((int64_t)128 * 8 * std::max(k, 1))));
-  const int first_row = c0 / CPT;
-  while ((tiles - first_row + R - 1) / R > 159) ++R;
-  mp.R = R;
-  mp.band0 = first_row / R;
-  int64_t acc = 0;
-  int nb = 0;
-  for (int b = mp.band0; b * R < tiles; ++b, ++nb) {
-    mp.band_start[nb] = (int)acc;
-    const int r0 = b * R, r1 = std::min(r0 + R, tiles);
-    for (int tm = r0; tm < r1; ++tm) acc += std::max(0, std::min(c1, CPT * (tm + 1)) - c0);
-  }
-  mp.band_start[nb] = (int)acc;
-  mp.nband = nb;
-  return acc;   // == nt
+  return syrk_map_build<SBN>(mp, tiles, c0, c1, k, order_cols != 0, r_env);
 }
 
 template <int SBN, bool ACCUM>
@@ -1432,7 +1352,10 @@ __global__ __launch_bounds__(NT, GEMM_OCC) void gemm_batched_nn_kernel(const Gem
   if (m0 >= d.m || n0 >= d.n) return;
   GemmOperands g{d.A, d.B, d.lda, d.ldb, d.m, d.n, d.k, d.kidx};
   d4 acc[4][4];
-  gemm_tile<false, false, 128, true>(g, m0, n0, 0, d.k, smem, acc);
+  // (uniform over the workgroup. A descriptor without kidx is a plain product: the gathering loader would read through
+  //  the null pointer)
+  if (d.kidx != nullptr) gemm_tile<false, false, 128, true>(g, m0, n0, 0, d.k, smem, acc);
+  else gemm_tile<false, false, 128>(g, m0, n0, 0, d.k, smem, acc);
   double* C = d.C;
   const int64_t ldc = d.ldc;
   const int M = d.m, N = d.n;

@@ -398,6 +398,31 @@ int bigkrls_dev_cholqr2(bigkrls_ctx* ctx, double* W, double* tmp, int64_t n, int
  * the one-kernel form and for a panel left to the Householder kernel, which *h_fallback = 1 reports). */
 int bigkrls_dev_panel_factor(bigkrls_ctx* ctx, double* P, int64_t ld, int64_t m, double* Vw, double* V, double* T,
                              double* Tfold, double* tau, int32_t* h_fallback);
+/* The symmetric rank-2k family of the MFMA GEMM core (exposed for tests): one unchanged call of the internal function
+ * that `form` names. A and B are m x k (device, column-major, lda, ldb >= m), C is m x m (ldc >= m); with P = A B' the
+ * update is C[i,j] += alpha P[i,j] for i >= j over a range of columns j, and the mirror forms store the new C[i,j] at
+ * C[j,i] as well (i > j). Nothing else of C is written.
+ *   form 0  syrk_lower: all columns, lower triangle only (the strict upper triangle is neither read nor written)
+ *   form 1  syrk_mirror, 128-wide tiles: the 128-wide tile columns [begin, end) (end < 0 or too large: to the last)
+ *   form 2  syrk_mirror, 64-wide tiles: the same columns; flags bit 0 (skip_first_column) leaves out the first 64
+ *   form 3  syrk_mirror_cols: the 64-wide columns [begin, end) (begin < 0: 0; end < 0 or too large: to the last)
+ *   form 4  syrk_mirror_set: C = alpha P on the lower triangle, mirrored; C is not read; needs k > 0
+ * begin and end are ignored by forms 0 and 4; any other form or flag is BIGKRLS_EINVAL. */
+int bigkrls_dev_syr2k(bigkrls_ctx* ctx, int form, int64_t m, int64_t k, double alpha, const double* A, int64_t lda,
+                      const double* B, int64_t ldb, double* C, int64_t ldc, int64_t begin, int64_t end, int flags);
+/* C (m x n, ldc; n <= 48) = A (m x k, lda) B (k x n, ldb), device pointers: gemm_nn_skinny48, the 128 x 48 tile of the
+ * marginal-effects pass with its deterministic split-K (exposed for tests). m, n, k > 0. */
+int bigkrls_dev_gemm_skinny48(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda,
+                              const double* B, int64_t ldb, double* C, int64_t ldc);
+/* n_batch independent products C_i (m_i x n_i, ldc_i) = A_i[:, kidx_i] B_i in one batched launch: gemm_batched_nn, the
+ * merge products of the divide & conquer eigensolver (exposed for tests). Every argument is a host array of n_batch
+ * entries; h_A, h_B, h_C and h_kidx hold device addresses as integers. A_i is m_i x k_i (lda_i) when h_kidx[i] == 0,
+ * else column l of the operand is column kidx_i[l] of A_i (kidx_i: k_i 32-bit integers on the device); B_i is k_i x n_i.
+ * max_m >= every m_i and max_n >= every n_i size the grid. The descriptors are uploaded as the eigensolver uploads
+ * them; the call returns after the stream has been synchronised. */
+int bigkrls_dev_gemm_batched(bigkrls_ctx* ctx, int64_t n_batch, const int64_t* h_m, const int64_t* h_n, const int64_t* h_k,
+                             const int64_t* h_A, const int64_t* h_lda, const int64_t* h_B, const int64_t* h_ldb,
+                             const int64_t* h_C, const int64_t* h_ldc, const int64_t* h_kidx, int64_t max_m, int64_t max_n);
 /* d_T (device, m x m column-major, m = steps b) = the block-tridiagonal projected matrix of a block Lanczos run:
  * diagonal blocks 0.5 (A_j + A_j') from d_A_blocks (steps blocks of b x b), sub-diagonal blocks beta_{j+1} (upper
  * triangular) from d_beta_blocks (steps - 1 blocks are read), super-diagonal blocks their transposes. */
