@@ -21,6 +21,7 @@
 // "B", so that the lane index (l&15) runs along the column-major-contiguous M
 // dimension of C and every 16 lanes store one 128-byte segment.
 #include "common.h"
+#include "splitplan.h"
 #include "syrkmap.h"
 #include <algorithm>
 #include <cstring>
@@ -441,6 +442,44 @@ __device__ __forceinline__ void acc_foreach(const d4 (&acc)[4][BN / 32], int m0,
       }
 }
 
+// The shared frame of the plain GEMM family. (Scalars arrive by reference: a helper that receives them by value is
+// unrolled before it is inlined, which moves the register allocation of the kernels around it.)
+// The k slab of a workgroup of a (tiles, splits) grid: slab z = blockIdx.y covers k in [kbeg, kend).
+struct KSlab { int z, kbeg, kend; };
+__device__ __forceinline__ KSlab k_slab(const int& K, const int& k_chunk) {
+  const int z = blockIdx.y;
+  const int kbeg = z * k_chunk;
+  return KSlab{z, kbeg, min(K, kbeg + k_chunk)};
+}
+// ... and its tile of the tiles_m x tiles_n grid of 128 x BN tiles, column by column in the XCD-aware order.
+struct TileAt { int tn, m0, n0, z, kbeg, kend; };
+template <int BN>
+__device__ __forceinline__ TileAt tile_at(const GemmOperands& g, const int& tiles_m, const int& tiles_n, const int& k_chunk) {
+  const int ntile = tiles_m * tiles_n;
+  const int tid = xcd_remap(blockIdx.x, ntile);
+  const int tm = tid % tiles_m, tn = tid / tiles_m;
+  const int m0 = tm * BM, n0 = tn * BN;
+  const KSlab s = k_slab(g.K, k_chunk);
+  return TileAt{tn, m0, n0, s.z, s.kbeg, s.kend};
+}
+
+// (The stores "m < M && n < N: C or the slab" stay spelled out in each kernel: through a shared helper the compiler
+//  schedules them differently, and gemm_modulated2_kernel<128> measured 0.7 % slower)
+
+// Sum of count slabs' entries p[0], p[stride], ... in the fixed order z = 0, 1, ... (deterministic); the loads of four
+// slabs are issued together -- with one load in flight per thread a reduction is latency-bound.
+__device__ __forceinline__ double slab_sum(const double* __restrict__ p, const int64_t& stride, const int& count) {
+  double s = 0.0;
+  int z = 0;
+  for (; z + 4 <= count; z += 4) {
+    const double a0 = p[(int64_t)(z + 0) * stride], a1 = p[(int64_t)(z + 1) * stride];
+    const double a2 = p[(int64_t)(z + 2) * stride], a3 = p[(int64_t)(z + 3) * stride];
+    s += a0; s += a1; s += a2; s += a3;
+  }
+  for (; z < count; ++z) s += p[(int64_t)z * stride];
+  return s;
+}
+
 constexpr size_t smem_bytes(int bn) { return (size_t)(2 * lds_stage(BM) + 2 * lds_stage(bn)) * sizeof(double); }
 constexpr size_t smem_bytes_nt(int bn) {   // op(A) = A, op(B) = B': both tiles x-contiguous
   return (size_t)(2 * lds_stage_of(true, BM) + 2 * lds_stage_of(true, bn)) * sizeof(double);
@@ -471,23 +510,17 @@ __global__ __launch_bounds__(NT, (gemm_occ<TA, TB, BN>())) void gemm_kernel(Gemm
                                                   double* __restrict__ partial) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   if (g.run_if != nullptr && *g.run_if == 0) return;      // (uniform: a scalar load)
-  const int ntile = tiles_m * tiles_n;
-  const int tid = xcd_remap(blockIdx.x, ntile);
-  const int tm = tid % tiles_m, tn = tid / tiles_m;
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int z = blockIdx.y;
-  const int kbeg = z * k_chunk;
-  const int kend = min(g.K, kbeg + k_chunk);
+  const TileAt at = tile_at<BN>(g, tiles_m, tiles_n, k_chunk);
+  const int m0 = at.m0, n0 = at.n0;
   d4 acc[4][BN / 32];
-  gemm_tile<TA, TB, BN, false, (BN <= GEMM_DEEP_BN && gemm_occ<TA, TB, BN>() <= GEMM_OCC)>(g, m0, n0, kbeg, kend, smem, acc);
+  gemm_tile<TA, TB, BN, false, (BN <= GEMM_DEEP_BN && gemm_occ<TA, TB, BN>() <= GEMM_OCC)>(g, m0, n0, at.kbeg, at.kend, smem, acc);
+  const int M = g.M, N = g.N;
   if (partial != nullptr) {
-    double* P = partial + (int64_t)z * g.M * g.N;
-    const int M = g.M, N = g.N;
+    double* P = partial + (int64_t)at.z * M * N;
     acc_foreach<BN>(acc, m0, n0, [&](int m, int n, double v) {
       if (m < M && n < N) P[(int64_t)m + (int64_t)n * M] = v;
     });
   } else {
-    const int M = g.M, N = g.N;
     if (beta == 0.0) {
       acc_foreach<BN>(acc, m0, n0, [&](int m, int n, double v) {
         if (m < M && n < N) C[(int64_t)m + (int64_t)n * ldc] = alpha * v;
@@ -532,65 +565,23 @@ __global__ void splitk_reduce_kernel(const double* __restrict__ partial, int spl
                                      double alpha, double beta, double* __restrict__ C,
                                      int64_t ldc, const int* __restrict__ run_if) {
   if (run_if != nullptr && *run_if == 0) return;
-  // slabs are summed in the fixed order z = 0, 1, ... (deterministic); the loads of four slabs are
-  // issued together -- with one load in flight per thread the kernel is latency-bound
   const int64_t total = (int64_t)M * N;
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
        e += (int64_t)gridDim.x * blockDim.x) {
-    const double* p = partial + e;
-    double s = 0.0;
-    int z = 0;
-    for (; z + 4 <= splits; z += 4) {
-      const double a0 = p[(int64_t)(z + 0) * total], a1 = p[(int64_t)(z + 1) * total];
-      const double a2 = p[(int64_t)(z + 2) * total], a3 = p[(int64_t)(z + 3) * total];
-      s += a0; s += a1; s += a2; s += a3;
-    }
-    for (; z < splits; ++z) s += p[(int64_t)z * total];
+    const double s = slab_sum(partial + e, total, splits);
     const int m = (int)(e % M), n = (int)(e / M);
     const int64_t o = (int64_t)m + (int64_t)n * ldc;
     C[o] = (beta == 0.0) ? alpha * s : alpha * s + beta * C[o];
   }
 }
 
-// The deterministic split-K choice of the plain GEMM kernels of one tile width (launch_gemm, launch_gemm_modulated):
-// the number of k slabs and the slab length, a multiple of BK.
-template <bool TA, bool TB, int BN>
-static void gemm_split_plan(const GemmOperands& g, int ntile, int* splits_out, int* k_chunk_out) {
-  // split-K when the tile grid does not fill whole rounds of the GPU and K is long
-  // The split count is chosen against the 512 workgroups the GPU holds at once (two per CU):
-  // ntile * splits workgroups take ceil(ntile * splits / 512) rounds of K / splits k-steps each, plus
-  // a per-split cost (prologue, partial store, reduction). A count that spills a few workgroups into
-  // one more round pays that whole round: m = 20 000, n = 64 (157 tiles): 7 splits 1.02 ms, 6 or 3
-  // splits 0.95 ms; m = 10 000 (79 tiles): 13 splits 0.30 ms, 6 splits 0.26 ms.
-  int splits = 1;
-  // (also above one round: 782 tiles -- N = 100 000 times a 128-column block -- fill 1.53 rounds unsplit,
-  //  i.e. run at 76 %; five splits fill 7.6 of 8)
-  if (ntile < 4096 && g.K >= 1024) {
-    const int maxs = std::min(64, std::max(1, g.K / 256));
-    // rough time model in us: a k-step of a workgroup ~0.06 us per unit of K; per split the partial
-    // slab is written and read again (16 bytes per output element at ~5 TB/s) plus a fixed ~0.2 us
-    // (measured for the block-Lanczos product, 391 tiles x K = 50 000: 5 splits 10.18 ms, 9 or 13 splits 9.98 ms,
-    //  tools/kb_shape_probe.hip -- for these long products the slab traffic costs half of what the model charged)
-    const double per_split = ((ntile >= 256 && g.K >= 16384) ? 1.6e-6 : 3.2e-6) * (double)g.M * (double)g.N + 0.2;
-    double best = 1e30;
-    constexpr int resident = 256 * gemm_occ<TA, TB, BN>();
-    for (int sp = 1; sp <= maxs; ++sp) {
-      const int rounds = (ntile * sp + resident - 1) / resident;
-      const double cost = 0.06 * rounds * ((double)g.K / sp) + per_split * sp;
-      if (cost < best - 1e-9) { best = cost; splits = sp; }
-    }
-  }
-  {
-    // (development: BIGKRLS_GEMM_SPLITS=<n> overrides the count for products with K >= 16384, tools/kb_shape_probe.hip)
-    static const int env_splits = [] { const char* e = getenv("BIGKRLS_GEMM_SPLITS"); return e ? atoi(e) : 0; }();
-    if (env_splits > 0 && g.K >= 16384) splits = env_splits;
-  }
-  int k_chunk = ((g.K + splits - 1) / splits + BK - 1) / BK * BK;
-  if (k_chunk < BK) k_chunk = BK;
-  splits = (g.K + k_chunk - 1) / k_chunk;
-  if (splits < 1) splits = 1;
-  *splits_out = splits;
-  *k_chunk_out = k_chunk;
+// ---- host frame of the family ---------------------------------------------------------------------------------------
+// The deterministic split-K choice (csrc/splitplan.h) of a launch of ntile tiles under one of the three models.
+// (development: BIGKRLS_GEMM_SPLITS=<n> overrides the count for products with K >= 16384 under the plain model,
+//  tools/kb_shape_probe.hip)
+static SplitPlan gemm_split_plan(const SplitModel& md, const GemmOperands& g, int ntile) {
+  static const int env_splits = [] { const char* e = getenv("BIGKRLS_GEMM_SPLITS"); return e ? atoi(e) : 0; }();
+  return split_plan(md, ntile, g.M, g.N, g.K, BK, env_splits);
 }
 
 // GEMMs issued on the look-ahead stream run concurrently with main-stream GEMMs: own partial buffer
@@ -598,53 +589,19 @@ static int gemm_split_slot(const bigkrls_ctx* ctx) {
   return (ctx->side_stream && (ctx->stream == ctx->side_stream || ctx->stream == ctx->bg_stream)) ? SLOT_SIDE_SPLITK : SLOT_GEMM_SPLITK;
 }
 
-// the slabs of the split-K partials (splits x M x N doubles); nullptr for a single split
-static int gemm_split_partials(bigkrls_ctx* ctx, const GemmOperands& g, int splits, double** partial) {
-  *partial = nullptr;
-  if (splits > 1) {
-    void* p = nullptr;
-    const int slot = gemm_split_slot(ctx);
-    BK_TRY(ws_get(ctx, slot, (int64_t)splits * g.M * g.N * sizeof(double), &p));
-    *partial = (double*)p;
-  }
-  return BIGKRLS_OK;
+// tile width of an n-column result: f(std::integral_constant<int, BN>), BN = 32, 64 or 128
+template <class F>
+static auto with_bn(int64_t n, F&& f) {
+  if (n <= 32) return f(std::integral_constant<int, 32>());
+  if (n <= 64) return f(std::integral_constant<int, 64>());
+  return f(std::integral_constant<int, 128>());
 }
 
-template <bool TA, bool TB, int BN>
-static int launch_gemm(bigkrls_ctx* ctx, const GemmOperands& g, double alpha, double beta,
-                       double* C, int64_t ldc) {
-  const int tiles_m = (g.M + BM - 1) / BM;
-  const int tiles_n = (g.N + BN - 1) / BN;
-  const int ntile = tiles_m * tiles_n;
-  int splits = 1, k_chunk = BK;
-  gemm_split_plan<TA, TB, BN>(g, ntile, &splits, &k_chunk);
-  double* partial = nullptr;
-  BK_TRY(gemm_split_partials(ctx, g, splits, &partial));
-  auto kern = gemm_kernel<TA, TB, BN>;
-  constexpr size_t smem = gemm_smem_bytes<TA, TB, BN>();
-  BK_TRY(ensure_dyn_smem(ctx, (const void*)kern, smem));
-  dim3 grid(ntile, splits);
-  hipLaunchKernelGGL(kern, grid, dim3(NT), smem, ctx->stream, g, alpha, beta, C, ldc,
-                     tiles_m, tiles_n, k_chunk, partial);
-  BK_CHECK_LAUNCH();
-  if (splits > 1) {
-    const int64_t total = (int64_t)g.M * g.N;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, partial,
-                       splits, g.M, g.N, alpha, beta, C, ldc, g.run_if);
-    BK_CHECK_LAUNCH();
-  }
+// the first two checks of every entry (c: a third dimension, or 0)
+static int require_dims(const char* who, int64_t a, int64_t b, int64_t c = 0) {
+  BK_REQUIRE(a >= 0 && b >= 0 && c >= 0, std::string(who) + ": negative dimension");
+  BK_REQUIRE(a < (1ll << 31) && b < (1ll << 31) && c < (1ll << 31), std::string(who) + ": dimension too large");
   return BIGKRLS_OK;
-}
-
-template <int BN>
-static int dispatch_trans(bigkrls_ctx* ctx, int ta, int tb, const GemmOperands& g, double alpha,
-                          double beta, double* C, int64_t ldc) {
-  if (!ta && !tb) return launch_gemm<false, false, BN>(ctx, g, alpha, beta, C, ldc);
-  if (!ta && tb) return launch_gemm<false, true, BN>(ctx, g, alpha, beta, C, ldc);
-  if (ta && !tb) return launch_gemm<true, false, BN>(ctx, g, alpha, beta, C, ldc);
-  return launch_gemm<true, true, BN>(ctx, g, alpha, beta, C, ldc);
 }
 
 __global__ void scale_matrix_kernel(double* C, int64_t ldc, int M, int N, double beta) {
@@ -655,26 +612,71 @@ __global__ void scale_matrix_kernel(double* C, int64_t ldc, int M, int N, double
     C[o] = (beta == 0.0) ? 0.0 : beta * C[o];
   }
 }
+// C (m x n) = beta C, C not read for beta == 0
+static int scale_matrix(bigkrls_ctx* ctx, double* C, int64_t ldc, int64_t m, int64_t n, double beta) {
+  const int blocks = (int)std::min<int64_t>((m * n + 255) / 256, 2048);
+  hipLaunchKernelGGL(scale_matrix_kernel, dim3(blocks), dim3(256), 0, ctx->stream, C, ldc, (int)m, (int)n, beta);
+  BK_CHECK_LAUNCH();
+  return BIGKRLS_OK;
+}
+// an empty sum
+static int zero_fill(bigkrls_ctx* ctx, double* C, int64_t ldc, int64_t m, int64_t n) { return scale_matrix(ctx, C, ldc, m, n, 0.0); }
+
+// partial (splits slabs of m x n) -> C = alpha (sum of the slabs) + beta C
+static int launch_splitk_reduce(bigkrls_ctx* ctx, const double* partial, int splits, int m, int n, double alpha, double beta,
+                                double* C, int64_t ldc, const int* run_if) {
+  const int blocks = (int)std::min<int64_t>(((int64_t)m * n + 255) / 256, 2048);
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, partial, splits, m, n, alpha, beta, C,
+                     ldc, run_if);
+  BK_CHECK_LAUNCH();
+  return BIGKRLS_OK;
+}
+
+// One launch of a plain kernel of tile width BN -- gemm_kernel<TA, TB, BN> (pre: alpha, beta) or a modulated kernel
+// (TA = TB = false; pre: GemmMod, or GemmMod and GemmMod2) -- over the split plan's (tiles, splits) grid, and for more than
+// one split the slabs' reduction C = alpha (sum) + beta C.
+template <bool TA, bool TB, int BN, class Kern, class... Pre>
+static int launch_gemm_splitk(bigkrls_ctx* ctx, const GemmOperands& g, Kern kern, double alpha, double beta, double* C,
+                              int64_t ldc, const Pre&... pre) {
+  const int tiles_m = (g.M + BM - 1) / BM;
+  const int tiles_n = (g.N + BN - 1) / BN;
+  const int ntile = tiles_m * tiles_n;
+  const SplitPlan plan = gemm_split_plan(split_model_gemm(gemm_occ<TA, TB, BN>()), g, ntile);
+  double* partial = nullptr;   // the slabs of the split-K partials (splits x M x N doubles); nullptr for a single split
+  if (plan.splits > 1) {
+    void* p = nullptr;
+    BK_TRY(ws_get(ctx, gemm_split_slot(ctx), (int64_t)plan.splits * g.M * g.N * sizeof(double), &p));
+    partial = (double*)p;
+  }
+  constexpr size_t smem = gemm_smem_bytes<TA, TB, BN>();
+  BK_TRY(ensure_dyn_smem(ctx, (const void*)kern, smem));
+  hipLaunchKernelGGL(kern, dim3(ntile, plan.splits), dim3(NT), smem, ctx->stream, g, pre..., C, ldc, tiles_m, tiles_n,
+                     plan.k_chunk, partial);
+  BK_CHECK_LAUNCH();
+  if (plan.splits > 1) BK_TRY(launch_splitk_reduce(ctx, partial, plan.splits, g.M, g.N, alpha, beta, C, ldc, g.run_if));
+  return BIGKRLS_OK;
+}
+
+template <bool TA, bool TB, int BN>
+static int launch_gemm(bigkrls_ctx* ctx, const GemmOperands& g, double alpha, double beta, double* C, int64_t ldc) {
+  return launch_gemm_splitk<TA, TB, BN>(ctx, g, gemm_kernel<TA, TB, BN>, alpha, beta, C, ldc, alpha, beta);
+}
 
 int gemm(bigkrls_ctx* ctx, int ta, int tb, int64_t m, int64_t n, int64_t k, double alpha,
          const double* A, int64_t lda, const double* B, int64_t ldb, double beta, double* C,
          int64_t ldc) {
-  BK_REQUIRE(m >= 0 && n >= 0 && k >= 0, "gemm: negative dimension");
-  BK_REQUIRE(m < (1ll << 31) && n < (1ll << 31) && k < (1ll << 31), "gemm: dimension too large");
+  BK_TRY(require_dims("gemm", m, n, k));
   if (m == 0 || n == 0) return BIGKRLS_OK;
-  if (k == 0 || alpha == 0.0) {
-    if (beta == 1.0) return BIGKRLS_OK;
-    int blocks = (int)std::min<int64_t>((m * n + 255) / 256, 2048);
-    hipLaunchKernelGGL(scale_matrix_kernel, dim3(blocks), dim3(256), 0, ctx->stream, C, ldc,
-                       (int)m, (int)n, beta);
-    BK_CHECK_LAUNCH();
-    return BIGKRLS_OK;
-  }
+  if (k == 0 || alpha == 0.0) return beta == 1.0 ? BIGKRLS_OK : scale_matrix(ctx, C, ldc, m, n, beta);
   BK_REQUIRE(A && B && C, "gemm: null pointer");
   GemmOperands g{A, B, lda, ldb, (int)m, (int)n, (int)k, nullptr, ctx->gemm_run_if};
-  if (n <= 32) return dispatch_trans<32>(ctx, ta, tb, g, alpha, beta, C, ldc);
-  if (n <= 64) return dispatch_trans<64>(ctx, ta, tb, g, alpha, beta, C, ldc);
-  return dispatch_trans<128>(ctx, ta, tb, g, alpha, beta, C, ldc);
+  return with_bn(n, [&](auto bn) {
+    constexpr int BN = decltype(bn)::value;
+    if (!ta && !tb) return launch_gemm<false, false, BN>(ctx, g, alpha, beta, C, ldc);
+    if (!ta && tb) return launch_gemm<false, true, BN>(ctx, g, alpha, beta, C, ldc);
+    if (ta && !tb) return launch_gemm<true, false, BN>(ctx, g, alpha, beta, C, ldc);
+    return launch_gemm<true, true, BN>(ctx, g, alpha, beta, C, ldc);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -685,82 +687,64 @@ int gemm(bigkrls_ctx* ctx, int ta, int tb, int64_t m, int64_t n, int64_t k, doub
 // so the splits' partials add in slab order as before (splitk_reduce_kernel: no atomics, bitwise reproducible).
 // With r = 1, t = 0 the factor is exactly 1 and the result is bitwise gemm()'s.
 // ---------------------------------------------------------------------------
-template <int BN>
-__global__ __launch_bounds__(NT, (gemm_occ<false, false, BN>())) void gemm_modulated_kernel(
-    GemmOperands g, GemmMod mod, double* __restrict__ C, int64_t ldc, int tiles_m, int tiles_n, int k_chunk,
-    double* __restrict__ partial) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int ntile = tiles_m * tiles_n;
-  const int tid = xcd_remap(blockIdx.x, ntile);
-  const int tm = tid % tiles_m, tn = tid / tiles_m;
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int z = blockIdx.y;
-  const int kbeg = z * k_chunk;
-  const int kend = min(g.K, kbeg + k_chunk);
+// (the one body of gemm_modulated_kernel and gemm_modulated2_kernel; MOD2 off: mod2 is never read)
+template <int BN, bool MOD2>
+__device__ __forceinline__ void gemm_modulated_body(const GemmOperands& g, const GemmMod& mod, const GemmMod2* mod2,
+                                                    double* __restrict__ C, const int64_t& ldc, const int& tiles_m,
+                                                    const int& tiles_n, const int& k_chunk, double* __restrict__ partial,
+                                                    double* __restrict__ smem) {
+  const TileAt at = tile_at<BN>(g, tiles_m, tiles_n, k_chunk);
   d4 acc[4][BN / 32];
-  gemm_tile<false, false, BN, false, (BN <= GEMM_DEEP_BN && gemm_occ<false, false, BN>() <= GEMM_OCC), true>(
-      g, m0, n0, kbeg, kend, smem, acc, &mod);
+  gemm_tile<false, false, BN, false, (BN <= GEMM_DEEP_BN && gemm_occ<false, false, BN>() <= GEMM_OCC), true, false, MOD2>(
+      g, at.m0, at.n0, at.kbeg, at.kend, smem, acc, &mod, nullptr, mod2);
   const int M = g.M, N = g.N;
   if (partial != nullptr) {
-    double* P = partial + (int64_t)z * M * N;
-    acc_foreach<BN>(acc, m0, n0, [&](int m, int n, double v) {
+    double* P = partial + (int64_t)at.z * M * N;
+    acc_foreach<BN>(acc, at.m0, at.n0, [&](int m, int n, double v) {
       if (m < M && n < N) P[(int64_t)m + (int64_t)n * M] = v;
     });
   } else {
-    acc_foreach<BN>(acc, m0, n0, [&](int m, int n, double v) {
+    acc_foreach<BN>(acc, at.m0, at.n0, [&](int m, int n, double v) {
       if (m < M && n < N) C[(int64_t)m + (int64_t)n * ldc] = v;
     });
   }
 }
 
-// launches gemm_modulated_kernel<BN> (mods: GemmMod) or gemm_modulated2_kernel<BN> (mods: GemmMod, GemmMod2)
-template <int BN, class Kern, class... Mods>
-static int launch_gemm_modulated(bigkrls_ctx* ctx, const GemmOperands& g, Kern kern, double* C, int64_t ldc,
-                                 const Mods&... mods) {
-  const int tiles_m = (g.M + BM - 1) / BM;
-  const int tiles_n = (g.N + BN - 1) / BN;
-  const int ntile = tiles_m * tiles_n;
-  int splits = 1, k_chunk = BK;
-  gemm_split_plan<false, false, BN>(g, ntile, &splits, &k_chunk);
-  double* partial = nullptr;
-  BK_TRY(gemm_split_partials(ctx, g, splits, &partial));
-  constexpr size_t smem = gemm_smem_bytes<false, false, BN>();
-  BK_TRY(ensure_dyn_smem(ctx, (const void*)kern, smem));
-  hipLaunchKernelGGL(kern, dim3(ntile, splits), dim3(NT), smem, ctx->stream, g, mods..., C, ldc, tiles_m, tiles_n,
-                     k_chunk, partial);
-  BK_CHECK_LAUNCH();
-  if (splits > 1) {
-    const int64_t total = (int64_t)g.M * g.N;
-    const int blocks = (int)std::min<int64_t>((total + 255) / 256, 2048);
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, partial, splits, g.M, g.N, 1.0,
-                       0.0, C, ldc, (const int*)nullptr);
-    BK_CHECK_LAUNCH();
-  }
+template <int BN>
+__global__ __launch_bounds__(NT, (gemm_occ<false, false, BN>())) void gemm_modulated_kernel(
+    GemmOperands g, GemmMod mod, double* __restrict__ C, int64_t ldc, int tiles_m, int tiles_n, int k_chunk,
+    double* __restrict__ partial) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  gemm_modulated_body<BN, false>(g, mod, nullptr, C, ldc, tiles_m, tiles_n, k_chunk, partial, smem);
+}
+
+// the shared host frame of gemm_modulated and gemm_modulated2 (kern(bn): the kernel of tile width bn; mods: its GemmMod,
+// or its GemmMod and GemmMod2)
+template <class KernOf, class... Mods>
+static int gemm_modulated_entry(bigkrls_ctx* ctx, const char* who, int64_t m, int64_t n, int64_t k, const double* A,
+                                int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc, bool vectors_ok,
+                                KernOf kern_of, const Mods&... mods) {
+  const std::string name(who);
+  BK_TRY(require_dims(who, m, n, k));
+  if (m == 0 || n == 0) return BIGKRLS_OK;
+  BK_REQUIRE(C && ldc >= m, name + ": null C or ldc < m");
+  if (k == 0) return zero_fill(ctx, C, ldc, m, n);   // empty sum
+  BK_REQUIRE(A && B && vectors_ok, name + ": null pointer");
+  BK_REQUIRE(lda >= m && ldb >= k, name + ": leading dimension of A or B too small");
+  const GemmOperands g{A, B, lda, ldb, (int)m, (int)n, (int)k, nullptr};
+  BK_TRY(prof_begin(ctx, who, 2.0 * (double)m * (double)n * (double)k));
+  BK_TRY(with_bn(n, [&](auto bn) {
+    constexpr int BN = decltype(bn)::value;
+    return launch_gemm_splitk<false, false, BN>(ctx, g, kern_of(bn), 1.0, 0.0, C, ldc, mods...);
+  }));
+  BK_TRY(prof_end(ctx, who));
   return BIGKRLS_OK;
 }
 
 int gemm_modulated(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* r,
                    const double* t, const double* s, const double* B, int64_t ldb, double* C, int64_t ldc) {
-  BK_REQUIRE(m >= 0 && n >= 0 && k >= 0, "gemm_modulated: negative dimension");
-  BK_REQUIRE(m < (1ll << 31) && n < (1ll << 31) && k < (1ll << 31), "gemm_modulated: dimension too large");
-  if (m == 0 || n == 0) return BIGKRLS_OK;
-  BK_REQUIRE(C && ldc >= m, "gemm_modulated: null C or ldc < m");
-  if (k == 0) {   // empty sum
-    const int blocks = (int)std::min<int64_t>((m * n + 255) / 256, 2048);
-    hipLaunchKernelGGL(scale_matrix_kernel, dim3(blocks), dim3(256), 0, ctx->stream, C, ldc, (int)m, (int)n, 0.0);
-    BK_CHECK_LAUNCH();
-    return BIGKRLS_OK;
-  }
-  BK_REQUIRE(A && B && r && t && s, "gemm_modulated: null pointer");
-  BK_REQUIRE(lda >= m && ldb >= k, "gemm_modulated: leading dimension of A or B too small");
-  const GemmOperands g{A, B, lda, ldb, (int)m, (int)n, (int)k, nullptr};
-  const GemmMod mod{r, t, s};
-  BK_TRY(prof_begin(ctx, "gemm_modulated", 2.0 * (double)m * (double)n * (double)k));
-  if (n <= 32) BK_TRY(launch_gemm_modulated<32>(ctx, g, gemm_modulated_kernel<32>, C, ldc, mod));
-  else if (n <= 64) BK_TRY(launch_gemm_modulated<64>(ctx, g, gemm_modulated_kernel<64>, C, ldc, mod));
-  else BK_TRY(launch_gemm_modulated<128>(ctx, g, gemm_modulated_kernel<128>, C, ldc, mod));
-  BK_TRY(prof_end(ctx, "gemm_modulated"));
-  return BIGKRLS_OK;
+  return gemm_modulated_entry(ctx, "gemm_modulated", m, n, k, A, lda, B, ldb, C, ldc, r && t && s,
+                              [](auto bn) { return gemm_modulated_kernel<decltype(bn)::value>; }, GemmMod{r, t, s});
 }
 
 // ---------------------------------------------------------------------------
@@ -776,53 +760,15 @@ __global__ __launch_bounds__(NT, (gemm_occ<false, false, BN>())) void gemm_modul
     GemmOperands g, GemmMod mod, GemmMod2 mod2, double* __restrict__ C, int64_t ldc, int tiles_m, int tiles_n,
     int k_chunk, double* __restrict__ partial) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int ntile = tiles_m * tiles_n;
-  const int tid = xcd_remap(blockIdx.x, ntile);
-  const int tm = tid % tiles_m, tn = tid / tiles_m;
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int z = blockIdx.y;
-  const int kbeg = z * k_chunk;
-  const int kend = min(g.K, kbeg + k_chunk);
-  d4 acc[4][BN / 32];
-  gemm_tile<false, false, BN, false, (BN <= GEMM_DEEP_BN && gemm_occ<false, false, BN>() <= GEMM_OCC), true, false,
-            true>(g, m0, n0, kbeg, kend, smem, acc, &mod, nullptr, &mod2);
-  const int M = g.M, N = g.N;
-  if (partial != nullptr) {
-    double* P = partial + (int64_t)z * M * N;
-    acc_foreach<BN>(acc, m0, n0, [&](int m, int n, double v) {
-      if (m < M && n < N) P[(int64_t)m + (int64_t)n * M] = v;
-    });
-  } else {
-    acc_foreach<BN>(acc, m0, n0, [&](int m, int n, double v) {
-      if (m < M && n < N) C[(int64_t)m + (int64_t)n * ldc] = v;
-    });
-  }
+  gemm_modulated_body<BN, true>(g, mod, &mod2, C, ldc, tiles_m, tiles_n, k_chunk, partial, smem);
 }
 
 int gemm_modulated2(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda, const double* r1,
                     const double* t1, const double* s1, const double* r2, const double* t2, const double* s2, double d,
                     const double* B, int64_t ldb, double* C, int64_t ldc) {
-  BK_REQUIRE(m >= 0 && n >= 0 && k >= 0, "gemm_modulated2: negative dimension");
-  BK_REQUIRE(m < (1ll << 31) && n < (1ll << 31) && k < (1ll << 31), "gemm_modulated2: dimension too large");
-  if (m == 0 || n == 0) return BIGKRLS_OK;
-  BK_REQUIRE(C && ldc >= m, "gemm_modulated2: null C or ldc < m");
-  if (k == 0) {   // empty sum
-    const int blocks = (int)std::min<int64_t>((m * n + 255) / 256, 2048);
-    hipLaunchKernelGGL(scale_matrix_kernel, dim3(blocks), dim3(256), 0, ctx->stream, C, ldc, (int)m, (int)n, 0.0);
-    BK_CHECK_LAUNCH();
-    return BIGKRLS_OK;
-  }
-  BK_REQUIRE(A && B && r1 && t1 && s1 && r2 && t2 && s2, "gemm_modulated2: null pointer");
-  BK_REQUIRE(lda >= m && ldb >= k, "gemm_modulated2: leading dimension of A or B too small");
-  const GemmOperands g{A, B, lda, ldb, (int)m, (int)n, (int)k, nullptr};
-  const GemmMod mod{r1, t1, s1};
-  const GemmMod2 mod2{r2, t2, s2, d};
-  BK_TRY(prof_begin(ctx, "gemm_modulated2", 2.0 * (double)m * (double)n * (double)k));
-  if (n <= 32) BK_TRY(launch_gemm_modulated<32>(ctx, g, gemm_modulated2_kernel<32>, C, ldc, mod, mod2));
-  else if (n <= 64) BK_TRY(launch_gemm_modulated<64>(ctx, g, gemm_modulated2_kernel<64>, C, ldc, mod, mod2));
-  else BK_TRY(launch_gemm_modulated<128>(ctx, g, gemm_modulated2_kernel<128>, C, ldc, mod, mod2));
-  BK_TRY(prof_end(ctx, "gemm_modulated2"));
-  return BIGKRLS_OK;
+  return gemm_modulated_entry(ctx, "gemm_modulated2", m, n, k, A, lda, B, ldb, C, ldc, r1 && t1 && s1 && r2 && t2 && s2,
+                              [](auto bn) { return gemm_modulated2_kernel<decltype(bn)::value>; }, GemmMod{r1, t1, s1},
+                              GemmMod2{r2, t2, s2, d});
 }
 
 // ---------------------------------------------------------------------------
@@ -835,30 +781,20 @@ int gemm_modulated2(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const dou
 // over n by gemm_split_plan, taken over the computed tiles; the slabs (one 128 x BN block per tile and split) are
 // summed in slab order by gram_reduce_kernel: no atomics, two calls give the same bits.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void gram_tile_of(int t, int T, int* tm, int* tn) {   // column-major walk of the lower tile triangle
-  int c = 0, rem = t;
-  while (rem >= T - c) { rem -= T - c; ++c; }
-  *tn = c;
-  *tm = c + rem;
-}
-
 template <int BN>
 __global__ __launch_bounds__(NT, (gemm_occ<true, false, BN>())) void gram_weighted_kernel(
     GemmOperands g, const double* __restrict__ omega, double* __restrict__ C, int64_t ldc, int T, int ntile, int k_chunk,
     double* __restrict__ partial) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int t = xcd_remap(blockIdx.x, ntile);
-  int tm, tn;
-  gram_tile_of(t, T, &tm, &tn);
-  const int m0 = tm * BM, n0 = tn * BN;   // (T > 1 only with BN == BM)
-  const int z = blockIdx.y;
-  const int kbeg = z * k_chunk;
-  const int kend = min(g.K, kbeg + k_chunk);
+  const LowerTile lt = lower_tile_of(t, T);   // csrc/syrkmap.h
+  const int m0 = lt.tm * BM, n0 = lt.tn * BN;   // (T > 1 only with BN == BM)
+  const KSlab ks = k_slab(g.K, k_chunk);
   d4 acc[4][BN / 32];
-  gemm_tile<true, false, BN, false, (BN <= GEMM_DEEP_BN), false, true>(g, m0, n0, kbeg, kend, smem, acc, nullptr, omega);
+  gemm_tile<true, false, BN, false, (BN <= GEMM_DEEP_BN), false, true>(g, m0, n0, ks.kbeg, ks.kend, smem, acc, nullptr, omega);
   const int M = g.M;
   if (partial != nullptr) {
-    double* P = partial + ((int64_t)z * ntile + t) * (BM * BN);
+    double* P = partial + ((int64_t)ks.z * ntile + t) * (BM * BN);
     acc_foreach<BN>(acc, m0, n0, [&](int m, int n, double v) {
       if (m < M && n < M && m >= n) P[(m - m0) + (n - n0) * BM] = v;
     });
@@ -879,26 +815,14 @@ __global__ void gram_reduce_kernel(const double* __restrict__ partial, int split
   const int per_tile = BM * bn;
   const int wg_per_tile = per_tile / 256;
   const int t = blockIdx.x / wg_per_tile;
-  int tm, tn;
-  gram_tile_of(t, T, &tm, &tn);
-  const int m0 = tm * BM, n0 = tn * bn;
-  const int64_t slab = (int64_t)ntile * per_tile;
-  {
-    const int e = (blockIdx.x % wg_per_tile) * 256 + threadIdx.x;
-    const int m = m0 + e % BM, n = n0 + e / BM;
-    if (m >= M || n >= M || m < n) return;
-    const double* p = partial + (int64_t)t * per_tile + e;
-    double s = 0.0;
-    int z = 0;
-    for (; z + 4 <= splits; z += 4) {
-      const double a0 = p[(int64_t)(z + 0) * slab], a1 = p[(int64_t)(z + 1) * slab];
-      const double a2 = p[(int64_t)(z + 2) * slab], a3 = p[(int64_t)(z + 3) * slab];
-      s += a0; s += a1; s += a2; s += a3;
-    }
-    for (; z < splits; ++z) s += p[(int64_t)z * slab];
-    C[(int64_t)m + (int64_t)n * ldc] = s;
-    C[(int64_t)n + (int64_t)m * ldc] = s;
-  }
+  const LowerTile lt = lower_tile_of(t, T);
+  const int m0 = lt.tm * BM, n0 = lt.tn * bn;
+  const int e = (blockIdx.x % wg_per_tile) * 256 + threadIdx.x;
+  const int m = m0 + e % BM, n = n0 + e / BM;
+  if (m >= M || n >= M || m < n) return;
+  const double s = slab_sum(partial + (int64_t)t * per_tile + e, (int64_t)ntile * per_tile, splits);
+  C[(int64_t)m + (int64_t)n * ldc] = s;
+  C[(int64_t)n + (int64_t)m * ldc] = s;
 }
 
 template <int BN>
@@ -906,8 +830,8 @@ static int launch_gram_weighted(bigkrls_ctx* ctx, const GemmOperands& g, const d
   const int T = (g.M + BN - 1) / BN;            // BN < BM only for g.M <= BN: one tile
   BK_REQUIRE((int64_t)T * (T + 1) / 2 * (BM * BN / 256) < (1ll << 31), "gram_weighted: k too large (too many tiles)");
   const int ntile = T * (T + 1) / 2;
-  int splits = 1, k_chunk = BK;
-  gemm_split_plan<true, false, BN>(g, ntile, &splits, &k_chunk);
+  const SplitPlan plan = gemm_split_plan(split_model_gemm(gemm_occ<true, false, BN>()), g, ntile);
+  const int splits = plan.splits;
   double* partial = nullptr;
   if (splits > 1) {
     void* p = nullptr;
@@ -917,7 +841,7 @@ static int launch_gram_weighted(bigkrls_ctx* ctx, const GemmOperands& g, const d
   auto kern = gram_weighted_kernel<BN>;
   constexpr size_t smem = gemm_smem_bytes<true, false, BN>();
   BK_TRY(ensure_dyn_smem(ctx, (const void*)kern, smem));
-  hipLaunchKernelGGL(kern, dim3(ntile, splits), dim3(NT), smem, ctx->stream, g, omega, C, ldc, T, ntile, k_chunk, partial);
+  hipLaunchKernelGGL(kern, dim3(ntile, splits), dim3(NT), smem, ctx->stream, g, omega, C, ldc, T, ntile, plan.k_chunk, partial);
   BK_CHECK_LAUNCH();
   if (splits > 1) {
     hipLaunchKernelGGL(gram_reduce_kernel, dim3((unsigned)(ntile * (BM * BN / 256))), dim3(256), 0, ctx->stream, (const double*)partial,
@@ -929,24 +853,126 @@ static int launch_gram_weighted(bigkrls_ctx* ctx, const GemmOperands& g, const d
 
 int gram_weighted(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* A, int64_t lda, const double* omega, double* M,
                   int64_t ldm) {
-  BK_REQUIRE(n >= 0 && k >= 0, "gram_weighted: negative dimension");
-  BK_REQUIRE(n < (1ll << 31) && k < (1ll << 31), "gram_weighted: dimension too large");
+  BK_TRY(require_dims("gram_weighted", n, k));
   if (k == 0) return BIGKRLS_OK;
   BK_REQUIRE(M && ldm >= k, "gram_weighted: null M or leading dimension of M too small");
-  if (n == 0) {   // empty sum
-    const int blocks = (int)std::min<int64_t>((k * k + 255) / 256, 2048);
-    hipLaunchKernelGGL(scale_matrix_kernel, dim3(blocks), dim3(256), 0, ctx->stream, M, ldm, (int)k, (int)k, 0.0);
-    BK_CHECK_LAUNCH();
-    return BIGKRLS_OK;
-  }
+  if (n == 0) return zero_fill(ctx, M, ldm, k, k);   // empty sum
   BK_REQUIRE(A && omega, "gram_weighted: null pointer");
   BK_REQUIRE(lda >= n, "gram_weighted: leading dimension of A too small");
   const GemmOperands g{A, A, lda, lda, (int)k, (int)k, (int)n, nullptr};
   BK_TRY(prof_begin(ctx, "gram_weighted", (double)n * (double)k * ((double)k + 1.0)));
-  if (k <= 32) BK_TRY(launch_gram_weighted<32>(ctx, g, omega, M, ldm));
-  else if (k <= 64) BK_TRY(launch_gram_weighted<64>(ctx, g, omega, M, ldm));
-  else BK_TRY(launch_gram_weighted<128>(ctx, g, omega, M, ldm));
+  BK_TRY(with_bn(k, [&](auto bn) { return launch_gram_weighted<decltype(bn)::value>(ctx, g, omega, M, ldm); }));
   BK_TRY(prof_end(ctx, "gram_weighted"));
+  return BIGKRLS_OK;
+}
+
+// ---------------------------------------------------------------------------
+// diagonal of a quadratic form (pointwise predict, bigkrls_predict_pointwise in csrc/fit.hip)
+// ---------------------------------------------------------------------------
+// out[i] = sum_j (A V)[i,j] A[i,j] = diag(A V A'), A m x n, V n x n general (not assumed symmetric), both column-major.
+// The product A V runs through gemm_tile<false, false, BN> exactly as gemm_kernel does; only the epilogue differs. Each
+// lane multiplies its accumulators by A at the same (row, column) and sums over its columns; the four lanes that share
+// a row (lane >> 4) are added with shuffles and the two waves that share a row half through LDS, in a fixed order.
+// Each workgroup writes one partial per row: part[(z tiles_n + tn) M + row]. The dot with A is linear in the product,
+// so the k splits' partials are dotted and added like the column tiles' (quadform_reduce_kernel, fixed order: no
+// atomics, bitwise reproducible). Extra memory: splits x tiles_n x m doubles, never the m x n product.
+template <int BN>
+__global__ __launch_bounds__(NT, (gemm_occ<false, false, BN>())) void quadform_diag_kernel(
+    GemmOperands g, int tiles_m, int tiles_n, int k_chunk, double* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const TileAt at = tile_at<BN>(g, tiles_m, tiles_n, k_chunk);
+  const int m0 = at.m0, n0 = at.n0, tn = at.tn, z = at.z;
+  d4 acc[4][BN / 32];
+  gemm_tile<false, false, BN, false, (BN <= GEMM_DEEP_BN && gemm_occ<false, false, BN>() <= GEMM_OCC)>(g, m0, n0, at.kbeg,
+                                                                                                       at.kend, smem, acc);
+  constexpr int NJ = BN / 32;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wm = (wave & 1) * 64, wn = (wave >> 1) * (BN / 2);
+  const int lm = lane & 15, lk = lane >> 4;
+  const int M = g.M, N = g.N;
+  // register r of acc[i][j] is (m0 + wm + 16 i + lm, n0 + wn + 16 j + lk + 4 r), as in acc_foreach; columns past N
+  // hold products with clamped (finite) operand columns and are weighted by 0, rows past M are never written
+  double s[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int m = m0 + wm + i * 16 + lm;
+    const double* arow = g.A + (m < M ? m : M - 1);
+    double a[NJ][4];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int n = n0 + wn + j * 16 + lk + 4 * r;
+        a[j][r] = n < N ? arow[(int64_t)n * g.lda] : 0.0;
+      }
+    double t = 0.0;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) t = fma(acc[i][j][r], a[j][r], t);
+    t += __shfl_xor(t, 16, 64);
+    t += __shfl_xor(t, 32, 64);
+    s[i] = t;
+  }
+  // gemm_tile ends on a barrier after its last LDS read; this one is for the early return of an empty k range
+  __syncthreads();
+  double* red = smem;   // [wave][64 rows of the wave's half]
+  if (lk == 0) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) red[wave * 64 + i * 16 + lm] = s[i];
+  }
+  __syncthreads();
+  if (threadIdx.x < BM) {
+    const int r = threadIdx.x, h = r >> 6, rr = r & 63;       // waves h and h + 2 own rows [64 h, 64 h + 64)
+    const int m = m0 + r;
+    if (m < M) part[((int64_t)z * tiles_n + tn) * M + m] = red[h * 64 + rr] + red[(h + 2) * 64 + rr];
+  }
+}
+
+// out[i] = sum over q = z tiles_n + tn of part[q M + i], in the order q = 0, 1, ...
+__global__ void quadform_reduce_kernel(const double* __restrict__ part, int nparts, int M, double* __restrict__ out) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += gridDim.x * blockDim.x)
+    out[i] = slab_sum(part + i, M, nparts);
+}
+
+template <int BN>
+static int launch_quadform_diag(bigkrls_ctx* ctx, const GemmOperands& g, double* out) {
+  const int tiles_m = (g.M + BM - 1) / BM;
+  const int tiles_n = (g.N + BN - 1) / BN;
+  const int ntile = tiles_m * tiles_n;
+  const SplitPlan plan = gemm_split_plan(split_model_quadform(gemm_occ<false, false, BN>()), g, ntile);
+  const int nparts = plan.splits * tiles_n;
+  void* p = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_QF_PART, (int64_t)nparts * g.M * (int64_t)sizeof(double), &p));
+  auto kern = quadform_diag_kernel<BN>;
+  constexpr size_t smem = gemm_smem_bytes<false, false, BN>();
+  static_assert(smem >= 4 * 64 * sizeof(double), "quadform_diag_kernel: LDS too small for the row reduction");
+  BK_TRY(ensure_dyn_smem(ctx, (const void*)kern, smem));
+  hipLaunchKernelGGL(kern, dim3(ntile, plan.splits), dim3(NT), smem, ctx->stream, g, tiles_m, tiles_n, plan.k_chunk,
+                     (double*)p);
+  BK_CHECK_LAUNCH();
+  const int blocks = std::min((g.M + 255) / 256, 2048);
+  hipLaunchKernelGGL(quadform_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const double*)p, nparts, g.M,
+                     out);
+  BK_CHECK_LAUNCH();
+  return BIGKRLS_OK;
+}
+
+int quadform_diag(bigkrls_ctx* ctx, int64_t m, int64_t n, const double* A, int64_t lda, const double* V, int64_t ldv,
+                  double* out) {
+  BK_TRY(require_dims("quadform_diag", m, n));
+  if (m == 0) return BIGKRLS_OK;
+  BK_REQUIRE(out, "quadform_diag: null pointer");
+  if (n == 0) {   // empty sum
+    BK_HIP(hipMemsetAsync(out, 0, (size_t)m * sizeof(double), ctx->stream));
+    return BIGKRLS_OK;
+  }
+  BK_REQUIRE(A && V, "quadform_diag: null pointer");
+  BK_REQUIRE(lda >= m && ldv >= n, "quadform_diag: leading dimension of A or V too small");
+  GemmOperands g{A, V, lda, ldv, (int)m, (int)n, (int)n, nullptr};
+  BK_TRY(prof_begin(ctx, "quadform_diag", 2.0 * (double)m * (double)n * (double)n + 2.0 * (double)m * (double)n));
+  BK_TRY(with_bn(n, [&](auto bn) { return launch_quadform_diag<decltype(bn)::value>(ctx, g, out); }));
+  BK_TRY(prof_end(ctx, "quadform_diag"));
   return BIGKRLS_OK;
 }
 
@@ -965,8 +991,8 @@ __global__ __launch_bounds__(NT, 2) void gemm_nn48_kernel(GemmOperands g, int ti
   constexpr int NJ = SK_BN / 16;
   const int tm = xcd_remap(blockIdx.x, tiles_m);
   const int m0 = tm * BM;
-  const int z = blockIdx.y;
-  const int kbeg = z * k_chunk, kend = min(g.K, kbeg + k_chunk);
+  const KSlab ks = k_slab(g.K, k_chunk);
+  const int z = ks.z, kbeg = ks.kbeg, kend = ks.kend;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wm = wave * 32, lm = lane & 15, lk = lane >> 4;
   d4 acc[2][NJ];
@@ -1055,32 +1081,14 @@ int gemm_nn_skinny48(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const do
   GemmOperands g{A, B, lda, ldb, (int)m, (int)n, (int)k, nullptr};
   const int tiles_m = (int)((m + BM - 1) / BM);
   // two workgroups per CU: split K so that the grid fills whole rounds of the 512 slots (or as much of one as K allows)
-  constexpr int resident = 256 * 2;
-  int splits = 1;
-  {
-    const int maxs = (int)std::min<int64_t>(64, std::max<int64_t>(1, k / 256));
-    const double per_split = 3.2e-6 * (double)m * (double)n + 0.2;
-    double best = 1e30;
-    for (int sp = 1; sp <= maxs; ++sp) {
-      const int rounds = (tiles_m * sp + resident - 1) / resident;
-      const double cost = 0.045 * rounds * ((double)k / sp) + per_split * sp;
-      if (cost < best - 1e-9) { best = cost; splits = sp; }
-    }
-  }
-  int k_chunk = (int)(((k + splits - 1) / splits + BK - 1) / BK * BK);
-  splits = (int)((k + k_chunk - 1) / k_chunk);
+  const SplitPlan plan = gemm_split_plan(split_model_skinny48(), g, tiles_m);
   void* p = nullptr;
-  const int slot = (ctx->side_stream && (ctx->stream == ctx->side_stream || ctx->stream == ctx->bg_stream)) ? SLOT_SIDE_SPLITK : SLOT_GEMM_SPLITK;
-  BK_TRY(ws_get(ctx, slot, (int64_t)splits * m * n * sizeof(double), &p));
+  BK_TRY(ws_get(ctx, gemm_split_slot(ctx), (int64_t)plan.splits * m * n * sizeof(double), &p));
   BK_TRY(ensure_dyn_smem(ctx, (const void*)gemm_nn48_kernel, sk48_smem_bytes()));
-  hipLaunchKernelGGL(gemm_nn48_kernel, dim3(tiles_m, splits), dim3(NT), sk48_smem_bytes(), ctx->stream, g, tiles_m, k_chunk,
-                     (double*)p);
+  hipLaunchKernelGGL(gemm_nn48_kernel, dim3(tiles_m, plan.splits), dim3(NT), sk48_smem_bytes(), ctx->stream, g, tiles_m,
+                     plan.k_chunk, (double*)p);
   BK_CHECK_LAUNCH();
-  int blocks = (int)std::min<int64_t>((m * n + 255) / 256, 2048);
-  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const double*)p, splits, (int)m, (int)n,
-                     1.0, 0.0, C, ldc, (const int*)nullptr);
-  BK_CHECK_LAUNCH();
-  return BIGKRLS_OK;
+  return launch_splitk_reduce(ctx, (const double*)p, plan.splits, (int)m, (int)n, 1.0, 0.0, C, ldc, nullptr);
 }
 
 // ---------------------------------------------------------------------------
@@ -1094,13 +1102,8 @@ __global__ __launch_bounds__(NT, GEMM_OCC) void syrk_lower_kernel(GemmOperands g
                                                         int tiles) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   // blockIdx.x enumerates the lower-triangular tiles column by column
-  const int t = blockIdx.x;
-  // tn = largest integer with tn*tiles - tn(tn-1)/2 <= t
-  int tn = (int)((2.0 * tiles + 1.0 - sqrt((2.0 * tiles + 1.0) * (2.0 * tiles + 1.0) - 8.0 * t)) * 0.5);
-  while (tn > 0 && tn * tiles - tn * (tn - 1) / 2 > t) --tn;
-  while ((tn + 1) * tiles - (tn + 1) * tn / 2 <= t) ++tn;
-  const int tm = tn + (t - (tn * tiles - tn * (tn - 1) / 2));
-  const int m0 = tm * BM, n0 = tn * 128;
+  const LowerTile lt = lower_tile_of(blockIdx.x, tiles);   // csrc/syrkmap.h
+  const int m0 = lt.tm * BM, n0 = lt.tn * 128;
   d4 acc[4][4];
   gemm_tile<false, true, 128>(g, m0, n0, 0, g.K, smem, acc);
   const int M = g.M;
@@ -1268,6 +1271,12 @@ static int64_t syrk_map_build(SyrkMap& mp, int tiles, int c0, int c1, int k) {
   return syrk_map_build<SBN>(mp, tiles, c0, c1, k, order_cols != 0, r_env);
 }
 
+// the operands of a rank-k update of an m x m matrix, and its number of 128-row tiles
+struct SyrkOperands { GemmOperands g; int tiles; };
+static SyrkOperands syrk_operands(int64_t m, int64_t k, const double* A, int64_t lda, const double* B, int64_t ldb) {
+  return SyrkOperands{GemmOperands{A, B, lda, ldb, (int)m, (int)m, (int)k, nullptr}, (int)((m + BM - 1) / BM)};
+}
+
 template <int SBN, bool ACCUM>
 static int launch_syrk_mirror(bigkrls_ctx* ctx, const GemmOperands& g, double alpha, double* C, int64_t ldc,
                               int tiles, int c0, int c1) {
@@ -1288,8 +1297,7 @@ int syrk_mirror(bigkrls_ctx* ctx, int64_t m, int64_t k, double alpha, const doub
                 bool narrow_tiles, bool skip_first_column) {
   if (m <= 0 || k <= 0) return BIGKRLS_OK;
   BK_REQUIRE(m < (1ll << 31) && k < (1ll << 31), "syrk_mirror: dimension too large");
-  GemmOperands g{A, B, lda, ldb, (int)m, (int)m, (int)k, nullptr};
-  const int tiles = (int)((m + BM - 1) / BM);
+  const auto [g, tiles] = syrk_operands(m, k, A, lda, B, ldb);
   if (tn_end < 0 || tn_end > tiles) tn_end = tiles;
   if (tn_begin >= tn_end) return BIGKRLS_OK;
   // 128 x 64 tiles (three workgroups per CU) share the GPU better with a concurrent
@@ -1306,8 +1314,7 @@ int syrk_mirror_set(bigkrls_ctx* ctx, int64_t m, int64_t k, double alpha, const 
                     const double* B, int64_t ldb, double* C, int64_t ldc) {
   if (m <= 0) return BIGKRLS_OK;
   BK_REQUIRE(k > 0 && m < (1ll << 31) && k < (1ll << 31), "syrk_mirror_set: bad dimensions");
-  GemmOperands g{A, B, lda, ldb, (int)m, (int)m, (int)k, nullptr};
-  const int tiles = (int)((m + BM - 1) / BM);
+  const auto [g, tiles] = syrk_operands(m, k, A, lda, B, ldb);
   return launch_syrk_mirror<128, false>(ctx, g, alpha, C, ldc, tiles, 0, tiles);
 }
 
@@ -1317,8 +1324,7 @@ int syrk_mirror_cols(bigkrls_ctx* ctx, int64_t m, int64_t k, double alpha, const
                      const double* B, int64_t ldb, double* C, int64_t ldc, int c64_begin, int c64_end) {
   if (m <= 0 || k <= 0) return BIGKRLS_OK;
   BK_REQUIRE(m < (1ll << 31) && k < (1ll << 31), "syrk_mirror_cols: dimension too large");
-  GemmOperands g{A, B, lda, ldb, (int)m, (int)m, (int)k, nullptr};
-  const int tiles = (int)((m + BM - 1) / BM);
+  const auto [g, tiles] = syrk_operands(m, k, A, lda, B, ldb);
   // (an odd last column of the matrix: the second column of the last group does not exist, but its
   //  tiles are enumerated; they lie entirely outside the matrix and store nothing)
   if (c64_end < 0 || c64_end > 2 * tiles) c64_end = 2 * tiles;
@@ -1330,8 +1336,7 @@ int syrk_lower(bigkrls_ctx* ctx, int64_t m, int64_t k, double alpha, const doubl
                const double* B, int64_t ldb, double* C, int64_t ldc) {
   if (m <= 0 || k <= 0) return BIGKRLS_OK;
   BK_REQUIRE(m < (1ll << 31) && k < (1ll << 31), "syrk_lower: dimension too large");
-  GemmOperands g{A, B, lda, ldb, (int)m, (int)m, (int)k, nullptr};
-  const int tiles = (int)((m + BM - 1) / BM);
+  const auto [g, tiles] = syrk_operands(m, k, A, lda, B, ldb);
   const int64_t nt = (int64_t)tiles * (tiles + 1) / 2;
   BK_TRY(ensure_dyn_smem(ctx, (const void*)syrk_lower_kernel, smem_bytes(128)));
   hipLaunchKernelGGL(syrk_lower_kernel, dim3((unsigned)nt), dim3(NT), smem_bytes(128), ctx->stream, g,
@@ -3458,152 +3463,6 @@ int kernel_op_times(bigkrls_ctx* ctx, const KernelOp& op, const double* W, int64
                     int64_t ldo) {
   return kernel_contract_centred(ctx, op.Xc, op.n, op.n, op.nrm, op.Xc, op.n, op.n, op.nrm, op.p, op.sigma, W, q, ldw,
                                  out, ldo);
-}
-
-
-// ---------------------------------------------------------------------------
-// diagonal of a quadratic form (pointwise predict, bigkrls_predict_pointwise in csrc/fit.hip)
-// ---------------------------------------------------------------------------
-// out[i] = sum_j (A V)[i,j] A[i,j] = diag(A V A'), A m x n, V n x n general (not assumed symmetric), both column-major.
-// The product A V runs through gemm_tile<false, false, BN> exactly as gemm_kernel does; only the epilogue differs. Each
-// lane multiplies its accumulators by A at the same (row, column) and sums over its columns; the four lanes that share
-// a row (lane >> 4) are added with shuffles and the two waves that share a row half through LDS, in a fixed order.
-// Each workgroup writes one partial per row: part[(z tiles_n + tn) M + row]. The dot with A is linear in the product,
-// so the k splits' partials are dotted and added like the column tiles' (quadform_reduce_kernel, fixed order: no
-// atomics, bitwise reproducible). Extra memory: splits x tiles_n x m doubles, never the m x n product.
-template <int BN>
-__global__ __launch_bounds__(NT, (gemm_occ<false, false, BN>())) void quadform_diag_kernel(
-    GemmOperands g, int tiles_m, int tiles_n, int k_chunk, double* __restrict__ part) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int ntile = tiles_m * tiles_n;
-  const int tid = xcd_remap(blockIdx.x, ntile);
-  const int tm = tid % tiles_m, tn = tid / tiles_m;
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int z = blockIdx.y;
-  const int kbeg = z * k_chunk;
-  const int kend = min(g.K, kbeg + k_chunk);
-  d4 acc[4][BN / 32];
-  gemm_tile<false, false, BN, false, (BN <= GEMM_DEEP_BN && gemm_occ<false, false, BN>() <= GEMM_OCC)>(g, m0, n0, kbeg,
-                                                                                                       kend, smem, acc);
-  constexpr int NJ = BN / 32;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wm = (wave & 1) * 64, wn = (wave >> 1) * (BN / 2);
-  const int lm = lane & 15, lk = lane >> 4;
-  const int M = g.M, N = g.N;
-  // register r of acc[i][j] is (m0 + wm + 16 i + lm, n0 + wn + 16 j + lk + 4 r), as in acc_foreach; columns past N
-  // hold products with clamped (finite) operand columns and are weighted by 0, rows past M are never written
-  double s[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int m = m0 + wm + i * 16 + lm;
-    const double* arow = g.A + (m < M ? m : M - 1);
-    double a[NJ][4];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = n0 + wn + j * 16 + lk + 4 * r;
-        a[j][r] = n < N ? arow[(int64_t)n * g.lda] : 0.0;
-      }
-    double t = 0.0;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) t = fma(acc[i][j][r], a[j][r], t);
-    t += __shfl_xor(t, 16, 64);
-    t += __shfl_xor(t, 32, 64);
-    s[i] = t;
-  }
-  // gemm_tile ends on a barrier after its last LDS read; this one is for the early return of an empty k range
-  __syncthreads();
-  double* red = smem;   // [wave][64 rows of the wave's half]
-  if (lk == 0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) red[wave * 64 + i * 16 + lm] = s[i];
-  }
-  __syncthreads();
-  if (threadIdx.x < BM) {
-    const int r = threadIdx.x, h = r >> 6, rr = r & 63;       // waves h and h + 2 own rows [64 h, 64 h + 64)
-    const int m = m0 + r;
-    if (m < M) part[((int64_t)z * tiles_n + tn) * M + m] = red[h * 64 + rr] + red[(h + 2) * 64 + rr];
-  }
-}
-
-// out[i] = sum over q = z tiles_n + tn of part[q M + i], in the order q = 0, 1, ...
-__global__ void quadform_reduce_kernel(const double* __restrict__ part, int nparts, int M, double* __restrict__ out) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += gridDim.x * blockDim.x) {
-    const double* p = part + i;
-    double s = 0.0;
-    int q = 0;
-    for (; q + 4 <= nparts; q += 4) {   // four loads in flight, added in order
-      const double a0 = p[(int64_t)(q + 0) * M], a1 = p[(int64_t)(q + 1) * M];
-      const double a2 = p[(int64_t)(q + 2) * M], a3 = p[(int64_t)(q + 3) * M];
-      s += a0; s += a1; s += a2; s += a3;
-    }
-    for (; q < nparts; ++q) s += p[(int64_t)q * M];
-    out[i] = s;
-  }
-}
-
-template <int BN>
-static int launch_quadform_diag(bigkrls_ctx* ctx, const GemmOperands& g, double* out) {
-  const int tiles_m = (g.M + BM - 1) / BM;
-  const int tiles_n = (g.N + BN - 1) / BN;
-  const int ntile = tiles_m * tiles_n;
-  // split-K with launch_gemm's time model (rounds of the resident workgroups times k-steps per split, plus a cost per
-  // split). Per split the partials are one double per row and column tile, but the epilogue reads A's m x n again:
-  // 8 bytes per element of the product instead of the 16 of gemm's partial slabs.
-  int splits = 1;
-  if (ntile < 4096 && g.K >= 1024) {
-    const int maxs = std::min(64, std::max(1, g.K / 256));
-    const double per_split = 1.6e-6 * (double)g.M * (double)g.N + 0.2;
-    double best = 1e30;
-    constexpr int resident = 256 * gemm_occ<false, false, BN>();
-    for (int sp = 1; sp <= maxs; ++sp) {
-      const int rounds = (ntile * sp + resident - 1) / resident;
-      const double cost = 0.06 * rounds * ((double)g.K / sp) + per_split * sp;
-      if (cost < best - 1e-9) { best = cost; splits = sp; }
-    }
-  }
-  int k_chunk = ((g.K + splits - 1) / splits + BK - 1) / BK * BK;
-  if (k_chunk < BK) k_chunk = BK;
-  splits = (g.K + k_chunk - 1) / k_chunk;
-  if (splits < 1) splits = 1;
-  const int nparts = splits * tiles_n;
-  void* p = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_QF_PART, (int64_t)nparts * g.M * (int64_t)sizeof(double), &p));
-  auto kern = quadform_diag_kernel<BN>;
-  constexpr size_t smem = gemm_smem_bytes<false, false, BN>();
-  static_assert(smem >= 4 * 64 * sizeof(double), "quadform_diag_kernel: LDS too small for the row reduction");
-  BK_TRY(ensure_dyn_smem(ctx, (const void*)kern, smem));
-  hipLaunchKernelGGL(kern, dim3(ntile, splits), dim3(NT), smem, ctx->stream, g, tiles_m, tiles_n, k_chunk, (double*)p);
-  BK_CHECK_LAUNCH();
-  const int blocks = std::min((g.M + 255) / 256, 2048);
-  hipLaunchKernelGGL(quadform_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (const double*)p, nparts, g.M,
-                     out);
-  BK_CHECK_LAUNCH();
-  return BIGKRLS_OK;
-}
-
-int quadform_diag(bigkrls_ctx* ctx, int64_t m, int64_t n, const double* A, int64_t lda, const double* V, int64_t ldv,
-                  double* out) {
-  BK_REQUIRE(m >= 0 && n >= 0, "quadform_diag: negative dimension");
-  BK_REQUIRE(m < (1ll << 31) && n < (1ll << 31), "quadform_diag: dimension too large");
-  if (m == 0) return BIGKRLS_OK;
-  BK_REQUIRE(out, "quadform_diag: null pointer");
-  if (n == 0) {   // empty sum
-    BK_HIP(hipMemsetAsync(out, 0, (size_t)m * sizeof(double), ctx->stream));
-    return BIGKRLS_OK;
-  }
-  BK_REQUIRE(A && V, "quadform_diag: null pointer");
-  BK_REQUIRE(lda >= m && ldv >= n, "quadform_diag: leading dimension of A or V too small");
-  GemmOperands g{A, V, lda, ldv, (int)m, (int)n, (int)n, nullptr};
-  BK_TRY(prof_begin(ctx, "quadform_diag", 2.0 * (double)m * (double)n * (double)n + 2.0 * (double)m * (double)n));
-  if (n <= 32) BK_TRY(launch_quadform_diag<32>(ctx, g, out));
-  else if (n <= 64) BK_TRY(launch_quadform_diag<64>(ctx, g, out));
-  else BK_TRY(launch_quadform_diag<128>(ctx, g, out));
-  BK_TRY(prof_end(ctx, "quadform_diag"));
-  return BIGKRLS_OK;
 }
 
 }  // namespace bk

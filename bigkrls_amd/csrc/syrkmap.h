@@ -33,6 +33,17 @@ BK_HD int xcd_remap(int bid, int nblocks) {
   return start + i;
 }
 
+// Column-major walk of the lower triangle of a T x T tile grid: tile t of T (T + 1) / 2 -> (row tm >= column tn). Column
+// tn starts at tn T - tn (tn - 1) / 2; tn is the largest integer with that start <= t: the closed form, then fix-ups for
+// the rounding of the square root. (gram_weighted_kernel, gram_reduce_kernel, syrk_lower_kernel)
+struct LowerTile { int tm, tn; };
+BK_HD LowerTile lower_tile_of(int t, int T) {
+  int tn = (int)((2.0 * T + 1.0 - sqrt((2.0 * T + 1.0) * (2.0 * T + 1.0) - 8.0 * t)) * 0.5);
+  while (tn > 0 && tn * T - tn * (tn - 1) / 2 > t) --tn;
+  while ((tn + 1) * T - (tn + 1) * tn / 2 <= t) ++tn;
+  return LowerTile{tn + (t - (tn * T - tn * (tn - 1) / 2)), tn};
+}
+
 constexpr int SYRK_MAX_BANDS = 159;
 struct SyrkMap {
   int tiles;            // 128-row tiles of the matrix

@@ -3,7 +3,8 @@
 // with the function the kernel runs, and the result must be exactly the set
 //     {(tc, tm): c0 <= tc < c1, tc / CPT <= tm < tiles},
 // every tile once, with the builder's return value equal to that count. Each map lives in a heap block of its own size,
-// so the sanitizer sees a band table that outgrows band_start.
+// so the sanitizer sees a band table that outgrows band_start. The walk of the whole lower tile triangle (lower_tile_of:
+// gram_weighted_kernel, gram_reduce_kernel, syrk_lower_kernel) is compared with the plain loop for every T up to 1024.
 #include "syrkmap.h"
 
 #include <cstdio>
@@ -118,6 +119,20 @@ int main() {
   // ... and gives XCD x (block ids x, x + 8, ...) one contiguous run
   for (int n : {8, 9, 15, 16, 1000, 1001})
     for (int b = 8; b < n; ++b) CHECK(bk::xcd_remap(b, n) == bk::xcd_remap(b - 8, n) + 1, "xcd_remap run at %d of %d", b, n);
+  // lower_tile_of (closed form with fix-ups) against the plain column-major walk of the lower tile triangle, for every
+  // tile of every grid of 1 to 1024 tile rows
+  long long walked = 0;
+  for (int T = 1; T <= 1024; ++T) {
+    int t = 0;
+    for (int tn = 0; tn < T; ++tn)
+      for (int tm = tn; tm < T; ++tm, ++t) {
+        const bk::LowerTile lt = bk::lower_tile_of(t, T);
+        CHECK(lt.tm == tm && lt.tn == tn, "lower_tile_of(%d, %d) = (%d, %d), the walk gives (%d, %d)", t, T, lt.tm, lt.tn, tm, tn);
+      }
+    CHECK(t == T * (T + 1) / 2, "T=%d: %d tiles", T, t);
+    walked += t;
+  }
+  std::printf("syrkmap_check: %lld lower-triangle tiles walked\n", walked);
   check_width<64>();
   check_width<128>();
   std::printf("syrkmap_check: %lld maps, %lld tiles decoded\n", cases, decoded);

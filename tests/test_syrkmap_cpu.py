@@ -3,7 +3,9 @@ syrk_mirror_kernel runs, xcd_remap) is pure index arithmetic: a stand-alone host
 its own main) decodes every block id of a launch for both tile widths and requires exactly the tiles of the requested
 columns of the lower tile triangle, each once, and the builder's count: 1 to 13 row tiles with every column range; 40,
 157, 318, 319, 330 and 700 row tiles, where the band table fills up and the rows per band are raised; every k that changes
-the rows per band; the rows-per-band override; the column order with its offset; empty ranges. Built with
+the rows per band; the rows-per-band override; the column order with its offset; empty ranges. The walk of the whole lower
+tile triangle (lower_tile_of: gram_weighted_kernel, gram_reduce_kernel, syrk_lower_kernel), a closed form with fix-ups, is
+compared with the plain loop for every tile of every grid of 1 to 1024 tile rows. Built with
 -fsanitize=address,undefined, so a band table that outgrows its array is seen. No GPU, no HIP, nothing loaded into
 Python."""
 import os
