@@ -125,6 +125,8 @@ int solveforc(bigkrls_ctx* ctx, const double* Q, int64_t n_rows, int64_t k, int6
   BK_REQUIRE(n_rows > 0 && k > 0 && n_rows < (1ll << 31) && k < (1ll << 31),
              "solveforc: bad dimensions");
   BK_REQUIRE(Q && d && a && h_Le, "solveforc: null pointer");
+  // (a too-small leading dimension would read outside the caller's matrix without any error)
+  BK_REQUIRE(ldq >= n_rows, "solveforc: ldq < n_rows");
   const int rb = (int)((n_rows + 255) / 256);
   int splits = (1024 + rb - 1) / rb;
   const int max_splits = (int)((k + SF_KC - 1) / SF_KC);
@@ -259,7 +261,7 @@ int lambda_bounds(const double* vals, int64_t n_vals, int64_t n, double* L, doub
 // state and trace) and then evaluates the loss at the lambda that decision asks for. One launch per probe, no
 // read-back inside the search: the host enqueues a chain of launches, the ones behind the terminating decision
 // return at once, and state + trace come back in one copy. The arithmetic of the control step is R's, statement
-// for statement and without fused multiply-adds (R/bigKRLS_Rcpp_functions.R:38-77).
+// for statement and without fused multiply-adds (R/bigKRLS_Rcpp_functions.R:38-77; sf_step).
 struct SfState {
   double L, U, X1, X2, S1, S2, tol, cur, lambda, last_le;
   int pending;   // the slot (1 or 2) the probe at `cur` fills
@@ -269,6 +271,10 @@ struct SfState {
 };
 
 __device__ __forceinline__ SfState sf_step(SfState s, double le) {
+  // R rounds the product and the sum of L + G (U - L) separately. hipcc contracts them into one fused multiply-add by
+  // default, and the __d*_rn intrinsics are plain operators to it, so contraction is switched off for this function:
+  // a fused step probes lambdas one unit in the last place off R's.
+#pragma clang fp contract(off)
   const double G = 0.381966;
   s.last_le = le;
   if (s.pending == 1) s.S1 = le; else s.S2 = le;
@@ -278,18 +284,18 @@ __device__ __forceinline__ SfState sf_step(SfState s, double le) {
     s.pending = 2;
     return s;
   }
-  if (fabs(__dsub_rn(s.S1, s.S2)) > s.tol) {                       // while (abs(S1 - S2) > tol)  (:55)
+  if (fabs(s.S1 - s.S2) > s.tol) {                                 // while (abs(S1 - S2) > tol)  (:55)
     if (s.S1 < s.S2) {                                            // :57-62
       s.U = s.X2;
       s.X2 = s.X1;
-      s.X1 = __dadd_rn(s.L, __dmul_rn(G, __dsub_rn(s.U, s.L)));
+      s.X1 = s.L + G * (s.U - s.L);
       s.S2 = s.S1;
       s.cur = s.X1;
       s.pending = 1;
     } else {                                                      // :66-71
       s.L = s.X1;
       s.X1 = s.X2;
-      s.X2 = __dsub_rn(s.U, __dmul_rn(G, __dsub_rn(s.U, s.L)));
+      s.X2 = s.U - G * (s.U - s.L);
       s.S1 = s.S2;
       s.cur = s.X2;
       s.pending = 2;
@@ -447,8 +453,14 @@ int lambda_search(bigkrls_ctx* ctx, const double* Q, int64_t n, int64_t k, int64
   BK_REQUIRE(n >= 0 && n_total > 0 && k > 0 && n_total < (1ll << 31) && k < (1ll << 31), "lambda_search: bad dimensions");
   BK_REQUIRE((Q || n == 0) && d && a, "lambda_search: null pointer");
   BK_REQUIRE(comm || n == n_total, "lambda_search: a row block needs a communicator");
+  // (a too-small leading dimension would read outside the caller's matrix without any error)
+  BK_REQUIRE(ldq >= n, "lambda_search: ldq < n");
   if (tol <= 0.0) tol = 1e-3 * (double)n_total;  // R/bigKRLS_Rcpp_functions.R:11-12
   if (L < 0.0 || U < 0.0) {
+    BK_REQUIRE(h_vals_all && n_vals > 0, "lambda_search: a derived bound needs all eigenvalues (h_vals_all)");
+    for (int64_t i = 0; i < n_vals; ++i)
+      BK_REQUIRE(!std::isnan(h_vals_all[i]),
+                 "lambda_search: Missing eigenvalues prevent bigKRLS from obtaining the regularization parameter lambda.");
     double l0, u0;
     BK_TRY(lambda_bounds(h_vals_all, n_vals, n_total, &l0, &u0));
     if (L < 0.0) L = l0;

@@ -85,6 +85,8 @@ __global__ void gemv_n_reduce_kernel(int m, int splits, double alpha,
 int gemv(bigkrls_ctx* ctx, int trans, int64_t m, int64_t n, double alpha, const double* A,
          int64_t lda, const double* x, double beta, double* y) {
   BK_REQUIRE(m >= 0 && n >= 0 && m < (1ll << 31) && n < (1ll << 31), "gemv: bad dimensions");
+  // (a too-small leading dimension would read outside the caller's matrix without any error; qty comes through here)
+  BK_REQUIRE(lda >= m, "gemv: lda < m");
   if (trans) {
     if (n == 0) return BIGKRLS_OK;
     hipLaunchKernelGGL(gemv_t_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, ctx->stream,

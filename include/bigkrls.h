@@ -432,13 +432,15 @@ int bigkrls_dev_lanczos_projected(bigkrls_ctx* ctx, const double* d_A_blocks, co
 int bigkrls_dev_copy_matrix(bigkrls_ctx* ctx, const double* src, int64_t m, int64_t n, int64_t lds,
                             double* dst, int64_t ldd);
 
-/* a = Q'y (k-vector), hoisted out of the lambda probes. Q rows [0,n), ld ldq. */
+/* a = Q'y (k-vector), hoisted out of the lambda probes. Q rows [0,n), ld ldq >= n
+ * (BIGKRLS_EINVAL otherwise, as in the two entries below). */
 int bigkrls_dev_qty(bigkrls_ctx* ctx, const double* Q, int64_t n, int64_t k, int64_t ldq,
                     const double* y, double* a);
 
 /* One solveforc probe on a row block of Q (n_rows x k, ldq): with
  * w_k = 1/(d_k+lambda): c_i = sum_k Q_ik w_k a_k, g_i = sum_k Q_ik^2 w_k,
- * *h_Le = sum_i (c_i/g_i)^2 over the block's rows. c (n_rows) may be NULL. */
+ * *h_Le = sum_i (c_i/g_i)^2 over the block's rows. c (n_rows) may be NULL.
+ * ldq >= n_rows. */
 int bigkrls_dev_solveforc(bigkrls_ctx* ctx, const double* Q, int64_t n_rows, int64_t k, int64_t ldq,
                           const double* d, const double* a, double lambda,
                           double* c, double* h_Le);
@@ -447,7 +449,9 @@ int bigkrls_dev_solveforc(bigkrls_ctx* ctx, const double* Q, int64_t n_rows, int
  * on one device: h_vals_all[n_vals] are ALL eigenvalues (host copy, bounds loops,
  * quirk Q5); d (device) the first k of them. h_L/h_U < 0 mean "derive the bound".
  * Outputs lambda, the number of probes and (optionally) the probe trace
- * h_trace[2*max_trace] = (lambda_t, Le_t). */
+ * h_trace[2*max_trace] = (lambda_t, Le_t): the first min(probes, max_trace) pairs;
+ * *h_nprobes is the full count. h_nprobes and h_trace may be NULL, h_vals_all may
+ * be NULL when both bounds are given, h_tol <= 0 means 1e-3 n, ldq >= n. */
 int bigkrls_dev_lambda_search(bigkrls_ctx* ctx, const double* Q, int64_t n, int64_t k, int64_t ldq,
                               const double* d, const double* a,
                               const double* h_vals_all, int64_t n_vals,
