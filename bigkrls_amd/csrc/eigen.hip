@@ -2192,8 +2192,6 @@ int eigen(bigkrls_ctx* ctx, const double* A, int64_t n64, int64_t lda, int64_t n
           int64_t n_vecs_max, double keep_thresh, double* vecs, int64_t ldv, int64_t* h_n_vecs,
           int part_index, int part_count, int mode);
 
-static thread_local std::string kry_diag;   // what the last block Lanczos did at its convergence checks (for the error text)
-
 // W (n x cols, ld n) = K B (n x cols, ld n): the only way the block Lanczos touches K. Single GPU: the whole matrix
 // A. Multi-GPU: this rank's column block Kcols = K[:, r0:r1] gives the rows r0:r1 of K B (K symmetric: Kcols' B),
 // one all-gather of the row blocks assembles the product on every rank ("Eigen, partial").
@@ -2245,85 +2243,200 @@ static int kry_agree_status(const KTimes& op, int rc) { return op.comm ? comm_ag
 // k_eff values, *h_n_vecs = c vectors. The schedule of the checks depends on sizes and Ritz data only: the first
 // check where a fixed k = 128 has it, the later ones by steps_to_go with the current k_eff; no estimate checks.
 // `ke` below is that effective rank; in a fixed run ke == k throughout.
-static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t k, double* vals,
-                        int64_t n_vecs_max, double keep_thresh, double* vecs, int64_t ldv,
-                        int64_t* h_n_vecs, int part_index, int part_count, bool auto_rank = false,
-                        int64_t* h_n_vals = nullptr) {
-  hipStream_t st = ctx->stream;
-  constexpr int b = 128;
-  const double tol = 1e-10;
-  kry_diag.clear();
-  if (auto_rank) BK_REQUIRE(keep_thresh > 0.0 && h_n_vals && !kop.comm, "eigen (Krylov, auto rank): needs keep_thresh > 0 and one GPU");
-  int64_t ke = auto_rank ? std::min<int64_t>(k, b) : k;
-  int n_checks = 0;
+namespace {
+
+struct KryArgs {     // (the arguments of eigen_krylov)
+  bigkrls_ctx* ctx;
+  const KTimes& kop;
+  int64_t n, k;
+  double* vals;
+  int64_t n_vecs_max;
+  double keep_thresh;
+  double* vecs;
+  int64_t ldv;
+  int64_t *h_n_vecs, *h_n_vals;
+  int part_index, part_count;
+  bool auto_rank;
+};
+
+// The development switches of the iteration (tools/kry_ab.py, tools/kry_sweep.py, tests/test_gpu_configs.py), read in
+// one place: BlockLanczos::run fills one of these when it starts.
+//   BIGKRLS_KRY_FIRST_CHECK=<step>  the first check at that step (at least 2) instead of where the schedule has it
+//   BIGKRLS_KRY_CGS=2               both Gram-Schmidt passes against every block, as until round 6
+//   BIGKRLS_KRY_PIVOTS              how well conditioned each new block was, on stderr
+//   BIGKRLS_KRY_NOEST               full checks only
+//   BIGKRLS_KRY_CHECK_EVERY         a full check after every step (the convergence history)
+//   BIGKRLS_KRY_REFINE=1            the Rayleigh-Ritz refinement of all pairs, whatever the sample check would say
+//   BIGKRLS_KRY_SAMPLE              the sample check against K also where the caller verifies (A/B timing)
+struct KrySwitches {
+  static bool is(const char* name, const char* value) { const char* e = getenv(name); return e && std::string(e) == value; }
+  const char* first_check = getenv("BIGKRLS_KRY_FIRST_CHECK");
+  const char* cgs = getenv("BIGKRLS_KRY_CGS");
+  bool cgs_full = cgs && cgs[0] == '2', refine = is("BIGKRLS_KRY_REFINE", "1");
+  bool pivots = getenv("BIGKRLS_KRY_PIVOTS"), no_estimate = getenv("BIGKRLS_KRY_NOEST");
+  bool check_every = getenv("BIGKRLS_KRY_CHECK_EVERY"), sample = getenv("BIGKRLS_KRY_SAMPLE");
+};
+
+struct BlockLanczos : KryArgs {
+  static constexpr int b = 128;
+  static constexpr double tol = 1e-10;
+  const hipStream_t st = ctx->stream;
+  bigkrls_comm* const comm = kop.comm;
   const int64_t maxdim = std::min<int64_t>(n / 2 / b * b, std::max<int64_t>(16 * k, 4096) / b * b);
   const int maxsteps = (int)(maxdim / b);
-  void *pB = nullptr, *pW = nullptr, *pC = nullptr, *pC2 = nullptr;
-  {
-    int rc = ws_get(ctx, SLOT_KRY_B, n * maxdim * sizeof(double), &pB);
-    if (rc == BIGKRLS_OK) rc = ws_get(ctx, SLOT_KRY_W, 2 * n * (int64_t)std::max<int64_t>(b, k) * sizeof(double), &pW);
-    if (rc == BIGKRLS_OK)
-      rc = ws_get(ctx, SLOT_KRY_C, (maxdim * b + 5 * b * b + 8 + k * k + 2 * k + 2 * (int64_t)maxsteps * b * b + k + b * k) *
-                                       sizeof(double), &pC);
-    if (rc == BIGKRLS_OK && kop.comm)   // the staging of the per-step all-gather, before the first one is entered
-      rc = ws_get(ctx, SLOT_COMM_STAGE, (int64_t)(kop.comm->nranks + 1) * kop.nb * std::max<int64_t>(b, k) * sizeof(double), &pC2);
-    BK_TRY(kry_agree_status(kop, rc));
-  }
-  double* B = (double*)pB;
-  double* W = (double*)pW;
-  double* W2 = W + n * std::max<int64_t>(b, k);
   // this rank's rows of every n-row array (see k_times); one GPU: all of them
-  bigkrls_comm* const comm = kop.comm;
   const int64_t ro = comm ? kop.r0 : 0, nr = comm ? kop.r1 - kop.r0 : n;
+  KrySwitches sw;
+  // ---- workspace (carve_workspace): the basis, the new block and its scratch, and the sub-arrays of SLOT_KRY_C:
+  // C: coefficients of a Gram-Schmidt pass (up to maxdim x b). dG: Cholesky-QR scratch: Gram / inverse, R1, R2, R2 R1,
+  // flag. dH, dvalsH: the k x k problem of the refinement and its values (2k). dAall, dBall: diagonal blocks A_j and
+  // sub-diagonal factors beta_{j+1} of the projected matrix stay on the device. dPrev: [theta (k) | C (b x k)] of the
+  // last full check (for the estimate).
+  double *B = nullptr, *W = nullptr, *W2 = nullptr;
+  double *C = nullptr, *dG = nullptr, *dH = nullptr, *dvalsH = nullptr, *dAall = nullptr, *dBall = nullptr, *dPrev = nullptr;
+  void* pY = nullptr;              // eigenvectors of the last projected problem (SLOT_KRY_Y)
+  const double* dvalsT = nullptr;  // Ritz values of the last full check (device: behind T in SLOT_KRY_T)
+  // ---- the iteration
+  int steps = 0;
+  int64_t dim = b;
+  int64_t ke = auto_rank ? std::min<int64_t>(k, b) : k;   // the effective rank (see above); in a fixed run ke == k throughout
+  std::vector<double> theta;       // Ritz values of the last full check (descending)
+  std::vector<double> th, Ylast;   // of the last projected problem solved: its values, the last b rows of its vectors (b x k)
+  std::vector<double> Rtmp;        // beta of the last step (host copy, for the Ritz residuals)
+  // piv: smallest / largest pivot and trace of the Gram matrix W'W, first and second pass of the Cholesky QR (the
+  // same on every rank: the Gram matrices are all-reduced)
+  double piv[6] = {0, 0, 0, 0, 0, 0};
+  double wnorm_sq = 0.0;           // |W|_F^2 of the block the last step produced (before its QR)
+  double wmax_seen = 0.0;          // the largest direction any new block had (square root of the largest Gram pivot)
+  double dropped = 0.0;            // |W|_F of the blocks replaced by random ones: what every residual estimate misses
+  bool breakdown = false, converged = false;
+  int n_checks = 0;
+  // ---- the schedule of the checks: each check is a dense eigensolve of T (latency-bound, ~12 us per row of T); the
+  // first one comes at a subspace of 5k columns, or of 2.5k where a step costs more than such a check (sizes only: the
+  // schedule, and with it the result, must not depend on timing)
+  const double step_s_est = 2.0 * (double)n * (double)n * b / 50e12;
+  bool check_is_cheap = 12e-6 * 4.0 * (double)(auto_rank ? (int64_t)b : k) < step_s_est;   // (auto rank: follows k_eff)
+  int next_check = 0;
+  int full_steps = 0;              // steps of the last full check (0: none yet)
+  bool next_is_estimate = false;   // the next check decomposes the compressed projected problem (see estimate_check)
+  bool early_check_done = false;   // the check ahead of the schedule on a (numerically) invariant Krylov space, see schedule_early_check
+  // ---- after convergence
+  bool refine = false;
+  const double* dvals_final = nullptr;
+  void* pZ = nullptr;
+  std::vector<double> hv;          // the values that are returned (host): Ritz values of T, descending, or the refined ones
+  std::string diag;                // what the iteration did at its convergence checks (for the error text)
+
+  explicit BlockLanczos(const KryArgs& a) : KryArgs(a) {}
+
+  // ---- shared pieces --------------------------------------------------------------------------------
   // C (rows x cols, ld rows) = sum over the ranks of  Xloc' Yloc  (X: n x rows, Y: n x cols, ld n)
-  auto gram = [&](const double* X, int64_t rows, const double* Y, int64_t cols, double* Cout) -> int {
+  int gram(const double* X, int64_t rows, const double* Y, int64_t cols, double* Cout) {
     if (nr > 0) BK_TRY(gemm(ctx, 1, 0, rows, cols, nr, 1.0, X + ro, n, Y + ro, n, 0.0, Cout, rows));
     else BK_HIP(hipMemsetAsync(Cout, 0, (size_t)(rows * cols) * sizeof(double), st));
     if (comm) BK_TRY(comm_all_reduce(comm, Cout, rows * cols, COMM_SUM));
     return BIGKRLS_OK;
-  };
-  double* C = (double*)pC;
-  double* dG = C + maxdim * b;            // Cholesky-QR scratch: Gram / inverse, R1, R2, R2 R1, flag
-  double* dA = dG + 4 * b * b + 8;
-  // diagonal blocks A_j and sub-diagonal factors beta_{j+1} of the projected matrix stay on the device
-  double* dAall = dA + b * b + k * k + 2 * k;
-  double* dBall = dAall + (int64_t)maxsteps * b * b;
-  double* dPrev = dBall + (int64_t)maxsteps * b * b;   // [theta (k) | C (b x k)] of the last full check (for the estimate)
-  std::vector<double> Rtmp;                        // beta of the last step (host copy, for the Ritz residuals)
-  bool breakdown = false;
-  // ---- B_0 ----------------------------------------------------------------------------------
-  BK_TRY(fill_random(ctx, W, n * b, 20240229u));
-  BK_TRY(kry_cholqr(ctx, &W, &W2, n, b, dG, Rtmp, &breakdown, nullptr, comm, ro, nr));
-  {
-    double okv = breakdown ? 0.0 : 1.0;
-    BK_TRY(kry_agree_min(kop, &okv, 1));
-    breakdown = !(okv > 0.5);
   }
-  BK_REQUIRE(!breakdown, "eigen (Krylov): start block is rank deficient");
-  BK_HIP(hipMemcpyAsync(B, W, n * b * sizeof(double), hipMemcpyDeviceToDevice, st));
-  int steps = 0;
-  int64_t dim = b;
-  std::vector<double> theta;       // Ritz values of the last full check (descending)
-  double wnorm_sq = 0.0;           // |W|_F^2 of the block the last step produced (before its QR)
-  double wmax_seen = 0.0;          // the largest direction any new block had (square root of the largest Gram pivot)
-  bool early_check_done = false;   // the check ahead of the schedule on a (numerically) invariant Krylov space, see below
-  double dropped = 0.0;            // |W|_F of the blocks replaced by random ones: what every residual estimate misses
-  int full_steps = 0;              // steps of the last full check (0: none yet)
-  bool next_is_estimate = false;   // the next check decomposes the compressed projected problem (see below)
-  void* pY = nullptr;
-  bool converged = false;
-  // each check is a dense eigensolve of T (latency-bound, ~12 us per row of T); the first one comes at a
-  // subspace of 5k columns, or of 2.5k where a step costs more than such a check (sizes only: the schedule, and
-  // with it the result, must not depend on timing)
-  const double step_s_est = 2.0 * (double)n * (double)n * b / 50e12;
-  bool check_is_cheap = 12e-6 * 4.0 * (double)(auto_rank ? (int64_t)b : k) < step_s_est;   // (auto rank: follows k_eff)
-  // (C4: the pairs converge at step 27, C5 at step 23; a first check at 4k / 2k columns -- step 16 in both -- sits on the
-  //  plateau of the worst residual and only costs a dense eigensolve of T: 5k / 2.5k columns, step 20, leaves three
-  //  checks at C4 (20, 25, 27) and two at C5 (20, 23) instead of four and three)
-  int next_check = (int)std::max<int64_t>(2, ((check_is_cheap ? 5 : 10) * (auto_rank ? (int64_t)b : k) / 2 + b - 1) / b);
-  if (const char* fc = getenv("BIGKRLS_KRY_FIRST_CHECK")) next_check = std::max(2, atoi(fc));   // (development)
-  while (true) {
-    // ---- one block Lanczos step: W = K B_j, orthogonalised against every block so far (CGS2) ---
+
+  // One Gram-Schmidt pass of the new block against the columns c0 ... dim of the basis: C = B' W, W -= B C (multi-GPU:
+  // local rows + one all-reduce of (dim - c0) x 128). Aj: where the pass keeps the rows of C that belong to block `steps`.
+  int project_out(int64_t c0, double* Aj = nullptr) {
+    const int64_t dimp = dim - c0;
+    BK_TRY(gram(B + c0 * n, dimp, W, b, C));
+    if (Aj) BK_TRY(copy_matrix(ctx, C + ((int64_t)steps * b - c0), b, b, dimp, Aj, b));
+    if (nr > 0) BK_TRY(gemm(ctx, 0, 0, nr, b, dimp, -1.0, B + c0 * n + ro, n, C, dimp, 1.0, W + ro, n));
+    return BIGKRLS_OK;
+  }
+
+  // control decisions on values agreed by all ranks (kry_agree_min): a breakdown anywhere is a breakdown everywhere
+  int agree_breakdown(bool& bd) {
+    double okv = bd ? 0.0 : 1.0;
+    BK_TRY(kry_agree_min(kop, &okv, 1));
+    bd = !(okv > 0.5);
+    return BIGKRLS_OK;
+  }
+
+  int agree_worst(double& worst, double& theta1) {
+    double ag[2] = {-worst, theta1};     // the largest residual and the smallest theta_1 over the ranks
+    BK_TRY(kry_agree_min(kop, ag, 2));
+    worst = -ag[0];
+    theta1 = ag[1];
+    return BIGKRLS_OK;
+  }
+
+  // room for a projected problem of mm rows: T (mm x mm) with its values behind it, and its k eigenvectors (pY)
+  struct Projected { double *dT, *dvalsT; };
+  int projected_workspace(int64_t mm, Projected* p) {
+    void* pT = nullptr;
+    int rc = ws_get(ctx, SLOT_KRY_T, (mm * mm + mm) * sizeof(double), &pT);
+    if (rc == BIGKRLS_OK) rc = ws_get(ctx, SLOT_KRY_Y, mm * k * sizeof(double), &pY);
+    BK_TRY(kry_agree_status(kop, rc));
+    p->dT = (double*)pT;
+    p->dvalsT = p->dT + mm * mm;
+    return BIGKRLS_OK;
+  }
+
+  // out (b) = beta x (b): beta = T[steps, steps - 1] (upper triangular) couples the last block to the next one
+  void beta_times(const double* x, double* out) const {
+    const std::vector<double>& beta = Rtmp;
+    for (int rr = 0; rr < b; ++rr) {
+      double sacc = 0.0;
+      for (int c = rr; c < b; ++c) sacc += beta[rr + (size_t)c * b] * x[c];
+      out[rr] = sacc;
+    }
+  }
+
+  // one entry of diag per check
+  void note(const char* kind, double worst, double theta0, const char* tail) {
+    char buf[160];
+    snprintf(buf, sizeof buf, " [%s steps=%d worst=%.3e theta0=%.6e%s]", kind, steps, worst, theta0, tail);
+    diag += buf;
+  }
+
+  // ---- workspace: the slots, and every sub-array of SLOT_KRY_C from the one list of extents that also gives its size
+  int carve_workspace() {
+    struct Part { double** at; int64_t doubles; };
+    const Part parts[] = {{&C, maxdim * b}, {&dG, 4 * b * b + 8},
+                          {nullptr, b * b},        // (a b x b block nothing reads any more: the slot keeps its size and offsets)
+                          {&dH, k * k}, {&dvalsH, 2 * k},
+                          {&dAall, (int64_t)maxsteps * b * b}, {&dBall, (int64_t)maxsteps * b * b}, {&dPrev, k + b * k}};
+    int64_t total = 0;
+    for (const Part& p : parts) total += p.doubles;
+    void *pB = nullptr, *pW = nullptr, *pC = nullptr, *pC2 = nullptr;
+    int rc = ws_get(ctx, SLOT_KRY_B, n * maxdim * sizeof(double), &pB);
+    if (rc == BIGKRLS_OK) rc = ws_get(ctx, SLOT_KRY_W, 2 * n * (int64_t)std::max<int64_t>(b, k) * sizeof(double), &pW);
+    if (rc == BIGKRLS_OK) rc = ws_get(ctx, SLOT_KRY_C, total * sizeof(double), &pC);
+    if (rc == BIGKRLS_OK && comm)   // the staging of the per-step all-gather, before the first one is entered
+      rc = ws_get(ctx, SLOT_COMM_STAGE, (int64_t)(comm->nranks + 1) * kop.nb * std::max<int64_t>(b, k) * sizeof(double), &pC2);
+    BK_TRY(kry_agree_status(kop, rc));
+    B = (double*)pB;
+    W = (double*)pW;
+    W2 = W + n * std::max<int64_t>(b, k);
+    double* at = (double*)pC;
+    for (const Part& p : parts) {
+      if (p.at) *p.at = at;
+      at += p.doubles;
+    }
+    return BIGKRLS_OK;
+  }
+
+  // ---- B_0 ----------------------------------------------------------------------------------
+  int start_block() {
+    BK_TRY(fill_random(ctx, W, n * b, 20240229u));
+    BK_TRY(kry_cholqr(ctx, &W, &W2, n, b, dG, Rtmp, &breakdown, nullptr, comm, ro, nr));
+    BK_TRY(agree_breakdown(breakdown));
+    BK_REQUIRE(!breakdown, "eigen (Krylov): start block is rank deficient");
+    BK_HIP(hipMemcpyAsync(B, W, n * b * sizeof(double), hipMemcpyDeviceToDevice, st));
+    // (C4: the pairs converge at step 27, C5 at step 23; a first check at 4k / 2k columns -- step 16 in both -- sits on the
+    //  plateau of the worst residual and only costs a dense eigensolve of T: 5k / 2.5k columns, step 20, leaves three
+    //  checks at C4 (20, 25, 27) and two at C5 (20, 23) instead of four and three)
+    next_check = (int)std::max<int64_t>(2, ((check_is_cheap ? 5 : 10) * (auto_rank ? (int64_t)b : k) / 2 + b - 1) / b);
+    if (sw.first_check) next_check = std::max(2, atoi(sw.first_check));   // (development)
+    return BIGKRLS_OK;
+  }
+
+  // ---- one block Lanczos step: W = K B_j, orthogonalised against every block so far (CGS2) ---
+  int step() {
     double* Bj = B + (int64_t)steps * b * n;
     // (bench.py: HIP-event sampling of the step's dominant product, 2 n^2 b flops, every launch)
     if (ctx->profile) BK_TRY(prof_begin(ctx, "lanczos_kb", 2.0 * (double)n * (double)n * b));
@@ -2335,348 +2448,324 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
     // first pass runs against the last two blocks only (256 of the dim columns), the second against all of them
     // -- 4 n (dim + 256) b flops per step instead of 8 n dim b. BIGKRLS_KRY_CGS=2 (development): both passes against
     // every block, as until round 6.
-    static const bool cgs_full = [] { const char* e = getenv("BIGKRLS_KRY_CGS"); return e && e[0] == '2'; }();
-    const int64_t loc0 = cgs_full ? 0 : (int64_t)std::max(0, steps - 1) * b;     // first column of the first pass
+    const int64_t loc0 = sw.cgs_full ? 0 : (int64_t)std::max(0, steps - 1) * b;     // first column of the first pass
     if (ctx->profile) BK_TRY(prof_begin(ctx, "lanczos_cgs2", 4.0 * (double)n * (double)(2 * dim - loc0) * b));
-    for (int pass = 0; pass < 2; ++pass) {
-      const int64_t c0 = pass == 0 ? loc0 : 0, dimp = dim - c0;
-      BK_TRY(gram(B + c0 * n, dimp, W, b, C));             // (multi-GPU: local rows + one all-reduce of dimp x 128)
-      if (pass == 0)   // A_j = B_j' K B_j: the last b rows of the first coefficient block
-        BK_TRY(copy_matrix(ctx, C + ((int64_t)steps * b - c0), b, b, dimp, dAall + (int64_t)steps * b * b, b));
-      if (nr > 0) BK_TRY(gemm(ctx, 0, 0, nr, b, dimp, -1.0, B + c0 * n + ro, n, C, dimp, 1.0, W + ro, n));
-    }
+    // A_j = B_j' K B_j: the last b rows of the first coefficient block, which that pass alone keeps
+    BK_TRY(project_out(loc0, dAall + (int64_t)steps * b * b));
+    BK_TRY(project_out(0));
     if (ctx->profile) BK_TRY(prof_end(ctx, "lanczos_cgs2"));
-    // piv: smallest / largest pivot and trace of the Gram matrix W'W, first and second pass of the Cholesky QR (the
-    // same on every rank: the Gram matrices are all-reduced)
-    double piv[6] = {0, 0, 0, 0, 0, 0};
+    std::fill(piv, piv + 6, 0.0);
     BK_TRY(kry_cholqr(ctx, &W, &W2, n, b, dG, Rtmp, &breakdown, dBall + (int64_t)steps * b * b, comm, ro, nr, piv));   // synchronises the stream
-    if (getenv("BIGKRLS_KRY_PIVOTS"))    // (development: how well conditioned the new block was)
+    if (sw.pivots)    // (development: how well conditioned the new block was)
       fprintf(stderr, "[bigkrls] block Lanczos step %d: Gram pivots %.3e ... %.3e (ratio %.1e), second pass %.3e ... %.3e%s\n", steps,
               piv[0], piv[1], piv[1] > 0 ? piv[0] / piv[1] : 0.0, piv[3], piv[4], breakdown ? "  BREAKDOWN" : "");
     wnorm_sq = piv[2];
-    // An ill-conditioned new block (cond(W) ~ sqrt(largest / smallest pivot) above 1e4): W was orthogonal to the
-    // earlier blocks to eps |W|, but its smallest directions were scaled up by the QR, and with them what they had
-    // left along the earlier blocks -- eps cond(W). One more Gram-Schmidt pass of the (now orthonormal) block
-    // against all blocks and one more Cholesky QR; beta takes the third factor. What the pass removes from the block
-    // recurrence is of the size of the rounding of W itself. (Numerically low-rank kernels: P = 2, 3.)
-    if (!breakdown && piv[1] > 0.0 && piv[0] < 1e-8 * piv[1]) {
-      BK_TRY(gram(B, dim, W, b, C));
-      if (nr > 0) BK_TRY(gemm(ctx, 0, 0, nr, b, dim, -1.0, B + ro, n, C, dim, 1.0, W + ro, n));
-      std::vector<double> R3, prev(Rtmp);
-      bool bd3 = false;
-      BK_TRY(kry_cholqr(ctx, &W, &W2, n, b, dG, R3, &bd3, nullptr, comm, ro, nr));
-      if (bd3) {
-        breakdown = true;
-      } else {
-        for (int c = 0; c < b; ++c)          // beta = R3 beta (both upper triangular)
-          for (int r = 0; r <= c; ++r) {
-            double acc = 0.0;
-            for (int t = r; t <= c; ++t) acc += R3[r + (size_t)t * b] * prev[t + (size_t)c * b];
-            Rtmp[r + (size_t)c * b] = acc;
-          }
-        double* hp = nullptr;
-        BK_TRY(pinned_get(ctx, (int64_t)b * b, &hp));
-        std::memcpy(hp, Rtmp.data(), (size_t)b * b * sizeof(double));
-        BK_HIP(hipMemcpyAsync(dBall + (int64_t)steps * b * b, hp, (size_t)b * b * sizeof(double), hipMemcpyHostToDevice, st));
-        BK_HIP(hipStreamSynchronize(st));
-        if (verbose()) fprintf(stderr, "[bigkrls] block Lanczos step %d: ill-conditioned block (pivot ratio %.1e) re-orthogonalised\n", steps, piv[0] / piv[1]);
-      }
-    }
-    // The Krylov space is invariant to working precision when the new block is nothing but rounding: its largest
-    // direction a millionth of the largest one any block had. Going on would normalise noise into unit vectors for
-    // step after step until a pivot turns negative (P = 2: ten such steps before the first scheduled check); the
-    // check comes now instead, as soon as the subspace has k columns, and decides with the true residuals.
-    // ... and while it has fewer than k columns (Neig above the numerical rank of K), the block that is nothing but
-    // rounding is REPLACED by a fresh random block orthogonalised against all blocks so far (what ARPACK does on an
-    // invariant subspace): normalising the rounding instead works for a few steps, then the noise -- amplified by K
-    // from step to step -- turns ill-conditioned and a pivot negative, short of k columns. The replaced W is what the
-    // block recurrence loses: only a block below 1e-10 of the largest direction seen -- below the tolerance times
-    // lambda_1, since no direction of a W exceeds lambda_1 -- is replaced, and its norm enters every later residual.
-    // beta of this step is zero (the new block is not coupled to the old ones).
-    {
-      const double wfro = std::sqrt(std::max(wnorm_sq, 0.0));
-      if (wmax_seen > 0.0 && wfro <= 1e-10 * wmax_seen && (int64_t)(steps + 1) * b < ke && steps + 1 < maxsteps) {
-        BK_TRY(fill_random(ctx, W, n * b, 20240229u + 7919u * (uint32_t)(steps + 1)));
-        for (int pass = 0; pass < 2; ++pass) {
-          BK_TRY(gram(B, dim, W, b, C));
-          if (nr > 0) BK_TRY(gemm(ctx, 0, 0, nr, b, dim, -1.0, B + ro, n, C, dim, 1.0, W + ro, n));
-        }
-        std::vector<double> Rr;
-        bool bdr = false;
-        BK_TRY(kry_cholqr(ctx, &W, &W2, n, b, dG, Rr, &bdr, nullptr, comm, ro, nr));
-        {
-          double okv = bdr ? 0.0 : 1.0;
-          BK_TRY(kry_agree_min(kop, &okv, 1));
-          bdr = !(okv > 0.5);
-        }
-        if (!bdr) {
-          breakdown = false;
-          dropped += wfro;                 // (a bound for what all the replaced blocks together took from the recurrence)
-          std::fill(Rtmp.begin(), Rtmp.end(), 0.0);
-          BK_HIP(hipMemsetAsync(dBall + (int64_t)steps * b * b, 0, (size_t)b * b * sizeof(double), st));
-          piv[1] = 0.0;       // (nothing of this step counts as a direction of a Krylov block)
-          if (verbose())
-            fprintf(stderr, "[bigkrls] block Lanczos step %d: invariant subspace of %lld columns (|W| = %.1e): continued with a random block\n",
-                    steps, (long long)((steps + 1) * b), wfro);
-        }
-      }
-    }
-    {
-      const double wmax = std::sqrt(std::max(piv[1], 0.0));
-      if (!breakdown && !early_check_done && wmax <= 1e-6 * wmax_seen && (int64_t)(steps + 1) * b >= ke) {
-        next_check = std::min(next_check, steps + 1);      // (once: the checks after it follow their own forecasts)
-        early_check_done = true;
-      }
-      wmax_seen = std::max(wmax_seen, wmax);
-    }
-    ++steps;
-    {
-      double okv = breakdown ? 0.0 : 1.0;
-      BK_TRY(kry_agree_min(kop, &okv, 1));
-      breakdown = !(okv > 0.5);
-    }
-    const bool last = breakdown || steps >= maxsteps;
-    // ---- convergence check on the projected problem ---------------------------------------------
-    if (last || steps >= next_check) {
-      const int64_t m = (int64_t)steps * b;
-      const std::vector<double>& beta = Rtmp;       // T[steps, steps - 1]: couples the last block to the next one
-      // residuals |beta y_i[last block]| of the first k Ritz pairs of a projected problem whose eigenvectors end in the
-      // b rows ylast (b x k, host)
-      struct Resid { double worst = 0.0, worst_kept = 0.0, first = 0.0; int64_t n_conv = 0; };
-      auto residuals = [&](const double* th, const double* ylast) {
-        Resid r;
-        if (breakdown) {
-          // the factor beta of the last block does not exist (its Gram matrix is not positive definite): every
-          // residual |W y| is bounded by |W|_F -- zero to working precision when the Krylov space is invariant, which
-          // is the breakdown that means convergence; anything else is reported as not converged (dense path)
-          r.worst = r.worst_kept = std::sqrt(std::max(wnorm_sq, 0.0));
-          return r;
-        }
-        for (int64_t i = 0; i < ke; ++i) {
-          double r2 = 0.0;
-          for (int rr = 0; rr < b; ++rr) {
-            double sacc = 0.0;
-            for (int c = rr; c < b; ++c) sacc += beta[rr + (size_t)c * b] * ylast[c + (size_t)i * b];
-            r2 += sacc * sacc;
-          }
-          if (i == 0) r.first = std::sqrt(r2);
-          r.worst = std::max(r.worst, std::sqrt(r2));
-          if (std::sqrt(r2) <= tol * std::fabs(th[0])) ++r.n_conv;
-          if (keep_thresh >= 0.0 && th[i] >= keep_thresh * th[0]) r.worst_kept = std::max(r.worst_kept, std::sqrt(r2));
-        }
-        r.worst = std::max(r.worst, dropped);      // (blocks replaced by random ones, see the step loop)
-        return r;
-      };
-      // the m x m projected matrix (estimate == false), or the compressed one of the estimate (below), is decomposed by the
-      // dense path; theta (mm values) and the last b rows of Y come down through the context's pinned buffer
-      std::vector<double> Ylast((size_t)b * k), th;
-      auto solve_projected = [&](double* dT, int64_t mm, double* dvalsT) -> int {
-        int64_t nvY = 0;
-        // (auto rank: the subspace of an early check can be narrower than the cap -- as many vectors as there are)
-        const int64_t kv = auto_rank ? std::min<int64_t>(k, mm) : k;
-        // (replicated, but after a fault one rank's copy may fail where its peers' do not: agreed, so nobody leaves alone)
-        BK_TRY(kry_agree_status(kop, eigen(ctx, dT, mm, mm, mm, dvalsT, kv, -1.0, (double*)pY, mm, &nvY, 0, 1, EIG_FULL)));
-        double* hp = nullptr;
-        BK_TRY(pinned_get(ctx, mm + (int64_t)b * k, &hp));
-        BK_HIP(hipMemcpyAsync(hp, dvalsT, mm * sizeof(double), hipMemcpyDeviceToHost, st));
-        BK_HIP(hipMemcpy2DAsync(hp + mm, b * sizeof(double), (double*)pY + (mm - b), mm * sizeof(double),
-                                b * sizeof(double), kv, hipMemcpyDeviceToHost, st));
-        BK_HIP(hipStreamSynchronize(st));
-        th.assign(hp, hp + mm);
-        std::memcpy(Ylast.data(), hp + mm, (size_t)b * kv * sizeof(double));
-        return BIGKRLS_OK;
-      };
-      auto agree_worst = [&](double& worst, double& theta1) -> int {
-        double ag[2] = {-worst, theta1};     // the largest residual and the smallest theta_1 over the ranks
-        BK_TRY(kry_agree_min(kop, ag, 2));
-        worst = -ag[0];
-        theta1 = ag[1];
-        return BIGKRLS_OK;
-      };
-      // Next check. The history of the worst residual is a plateau (O(1) while the subspace does not reach the
-      // k-th eigenvalue yet) followed by a collapse at a steady x25 - x45 per step (measured: N = 100 000,
-      // k = 1024: 2.6e-2, 6.0e-4, 1.4e-5, 3.1e-7; N = 50 000, k = 512: 6.0e-4, 3.5e-5, 1.4e-6, 6.1e-8), so a rate
-      // fitted to two plateau samples overshoots by many steps. The distance to the tolerance at an assumed
-      // collapse rate is used instead: an optimistic rate where a check (a dense eigensolve of T, ~12 us per
-      // row) is cheaper than a step (2 n^2 b flops), so undershooting costs little, a cautious one otherwise.
-      auto steps_to_go = [&](double worst, double theta1) {
-        const double gain = check_is_cheap ? 40.0 : 15.0;
-        int inc = (worst > 0.0) ? (int)std::ceil(std::log(worst / (tol * theta1)) / std::log(gain)) : 1;
-        return std::max(1, std::min(inc, std::max(2, steps / 2)));
-      };
-      // ---- an ESTIMATE instead of the full check (round 6): where the last full check (at full_steps) put the end of
-      // the iteration four or more steps away -- a forecast made from the plateau, which the check at its end only
-      // ever corrected (C4: 20 -> 25 -> 27) -- the check at that point decomposes the COMPRESSED projected problem:
-      // the k Ritz vectors of the last full check plus the blocks since, dimension k + 128 d instead of 128 steps
-      // (C4, step 25: 1 152 instead of 3 200). The Lanczos relation holds exactly for that basis, so its residuals are
-      // true residuals and track the full check's within a factor of two; the directions dropped at the compression
-      // never come back, so it cannot replace the full check (its converged set can miss wanted eigenvalues,
-      // tools/experiments/DEAD_ENDS.md): it only says where the next FULL check goes, and a full check follows at
-      // once should it report convergence.
-      if (m < ke) {     // (a breakdown before the subspace had k columns: nothing to decompose -- the dense path)
-        dim = m;
-        break;
-      }
-      bool full = true;
-      const int64_t mc = k + (int64_t)(steps - full_steps) * b;
-      if (!auto_rank && next_is_estimate && !last && full_steps > 0 && 2 * mc <= m && !getenv("BIGKRLS_KRY_NOEST")) {
-        void* pT = nullptr;
-        {
-          int rc = ws_get(ctx, SLOT_KRY_T, (mc * mc + mc) * sizeof(double), &pT);
-          if (rc == BIGKRLS_OK) rc = ws_get(ctx, SLOT_KRY_Y, mc * k * sizeof(double), &pY);
-          BK_TRY(kry_agree_status(kop, rc));
-        }
-        double* dT = (double*)pT;
-        hipLaunchKernelGGL(kry_assemble_compressed, dim3((unsigned)std::min<int64_t>((mc * mc + 255) / 256, 8192)), dim3(256), 0,
-                           st, (const double*)dPrev, (const double*)(dPrev + k), (int)k, (const double*)dAall,
-                           (const double*)dBall, full_steps, steps, b, dT);
-        BK_CHECK_LAUNCH();
-        BK_TRY(solve_projected(dT, mc, dT + mc * mc));
-        Resid r = residuals(th.data(), Ylast.data());
-        double worst = r.worst, theta1 = std::fabs(th[0]);
-        BK_TRY(agree_worst(worst, theta1));
-        if (verbose())
-          fprintf(stderr, "[bigkrls] block Lanczos estimate: steps=%d (compressed from %d: %lld instead of %lld) worst=%.3e converged=%lld of %lld theta0=%.4e\n",
-                  steps, full_steps, (long long)mc, (long long)m, worst, (long long)r.n_conv, (long long)k, th[0]);
-        {
-          char buf[160];
-          snprintf(buf, sizeof buf, " [estimate steps=%d worst=%.3e theta0=%.6e]", steps, worst, th[0]);
-          kry_diag += buf;
-        }
-        next_is_estimate = false;            // (what follows an estimate is a full check)
-        if (!(worst <= tol * theta1)) {
-          full = false;
-          next_check = steps + steps_to_go(worst, theta1);
-        }
-      }
-      if (full) {
-        void *pT = nullptr;
-        {
-          int rc = ws_get(ctx, SLOT_KRY_T, (m * m + m) * sizeof(double), &pT);
-          if (rc == BIGKRLS_OK) rc = ws_get(ctx, SLOT_KRY_Y, m * k * sizeof(double), &pY);
-          BK_TRY(kry_agree_status(kop, rc));
-        }
-        double* dT = (double*)pT;
-        double* dvalsT = dT + m * m;
-        hipLaunchKernelGGL(kry_assemble_t, dim3((unsigned)std::min<int64_t>((m * m + 255) / 256, 8192)), dim3(256), 0, st,
-                           (const double*)dAall, (const double*)dBall, steps, b, dT);
-        BK_CHECK_LAUNCH();
-        BK_TRY(solve_projected(dT, m, dvalsT));
-        theta = th;
-        ++n_checks;
-        // auto rank: the rank this check asks for. need > cap: the residuals below are those of the first `cap` pairs
-        // (theta_1's among them: the cap error waits for it); need > m: the subspace is still too narrow.
-        int64_t need = 0;
-        if (auto_rank) {
-          int64_t c = 0;
-          while (c < m && theta[c] >= keep_thresh * theta[0]) ++c;
-          need = c + 1;
-          ke = std::min<int64_t>(std::min<int64_t>(need, k), m);
-          check_is_cheap = 12e-6 * 4.0 * (double)ke < step_s_est;
-        }
-        Resid r = residuals(theta.data(), Ylast.data());
-        double worst = r.worst, theta1 = std::fabs(theta[0]);
-        BK_TRY(agree_worst(worst, theta1));
-        if (auto_rank && need > k && !breakdown && std::max(r.first, dropped) <= tol * theta1) {
-          char buf[320];
-          snprintf(buf, sizeof buf, "eigen (Krylov, auto rank): more than kcap = %lld eigenvalues reach the threshold: theta_kcap / theta_1 = %.3e "
-                                    "is still above keep_thresh = %.3e (raise the cap, or give the rank)", (long long)k,
-                   theta[k - 1] / theta[0], keep_thresh);
-          set_error(buf);
-          return BIGKRLS_EINVAL;
-        }
-        if (auto_rank && need > ke) worst = std::max(worst, 2.0 * tol * theta1);   // (not converged whatever the first ke pairs say)
-        if (verbose())
-          fprintf(stderr, "[bigkrls] block Lanczos check: steps=%d worst=%.3e worst(kept)=%.3e converged=%lld of %lld theta0=%.4e\n",
-                  steps, worst, r.worst_kept, (long long)r.n_conv, (long long)k, theta[0]);
-        {
-          char buf[160];
-          snprintf(buf, sizeof buf, " [check steps=%d worst=%.3e theta0=%.6e breakdown=%d]", steps, worst, theta[0], (int)breakdown);
-          kry_diag += buf;
-        }
-        if (worst <= tol * theta1 || last) {
-          converged = worst <= tol * theta1;
-          dim = m;
-          break;
-        }
-        int inc = steps_to_go(worst, theta1);
-        if (auto_rank && need > m) inc = std::max<int>(inc, (int)((std::min<int64_t>(need, k) - m + b - 1) / b));   // (columns first)
-        next_check = steps + inc;
-        // what the estimate at next_check needs of this check: the k Ritz values and C = beta Y[last block rows, :]
-        // (b x k), the coupling of the Ritz vectors to the next block -- kept on the device behind the blocks of T
-        next_is_estimate = inc >= 4 && !auto_rank;
-        full_steps = steps;
-        if (next_is_estimate) {
-          double* hp = nullptr;
-          BK_TRY(pinned_get(ctx, k + (int64_t)b * k, &hp));
-          for (int64_t i = 0; i < k; ++i) hp[i] = theta[i];
-          for (int64_t i = 0; i < k; ++i)
-            for (int rr = 0; rr < b; ++rr) {
-              double sacc = 0.0;
-              for (int c = rr; c < b; ++c) sacc += beta[rr + (size_t)c * b] * Ylast[c + (size_t)i * b];
-              hp[k + rr + i * b] = sacc;
-            }
-          BK_HIP(hipMemcpyAsync(dPrev, hp, (size_t)(k + (int64_t)b * k) * sizeof(double), hipMemcpyHostToDevice, st));
-          BK_HIP(hipStreamSynchronize(st));     // (the pinned buffer is the eigensolver's as well)
-        }
-      }
-      if (getenv("BIGKRLS_KRY_CHECK_EVERY")) { next_check = steps + 1; next_is_estimate = false; }   // (development: the convergence history)
-    }
-    BK_HIP(hipMemcpyAsync(B + (int64_t)steps * b * n, W, n * b * sizeof(double), hipMemcpyDeviceToDevice, st));
-    dim = (int64_t)(steps + 1) * b;
+    return BIGKRLS_OK;
   }
-  if (verbose()) fprintf(stderr, "[bigkrls] block Lanczos: n=%lld k=%lld steps=%d dim=%lld converged=%d\n", (long long)n, (long long)k, steps, (long long)dim, (int)converged);
-  if (verbose() && auto_rank) fprintf(stderr, "[bigkrls] block Lanczos (auto rank): cap=%lld rank=%lld checks=%d\n", (long long)k, (long long)ke, n_checks);
+
+  // An ill-conditioned new block (cond(W) ~ sqrt(largest / smallest pivot) above 1e4): W was orthogonal to the
+  // earlier blocks to eps |W|, but its smallest directions were scaled up by the QR, and with them what they had
+  // left along the earlier blocks -- eps cond(W). One more Gram-Schmidt pass of the (now orthonormal) block
+  // against all blocks and one more Cholesky QR; beta takes the third factor. What the pass removes from the block
+  // recurrence is of the size of the rounding of W itself. (Numerically low-rank kernels: P = 2, 3.)
+  int reorthogonalise_ill_conditioned() {
+    if (!(!breakdown && piv[1] > 0.0 && piv[0] < 1e-8 * piv[1])) return BIGKRLS_OK;
+    BK_TRY(project_out(0));
+    std::vector<double> R3, prev(Rtmp);
+    bool bd3 = false;
+    BK_TRY(kry_cholqr(ctx, &W, &W2, n, b, dG, R3, &bd3, nullptr, comm, ro, nr));
+    if (bd3) { breakdown = true; return BIGKRLS_OK; }
+    for (int c = 0; c < b; ++c)          // beta = R3 beta (both upper triangular)
+      for (int r = 0; r <= c; ++r) {
+        double acc = 0.0;
+        for (int t = r; t <= c; ++t) acc += R3[r + (size_t)t * b] * prev[t + (size_t)c * b];
+        Rtmp[r + (size_t)c * b] = acc;
+      }
+    double* hp = nullptr;
+    BK_TRY(pinned_get(ctx, (int64_t)b * b, &hp));
+    std::memcpy(hp, Rtmp.data(), (size_t)b * b * sizeof(double));
+    BK_HIP(hipMemcpyAsync(dBall + (int64_t)steps * b * b, hp, (size_t)b * b * sizeof(double), hipMemcpyHostToDevice, st));
+    BK_HIP(hipStreamSynchronize(st));
+    if (verbose()) fprintf(stderr, "[bigkrls] block Lanczos step %d: ill-conditioned block (pivot ratio %.1e) re-orthogonalised\n", steps, piv[0] / piv[1]);
+    return BIGKRLS_OK;
+  }
+
+  // The Krylov space is invariant to working precision when the new block is nothing but rounding: its largest
+  // direction a millionth of the largest one any block had. Going on would normalise noise into unit vectors for
+  // step after step until a pivot turns negative (P = 2: ten such steps before the first scheduled check); the
+  // check comes now instead, as soon as the subspace has k columns, and decides with the true residuals
+  // (schedule_early_check).
+  // ... and while it has fewer than k columns (Neig above the numerical rank of K), the block that is nothing but
+  // rounding is REPLACED by a fresh random block orthogonalised against all blocks so far (what ARPACK does on an
+  // invariant subspace): normalising the rounding instead works for a few steps, then the noise -- amplified by K
+  // from step to step -- turns ill-conditioned and a pivot negative, short of k columns. The replaced W is what the
+  // block recurrence loses: only a block below 1e-10 of the largest direction seen -- below the tolerance times
+  // lambda_1, since no direction of a W exceeds lambda_1 -- is replaced, and its norm enters every later residual.
+  // beta of this step is zero (the new block is not coupled to the old ones).
+  int replace_invariant_block() {
+    const double wfro = std::sqrt(std::max(wnorm_sq, 0.0));
+    if (!(wmax_seen > 0.0 && wfro <= 1e-10 * wmax_seen && (int64_t)(steps + 1) * b < ke && steps + 1 < maxsteps)) return BIGKRLS_OK;
+    BK_TRY(fill_random(ctx, W, n * b, 20240229u + 7919u * (uint32_t)(steps + 1)));
+    for (int pass = 0; pass < 2; ++pass) BK_TRY(project_out(0));
+    std::vector<double> Rr;
+    bool bdr = false;
+    BK_TRY(kry_cholqr(ctx, &W, &W2, n, b, dG, Rr, &bdr, nullptr, comm, ro, nr));
+    BK_TRY(agree_breakdown(bdr));
+    if (bdr) return BIGKRLS_OK;
+    breakdown = false;
+    dropped += wfro;                 // (a bound for what all the replaced blocks together took from the recurrence)
+    std::fill(Rtmp.begin(), Rtmp.end(), 0.0);
+    BK_HIP(hipMemsetAsync(dBall + (int64_t)steps * b * b, 0, (size_t)b * b * sizeof(double), st));
+    piv[1] = 0.0;       // (nothing of this step counts as a direction of a Krylov block)
+    if (verbose())
+      fprintf(stderr, "[bigkrls] block Lanczos step %d: invariant subspace of %lld columns (|W| = %.1e): continued with a random block\n",
+              steps, (long long)((steps + 1) * b), wfro);
+    return BIGKRLS_OK;
+  }
+
+  // the check ahead of the schedule on an invariant Krylov space (see replace_invariant_block)
+  void schedule_early_check() {
+    const double wmax = std::sqrt(std::max(piv[1], 0.0));
+    if (!breakdown && !early_check_done && wmax <= 1e-6 * wmax_seen && (int64_t)(steps + 1) * b >= ke) {
+      next_check = std::min(next_check, steps + 1);      // (once: the checks after it follow their own forecasts)
+      early_check_done = true;
+    }
+    wmax_seen = std::max(wmax_seen, wmax);
+  }
+
+  // ---- convergence check on the projected problem ---------------------------------------------
+  // residuals |beta y_i[last block]| of the first k Ritz pairs of a projected problem whose eigenvectors end in the
+  // b rows ylast (b x k, host)
+  struct Resid { double worst = 0.0, worst_kept = 0.0, first = 0.0; int64_t n_conv = 0; };
+  Resid residuals(const double* thv, const double* ylast) const {
+    Resid r;
+    if (breakdown) {
+      // the factor beta of the last block does not exist (its Gram matrix is not positive definite): every
+      // residual |W y| is bounded by |W|_F -- zero to working precision when the Krylov space is invariant, which
+      // is the breakdown that means convergence; anything else is reported as not converged (dense path)
+      r.worst = r.worst_kept = std::sqrt(std::max(wnorm_sq, 0.0));
+      return r;
+    }
+    double by[b];
+    for (int64_t i = 0; i < ke; ++i) {
+      beta_times(ylast + (size_t)i * b, by);
+      double r2 = 0.0;
+      for (int rr = 0; rr < b; ++rr) r2 += by[rr] * by[rr];
+      if (i == 0) r.first = std::sqrt(r2);
+      r.worst = std::max(r.worst, std::sqrt(r2));
+      if (std::sqrt(r2) <= tol * std::fabs(thv[0])) ++r.n_conv;
+      if (keep_thresh >= 0.0 && thv[i] >= keep_thresh * thv[0]) r.worst_kept = std::max(r.worst_kept, std::sqrt(r2));
+    }
+    r.worst = std::max(r.worst, dropped);      // (blocks replaced by random ones, see replace_invariant_block)
+    return r;
+  }
+
+  // the m x m projected matrix, or the compressed one of the estimate, is decomposed by the dense path; theta (mm
+  // values, th) and the last b rows of Y (Ylast) come down through the context's pinned buffer
+  int solve_projected(const Projected& p, int64_t mm) {
+    int64_t nvY = 0;
+    // (auto rank: the subspace of an early check can be narrower than the cap -- as many vectors as there are)
+    const int64_t kv = auto_rank ? std::min<int64_t>(k, mm) : k;
+    // (replicated, but after a fault one rank's copy may fail where its peers' do not: agreed, so nobody leaves alone)
+    BK_TRY(kry_agree_status(kop, eigen(ctx, p.dT, mm, mm, mm, p.dvalsT, kv, -1.0, (double*)pY, mm, &nvY, 0, 1, EIG_FULL)));
+    double* hp = nullptr;
+    BK_TRY(pinned_get(ctx, mm + (int64_t)b * k, &hp));
+    BK_HIP(hipMemcpyAsync(hp, p.dvalsT, mm * sizeof(double), hipMemcpyDeviceToHost, st));
+    BK_HIP(hipMemcpy2DAsync(hp + mm, b * sizeof(double), (double*)pY + (mm - b), mm * sizeof(double),
+                            b * sizeof(double), kv, hipMemcpyDeviceToHost, st));
+    BK_HIP(hipStreamSynchronize(st));
+    th.assign(hp, hp + mm);
+    Ylast.assign((size_t)b * k, 0.0);
+    std::memcpy(Ylast.data(), hp + mm, (size_t)b * kv * sizeof(double));
+    return BIGKRLS_OK;
+  }
+
+  // Next check. The history of the worst residual is a plateau (O(1) while the subspace does not reach the
+  // k-th eigenvalue yet) followed by a collapse at a steady x25 - x45 per step (measured: N = 100 000,
+  // k = 1024: 2.6e-2, 6.0e-4, 1.4e-5, 3.1e-7; N = 50 000, k = 512: 6.0e-4, 3.5e-5, 1.4e-6, 6.1e-8), so a rate
+  // fitted to two plateau samples overshoots by many steps. The distance to the tolerance at an assumed
+  // collapse rate is used instead: an optimistic rate where a check (a dense eigensolve of T, ~12 us per
+  // row) is cheaper than a step (2 n^2 b flops), so undershooting costs little, a cautious one otherwise.
+  int steps_to_go(double worst, double theta1) const {
+    const double gain = check_is_cheap ? 40.0 : 15.0;
+    int inc = (worst > 0.0) ? (int)std::ceil(std::log(worst / (tol * theta1)) / std::log(gain)) : 1;
+    return std::max(1, std::min(inc, std::max(2, steps / 2)));
+  }
+
+  // The check after step `steps` (last: the iteration cannot go on): *done when the loop ends here, converged or not.
+  int check(bool last, bool* done) {
+    const int64_t m = (int64_t)steps * b;
+    *done = false;
+    // (a breakdown before the subspace had k columns: nothing to decompose -- the dense path)
+    if (m < ke) { dim = m; *done = true; return BIGKRLS_OK; }
+    bool full = true;
+    const int64_t mc = k + (int64_t)(steps - full_steps) * b;
+    if (!auto_rank && next_is_estimate && !last && full_steps > 0 && 2 * mc <= m && !sw.no_estimate)
+      BK_TRY(estimate_check(m, mc, &full));
+    if (full) BK_TRY(full_check(m, last, done));
+    if (!*done && sw.check_every) { next_check = steps + 1; next_is_estimate = false; }   // (development: the convergence history)
+    return BIGKRLS_OK;
+  }
+
+  // ---- an ESTIMATE instead of the full check (round 6): where the last full check (at full_steps) put the end of
+  // the iteration four or more steps away -- a forecast made from the plateau, which the check at its end only
+  // ever corrected (C4: 20 -> 25 -> 27) -- the check at that point decomposes the COMPRESSED projected problem:
+  // the k Ritz vectors of the last full check plus the blocks since, dimension k + 128 d instead of 128 steps
+  // (C4, step 25: 1 152 instead of 3 200). The Lanczos relation holds exactly for that basis, so its residuals are
+  // true residuals and track the full check's within a factor of two; the directions dropped at the compression
+  // never come back, so it cannot replace the full check (its converged set can miss wanted eigenvalues,
+  // tools/experiments/DEAD_ENDS.md): it only says where the next FULL check goes, and a full check follows at
+  // once should it report convergence (*full stays set).
+  int estimate_check(int64_t m, int64_t mc, bool* full) {
+    Projected p;
+    BK_TRY(projected_workspace(mc, &p));
+    hipLaunchKernelGGL(kry_assemble_compressed, dim3((unsigned)std::min<int64_t>((mc * mc + 255) / 256, 8192)), dim3(256), 0,
+                       st, (const double*)dPrev, (const double*)(dPrev + k), (int)k, (const double*)dAall,
+                       (const double*)dBall, full_steps, steps, b, p.dT);
+    BK_CHECK_LAUNCH();
+    BK_TRY(solve_projected(p, mc));
+    Resid r = residuals(th.data(), Ylast.data());
+    double worst = r.worst, theta1 = std::fabs(th[0]);
+    BK_TRY(agree_worst(worst, theta1));
+    if (verbose())
+      fprintf(stderr, "[bigkrls] block Lanczos estimate: steps=%d (compressed from %d: %lld instead of %lld) worst=%.3e converged=%lld of %lld theta0=%.4e\n",
+              steps, full_steps, (long long)mc, (long long)m, worst, (long long)r.n_conv, (long long)k, th[0]);
+    note("estimate", worst, th[0], "");
+    next_is_estimate = false;            // (what follows an estimate is a full check)
+    if (!(worst <= tol * theta1)) {
+      *full = false;
+      next_check = steps + steps_to_go(worst, theta1);
+    }
+    return BIGKRLS_OK;
+  }
+
+  int full_check(int64_t m, bool last, bool* done) {
+    Projected p;
+    BK_TRY(projected_workspace(m, &p));
+    hipLaunchKernelGGL(kry_assemble_t, dim3((unsigned)std::min<int64_t>((m * m + 255) / 256, 8192)), dim3(256), 0, st,
+                       (const double*)dAall, (const double*)dBall, steps, b, p.dT);
+    BK_CHECK_LAUNCH();
+    BK_TRY(solve_projected(p, m));
+    dvalsT = p.dvalsT;
+    theta = th;
+    ++n_checks;
+    // auto rank: the rank this check asks for. need > cap: the residuals below are those of the first `cap` pairs
+    // (theta_1's among them: the cap error waits for it); need > m: the subspace is still too narrow.
+    int64_t need = 0;
+    if (auto_rank) {
+      int64_t c = 0;
+      while (c < m && theta[c] >= keep_thresh * theta[0]) ++c;
+      need = c + 1;
+      ke = std::min<int64_t>(std::min<int64_t>(need, k), m);
+      check_is_cheap = 12e-6 * 4.0 * (double)ke < step_s_est;
+    }
+    Resid r = residuals(theta.data(), Ylast.data());
+    double worst = r.worst, theta1 = std::fabs(theta[0]);
+    BK_TRY(agree_worst(worst, theta1));
+    if (auto_rank && need > k && !breakdown && std::max(r.first, dropped) <= tol * theta1) {
+      char buf[320];
+      snprintf(buf, sizeof buf, "eigen (Krylov, auto rank): more than kcap = %lld eigenvalues reach the threshold: theta_kcap / theta_1 = %.3e "
+                                "is still above keep_thresh = %.3e (raise the cap, or give the rank)", (long long)k,
+               theta[k - 1] / theta[0], keep_thresh);
+      set_error(buf);
+      return BIGKRLS_EINVAL;
+    }
+    if (auto_rank && need > ke) worst = std::max(worst, 2.0 * tol * theta1);   // (not converged whatever the first ke pairs say)
+    if (verbose())
+      fprintf(stderr, "[bigkrls] block Lanczos check: steps=%d worst=%.3e worst(kept)=%.3e converged=%lld of %lld theta0=%.4e\n",
+              steps, worst, r.worst_kept, (long long)r.n_conv, (long long)k, theta[0]);
+    note("check", worst, theta[0], breakdown ? " breakdown=1" : " breakdown=0");
+    if (worst <= tol * theta1 || last) {
+      converged = worst <= tol * theta1;
+      dim = m;
+      *done = true;
+      return BIGKRLS_OK;
+    }
+    int inc = steps_to_go(worst, theta1);
+    if (auto_rank && need > m) inc = std::max<int>(inc, (int)((std::min<int64_t>(need, k) - m + b - 1) / b));   // (columns first)
+    next_check = steps + inc;
+    next_is_estimate = inc >= 4 && !auto_rank;
+    full_steps = steps;
+    if (next_is_estimate) BK_TRY(keep_for_estimate());
+    return BIGKRLS_OK;
+  }
+
+  // what the estimate at next_check needs of this check: the k Ritz values and C = beta Y[last block rows, :]
+  // (b x k), the coupling of the Ritz vectors to the next block -- kept on the device behind the blocks of T
+  int keep_for_estimate() {
+    double* hp = nullptr;
+    BK_TRY(pinned_get(ctx, k + (int64_t)b * k, &hp));
+    for (int64_t i = 0; i < k; ++i) hp[i] = theta[i];
+    for (int64_t i = 0; i < k; ++i) beta_times(Ylast.data() + (size_t)i * b, hp + k + i * b);
+    BK_HIP(hipMemcpyAsync(dPrev, hp, (size_t)(k + (int64_t)b * k) * sizeof(double), hipMemcpyHostToDevice, st));
+    BK_HIP(hipStreamSynchronize(st));     // (the pinned buffer is the eigensolver's as well)
+    return BIGKRLS_OK;
+  }
+
+  // the two ways the iteration ends without the pairs: BIGKRLS_ENOCONV (on one GPU the dense path takes over)
+  int finish_not_converged() {
 #ifdef BK_FAULT_INJECT
-  {
-    const char* fault = getenv("BIGKRLS_FAULT");   // BIGKRLS_FAULT=noconv (test build): pretend the iteration stalled
-    if (fault && std::string(fault) == "noconv") converged = false;
-  }
+    {
+      const char* fault = getenv("BIGKRLS_FAULT");   // BIGKRLS_FAULT=noconv (test build): pretend the iteration stalled
+      if (fault && std::string(fault) == "noconv") converged = false;
+    }
 #endif
-  if (!converged && dim < ke) {
-    set_error("eigen (Krylov): breakdown with a subspace smaller than the number of requested pairs (a kernel of lower "
-              "numerical rank than Neig: the dense path decomposes it -- taken automatically on one GPU; "
-              "bigkrls_fit_dist: eigen_mode \"dense\")");
+    if (converged) return BIGKRLS_OK;
+    if (dim < ke)
+      set_error("eigen (Krylov): breakdown with a subspace smaller than the number of requested pairs (a kernel of lower "
+                "numerical rank than Neig: the dense path decomposes it -- taken automatically on one GPU; "
+                "bigkrls_fit_dist: eigen_mode \"dense\")");
+    else
+      set_error("eigen (Krylov): not converged within the subspace limit; use the dense path (BIGKRLS_EIGK=dense);" + diag);
     return BIGKRLS_ENOCONV;
   }
-  if (!converged) {
-    set_error("eigen (Krylov): not converged within the subspace limit; use the dense path (BIGKRLS_EIGK=dense);" + kry_diag);
-    return BIGKRLS_ENOCONV;
-  }
+
   // ---- Ritz vectors Q = B Y -------------------------------------------------------------------------
   // With full re-orthogonalisation the Ritz pairs of T are Ritz pairs of K and |beta y_last| is their residual.
   // That is verified against K itself on the block of pairs that converge last (the smallest min(k, 128) Ritz
   // values: one more K-times-block product); only if the true residuals are not at the estimated level are
   // all k pairs refined by a Rayleigh-Ritz step against K (k more columns of K Q and a k x k eigenproblem),
   // which is what every call did before (BIGKRLS_KRY_REFINE=1 still forces it).
-  double* Q = W;                        // n x k (W, W2 are n x max(b,k))
-  double* KQ = W2;
-  if (nr > 0) BK_TRY(gemm(ctx, 0, 0, nr, ke, dim, 1.0, B + ro, n, (double*)pY, dim, 0.0, Q + ro, n));
-  double* dH = dA + b * b;              // k x k + 2k
-  double* dvalsH = dH + k * k;
-  std::vector<double> hv(theta.begin(), theta.begin() + ke);     // Ritz values of T, descending
-  bool refine = false;
-  {
-    const char* rf = getenv("BIGKRLS_KRY_REFINE");
-    refine = rf && std::string(rf) == "1";
+  double* Q() const { return W; }       // n x k (W, W2 are n x max(b,k))
+  double* KQ() const { return W2; }
+  int ritz_vectors() {
+    if (nr > 0) BK_TRY(gemm(ctx, 0, 0, nr, ke, dim, 1.0, B + ro, n, (double*)pY, dim, 0.0, Q() + ro, n));
+    hv.assign(theta.begin(), theta.begin() + ke);     // Ritz values of T, descending
+    return BIGKRLS_OK;
   }
-  const double* dvals_final = nullptr;
-  if (!refine && ctx->caller_verifies && !getenv("BIGKRLS_KRY_SAMPLE")) {     // (the variable: A/B timing)
-    // the fit checks ALL kept pairs against K itself right after this call (two +-1 combinations, tighter than this
-    // sample's error threshold and as tight as its refinement threshold times sqrt(k)); if that fails, the decomposition
-    // is redone with the flag cleared, i.e. with the sample check and, where it asks for it, the refinement below
-    void* pT = nullptr;
-    BK_TRY(ws_get(ctx, SLOT_KRY_T, (dim * dim + dim) * sizeof(double), &pT));
-    dvals_final = (const double*)pT + dim * dim;
-  } else if (!refine) {
+
+  int verify_or_refine() {
+    refine = sw.refine;
+    if (!refine && ctx->caller_verifies && !sw.sample) {     // (the switch: A/B timing)
+      // the fit checks ALL kept pairs against K itself right after this call (two +-1 combinations, tighter than this
+      // sample's error threshold and as tight as its refinement threshold times sqrt(k)); if that fails, the decomposition
+      // is redone with the flag cleared, i.e. with the sample check and, where it asks for it, the refinement below
+      dvals_final = dvalsT;
+    } else if (!refine) {
+      BK_TRY(sample_check());
+    }
+    if (!refine) return BIGKRLS_OK;
+    BK_TRY(k_times(ctx, kop, n, Q(), ke, KQ()));
+    BK_TRY(gram(Q(), ke, KQ(), ke, dH));
+    BK_TRY(ws_get(ctx, SLOT_KRY_Y, std::max<int64_t>(dim * k, k * k) * sizeof(double), &pZ));
+    int64_t nvZ = 0;
+    BK_TRY(eigen(ctx, dH, ke, ke, ke, dvalsH, ke, -1.0, (double*)pZ, ke, &nvZ, 0, 1, EIG_FULL));
+    {
+      PinnedFetch pf(ctx, ke);
+      BK_TRY(pf.add(hv.data(), dvalsH, ke * sizeof(double)));
+      BK_TRY(pf.finish());
+    }
+    dvals_final = dvalsH;
+    return BIGKRLS_OK;
+  }
+
+  // the true residuals of the block of pairs that converge last; sets `refine` where they are not at the estimated level
+  int sample_check() {
     const int64_t bs = std::min<int64_t>(ke, b), c0 = ke - bs;
-    // theta of T sits at the head of SLOT_KRY_T's value vector (device): dvalsT of the last check
-    void* pT = nullptr;
-    BK_TRY(ws_get(ctx, SLOT_KRY_T, (dim * dim + dim) * sizeof(double), &pT));
-    const double* dtheta = (const double*)pT + dim * dim;
-    BK_TRY(k_times(ctx, kop, n, Q + c0 * n, bs, KQ));
-    hipLaunchKernelGGL(kry_resid_sq_kernel, dim3((unsigned)bs), dim3(256), 0, st, (const double*)KQ,
-                       (const double*)(Q + c0 * n), dtheta + c0, n, ro, nr, dvalsH);
+    const double* dtheta = dvalsT;      // theta of T (device): dvalsT of the last check
+    BK_TRY(k_times(ctx, kop, n, Q() + c0 * n, bs, KQ()));
+    hipLaunchKernelGGL(kry_resid_sq_kernel, dim3((unsigned)bs), dim3(256), 0, st, (const double*)KQ(),
+                       (const double*)(Q() + c0 * n), dtheta + c0, n, ro, nr, dvalsH);
     BK_CHECK_LAUNCH();
     if (comm) BK_TRY(comm_all_reduce(comm, dvalsH, bs, COMM_SUM));       // the squared norms over all rows
     double* hp = nullptr;
@@ -2688,80 +2777,112 @@ static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t 
     if (verbose())
       fprintf(stderr, "[bigkrls] block Lanczos: true residual of the last %lld pairs %.3e (tolerance %.3e)\n", (long long)bs,
               rmax, tol * std::fabs(theta[0]));
-    {
-      double ag[2] = {-rmax, std::fabs(theta[0])};
-      BK_TRY(kry_agree_min(kop, ag, 2));
-      if (!(-ag[0] <= 10.0 * tol * ag[1])) refine = true;    // also NaN
-      // ... and a residual that is not even small against theta_1 means that the recurrence K B_j = ... did not hold
-      // (a product or an exchange delivered wrong data): the Ritz pairs of T are then no pairs of K at all. Every rank
-      // sees the same agreed figures, so every rank returns the error.
-      if (!(-ag[0] <= 1e-3 * ag[1])) {
-        char buf[200];
-        snprintf(buf, sizeof buf, "eigen (Krylov): the Ritz pairs fail the check against K itself (residual %.3e, theta_1 %.3e): "
-                                  "the block recurrence was corrupted", -ag[0], ag[1]);
-        set_error(buf);
-        ctx->corrupt_run = true;
-        return BIGKRLS_ENOCONV;
-      }
+    double theta1 = std::fabs(theta[0]);
+    BK_TRY(agree_worst(rmax, theta1));
+    if (!(rmax <= 10.0 * tol * theta1)) refine = true;    // also NaN
+    // ... and a residual that is not even small against theta_1 means that the recurrence K B_j = ... did not hold
+    // (a product or an exchange delivered wrong data): the Ritz pairs of T are then no pairs of K at all. Every rank
+    // sees the same agreed figures, so every rank returns the error.
+    if (!(rmax <= 1e-3 * theta1)) {
+      char buf[200];
+      snprintf(buf, sizeof buf, "eigen (Krylov): the Ritz pairs fail the check against K itself (residual %.3e, theta_1 %.3e): "
+                                "the block recurrence was corrupted", rmax, theta1);
+      set_error(buf);
+      ctx->corrupt_run = true;
+      return BIGKRLS_ENOCONV;
     }
     dvals_final = dtheta;
+    return BIGKRLS_OK;
   }
-  void* pZ = nullptr;
-  if (refine) {
-    BK_TRY(k_times(ctx, kop, n, Q, ke, KQ));
-    BK_TRY(gram(Q, ke, KQ, ke, dH));
-    BK_TRY(ws_get(ctx, SLOT_KRY_Y, std::max<int64_t>(dim * k, k * k) * sizeof(double), &pZ));
-    int64_t nvZ = 0;
-    BK_TRY(eigen(ctx, dH, ke, ke, ke, dvalsH, ke, -1.0, (double*)pZ, ke, &nvZ, 0, 1, EIG_FULL));
-    {
-      PinnedFetch pf(ctx, ke);
-      BK_TRY(pf.add(hv.data(), dvalsH, ke * sizeof(double)));
-      BK_TRY(pf.finish());
+
+  // the values, the number of kept vectors, the vectors themselves (all rows on every rank; other parts' columns zeroed)
+  int deliver() {
+    BK_HIP(hipMemcpyAsync(vals, dvals_final, ke * sizeof(double), hipMemcpyDeviceToDevice, st));
+    int64_t nv = 0;
+    if (keep_thresh >= 0.0) {
+      for (int64_t i = 0; i < ke; ++i)
+        if (hv[i] >= keep_thresh * hv[0]) nv = i + 1;     // max(which(values >= eigtrunc * values[1]))
+    } else {
+      nv = ke;
     }
-    dvals_final = dvalsH;
-  }
-  BK_HIP(hipMemcpyAsync(vals, dvals_final, ke * sizeof(double), hipMemcpyDeviceToDevice, st));
-  int64_t nv = 0;
-  if (keep_thresh >= 0.0) {
-    for (int64_t i = 0; i < ke; ++i)
-      if (hv[i] >= keep_thresh * hv[0]) nv = i + 1;     // max(which(values >= eigtrunc * values[1]))
-  } else {
-    nv = ke;
-  }
-  nv = std::min<int64_t>(nv, n_vecs_max);
-  if (h_n_vecs) *h_n_vecs = nv;
-  if (auto_rank) *h_n_vals = ke;
-  if (nv > 0) {
-    if (nr > 0) {
-      if (refine) BK_TRY(gemm(ctx, 0, 0, nr, nv, ke, 1.0, Q + ro, n, (double*)pZ, ke, 0.0, vecs + ro, ldv));
-      else BK_TRY(copy_matrix(ctx, Q + ro, nr, nv, n, vecs + ro, ldv));
+    nv = std::min<int64_t>(nv, n_vecs_max);
+    if (h_n_vecs) *h_n_vecs = nv;
+    if (auto_rank) *h_n_vals = ke;
+    if (nv > 0) {
+      if (nr > 0) {
+        if (refine) BK_TRY(gemm(ctx, 0, 0, nr, nv, ke, 1.0, Q() + ro, n, (double*)pZ, ke, 0.0, vecs + ro, ldv));
+        else BK_TRY(copy_matrix(ctx, Q() + ro, nr, nv, n, vecs + ro, ldv));
+      }
+      // every rank returns all rows of the kept eigenvectors (the later passes of the fit read row blocks of Q but
+      // build column blocks of Q diag(w) Q'): one all-gather of the row blocks, n x nv doubles
+      if (comm) BK_TRY(comm_gather_rows(comm, vecs + ro, nr, ldv, nv, kop.nb, n, vecs, ldv));
+      const int64_t pc0 = nv * part_index / part_count, pc1 = nv * (part_index + 1) / part_count;
+      if (pc0 > 0) BK_HIP(hipMemsetAsync(vecs, 0, (size_t)pc0 * ldv * sizeof(double), st));
+      if (pc1 < nv) BK_HIP(hipMemsetAsync(vecs + pc1 * ldv, 0, (size_t)(nv - pc1) * ldv * sizeof(double), st));
     }
-    // every rank returns all rows of the kept eigenvectors (the later passes of the fit read row blocks of Q but
-    // build column blocks of Q diag(w) Q'): one all-gather of the row blocks, n x nv doubles
-    if (comm) BK_TRY(comm_gather_rows(comm, vecs + ro, nr, ldv, nv, kop.nb, n, vecs, ldv));
-    const int64_t pc0 = nv * part_index / part_count, pc1 = nv * (part_index + 1) / part_count;
-    if (pc0 > 0) BK_HIP(hipMemsetAsync(vecs, 0, (size_t)pc0 * ldv * sizeof(double), st));
-    if (pc1 < nv) BK_HIP(hipMemsetAsync(vecs + pc1 * ldv, 0, (size_t)(nv - pc1) * ldv * sizeof(double), st));
-  }
 #ifdef BK_FAULT_INJECT
-  {
-    const char* fault = getenv("BIGKRLS_FAULT");   // BIGKRLS_FAULT=vals_ulp: see the dense path
-    if (fault && std::string(fault) == "vals_ulp" && nv > 1) {
-      fault_nudge_ulp<<<1, 1, 0, st>>>(vals + nv / 2);
-      BK_HIP(hipGetLastError());
+    {
+      const char* fault = getenv("BIGKRLS_FAULT");   // BIGKRLS_FAULT=vals_ulp: see the dense path
+      if (fault && std::string(fault) == "vals_ulp" && nv > 1) {
+        fault_nudge_ulp<<<1, 1, 0, st>>>(vals + nv / 2);
+        BK_HIP(hipGetLastError());
+      }
+      // BIGKRLS_FAULT=kry_swap: two kept Ritz vectors exchanged in the first call (see eig_swap in the dense path)
+      static int kswap_calls = 0;
+      const bool ks = fault && std::string(fault) == "kry_swap";
+      if (!ks) kswap_calls = 0;
+      if (ks && kswap_calls++ == 0 && nv > 3 && !comm) {
+        fault_swap_cols<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(vecs + (nv / 2) * ldv, vecs + (nv / 2 + 1) * ldv, (int)n);
+        BK_HIP(hipGetLastError());
+      }
     }
-    // BIGKRLS_FAULT=kry_swap: two kept Ritz vectors exchanged in the first call (see eig_swap in the dense path)
-    static int kswap_calls = 0;
-    const bool ks = fault && std::string(fault) == "kry_swap";
-    if (!ks) kswap_calls = 0;
-    if (ks && kswap_calls++ == 0 && nv > 3 && !comm) {
-      fault_swap_cols<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(vecs + (nv / 2) * ldv, vecs + (nv / 2 + 1) * ldv, (int)n);
-      BK_HIP(hipGetLastError());
-    }
-  }
 #endif
-  BK_HIP(hipStreamSynchronize(st));
-  return BIGKRLS_OK;
+    BK_HIP(hipStreamSynchronize(st));
+    return BIGKRLS_OK;
+  }
+
+  int run() {
+    sw = KrySwitches();
+    if (auto_rank) BK_REQUIRE(keep_thresh > 0.0 && h_n_vals && !comm, "eigen (Krylov, auto rank): needs keep_thresh > 0 and one GPU");
+    BK_TRY(carve_workspace());
+    BK_TRY(start_block());
+    while (true) {
+      BK_TRY(step());
+      BK_TRY(reorthogonalise_ill_conditioned());
+      BK_TRY(replace_invariant_block());
+      schedule_early_check();
+      ++steps;
+      BK_TRY(agree_breakdown(breakdown));
+      const bool last = breakdown || steps >= maxsteps;
+      if (last || steps >= next_check) {
+        bool done = false;
+        BK_TRY(check(last, &done));
+        if (done) break;
+      }
+      BK_HIP(hipMemcpyAsync(B + (int64_t)steps * b * n, W, n * b * sizeof(double), hipMemcpyDeviceToDevice, st));
+      dim = (int64_t)(steps + 1) * b;
+    }
+    if (verbose()) fprintf(stderr, "[bigkrls] block Lanczos: n=%lld k=%lld steps=%d dim=%lld converged=%d\n", (long long)n, (long long)k, steps, (long long)dim, (int)converged);
+    if (verbose() && auto_rank) fprintf(stderr, "[bigkrls] block Lanczos (auto rank): cap=%lld rank=%lld checks=%d\n", (long long)k, (long long)ke, n_checks);
+    BK_TRY(finish_not_converged());
+    BK_TRY(ritz_vectors());
+    BK_TRY(verify_or_refine());
+    return deliver();
+  }
+};
+
+}  // namespace
+
+// diag (optional): receives what the iteration did at its convergence checks, for a caller that reports on its behalf
+static int eigen_krylov(bigkrls_ctx* ctx, const KTimes& kop, int64_t n, int64_t k, double* vals,
+                        int64_t n_vecs_max, double keep_thresh, double* vecs, int64_t ldv,
+                        int64_t* h_n_vecs, int part_index, int part_count, bool auto_rank = false,
+                        int64_t* h_n_vals = nullptr, std::string* diag = nullptr) {
+  BlockLanczos bl(KryArgs{ctx, kop, n, k, vals, n_vecs_max, keep_thresh, vecs, ldv, h_n_vecs, h_n_vals, part_index,
+                          part_count, auto_rank});
+  const int rc = bl.run();
+  if (diag) *diag = bl.diag;
+  return rc;
 }
 
 int eigen_krylov_dist(bigkrls_comm* comm, const double* Kcols, int64_t n, int64_t r0, int64_t r1, int64_t nb,
@@ -3021,8 +3142,9 @@ struct DenseEig : EigArgs {
     KTimes whole;
     whole.A = A;
     whole.lda = lda;
+    std::string kry_diag;   // what the block Lanczos did at its convergence checks (for the error text)
     const int rc = eigen_krylov(ctx, whole, N, n_vals, vals, n_vecs_max, keep_thresh, vecs, ldv, h_n_vecs, part_index,
-                                part_count, auto_rank, h_n_vals);
+                                part_count, auto_rank, h_n_vals, &kry_diag);
     // A spectrum the iteration does not resolve within its subspace limit (or a breakdown) is
     // handed to the dense path in the same call -- A is untouched. Only an explicit
     // BIGKRLS_EIGK=krylov reports the non-convergence.
