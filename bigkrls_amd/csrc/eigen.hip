@@ -22,6 +22,7 @@
 // (src/eigen.cpp:28-29). Signs are arbitrary (the reference flips them and never
 // returns them to the user: R/bigKRLS_Rcpp_functions.R:186, quirk Q9).
 #include "common.h"
+#include "s1sched.h"
 
 #include <algorithm>
 #include <cmath>
@@ -2928,7 +2929,7 @@ int eigen_implicit(bigkrls_ctx* ctx, const KernelOp& kernel, int64_t n_vals, dou
 // Stage-1 state of a row-block distributed reduction, kept in the context between
 // bigkrls_dev_s1_open and bigkrls_dev_eigen_resume.
 struct DistS1 {
-  S1Ops ops;
+  Stage1 ops;
   int n = 0;
   bool panel_pending = false;   // a panel factorisation is running on the look-ahead stream (ev_join marks its end)
   int agg_mode = 0;             // panels per trailing update the ranks agreed on: 4 (groups of four, then pairs), 2 (pairs), 0 (none)
@@ -2993,9 +2994,11 @@ static int stage1_run(bigkrls_ctx* ctx, double* W, int n, double* taus1, const S
     }
     hipGraph_t graph = nullptr;
     BK_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-    ctx->stream = st;
-    const int rc = stage1_to_band(ctx, W, n, taus1, s1);
-    ctx->stream = user;
+    int rc = BIGKRLS_OK;
+    {
+      StreamScope on(ctx, st);
+      rc = stage1_to_band(ctx, W, n, taus1, s1);
+    }
     const hipError_t ec = hipStreamEndCapture(st, &graph);      // (always: the stream must leave capture mode)
     if (rc != BIGKRLS_OK) {
       if (graph) (void)hipGraphDestroy(graph);
@@ -3691,16 +3694,22 @@ int dist_s1_open(bigkrls_ctx* ctx, int64_t n) {
   return eigen(ctx, nullptr, n, n, n, nullptr, 0, -1.0, nullptr, n, nullptr, 0, 1, EIG_SETUP_ONLY);
 }
 
+// the strip into W (rows k..n of the panel's columns: the final diagonal block and the sub-diagonal panel), the panel
+// factorisation and its T factor, all on stream ps
+static int dist_s1_factor(bigkrls_ctx* ctx, DistS1* ds, int64_t n, int64_t k, const double* strip, hipStream_t ps) {
+  {
+    StreamScope on(ctx, ps);
+    BK_TRY(copy_matrix(ctx, strip, n - k, S2_B, n - k, ds->ops.W + k + k * n, n));
+  }
+  BK_TRY(ds->ops.panel_qr((int)k, ps));
+  return ds->ops.build_T((int)k, ps);
+}
+
 int dist_s1_panel(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* strip) {
   DistS1* ds = nullptr;
   BK_TRY(dist_state(ctx, n, &ds));
   BK_REQUIRE(strip && k >= 0 && k % S2_B == 0 && ds->ops.has_panel((int)k), "s1_panel: not a panel column");
-  double* W = ds->ops.W;
-  // rows k..n of the panel's columns: the final diagonal block and the sub-diagonal panel
-  BK_TRY(copy_matrix(ctx, strip, n - k, S2_B, n - k, W + k + k * n, n));
-  BK_TRY(ds->ops.panel_qr((int)k, ctx->stream));
-  BK_TRY(ds->ops.build_T((int)k, ctx->stream));
-  return BIGKRLS_OK;
+  return dist_s1_factor(ctx, ds, n, k, strip, ctx->stream);
 }
 
 // the panel factorisation and its T factor on the look-ahead stream, after everything queued on the main stream so
@@ -3714,13 +3723,7 @@ int dist_s1_panel_begin(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* st
   hipStream_t side = ctx->side_stream, st = ctx->stream;
   BK_HIP(hipEventRecord(ctx->ev_fork, st));
   BK_HIP(hipStreamWaitEvent(side, ctx->ev_fork, 0));
-  double* W = ds->ops.W;
-  ctx->stream = side;
-  int rc = copy_matrix(ctx, strip, n - k, S2_B, n - k, W + k + k * n, n);
-  ctx->stream = st;
-  BK_TRY(rc);
-  BK_TRY(ds->ops.panel_qr((int)k, side));
-  BK_TRY(ds->ops.build_T((int)k, side));
+  BK_TRY(dist_s1_factor(ctx, ds, n, k, strip, side));
   BK_HIP(hipEventRecord(ctx->ev_join, side));
   ds->panel_pending = true;
   return BIGKRLS_OK;
@@ -3761,6 +3764,21 @@ int dist_s1_thin(bigkrls_ctx* ctx, int64_t n, int64_t k, double* Y) {
   return ds->ops.small_products((int)k, Y, nullptr);
 }
 
+// Acols -= PZ1 PZ2[cols, :]' (m x ncols, inner dimension kk, PZ1 / PZ2 with leading dimension ld) for `ncols` own columns
+// whose first one is row `row0` of the trailing matrix. The own columns' diagonal block (rows row0 .. row0 + ncols of the
+// trailing matrix) is symmetric: lower tiles computed and mirrored (half the MFMA work of the plain product; with one
+// rank that is the whole update); the rows above and below it are plain products. Fewer than 128 columns: one product.
+static int dist_s1_apply_cols(bigkrls_ctx* ctx, const double* PZ1, const double* PZ2, int64_t ld, int64_t kk, int64_t m,
+                              double* Acols, int64_t lda, int64_t ncols, int64_t row0) {
+  if (ncols < 128) return gemm(ctx, 0, 1, m, ncols, kk, -1.0, PZ1, ld, PZ2 + row0, ld, 1.0, Acols, lda);
+  if (row0 > 0) BK_TRY(gemm(ctx, 0, 1, row0, ncols, kk, -1.0, PZ1, ld, PZ2 + row0, ld, 1.0, Acols, lda));
+  BK_TRY(syrk_mirror(ctx, ncols, kk, -1.0, PZ1 + row0, ld, PZ2 + row0, ld, Acols + row0, lda, 0, -1, true));
+  const int64_t below = m - row0 - ncols;
+  if (below > 0)
+    BK_TRY(gemm(ctx, 0, 1, below, ncols, kk, -1.0, PZ1 + row0 + ncols, ld, PZ2 + row0, ld, 1.0, Acols + row0 + ncols, lda));
+  return BIGKRLS_OK;
+}
+
 // A22[:, cols] -= [V | Z] [Z | V][cols, :]' for `ncols` own columns whose first one is row `row0` of the trailing matrix
 int dist_s1_update_cols(bigkrls_ctx* ctx, int64_t n, int64_t k, double* Acols, int64_t lda, int64_t ncols,
                         int64_t row0) {
@@ -3771,20 +3789,7 @@ int dist_s1_update_cols(bigkrls_ctx* ctx, int64_t n, int64_t k, double* Acols, i
   if (ncols == 0) return BIGKRLS_OK;
   BK_REQUIRE(Acols && lda >= m, "s1_update_cols: bad column block");
   if (ds->panel_pending) BK_TRY(ds->ops.gate());   // (the next panel's factorisation, on the look-ahead stream, becomes resident first)
-  const double *PZ1 = ds->ops.ws.PZ1, *PZ2 = ds->ops.ws.PZ2;
-  // The own columns' diagonal block (rows row0 .. row0 + ncols of the trailing matrix) is symmetric: lower tiles
-  // computed and mirrored (half the MFMA work of the plain product; with one rank that is the whole update);
-  // the rows above and below it are plain products.
-  if (ncols >= 128) {
-    if (row0 > 0) BK_TRY(gemm(ctx, 0, 1, row0, ncols, 2 * S2_B, -1.0, PZ1, m, PZ2 + row0, m, 1.0, Acols, lda));
-    BK_TRY(syrk_mirror(ctx, ncols, 2 * S2_B, -1.0, PZ1 + row0, m, PZ2 + row0, m, Acols + row0, lda, 0, -1, true));
-    const int64_t below = m - row0 - ncols;
-    if (below > 0)
-      BK_TRY(gemm(ctx, 0, 1, below, ncols, 2 * S2_B, -1.0, PZ1 + row0 + ncols, m, PZ2 + row0, m, 1.0,
-                  Acols + row0 + ncols, lda));
-    return BIGKRLS_OK;
-  }
-  return gemm(ctx, 0, 1, m, ncols, 2 * S2_B, -1.0, PZ1, m, PZ2 + row0, m, 1.0, Acols, lda);
+  return dist_s1_apply_cols(ctx, ds->ops.ws.PZ1, ds->ops.ws.PZ2, m, 2 * S2_B, m, Acols, lda, ncols, row0);
 }
 
 // ---- several panels per trailing update in the partitioned stage 1 (no pieces: the update of a group of G = 4 or 2
@@ -3808,17 +3813,8 @@ int dist_s1_set_agg_mode(bigkrls_ctx* ctx, int64_t n, int mode) {
 }
 int dist_s1_group_size(bigkrls_ctx* ctx, int64_t n, int64_t k0) {
   DistS1* ds = nullptr;
-  if (dist_state(ctx, n, &ds) != BIGKRLS_OK || ds->agg_mode == 0) return 0;
-  const int env = ds->agg_mode == 2 ? 2 : -1;
-  const int b = S2_B;
-  auto panels = [&](int g) {
-    for (int j = 0; j < g; ++j)
-      if (!ds->ops.has_panel((int)(k0 + j * b))) return false;
-    return true;
-  };
-  if (env != 2 && panels(4) && n - k0 - 4 * b >= S1_QUAD_MIN_M) return 4;
-  if (panels(2) && n - k0 - 2 * b >= S1_AGG_MIN_M) return 2;
-  return 0;
+  if (dist_state(ctx, n, &ds) != BIGKRLS_OK) return 0;
+  return s1_dist_group_size((int)n, (int)k0, ds->agg_mode);
 }
 
 // the thin products of panel k = k0 + 64 j of the group that starts at k0, from the summed Y = (stale A22) V, written
@@ -3855,17 +3851,8 @@ int dist_s1_update_cols_group(bigkrls_ctx* ctx, int64_t n, int64_t k, double* Ac
   if (ncols == 0) return BIGKRLS_OK;
   BK_REQUIRE(Acols && lda >= m, "s1_update_cols_group: bad column block");
   if (ds->panel_pending) BK_TRY(ds->ops.gate());   // (see dist_s1_update_cols)
-  const int64_t ldg = ds->ops.ws.aggLd, kk = 2 * b * nblk;
-  const double *PZ1 = ds->ops.ws.aggPZ1[0] + off, *PZ2 = ds->ops.ws.aggPZ1[1] + off;
-  if (ncols >= 128) {
-    if (row0 > 0) BK_TRY(gemm(ctx, 0, 1, row0, ncols, kk, -1.0, PZ1, ldg, PZ2 + row0, ldg, 1.0, Acols, lda));
-    BK_TRY(syrk_mirror(ctx, ncols, kk, -1.0, PZ1 + row0, ldg, PZ2 + row0, ldg, Acols + row0, lda, 0, -1, true));
-    const int64_t below = m - row0 - ncols;
-    if (below > 0)
-      BK_TRY(gemm(ctx, 0, 1, below, ncols, kk, -1.0, PZ1 + row0 + ncols, ldg, PZ2 + row0, ldg, 1.0, Acols + row0 + ncols, lda));
-    return BIGKRLS_OK;
-  }
-  return gemm(ctx, 0, 1, m, ncols, kk, -1.0, PZ1, ldg, PZ2 + row0, ldg, 1.0, Acols, lda);
+  return dist_s1_apply_cols(ctx, ds->ops.ws.aggPZ1[0] + off, ds->ops.ws.aggPZ1[1] + off, ds->ops.ws.aggLd, 2 * b * nblk, m,
+                            Acols, lda, ncols, row0);
 }
 
 int dist_s1_update(bigkrls_ctx* ctx, int64_t n, int64_t k, double* Y, double* Acols, int64_t lda, int64_t ncols,
@@ -3894,7 +3881,7 @@ int dist_s1_put(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* strip, int
   return copy_matrix(ctx, strip, n - k, ncols, n - k, ds->ops.W + k + k * n, n);
 }
 
-// One stage-1 panel factorisation on its own (exposed for tests): S1Ops::panel_qr and build_T, i.e. head -> Householder
+// One stage-1 panel factorisation on its own (exposed for tests): Stage1::panel_qr and build_T, i.e. head -> Householder
 // kernel's slot -> tail (the one-kernel form under BIGKRLS_PQ=fused), on the context's otherwise idle stream with a
 // workspace of its own. The panel is block column 0 of an imagined (m + 64)-row matrix whose sub-diagonal block is P.
 int panel_factor(bigkrls_ctx* ctx, double* P, int64_t ld, int64_t m, double* Vw, double* V, double* T, double* Tfold,
@@ -3923,7 +3910,7 @@ int panel_factor(bigkrls_ctx* ctx, double* P, int64_t ld, int64_t m, double* Vw,
   BK_HIP(hipMemsetAsync(ws.mail, 0, nmail * sizeof(double), st));
   BK_HIP(hipMemsetAsync(ws.pqc, 0, PQC_MAIL_DOUBLES * sizeof(double), st));
   BK_HIP(hipMemsetAsync(taus, 0, (2 * n + 16) * sizeof(double), st));
-  S1Ops ops;
+  Stage1 ops;
   BK_TRY(ops.init(ctx, P - b, n, taus, ws));
   ops.N = ld;
   BK_REQUIRE(ops.chol_panel(0), "panel_factor: the register-resident factorisation is not available (BIGKRLS_PQ, co-residency)");

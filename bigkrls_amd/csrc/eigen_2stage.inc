@@ -569,14 +569,9 @@ __global__ __launch_bounds__(256, 1) void pq_resident(double* __restrict__ P, in
 // two CholeskyQR passes, W left for the product; pq_tail, the TAIL: V, R, tau, T and U^-1 T beside that product);
 // pq_chol<false> is the one-kernel form (BIGKRLS_PQ=fused).
 // ---------------------------------------------------------------------------
-// trailing-matrix height down to which stage 1 aggregates two panels per update (stage1_to_band): where the update,
-// not the panel factorisation beside it, is the longer launch -- 14 848 with the 64-exchange Householder kernel,
-// 10 752 since pq_chol (threshold sweep at N = 20 000: 0.4532 / 0.4498 / 0.4478 / 0.4500 / 0.4520 s at 14 848 / 12 800 /
-// 10 752 / 9 216 / 7 680)
-constexpr int S1_AGG_MIN_M = 10752;
-constexpr int S1_SWAP_M = 6144;         // trailing-matrix height below which the panel chain stays on one stream (stage1_to_band)
-constexpr int S1_QUAD_MIN_M = 12800;    // ... down to which four panels share one update (sweep: 10 752 / 12 800 / 14 000 / 15 000 equal within 1 ms)
-constexpr int PQC_LD = 66;              // LDS row stride of the 64 x 64 matrices and of the staged rows
+// (the schedule's thresholds S1_AGG_MIN_M, S1_SWAP_M, S1_QUAD_MIN_M: csrc/s1sched.h)
+static_assert(S1_B == S2_B, "the schedule's panel width is the band width");
+constexpr int PQC_LD = 66;             // LDS row stride of the 64 x 64 matrices and of the staged rows
 constexpr int PQC_NG = S2_B * S2_B;     // Gram entries
 constexpr double PQC_RATIO = 1e-5;      // min / max diagonal of the first Cholesky factor below which the panel is left
                                         // to the Householder kernel (kappa^2 eps must stay far below 1)
@@ -1369,7 +1364,7 @@ __global__ __launch_bounds__(256, 2) void pq_chol(double* __restrict__ P, int64_
   //      ~2 us in workgroup 0 behind its stores, instead of the chain V'V (split-K GEMM) -> slab reduction -> dlarft
   //      recurrence behind the kernel (69 us at m = 2 500, on the critical path of every panel below m ~ 6 000). A panel
   //      left to the Householder kernel (s_bad above: this point is not reached) gets its T from that chain, which
-  //      S1Ops::build_T launches behind a device-side predicate.
+  //      Stage1::build_T launches behind a device-side predicate.
   if (Tout != nullptr && blk == 0) pqc_t_factor<true, false>(sA, sS, Tout, nullptr);
 }
 
@@ -1380,7 +1375,7 @@ __global__ __launch_bounds__(256, 2) void pq_chol(double* __restrict__ P, int64_
 // V = W U^-1 (the top block comes out as L) and stores it to V and, below the diagonal, into the panel. The LAST
 // workgroup, beside them: R = S (R2 R1), tau, T = -U S L^-T (write_T) and Tfold = U^-1 T = -S L^-T, which takes A22 W to
 // Y = A22 V T (s1_fused_yt). A panel the head left to the Householder kernel (*fallback != 0) has its V in Vw already:
-// copied to V, and T -- built by the chain S1Ops::build_T launches in front of this kernel -- to Tfold.
+// copied to V, and T -- built by the chain Stage1::build_T launches in front of this kernel -- to Tfold.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void pq_tail(double* __restrict__ P, int64_t ld, int m, double* __restrict__ taus,
                                                double* __restrict__ scales, const double* __restrict__ Vw,
@@ -1969,9 +1964,21 @@ struct Stage1Ws {
   double* aggC = nullptr;   // 3 x (256 x 64)
 };
 
-// The per-panel operations of stage 1, shared by the single-GPU loop (stage1_to_band) and by the
-// per-panel entry points of the row-block distributed reduction (bigkrls_dev_s1_*, eigen.hip).
-struct S1Ops {
+// ctx->stream pointed at another stream for the host calls of one scope (gemm(), copy_matrix(), syrk_mirror() and the
+// profile brackets launch on ctx->stream); restored on every exit
+struct StreamScope {
+  bigkrls_ctx* ctx;
+  hipStream_t saved;
+  StreamScope(bigkrls_ctx* c, hipStream_t s) : ctx(c), saved(c->stream) { c->stream = s; }
+  ~StreamScope() { ctx->stream = saved; }
+  StreamScope(const StreamScope&) = delete;
+  StreamScope& operator=(const StreamScope&) = delete;
+};
+
+// Stage 1, full matrix to band. The per-panel operations (panel_qr, build_T, small_products*) are shared by the
+// single-GPU loop and by the per-panel entry points of the row-block distributed reduction (bigkrls_dev_s1_*, eigen.hip);
+// the single-GPU loop is stage1_to_band: one member per phase, the schedule by csrc/s1sched.h.
+struct Stage1 {
   bigkrls_ctx* ctx = nullptr;
   double* W = nullptr;
   int n = 0;
@@ -1996,6 +2003,15 @@ struct S1Ops {
   // (*ws.fallback != 0: the panel was left to the Householder kernel, which forms no T)
   bool t_in_pq = true;
   int t_from_pq_k = -1;
+  S1Sched sched;                       // which arm takes which panel (init: n, residency, switches; begin_loop: the rest)
+  // ---- state of the loop (run)
+  hipStream_t st = nullptr, side = nullptr;   // main stream; look-ahead stream
+  int k = 0, gq = 0, gi = 0;           // the panel whose step comes next; groups of four / of two done
+  bool t_pending = false;              // ev_join2 (T and the correction factors of panel k, from the look-ahead stream) not waited for yet
+  bool panel_in_z = false;             // s1_fused_z has updated the next panel's columns
+  bool have_prev = false;              // piece b of the previous pair group is still to run
+  int c1 = 0, c1_prev = 0, og = 0, og_prev = 0;   // first column of piece a / first row of the buffers of this / the previous pair group
+  S1Counts done;                       // what went down each arm (BIGKRLS_VERBOSE)
   // on ctx->stream: wait until the panel factorisation enqueued last is resident (s1_gate)
   int gate() {
     static const bool on = [] { const char* e = getenv("BIGKRLS_S1_GATE"); return !(e && e[0] == '0'); }();
@@ -2049,11 +2065,17 @@ struct S1Ops {
       BK_TRY(ensure_dyn_smem(ctx, (const void*)s1_fused_yt, yt_smem));
       BK_TRY(ensure_dyn_smem(ctx, (const void*)s1_fused_z, z_smem));
     }
+    sched = S1Sched();
+    sched.n = n;
+    sched.cap = pq_cap;
+    sched.pq_steps = pq_steps;
+    sched.fused_panel = fused_panel;
+    sched.agg_ws = ws.aggPZ1[0] != nullptr;
     return BIGKRLS_OK;
   }
 
-  bool resident_qr(int k) const { return !pq_steps && (n - k - S2_B + 255) / 256 <= std::min(pq_cap, 80); }
-  bool has_panel(int k) const { return k + S2_B < n && n - k - S2_B > 1; }
+  bool resident_qr(int k) const { return sched.resident_qr(k); }
+  bool has_panel(int k) const { return sched.has_panel(k); }
   double* Tof(int k) const { return ws.Tall + (int64_t)(k / S2_B) * S2_B * S2_B; }
   // the panels pq_chol takes: register-resident, at most PQC_MAXWG workgroups, at least 2 b rows
   bool chol_panel(int k) const {
@@ -2070,18 +2092,8 @@ struct S1Ops {
     const int pw = b;
     t_from_pq_k = -1;
     double* P = W + (k + b) + (int64_t)k * N;
-    // Above ~80 workgroups the all-to-all (each workgroup reads every other's partials) and the
-    // CUs its spinning workgroups hold while the concurrent trailing update still owns the rest
-    // cost more than the 64 launches they replace (measured at N = 50 000).
 #ifdef BK_PQ_STUB
-    // experiment build only (tools/pq_exposure.py): no panel QR at all -- tau = 0, V = 0: the decomposition is garbage
-    // but finite, and its stage-1 time is what a free panel factorisation would leave
-    if (getenv("BIGKRLS_PQ_STUB")) {
-      BK_HIP(hipMemsetAsync(taus1 + k, 0, pw * sizeof(double), ps));
-      BK_HIP(hipMemsetAsync(taus1 + n + k, 0, pw * sizeof(double), ps));
-      BK_HIP(hipMemsetAsync(ws.Vp, 0, (size_t)m * pw * sizeof(double), ps));
-      return BIGKRLS_OK;
-    }
+    if (getenv("BIGKRLS_PQ_STUB")) return pq_stub(k, ps);
 #endif
     if (resident_qr(k)) {
       // algorithmic bytes: the m x 64 panel read and written once, the explicit V written once
@@ -2089,7 +2101,7 @@ struct S1Ops {
       if (samp) BK_TRY(prof_begin(ctx, "panel_qr", 24.0 * (double)m * pw, ps));
       const int npq = (m + 255) / 256;
       const bool chol = chol_panel(k), split = split_panel(k);
-      static const int pqc_dbg = [] { const char* e = getenv("BIGKRLS_PQC_DEBUG"); return e ? atoi(e) : 0; }();
+      static const int pqc_dbg = [] { const char* e = getenv("BIGKRLS_PQC_DEBUG"); return e ? atoi(e) : 0; }();   // (bits: pqc_debug)
       if (chol && (pqc_dbg & 1)) BK_HIP(hipDeviceSynchronize());     // debug: nothing runs beside the kernel
       if (chol) {
         if (split)
@@ -2101,36 +2113,7 @@ struct S1Ops {
         pq_started += (unsigned long long)npq;
         t_from_pq_k = t_in_pq ? k : -1;
       }
-      std::vector<double> dbgP;
-      if (chol && (pqc_dbg & 4)) {                                   // debug: the panel as the kernel will see it
-        BK_HIP(hipDeviceSynchronize());
-        dbgP.resize((size_t)m * b);
-        BK_HIP(hipMemcpy2D(dbgP.data(), (size_t)m * 8, P, (size_t)N * 8, (size_t)m * 8, b, hipMemcpyDeviceToHost));
-      }
-      if (chol && (pqc_dbg & 2)) {                                   // debug: report the panels left to pq_resident
-        BK_HIP(hipDeviceSynchronize());
-        if (!dbgP.empty()) {
-          std::vector<double> Gd(PQC_NG);
-          BK_HIP(hipMemcpy(Gd.data(), ws.pqc + PQC_OFF_SLICES, PQC_NG * sizeof(double), hipMemcpyDeviceToHost));
-          double worst = 0.0, gmax = 0.0; int wi = 0, wc = 0, nanc = 0;
-          for (int i = 0; i < b; ++i)
-            for (int c = 0; c < b; ++c) {
-              long double sum = 0.0L;
-              for (int r = 0; r < m; ++r) sum += (long double)dbgP[r + (size_t)i * m] * dbgP[r + (size_t)c * m];
-              const double g = Gd[i * b + c];
-              if (!(g == g)) ++nanc;
-              const double d = fabs(g - (double)sum);
-              gmax = std::max(gmax, fabs((double)sum));
-              if (d > worst || !(d == d)) { worst = d; wi = i; wc = c; }
-            }
-          fprintf(stderr, "[bigkrls] panel k=%d: summed Gram matrix in the mailbox vs host: max diff %.3e at (%d,%d), |G| max %.3e, NaNs %d\n", k, worst, wi, wc, gmax, nanc);
-        }
-        int fb = 0;
-        BK_HIP(hipMemcpy(&fb, ws.fallback, sizeof(int), hipMemcpyDeviceToHost));
-        double dbg[16];
-        BK_HIP(hipMemcpy(dbg, ws.pqc + PQC_OFF_SLICES + PQC_NG, sizeof(dbg), hipMemcpyDeviceToHost));
-        if (fb) fprintf(stderr, "[bigkrls] pq_chol left panel k=%d (m=%d) to the Householder kernel: pass 0 bad=%g dmin=%.3e dmax=%.3e; pass 1 bad=%g dmin=%.3e dmax=%.3e\n", k, m, dbg[0], dbg[1], dbg[2], dbg[8], dbg[9], dbg[10]);
-      }
+      if (chol && (pqc_dbg & 6)) BK_TRY(pqc_debug(k, P, pqc_dbg));
       // (a split panel left to this kernel: its V goes where A22 (.) reads, pq_tail copies it to ws.Vp)
       hipLaunchKernelGGL(pq_resident, dim3(npq), dim3(256), 0, ps, P, N, m, taus1 + k,
                          taus1 + n + k, split ? ws.Vw : ws.Vp, ws.mail, ws.mail2, (k / b) * S2_B + 1, ws.err,
@@ -2191,13 +2174,13 @@ struct S1Ops {
     };
     if (split && pred == nullptr) tail(false);
     const double* Vchain = (split && pred != nullptr) ? ws.Vw : ws.Vp;
-    hipStream_t saved = ctx->stream;
-    ctx->stream = ps;
-    ctx->gemm_run_if = pred;
-    const int rc = gemm(ctx, 1, 0, b, b, m, 1.0, Vchain, m, Vchain, m, 0.0, G, b);
-    ctx->gemm_run_if = nullptr;
-    ctx->stream = saved;
-    BK_TRY(rc);
+    {
+      StreamScope on(ctx, ps);
+      ctx->gemm_run_if = pred;
+      const int rc = gemm(ctx, 1, 0, b, b, m, 1.0, Vchain, m, Vchain, m, 0.0, G, b);
+      ctx->gemm_run_if = nullptr;
+      BK_TRY(rc);
+    }
     hipLaunchKernelGGL(bt_build_t, dim3(1), dim3(256), 0, ps, (const double*)G, b, (const double*)(taus1 + k), T, pred);
     if (split && pred != nullptr) tail(true);
     else if (split)
@@ -2241,6 +2224,288 @@ struct S1Ops {
     }
     return BIGKRLS_OK;
   }
+
+  // debug bodies, out of line (below): behind the same conditions and at the same points as ever
+  int pq_stub(int k, hipStream_t ps);                        // BK_PQ_STUB builds with BIGKRLS_PQ_STUB
+  int pqc_debug(int k, const double* P, int bits);           // BIGKRLS_PQC_DEBUG bits 4 and 2, after pq_chol's launch
+  int trace_duplicate_run(int k);                            // BIGKRLS_TRACE_FINE: the thin products once more, compared
+  // fine diagnostic trace (BIGKRLS_TRACE_FINE with BIGKRLS_TRACE_DIR): both streams drained, then hashes of the panel's
+  // factors and of the whole working matrix -- serialises the loop, for hunting a nondeterminism only
+  int fine(const char* tag, const double* p, int64_t count, int k) {
+    if (!trace_fine()) return BIGKRLS_OK;
+    BK_HIP(hipStreamSynchronize(side));
+    return trace_point(ctx, st, tag, p, count, k);
+  }
+
+  // ---- the loop: helpers ---------------------------------------------------------------------------------------
+  double* A22(int k) const { return W + (k + S2_B) + (int64_t)(k + S2_B) * N; }   // trailing matrix of panel k
+  bool samp(int k) const { return ctx->profile && (k / S2_B) % S1_PROF_STRIDE == 0; }   // HIP-event sampling: every 8th panel
+  static double piece_flops(double mm, double ca, double cb, double kk) {   // columns [ca, cb) of the lower triangle
+    return 2.0 * kk * ((cb - ca) * mm - 0.5 * (cb * cb - ca * ca));
+  }
+  // Y2 = A22 W(k) on the main stream (A22 possibly stale: the callers correct the product), then the wait for the T
+  // factor and the correction factors that were built on the look-ahead stream beside it
+  int av(int k) {
+    const int b = S2_B, m = n - k - b;
+    if (samp(k)) BK_TRY(prof_begin(ctx, "band_av", 2.0 * (double)m * (double)m * b));
+    BK_TRY(gemm(ctx, 0, 0, m, b, m, 1.0, A22(k), N, Vw(k), m, 0.0, ws.Y2, m));
+    if (samp(k)) BK_TRY(prof_end(ctx, "band_av"));
+    if (t_pending) {
+      BK_HIP(hipStreamWaitEvent(st, ctx->ev_join2, 0));
+      t_pending = false;
+    }
+    return BIGKRLS_OK;
+  }
+  // Look-ahead: panel kn is final once the step's thin products have updated its columns, so its latency-bound
+  // factorisation runs on the side stream beside the throughput-bound update the caller launches next. ev_join: V (W) of
+  // panel kn is ready; ev_join2: its T factor and factors() -- the caller's correction-factor products U'^T W(kn), with
+  // ctx->stream on the side stream -- which only the step after A22 W(kn) needs.
+  template <class F>
+  int fork_panel(int kn, F factors) {
+    BK_HIP(hipEventRecord(ctx->ev_fork, st));
+    BK_HIP(hipStreamWaitEvent(side, ctx->ev_fork, 0));
+    BK_TRY(panel_qr(kn, side));
+    BK_HIP(hipEventRecord(ctx->ev_join, side));
+    BK_TRY(build_T(kn, side));
+    { StreamScope on(ctx, side); BK_TRY(factors()); }
+    BK_HIP(hipEventRecord(ctx->ev_join2, side));
+    t_pending = true;
+    return BIGKRLS_OK;
+  }
+  int join() { BK_HIP(hipStreamWaitEvent(st, ctx->ev_join, 0)); return BIGKRLS_OK; }
+  // One piece of a pair group's k = 256 update: the 64-wide columns [j0, j1) (j1 < 0: to the end) of the trailing matrix
+  // that starts at row0, from buffer set `set` whose first row is og_
+  int piece(int row0, int set, int og_, int j0, int j1, bool bracket) {
+    const int b = S2_B, rows = n - row0;
+    const int64_t off = row0 - og_;
+    if (bracket) BK_TRY(prof_begin(ctx, "band_update2", piece_flops(rows, 64.0 * j0, j1 < 0 ? (double)rows : 64.0 * j1, 4.0 * b)));
+    BK_TRY(syrk_mirror_cols(ctx, rows, 4 * b, -1.0, ws.aggPZ1[set] + off, ws.aggLd, ws.aggPZ2[set] + off, ws.aggLd,
+                            W + row0 + (int64_t)row0 * N, N, j0, j1));
+    if (bracket) BK_TRY(prof_end(ctx, "band_update2"));
+    return BIGKRLS_OK;
+  }
+
+  // ---- the loop: phases (DESIGN.md section 4, "Stage 1: phases of one struct") ------------------------------------
+  // the per-call switches of the schedule and the streams (the loop state starts as a fresh Stage1 has it)
+  int begin_loop() {
+    if (const char* am = getenv("BIGKRLS_S1AGG_MIN")) sched.agg_min = std::max(4 * S2_B, atoi(am));   // (development: threshold sweep)
+    const char* agg_env = getenv("BIGKRLS_S1AGG");   // =0: one trailing update per panel from the start; =2: pairs from the start
+    sched.agg_mode = agg_env && std::string(agg_env) == "0" ? 0 : agg_env && std::string(agg_env) == "2" ? 2 : -1;
+    if (sched.quads_on())
+      if (const char* qm = getenv("BIGKRLS_S1AGG4_MIN")) sched.quad_min = std::max(sched.agg_min, atoi(qm));
+    static const int swap_m = [] { const char* e = getenv("BIGKRLS_S1_SWAP_M"); return e ? atoi(e) : S1_SWAP_M; }();
+    sched.swap_m = swap_m;
+    st = ctx->stream;
+    BK_TRY(side_stream_get(ctx));
+    side = ctx->side_stream;
+    sched.side_is_main = ctx->side_is_main;
+    return BIGKRLS_OK;
+  }
+  int first_panel() {
+    if (!has_panel(0)) return BIGKRLS_OK;
+    BK_TRY(panel_qr(0, st));
+    return build_T(0, st);
+  }
+
+  // ---- aggregated phases: several panels per pass over A22 ------------------------------------------------------
+  // At k = 128 the trailing update sits on the ridge between the MFMA and the HBM roof and reaches neither
+  // (read-modify-write of 12 m^2 bytes per 128 ranks); applied for two panels at once (k = 256) it runs at 0.60 of the
+  // MFMA peak instead of 0.41, for four (k = 512) at 0.73. Until a deferred update has run the bulk of A22 is stale, and
+  // what reads it is corrected by thin products with the pending reflector blocks U = [V_a Z_a V_b Z_b ...],
+  // U' = [Z_a V_a Z_b V_b ...]:
+  //   Y = A22 V  =  A22_stale V  -  U (U'^T V)  (+  P1 U (U'^T P1 V)      P1: rows in R1, where a pair's piece a is applied)
+  //   the next panel's 64 columns (never covered by a deferred update) get  - U U'[those rows]^T  explicitly.
+  // The factors U'^T V only need the next panel's V: they are formed on the look-ahead stream right after its QR.
+  //
+  // Groups of FOUR panels, one k = 512 update per group, while the trailing matrix has >= 12 800 rows. No pieces here: the
+  // whole update of a group is launched at the end of its fourth step (beside the next group's first panel
+  // factorisation); the three factorisations inside a group run alone, which costs little -- beside an update they only
+  // overlap by a quarter of their length. Panel j of a group corrects its product with the j pending blocks and updates
+  // the next panel's columns with them explicitly. Stage 1 at N = 20 000: 285.7 -> 283.0 ms (same box; BIGKRLS_S1AGG=2:
+  // pairs from the start).
+  int run_quads() {
+    for (; sched.quad_ok(k); ++gq, ++done.quads) {
+      const int ogq = k + S2_B;
+      for (int j = 0; j < 4; ++j, k += S2_B) BK_TRY(quad_step(j, ogq));
+    }
+    return BIGKRLS_OK;
+  }
+  int quad_step(int j, int ogq) {
+    const int b = S2_B, m = n - k - b, mn = m - b;
+    const int64_t ldg = ws.aggLd;
+    double *PZ1q = ws.aggPZ1[0], *PZ2q = ws.aggPZ1[1];           // n x 8b each: the allocation's four 4b-wide blocks
+    double* Cfull = ws.aggC;
+    BK_TRY(av(k));
+    const int64_t off = (k + b) - ogq;
+    if (j > 0) {
+      BK_TRY(gemm(ctx, 0, 0, m, b, 2 * b * j, -1.0, PZ1q + off, ldg, Cfull, 2 * b * j, 1.0, ws.Y2, m));
+      BK_TRY(gemm(ctx, 0, 1, m, b, 2 * b * j, -1.0, PZ1q + off, ldg, PZ2q + off, ldg, 1.0, A22(k), N));
+    }
+    const int64_t roff = off + (int64_t)j * 2 * b * ldg;
+    BK_TRY(small_products_to(k, ws.Y2, A22(k), PZ1q + roff, PZ2q + roff, ldg));
+    BK_TRY(fork_panel(k + b, [&] {
+      return j < 3 ? gemm(ctx, 1, 0, 2 * b * (j + 1), b, mn, 1.0, PZ2q + off + b, ldg, Vw(k + b), mn, 0.0, Cfull, 2 * b * (j + 1))
+                   : BIGKRLS_OK;
+    }));
+    if (j == 3) {
+      const bool samp4 = ctx->profile && (gq & 1) == 0;      // (bench.py: every second group's update bracketed)
+      BK_TRY(gate());
+      if (samp4) BK_TRY(prof_begin(ctx, "band_update4", piece_flops(mn, 0.0, (double)mn, 8.0 * b)));
+      BK_TRY(syrk_mirror_cols(ctx, mn, 8 * b, -1.0, PZ1q + off + b, ldg, PZ2q + off + b, ldg, A22(k + b), N, 0, -1));
+      if (samp4) BK_TRY(prof_end(ctx, "band_update4"));
+    }
+    return join();
+  }
+
+  // Groups of TWO panels down to AGG_MIN_M rows. The update of a group is applied in two pieces of equal area, one per
+  // panel step, so that every step still has a throughput-bound launch to hide the next panel's latency-bound QR behind:
+  //   piece a, launched at the end of the group's second step: the columns >= c1 of the trailing matrix (lower triangle +
+  //            mirror = the square R1 x R1, R1 = [c1, n));
+  //   piece b, launched at the end of the next group's first step (or by hand_over): the columns < c1.
+  // Below AGG_MIN_M the panel QR (~0.8 ms while it shares the GPU with an update), not the piece, is the longer of the two
+  // concurrent launches and the ~0.1 ms of thin correction products per step no longer pay (measured per step,
+  // N = 20 000: -0.2 ms at m = 19 000, 0 at m = 14 500).
+  int run_pairs() {
+    for (; sched.pair_ok(k); ++gi, ++done.pairs) {
+      og = k + S2_B;                                        // first row held by this group's buffers
+      for (int half = 0; half < 2; ++half, k += S2_B) BK_TRY(pair_step(half));
+      have_prev = true;
+      c1_prev = c1;
+      og_prev = og;
+    }
+    return BIGKRLS_OK;
+  }
+  int pair_step(int half) {
+    const int b = S2_B, m = n - k - b, mn = m - b;          // rows of the trailing matrices T_k, T_{k+1}
+    const int64_t ldg = ws.aggLd;
+    const int set = gi & 1;
+    double *PZ1g = ws.aggPZ1[set], *PZ2g = ws.aggPZ2[set], *PZ1p = ws.aggPZ1[set ^ 1], *PZ2p = ws.aggPZ2[set ^ 1];
+    double *Cfull = ws.aggC, *CR1 = Cfull + 4 * b * b, *Ca = CR1 + 4 * b * b;
+    BK_TRY(av(k));
+    if (half == 0 && have_prev) {
+      const int64_t off = (k + b) - og_prev;
+      const int64_t r1 = c1_prev - (k + b);
+      BK_TRY(gemm(ctx, 0, 0, m, b, 4 * b, -1.0, PZ1p + off, ldg, Cfull, 4 * b, 1.0, ws.Y2, m));
+      if (r1 < m)
+        BK_TRY(gemm(ctx, 0, 0, m - r1, b, 4 * b, 1.0, PZ1p + off + r1, ldg, CR1, 4 * b, 1.0, ws.Y2 + r1, m));
+      // the next panel's columns: the previous group's update (no piece covers them)
+      BK_TRY(gemm(ctx, 0, 1, m, b, 4 * b, -1.0, PZ1p + off, ldg, PZ2p + off, ldg, 1.0, A22(k), N));
+    } else if (half == 1) {
+      const int64_t off = (k + b) - og;
+      BK_TRY(gemm(ctx, 0, 0, m, b, 2 * b, -1.0, PZ1g + off, ldg, Ca, 2 * b, 1.0, ws.Y2, m));
+      BK_TRY(gemm(ctx, 0, 1, m, b, 2 * b, -1.0, PZ1g + off, ldg, PZ2g + off, ldg, 1.0, A22(k), N));
+    }
+    // Z of this panel into the group's blocks; s1_fused_z also applies this panel's own update to the next panel's columns
+    const int64_t roff = (k + b) - og + (int64_t)half * 2 * b * ldg;
+    BK_TRY(small_products_to(k, ws.Y2, A22(k), PZ1g + roff, PZ2g + roff, ldg));
+    // correction factors of the next step: U'^T W_{next} (and its part over R1) -- they act on Y2 = A22 W_{next}, which
+    // Tfold takes to Y as a whole (W = V U row by row, so the part over R1 is in the same space)
+    BK_TRY(fork_panel(k + b, [&] {
+      if (half == 0) return gemm(ctx, 1, 0, 2 * b, b, mn, 1.0, PZ2g + b, ldg, Vw(k + b), mn, 0.0, Ca, 2 * b);
+      c1 = s1_piece_c1(k + 2 * b, mn);
+      const int64_t r1n = c1 - (k + 2 * b);
+      BK_TRY(gemm(ctx, 1, 0, 4 * b, b, mn, 1.0, PZ2g + 2 * b, ldg, Vw(k + b), mn, 0.0, Cfull, 4 * b));
+      return gemm(ctx, 1, 0, 4 * b, b, mn - r1n, 1.0, PZ2g + 2 * b + r1n, ldg, Vw(k + b) + r1n, mn, 0.0, CR1, 4 * b);
+    }));
+    // the throughput-bound launch of this step, concurrent with the panel QR
+    if (half == 0 && have_prev) {
+      BK_TRY(gate());
+      BK_TRY(piece(k + 2 * b, set ^ 1, og_prev, 0, s1_piece_cols(c1_prev, k + 2 * b), samp(k)));
+    } else if (half == 1) {
+      BK_TRY(gate());
+      BK_TRY(piece(k + 2 * b, set, og, s1_piece_cols(c1, k + 2 * b), -1, samp(k)));
+    }
+    return join();
+  }
+  // hand-over to one update per panel: piece b of the last pair group on the whole of T_k
+  int hand_over() {
+    if (!have_prev) return BIGKRLS_OK;
+    return piece(k + S2_B, (gi - 1) & 1, og_prev, 0, s1_piece_cols(c1_prev, k + S2_B), false);
+  }
+
+  // ---- one update per panel -------------------------------------------------------------------------------------
+  int run_single() {
+    for (; has_panel(k); k += S2_B) {
+      BK_TRY(single_products());
+      switch (sched.single_arm(k)) {
+        case S1Arm::OneStream: ++done.one_stream; BK_TRY(single_one_stream()); break;
+        case S1Arm::TwoStream: ++done.two_stream; BK_TRY(single_two_stream()); break;
+        default: ++done.last; BK_TRY(single_last()); break;
+      }
+    }
+    return BIGKRLS_OK;
+  }
+  // what every arm starts with: A22 W, the thin products and, when a register-resident panel QR follows, the update of
+  // the next panel's columns by s1_fused_z
+  int single_products() {
+    const int b = S2_B, m = n - k - b;
+    BK_TRY(fine("R:s1_W", W, N * N, k));
+    BK_TRY(fine("R:s1_V", ws.Vp, (int64_t)m * b, k));
+    BK_TRY(fine("R:s1_tau", taus1 + k, b, k));
+    BK_TRY(av(k));
+    panel_in_z = sched.panel_in_z(k);
+    BK_TRY(fine("R:s1_Y2", ws.Y2, (int64_t)m * b, k));
+    BK_TRY(fine("R:s1_T", Tof(k), b * b, k));
+    BK_TRY(small_products(k, ws.Y2, panel_in_z ? A22(k) : (double*)nullptr));
+    BK_TRY(fine("R:s1_PZ1", ws.PZ1, (int64_t)m * 2 * b, k));
+    BK_TRY(fine("R:s1_PZ2", ws.PZ2, (int64_t)m * 2 * b, k));
+    if (trace_fine()) BK_TRY(trace_duplicate_run(k));
+    return BIGKRLS_OK;
+  }
+  // algorithmic flops of the bracketed update: without the first 64 columns when s1_fused_z has already updated them
+  double single_flops() const {
+    const double mu = (double)(n - k - S2_B - (panel_in_z ? S2_B : 0));
+    return mu * (mu + 1.0) * 2.0 * S2_B;
+  }
+  // the two-sided update A22 -= V Z' + Z V' of panel k: tile columns [c0, c1) (c1 < 0: to the end)
+  int single_update(int c0, int c1_, bool narrow, bool skip_first = false) {
+    return syrk_mirror(ctx, n - k - S2_B, 2 * S2_B, -1.0, ws.PZ1, n - k - S2_B, ws.PZ2, n - k - S2_B, A22(k), N, c0, c1_, narrow, skip_first);
+  }
+  // Small trailing matrices (below S1_SWAP_M rows; round 6): the chain fused products -> panel factorisation -> A22 V
+  // -> fused products IS the critical path there (the update is the shorter of the two concurrent launches), and
+  // each of its two stream changes cost 12-15 us (from the end of a kernel on one stream to the start of its
+  // dependant on the other; profiles/r05/r05b_C2_panel_chain_timeline.log). So the chain stays on the main stream --
+  // the factorisation (which now writes its T factor itself) starts right behind s1_fused_z, A22 V right behind it --
+  // and the trailing update moves to the look-ahead stream, joined before A22 V reads the matrix. The tail of the split
+  // factorisation follows the update there (behind ev_pq): the update is the shorter of the two launches, so the tail
+  // starts with A22 W and ends before s1_fused_yt needs V and Tfold wherever that product is the longer one.
+  int single_one_stream() {
+    BK_HIP(hipEventRecord(ctx->ev_fork, st));
+    BK_HIP(hipStreamWaitEvent(side, ctx->ev_fork, 0));
+    {
+      StreamScope on(ctx, side);
+      if (samp(k)) BK_TRY(prof_begin(ctx, "band_update", single_flops()));
+      BK_TRY(single_update(0, -1, true, true));
+      if (samp(k)) BK_TRY(prof_end(ctx, "band_update"));
+    }
+    BK_HIP(hipEventRecord(ctx->ev_join, side));     // the update is done
+    BK_TRY(panel_qr(k + S2_B, st));
+    BK_HIP(hipEventRecord(ctx->ev_pq, st));
+    BK_HIP(hipStreamWaitEvent(side, ctx->ev_pq, 0));
+    BK_TRY(build_T(k + S2_B, side));                // (the factorisation's tail, beside A22 W; the T chain of a panel that fell back)
+    BK_HIP(hipEventRecord(ctx->ev_join2, side));
+    t_pending = true;
+    return join();
+  }
+  // the update on the main stream, the next factorisation beside all of it but the next panel's own tile column
+  int single_two_stream() {
+    const bool narrow = resident_qr(k + S2_B);   // tile shape that shares the GPU best with the concurrent QR
+    if (samp(k)) BK_TRY(prof_begin(ctx, "band_update", single_flops()));
+    if (!panel_in_z) BK_TRY(single_update(0, 1, narrow));   // next panel's tiles
+    BK_TRY(fork_panel(k + S2_B, [] { return (int)BIGKRLS_OK; }));
+    BK_TRY(gate());
+    if (panel_in_z) BK_TRY(single_update(0, -1, narrow, true));   // everything but the first 64-wide tile column (done by s1_fused_z)
+    else BK_TRY(single_update(1, -1, narrow));                     // the rest
+    if (samp(k)) BK_TRY(prof_end(ctx, "band_update"));
+    return join();
+  }
+  int single_last() {
+    if (samp(k)) BK_TRY(prof_begin(ctx, "band_update", single_flops()));
+    BK_TRY(single_update(0, -1, false));        // A22 -= VZ' + ZV'
+    if (samp(k)) BK_TRY(prof_end(ctx, "band_update"));
+    return BIGKRLS_OK;
+  }
+
 };
 
 // fine diagnostic trace only: element-wise comparison of two runs of the same kernels on the same inputs.
@@ -2262,343 +2527,99 @@ __global__ void s1_dbg_compare(const double* __restrict__ a, const double* __res
   }
 }
 
-int stage1_to_band(bigkrls_ctx* ctx, double* W, int n, double* taus1, const Stage1Ws& ws) {
-  hipStream_t st = ctx->stream;
-  const int64_t N = n;
-  const int b = S2_B;
-  S1Ops ops;
-  BK_TRY(ops.init(ctx, W, n, taus1, ws));
-  auto has_panel = [&](int k) { return ops.has_panel(k); };
+// experiment build only (BK_PQ_STUB, tools/pq_exposure.py): no panel QR at all -- tau = 0, V = 0: the decomposition is
+// garbage but finite, and its stage-1 time is what a free panel factorisation would leave
+inline int Stage1::pq_stub(int k, hipStream_t ps) {
+  const int pw = S2_B, m = n - k - S2_B;
+  BK_HIP(hipMemsetAsync(taus1 + k, 0, pw * sizeof(double), ps));
+  BK_HIP(hipMemsetAsync(taus1 + n + k, 0, pw * sizeof(double), ps));
+  BK_HIP(hipMemsetAsync(ws.Vp, 0, (size_t)m * pw * sizeof(double), ps));
+  return BIGKRLS_OK;
+}
 
-  // Look-ahead: once the first tile column of the trailing update is done, the next panel
-  // (which lives in that tile column) is final, so its latency-bound QR runs on a side stream
-  // while the main stream finishes the remaining, throughput-bound tiles of the update.
-  BK_TRY(side_stream_get(ctx));
-  hipStream_t side = ctx->side_stream;
-  bool t_pending = false;
-  bool panel_in_z = false;
-  if (has_panel(0)) {
-    BK_TRY(ops.panel_qr(0, st));
-    BK_TRY(ops.build_T(0, st));
+// BIGKRLS_PQC_DEBUG, after pq_chol's launch for panel k (P: its m x 64 block, leading dimension N). Bit 4: the panel as
+// the kernel will see it, for bit 2: report the panels left to pq_resident (and the mailbox's Gram matrix against the host's)
+inline int Stage1::pqc_debug(int k, const double* P, int bits) {
+  const int b = S2_B, m = n - k - b;
+  std::vector<double> dbgP;
+  if (bits & 4) {
+    BK_HIP(hipDeviceSynchronize());
+    dbgP.resize((size_t)m * b);
+    BK_HIP(hipMemcpy2D(dbgP.data(), (size_t)m * 8, P, (size_t)N * 8, (size_t)m * 8, b, hipMemcpyDeviceToHost));
   }
-  int k0 = 0;
-  // ---- aggregated phase: two panels per pass over A22 -------------------------------------------
-  // At k = 128 the trailing update sits on the ridge between the MFMA and the HBM roof and reaches
-  // neither (read-modify-write of 12 m^2 bytes per 128 ranks); applied for two panels at once
-  // (k = 256) it runs at 0.60 of the MFMA peak instead of 0.41. The update of a GROUP of two panels
-  // (a, b) is therefore deferred and applied in two pieces of equal area, one per panel step, so that
-  // every step still has a throughput-bound launch to hide the next panel's latency-bound QR behind:
-  //   piece a, launched at the end of the group's second step: the columns >= c1 of the trailing
-  //            matrix (lower triangle + mirror = the square R1 x R1, R1 = [c1, n));
-  //   piece b, launched at the end of the next group's first step: the columns < c1.
-  // Until a piece has run the bulk of A22 is stale, and what reads it is corrected by thin products
-  // with the pending reflector blocks U = [V_a Z_a V_b Z_b], U' = [Z_a V_a Z_b V_b]:
-  //   Y = A22 V  =  A22_stale V  -  U (U'^T V)  +  P1 U (U'^T P1 V)      (P1: rows in R1, piece a applied)
-  //   the next panel's 64 columns (never covered by a piece) get  - U U'[those rows]^T  explicitly.
-  // The factors U'^T V only need the next panel's V: they are formed on the look-ahead stream right
-  // after its QR. Below m = AGG_MIN_M the panel QR (~0.8 ms while it shares the GPU with an update), not
-  // the piece, is the longer of the two concurrent launches and the ~0.1 ms of thin correction products
-  // per step no longer pay (measured per step, N = 20 000: -0.2 ms at m = 19 000, 0 at m = 14 500):
-  // the loop continues with one update per panel.
-  {
-    int AGG_MIN_M = S1_AGG_MIN_M;
-    if (const char* am = getenv("BIGKRLS_S1AGG_MIN")) AGG_MIN_M = std::max(4 * S2_B, atoi(am));   // (development: threshold sweep)
-    const char* agg_env = getenv("BIGKRLS_S1AGG");   // BIGKRLS_S1AGG=0: one trailing update per panel from the start
-    const bool agg_on = ws.aggPZ1[0] != nullptr && ops.fused_panel && !(agg_env && std::string(agg_env) == "0");
-    auto agg_ok = [&](int kk) {
-      return agg_on && has_panel(kk) && has_panel(kk + b) && ops.resident_qr(kk) && ops.resident_qr(kk + b) &&
-             n - kk - b >= AGG_MIN_M;
-    };
-    const int64_t ldg = ws.aggLd;
-    double* Cfull = ws.aggC;
-    double* CR1 = Cfull + 4 * b * b;
-    double* Ca = CR1 + 4 * b * b;
-    int gi = 0, k = 0;
-    bool have_prev = false;
-    int c1_prev = 0, c1 = 0, og_prev = 0, og = 0;
-    auto piece_flops = [](double mm, double ca, double cb, double kk) {   // columns [ca, cb) of the lower triangle
-      return 2.0 * kk * ((cb - ca) * mm - 0.5 * (cb * cb - ca * ca));
-    };
-    // ---- groups of FOUR panels, one k = 512 update per group, while the trailing matrix has >= 12 800 rows ---------
-    // At k = 512 the update runs at 0.73 of the MFMA peak in isolation (0.60 at k = 256). No pieces here: the whole
-    // update of a group is launched at the end of its fourth step (beside the next group's first panel factorisation);
-    // the three factorisations inside a group run alone, which costs little -- beside an update they only overlap by a
-    // quarter of their length. Panel j of a group corrects its product with the j pending blocks, U_j (U'_j^T V), and
-    // updates the next panel's columns with them explicitly. Stage 1 at N = 20 000: 285.7 -> 283.0 ms (same box;
-    // BIGKRLS_S1AGG=2: pairs from the start).
-    if (agg_on && !(agg_env && std::string(agg_env) == "2")) {
-      int Q_MIN_M = S1_QUAD_MIN_M;
-      if (const char* qm = getenv("BIGKRLS_S1AGG4_MIN")) Q_MIN_M = std::max(AGG_MIN_M, atoi(qm));
-      double* PZ1q = ws.aggPZ1[0];           // n x 8b each: the allocation's four 4b-wide blocks
-      double* PZ2q = ws.aggPZ1[1];
-      auto quad_ok = [&](int kk) {
-        return agg_ok(kk) && agg_ok(kk + b) && agg_ok(kk + 2 * b) && agg_ok(kk + 3 * b) && n - kk - 4 * b >= Q_MIN_M;
-      };
-      int gq = 0;
-      while (quad_ok(k)) {
-        const int ogq = k + b;
-        for (int j = 0; j < 4; ++j, k += b) {
-          const int m = n - k - b, mn = m - b;
-          double* A22 = W + (k + b) + (int64_t)(k + b) * N;
-          const bool samp = ctx->profile && (k / b) % S1_PROF_STRIDE == 0;
-          if (samp) BK_TRY(prof_begin(ctx, "band_av", 2.0 * (double)m * (double)m * b));
-          BK_TRY(gemm(ctx, 0, 0, m, b, m, 1.0, A22, N, ops.Vw(k), m, 0.0, ws.Y2, m));     // (stale A22) W
-          if (samp) BK_TRY(prof_end(ctx, "band_av"));
-          if (t_pending) {
-            BK_HIP(hipStreamWaitEvent(st, ctx->ev_join2, 0));
-            t_pending = false;
-          }
-          const int64_t off = (k + b) - ogq;
-          if (j > 0) {
-            BK_TRY(gemm(ctx, 0, 0, m, b, 2 * b * j, -1.0, PZ1q + off, ldg, Cfull, 2 * b * j, 1.0, ws.Y2, m));
-            BK_TRY(gemm(ctx, 0, 1, m, b, 2 * b * j, -1.0, PZ1q + off, ldg, PZ2q + off, ldg, 1.0, A22, N));
-          }
-          const int64_t roff = off + (int64_t)j * 2 * b * ldg;
-          BK_TRY(ops.small_products_to(k, ws.Y2, A22, PZ1q + roff, PZ2q + roff, ldg));
-          BK_HIP(hipEventRecord(ctx->ev_fork, st));
-          BK_HIP(hipStreamWaitEvent(side, ctx->ev_fork, 0));
-          BK_TRY(ops.panel_qr(k + b, side));
-          BK_HIP(hipEventRecord(ctx->ev_join, side));
-          BK_TRY(ops.build_T(k + b, side));
-          if (j < 3) {
-            hipStream_t saved = ctx->stream;
-            ctx->stream = side;
-            const int rc = gemm(ctx, 1, 0, 2 * b * (j + 1), b, mn, 1.0, PZ2q + off + b, ldg, ops.Vw(k + b), mn, 0.0, Cfull,
-                                2 * b * (j + 1));
-            ctx->stream = saved;
-            BK_TRY(rc);
-          }
-          BK_HIP(hipEventRecord(ctx->ev_join2, side));
-          t_pending = true;
-          if (j == 3) {
-            double* A22n = W + (k + 2 * b) + (int64_t)(k + 2 * b) * N;
-            const bool samp4 = ctx->profile && (gq & 1) == 0;      // (bench.py: every second group's update bracketed)
-            BK_TRY(ops.gate());
-            if (samp4) BK_TRY(prof_begin(ctx, "band_update4", piece_flops(mn, 0.0, (double)mn, 8.0 * b)));
-            BK_TRY(syrk_mirror_cols(ctx, mn, 8 * b, -1.0, PZ1q + off + b, ldg, PZ2q + off + b, ldg, A22n, N, 0, -1));
-            if (samp4) BK_TRY(prof_end(ctx, "band_update4"));
-          }
-          BK_HIP(hipStreamWaitEvent(st, ctx->ev_join, 0));
-        }
-        ++gq;
+  if (!(bits & 2)) return BIGKRLS_OK;
+  BK_HIP(hipDeviceSynchronize());
+  if (!dbgP.empty()) {
+    std::vector<double> Gd(PQC_NG);
+    BK_HIP(hipMemcpy(Gd.data(), ws.pqc + PQC_OFF_SLICES, PQC_NG * sizeof(double), hipMemcpyDeviceToHost));
+    double worst = 0.0, gmax = 0.0; int wi = 0, wc = 0, nanc = 0;
+    for (int i = 0; i < b; ++i)
+      for (int c = 0; c < b; ++c) {
+        long double sum = 0.0L;
+        for (int r = 0; r < m; ++r) sum += (long double)dbgP[r + (size_t)i * m] * dbgP[r + (size_t)c * m];
+        const double g = Gd[i * b + c];
+        if (!(g == g)) ++nanc;
+        const double d = fabs(g - (double)sum);
+        gmax = std::max(gmax, fabs((double)sum));
+        if (d > worst || !(d == d)) { worst = d; wi = i; wc = c; }
       }
-    }
-    while (agg_ok(k) && agg_ok(k + b)) {
-      const int set = gi & 1;
-      double *PZ1g = ws.aggPZ1[set], *PZ2g = ws.aggPZ2[set];
-      double *PZ1p = ws.aggPZ1[set ^ 1], *PZ2p = ws.aggPZ2[set ^ 1];
-      og = k + b;                                           // first row held by this group's buffers
-      for (int half = 0; half < 2; ++half, k += b) {
-        const int m = n - k - b;                            // rows of the trailing matrix T_k
-        const int mn = m - b;                               // ... of T_{k+1}
-        double* A22 = W + (k + b) + (int64_t)(k + b) * N;
-        const bool samp = ctx->profile && (k / b) % S1_PROF_STRIDE == 0;
-        if (samp) BK_TRY(prof_begin(ctx, "band_av", 2.0 * (double)m * (double)m * b));
-        BK_TRY(gemm(ctx, 0, 0, m, b, m, 1.0, A22, N, ops.Vw(k), m, 0.0, ws.Y2, m));     // (stale A22) W
-        if (samp) BK_TRY(prof_end(ctx, "band_av"));
-        if (t_pending) {
-          BK_HIP(hipStreamWaitEvent(st, ctx->ev_join2, 0));   // T factor and the correction factors
-          t_pending = false;
-        }
-        if (half == 0 && have_prev) {
-          const int64_t off = (k + b) - og_prev;
-          const int64_t r1 = c1_prev - (k + b);
-          BK_TRY(gemm(ctx, 0, 0, m, b, 4 * b, -1.0, PZ1p + off, ldg, Cfull, 4 * b, 1.0, ws.Y2, m));
-          if (r1 < m)
-            BK_TRY(gemm(ctx, 0, 0, m - r1, b, 4 * b, 1.0, PZ1p + off + r1, ldg, CR1, 4 * b, 1.0, ws.Y2 + r1, m));
-          // the next panel's columns: the previous group's update (no piece covers them)
-          BK_TRY(gemm(ctx, 0, 1, m, b, 4 * b, -1.0, PZ1p + off, ldg, PZ2p + off, ldg, 1.0, A22, N));
-        } else if (half == 1) {
-          const int64_t off = (k + b) - og;
-          BK_TRY(gemm(ctx, 0, 0, m, b, 2 * b, -1.0, PZ1g + off, ldg, Ca, 2 * b, 1.0, ws.Y2, m));
-          BK_TRY(gemm(ctx, 0, 1, m, b, 2 * b, -1.0, PZ1g + off, ldg, PZ2g + off, ldg, 1.0, A22, N));
-        }
-        // Z of this panel into the group's blocks; s1_fused_z also applies this panel's own update to
-        // the next panel's columns
-        const int64_t roff = (k + b) - og + (int64_t)half * 2 * b * ldg;
-        BK_TRY(ops.small_products_to(k, ws.Y2, A22, PZ1g + roff, PZ2g + roff, ldg));
-        BK_HIP(hipEventRecord(ctx->ev_fork, st));
-        BK_HIP(hipStreamWaitEvent(side, ctx->ev_fork, 0));
-        BK_TRY(ops.panel_qr(k + b, side));
-        BK_HIP(hipEventRecord(ctx->ev_join, side));
-        BK_TRY(ops.build_T(k + b, side));
-        {
-          // correction factors of the next step: U'^T W_{next} (and its part over R1) -- they act on Y2 = A22 W_{next}, which
-          // Tfold takes to Y as a whole (W = V U row by row, so the part over R1 is in the same space)
-          hipStream_t saved = ctx->stream;
-          ctx->stream = side;
-          int rc = BIGKRLS_OK;
-          if (half == 0) {
-            rc = gemm(ctx, 1, 0, 2 * b, b, mn, 1.0, PZ2g + b, ldg, ops.Vw(k + b), mn, 0.0, Ca, 2 * b);
-          } else {
-            const int ncol64 = (mn + 63) / 64;
-            const int J1 = std::min(std::max((int)(ncol64 * 0.2929 + 0.5), 1), ncol64 - 1);
-            c1 = (k + 2 * b) + 64 * J1;
-            const int64_t r1n = 64 * (int64_t)J1;
-            rc = gemm(ctx, 1, 0, 4 * b, b, mn, 1.0, PZ2g + 2 * b, ldg, ops.Vw(k + b), mn, 0.0, Cfull, 4 * b);
-            if (rc == BIGKRLS_OK)
-              rc = gemm(ctx, 1, 0, 4 * b, b, mn - r1n, 1.0, PZ2g + 2 * b + r1n, ldg, ops.Vw(k + b) + r1n, mn, 0.0, CR1, 4 * b);
-          }
-          ctx->stream = saved;
-          BK_TRY(rc);
-        }
-        BK_HIP(hipEventRecord(ctx->ev_join2, side));
-        t_pending = true;
-        // the throughput-bound launch of this step, concurrent with the panel QR
-        double* A22n = W + (k + 2 * b) + (int64_t)(k + 2 * b) * N;
-        if ((half == 0 && have_prev) || half == 1) BK_TRY(ops.gate());
-        if (half == 0 && have_prev) {
-          const int64_t off = (k + 2 * b) - og_prev;
-          const int J1b = (c1_prev - (k + 2 * b)) / 64;
-          if (samp) BK_TRY(prof_begin(ctx, "band_update2", piece_flops(mn, 0.0, 64.0 * J1b, 4.0 * b)));
-          BK_TRY(syrk_mirror_cols(ctx, mn, 4 * b, -1.0, PZ1p + off, ldg, PZ2p + off, ldg, A22n, N, 0, J1b));
-          if (samp) BK_TRY(prof_end(ctx, "band_update2"));
-        } else if (half == 1) {
-          const int64_t off = (k + 2 * b) - og;
-          const int J1 = (c1 - (k + 2 * b)) / 64;
-          if (samp) BK_TRY(prof_begin(ctx, "band_update2", piece_flops(mn, 64.0 * J1, (double)mn, 4.0 * b)));
-          BK_TRY(syrk_mirror_cols(ctx, mn, 4 * b, -1.0, PZ1g + off, ldg, PZ2g + off, ldg, A22n, N, J1, -1));
-          if (samp) BK_TRY(prof_end(ctx, "band_update2"));
-        }
-        BK_HIP(hipStreamWaitEvent(st, ctx->ev_join, 0));
-      }
-      have_prev = true;
-      c1_prev = c1;
-      og_prev = og;
-      ++gi;
-    }
-    if (have_prev) {
-      // hand-over to one update per panel: piece b of the last group on the whole of T_k
-      const int m = n - k - b;
-      const int64_t off = (k + b) - og_prev;
-      const int J1b = (c1_prev - (k + b)) / 64;
-      double* A22 = W + (k + b) + (int64_t)(k + b) * N;
-      BK_TRY(syrk_mirror_cols(ctx, m, 4 * b, -1.0, ws.aggPZ1[(gi - 1) & 1] + off, ldg, ws.aggPZ2[(gi - 1) & 1] + off, ldg,
-                              A22, N, 0, J1b));
-    }
-    k0 = k;
+    fprintf(stderr, "[bigkrls] panel k=%d: summed Gram matrix in the mailbox vs host: max diff %.3e at (%d,%d), |G| max %.3e, NaNs %d\n", k, worst, wi, wc, gmax, nanc);
   }
-  // fine diagnostic trace (BIGKRLS_TRACE_FINE with BIGKRLS_TRACE_DIR): both streams drained, then hashes of the panel's
-  // factors and of the whole working matrix -- serialises the loop, for hunting a nondeterminism only
-  auto fine = [&](const char* tag, const double* p, int64_t count, int k) -> int {
-    if (!trace_fine()) return BIGKRLS_OK;
-    BK_HIP(hipStreamSynchronize(side));
-    return trace_point(ctx, st, tag, p, count, k);
-  };
-  for (int k = k0; has_panel(k); k += b) {
-    const int m = n - k - b;
-    const int pw = b;
-    // ---- two-sided update of A22 = W[k+b:, k+b:] (full symmetric storage) -------------
-    double* A22 = W + (k + b) + (int64_t)(k + b) * N;
-    BK_TRY(fine("R:s1_W", W, N * N, k));
-    BK_TRY(fine("R:s1_V", ws.Vp, (int64_t)m * pw, k));
-    BK_TRY(fine("R:s1_tau", taus1 + k, pw, k));
-    const bool samp = ctx->profile && (k / b) % S1_PROF_STRIDE == 0;   // HIP-event sampling: every 8th panel
-    if (samp) BK_TRY(prof_begin(ctx, "band_av", 2.0 * (double)m * (double)m * pw));
-    BK_TRY(gemm(ctx, 0, 0, m, pw, m, 1.0, A22, N, ops.Vw(k), m, 0.0, ws.Y2, m));       // A22 W
-    if (samp) BK_TRY(prof_end(ctx, "band_av"));
-    if (t_pending) {   // the T factor was built on the look-ahead stream, concurrently with A22 V
-      BK_HIP(hipStreamWaitEvent(st, ctx->ev_join2, 0));
-      t_pending = false;
-    }
-    // ... and, when a register-resident panel QR follows, the update of the next panel's columns
-    panel_in_z = ops.fused_panel && has_panel(k + b) && ops.resident_qr(k + b);
-    BK_TRY(fine("R:s1_Y2", ws.Y2, (int64_t)m * pw, k));
-    BK_TRY(fine("R:s1_T", ops.Tof(k), pw * pw, k));
-    BK_TRY(ops.small_products(k, ws.Y2, panel_in_z ? A22 : (double*)nullptr));
-    BK_TRY(fine("R:s1_PZ1", ws.PZ1, (int64_t)m * 2 * pw, k));
-    BK_TRY(fine("R:s1_PZ2", ws.PZ2, (int64_t)m * 2 * pw, k));
-    if (trace_fine()) {
-      // the same three kernels once more on the same inputs (without the update of the next panel's columns), into a
-      // second pair of buffers: any difference is a nondeterminism caught in the act -- where, how much, how many
-      void* pdup = nullptr;
-      BK_TRY(ws_get(ctx, SLOT_DERIV_B, (4 * (int64_t)N * pw + 2 * (N / 64 + 2) * 4 + 64) * (int64_t)sizeof(double), &pdup));
-      double* d1 = (double*)pdup;
-      double* d2 = d1 + 2 * (int64_t)N * pw;
-      unsigned long long* dout = (unsigned long long*)(d2 + 2 * (int64_t)N * pw);
-      unsigned int* dflag = (unsigned int*)(dout + 8);
-      BK_TRY(ops.small_products_to(k, ws.Y2, nullptr, d1, d2, m));
-      for (int which = 0; which < 2; ++which) {
-        BK_HIP(hipMemsetAsync(dout, 0, 8 * sizeof(unsigned long long), st));
-        BK_HIP(hipMemsetAsync(dout + 1, 0xff, sizeof(unsigned long long), st));
-        BK_HIP(hipMemsetAsync(dflag, 0, (size_t)(N / 64 + 2) * 4 * sizeof(unsigned int), st));
-        hipLaunchKernelGGL(s1_dbg_compare, dim3(512), dim3(256), 0, st, (const double*)(which ? ws.PZ2 : ws.PZ1),
-                           (const double*)(which ? d2 : d1), (int64_t)m, (int64_t)2 * pw, (int64_t)m, dout, dflag);
-        BK_CHECK_LAUNCH();
-        unsigned long long h[4] = {0, 0, 0, 0};
-        PinnedFetch pfc(ctx, 4);
-        BK_TRY(pfc.add(h, dout, 4 * sizeof(unsigned long long)));
-        BK_TRY(pfc.finish());
-        if (h[0] != 0) {
-          double md;
-          memcpy(&md, &h[2], sizeof md);
-          // (count in `count`, first differing row in `extra`; the hash field carries the largest difference's bits)
-          fprintf(stderr, "[bigkrls] NONDETERMINISM caught: panel k=%d, %s of two runs of s1_fused_yt/s/z on the same inputs differ in %llu of %lld "
-                          "entries, first at (row %lld, column %lld), largest difference %.3e, %llu distinct 64 x 64 blocks\n",
-                  k, which ? "[Z | V]" : "[V | Z]", h[0], (long long)m * 2 * pw, (long long)(h[1] % m), (long long)(h[1] / m), md, h[3]);
-          BK_TRY(trace_host(which ? "X:dup_PZ2" : "X:dup_PZ1", h, 4, k));
-        }
-      }
-    }
-    // (algorithmic flops of what the bracketed launch does: without the first 64 columns when
-    //  s1_fused_z has already updated them)
-    const double mu = panel_in_z ? (double)(m - pw) : (double)m;
-    // Small trailing matrices (below S1_SWAP_M rows; round 6): the chain fused products -> panel factorisation -> A22 V
-    // -> fused products IS the critical path there (the update is the shorter of the two concurrent launches), and
-    // each of its two stream changes cost 12-15 us (from the end of a kernel on one stream to the start of its
-    // dependant on the other; profiles/r05/r05b_C2_panel_chain_timeline.log). So the chain stays on the main stream --
-    // the factorisation (which now writes its T factor itself) starts right behind s1_fused_z, A22 V right behind it --
-    // and the trailing update moves to the look-ahead stream, joined before A22 V reads the matrix. The tail of the split
-    // factorisation follows the update there (behind ev_pq): the update is the shorter of the two launches, so the tail
-    // starts with A22 W and ends before s1_fused_yt needs V and Tfold wherever that product is the longer one.
-    static const int swap_m = [] { const char* e = getenv("BIGKRLS_S1_SWAP_M"); return e ? atoi(e) : S1_SWAP_M; }();
-    if (has_panel(k + b) && panel_in_z && m - pw < swap_m && !ctx->side_is_main) {
-      const bool narrow = true;
-      BK_HIP(hipEventRecord(ctx->ev_fork, st));
-      BK_HIP(hipStreamWaitEvent(side, ctx->ev_fork, 0));
-      {
-        hipStream_t saved = ctx->stream;
-        ctx->stream = side;
-        int rc = BIGKRLS_OK;
-        if (samp) rc = prof_begin(ctx, "band_update", mu * (mu + 1.0) * 2.0 * pw);
-        if (rc == BIGKRLS_OK) rc = syrk_mirror(ctx, m, 2 * pw, -1.0, ws.PZ1, m, ws.PZ2, m, A22, N, 0, -1, narrow, true);
-        if (rc == BIGKRLS_OK && samp) rc = prof_end(ctx, "band_update");
-        ctx->stream = saved;
-        BK_TRY(rc);
-      }
-      BK_HIP(hipEventRecord(ctx->ev_join, side));     // the update is done
-      BK_TRY(ops.panel_qr(k + b, st));
-      BK_HIP(hipEventRecord(ctx->ev_pq, st));
-      BK_HIP(hipStreamWaitEvent(side, ctx->ev_pq, 0));
-      BK_TRY(ops.build_T(k + b, side));               // (the factorisation's tail, beside A22 W; the T chain of a panel that fell back)
-      BK_HIP(hipEventRecord(ctx->ev_join2, side));
-      t_pending = true;
-      BK_HIP(hipStreamWaitEvent(st, ctx->ev_join, 0));
-    } else if (has_panel(k + b)) {
-      const bool narrow = ops.resident_qr(k + b);   // tile shape that shares the GPU best with the concurrent QR
-      if (samp) BK_TRY(prof_begin(ctx, "band_update", mu * (mu + 1.0) * 2.0 * pw));
-      if (!panel_in_z)
-        BK_TRY(syrk_mirror(ctx, m, 2 * pw, -1.0, ws.PZ1, m, ws.PZ2, m, A22, N, 0, 1, narrow));   // next panel's tiles
-      BK_HIP(hipEventRecord(ctx->ev_fork, st));
-      BK_HIP(hipStreamWaitEvent(side, ctx->ev_fork, 0));
-      BK_TRY(ops.panel_qr(k + b, side));
-      BK_HIP(hipEventRecord(ctx->ev_join, side));     // V of the next panel is ready
-      BK_TRY(ops.build_T(k + b, side));
-      BK_HIP(hipEventRecord(ctx->ev_join2, side));    // ... and its T factor (only needed after A22 V)
-      t_pending = true;
-      BK_TRY(ops.gate());
-      if (panel_in_z)   // everything but the first 64-wide tile column (done by s1_fused_z)
-        BK_TRY(syrk_mirror(ctx, m, 2 * pw, -1.0, ws.PZ1, m, ws.PZ2, m, A22, N, 0, -1, narrow, true));
-      else
-        BK_TRY(syrk_mirror(ctx, m, 2 * pw, -1.0, ws.PZ1, m, ws.PZ2, m, A22, N, 1, -1, narrow));  // the rest
-      if (samp) BK_TRY(prof_end(ctx, "band_update"));
-      BK_HIP(hipStreamWaitEvent(st, ctx->ev_join, 0));
-    } else {
-      if (samp) BK_TRY(prof_begin(ctx, "band_update", mu * (mu + 1.0) * 2.0 * pw));
-      BK_TRY(syrk_mirror(ctx, m, 2 * pw, -1.0, ws.PZ1, m, ws.PZ2, m, A22, N));        // A22 -= VZ' + ZV'
-      if (samp) BK_TRY(prof_end(ctx, "band_update"));
+  int fb = 0;
+  BK_HIP(hipMemcpy(&fb, ws.fallback, sizeof(int), hipMemcpyDeviceToHost));
+  double dbg[16];
+  BK_HIP(hipMemcpy(dbg, ws.pqc + PQC_OFF_SLICES + PQC_NG, sizeof(dbg), hipMemcpyDeviceToHost));
+  if (fb) fprintf(stderr, "[bigkrls] pq_chol left panel k=%d (m=%d) to the Householder kernel: pass 0 bad=%g dmin=%.3e dmax=%.3e; pass 1 bad=%g dmin=%.3e dmax=%.3e\n", k, m, dbg[0], dbg[1], dbg[2], dbg[8], dbg[9], dbg[10]);
+  return BIGKRLS_OK;
+}
+
+// BIGKRLS_TRACE_FINE: the same three kernels once more on the same inputs (without the update of the next panel's
+// columns), into a second pair of buffers: any difference is a nondeterminism caught in the act -- where, how much, how many
+inline int Stage1::trace_duplicate_run(int k) {
+  const int pw = S2_B, m = n - k - S2_B;
+  void* pdup = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_DERIV_B, (4 * (int64_t)N * pw + 2 * (N / 64 + 2) * 4 + 64) * (int64_t)sizeof(double), &pdup));
+  double* d1 = (double*)pdup;
+  double* d2 = d1 + 2 * (int64_t)N * pw;
+  unsigned long long* dout = (unsigned long long*)(d2 + 2 * (int64_t)N * pw);
+  unsigned int* dflag = (unsigned int*)(dout + 8);
+  BK_TRY(small_products_to(k, ws.Y2, nullptr, d1, d2, m));
+  for (int which = 0; which < 2; ++which) {
+    BK_HIP(hipMemsetAsync(dout, 0, 8 * sizeof(unsigned long long), st));
+    BK_HIP(hipMemsetAsync(dout + 1, 0xff, sizeof(unsigned long long), st));
+    BK_HIP(hipMemsetAsync(dflag, 0, (size_t)(N / 64 + 2) * 4 * sizeof(unsigned int), st));
+    hipLaunchKernelGGL(s1_dbg_compare, dim3(512), dim3(256), 0, st, (const double*)(which ? ws.PZ2 : ws.PZ1),
+                       (const double*)(which ? d2 : d1), (int64_t)m, (int64_t)2 * pw, (int64_t)m, dout, dflag);
+    BK_CHECK_LAUNCH();
+    unsigned long long h[4] = {0, 0, 0, 0};
+    PinnedFetch pfc(ctx, 4);
+    BK_TRY(pfc.add(h, dout, 4 * sizeof(unsigned long long)));
+    BK_TRY(pfc.finish());
+    if (h[0] != 0) {
+      double md;
+      memcpy(&md, &h[2], sizeof md);
+      // (count in `count`, first differing row in `extra`; the hash field carries the largest difference's bits)
+      fprintf(stderr, "[bigkrls] NONDETERMINISM caught: panel k=%d, %s of two runs of s1_fused_yt/s/z on the same inputs differ in %llu of %lld "
+                      "entries, first at (row %lld, column %lld), largest difference %.3e, %llu distinct 64 x 64 blocks\n",
+              k, which ? "[Z | V]" : "[V | Z]", h[0], (long long)m * 2 * pw, (long long)(h[1] % m), (long long)(h[1] / m), md, h[3]);
+      BK_TRY(trace_host(which ? "X:dup_PZ2" : "X:dup_PZ1", h, 4, k));
     }
   }
+  return BIGKRLS_OK;
+}
+
+int stage1_to_band(bigkrls_ctx* ctx, double* W, int n, double* taus1, const Stage1Ws& ws) {
+  Stage1 s1;
+  BK_TRY(s1.init(ctx, W, n, taus1, ws));
+  BK_TRY(s1.begin_loop());
+  BK_TRY(s1.first_panel());
+  BK_TRY(s1.run_quads());
+  BK_TRY(s1.run_pairs());
+  BK_TRY(s1.hand_over());
+  BK_TRY(s1.run_single());
+  if (verbose())
+    fprintf(stderr, "[bigkrls] stage 1 schedule: n=%d: %d groups of four, %d pair groups, %d two-stream panels, %d one-stream panels\n",
+            n, s1.done.quads, s1.done.pairs, s1.done.two_stream, s1.done.one_stream);
   return BIGKRLS_OK;
 }
 
@@ -4664,16 +4685,12 @@ int bt1_precompute(bigkrls_ctx* ctx, const double* W, int n, const double* taus1
   hipLaunchKernelGGL(bt1_extract_all, dim3(blocks, ng), dim3(256), 0, ps, (const Bt1Group*)d_groups, W, N,
                      (const double*)(taus1 + n), Tall, LT, Vstore, Tstore);
   BK_CHECK_LAUNCH();
-  hipStream_t saved = ctx->stream;
-  ctx->stream = ps;   // gemm() launches on ctx->stream
-  int rc = BIGKRLS_OK;
-  for (int q = 0; q < ng && rc == BIGKRLS_OK; ++q) {
+  for (int q = 0; q < ng; ++q) {
+    StreamScope on(ctx, ps);   // gemm() launches on ctx->stream
     const int g = plan.g[q], m0 = n - plan.k0[q] - b, w = b * g;
     const double* Vb = Vstore + plan.voff[q];
-    if (g > 1) rc = gemm(ctx, 1, 0, w, w, m0, 1.0, Vb, m0, Vb, m0, 0.0, Gstore + (int64_t)q * LT * LT, LT);   // Gb = Vb' Vb
+    if (g > 1) BK_TRY(gemm(ctx, 1, 0, w, w, m0, 1.0, Vb, m0, Vb, m0, 0.0, Gstore + (int64_t)q * LT * LT, LT));   // Gb = Vb' Vb
   }
-  ctx->stream = saved;
-  BK_TRY(rc);
   for (int j = 1; j < gmax; ++j)
     for (int mode = 0; mode < 2; ++mode)
       hipLaunchKernelGGL(bt1_merge_step, dim3(j, ng), dim3(256), 0, ps, (const Bt1Group*)d_groups, j, mode, LT, Tall,

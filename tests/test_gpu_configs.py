@@ -517,7 +517,7 @@ def test_lanczos_sampled_verification_matches_full_rayleigh_ritz(ctx, monkeypatc
 def test_aggregated_trailing_update_matches_one_update_per_panel(ctx, monkeypatch):
     """Stage 1 applies the trailing update for four panels at once (k = 512) while the trailing matrix has at least
     12800 rows, for two at once (k = 256, as two pieces of equal area) down to 10752, with thin corrections of
-    everything that reads the stale matrix (csrc/eigen_2stage.inc, "aggregated phase"). n = 15700 runs ten groups
+    everything that reads the stale matrix (csrc/eigen_2stage.inc, "aggregated phase"). n = 15700 runs eleven groups
     of four, the hand-over to pairs and the one to one update per panel; BIGKRLS_S1AGG=2 starts with pairs,
     BIGKRLS_S1AGG=0 is the plain loop. Same eigenvalues to rounding, kept eigenvectors with residual and
     orthogonality at rounding level."""
