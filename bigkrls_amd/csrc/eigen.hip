@@ -23,6 +23,7 @@
 // returns them to the user: R/bigKRLS_Rcpp_functions.R:186, quirk Q9).
 #include "common.h"
 #include "s1sched.h"
+#include "dcplan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -518,23 +519,13 @@ int tridiagonalize(bigkrls_ctx* ctx, double* W, int n, double* d, double* e, dou
 // =============================================================================
 // phase 2: divide & conquer
 // =============================================================================
-struct MergeDesc {
-  int s, n1, m, K;
-  int k1, k2, k3, Kneed;
-  int rot_off, nrot, ndef, rev;   // rev: columns stored in descending order of the roots (the root of the tree)
-  double rho;
-  // where the merge's secular vectors go: column c at Ubase + uoff + c * uld -- the block (s, s) of the N x N buffer U
-  // (uoff = s + s N, uld = N), or, on a level whose operators stay factored, a contiguous K x K block of the stash
-  long long uoff;
-  int uld, pad_;
-};
+// (MergeDesc, the descriptor of one merge that the kernels below read, and all host arithmetic: csrc/dcplan.h)
 
 // Leaves of the divide & conquer tree (17..32 rows when n > 64): implicit QL with eigenvectors
 // (EISPACK tql2 / "tqli"), one wave per leaf. Every lane runs the same scalar recurrence on d, e in
 // LDS (identical values, so the redundant stores are harmless) and lane r applies the rotations to
 // row r of the eigenvector block. Replaces the five lowest merge levels (of ~1 ms of launches, copies
-// and synchronisations each) by one launch.
-constexpr int DC_LEAF = 32;
+// and synchronisations each) by one launch. (DC_LEAF: csrc/dcplan.h)
 __global__ __launch_bounds__(64) void dc_leaf_ql(const int2* __restrict__ leaves, const double* __restrict__ dd,
                                                  const double* __restrict__ ee, double* __restrict__ Q0,
                                                  double* __restrict__ Q1, int64_t ld,
@@ -1010,26 +1001,14 @@ __global__ void gather_cols(int n, int nv, const int* __restrict__ src, const do
   }
 }
 
-struct Node {
-  int s, m, left, right, depth;
-  std::vector<double> dv;  // eigenvalue of storage column s+t
-  int ksorted = 0;         // dv[0 .. ksorted) is ascending (the secular roots of the merge that produced the node)
+// wall-clock of the host between two points, for the BIGKRLS_VERBOSE lines: ms() since the start or the last lap()
+struct Stopwatch {
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+  double lap() { const double m = ms(); t0 = std::chrono::steady_clock::now(); return m; }
 };
 
-// host side of one merge (LAPACK dlaed2's scan, re-derived): fills the packed
-// per-level arrays at offset s.
-// The n-long arrays are slices of the context's pinned upload arena (PinnedStage::fixed), laid out like their device
-// copies -- [dlam | w] and [pole_of_row | srccol | cpos | defsrc | defdst] -- so that a level uploads them with two
-// copies straight from where host_merge wrote them.
-struct LevelArrays {
-  double *dlam = nullptr, *w = nullptr;
-  int *pole_of_row = nullptr, *srccol = nullptr, *cpos = nullptr, *defsrc = nullptr, *defdst = nullptr;
-  std::vector<int> rowpos;
-  std::vector<double> rc, rs;
-  std::vector<int> ra, rb;
-};
-
-// one level whose merge operators stay factored (see divide_conquer)
+// one level whose merge operators stay factored (see DivideConquer)
 struct LazyLevel {
   std::vector<MergeDesc> descs;
   std::vector<int> srccol, defsrc, ra, rb, rot_merges;
@@ -1038,268 +1017,259 @@ struct LazyLevel {
   int max_m = 0, maxK = 0;
 };
 
-void host_merge(const Node& L, const Node& R, double ecut, const double* zraw, MergeDesc& md,
-                LevelArrays& A, std::vector<double>& defvals) {
-  const int n1 = L.m, n2 = R.m, m = n1 + n2, s = L.s;
-  const double theta = (ecut >= 0.0) ? 1.0 : -1.0;
-  const double rho = 2.0 * std::fabs(ecut);
-  // scratch reused across the merges of a level (thousands of small merges at the bottom of the tree)
-  static thread_local std::vector<double> z, D;
-  static thread_local std::vector<std::pair<double, int>> keyed, kbuf;
-  static thread_local std::vector<int> order, typ, nd, df;
-  z.resize(m); D.resize(m); keyed.resize(m); kbuf.resize(m); order.resize(m); typ.resize(m);
-  nd.clear(); df.clear();
-  const double isq2 = 1.0 / std::sqrt(2.0);
-  double dmax = 0.0, zmax = 0.0;
-  for (int t = 0; t < m; ++t) {
-    z[t] = zraw[s + t] * ((t < n1) ? 1.0 : theta) * isq2;
-    D[t] = (t < n1) ? L.dv[t] : R.dv[t - n1];
-    keyed[t] = {D[t], t};
-    typ[t] = (t < n1) ? 1 : 3;
-    dmax = std::max(dmax, std::fabs(D[t]));
-    zmax = std::max(zmax, std::fabs(z[t]));
-  }
-  // ascending in D, ties in storage order: what a stable sort of the indices gives, on (value, index) pairs. Each
-  // child's list is its ascending secular roots followed by its deflated values: only the two tails are sorted, the
-  // four runs are merged (the root of an N = 20 000 tree: 0.25 instead of 0.7 ms)
-  {
-    int kl = std::min(L.ksorted, n1), kr = std::min(R.ksorted, m - n1);
-    if (!std::is_sorted(keyed.begin(), keyed.begin() + kl)) kl = 0;          // (never seen; costs O(K))
-    if (!std::is_sorted(keyed.begin() + n1, keyed.begin() + n1 + kr)) kr = 0;
-    std::sort(keyed.begin() + kl, keyed.begin() + n1);
-    std::sort(keyed.begin() + n1 + kr, keyed.end());
-    // (std::merge into the scratch list and back: std::inplace_merge allocates its buffer at every call -- three calls
-    //  per merge, thousands of merges per level)
-    std::merge(keyed.begin(), keyed.begin() + kl, keyed.begin() + kl, keyed.begin() + n1, kbuf.begin());
-    std::merge(keyed.begin() + n1, keyed.begin() + n1 + kr, keyed.begin() + n1 + kr, keyed.end(), kbuf.begin() + n1);
-    std::merge(kbuf.begin(), kbuf.begin() + n1, kbuf.begin() + n1, kbuf.end(), keyed.begin());
-  }
-  for (int t = 0; t < m; ++t) order[t] = keyed[t].second;
-  const double tol = 8.0 * DEPS * std::max(dmax, zmax);
-  md.s = s; md.n1 = n1; md.m = m; md.rho = rho;
-  md.rot_off = (int)A.ra.size(); md.nrot = 0;
-  if (rho * zmax <= tol) {
-    for (int t : order) df.push_back(t);
-  } else {
-    int pj = -1;
-    for (int t : order) {
-      if (rho * std::fabs(z[t]) <= tol) { df.push_back(t); typ[t] = 4; continue; }
-      if (pj < 0) { pj = t; continue; }
-      double sv = z[pj], cv = z[t];
-      const double tt = D[t] - D[pj];
-      // dlaed2's test |tt c s| <= tol with c = z_t / tau, s = -z_pj / tau, tau = hypot(z_t, z_pj), in the form that
-      // needs neither the root nor the divisions (z is normalised: no overflow): they are only formed for the rare pair
-      // that deflates -- the scan visits every non-deflated entry of every level, and hypot + two divisions per entry
-      // were most of its time
-      const double ss = cv * cv + sv * sv;
-      const double tau_safe = (ss > 1e-280) ? 0.0 : std::hypot(cv, sv);     // (squares that underflow: the safe form)
-      const bool defl = (ss > 1e-280) ? (std::fabs(tt * cv * sv) <= tol * ss)
-                                      : (std::fabs(tt * (cv / tau_safe) * (sv / tau_safe)) <= tol);
-      if (defl) {
-        const double tau = (ss > 1e-280) ? std::sqrt(ss) : tau_safe;
-        cv /= tau; sv = -sv / tau;
-        z[t] = tau; z[pj] = 0.0;
-        if (typ[t] != typ[pj]) typ[t] = 2;
-        typ[pj] = 4;
-        A.ra.push_back(pj); A.rb.push_back(t); A.rc.push_back(cv); A.rs.push_back(sv);
-        md.nrot++;
-        const double tmp = D[pj] * cv * cv + D[t] * sv * sv;
-        D[t] = D[pj] * sv * sv + D[t] * cv * cv;
-        D[pj] = tmp;
-        df.push_back(pj);
-        pj = t;
-      } else {
-        nd.push_back(pj);
-        pj = t;
-      }
-    }
-    if (pj >= 0) nd.push_back(pj);
-  }
-  const int K = (int)nd.size();
-  md.K = K; md.Kneed = K; md.ndef = m - K;
-  // poles ascending = nd order; rows of U grouped by column type 1,2,3
-  int k1 = 0, k2 = 0, k3 = 0;
-  for (int t : nd) { if (typ[t] == 1) ++k1; else if (typ[t] == 2) ++k2; else ++k3; }
-  md.k1 = k1; md.k2 = k2; md.k3 = k3;
-  int p1 = 0, p2 = k1, p3 = k1 + k2;
-  for (int i = 0; i < K; ++i) {
-    const int t = nd[i];
-    A.dlam[s + i] = D[t];
-    A.w[s + i] = z[t];
-    int row = (typ[t] == 1) ? p1++ : (typ[t] == 2) ? p2++ : p3++;
-    A.rowpos[s + i] = row;
-    A.pole_of_row[s + row] = i;
-    A.srccol[s + row] = t;
-    A.cpos[s + i] = i;
-  }
-  defvals.resize(m - K);
-  for (int q = 0; q < m - K; ++q) {
-    A.defsrc[s + q] = df[q];
-    A.defdst[s + q] = K + q;
-    defvals[q] = D[df[q]];
-  }
-}
-
 // pinned upload arena of one decomposition: the level arrays of the divide & conquer + one level's other uploads
 static size_t dc_stage_bytes(int n) {
   return (size_t)n * (2 * sizeof(double) + 5 * sizeof(int)) + (size_t)n * 96 + ((size_t)2 << 20);
 }
 
-int divide_conquer(bigkrls_ctx* ctx, int n, const std::vector<double>& hd,
-                   const std::vector<double>& he, double* Q0, double* Q1, double* U,
-                   int64_t n_vals, int64_t n_vecs_max, double keep_thresh,
-                   std::vector<double>& vals_desc, std::vector<int>& src_cols, double** Qfinal,
-                   bool allow_lazy = true) {
-  hipStream_t st = ctx->stream;
-  const int64_t N = n;
-  // ---- tree -----------------------------------------------------------------
-  // (BIGKRLS_DCLEAF=1: tear down to 1 x 1 leaves, no QL leaf solver)
-  const char* leaf_env = getenv("BIGKRLS_DCLEAF");
-  const int leaf_max = (n > 2 * DC_LEAF && !(leaf_env && std::string(leaf_env) == "1")) ? DC_LEAF : 1;
-  std::vector<Node> nodes;
-  nodes.reserve(2 * n);
-  std::vector<double> dadj = hd;
-  {
-    struct Item { int s, m, depth, parent, side; };
-    std::vector<Item> stack;
-    stack.push_back({0, n, 0, -1, 0});
-    while (!stack.empty()) {
-      Item it = stack.back();
-      stack.pop_back();
-      Node nd;
-      nd.s = it.s; nd.m = it.m; nd.left = nd.right = -1; nd.depth = it.depth;
-      const int id = (int)nodes.size();
-      nodes.push_back(nd);
-      if (it.parent >= 0) {
-        if (it.side == 0) nodes[it.parent].left = id; else nodes[it.parent].right = id;
-      }
-      if (it.m > leaf_max) {
-        const int n1 = it.m / 2;
-        const int cut = it.s + n1 - 1;  // e[cut] couples rows cut, cut+1
-        const double rho = std::fabs(he[cut]);
-        dadj[cut] -= rho;
-        dadj[cut + 1] -= rho;
-        stack.push_back({it.s, n1, it.depth + 1, id, 0});
-        stack.push_back({it.s + n1, it.m - n1, it.depth + 1, id, 1});
-      }
-    }
-  }
-  int maxdepth = 0;
-  for (auto& nd : nodes) {
-    maxdepth = std::max(maxdepth, nd.depth);
-    if (nd.m == 1) nd.dv.assign(1, dadj[nd.s]);
-  }
-  std::vector<std::vector<int>> by_depth(maxdepth + 1);
-  for (int id = 0; id < (int)nodes.size(); ++id)
-    if (nodes[id].left >= 0) by_depth[nodes[id].depth].push_back(id);
+// the merges [b0, b0 + nb) of one launch with one row of workgroups per merge: grid.y holds at most 65 535
+struct Batch { int b0, nb; };
+struct Batches {
+  int total;
+  struct It {
+    int b0, total;
+    Batch operator*() const { return {b0, std::min(65535, total - b0)}; }
+    It& operator++() { b0 += 65535; return *this; }
+    bool operator!=(const It&) const { return b0 < total; }
+  };
+  It begin() const { return {0, total}; }
+  It end() const { return {total, total}; }
+};
 
-  // ---- device state ---------------------------------------------------------
-  // every host -> device upload below goes through the context's pinned arena: the level arrays live in it (uploaded
-  // from where they are written), everything else is copied into a slice of the current level's cycle
-  PinnedStage stage(ctx);
-  BK_TRY(stage.reserve(dc_stage_bytes(n)));
+static GemmDesc gemm_desc(const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int64_t ldc, int m,
+                          int n, int k, const int* kidx) {
+  GemmDesc g{};
+  g.A = A; g.B = B; g.C = C;
+  g.lda = lda; g.ldb = ldb; g.ldc = ldc;
+  g.m = m; g.n = n; g.k = k; g.kidx = kidx;
+  return g;
+}
+
+// Eigenvalues (descending, vals_desc) and eigenvectors of the tridiagonal matrix (hd, he): the columns src_cols of
+// *Qfinal (one of Q0 / Q1 / a part of U) are the kept ones. The host arithmetic is csrc/dcplan.h; here are the phases
+// that launch, upload and read back. One pass: tree, Q = I, QL leaves, then level by level from the bottom
+//   gather z -> host deflation scans -> uploads -> rotations -> secular equation -> roots back -> vectors -> products.
+// Few eigenvectors wanted (truncation or Neig << N): the merge operators of the top DC_LAZY_TOP
+// levels below the root stay factored. Q of depth Dl+1 is the last one formed; above it only the
+// first and last row of every node's eigenvector matrix (what the parent's z needs) are
+// propagated, the K x K secular-vector blocks are stashed, and at the end the operators are
+// applied right-to-left to the N x nv kept columns of the root:
+//   Q[:, kept] = Q_{Dl+1} M_Dl ... M_1 M_0[:, kept]      (2 K^2 nv flops per merge instead of 2 m K^2).
+// BIGKRLS_DC=explicit forms every level, =factored forces this path at any size; a root that
+// keeps more than N/8 columns redoes the divide & conquer explicitly: a second pass with allow_lazy = false.
+struct DcArgs {      // (the arguments of divide_conquer)
+  bigkrls_ctx* ctx;
+  int n;
+  const std::vector<double>&hd, &he;
+  double *Q0, *Q1, *U;
+  int64_t n_vals, n_vecs_max;
+  double keep_thresh;
+  std::vector<double>& vals_desc;
+  std::vector<int>& src_cols;
+  double** Qfinal;
+};
+
+struct DivideConquer : DcArgs {
+  const hipStream_t st = ctx->stream;
+  const int64_t N = n;
+  const bool chatty = verbose();
+  // ---- one pass (begin_pass): the tree, which levels stay factored, the pinned arena and the level arrays in it
+  DcTree tree;
+  int Dl = -1;                       // the deepest level whose merge operators stay factored (-1: none)
+  bool redo = false;                 // the root kept too many columns for the factored form: one more pass, all explicit
+  PinnedStage stage{ctx};
   LevelArrays A;
-  A.dlam = (double*)stage.fixed((size_t)2 * n * sizeof(double));
-  int* a_int = (int*)stage.fixed((size_t)5 * n * sizeof(int));
-  BK_REQUIRE(A.dlam && a_int, "divide & conquer: pinned arena too small");
-  A.w = A.dlam + n;
-  A.pole_of_row = a_int; A.srccol = a_int + n; A.cpos = a_int + 2 * n; A.defsrc = a_int + 3 * n; A.defdst = a_int + 4 * n;
-  std::memset(A.dlam, 0, (size_t)2 * n * sizeof(double));
-  std::memset(a_int, 0, (size_t)5 * n * sizeof(int));
-  A.rowpos.resize(n);
-  // Few eigenvectors wanted (truncation or Neig << N): the merge operators of the top LAZY_TOP
-  // levels below the root stay factored. Q of depth Dl+1 is the last one formed; above it only the
-  // first and last row of every node's eigenvector matrix (what the parent's z needs) are
-  // propagated, the K x K secular-vector blocks are stashed, and at the end the operators are
-  // applied right-to-left to the N x nv kept columns of the root:
-  //   Q[:, kept] = Q_{Dl+1} M_Dl ... M_1 M_0[:, kept]      (2 K^2 nv flops per merge instead of 2 m K^2).
-  // BIGKRLS_DC=explicit forms every level, =factored forces this path at any size; a root that
-  // keeps more than N/8 columns redoes the divide & conquer explicitly.
-  constexpr int LAZY_TOP = 3;
-  const char* dc_env = getenv("BIGKRLS_DC");
-  const std::string dc_mode = dc_env ? dc_env : "";
-  const bool lazy = allow_lazy && maxdepth - 1 > LAZY_TOP && dc_mode != "explicit" &&
-                    ((n >= 4096 && (keep_thresh > 0.0 || n_vecs_max * 8 <= N)) ||
-                     (dc_mode == "factored" && n >= 128));   // (forced: the tests run small hard spectra)
-  const int Dl = lazy ? LAZY_TOP : -1;
+  MergeScratch scratch;
+  // ---- workspace (carve_workspace), every array n long. d_gf .. d_ol: factored levels, gathered first / last rows in,
+  // merged rows out. d_dorg, d_tau: per root, the pole it is measured from and its offset from that pole.
+  static constexpr int DOUBLE_ARRAYS = 14, INT_ARRAYS = 11;      // (of SLOT_EIG_MISC / SLOT_EIG_INT; the last of each is unused)
+  double *d_z = nullptr, *d_dlam = nullptr, *d_w = nullptr, *d_lam = nullptr, *d_zhat = nullptr, *d_rc = nullptr,
+         *d_rs = nullptr, *d_gf = nullptr, *d_gl = nullptr, *d_of = nullptr, *d_ol = nullptr, *d_dorg = nullptr,
+         *d_tau = nullptr;
+  int *d_rowpos = nullptr, *d_pole = nullptr, *d_srccol = nullptr, *d_cpos = nullptr, *d_defsrc = nullptr,
+      *d_defdst = nullptr, *d_ra = nullptr, *d_rb = nullptr, *d_rotids = nullptr, *d_iota = nullptr;
+  MergeDesc* d_descs = nullptr;
+  GemmDesc* d_gdescs = nullptr;
+  // ---- the level loop
+  double *Qc = nullptr, *Qn = nullptr;                     // the copy of Q the children's blocks are in / the parents' go to
+  std::vector<double> hz, hlam;
+  int64_t nv_final = 0;
+  std::vector<LazyLevel> lazy_levels;                      // indexed by depth
+  std::vector<double> bf, bl, yf, yl;                      // boundary rows of the current frontier / of a level
+  double* stash = nullptr;
+  int64_t stash_used = 0;
+  // ---- the apply phase: X, its ping-pong partner and the product buffer (in U), the descriptors of a level's products
+  double *X_cur = nullptr, *X_oth = nullptr, *X_prod = nullptr;
+  std::vector<GemmDesc> apply_gd;
+
+  explicit DivideConquer(const DcArgs& a) : DcArgs(a) {}
+
+  static int64_t int_workspace_bytes(int n) { return (int64_t)INT_ARRAYS * n * sizeof(int); }
+
+  bool lazy() const { return Dl >= 0; }
+  bool level_factored(int depth) const { return lazy() && depth <= Dl; }   // this level's merge operators stay factored
+  bool kids_factored(int depth) const { return lazy() && depth < Dl; }     // ... and so do the children's eigenvector matrices
+  // where a level's secular vectors are written: straight into the stash on a factored level below the root (their
+  // K x K blocks used to be formed in U and copied: 1.9 GB of copies at N = 20 000), else block (s, s) of U
+  bool u_to_stash(int depth) const { return level_factored(depth) && depth != 0; }
+
+  // one level of the tree: its merges, what the host scans found, the verbose laps
+  struct Level {
+    int depth = 0, nm = 0, max_m = 0, maxK = 0, max_ndef = 0, maxKneed = 0;
+    const std::vector<int>* ids = nullptr;
+    std::vector<MergeDesc> descs;
+    std::vector<std::vector<double>> defvals;
+    std::vector<int> rot_merges;
+    std::vector<int64_t> stash_off;
+    // Descriptors of this level's batched products: a source of an asynchronous host -> device copy, declared at the
+    // level's scope so that it lives until the synchronisation at the end of the level. (It used to be a local of the
+    // branch that fills it, destroyed before that synchronisation. On this runtime that was harmless -- hipMemcpyAsync
+    // takes its copy of a pageable source before it returns, at every size, also in bursts and under load:
+    // tools/pageable_h2d_probe.hip, BIGKRLS_FAULT=dc_gd_clobber -- but nothing in the API promises it.)
+    std::vector<GemmDesc> gd;
+    Stopwatch total, mark;
+    double ms_split[5] = {0, 0, 0, 0, 0};   // (verbose) wait for z | host scans | uploads + secular | wait for the roots | rest
+    void lap(int slot) { ms_split[slot] += mark.lap(); }
+  };
+
+  int run() {
+    for (bool allow_lazy : {true, false}) {
+      BK_TRY(begin_pass(allow_lazy));
+      BK_TRY(init_q());
+      BK_TRY(carve_workspace());
+      BK_TRY(solve_leaves());
+      for (int depth = tree.maxdepth - 1; depth >= 0 && !redo; --depth)
+        if (!tree.by_depth[depth].empty()) BK_TRY(merge_level(depth));
+      if (!redo) break;
+    }
+    if (n == 1) {
+      vals_desc.assign(1, tree.dadj[0]);
+      src_cols.assign(1, 0);
+      nv_final = 1;
+    }
+    if (lazy()) return apply_factored();
+    *Qfinal = Qc;
+    return BIGKRLS_OK;
+  }
+
+  int merge_level(int depth) {
+    Level lv;     // host vectors (gd, descs, A.*) are sources of asynchronous copies: alive and unmodified up to end_level
+    BK_TRY(begin_level(depth, lv));
+    BK_TRY(kids_factored(depth) ? gather_z_from_rows(lv) : gather_z(lv));
+    scan_level(lv);
+    BK_TRY(upload_level(lv));
+    BK_TRY(rotate_children(lv));
+    BK_TRY(secular(lv));
+    BK_TRY(read_roots(lv));
+    if (depth == 0) BK_TRY(select_at_root(lv));
+    if (redo) return BIGKRLS_OK;
+    BK_TRY(vectors(lv));
+    if (level_factored(depth)) {
+      BK_TRY(push_boundary_rows(lv));
+    } else {
+      BK_TRY(explicit_products(lv));
+      BK_TRY(copy_deflated(lv));
+    }
+    return end_level(lv);
+  }
+
+  // ---- the tree, the pinned arena, which levels stay factored. Everything a pass leaves behind starts afresh: the
+  // second pass issues what a decomposition that never went factored issues.
+  int begin_pass(bool allow_lazy) {
+    dc_build_tree(n, hd, he, dc_leaf_max(n, getenv("BIGKRLS_DCLEAF")), tree);
+    // every host -> device upload below goes through the context's pinned arena: the level arrays live in it (uploaded
+    // from where they are written), everything else is copied into a slice of the current level's cycle
+    stage = PinnedStage(ctx);
+    BK_TRY(stage.reserve(dc_stage_bytes(n)));
+    A = LevelArrays{};
+    A.dlam = (double*)stage.fixed((size_t)2 * n * sizeof(double));
+    int* a_int = (int*)stage.fixed((size_t)5 * n * sizeof(int));
+    BK_REQUIRE(A.dlam && a_int, "divide & conquer: pinned arena too small");
+    A.w = A.dlam + n;
+    A.pole_of_row = a_int; A.srccol = a_int + n; A.cpos = a_int + 2 * n; A.defsrc = a_int + 3 * n; A.defdst = a_int + 4 * n;
+    std::memset(A.dlam, 0, (size_t)2 * n * sizeof(double));
+    std::memset(a_int, 0, (size_t)5 * n * sizeof(int));
+    A.rowpos.resize(n);
+    const bool go_lazy = dc_lazy(n, tree.maxdepth, keep_thresh, n_vecs_max, getenv("BIGKRLS_DC"), allow_lazy);
+    Dl = go_lazy ? DC_LAZY_TOP : -1;
+    redo = false;
+    Qc = Q0;
+    Qn = Q1;
+    hz.assign(n, 0.0);
+    hlam.assign(n, 0.0);
+    nv_final = 0;
+    lazy_levels.assign(lazy() ? Dl + 1 : 0, LazyLevel());
+    stash = nullptr;
+    stash_used = 0;
+    for (std::vector<double>* v : {&bf, &bl, &yf, &yl}) v->assign(lazy() ? n : 0, 0.0);
+    return BIGKRLS_OK;
+  }
+
   // Both copies of Q start as the identity. What is READ of them are the diagonal blocks of the nodes whose eigenvector
   // matrices are formed explicitly: a merge reads its two children's blocks and the zero blocks between them (rotations
   // and deflated columns run over the parent's full height) and writes the parent's whole block in the other copy.
   // With factored top levels the largest such blocks are the depth-Dl nodes' (8 blocks of 2 500^2 at N = 20 000: 0.8 GB
   // of zeros instead of 6.4 GB, -1.1 ms); without, the whole matrix.
-  std::vector<int> zb;       // (s, m) of the depth-Dl nodes
-  if (lazy)
-    for (const Node& nd : nodes)
-      if (nd.depth == Dl && nd.m > 0) { zb.push_back(nd.s); zb.push_back(nd.m); }
-  if (lazy && !zb.empty()) {
-    // (the list goes up through the integer workspace of the levels, which is first used after the leaves)
-    void* pzi = nullptr;
-    BK_TRY(ws_get(ctx, SLOT_EIG_INT, (int64_t)11 * n * sizeof(int), &pzi));
-    int* zlist = (int*)stage.fixed(zb.size() * sizeof(int));     // (a slice that no later upload of this call reuses)
-    BK_REQUIRE(zlist, "divide & conquer: pinned arena too small");
-    std::memcpy(zlist, zb.data(), zb.size() * sizeof(int));
-    BK_TRY(stage.send(pzi, zlist, zb.size() * sizeof(int)));
-    int zmax = 0;
-    for (size_t i = 1; i < zb.size(); i += 2) zmax = std::max(zmax, zb[i]);
-    hipLaunchKernelGGL(dc_zero_blocks, dim3(zmax, (unsigned)(zb.size() / 2)), dim3(256), 0, st, (const int2*)pzi, Q0, Q1, N);
+  int init_q() {
+    const std::vector<int> zb = lazy() ? dc_blocks_at_depth(tree, Dl) : std::vector<int>();   // (s, m) of the depth-Dl nodes
+    if (!zb.empty()) {
+      // The list goes up through the integer workspace of the levels, which is first used after the leaves. ALIAS: pzi
+      // is the address carve_workspace names d_rowpos, which solve_leaves fills with the leaf list -- behind
+      // dc_zero_blocks on the one stream.
+      void* pzi = nullptr;
+      BK_TRY(ws_get(ctx, SLOT_EIG_INT, int_workspace_bytes(n), &pzi));
+      int* zlist = (int*)stage.fixed(zb.size() * sizeof(int));     // (a slice that no later upload of this call reuses)
+      BK_REQUIRE(zlist, "divide & conquer: pinned arena too small");
+      std::memcpy(zlist, zb.data(), zb.size() * sizeof(int));
+      BK_TRY(stage.send(pzi, zlist, zb.size() * sizeof(int)));
+      int zmax = 0;
+      for (size_t i = 1; i < zb.size(); i += 2) zmax = std::max(zmax, zb[i]);
+      hipLaunchKernelGGL(dc_zero_blocks, dim3(zmax, (unsigned)(zb.size() / 2)), dim3(256), 0, st, (const int2*)pzi, Q0, Q1, N);
+      BK_CHECK_LAUNCH();
+    } else {
+      BK_HIP(hipMemsetAsync(Q0, 0, (size_t)N * N * sizeof(double), st));
+      BK_HIP(hipMemsetAsync(Q1, 0, (size_t)N * N * sizeof(double), st));
+    }
+    hipLaunchKernelGGL(dc_init_identity, dim3((n + 255) / 256), dim3(256), 0, st, Q0, n);
+    hipLaunchKernelGGL(dc_init_identity, dim3((n + 255) / 256), dim3(256), 0, st, Q1, n);
     BK_CHECK_LAUNCH();
-  } else {
-    BK_HIP(hipMemsetAsync(Q0, 0, (size_t)N * N * sizeof(double), st));
-    BK_HIP(hipMemsetAsync(Q1, 0, (size_t)N * N * sizeof(double), st));
+    return BIGKRLS_OK;
   }
-  hipLaunchKernelGGL(dc_init_identity, dim3((n + 255) / 256), dim3(256), 0, st, Q0, n);
-  hipLaunchKernelGGL(dc_init_identity, dim3((n + 255) / 256), dim3(256), 0, st, Q1, n);
-  BK_CHECK_LAUNCH();
-  // double arrays: z, dlam, w, lam, zhat, rc, rs  (7n) ; int arrays: 8n ; descs
-  void* pd = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_EIG_MISC, (int64_t)14 * n * sizeof(double), &pd));
-  double* d_z = (double*)pd;
-  double* d_dlam = d_z + n;
-  double* d_w = d_dlam + n;
-  double* d_lam = d_w + n;
-  double* d_zhat = d_lam + n;
-  double* d_rc = d_zhat + n;
-  double* d_rs = d_rc + n;
-  double* d_gf = d_rs + n;      // factored levels: gathered first / last rows in, merged rows out
-  double* d_gl = d_gf + n;
-  double* d_of = d_gl + n;
-  double* d_ol = d_of + n;
-  double* d_dorg = d_ol + n;    // per root: the pole it is measured from, and its offset from that pole
-  double* d_tau = d_dorg + n;
-  void* pi = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_EIG_INT, (int64_t)11 * n * sizeof(int), &pi));
-  int* d_rowpos = (int*)pi;
-  int* d_pole = d_rowpos + n;
-  int* d_srccol = d_pole + n;
-  int* d_cpos = d_srccol + n;
-  int* d_defsrc = d_cpos + n;
-  int* d_defdst = d_defsrc + n;
-  int* d_ra = d_defdst + n;
-  int* d_rb = d_ra + n;
-  int* d_rotids = d_rb + n;
-  int* d_iota = d_rotids + n;
-  const int max_merges = n / 2 + 1;
-  void* pdesc = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_EIG_DESC,
-                (int64_t)max_merges * (sizeof(MergeDesc) + 2 * sizeof(GemmDesc)), &pdesc));
-  MergeDesc* d_descs = (MergeDesc*)pdesc;
-  GemmDesc* d_gdescs = (GemmDesc*)(d_descs + max_merges);
 
-  double* Qc = Q0;
-  double* Qn = Q1;
-  std::vector<double> hz(n), hlam(n);
+  // ---- workspace: 14 n doubles of SLOT_EIG_MISC (13 arrays), 11 n ints of SLOT_EIG_INT (10 arrays), and n / 2 + 1
+  // merge descriptors with two product descriptors each in SLOT_EIG_DESC -- the two lists give the pointers, their
+  // lengths the sizes
+  int carve_workspace() {
+    double** const doubles[] = {&d_z, &d_dlam, &d_w, &d_lam, &d_zhat, &d_rc, &d_rs, &d_gf, &d_gl, &d_of, &d_ol, &d_dorg,
+                                &d_tau, nullptr};
+    int** const ints[] = {&d_rowpos, &d_pole, &d_srccol, &d_cpos, &d_defsrc, &d_defdst, &d_ra, &d_rb, &d_rotids, &d_iota,
+                          nullptr};
+    static_assert(sizeof doubles / sizeof *doubles == DOUBLE_ARRAYS && sizeof ints / sizeof *ints == INT_ARRAYS,
+                  "the slots keep their sizes");
+    void *pd = nullptr, *pi = nullptr, *pdesc = nullptr;
+    BK_TRY(ws_get(ctx, SLOT_EIG_MISC, (int64_t)DOUBLE_ARRAYS * n * sizeof(double), &pd));
+    BK_TRY(ws_get(ctx, SLOT_EIG_INT, int_workspace_bytes(n), &pi));
+    for (int i = 0; i < DOUBLE_ARRAYS; ++i)
+      if (doubles[i]) *doubles[i] = (double*)pd + (int64_t)i * n;
+    for (int i = 0; i < INT_ARRAYS; ++i)
+      if (ints[i]) *ints[i] = (int*)pi + (int64_t)i * n;
+    const int max_merges = n / 2 + 1;
+    BK_TRY(ws_get(ctx, SLOT_EIG_DESC, (int64_t)max_merges * (sizeof(MergeDesc) + 2 * sizeof(GemmDesc)), &pdesc));
+    d_descs = (MergeDesc*)pdesc;
+    d_gdescs = (GemmDesc*)(d_descs + max_merges);
+    return BIGKRLS_OK;
+  }
 
   // ---- leaves larger than 1 x 1: QL on the device, eigenvector blocks into both copies of Q --------
-  if (leaf_max > 1) {
-    const auto t_leaf = std::chrono::steady_clock::now();
-    std::vector<int> lf;   // (s, m) pairs
-    for (const Node& nd : nodes)
-      if (nd.left < 0 && nd.m > 1) { lf.push_back(nd.s); lf.push_back(nd.m); }
+  int solve_leaves() {
+    if (tree.leaf_max <= 1) return BIGKRLS_OK;
+    Stopwatch t_leaf;
+    const std::vector<int> lf = dc_ql_leaves(tree);   // (s, m) pairs
     const int nleaf = (int)lf.size() / 2;
     if (nleaf > 0) {
-      int* d_fail = d_iota;                        // (d_iota is filled later, only on the factored path)
+      int* d_fail = d_iota;    // ALIAS: d_iota is filled later (apply_root_columns), only on the factored path, behind this on the one stream
       BK_HIP(hipMemsetAsync(d_fail, 0, sizeof(int), st));
-      BK_TRY(stage.put(d_dlam, dadj.data(), n * sizeof(double)));
+      BK_TRY(stage.put(d_dlam, tree.dadj.data(), n * sizeof(double)));
       BK_TRY(stage.put(d_w, he.data(), n * sizeof(double)));
       BK_TRY(stage.put(d_rowpos, lf.data(), lf.size() * sizeof(int)));
       hipLaunchKernelGGL(dc_leaf_ql, dim3(nleaf), dim3(64), 0, st, (const int2*)d_rowpos, (const double*)d_dlam,
@@ -1314,470 +1284,400 @@ int divide_conquer(bigkrls_ctx* ctx, int n, const std::vector<double>& hd,
         set_error("eigen: the QL iteration of a divide & conquer leaf did not converge");
         return BIGKRLS_ENOCONV;
       }
-      for (Node& nd : nodes)
+      for (Node& nd : tree.nodes)
         if (nd.left < 0 && nd.m > 1) nd.dv.assign(hlam.begin() + nd.s, hlam.begin() + nd.s + nd.m);
       if (trace_fine()) {
         BK_TRY(trace_host("R:dc_leaf_lam", hlam.data(), n, nleaf));
         BK_TRY(trace_point(ctx, st, "R:dc_leaf_Q", Q0, N * N, nleaf));
       }
     }
-    if (verbose())
-      fprintf(stderr, "[bigkrls]   d&c leaves: %6d of up to %d rows (QL) %8.2f ms\n", nleaf, leaf_max,
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_leaf).count());
+    if (chatty)
+      fprintf(stderr, "[bigkrls]   d&c leaves: %6d of up to %d rows (QL) %8.2f ms\n", nleaf, tree.leaf_max, t_leaf.ms());
+    return BIGKRLS_OK;
   }
 
-  int64_t nv_final = 0;
-  const bool verbose = bk::verbose();
-  std::vector<LazyLevel> lazy_levels(lazy ? Dl + 1 : 0);   // indexed by depth
-  std::vector<double> bf, bl, yf, yl;                      // boundary rows of the current frontier / of a level
-  double* stash = nullptr;
-  int64_t stash_used = 0;
-  if (lazy) { bf.assign(n, 0.0); bl.assign(n, 0.0); yf.assign(n, 0.0); yl.assign(n, 0.0); }
-  for (int depth = maxdepth - 1; depth >= 0; --depth) {
-    const std::vector<int>& ids = by_depth[depth];
-    const int nm = (int)ids.size();
-    if (nm == 0) continue;
-    const auto t_level = std::chrono::steady_clock::now();
-    auto t_mark = t_level;
-    double ms_split[5] = {0, 0, 0, 0, 0};   // (verbose) wait for z | host scans | uploads + secular | wait for the roots | rest
-    auto lap = [&](int slot) {
-      const auto now = std::chrono::steady_clock::now();
-      ms_split[slot] += std::chrono::duration<double, std::milli>(now - t_mark).count();
-      t_mark = now;
-    };
-    std::vector<MergeDesc> descs(nm);
-    int max_m = 0;
-    for (int q = 0; q < nm; ++q) {
-      const Node& P = nodes[ids[q]];
-      descs[q] = MergeDesc{};
-      descs[q].s = P.s; descs[q].n1 = nodes[P.left].m; descs[q].m = P.m;
-      max_m = std::max(max_m, P.m);
+  // ---- one level ------------------------------------------------------------------------------------
+  // the level's merges (s, n1, m) to the device: what the gather kernels need
+  int begin_level(int depth, Level& lv) {
+    lv.depth = depth;
+    lv.ids = &tree.by_depth[depth];
+    lv.nm = (int)lv.ids->size();
+    lv.descs.resize(lv.nm);
+    for (int q = 0; q < lv.nm; ++q) {
+      const Node& P = tree.nodes[(*lv.ids)[q]];
+      lv.descs[q] = MergeDesc{};
+      lv.descs[q].s = P.s; lv.descs[q].n1 = tree.nodes[P.left].m; lv.descs[q].m = P.m;
+      lv.max_m = std::max(lv.max_m, P.m);
     }
-    const bool lazy_level = lazy && depth <= Dl;   // this level's merge operators stay factored
-    const bool lazy_kids = lazy && depth < Dl;     // ... and so do the children's eigenvector matrices
     stage.reset();      // (the previous level ended with a synchronisation: its uploads have executed)
-    BK_TRY(stage.put(d_descs, descs.data(), nm * sizeof(MergeDesc)));
-    if (!lazy_kids) {
-      for (int b0 = 0; b0 < nm; b0 += 65535) {
-        const int nb = std::min(65535, nm - b0);
-        hipLaunchKernelGGL(dc_gather_z, dim3((max_m + 63) / 64, nb), dim3(64), 0, st,
-                           (const MergeDesc*)(d_descs + b0), (const double*)Qc, N, d_z);
-        if (lazy_level)
-          hipLaunchKernelGGL(dc_gather_rows, dim3((max_m + 63) / 64, nb), dim3(64), 0, st,
-                             (const MergeDesc*)(d_descs + b0), (const double*)Qc, N, d_gf, d_gl);
-      }
-      BK_CHECK_LAUNCH();
-      PinnedFetch pf(ctx, 3 * (int64_t)n);
-      BK_TRY(pf.add(hz.data(), d_z, n * sizeof(double)));
-      if (lazy_level) {
-        BK_TRY(pf.add(yf.data(), d_gf, n * sizeof(double)));
-        BK_TRY(pf.add(yl.data(), d_gl, n * sizeof(double)));
-      }
-      BK_TRY(pf.finish());
-    } else {
-      for (int q = 0; q < nm; ++q) {
-        const MergeDesc& md = descs[q];
-        for (int t = 0; t < md.m; ++t) {
-          const bool left = t < md.n1;
-          hz[md.s + t] = left ? bl[md.s + t] : bf[md.s + t];
-          yf[md.s + t] = left ? bf[md.s + t] : 0.0;
-          yl[md.s + t] = left ? 0.0 : bl[md.s + t];
-        }
-      }
-      BK_HIP(hipStreamSynchronize(st));
-    }
+    return stage.put(d_descs, lv.descs.data(), lv.nm * sizeof(MergeDesc));
+  }
 
-    lap(0);
-    if (trace_fine()) BK_TRY(trace_host("R:dc_z", hz.data(), n, depth));
-    // host deflation scans
+  // z = [last row of the left child's Q | first row of the right child's] from the explicit Q (at depth Dl also the
+  // children's first / last rows, yf / yl)
+  int gather_z(Level& lv) {
+    const bool rows_too = level_factored(lv.depth);
+    for (const Batch b : Batches{lv.nm}) {
+      hipLaunchKernelGGL(dc_gather_z, dim3((lv.max_m + 63) / 64, b.nb), dim3(64), 0, st,
+                         (const MergeDesc*)(d_descs + b.b0), (const double*)Qc, N, d_z);
+      if (rows_too)
+        hipLaunchKernelGGL(dc_gather_rows, dim3((lv.max_m + 63) / 64, b.nb), dim3(64), 0, st,
+                           (const MergeDesc*)(d_descs + b.b0), (const double*)Qc, N, d_gf, d_gl);
+    }
+    BK_CHECK_LAUNCH();
+    PinnedFetch pf(ctx, 3 * (int64_t)n);
+    BK_TRY(pf.add(hz.data(), d_z, n * sizeof(double)));
+    if (rows_too) {
+      BK_TRY(pf.add(yf.data(), d_gf, n * sizeof(double)));
+      BK_TRY(pf.add(yl.data(), d_gl, n * sizeof(double)));
+    }
+    BK_TRY(pf.finish());
+    return z_ready(lv);
+  }
+  // ... or, above factored children, from the boundary rows the host carries
+  int gather_z_from_rows(Level& lv) {
+    dc_rows_from_frontier(lv.descs, bf, bl, hz, yf, yl);
+    BK_HIP(hipStreamSynchronize(st));
+    return z_ready(lv);
+  }
+  int z_ready(Level& lv) {
+    lv.lap(0);
+    if (trace_fine()) BK_TRY(trace_host("R:dc_z", hz.data(), n, lv.depth));
+    return BIGKRLS_OK;
+  }
+
+  // host deflation scans; where the secular vectors go; the root's storage order; the rotations on yf / yl
+  void scan_level(Level& lv) {
+    const int depth = lv.depth;
     A.ra.clear(); A.rb.clear(); A.rc.clear(); A.rs.clear();
-    std::vector<std::vector<double>> defvals(nm);
-    std::vector<int> rot_merges;
-    int maxK = 0, max_ndef = 0;
-    for (int q = 0; q < nm; ++q) {
-      const Node& P = nodes[ids[q]];
-      const Node& Ln = nodes[P.left];
-      const Node& Rn = nodes[P.right];
+    lv.defvals.resize(lv.nm);
+    for (int q = 0; q < lv.nm; ++q) {
+      const Node& P = tree.nodes[(*lv.ids)[q]];
+      const Node& Ln = tree.nodes[P.left];
+      const Node& Rn = tree.nodes[P.right];
       const int cut = P.s + Ln.m - 1;
-      host_merge(Ln, Rn, he[cut], hz.data(), descs[q], A, defvals[q]);
-      if (descs[q].nrot > 0) rot_merges.push_back(q);
-      maxK = std::max(maxK, descs[q].K);
-      max_ndef = std::max(max_ndef, descs[q].ndef);
+      host_merge(Ln, Rn, he[cut], hz.data(), lv.descs[q], A, lv.defvals[q], scratch);
+      if (lv.descs[q].nrot > 0) lv.rot_merges.push_back(q);
+      lv.maxK = std::max(lv.maxK, lv.descs[q].K);
+      lv.max_ndef = std::max(lv.max_ndef, lv.descs[q].ndef);
     }
-    const bool is_root = (depth == 0);
-    // where this level's secular vectors are written: straight into the stash on a factored level below the root (their
-    // K x K blocks used to be formed in U and copied: 1.9 GB of copies at N = 20 000), else block (s, s) of U
-    const bool u_to_stash = lazy_level && !is_root;
-    if (u_to_stash && stash == nullptr) stash = Qn;
-    std::vector<int64_t> level_stash_off(u_to_stash ? nm : 0);
-    for (int q = 0; q < nm; ++q) {
-      MergeDesc& md = descs[q];
-      if (u_to_stash) {
-        level_stash_off[q] = stash_used;
-        md.uoff = stash_used;
-        md.uld = std::max(md.K, 1);
-        stash_used += (int64_t)md.K * md.K;
-      } else {
-        md.uoff = md.s + (int64_t)md.s * N;
-        md.uld = n;
-      }
-    }
-    double* Ubase = u_to_stash ? stash : U;
-    if (is_root) {
-      // store roots in descending order so that the kept ones are a prefix
-      const int K = descs[0].K, s = descs[0].s;
-      for (int j = 0; j < K; ++j) A.cpos[s + j] = K - 1 - j;
-      descs[0].rev = 1;
-    }
-    if (lazy_level && !is_root) {
-      // the deflation rotations act on the columns of the children's matrices, hence on yf, yl
-      for (int q = 0; q < nm; ++q) {
-        const MergeDesc& md = descs[q];
-        double* f = yf.data() + md.s;
-        double* l = yl.data() + md.s;
-        for (int t = 0; t < md.nrot; ++t) {
-          const int a = A.ra[md.rot_off + t], b = A.rb[md.rot_off + t];
-          const double c = A.rc[md.rot_off + t], sn = A.rs[md.rot_off + t];
-          const double fa = f[a], fb = f[b], la = l[a], lb = l[b];
-          f[a] = c * fa + sn * fb; f[b] = c * fb - sn * fa;
-          l[a] = c * la + sn * lb; l[b] = c * lb - sn * la;
-        }
-      }
-    }
-    lap(1);
-    BK_TRY(stage.put(d_descs, descs.data(), nm * sizeof(MergeDesc)));
+    if (u_to_stash(depth) && stash == nullptr) stash = Qn;
+    dc_assign_u(lv.descs, u_to_stash(depth), n, stash_used, lv.stash_off);
+    if (depth == 0) dc_root_descending(lv.descs[0], A);
+    if (u_to_stash(depth)) dc_rows_rotate(lv.descs, A, yf, yl);
+    lv.lap(1);
+  }
+
+  int upload_level(Level& lv) {
+    BK_TRY(stage.put(d_descs, lv.descs.data(), lv.nm * sizeof(MergeDesc)));
     // [dlam | w] -> d_dlam, d_w and [pole_of_row | srccol | cpos | defsrc | defdst] -> d_pole ... d_defdst: the device
     // arrays are laid out the same way (d_cpos receives the host's cpos: no kernel of the level loop reads it)
     BK_TRY(stage.send(d_dlam, A.dlam, (size_t)2 * n * sizeof(double)));
-    BK_TRY(stage.send(d_pole, A.pole_of_row, (size_t)5 * n * sizeof(int)));
-    const int nrot_total = (int)A.ra.size();
-    if (nrot_total > 0) {
-      BK_TRY(stage.put(d_ra, A.ra.data(), nrot_total * sizeof(int)));
-      BK_TRY(stage.put(d_rb, A.rb.data(), nrot_total * sizeof(int)));
-      BK_TRY(stage.put(d_rc, A.rc.data(), nrot_total * sizeof(double)));
-      BK_TRY(stage.put(d_rs, A.rs.data(), nrot_total * sizeof(double)));
-      BK_TRY(stage.put(d_rotids, rot_merges.data(), rot_merges.size() * sizeof(int)));
-      const int nrm = (int)rot_merges.size();
-      for (int b0 = 0; b0 < nrm && !lazy_kids; b0 += 65535) {
-        const int nb = std::min(65535, nrm - b0);
-        hipLaunchKernelGGL(dc_rotate, dim3((max_m + 63) / 64, nb), dim3(64), 0, st,
-                           (const MergeDesc*)d_descs, (const int*)(d_rotids + b0), (const int*)d_ra,
-                           (const int*)d_rb, (const double*)d_rc, (const double*)d_rs, Qc, N);
-      }
-      BK_CHECK_LAUNCH();
+    return stage.send(d_pole, A.pole_of_row, (size_t)5 * n * sizeof(int));
+  }
+
+  // Recorded deflation rotations to the device, then applied: to the columns of the children's blocks of Q (Qcols, the
+  // level loop: `extent` rows), to the rows of the nv = `extent` kept columns X (Xrows, the apply phase: the rotations
+  // moved to the other factor), or to nothing here (Upload: the level loop above factored children, whose rotations the
+  // apply phase replays). d_descs holds the descriptors the rotations belong to.
+  enum class Rotate { Qcols, Xrows, Upload };
+  int rotate(const std::vector<int>& ra, const std::vector<int>& rb, const std::vector<double>& rc,
+             const std::vector<double>& rs, const std::vector<int>& merges, Rotate what, double* M, int extent) {
+    if (ra.empty() || merges.empty()) return BIGKRLS_OK;
+    const int nrt = (int)ra.size(), nrm = (int)merges.size();
+    BK_TRY(stage.put(d_ra, ra.data(), nrt * sizeof(int)));
+    BK_TRY(stage.put(d_rb, rb.data(), nrt * sizeof(int)));
+    BK_TRY(stage.put(d_rc, rc.data(), nrt * sizeof(double)));
+    BK_TRY(stage.put(d_rs, rs.data(), nrt * sizeof(double)));
+    BK_TRY(stage.put(d_rotids, merges.data(), nrm * sizeof(int)));
+    if (what == Rotate::Qcols) {
+      for (const Batch b : Batches{nrm})
+        hipLaunchKernelGGL(dc_rotate, dim3((extent + 63) / 64, b.nb), dim3(64), 0, st,
+                           (const MergeDesc*)d_descs, (const int*)(d_rotids + b.b0), (const int*)d_ra,
+                           (const int*)d_rb, (const double*)d_rc, (const double*)d_rs, M, N);
+    } else if (what == Rotate::Xrows) {
+      hipLaunchKernelGGL(dc_lazy_rotate, dim3((extent + 63) / 64, nrm), dim3(64), 0, st,
+                         (const MergeDesc*)d_descs, (const int*)d_rotids, (const int*)d_ra,
+                         (const int*)d_rb, (const double*)d_rc, (const double*)d_rs, M, N, extent);
     }
-    if (maxK > 0) {
-      for (int b0 = 0; b0 < nm; b0 += 65535) {
-        const int nb = std::min(65535, nm - b0);
-        hipLaunchKernelGGL(dc_secular, dim3((maxK + 4 * DC_SEC_R - 1) / (4 * DC_SEC_R), nb), dim3(256), 0, st,
-                           (const MergeDesc*)(d_descs + b0), (const double*)d_dlam,
+    BK_CHECK_LAUNCH();
+    return BIGKRLS_OK;
+  }
+
+  int rotate_children(Level& lv) {
+    return rotate(A.ra, A.rb, A.rc, A.rs, lv.rot_merges, kids_factored(lv.depth) ? Rotate::Upload : Rotate::Qcols, Qc,
+                  lv.max_m);
+  }
+
+  // the secular equation and the re-derived z of every merge; the roots back to the host; the level's one wait
+  int secular(Level& lv) {
+    if (lv.maxK > 0) {
+      for (const Batch b : Batches{lv.nm}) {
+        hipLaunchKernelGGL(dc_secular, dim3((lv.maxK + 4 * DC_SEC_R - 1) / (4 * DC_SEC_R), b.nb), dim3(256), 0, st,
+                           (const MergeDesc*)(d_descs + b.b0), (const double*)d_dlam,
                            (const double*)d_w, d_lam, d_dorg, d_tau);
-        hipLaunchKernelGGL(dc_zhat, dim3((maxK + 3) / 4, nb), dim3(256), 0, st,
-                           (const MergeDesc*)(d_descs + b0), (const double*)d_dlam,
+        hipLaunchKernelGGL(dc_zhat, dim3((lv.maxK + 3) / 4, b.nb), dim3(256), 0, st,
+                           (const MergeDesc*)(d_descs + b.b0), (const double*)d_dlam,
                            (const double*)d_w, (const int*)d_pole, (const double*)d_dorg,
                            (const double*)d_tau, d_zhat);
       }
       BK_CHECK_LAUNCH();
-      lap(2);
+      lv.lap(2);
       PinnedFetch pf(ctx, (int64_t)n);
       BK_TRY(pf.add(hlam.data(), d_lam, n * sizeof(double)));
       BK_TRY(pf.finish());
     }
     BK_HIP(hipStreamSynchronize(st));
-    lap(3);
+    lv.lap(3);
     if (trace_fine()) {
-      BK_TRY(trace_host("R:dc_dlam", A.dlam, n, depth));
-      BK_TRY(trace_host("R:dc_w", A.w, n, depth));
-      BK_TRY(trace_host("R:dc_roots", hlam.data(), n, maxK));
+      BK_TRY(trace_host("R:dc_dlam", A.dlam, n, lv.depth));
+      BK_TRY(trace_host("R:dc_w", A.w, n, lv.depth));
+      BK_TRY(trace_host("R:dc_roots", hlam.data(), n, lv.maxK));
     }
-    // new eigenvalue lists in storage order
-    for (int q = 0; q < nm; ++q) {
-      Node& P = nodes[ids[q]];
-      const int K = descs[q].K, s = P.s;
+    return BIGKRLS_OK;
+  }
+
+  // new eigenvalue lists in storage order
+  int read_roots(Level& lv) {
+    for (int q = 0; q < lv.nm; ++q) {
+      Node& P = tree.nodes[(*lv.ids)[q]];
+      const int K = lv.descs[q].K, s = P.s;
       P.dv.assign(P.m, 0.0);
       for (int j = 0; j < K; ++j) {
-        const double lv = hlam[s + j];
-        if (!std::isfinite(lv)) {
+        const double lval = hlam[s + j];
+        if (!std::isfinite(lval)) {
           set_error("eigen: secular equation produced a non-finite root");
           return BIGKRLS_ENOCONV;
         }
-        P.dv[A.cpos[s + j]] = lv;
+        P.dv[A.cpos[s + j]] = lval;
       }
-      for (int t = 0; t < P.m - K; ++t) P.dv[K + t] = defvals[q][t];
-      P.ksorted = (depth == 0) ? 0 : K;      // (the root stores its roots in descending order)
-      nodes[P.left].dv.clear(); nodes[P.left].dv.shrink_to_fit();
-      nodes[P.right].dv.clear(); nodes[P.right].dv.shrink_to_fit();
+      for (int t = 0; t < P.m - K; ++t) P.dv[K + t] = lv.defvals[q][t];
+      P.ksorted = (lv.depth == 0) ? 0 : K;      // (the root stores its roots in descending order)
+      tree.nodes[P.left].dv.clear(); tree.nodes[P.left].dv.shrink_to_fit();
+      tree.nodes[P.right].dv.clear(); tree.nodes[P.right].dv.shrink_to_fit();
     }
-    if (is_root) {
-      const Node& P = nodes[ids[0]];
-      // descending order of all n values, ties in storage order (= a stable sort of the indices): the K roots are stored
-      // in descending order already, so only the deflated tail is sorted and the two runs are merged
-      std::vector<int> ord(n);
-      std::iota(ord.begin(), ord.end(), 0);
-      {
-        auto desc = [&](int a, int b) { return P.dv[a] > P.dv[b]; };
-        const int Kr = descs[0].K;
-        if (std::is_sorted(ord.begin(), ord.begin() + Kr, desc)) {
-          std::stable_sort(ord.begin() + Kr, ord.end(), desc);
-          std::inplace_merge(ord.begin(), ord.begin() + Kr, ord.end(), desc);
-        } else {
-          std::stable_sort(ord.begin(), ord.end(), desc);
-        }
-      }
-      vals_desc.resize(n);
-      for (int t = 0; t < n; ++t) vals_desc[t] = P.dv[ord[t]];
-      int64_t nv = n_vecs_max;
-      if (keep_thresh >= 0.0) {
-        int64_t keep = 0;
-        const double thr = keep_thresh * vals_desc[0];
-        for (int64_t t = 0; t < n_vals; ++t)
-          if (vals_desc[t] >= thr) keep = t + 1;   // max(which(values >= eigtrunc*values[1]))
-        nv = std::min<int64_t>(nv, std::max<int64_t>(keep, 1));
-      }
-      nv_final = nv;
-      src_cols.resize(nv);
-      int kneed = 0;
-      for (int64_t t = 0; t < nv; ++t) {
-        src_cols[t] = ord[t];
-        if (ord[t] < descs[0].K) ++kneed;
-      }
-      descs[0].Kneed = kneed;
-      if (lazy && nv * 8 > N) {
-        BK_HIP(hipStreamSynchronize(st));
-        if (verbose) fprintf(stderr, "[bigkrls]   d&c: %lld columns kept, redoing the top levels explicitly\n", (long long)nv);
-        return divide_conquer(ctx, n, hd, he, Q0, Q1, U, n_vals, n_vecs_max, keep_thresh, vals_desc,
-                              src_cols, Qfinal, false);
-      }
-      BK_TRY(stage.put(d_descs, descs.data(), nm * sizeof(MergeDesc)));
+    return BIGKRLS_OK;
+  }
+
+  // the root: all values in descending order, which columns are kept, how many of them are secular vectors
+  int select_at_root(Level& lv) {
+    int kneed = 0;
+    const int64_t nv = dc_select_root(tree.nodes[(*lv.ids)[0]].dv, lv.descs[0].K, n, n_vals, n_vecs_max, keep_thresh,
+                                      vals_desc, src_cols, kneed);
+    nv_final = nv;
+    lv.descs[0].Kneed = kneed;
+    if (lazy() && dc_redo_explicit(nv, N)) {
+      BK_HIP(hipStreamSynchronize(st));
+      if (chatty) fprintf(stderr, "[bigkrls]   d&c: %lld columns kept, redoing the top levels explicitly\n", (long long)nv);
+      redo = true;
+      return BIGKRLS_OK;
     }
-    // eigenvector update
-    int maxKneed = 0;
-    for (int q = 0; q < nm; ++q) maxKneed = std::max(maxKneed, descs[q].Kneed);
-    // Descriptors of this level's batched products: a source of an asynchronous host -> device copy, declared at the
-    // level's scope so that it lives until the synchronisation at the end of the level. (It used to be a local of the
-    // branch that fills it, destroyed before that synchronisation. On this runtime that was harmless -- hipMemcpyAsync
-    // takes its copy of a pageable source before it returns, at every size, also in bursts and under load:
-    // tools/pageable_h2d_probe.hip, BIGKRLS_FAULT=dc_gd_clobber -- but nothing in the API promises it.)
-    std::vector<GemmDesc> gd;
-    if (u_to_stash) {
-      // the children's first / last rows gathered into the order of the merge's secular-vector rows: dc_vectors pushes
-      // them through the merge in the pass that writes the vectors
+    return stage.put(d_descs, lv.descs.data(), lv.nm * sizeof(MergeDesc));
+  }
+
+  // the secular vectors of every merge, into U or the stash (there with the children's boundary rows pushed through)
+  int vectors(Level& lv) {
+    const bool to_stash = u_to_stash(lv.depth);
+    for (int q = 0; q < lv.nm; ++q) lv.maxKneed = std::max(lv.maxKneed, lv.descs[q].Kneed);
+    if (to_stash) {
       std::vector<double> gfh(n, 0.0), glh(n, 0.0);
-      for (int q = 0; q < nm; ++q) {
-        const MergeDesc& md = descs[q];
-        for (int i = 0; i < md.K; ++i) {
-          gfh[md.s + i] = yf[md.s + A.srccol[md.s + i]];
-          glh[md.s + i] = yl[md.s + A.srccol[md.s + i]];
-        }
-      }
+      dc_rows_gather(lv.descs, A, yf, yl, gfh, glh);
       BK_TRY(stage.put(d_gf, gfh.data(), n * sizeof(double)));
       BK_TRY(stage.put(d_gl, glh.data(), n * sizeof(double)));
     }
-    if (maxKneed > 0) {
-      for (int b0 = 0; b0 < nm; b0 += 65535) {
-        const int nb = std::min(65535, nm - b0);
-        hipLaunchKernelGGL(dc_vectors, dim3(maxKneed, nb), dim3(256), 0, st,
-                           (const MergeDesc*)(d_descs + b0), (const double*)d_zhat, (const double*)d_dlam,
-                           (const int*)d_pole, (const double*)d_dorg, (const double*)d_tau, Ubase,
-                           u_to_stash ? (const double*)d_gf : (const double*)nullptr, (const double*)d_gl, d_of, d_ol);
+    if (lv.maxKneed > 0) {
+      for (const Batch b : Batches{lv.nm}) {
+        hipLaunchKernelGGL(dc_vectors, dim3(lv.maxKneed, b.nb), dim3(256), 0, st,
+                           (const MergeDesc*)(d_descs + b.b0), (const double*)d_zhat, (const double*)d_dlam,
+                           (const int*)d_pole, (const double*)d_dorg, (const double*)d_tau, to_stash ? stash : U,
+                           to_stash ? (const double*)d_gf : (const double*)nullptr, (const double*)d_gl, d_of, d_ol);
       }
       BK_CHECK_LAUNCH();
     }
-    if (lazy_level) {
-      LazyLevel& L = lazy_levels[depth];
-      L.descs = descs;
-      L.srccol.assign(A.srccol, A.srccol + n);
-      L.defsrc.assign(A.defsrc, A.defsrc + n);
-      L.max_m = max_m; L.maxK = maxK;
-      if (lazy_kids) {   // (at depth Dl the rotations went into the explicit Q of depth Dl+1)
-        L.ra = A.ra; L.rb = A.rb; L.rc = A.rc; L.rs = A.rs; L.rot_merges = rot_merges;
-      } else {
-        for (auto& md : L.descs) md.nrot = 0;
-      }
-      if (!is_root) {
-        // the secular-vector blocks were written straight into the stash (the idle ping-pong copy of Q: the U buffer is
-        // reused by the next level); push the boundary rows through the merge
-        L.stash_off = level_stash_off;
-        std::vector<double> ofh(n), olh(n);
-        PinnedFetch pf(ctx, 2 * (int64_t)n);
-        BK_TRY(pf.add(ofh.data(), d_of, n * sizeof(double)));
-        BK_TRY(pf.add(olh.data(), d_ol, n * sizeof(double)));
-        BK_TRY(pf.finish());
-        for (int q = 0; q < nm; ++q) {
-          const MergeDesc& md = descs[q];
-          for (int j = 0; j < md.K; ++j) { bf[md.s + j] = ofh[md.s + j]; bl[md.s + j] = olh[md.s + j]; }
-          for (int t = 0; t < md.m - md.K; ++t) {
-            bf[md.s + md.K + t] = yf[md.s + A.defsrc[md.s + t]];
-            bl[md.s + md.K + t] = yl[md.s + A.defsrc[md.s + t]];
-          }
-        }
-      }
-    } else if (maxKneed > 0) {
-      gd.reserve(2 * nm);
-      int gm = 0, gn = 0;
-      for (int q = 0; q < nm; ++q) {
-        const MergeDesc& md = descs[q];
-        if (md.Kneed <= 0) continue;
-        const int k12 = md.k1 + md.k2, k23 = md.k2 + md.k3;
-        const int n2 = md.m - md.n1;
-        const int64_t o = md.s + (int64_t)md.s * N;
-        // rows of the left child that no kept column touches must still be written
-        GemmDesc g1{};
-        g1.A = Qc + o; g1.B = U + o; g1.C = Qn + o;
-        g1.lda = N; g1.ldb = N; g1.ldc = N;
-        g1.m = md.n1; g1.n = md.Kneed; g1.k = k12; g1.kidx = d_srccol + md.s;
-        gd.push_back(g1);
-        GemmDesc g2{};
-        g2.A = Qc + o + md.n1; g2.B = U + o + md.k1; g2.C = Qn + o + md.n1;
-        g2.lda = N; g2.ldb = N; g2.ldc = N;
-        g2.m = n2; g2.n = md.Kneed; g2.k = k23; g2.kidx = d_srccol + md.s + md.k1;
-        gd.push_back(g2);
-        gm = std::max(gm, std::max(md.n1, n2));
-        gn = std::max(gn, md.Kneed);
-      }
-#ifdef BK_FAULT_INJECT
-      // BIGKRLS_FAULT=dc_lag (test build): the stream runs 2 ms behind the host, as it does with many processes on one
-      // GPU -- the copy below executes long after hipMemcpyAsync has returned. =dc_gd_clobber additionally overwrites
-      // the descriptors right after the launch (what freeing them early amounted to): tools/dc_async_source_probe.py
-      // uses it to see WHEN the runtime reads a pageable source (result: before hipMemcpyAsync returns).
-      const char* dc_fault = getenv("BIGKRLS_FAULT");
-      const bool dc_lag = dc_fault && (std::string(dc_fault) == "dc_lag" || std::string(dc_fault) == "dc_gd_clobber");
-      if (dc_lag) hipLaunchKernelGGL(dc_fault_spin, dim3(1), dim3(64), 0, st, 200000LL);
-#endif
-      BK_TRY(stage.put(d_gdescs, gd.data(), gd.size() * sizeof(GemmDesc)));
-      BK_TRY(gemm_batched_nn(ctx, d_gdescs, (int)gd.size(), gm, gn));
-#ifdef BK_FAULT_INJECT
-      if (dc_fault && std::string(dc_fault) == "dc_gd_clobber") std::memset((void*)gd.data(), 0, gd.size() * sizeof(GemmDesc));
-      if (dc_lag) {   // heap churn: blocks of the descriptors' size, zero-filled and freed (lands on anything freed too early)
-        for (int rep = 0; rep < 4; ++rep) {
-          std::vector<char> junk(gd.size() * sizeof(GemmDesc) + 16, 0);
-          asm volatile("" ::"r"(junk.data()) : "memory");
-        }
-      }
-#endif
+    return BIGKRLS_OK;
+  }
+
+  // a factored level: what the apply phase needs of it is kept; below the root the boundary rows go through the merge
+  int push_boundary_rows(Level& lv) {
+    LazyLevel& L = lazy_levels[lv.depth];
+    L.descs = lv.descs;
+    L.srccol.assign(A.srccol, A.srccol + n);
+    L.defsrc.assign(A.defsrc, A.defsrc + n);
+    L.max_m = lv.max_m; L.maxK = lv.maxK;
+    if (kids_factored(lv.depth)) {   // (at depth Dl the rotations went into the explicit Q of depth Dl+1)
+      L.ra = A.ra; L.rb = A.rb; L.rc = A.rc; L.rs = A.rs; L.rot_merges = lv.rot_merges;
+    } else {
+      for (auto& md : L.descs) md.nrot = 0;
     }
-    if (max_ndef > 0 && !lazy_level) {
-      for (int b0 = 0; b0 < nm; b0 += 65535) {
-        const int nb = std::min(65535, nm - b0);
-        hipLaunchKernelGGL(dc_copy_deflated, dim3(max_ndef, nb), dim3(64), 0, st,
-                           (const MergeDesc*)(d_descs + b0), (const int*)d_defsrc,
-                           (const int*)d_defdst, (const double*)Qc, Qn, N);
-      }
-      BK_CHECK_LAUNCH();
+    if (lv.depth == 0) return BIGKRLS_OK;
+    // the secular-vector blocks were written straight into the stash (the idle ping-pong copy of Q: the U buffer is
+    // reused by the next level); push the boundary rows through the merge
+    L.stash_off = lv.stash_off;
+    std::vector<double> ofh(n), olh(n);
+    PinnedFetch pf(ctx, 2 * (int64_t)n);
+    BK_TRY(pf.add(ofh.data(), d_of, n * sizeof(double)));
+    BK_TRY(pf.add(olh.data(), d_ol, n * sizeof(double)));
+    BK_TRY(pf.finish());
+    dc_rows_scatter(lv.descs, A, ofh, olh, yf, yl, bf, bl);
+    return BIGKRLS_OK;
+  }
+
+  // an explicit level: the parents' blocks of Qn = the children's blocks of Qc times the secular vectors, two batched
+  // products per merge (the rows of the left and of the right child)
+  int explicit_products(Level& lv) {
+    if (lv.maxKneed <= 0) return BIGKRLS_OK;
+    std::vector<GemmDesc>& gd = lv.gd;
+    gd.reserve(2 * lv.nm);
+    int gm = 0, gn = 0;
+    for (const MergeDesc& md : lv.descs) {
+      if (md.Kneed <= 0) continue;
+      const int k12 = md.k1 + md.k2, k23 = md.k2 + md.k3;
+      const int n2 = md.m - md.n1;
+      const int64_t o = md.s + (int64_t)md.s * N;
+      // rows of the left child that no kept column touches must still be written
+      gd.push_back(gemm_desc(Qc + o, N, U + o, N, Qn + o, N, md.n1, md.Kneed, k12, d_srccol + md.s));
+      gd.push_back(gemm_desc(Qc + o + md.n1, N, U + o + md.k1, N, Qn + o + md.n1, N, n2, md.Kneed, k23,
+                             d_srccol + md.s + md.k1));
+      gm = std::max(gm, std::max(md.n1, n2));
+      gn = std::max(gn, md.Kneed);
     }
+#ifdef BK_FAULT_INJECT
+    // BIGKRLS_FAULT=dc_lag (test build): the stream runs 2 ms behind the host, as it does with many processes on one
+    // GPU -- the copy below executes long after hipMemcpyAsync has returned. =dc_gd_clobber additionally overwrites
+    // the descriptors right after the launch (what freeing them early amounted to): tools/dc_async_source_probe.py
+    // uses it to see WHEN the runtime reads a pageable source (result: before hipMemcpyAsync returns).
+    const char* dc_fault = getenv("BIGKRLS_FAULT");
+    const bool dc_lag = dc_fault && (std::string(dc_fault) == "dc_lag" || std::string(dc_fault) == "dc_gd_clobber");
+    if (dc_lag) hipLaunchKernelGGL(dc_fault_spin, dim3(1), dim3(64), 0, st, 200000LL);
+#endif
+    BK_TRY(stage.put(d_gdescs, gd.data(), gd.size() * sizeof(GemmDesc)));
+    BK_TRY(gemm_batched_nn(ctx, d_gdescs, (int)gd.size(), gm, gn));
+#ifdef BK_FAULT_INJECT
+    if (dc_fault && std::string(dc_fault) == "dc_gd_clobber") std::memset((void*)gd.data(), 0, gd.size() * sizeof(GemmDesc));
+    if (dc_lag) {   // heap churn: blocks of the descriptors' size, zero-filled and freed (lands on anything freed too early)
+      for (int rep = 0; rep < 4; ++rep) {
+        std::vector<char> junk(gd.size() * sizeof(GemmDesc) + 16, 0);
+        asm volatile("" ::"r"(junk.data()) : "memory");
+      }
+    }
+#endif
+    return BIGKRLS_OK;
+  }
+
+  int copy_deflated(Level& lv) {
+    if (lv.max_ndef <= 0) return BIGKRLS_OK;
+    for (const Batch b : Batches{lv.nm}) {
+      hipLaunchKernelGGL(dc_copy_deflated, dim3(lv.max_ndef, b.nb), dim3(64), 0, st,
+                         (const MergeDesc*)(d_descs + b.b0), (const int*)d_defsrc,
+                         (const int*)d_defdst, (const double*)Qc, Qn, N);
+    }
+    BK_CHECK_LAUNCH();
+    return BIGKRLS_OK;
+  }
+
+  int end_level(Level& lv) {
+    const bool factored = level_factored(lv.depth);
     // host vectors (gd, descs, A.*) are sources of asynchronous copies: alive and unmodified up to here
     BK_HIP(hipStreamSynchronize(st));
-    if (trace_fine() && !lazy_level) {
-      BK_TRY(trace_point(ctx, st, "R:dc_Qn", Qn, N * N, depth));
+    if (trace_fine() && !factored) {
+      BK_TRY(trace_point(ctx, st, "R:dc_Qn", Qn, N * N, lv.depth));
     }
-    if (!lazy_level) std::swap(Qc, Qn);
-    lap(4);
-    if (verbose)
+    if (!factored) std::swap(Qc, Qn);
+    lv.lap(4);
+    if (chatty)
       fprintf(stderr, "[bigkrls]   d&c depth %2d%s: %6d merges, largest %6d (non-deflated %6d, %d rotations) %8.2f ms"
                       "  [wait z %.2f | host scans %.2f | upload+launch %.2f | wait roots %.2f | vectors %.2f]\n",
-              depth, lazy_level ? " (factored)" : "", nm, max_m, maxK, (int)A.ra.size(),
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_level).count(),
-              ms_split[0], ms_split[1], ms_split[2], ms_split[3], ms_split[4]);
+              lv.depth, factored ? " (factored)" : "", lv.nm, lv.max_m, lv.maxK, (int)A.ra.size(), lv.total.ms(),
+              lv.ms_split[0], lv.ms_split[1], lv.ms_split[2], lv.ms_split[3], lv.ms_split[4]);
+    return BIGKRLS_OK;
   }
-  if (n == 1) {
-    vals_desc.assign(1, dadj[0]);
-    src_cols.assign(1, 0);
-    nv_final = 1;
-  }
-  if (lazy) {
-    // ---- apply the factored levels to the kept columns, root first ---------------------------
-    const auto t_apply = std::chrono::steady_clock::now();
+
+  // ---- apply the factored levels to the kept columns, root first ---------------------------
+  int apply_factored() {
+    Stopwatch t_apply;
     const int nv = (int)nv_final;
+    BK_TRY(apply_root_columns(nv));
+    for (int d = 1; d <= Dl; ++d) BK_TRY(apply_level(lazy_levels[d], nv));
+    BK_TRY(apply_explicit_base(nv));
+    for (int t = 0; t < nv; ++t) src_cols[t] = t;
+    *Qfinal = X_oth;
+    if (chatty)
+      fprintf(stderr, "[bigkrls]   d&c: factored levels applied to %d columns %8.2f ms\n", nv, t_apply.ms());
+    return BIGKRLS_OK;
+  }
+
+  // X = the kept columns of the root's merge operator
+  int apply_root_columns(int nv) {
     const LazyLevel& R = lazy_levels[0];
     const int K0 = R.descs[0].K, kc = R.descs[0].Kneed;
     // the root's secular vectors occupy the first kc columns of U; the rest of U holds X, its
     // ping-pong partner and the product buffer (nv <= N/8)
-    double* Xa = U + N * (int64_t)kc;
-    double* Xb = Xa + N * (int64_t)nv;
-    double* Tm = Xb + N * (int64_t)nv;
+    X_cur = U + N * (int64_t)kc;
+    X_oth = X_cur + N * (int64_t)nv;
+    X_prod = X_oth + N * (int64_t)nv;
     stage.reset();      // (the root level ended with a synchronisation)
-    BK_HIP(hipMemsetAsync(Xa, 0, (size_t)N * nv * sizeof(double), st));
+    BK_HIP(hipMemsetAsync(X_cur, 0, (size_t)N * nv * sizeof(double), st));
     BK_TRY(stage.put(d_cpos, src_cols.data(), nv * sizeof(int)));
     BK_TRY(stage.put(d_srccol, R.srccol.data(), n * sizeof(int)));
     BK_TRY(stage.put(d_defsrc, R.defsrc.data(), n * sizeof(int)));
     hipLaunchKernelGGL(dc_iota, dim3((n + 255) / 256), dim3(256), 0, st, d_iota, n);
     hipLaunchKernelGGL(dc_lazy_root_x, dim3(nv), dim3(256), 0, st, nv, (const int*)d_cpos, K0,
-                       (const int*)d_srccol, (const int*)d_defsrc, (const double*)U, N, Xa, N);
+                       (const int*)d_srccol, (const int*)d_defsrc, (const double*)U, N, X_cur, N);
     BK_CHECK_LAUNCH();
-    auto apply_rotations = [&](const LazyLevel& L, double* X) -> int {
-      if (L.ra.empty() || L.rot_merges.empty()) return BIGKRLS_OK;
-      const int nrt = (int)L.ra.size(), nrm = (int)L.rot_merges.size();
-      BK_TRY(stage.put(d_ra, L.ra.data(), nrt * sizeof(int)));
-      BK_TRY(stage.put(d_rb, L.rb.data(), nrt * sizeof(int)));
-      BK_TRY(stage.put(d_rc, L.rc.data(), nrt * sizeof(double)));
-      BK_TRY(stage.put(d_rs, L.rs.data(), nrt * sizeof(double)));
-      BK_TRY(stage.put(d_rotids, L.rot_merges.data(), nrm * sizeof(int)));
-      hipLaunchKernelGGL(dc_lazy_rotate, dim3((nv + 63) / 64, nrm), dim3(64), 0, st,
-                         (const MergeDesc*)d_descs, (const int*)d_rotids, (const int*)d_ra,
-                         (const int*)d_rb, (const double*)d_rc, (const double*)d_rs, X, N, nv);
-      BK_CHECK_LAUNCH();
-      return BIGKRLS_OK;
-    };
     BK_TRY(stage.put(d_descs, R.descs.data(), sizeof(MergeDesc)));
-    BK_TRY(apply_rotations(R, Xa));
-    double* cur = Xa;
-    double* oth = Xb;
-    std::vector<GemmDesc> gd;
-    for (int d = 1; d <= Dl; ++d) {
-      const LazyLevel& L = lazy_levels[d];
-      const int nm = (int)L.descs.size();
-      BK_TRY(stage.put(d_descs, L.descs.data(), nm * sizeof(MergeDesc)));
-      BK_TRY(stage.put(d_srccol, L.srccol.data(), n * sizeof(int)));
-      BK_TRY(stage.put(d_defsrc, L.defsrc.data(), n * sizeof(int)));
-      gd.clear();
-      for (int q = 0; q < nm; ++q) {
-        const MergeDesc& md = L.descs[q];
-        if (md.K <= 0) continue;
-        GemmDesc g{};
-        g.A = stash + L.stash_off[q]; g.B = cur + md.s; g.C = Tm + md.s;
-        g.lda = md.K; g.ldb = N; g.ldc = N;
-        g.m = md.K; g.n = nv; g.k = md.K; g.kidx = d_iota;
-        gd.push_back(g);
-      }
-      if (!gd.empty()) {
-        BK_TRY(stage.put(d_gdescs, gd.data(), gd.size() * sizeof(GemmDesc)));
-        BK_TRY(gemm_batched_nn(ctx, d_gdescs, (int)gd.size(), L.maxK, nv));
-      }
-      hipLaunchKernelGGL(dc_lazy_scatter, dim3((L.max_m + 255) / 256, nm, nv), dim3(256), 0, st,
-                         (const MergeDesc*)d_descs, (const int*)d_srccol, (const int*)d_defsrc,
-                         (const double*)Tm, (const double*)cur, oth, N);
-      BK_CHECK_LAUNCH();
-      BK_TRY(apply_rotations(L, oth));    // (every upload has its own slice of the pinned arena: no synchronisation here)
-      std::swap(cur, oth);
+    return rotate(R.ra, R.rb, R.rc, R.rs, R.rot_merges, Rotate::Xrows, X_cur, nv);
+  }
+
+  // X <- (merge operators of one factored level) X: the stashed K x K blocks times the rows of X, scattered, rotated
+  int apply_level(const LazyLevel& L, int nv) {
+    const int nm = (int)L.descs.size();
+    BK_TRY(stage.put(d_descs, L.descs.data(), nm * sizeof(MergeDesc)));
+    BK_TRY(stage.put(d_srccol, L.srccol.data(), n * sizeof(int)));
+    BK_TRY(stage.put(d_defsrc, L.defsrc.data(), n * sizeof(int)));
+    std::vector<GemmDesc>& gd = apply_gd;
+    gd.clear();
+    for (int q = 0; q < nm; ++q) {
+      const MergeDesc& md = L.descs[q];
+      if (md.K <= 0) continue;
+      gd.push_back(gemm_desc(stash + L.stash_off[q], md.K, X_cur + md.s, N, X_prod + md.s, N, md.K, nv, md.K, d_iota));
     }
-    // the explicit eigenvector matrices of depth Dl+1, one block per depth-Dl merge: that level's
-    // deflation rotations were applied to them in place and couple the two children's columns
-    {
-      const LazyLevel& L = lazy_levels[Dl];
-      gd.clear();
-      int gm = 0;
-      for (const MergeDesc& md : L.descs) {
-        GemmDesc g{};
-        g.A = Qc + md.s + (int64_t)md.s * N; g.B = cur + md.s; g.C = oth + md.s;
-        g.lda = N; g.ldb = N; g.ldc = N;
-        g.m = md.m; g.n = nv; g.k = md.m; g.kidx = d_iota;
-        gd.push_back(g);
-        gm = std::max(gm, md.m);
-      }
+    if (!gd.empty()) {
       BK_TRY(stage.put(d_gdescs, gd.data(), gd.size() * sizeof(GemmDesc)));
-      BK_TRY(gemm_batched_nn(ctx, d_gdescs, (int)gd.size(), gm, nv));
-      BK_HIP(hipStreamSynchronize(st));
+      BK_TRY(gemm_batched_nn(ctx, d_gdescs, (int)gd.size(), L.maxK, nv));
     }
-    for (int t = 0; t < nv; ++t) src_cols[t] = t;
-    *Qfinal = oth;
-    if (verbose)
-      fprintf(stderr, "[bigkrls]   d&c: factored levels applied to %d columns %8.2f ms\n", nv,
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_apply).count());
+    hipLaunchKernelGGL(dc_lazy_scatter, dim3((L.max_m + 255) / 256, nm, nv), dim3(256), 0, st,
+                       (const MergeDesc*)d_descs, (const int*)d_srccol, (const int*)d_defsrc,
+                       (const double*)X_prod, (const double*)X_cur, X_oth, N);
+    BK_CHECK_LAUNCH();
+    // (every upload has its own slice of the pinned arena: no synchronisation here)
+    BK_TRY(rotate(L.ra, L.rb, L.rc, L.rs, L.rot_merges, Rotate::Xrows, X_oth, nv));
+    std::swap(X_cur, X_oth);
     return BIGKRLS_OK;
   }
-  (void)nv_final;
-  *Qfinal = Qc;
-  return BIGKRLS_OK;
+
+  // the explicit eigenvector matrices of depth Dl+1, one block per depth-Dl merge: that level's
+  // deflation rotations were applied to them in place and couple the two children's columns
+  int apply_explicit_base(int nv) {
+    std::vector<GemmDesc>& gd = apply_gd;
+    gd.clear();
+    int gm = 0;
+    for (const MergeDesc& md : lazy_levels[Dl].descs) {
+      gd.push_back(gemm_desc(Qc + md.s + (int64_t)md.s * N, N, X_cur + md.s, N, X_oth + md.s, N, md.m, nv, md.m, d_iota));
+      gm = std::max(gm, md.m);
+    }
+    BK_TRY(stage.put(d_gdescs, gd.data(), gd.size() * sizeof(GemmDesc)));
+    BK_TRY(gemm_batched_nn(ctx, d_gdescs, (int)gd.size(), gm, nv));
+    BK_HIP(hipStreamSynchronize(st));
+    return BIGKRLS_OK;
+  }
+};
+
+int divide_conquer(bigkrls_ctx* ctx, int n, const std::vector<double>& hd,
+                   const std::vector<double>& he, double* Q0, double* Q1, double* U,
+                   int64_t n_vals, int64_t n_vecs_max, double keep_thresh,
+                   std::vector<double>& vals_desc, std::vector<int>& src_cols, double** Qfinal) {
+  DivideConquer dc(DcArgs{ctx, n, hd, he, Q0, Q1, U, n_vals, n_vecs_max, keep_thresh, vals_desc, src_cols, Qfinal});
+  return dc.run();
 }
 
 // =============================================================================
@@ -2935,13 +2835,6 @@ struct DistS1 {
   int agg_mode = 0;             // panels per trailing update the ranks agreed on: 4 (groups of four, then pairs), 2 (pairs), 0 (none)
 };
 
-// wall-clock of the host between two points, for the BIGKRLS_VERBOSE lines: ms() since the start or the last lap()
-struct Stopwatch {
-  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-  double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-  double lap() { const double m = ms(); t0 = std::chrono::steady_clock::now(); return m; }
-};
-
 // The stage-1 panel loop as a captured hipGraph (round 6; OPT-IN, off by default). The loop has no host synchronisation
 // and no host decision that depends on device data -- every launch dimension follows from n -- and its two streams meet
 // only through ev_fork / ev_join / ev_join2 / ev_pq, the fork-join shape stream capture accepts: 824 nodes at N = 5 000,
@@ -3446,7 +3339,8 @@ struct DenseEig : EigArgs {
     if (h_n_vecs) *h_n_vecs = nv;
     if (nv == 0 || n_vecs_max <= 0) return BIGKRLS_OK;
     void* pidx = nullptr;
-    BK_TRY(ws_get(ctx, SLOT_EIG_INT, (int64_t)10 * n * sizeof(int), &pidx));
+    // (the size the divide & conquer asked this slot for: nothing is reallocated, the list goes to the slot's start)
+    BK_TRY(ws_get(ctx, SLOT_EIG_INT, DivideConquer::int_workspace_bytes(n), &pidx));
     int* d_src = (int*)pidx;
     BK_TRY(up.put(d_src, src_cols.data(), nv * sizeof(int)));
     int blocks = (int)std::min<int64_t>((N * nv + 255) / 256, 8192);
