@@ -54,6 +54,10 @@ constexpr int LDS_XK = BK + 2;
 #ifndef GEMM_DEEP_BN
 #define GEMM_DEEP_BN 64
 #endif
+// ... and keep load issue, MFMAs and staging stores of a half-iteration in that order (0: the compiler's own order)
+#ifndef GEMM_DEEP_PIN
+#define GEMM_DEEP_PIN 1
+#endif
 constexpr int lds_stage(int w) {   // room for either layout
   return BK * (w + GEMM_KX_PAD) > w * LDS_XK ? BK * (w + GEMM_KX_PAD) : w * LDS_XK;
 }
@@ -350,6 +354,32 @@ __device__ __forceinline__ void gemm_tile(const GemmOperands& g, int m0, int n0,
     // waits in the other register set and goes to LDS after them. A thin tile (BN = 64) has only
     // ~1.7 us of MFMA work per k-tile and CU -- less than the HBM latency a single tile in flight
     // would have to hide.
+    //
+    // What is in flight where (L = loads of one register set: BM / 16 + BN / 16, plus the modulation's; 12 for
+    // gemm_kernel<N,N,64>), in the interior loop below:
+    //   half 0:  issue L loads of tile t+2 into set 1          outstanding: set 2 (tile t+1), set 1 (tile t+2) = 2 L
+    //            MFMAs of tile t from LDS stage 0
+    //            stage set 2 (tile t+1) into LDS stage 1       its q-th store needs the q-th oldest load: loads return in
+    //                                                          order, so the wait is vmcnt(2 L - 1 - q) ... vmcnt(L) --
+    //                                                          never below L, set 1's loads stay outstanding
+    //            lgkmcnt(0) (this wave's LDS stores), barrier  outstanding across the barrier: set 1 (tile t+2) = L
+    //   half 1:  the same with the sets and the LDS stages swapped, tile t+3 issued, tile t+2 staged.
+    // The compiler places these waits itself (the loads are ordinary loads, __syncthreads() with no LDS-DMA outstanding
+    // is `s_waitcnt lgkmcnt(0); s_barrier`), but it places them for the worst path that reaches the store: where a half
+    // can be entered without its loads having been issued (`if (t + 2 < ntiles) load ...`, the general loop further
+    // down), the stores of the other set wait as if nothing had been issued after it -- vmcnt(L - 1) ... vmcnt(0) --
+    // and every half ends with nothing in flight: a one-deep pipeline at the registers of a two-deep one.
+    // Hence the interior loop: while tiles t+2 and t+3 exist and are full, and both operands are on the strided
+    // loader, both halves are straight-line code in which every load is issued on every path. The general loop takes
+    // over for the last two to four tiles (two or three full ones and a partial one, if any), for the tiles on the
+    // ragged edge of a not-contiguous operand and for a gathered A, in the state the interior loop leaves: tile t in
+    // LDS stage 0, tile t+1 in set 2. The k-weighted tile (WK, gram_weighted) never enters the interior loop: it is
+    // DEEP only up to 64 columns, and its transposed A operand then never fills the 128 rows of a tile (a_fast is
+    // false); the doubly modulated one (MOD2) is kept off it, see below.
+    // deep_pin() keeps the compiler from moving the phases of a half across each other: left to itself it hoists the
+    // staging stores of half 0 above the MFMAs, sinks the loads below them and runs the MFMAs of both tiles in half 1
+    // -- correct, with exact waits, and as slow as the drained loop (GEMM_DEEP_PIN=0).
+    // The arithmetic, its order and the LDS images are those of the general loop.
     double ra2[BM / 16];
     double rb2[BN / 16];
     double rs2[MQ];
@@ -376,7 +406,47 @@ __device__ __forceinline__ void gemm_tile(const GemmOperands& g, int m0, int n0,
     stage(kbeg, 0, ra, rb, rs);
     if (ntiles > 1) load_into(kbeg + BK, ra2, rb2, rs2);
     __syncthreads();
-    for (int t = 0; t < ntiles; t += 2) {
+    int t = 0;
+    // (not the doubly modulated tile: with the interior loop gemm_modulated2_kernel<64>, at 256 VGPRs, spills)
+    if (!MOD2 && !WK && a_fast && b_fast) {
+      auto load_full = [&](double (&xa)[BM / 16], double (&xb)[BN / 16], double (&xs)[MQ]) {
+        tile_load_strided<BM>(pa, sa, xa);
+        tile_load_strided<BN>(pb, sb, xb);
+        if constexpr (MOD) {              // (mod_load's full-tile branch, without its test)
+#pragma unroll
+          for (int q = 0; q < MQ1; ++q) xs[q] = ps[q * (NT / BM)];
+          ps += BK;
+        }
+        pa += ia;
+        pb += ib;
+      };
+      auto stage_full = [&](int st, double (&xa)[BM / 16], double (&xb)[BN / 16], const double (&xs)[MQ]) {
+        if constexpr (MOD) mod_apply(xa, xs);
+        tile_store<A_CONTIG, BM>(smem + st * A_STAGE, xa);
+        tile_store<B_CONTIG, BN>(smem + B_BASE + st * B_STAGE, xb);
+      };
+      auto deep_pin = [] {
+#if GEMM_DEEP_PIN
+        __builtin_amdgcn_sched_barrier(0);
+#endif
+      };
+      const int nfull = (kend - kbeg) / BK;
+      for (; t + 3 < nfull; t += 2) {
+        load_full(ra, rb, rs);            // tile t+2; in flight: tile t+1 (set 2), tile t+2 (set 1)
+        deep_pin();
+        mfma_tile(0);
+        deep_pin();
+        stage_full(1, ra2, rb2, rs2);     // waits for set 2 only: set 1's loads stay outstanding
+        __syncthreads();                  // in flight across the barrier: tile t+2
+        load_full(ra2, rb2, rs2);         // tile t+3; in flight: tile t+2 (set 1), tile t+3 (set 2)
+        deep_pin();
+        mfma_tile(1);
+        deep_pin();
+        stage_full(0, ra, rb, rs);        // waits for set 1 only
+        __syncthreads();                  // in flight across the barrier: tile t+3
+      }
+    }
+    for (; t < ntiles; t += 2) {
       // even tile t: LDS stage 0; tile t+1 waits in (ra2, rb2); tile t+2 loads into (ra, rb)
       if (t + 2 < ntiles) load_into(kbeg + (t + 2) * BK, ra, rb, rs);
       mfma_tile(0);
