@@ -21,6 +21,7 @@
 // "B", so that the lane index (l&15) runs along the column-major-contiguous M
 // dimension of C and every 16 lanes store one 128-byte segment.
 #include "common.h"
+#include "ktplan.h"
 #include "splitplan.h"
 #include "syrkmap.h"
 #include <algorithm>
@@ -2094,28 +2095,6 @@ __global__ __launch_bounds__(NT, 2) void kernel_block_tiled_kernel(
     }
 }
 
-// tile rows per band of the wave kernels' order: the band's rows of X (R x 32 x P doubles) take about 1 MB of an XCD's
-// 4 MB L2 (BIGKRLS_KB_R overrides; a value >= the number of tile rows gives the plain column-by-column order)
-static int kb_band_rows(int64_t p, int tiles) {
-  static const int r_env = [] { const char* e = getenv("BIGKRLS_KB_R"); return e ? atoi(e) : 0; }();
-  int64_t R = r_env > 0 ? r_env : std::max<int64_t>(8, (1 << 20) / (32 * 8 * std::max<int64_t>(p, 1)));
-  R = std::max<int64_t>(1, std::min<int64_t>(R, 1024));
-  return (int)std::min<int64_t>(R, std::max(tiles, 1));
-}
-
-// Non-temporal stores of the output tiles (the wave kernels; the workgroup-tiled kernel always uses them): the 8 N^2
-// bytes of K pass through the write-back L2s and evict the rows of X the tiles are built from; with X larger than an
-// XCD's 4 MB L2 the re-fetches stall the waves and non-temporal stores are 13 % faster (N = 50 000: 4.80 -> 4.24 ms,
-// 4.17 -> 4.71 TB/s written). At N = 20 000, P = 20 (X = 3.2 MB) a loop over the launch alone prefers ordinary stores
-// (0.730 vs 0.775 ms, round 4), but INSIDE the fit -- cold caches, the launch once per fit -- non-temporal stores are
-// the faster ones (round 5, same-box A/B in fresh processes: 0.620 / 0.628 ms ordinary, 0.597 / 0.595 ms non-temporal;
-// profiles/r05/r05b_knob_ab_C3.log): the threshold is X > 2 MB. BIGKRLS_KB_NT=0|1 overrides.
-static int kb_nontemporal(int64_t rows, int64_t p) {
-  static const int env = [] { const char* e = getenv("BIGKRLS_KB_NT"); return e ? atoi(e) : -1; }();
-  if (env >= 0) return env != 0;
-  return rows * p * (int64_t)sizeof(double) > (2ll << 20);    // 2 MB
-}
-
 // Operands of a kernel build moved by one common vector, with their squared row norms. exp(-|a - b|^2 / sigma) depends
 // on differences only, but |a|^2 + |b|^2 - 2 a.b cancels on data that are not centred (rows near 1e5: errors of 1e-5 in K),
 // so both operands are copied with the column means of A subtracted (col_means, shift_rows_sqnorms in vecops.hip:
@@ -2172,119 +2151,50 @@ int kernel_block(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, cons
 int kernel_block_centred(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* pna, const double* B,
                          int64_t v, int64_t ldb, const double* pnb, int64_t p, double sigma, double* out, int64_t ldo,
                          int64_t diag_shift, bool sym) {
-  // one workgroup per 128 x 128 tile with the X panels in LDS where it beats the one-wave-per-32x32 kernels: P > 32
-  // (measured, TFLOP/s tiled vs wave: N = 100 000, P = 50: 44.7 vs 38.5; N = 30 000, P = 50: 37.2 vs 33.9;
-  //  N = 50 000, P = 20: 21.1 vs 20.7; N = 20 000, P = 20: 17.8 vs 19.9; BIGKRLS_KB=wave|tiled forces either)
+  // the development switches of kb_plan (csrc/ktplan.h), read once per process
   static const int kb_force = [] {
     const char* e = getenv("BIGKRLS_KB");
     return e ? (std::string(e) == "tiled" ? 1 : (std::string(e) == "wave" ? -1 : 0)) : 0;
   }();
-  const bool big = u >= 1024 && v >= 1024;
-  if (kb_force > 0 || (kb_force == 0 && big && p > 32)) {
-    const int tiles_m = (int)((u + 127) / 128), tiles_n = (int)((v + 127) / 128);
-    SyrkMap mp{};
-    int64_t nt = (int64_t)tiles_m * tiles_n;
-    if (sym) {
-      // rows per band: the A panels of a band are tiny (128 P doubles each): 32 rows keep them and the streamed B
-      // panels far inside the L2
-      static const int r_env = [] { const char* e = getenv("BIGKRLS_KB_R"); return e ? atoi(e) : 0; }();
-      int R = r_env > 0 ? r_env : 32;
-      while ((tiles_m + R - 1) / R > 159) ++R;
-      mp.tiles = tiles_m; mp.c0 = 0; mp.c1 = tiles_m; mp.R = R; mp.band0 = 0; mp.t_off = 0;
-      int64_t acc = 0;
-      int nbands = 0;
-      for (int b0 = 0; b0 * R < tiles_m; ++b0, ++nbands) {
-        mp.band_start[nbands] = (int)acc;
-        for (int tmr = b0 * R; tmr < std::min((b0 + 1) * R, tiles_m); ++tmr) acc += tmr + 1;
-      }
-      mp.band_start[nbands] = (int)acc;
-      mp.nband = nbands;
-      nt = acc;
-    }
-    BK_REQUIRE(nt < (1ll << 31), "kernel_block: too many tiles");
-    BK_TRY(ensure_dyn_smem(ctx, sym ? (const void*)kernel_block_tiled_kernel<true> : (const void*)kernel_block_tiled_kernel<false>,
-                           kbt_smem_bytes()));
-    BK_TRY(prof_begin(ctx, "kernel_block", 2.0 * (double)u * (double)v * (double)p));
-    if (sym)
-      hipLaunchKernelGGL(kernel_block_tiled_kernel<true>, dim3((unsigned)nt), dim3(NT), kbt_smem_bytes(), ctx->stream, A, lda,
-                         (int)u, B, ldb, (int)v, (int)p, (const double*)pna, (const double*)pnb, -1.0 / sigma, out, ldo,
-                         diag_shift, tiles_m, tiles_n, mp);
-    else
-      hipLaunchKernelGGL(kernel_block_tiled_kernel<false>, dim3((unsigned)nt), dim3(NT), kbt_smem_bytes(), ctx->stream, A, lda,
-                         (int)u, B, ldb, (int)v, (int)p, (const double*)pna, (const double*)pnb, -1.0 / sigma, out, ldo,
-                         diag_shift, tiles_m, tiles_n, mp);
-    BK_CHECK_LAUNCH();
-    BK_TRY(prof_end(ctx, "kernel_block"));
-    return BIGKRLS_OK;
-  }
-  if (p <= 128 && sym) {
-    // symmetric Gram matrix (bGaussKernel): lower wave tiles + mirrored stores
-    const int tiles = (int)((u + 31) / 32);
-    const int64_t ntiles = (int64_t)tiles * (tiles + 1) / 2;
-    BK_TRY(prof_begin(ctx, "kernel_block", 2.0 * (double)u * (double)v * (double)p));
-    const int steps = (int)((p + 3) / 4);
-    const int chunks = (steps + 7) / 8;
-    const int ks = (steps + chunks - 1) / chunks;
-    BK_REQUIRE((ntiles + 3) / 4 < (1ll << 31), "kernel_block: too many tiles");
-    const dim3 grid((unsigned)((ntiles + 3) / 4));
-    const int band_rows = kb_band_rows(p, tiles);
-    const int kb_nt = kb_nontemporal(u, p);
-#define BK_KBS(KS)                                                                                 \
-  hipLaunchKernelGGL(kernel_block_sym_kernel<KS>, grid, dim3(NT), 0, ctx->stream, A, lda, (int)u,   \
-                     (int)p, (const double*)pna, -1.0 / sigma, out, ldo, tiles, band_rows, kb_nt, ntiles)
-    switch (ks) {
-      case 1: BK_KBS(1); break;
-      case 2: BK_KBS(2); break;
-      case 3: BK_KBS(3); break;
-      case 4: BK_KBS(4); break;
-      case 5: BK_KBS(5); break;
-      case 6: BK_KBS(6); break;
-      case 7: BK_KBS(7); break;
-      default: BK_KBS(8); break;
-    }
-#undef BK_KBS
-    BK_CHECK_LAUNCH();
-    BK_TRY(prof_end(ctx, "kernel_block"));
-    return BIGKRLS_OK;
-  }
-  if (p <= 128) {
-    const int tiles_m = (int)((u + 31) / 32), tiles_n = (int)((v + 31) / 32);
-    const int64_t ntiles = (int64_t)tiles_m * tiles_n;
-    BK_TRY(prof_begin(ctx, "kernel_block", 2.0 * (double)u * (double)v * (double)p));
-    const int steps = (int)((p + 3) / 4);
-    const int chunks = (steps + 7) / 8;
-    const int ks = (steps + chunks - 1) / chunks;  // 1..8 MFMA steps per chunk, minimal padding
-    BK_REQUIRE((ntiles + 3) / 4 < (1ll << 31), "kernel_block: too many tiles");
-    const dim3 grid((unsigned)((ntiles + 3) / 4));
-    const int band_rows = kb_band_rows(p, tiles_m);
-    const int kb_nt = kb_nontemporal(std::max(u, v), p);
-#define BK_KBW(KS)                                                                                  \
-  hipLaunchKernelGGL(kernel_block_wave_kernel<KS>, grid, dim3(NT), 0, ctx->stream, A, lda, (int)u, B, \
-                     ldb, (int)v, (int)p, (const double*)pna, (const double*)pnb, -1.0 / sigma, out,  \
-                     ldo, diag_shift, tiles_m, tiles_n, band_rows, kb_nt, ntiles)
-    switch (ks) {
-      case 1: BK_KBW(1); break;
-      case 2: BK_KBW(2); break;
-      case 3: BK_KBW(3); break;
-      case 4: BK_KBW(4); break;
-      case 5: BK_KBW(5); break;
-      case 6: BK_KBW(6); break;
-      case 7: BK_KBW(7); break;
-      default: BK_KBW(8); break;
-    }
-#undef BK_KBW
-    BK_CHECK_LAUNCH();
-    BK_TRY(prof_end(ctx, "kernel_block"));
-    return BIGKRLS_OK;
-  }
-  GemmOperands g{A, B, lda, ldb, (int)u, (int)v, (int)p, nullptr};
-  constexpr int KBN = 64;
-  const int tiles_m = (int)((u + BM - 1) / BM), tiles_n = (int)((v + KBN - 1) / KBN);
-  BK_TRY(ensure_dyn_smem(ctx, (const void*)kernel_block_kernel<KBN>, smem_bytes(KBN)));
+  static const int r_env = [] { const char* e = getenv("BIGKRLS_KB_R"); return e ? atoi(e) : 0; }();
+  static const int nt_env = [] { const char* e = getenv("BIGKRLS_KB_NT"); return e ? atoi(e) : -1; }();
+  // The wave kernels by their KS = 1..8, named one by one: a code object lays its kernels out in the order in which
+  // the source first names them, and chosen through with_ks they would be instantiated at the call and move ahead.
+  using SymFn = void (*)(const double*, int64_t, int, int, const double*, double, double*, int64_t, int, int, int, int64_t);
+  using WaveFn = void (*)(const double*, int64_t, int, const double*, int64_t, int, int, const double*, const double*, double,
+                          double*, int64_t, int64_t, int, int, int, int, int64_t);
+  const auto tiled_fn = sym ? kernel_block_tiled_kernel<true> : kernel_block_tiled_kernel<false>;
+  static constexpr SymFn sym_fns[8] = {kernel_block_sym_kernel<1>, kernel_block_sym_kernel<2>, kernel_block_sym_kernel<3>,
+                                       kernel_block_sym_kernel<4>, kernel_block_sym_kernel<5>, kernel_block_sym_kernel<6>,
+                                       kernel_block_sym_kernel<7>, kernel_block_sym_kernel<8>};
+  static constexpr WaveFn wave_fns[8] = {kernel_block_wave_kernel<1>, kernel_block_wave_kernel<2>, kernel_block_wave_kernel<3>,
+                                         kernel_block_wave_kernel<4>, kernel_block_wave_kernel<5>, kernel_block_wave_kernel<6>,
+                                         kernel_block_wave_kernel<7>, kernel_block_wave_kernel<8>};
+  constexpr auto generic_fn = kernel_block_kernel<KB_GENERIC_BN>;
+  static_assert(BM == KB_GENERIC_BM, "kb_plan counts the generic kernel's tiles");
+
+  const KbPlan k = kb_plan(u, v, p, sym, kb_force, r_env, nt_env);
+  const bool wave = k.arm == KB_SYM_WAVE || k.arm == KB_WAVE;   // (their ks is 1..8)
+  BK_REQUIRE(wave ? k.grid < (1ll << 31) : (k.arm == KB_GENERIC || k.ntiles < (1ll << 31)), "kernel_block: too many tiles");
+  if (k.arm == KB_TILED) BK_TRY(ensure_dyn_smem(ctx, (const void*)tiled_fn, kbt_smem_bytes()));
+  if (k.arm == KB_GENERIC) BK_TRY(ensure_dyn_smem(ctx, (const void*)generic_fn, smem_bytes(KB_GENERIC_BN)));
   BK_TRY(prof_begin(ctx, "kernel_block", 2.0 * (double)u * (double)v * (double)p));
-  hipLaunchKernelGGL(kernel_block_kernel<KBN>, dim3(tiles_m * tiles_n), dim3(NT), smem_bytes(KBN),
-                     ctx->stream, g, (const double*)pna, (const double*)pnb, -1.0 / sigma, out, ldo,
-                     tiles_m, tiles_n, diag_shift);
+  const double nis = -1.0 / sigma;
+  const dim3 grid((unsigned)k.grid);
+  if (k.arm == KB_TILED) {
+    hipLaunchKernelGGL(tiled_fn, grid, dim3(NT), kbt_smem_bytes(), ctx->stream, A, lda, (int)u, B, ldb, (int)v, (int)p, pna,
+                       pnb, nis, out, ldo, diag_shift, k.tiles_m, k.tiles_n, k.map);
+  } else if (k.arm == KB_SYM_WAVE) {   // symmetric Gram matrix (bGaussKernel): lower wave tiles + mirrored stores
+    hipLaunchKernelGGL(sym_fns[k.ks - 1], grid, dim3(NT), 0, ctx->stream, A, lda, (int)u, (int)p, pna, nis, out, ldo,
+                       k.tiles_m, k.band_rows, k.nontemporal, k.ntiles);
+  } else if (k.arm == KB_WAVE) {
+    hipLaunchKernelGGL(wave_fns[k.ks - 1], grid, dim3(NT), 0, ctx->stream, A, lda, (int)u, B, ldb, (int)v, (int)p, pna, pnb,
+                       nis, out, ldo, diag_shift, k.tiles_m, k.tiles_n, k.band_rows, k.nontemporal, k.ntiles);
+  } else {
+    GemmOperands g{A, B, lda, ldb, (int)u, (int)v, (int)p, nullptr};
+    hipLaunchKernelGGL(generic_fn, dim3(k.tiles_m * k.tiles_n), dim3(NT), smem_bytes(KB_GENERIC_BN), ctx->stream, g, pna, pnb,
+                       nis, out, ldo, k.tiles_m, k.tiles_n, diag_shift);
+  }
   BK_CHECK_LAUNCH();
   BK_TRY(prof_end(ctx, "kernel_block"));
   return BIGKRLS_OK;
@@ -2625,47 +2535,13 @@ __global__ __launch_bounds__(NT, 2) void kernel_contract_wide_kernel(
 }
 
 // ---- the host side of the frame ----
-// The KS of the tile kernels for p columns: the MFMA steps of the Gram tile where the fragments fit (p <= 32), else 0.
-static int ks_of(int64_t p) {
-  const int steps = (int)((p + 3) / 4);
-  return steps <= 8 ? steps : 0;
-}
-// f(std::integral_constant<int, KS>()) for a runtime ks in 0..8
-template <class F>
-static auto with_ks(int ks, F&& f) {
-  switch (ks) {
-    case 1: return f(std::integral_constant<int, 1>());
-    case 2: return f(std::integral_constant<int, 2>());
-    case 3: return f(std::integral_constant<int, 3>());
-    case 4: return f(std::integral_constant<int, 4>());
-    case 5: return f(std::integral_constant<int, 5>());
-    case 6: return f(std::integral_constant<int, 6>());
-    case 7: return f(std::integral_constant<int, 7>());
-    case 8: return f(std::integral_constant<int, 8>());
-    default: return f(std::integral_constant<int, 0>());
-  }
-}
+// (ks_of, with_ks and plan_loop_splits: csrc/ktplan.h)
 // the waves of a tile kernel that the device holds at once (2 or 3 per SIMD, by the kernel's registers)
 static int wave_slots(bigkrls_ctx* ctx, const void* fn, int64_t* slots) {
   int cap = 0;
   BK_TRY(resident_capacity(ctx, fn, &cap, NT));
   *slots = (int64_t)cap * (NT / 64);
   return BIGKRLS_OK;
-}
-// Loop splits against the wave slots: the time is about (rounds of resident waves) x (loop tiles per wave), so the split
-// count minimises ceil(base s / slots) / s for `base` tasks per split -- a last round that is nearly empty costs as much
-// as a full one (C3 shape: 313 tiles x 7 splits = 2191 waves on 2048 slots took 1.36 ms). At most 64 splits, each at
-// least 16 loop tiles (256 rows), all partial sums together at most 64 MB; fewer splits on a tie (a gain below 2 % does
-// not count).
-static int64_t plan_loop_splits(int64_t base, int64_t slots, int64_t ltiles, int64_t bytes_per_split) {
-  const int64_t max_split = std::max<int64_t>(1, std::min<int64_t>({(int64_t)64, ltiles / 16, (64ll << 20) / bytes_per_split}));
-  int64_t nsplit = 1;
-  double best = (double)((base + slots - 1) / slots);
-  for (int64_t s = 2; s <= max_split; ++s) {
-    const double cost = (double)((base * s + slots - 1) / slots) / (double)s;
-    if (cost < best * 0.98) { best = cost; nsplit = s; }
-  }
-  return nsplit;
 }
 // One launch over nsplit loop splits and what follows it. launch(dst, ldd, split_stride) starts the tile kernel: a single
 // split stores the ns x nc result where it belongs; several store their partial sums (each ns x nc, ld ns) into the
@@ -2770,11 +2646,7 @@ int kernel_contract(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, c
 // of (tile, chunk, split), and the loop tiles, which start at l_begin (not at a multiple of 16) and are masked by
 // l < l_end (not by NL).
 // A segment that is a whole group stores into out; the segments of a longer group store into their slots of `part`
-// (each NS x Q, ld NS) and contract_grouped_reduce_kernel adds them in segment order.
-struct KcgSeg {
-  int l_begin, l_end, group, slot;   // slot < 0: the group's only segment
-};
-
+// (each NS x Q, ld NS) and contract_grouped_reduce_kernel adds them in segment order. (KcgSeg: csrc/ktplan.h)
 template <int KS, int CT>
 __global__ __launch_bounds__(NT) void kernel_contract_grouped_kernel(
     const double* __restrict__ S, int64_t lds, int NS, const double* __restrict__ L, int64_t ldl, int P,
@@ -2877,6 +2749,69 @@ __global__ void contract_gather_kernel(int U, int P, int Q, const int* __restric
   }
 }
 
+// The device side of a grouped pass: the table (segments, then the multi triples), the permutation and the gathered
+// loop rows, all carved from SLOT_KCG_GATHER in that order, and the partial sums of the cut groups (SLOT_KCG_PART).
+struct KcgDevice {
+  const KcgSeg* segs;
+  const int *multi, *perm;   // perm: only with a permutation
+  double *Lg, *ng, *Wg;      // the loop rows, their norms and W in group order (u x p, u, u x q; ld u): likewise
+  double* part;
+};
+// Carves the buffers and sends the table and, if there is one, the permutation (perm: group_order's).
+static int kcg_upload(bigkrls_ctx* ctx, const GroupedPlan& pl, const std::vector<int32_t>& perm, int64_t u, int64_t v,
+                      int64_t p, int64_t q, KcgDevice* d) {
+  hipStream_t st = ctx->stream;
+  const bool identity = perm.empty();
+  const int64_t nseg = (int64_t)pl.segs.size(), nmulti = (int64_t)pl.multi.size() / 3;
+  const int64_t b_seg = nseg * (int64_t)sizeof(KcgSeg), b_mu = (nmulti * 12 + 15) / 16 * 16;
+  const int64_t b_perm = identity ? 0 : (u * 4 + 15) / 16 * 16, b_idx = b_seg + b_mu + b_perm;
+  const int64_t gather_doubles = identity ? 0 : u * (p + q + 1);
+  void* pg = nullptr;
+  void* ppart = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_KCG_GATHER, b_idx + gather_doubles * (int64_t)sizeof(double) + 64, &pg));
+  BK_TRY(ws_get(ctx, SLOT_KCG_PART, std::max<int64_t>(pl.nslots, 1) * v * q * (int64_t)sizeof(double), &ppart));
+  char* dbase = (char*)pg;
+  d->segs = (const KcgSeg*)dbase;
+  d->multi = (const int*)(dbase + b_seg);
+  d->perm = (const int*)(dbase + b_seg + b_mu);
+  d->Lg = (double*)(dbase + b_idx);
+  d->ng = d->Lg + u * p;
+  d->Wg = d->ng + u;
+  d->part = (double*)ppart;
+  const bool inline_table = nseg <= KCG_INLINE_SEGS && nmulti <= KCG_INLINE_MULTI;
+  if (inline_table) {
+    KcgInline t;
+    std::memcpy(t.s, pl.segs.data(), (size_t)b_seg);
+    if (nmulti > 0) std::memcpy(t.m, pl.multi.data(), (size_t)nmulti * 12);
+    hipLaunchKernelGGL(contract_table_kernel, dim3(1), dim3(256), 0, st, t, (int)nseg, (int)(3 * nmulti),
+                       (KcgSeg*)dbase, (int*)(dbase + b_seg));
+    BK_CHECK_LAUNCH();
+  }
+  if (inline_table && identity) return BIGKRLS_OK;
+  // a pinned buffer of this function's own, guarded by an event behind the upload: waiting for the STREAM here (the
+  // context's shared pinned buffer would need it) leaves the device idle between the centring kernels and the pass,
+  // 4 % of the whole call at u = v = 20 000
+  if (ctx->ev_kcg) BK_HIP(hipEventSynchronize(ctx->ev_kcg));   // (the previous call's upload has left the buffer)
+  else BK_HIP(hipEventCreateWithFlags(&ctx->ev_kcg, hipEventDisableTiming));
+  if (ctx->h_kcg_bytes < b_idx) {
+    if (ctx->h_kcg) BK_HIP(hipHostFree(ctx->h_kcg));
+    ctx->h_kcg = nullptr;
+    ctx->h_kcg_bytes = 0;
+    BK_HIP(hipHostMalloc((void**)&ctx->h_kcg, (size_t)b_idx + 4096, hipHostMallocDefault));
+    ctx->h_kcg_bytes = b_idx + 4096;
+  }
+  char* hb = ctx->h_kcg;
+  const int64_t from = inline_table ? b_seg + b_mu : 0;      // (the table is already there: the permutation alone)
+  if (!inline_table) {
+    std::memcpy(hb, pl.segs.data(), (size_t)b_seg);
+    if (nmulti > 0) std::memcpy(hb + b_seg, pl.multi.data(), (size_t)nmulti * 12);
+  }
+  if (!identity) std::memcpy(hb + b_seg + b_mu, perm.data(), (size_t)u * 4);
+  BK_HIP(hipMemcpyAsync(dbase + from, hb + from, (size_t)(b_idx - from), hipMemcpyHostToDevice, st));
+  BK_HIP(hipEventRecord(ctx->ev_kcg, st));
+  return BIGKRLS_OK;
+}
+
 // For operands that are already centred and come with their squared row norms (kernel_contract_centred's contract): S the
 // stationary rows (v x p, lds), L the loop rows (u x p, ldl) with the labels h_group, W u x q.
 int kernel_contract_grouped_centred(bigkrls_ctx* ctx, const double* S, int64_t v, int64_t lds, const double* nrm_s,
@@ -2891,41 +2826,11 @@ int kernel_contract_grouped_centred(bigkrls_ctx* ctx, const double* S, int64_t v
   BK_REQUIRE(G * q < (1ll << 31) && v * q < (1ll << 40), "kernel_contract_grouped: out too large");
   BK_REQUIRE(G >= 1, "kernel_contract_grouped: G must be at least 1: the label of row 1 is outside [0, G)");
   hipStream_t st = ctx->stream;
+  // the rows of one group in their original order (the host works while the device centres the operands)
+  const GroupOrder go = group_order(h_group, u, G);
+  BK_REQUIRE(go.bad < 0, "kernel_contract_grouped: the label of row " + std::to_string(go.bad + 1) + " is outside [0, G)");
+  const bool identity = go.perm.empty();
 
-  // ---- stable counting sort (cluster_scores' rule): the rows of one group in their original order -------------------
-  // Rows that are already grouped (labels that never decrease) are recognised first, in a pass without the counters'
-  // store-to-load chains: their offsets are the places where the label changes and nothing is permuted. (The host works
-  // while the device centres the operands; at u = 20 000 the counting passes take longer than that and would show.)
-  std::vector<int64_t> off((size_t)G + 1, 0);
-  std::vector<int32_t> perm;
-  bool identity = h_group[0] >= 0 && h_group[u - 1] < G;
-  {
-    int64_t decreases = 0;
-    for (int64_t i = 1; i < u; ++i) decreases += h_group[i] < h_group[i - 1];
-    identity = identity && decreases == 0;
-  }
-  if (identity) {
-    int64_t prev = -1;
-    for (int64_t i = 0; i < u; ++i) {
-      const int64_t g = h_group[i];
-      if (g == prev) continue;
-      for (int64_t gg = prev + 1; gg <= g; ++gg) off[(size_t)gg] = i;
-      prev = g;
-    }
-    for (int64_t gg = prev + 1; gg <= G; ++gg) off[(size_t)gg] = u;
-  } else {
-    for (int64_t i = 0; i < u; ++i) {
-      BK_REQUIRE(h_group[i] >= 0 && h_group[i] < G, "kernel_contract_grouped: the label of row " + std::to_string(i + 1) +
-                                                        " is outside [0, G)");
-      ++off[(size_t)h_group[i] + 1];
-    }
-    for (int64_t g = 0; g < G; ++g) off[(size_t)g + 1] += off[(size_t)g];
-    perm.resize((size_t)u);
-    std::vector<int64_t> pos(off.begin(), off.end() - 1);
-    for (int64_t i = 0; i < u; ++i) perm[(size_t)(pos[(size_t)h_group[i]]++)] = (int32_t)i;
-  }
-
-  // ---- the kernel ---------------------------------------------------------------------------------------------------
   const int CT = q <= 16 ? 1 : (q <= 32 ? 2 : 4);
   using KcgFn = void (*)(const double*, int64_t, int, const double*, int64_t, int, const double*, const double*, double,
                          const double*, int64_t, int, double*, int64_t, double*, const KcgSeg*, int, int, int64_t);
@@ -2937,130 +2842,32 @@ int kernel_contract_grouped_centred(bigkrls_ctx* ctx, const double* S, int64_t v
   });
   const int64_t stiles = (v + 16 * KC_MS - 1) / (16 * KC_MS);
   const int64_t nchunks = (q + 16 * CT - 1) / (16 * CT);
-
-  // ---- the segments ---------------------------------------------------------------------------------------------------
-  // plan_loop_splits' model over all groups together: the time is about (rounds of resident waves) x (loop tiles
-  // of the longest part). A candidate s cuts the largest group (lt_max loop tiles) into s equal parts and every group
-  // into parts of about that length, s_g = ceil(lt_g s / lt_max), each part at least 16 loop tiles (s_g <= lt_g / 16) and
-  // at most 64 parts per group; the slots of the groups with s_g > 1 hold at most 64 MB; s minimises
-  // ceil(base sum_g s_g / slots) / s, fewer parts on a tie (a gain below 2 % does not count). With G = 1 this is
-  // plan_loop_splits' rule, cuts included: part k of a group is its loop tiles [lt k / s, lt (k + 1) / s).
   int64_t slots = 0;
   BK_TRY(wave_slots(ctx, (const void*)fn, &slots));
-  const int64_t base = stiles * nchunks;
-  const int64_t slot_cap = (64ll << 20) / (v * q * (int64_t)sizeof(double));
-  int64_t lt_max = 0, nonempty = 0;
-  for (int64_t g = 0; g < G; ++g) {
-    const int64_t ng = off[(size_t)g + 1] - off[(size_t)g];
-    lt_max = std::max(lt_max, (ng + 15) / 16);
-    nonempty += ng > 0;
-  }
-  auto parts_of = [&](int64_t g, int64_t s) {
-    const int64_t lt = (off[(size_t)g + 1] - off[(size_t)g] + 15) / 16;
-    const int64_t most = std::max<int64_t>(1, std::min<int64_t>(64, lt / 16));
-    return std::min(most, std::max<int64_t>(1, (lt * s + lt_max - 1) / lt_max));
-  };
-  const int64_t max_split = std::max<int64_t>(1, std::min<int64_t>(64, lt_max / 16));
-  int64_t nsplit = 1;
-  double best = (double)((base * nonempty + slots - 1) / slots);
-  for (int64_t s = 2; s <= max_split; ++s) {
-    int64_t nseg = 0, nslots = 0;
-    for (int64_t g = 0; g < G; ++g) {
-      if (off[(size_t)g + 1] == off[(size_t)g]) continue;
-      const int64_t sg = parts_of(g, s);
-      nseg += sg;
-      if (sg > 1) nslots += sg;
-    }
-    if (nslots > slot_cap) break;   // (the slots grow with s)
-    const double cost = (double)((base * nseg + slots - 1) / slots) / (double)s;
-    if (cost < best * 0.98) { best = cost; nsplit = s; }
-  }
-  std::vector<KcgSeg> segs;
-  std::vector<int32_t> multi;   // (group, first slot, segments) of the groups that are not one segment
-  int64_t nslots = 0;
-  for (int64_t g = 0; g < G; ++g) {
-    const int64_t b = off[(size_t)g], t = off[(size_t)g + 1];
-    if (b == t) {
-      multi.insert(multi.end(), {(int32_t)g, 0, 0});
-      continue;
-    }
-    const int64_t lt = (t - b + 15) / 16, sg = parts_of(g, nsplit);
-    if (sg > 1) multi.insert(multi.end(), {(int32_t)g, (int32_t)nslots, (int32_t)sg});
-    for (int64_t k = 0; k < sg; ++k) {
-      const int64_t t0 = lt * k / sg, t1 = lt * (k + 1) / sg;
-      segs.push_back(KcgSeg{(int)(b + 16 * t0), (int)std::min(b + 16 * t1, t), (int)g, sg > 1 ? (int)nslots++ : -1});
-    }
-  }
-  const int64_t nseg = (int64_t)segs.size(), nmulti = (int64_t)multi.size() / 3;
-  const int64_t ntasks = base * nseg;
+  // the slots of the cut groups hold at most 64 MB
+  const GroupedPlan pl = plan_grouped_segments(go.off.data(), G, stiles * nchunks, slots,
+                                               (64ll << 20) / (v * q * (int64_t)sizeof(double)));
+  const int64_t nmulti = (int64_t)pl.multi.size() / 3;
+  const int64_t ntasks = stiles * nchunks * (int64_t)pl.segs.size();
   BK_REQUIRE((ntasks + 3) / 4 < (1ll << 31), "kernel_contract_grouped: too many tiles");
+  KcgDevice d;
+  BK_TRY(kcg_upload(ctx, pl, go.perm, u, v, p, q, &d));
 
-  // ---- the table, the permutation and the gathered rows ---------------------------------------------------------------------
-  const int64_t b_seg = nseg * (int64_t)sizeof(KcgSeg), b_mu = (nmulti * 12 + 15) / 16 * 16;
-  const int64_t b_perm = identity ? 0 : (u * 4 + 15) / 16 * 16, b_idx = b_seg + b_mu + b_perm;
-  const int64_t gather_doubles = identity ? 0 : u * (p + q + 1);
-  void* pg = nullptr;
-  void* ppart = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_KCG_GATHER, b_idx + gather_doubles * (int64_t)sizeof(double) + 64, &pg));
-  BK_TRY(ws_get(ctx, SLOT_KCG_PART, std::max<int64_t>(nslots, 1) * v * q * (int64_t)sizeof(double), &ppart));
-  char* dbase = (char*)pg;
-  const KcgSeg* d_segs = (const KcgSeg*)dbase;
-  const int* d_multi = (const int*)(dbase + b_seg);
-  const int* d_perm = (const int*)(dbase + b_seg + b_mu);
-  double* dLg = (double*)(dbase + b_idx);
-  double* dng = dLg + u * p;
-  double* dWg = dng + u;
-  const bool inline_table = nseg <= KCG_INLINE_SEGS && nmulti <= KCG_INLINE_MULTI;
-  if (inline_table) {
-    KcgInline t;
-    std::memcpy(t.s, segs.data(), (size_t)b_seg);
-    if (nmulti > 0) std::memcpy(t.m, multi.data(), (size_t)nmulti * 12);
-    hipLaunchKernelGGL(contract_table_kernel, dim3(1), dim3(256), 0, st, t, (int)nseg, (int)(3 * nmulti),
-                       (KcgSeg*)dbase, (int*)(dbase + b_seg));
-    BK_CHECK_LAUNCH();
-  }
-  if (!inline_table || !identity) {
-    // a pinned buffer of this function's own, guarded by an event behind the upload: waiting for the STREAM here (the
-    // context's shared pinned buffer would need it) leaves the device idle between the centring kernels and the pass,
-    // 4 % of the whole call at u = v = 20 000
-    if (ctx->ev_kcg) BK_HIP(hipEventSynchronize(ctx->ev_kcg));   // (the previous call's upload has left the buffer)
-    else BK_HIP(hipEventCreateWithFlags(&ctx->ev_kcg, hipEventDisableTiming));
-    if (ctx->h_kcg_bytes < b_idx) {
-      if (ctx->h_kcg) BK_HIP(hipHostFree(ctx->h_kcg));
-      ctx->h_kcg = nullptr;
-      ctx->h_kcg_bytes = 0;
-      BK_HIP(hipHostMalloc((void**)&ctx->h_kcg, (size_t)b_idx + 4096, hipHostMallocDefault));
-      ctx->h_kcg_bytes = b_idx + 4096;
-    }
-    char* hb = ctx->h_kcg;
-    const int64_t from = inline_table ? b_seg + b_mu : 0;      // (the table is already there: the permutation alone)
-    if (!inline_table) {
-      std::memcpy(hb, segs.data(), (size_t)b_seg);
-      if (nmulti > 0) std::memcpy(hb + b_seg, multi.data(), (size_t)nmulti * 12);
-    }
-    if (!identity) std::memcpy(hb + b_seg + b_mu, perm.data(), (size_t)u * 4);
-    BK_HIP(hipMemcpyAsync(dbase + from, hb + from, (size_t)(b_idx - from), hipMemcpyHostToDevice, st));
-    BK_HIP(hipEventRecord(ctx->ev_kcg, st));
-  }
-  const double *Lp = L, *nlp = nrm_l, *Wp = W;
-  int64_t ldlp = ldl, ldwp = ldw;
   BK_TRY(prof_begin(ctx, "kernel_contract_grouped", 2.0 * (double)u * (double)v * (double)(p + q)));
   if (!identity) {
     const int blocks = (int)std::min<int64_t>((u * (p + q + 1) + 255) / 256, 8192);
-    hipLaunchKernelGGL(contract_gather_kernel, dim3(blocks), dim3(256), 0, st, (int)u, (int)p, (int)q, d_perm, L, ldl, nrm_l,
-                       W, ldw, dLg, dng, dWg);
+    hipLaunchKernelGGL(contract_gather_kernel, dim3(blocks), dim3(256), 0, st, (int)u, (int)p, (int)q, d.perm, L, ldl, nrm_l,
+                       W, ldw, d.Lg, d.ng, d.Wg);
     BK_CHECK_LAUNCH();
-    Lp = dLg; nlp = dng; Wp = dWg;
-    ldlp = u; ldwp = u;
   }
-  hipLaunchKernelGGL(fn, dim3((unsigned)((ntasks + 3) / 4)), dim3(NT), 0, st, S, lds, (int)v, Lp, ldlp, (int)p, nrm_s,
-                     nlp, -1.0 / sigma, Wp, ldwp, (int)q, out, ldo, (double*)ppart, d_segs, (int)stiles, (int)nchunks,
-                     ntasks);
+  hipLaunchKernelGGL(fn, dim3((unsigned)((ntasks + 3) / 4)), dim3(NT), 0, st, S, lds, (int)v, identity ? L : d.Lg,
+                     identity ? ldl : u, (int)p, nrm_s, identity ? nrm_l : d.ng, -1.0 / sigma, identity ? W : d.Wg,
+                     identity ? ldw : u, (int)q, out, ldo, d.part, d.segs, (int)stiles, (int)nchunks, ntasks);
   BK_CHECK_LAUNCH();
   if (nmulti > 0) {
     const dim3 grid((unsigned)std::min<int64_t>((v * q + 255) / 256, 1024), (unsigned)std::min<int64_t>(nmulti, 1024));
-    hipLaunchKernelGGL(contract_grouped_reduce_kernel, grid, dim3(256), 0, st, (int)v, (int)q, (int)nmulti, d_multi,
-                       (const double*)ppart, out, ldo);
+    hipLaunchKernelGGL(contract_grouped_reduce_kernel, grid, dim3(256), 0, st, (int)v, (int)q, (int)nmulti, d.multi,
+                       (const double*)d.part, out, ldo);
     BK_CHECK_LAUNCH();
   }
   BK_TRY(prof_end(ctx, "kernel_contract_grouped"));
@@ -3112,7 +2919,6 @@ int kernel_contract_grouped(bigkrls_ctx* ctx, const double* A, int64_t u, int64_
 // host's list needs no device copy and no synchronisation.
 constexpr int KL_MS = 4;       // 16-row stationary tiles per wave
 constexpr int KL_CW = 4;       // selected columns per wave (the chunk width)
-constexpr int KL_GROUP = 64;   // selected columns per launch
 struct LooCols {
   int c[KL_GROUP];
 };
@@ -3275,15 +3081,7 @@ int kernel_loo_colsums(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda
 // compiler's figures per KS and the chunk width they led to: DESIGN.md section 4, "Conditional effects".
 constexpr int KM_CW = 3;       // entries per wave (the chunk width) ...
 constexpr int KM_CW_KS8 = 2;   // ... and with KS = 8 (29 <= P <= 32), where the resident fragments leave room for two
-struct LooMomentEntries {
-  int c[KL_GROUP];           // the column every entry leaves out (one value per chunk)
-  int j[KL_GROUP];           // kind 1: the weight's column; kind 2: the second column left out; kind 0: c again
-  int kind[KL_GROUP];
-  int begin[KL_GROUP + 1];   // chunk cc holds the launch's entries [begin[cc], begin[cc + 1])
-};
-struct LooMomentDest {
-  int d[KL_GROUP];           // the caller's column of every entry of the launch
-};
+// (LooMomentEntries, LooMomentDest, and KL_GROUP entries per launch: csrc/ktplan.h)
 
 template <int KS, int CW>
 __global__ __launch_bounds__(NT, 2) void kernel_loo_moments_kernel(
@@ -3397,16 +3195,8 @@ __global__ void loo_moments_fill_kernel(int NS, double value, double* __restrict
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < NS; i += gridDim.x * blockDim.x) o[i] = value;
 }
 
-int kernel_loo_moments(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
-                       int64_t ldb, int64_t p, double sigma, const int64_t* h_entries, int64_t n_entries, double* out,
-                       int64_t ldo) {
-  BK_REQUIRE(u > 0 && v > 0 && p > 0, "kernel_loo_moments: bad dimensions");
-  BK_REQUIRE(u < (1ll << 31) && v < (1ll << 31) && p < (1ll << 20), "kernel_loo_moments: too large");
-  BK_REQUIRE(sigma > 0.0, "kernel_loo_moments: sigma must be > 0");
-  BK_REQUIRE(A && B && h_entries && out, "kernel_loo_moments: null pointer");
-  BK_REQUIRE(lda >= u && ldb >= v, "kernel_loo_moments: leading dimension of A or B too small");
-  BK_REQUIRE(ldo >= v, "kernel_loo_moments: leading dimension of out too small");
-  BK_REQUIRE(n_entries >= 1 && n_entries < (1ll << 20), "kernel_loo_moments: n_entries must be at least 1 (and below 2^20)");
+// every entry (kind, c, j): a known kind, its columns inside [0, p), j another column than c
+static int loo_moments_check_entries(const int64_t* h_entries, int64_t n_entries, int64_t p) {
   for (int64_t e = 0; e < n_entries; ++e) {
     const int64_t kind = h_entries[3 * e], c = h_entries[3 * e + 1], j = h_entries[3 * e + 2];
     const std::string where = "kernel_loo_moments: entry " + std::to_string(e) + " (kind " + std::to_string(kind) +
@@ -3418,32 +3208,35 @@ int kernel_loo_moments(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda
       BK_REQUIRE(j != c, where + "j must differ from c");
     }
   }
-  // An entry that leaves out every column (kind 0 at p = 1, kind 2 at p = 2) has the exponent 0 in every term: its sums
-  // are u, written as such (from the Gram tile the exponent would be rounding noise, and the sum u only to ~1e-16).
-  // The others in the order of their c (stable): a chunk is a run of up to cw entries of one c.
-  std::vector<int64_t> order;
-  order.reserve((size_t)n_entries);
-  for (int64_t e = 0; e < n_entries; ++e) {
-    const int64_t kind = h_entries[3 * e];
-    if ((kind == 0 && p == 1) || (kind == 2 && p == 2)) {
-      const int blocks = (int)std::min<int64_t>((v + 255) / 256, 1024);
-      hipLaunchKernelGGL(loo_moments_fill_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (int)v, (double)u, out + e * ldo);
-      BK_CHECK_LAUNCH();
-    } else {
-      order.push_back(e);
-    }
+  return BIGKRLS_OK;
+}
+
+int kernel_loo_moments(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
+                       int64_t ldb, int64_t p, double sigma, const int64_t* h_entries, int64_t n_entries, double* out,
+                       int64_t ldo) {
+  BK_REQUIRE(u > 0 && v > 0 && p > 0, "kernel_loo_moments: bad dimensions");
+  BK_REQUIRE(u < (1ll << 31) && v < (1ll << 31) && p < (1ll << 20), "kernel_loo_moments: too large");
+  BK_REQUIRE(sigma > 0.0, "kernel_loo_moments: sigma must be > 0");
+  BK_REQUIRE(A && B && h_entries && out, "kernel_loo_moments: null pointer");
+  BK_REQUIRE(lda >= u && ldb >= v, "kernel_loo_moments: leading dimension of A or B too small");
+  BK_REQUIRE(ldo >= v, "kernel_loo_moments: leading dimension of out too small");
+  BK_REQUIRE(n_entries >= 1 && n_entries < (1ll << 20), "kernel_loo_moments: n_entries must be at least 1 (and below 2^20)");
+  BK_TRY(loo_moments_check_entries(h_entries, n_entries, p));
+  // the entries that leave out every column are written as such; the others by c, KL_GROUP per launch (csrc/ktplan.h)
+  const int64_t cw = ks_of(p) == 8 ? KM_CW_KS8 : KM_CW;
+  const LooPlan pl = plan_loo_moments(h_entries, n_entries, p, cw);
+  for (int64_t e : pl.trivial) {
+    const int blocks = (int)std::min<int64_t>((v + 255) / 256, 1024);
+    hipLaunchKernelGGL(loo_moments_fill_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (int)v, (double)u, out + e * ldo);
+    BK_CHECK_LAUNCH();
   }
-  if (order.empty()) return BIGKRLS_OK;
-  std::stable_sort(order.begin(), order.end(),
-                   [h_entries](int64_t a, int64_t b) { return h_entries[3 * a + 1] < h_entries[3 * b + 1]; });
-  const int64_t n_sorted = (int64_t)order.size();
+  if (pl.launches.empty()) return BIGKRLS_OK;
 
   CentredOperands co;     // both operands moved by the column means of A (see centre_operands)
   BK_TRY(centre_operands(ctx, A, u, lda, B, v, ldb, p, &co));
   // the rows of B are stationary, the rows of A the loop (kernel_contract's trans = 1)
   const double *S = co.B, *L = co.A, *nrm_s = co.nb, *nrm_l = co.na;
   const int64_t ns = v, nl = u, lds = co.ldb, ldl = co.lda;
-  const int64_t cw = ks_of(p) == 8 ? KM_CW_KS8 : KM_CW;
   using KmFn = void (*)(const double*, int64_t, int, const double*, int64_t, int, int, const double*, const double*,
                         double, LooMomentEntries, double*, int64_t, int64_t, int, int, int, int, int64_t);
   const KmFn fn = with_ks(ks_of(p), [](auto ks) -> KmFn {
@@ -3454,54 +3247,25 @@ int kernel_loo_moments(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda
   BK_TRY(wave_slots(ctx, (const void*)fn, &slots));
   const int64_t stiles = (ns + 16 * KL_MS - 1) / (16 * KL_MS);
   const int64_t ltiles = (nl + 15) / 16;
-  for (int64_t g0 = 0; g0 < n_sorted; g0 += KL_GROUP) {
-    const int64_t nc = std::min<int64_t>(KL_GROUP, n_sorted - g0);
-    LooMomentEntries le;
-    LooMomentDest dest;
-    bool in_place = true;   // the launch's columns are consecutive columns of out, in order
-    for (int64_t i = 0; i < KL_GROUP; ++i) {
-      const int64_t e = order[(size_t)(g0 + std::min(i, nc - 1))];
-      le.kind[i] = (int)h_entries[3 * e];
-      le.c[i] = (int)h_entries[3 * e + 1];
-      le.j[i] = le.kind[i] == 0 ? le.c[i] : (int)h_entries[3 * e + 2];
-      dest.d[i] = (int)e;
-      if (i < nc && e != order[(size_t)g0] + i) in_place = false;
-    }
-    // chunks: every run of one c, split evenly into pieces of at most cw entries; the exponentials per row pair
-    int64_t nchunks = 0, nexp = 0;
-    for (int64_t r0 = 0; r0 < nc;) {
-      int64_t r1 = r0 + 1;
-      while (r1 < nc && le.c[r1] == le.c[r0]) ++r1;
-      const int64_t len = r1 - r0, pieces = (len + cw - 1) / cw;
-      for (int64_t q = 0; q < pieces; ++q) {
-        const int64_t b0 = r0 + len * q / pieces, b1 = r0 + len * (q + 1) / pieces;
-        le.begin[nchunks++] = (int)b0;
-        bool has01 = false;
-        for (int64_t i = b0; i < b1; ++i) {
-          if (le.kind[i] == 2) ++nexp; else has01 = true;
-        }
-        if (has01) ++nexp;
-      }
-      r0 = r1;
-    }
-    for (int64_t i = nchunks; i <= KL_GROUP; ++i) le.begin[i] = (int)nc;
+  for (const LooLaunch& ln : pl.launches) {
+    const int64_t nc = ln.nc, nchunks = ln.nchunks;
     const int64_t nsplit = plan_loop_splits(stiles * nchunks, slots, ltiles, ns * nc * (int64_t)sizeof(double));
     const int64_t ntasks = stiles * nchunks * nsplit;
     BK_REQUIRE((ntasks + 3) / 4 < (1ll << 31), "kernel_loo_moments: too many tiles");
     // the launch's columns go into out at once, or into a staging buffer and are scattered from there afterwards
     double* tmp = nullptr;
-    BK_TRY(launch_loop_splits(ctx, SLOT_LOO_PART, nsplit, ns, nc, in_place ? out + order[(size_t)g0] * ldo : nullptr, ldo,
+    BK_TRY(launch_loop_splits(ctx, SLOT_LOO_PART, nsplit, ns, nc, ln.in_place ? out + ln.first * ldo : nullptr, ldo,
                               &tmp, [&](double* dst, int64_t ldd, int64_t split_stride) -> int {
-      BK_TRY(prof_begin(ctx, "kernel_loo_moments", (double)ns * (double)nl * (double)nexp));
+      BK_TRY(prof_begin(ctx, "kernel_loo_moments", (double)ns * (double)nl * (double)ln.nexp));
       hipLaunchKernelGGL(fn, dim3((unsigned)((ntasks + 3) / 4)), dim3(NT), 0, ctx->stream, S, lds, (int)ns, L, ldl,
-                         (int)nl, (int)p, nrm_s, nrm_l, -1.0 / sigma, le, dst, ldd, split_stride, (int)stiles,
+                         (int)nl, (int)p, nrm_s, nrm_l, -1.0 / sigma, ln.le, dst, ldd, split_stride, (int)stiles,
                          (int)nchunks, (int)nsplit, (int)ltiles, ntasks);
       return BIGKRLS_OK;
     }));
-    if (!in_place) {
+    if (!ln.in_place) {
       const int blocks = (int)std::min<int64_t>((ns + 255) / 256, 1024);
       hipLaunchKernelGGL(loo_moments_scatter_kernel, dim3(blocks, (unsigned)nc), dim3(256), 0, ctx->stream, (int)ns,
-                         (const double*)tmp, dest, out, ldo);
+                         (const double*)tmp, ln.dest, out, ldo);
       BK_CHECK_LAUNCH();
     }
     BK_TRY(prof_end(ctx, "kernel_loo_moments"));

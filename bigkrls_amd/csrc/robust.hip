@@ -19,6 +19,7 @@
 // two calls give the same bits. Rows already grouped (identity permutation) are read without the indirection, 64
 // consecutive doubles of a column per wave; G = n needs no second pass at all.
 #include "hostprep.h"
+#include "ktplan.h"
 
 #include <cstring>
 
@@ -151,6 +152,35 @@ __global__ void sandwich_kernel(int k, const double* __restrict__ M, const doubl
   }
 }
 
+// The sorted rows cut into pieces (maximal runs of one cluster inside one 64-row chunk): the piece of every sorted row,
+// where every piece's sum goes (>= 0: the offset of the cluster's column in S; < 0: -(offset in the scratch) - 1), and
+// (cluster, first scratch column, pieces) of the clusters that are not one piece, the empty ones with 0 pieces.
+struct ClusterPieces {
+  std::vector<int32_t> row_piece, multi;
+  std::vector<long long> piece_dst;
+  int64_t ncolsP = 0, max_pieces = 0;   // scratch columns; the most pieces of one cluster
+};
+ClusterPieces cluster_pieces(const std::vector<int64_t>& off, int64_t n, int64_t G, int64_t k, int64_t lds) {
+  ClusterPieces pc;
+  pc.row_piece.resize((size_t)n);
+  for (int64_t g = 0; g < G; ++g) {
+    const int64_t b = off[(size_t)g], t = off[(size_t)g + 1];
+    if (b == t) {
+      pc.multi.insert(pc.multi.end(), {(int32_t)g, 0, 0});
+      continue;
+    }
+    const int64_t c0 = b / CS_ROWS, c1 = (t - 1) / CS_ROWS;
+    if (c1 > c0) pc.multi.insert(pc.multi.end(), {(int32_t)g, (int32_t)pc.ncolsP, (int32_t)(c1 - c0 + 1)});
+    if (c1 > c0) pc.max_pieces = std::max(pc.max_pieces, c1 - c0 + 1);
+    for (int64_t c = c0; c <= c1; ++c) {
+      const int64_t rb = std::max(b, c * CS_ROWS), re = std::min(t, (c + 1) * CS_ROWS);
+      for (int64_t r = rb; r < re; ++r) pc.row_piece[(size_t)r] = (int32_t)pc.piece_dst.size();
+      pc.piece_dst.push_back(c1 == c0 ? (long long)(g * lds) : -(long long)(pc.ncolsP++ * k) - 1);
+    }
+  }
+  return pc;
+}
+
 }  // namespace
 
 int cluster_scores(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* A, int64_t lda, const double* e,
@@ -158,9 +188,9 @@ int cluster_scores(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* A, int6
   BK_REQUIRE(n >= 0 && k >= 0 && n < (1ll << 31) && k < (1ll << 31), "cluster_scores: bad dimensions");
   BK_REQUIRE(G >= 1 && G < (1ll << 31), "cluster_scores: G must be at least 1");
   BK_REQUIRE(n == 0 || h_cluster, "cluster_scores: null labels");
-  for (int64_t i = 0; i < n; ++i)
-    BK_REQUIRE(h_cluster[i] >= 0 && h_cluster[i] < G, "cluster_scores: the label of row " + std::to_string(i + 1) +
-                                                          " is outside [0, G)");
+  // stable counting sort (csrc/ktplan.h): the rows of one cluster in their original order
+  const GroupOrder go = group_order(h_cluster, n, G);
+  BK_REQUIRE(go.bad < 0, "cluster_scores: the label of row " + std::to_string(go.bad + 1) + " is outside [0, G)");
   if (k == 0) return BIGKRLS_OK;
   BK_REQUIRE(S && lds >= k, "cluster_scores: null S or leading dimension of S too small");
   BK_REQUIRE(n == 0 || (A && e), "cluster_scores: null pointer");
@@ -168,38 +198,13 @@ int cluster_scores(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* A, int6
   BK_REQUIRE(G * lds < (1ll << 62) / 8, "cluster_scores: S too large");
   hipStream_t st = ctx->stream;
 
-  // ---- stable counting sort; the pieces ------------------------------------------------------------------------
-  std::vector<int64_t> off((size_t)G + 1, 0);
-  for (int64_t i = 0; i < n; ++i) ++off[(size_t)h_cluster[i] + 1];
-  for (int64_t g = 0; g < G; ++g) off[(size_t)g + 1] += off[(size_t)g];
-  std::vector<int32_t> perm((size_t)n), row_piece((size_t)n);
-  bool identity = true;
-  {
-    std::vector<int64_t> pos(off.begin(), off.end() - 1);
-    for (int64_t i = 0; i < n; ++i) {
-      const int64_t r = pos[(size_t)h_cluster[i]]++;
-      perm[(size_t)r] = (int32_t)i;
-      identity = identity && r == i;
-    }
-  }
-  std::vector<long long> piece_dst;
-  std::vector<int32_t> multi;         // (cluster, first scratch column, pieces) of the clusters that are not one piece
-  int64_t ncolsP = 0, max_pieces = 0;
-  for (int64_t g = 0; g < G; ++g) {
-    const int64_t b = off[(size_t)g], t = off[(size_t)g + 1];
-    if (b == t) {
-      multi.insert(multi.end(), {(int32_t)g, 0, 0});
-      continue;
-    }
-    const int64_t c0 = b / CS_ROWS, c1 = (t - 1) / CS_ROWS;
-    if (c1 > c0) multi.insert(multi.end(), {(int32_t)g, (int32_t)ncolsP, (int32_t)(c1 - c0 + 1)});
-    if (c1 > c0) max_pieces = std::max(max_pieces, c1 - c0 + 1);
-    for (int64_t c = c0; c <= c1; ++c) {
-      const int64_t rb = std::max(b, c * CS_ROWS), re = std::min(t, (c + 1) * CS_ROWS);
-      for (int64_t r = rb; r < re; ++r) row_piece[(size_t)r] = (int32_t)piece_dst.size();
-      piece_dst.push_back(c1 == c0 ? (long long)(g * lds) : -(long long)(ncolsP++ * k) - 1);
-    }
-  }
+  // ---- the pieces ----------------------------------------------------------------------------------------------
+  const std::vector<int32_t>& perm = go.perm;
+  const bool identity = perm.empty();   // (no row moves: the labels never decrease)
+  const ClusterPieces pc = cluster_pieces(go.off, n, G, k, lds);
+  const std::vector<int32_t>&row_piece = pc.row_piece, &multi = pc.multi;
+  const std::vector<long long>& piece_dst = pc.piece_dst;
+  const int64_t ncolsP = pc.ncolsP, max_pieces = pc.max_pieces;
   const int64_t npieces = (int64_t)piece_dst.size(), nmulti = (int64_t)multi.size() / 3;
   BK_REQUIRE(ncolsP < (1ll << 31), "cluster_scores: too many pieces");
 

@@ -12,6 +12,9 @@ vcov.est.c). Prints one JSON line per G: median times in ms, the largest differe
 largest entry, and (a) / (b).
 
     python tools/group_effects_bench.py [--n 20000] [--p 20] [--J 20] [--groups 1 4 50 400] [--reps 10] [--e2e]
+
+--sorted: the labels in ascending order (no permutation, no gather: the host's plan is all that stands before the pass);
+--grouped-only: (a) alone; --lib PATH: another build of libbigkrls_hip.so, to compare two builds on one machine.
 """
 import argparse
 import json
@@ -35,9 +38,14 @@ def main():
     ap.add_argument("--max-padded-groups", type=int, default=50)
     ap.add_argument("--e2e", action="store_true")
     ap.add_argument("--e2e-reps", type=int, default=3)
+    ap.add_argument("--sorted", action="store_true")
+    ap.add_argument("--grouped-only", action="store_true")
+    ap.add_argument("--lib", default=None)
     args = ap.parse_args()
-    import bigkrls_amd as bk
     from bigkrls_amd import _lib
+    if args.lib:
+        _lib.LIB_PATH = os.path.abspath(args.lib)
+    import bigkrls_amd as bk
 
     ctx = bk.Context(0)
     n = u = args.n
@@ -68,6 +76,8 @@ def main():
 
     for G in args.groups:
         labels = np.ascontiguousarray(rng.integers(0, G, size=u), dtype=np.int64)
+        if args.sorted:
+            labels = np.sort(labels)
         order = np.argsort(labels, kind="stable")
         off = np.concatenate([[0], np.cumsum(np.bincount(labels, minlength=G))])
         out = ctx.empty(n, G * q)
@@ -77,6 +87,11 @@ def main():
                       W.ptr, q, W.ld, labels.ctypes.data, G, out.ptr, out.ld)
         t_a = timed(grouped)
         got = out.to_numpy()
+        if args.grouped_only:
+            print(json.dumps({"n": n, "u": u, "p": p, "q": q, "G": G, "sorted": args.sorted, "grouped_ms": t_a}), flush=True)
+            del out
+            ctx.release_workspace()
+            continue
 
         Zsort, Wsort = ctx.from_numpy(np.asfortranarray(Zh[order])), ctx.from_numpy(np.asfortranarray(Wh[order]))
         out_b = ctx.empty(n, G * q)
