@@ -606,6 +606,8 @@ int bigkrls_dev_eigen_implicit(bigkrls_ctx* ctx, const double* X, int64_t n, int
                                int64_t n_vals, double* vals, int64_t n_vecs_max, double h_keep_thresh, double* vecs,
                                int64_t ldv, int64_t* h_n_vecs) {
   BK_TRY(check_ctx(ctx));
+  // (refused before the operator is prepared: a refusal launches nothing)
+  BK_REQUIRE(n_vecs_max <= 0 || ldv >= n, "eigen (implicit kernel): leading dimension of vecs too small");
   KernelOp kernel;
   BK_TRY(kernel_op_prepare(ctx, X, n, ldx, p, sigma, &kernel));
   return eigen_implicit(ctx, kernel, n_vals, vals, n_vecs_max, h_keep_thresh, vecs, ldv, h_n_vecs);
@@ -617,6 +619,7 @@ int bigkrls_dev_eigen_auto(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t
   BK_TRY(check_ctx(ctx));
   BK_REQUIRE(h_n_vals && h_n_vecs, "eigen_auto: the counts are required");
   if (A) return eigen_auto(ctx, A, n, lda, n_vals_max, vals, h_keep_thresh, vecs, ldv, h_n_vals, h_n_vecs);
+  BK_REQUIRE(ldv >= n, "eigen (implicit kernel): leading dimension of vecs too small");   // (before anything is launched)
   KernelOp kernel;
   BK_TRY(kernel_op_prepare(ctx, X, n, ldx, p, sigma, &kernel));
   return eigen_implicit(ctx, kernel, n_vals_max, vals, n_vals_max, h_keep_thresh, vecs, ldv, h_n_vecs, true, h_n_vals);

@@ -1001,6 +1001,15 @@ __global__ void gather_cols(int n, int nv, const int* __restrict__ src, const do
   }
 }
 
+// Z[0:n, 0:ncols] = 0 (the columns of a column partition that other parts own): one contiguous memset for a packed Z,
+// n rows per column otherwise -- rows n .. ldz of a column belong to the caller
+static int zero_cols(hipStream_t st, double* Z, int64_t ldz, int64_t n, int64_t ncols) {
+  if (ncols <= 0) return BIGKRLS_OK;
+  if (ldz == n) BK_HIP(hipMemsetAsync(Z, 0, (size_t)ncols * ldz * sizeof(double), st));
+  else BK_HIP(hipMemset2DAsync(Z, (size_t)ldz * sizeof(double), 0, (size_t)n * sizeof(double), (size_t)ncols, st));
+  return BIGKRLS_OK;
+}
+
 // wall-clock of the host between two points, for the BIGKRLS_VERBOSE lines: ms() since the start or the last lap()
 struct Stopwatch {
   std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
@@ -2718,8 +2727,8 @@ struct BlockLanczos : KryArgs {
       // build column blocks of Q diag(w) Q'): one all-gather of the row blocks, n x nv doubles
       if (comm) BK_TRY(comm_gather_rows(comm, vecs + ro, nr, ldv, nv, kop.nb, n, vecs, ldv));
       const int64_t pc0 = nv * part_index / part_count, pc1 = nv * (part_index + 1) / part_count;
-      if (pc0 > 0) BK_HIP(hipMemsetAsync(vecs, 0, (size_t)pc0 * ldv * sizeof(double), st));
-      if (pc1 < nv) BK_HIP(hipMemsetAsync(vecs + pc1 * ldv, 0, (size_t)(nv - pc1) * ldv * sizeof(double), st));
+      BK_TRY(zero_cols(st, vecs, ldv, n, pc0));
+      BK_TRY(zero_cols(st, vecs + pc1 * ldv, ldv, n, nv - pc1));
     }
 #ifdef BK_FAULT_INJECT
     {
@@ -2813,7 +2822,8 @@ int eigen_implicit(bigkrls_ctx* ctx, const KernelOp& kernel, int64_t n_vals, dou
     return BIGKRLS_EINVAL;
   }
   BK_REQUIRE(n_vecs_max >= 0 && n_vecs_max <= n, "eigen (implicit kernel): n_vecs_max out of range");
-  BK_REQUIRE(n_vecs_max == 0 || (vecs && ldv >= n), "eigen (implicit kernel): bad eigenvector buffer");
+  BK_REQUIRE(n_vecs_max == 0 || vecs, "eigen (implicit kernel): bad eigenvector buffer");
+  BK_REQUIRE(n_vecs_max == 0 || ldv >= n, "eigen (implicit kernel): leading dimension of vecs too small");
   if (auto_rank)
     BK_REQUIRE(h_n_vals && keep_thresh > 0.0 && keep_thresh <= 1.0 && n_vecs_max == n_vals,
                "eigen (implicit kernel, auto rank): needs 0 < keep_thresh <= 1 and room for n_vals eigenvectors");
@@ -3357,8 +3367,8 @@ struct DenseEig : EigArgs {
     if (nv == 0 || n_vecs_max <= 0) return BIGKRLS_OK;
     const int pc0 = (int)((int64_t)nv * part_index / part_count);
     const int pc1 = (int)((int64_t)nv * (part_index + 1) / part_count);
-    if (pc0 > 0) BK_HIP(hipMemsetAsync(vecs, 0, (size_t)pc0 * ldv * sizeof(double), st));
-    if (pc1 < nv) BK_HIP(hipMemsetAsync(vecs + (int64_t)pc1 * ldv, 0, (size_t)(nv - pc1) * ldv * sizeof(double), st));
+    BK_TRY(zero_cols(st, vecs, ldv, N, pc0));
+    BK_TRY(zero_cols(st, vecs + (int64_t)pc1 * ldv, ldv, N, nv - pc1));
     double* pvecs = vecs + (int64_t)pc0 * ldv;
     const int pnv = pc1 - pc0;
     if (pnv <= 0) return BIGKRLS_OK;
@@ -3496,7 +3506,9 @@ int eigen(bigkrls_ctx* ctx, const double* A, int64_t n64, int64_t lda, int64_t n
     BK_REQUIRE((A || mode == EIG_RESUME) && vals, "eigen: bad matrix");
     BK_REQUIRE(n_vals > 0 && n_vals <= n64, "eigen: n_vals out of range");
     BK_REQUIRE(n_vecs_max >= 0 && n_vecs_max <= n64, "eigen: n_vecs_max out of range");
-    BK_REQUIRE(n_vecs_max == 0 || (vecs && ldv >= n64), "eigen: bad eigenvector buffer");
+    BK_REQUIRE(n_vecs_max == 0 || vecs, "eigen: bad eigenvector buffer");
+    BK_REQUIRE(mode != EIG_FULL || lda >= n64, "eigen: leading dimension of A too small");   // (A is read by EIG_FULL alone)
+    BK_REQUIRE(n_vecs_max == 0 || ldv >= n64, "eigen: leading dimension of vecs too small");
   }
   if (mode != EIG_FULL) BK_REQUIRE(n64 > 4 * S2_B, "eigen: the distributed dense path needs n > 256");
   DenseEig dense(EigArgs{ctx, A, n64, lda, n_vals, vals, n_vecs_max, keep_thresh, vecs, ldv, h_n_vecs, part_index,
@@ -3516,8 +3528,8 @@ int eigen(bigkrls_ctx* ctx, const double* A, int64_t n64, int64_t lda, int64_t n
 // path as a fixed-rank call does: all n values with keep_thresh, of which the first lastkeeper + 1 are returned.
 int eigen_auto(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t lda, int64_t kcap, double* vals, double keep_thresh,
                double* vecs, int64_t ldv, int64_t* h_n_vals, int64_t* h_n_vecs) {
-  BK_REQUIRE(A && vals && vecs && h_n_vals && h_n_vecs && n > 0 && n < (1ll << 30) && lda >= n && ldv >= n,
-             "eigen (auto rank): bad arguments");
+  BK_REQUIRE(A && vals && vecs && h_n_vals && h_n_vecs && n > 0 && n < (1ll << 30), "eigen (auto rank): bad arguments");
+  BK_REQUIRE(lda >= n && ldv >= n, "eigen (auto rank): leading dimension of A or vecs too small");
   BK_REQUIRE(kcap >= 1 && kcap <= n, "eigen (auto rank): the cap must be between 1 and n");
   BK_REQUIRE(keep_thresh > 0.0 && keep_thresh <= 1.0, "eigen (auto rank): needs 0 < keep_thresh <= 1");
   ctx->corrupt_run = false;

@@ -3277,7 +3277,8 @@ int kernel_loo_moments(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda
 // The centred copy of X and its squared row norms live in slots of their own, so that they survive every other kernel
 // build or contraction of the context until the next kernel_op_prepare.
 int kernel_op_prepare(bigkrls_ctx* ctx, const double* X, int64_t n, int64_t ldx, int64_t p, double sigma, KernelOp* op) {
-  BK_REQUIRE(X && op && n > 0 && p > 0 && ldx >= n && n < (1ll << 31) && p < (1ll << 20), "kernel operator: bad arguments");
+  BK_REQUIRE(X && op && n > 0 && p > 0 && n < (1ll << 31) && p < (1ll << 20), "kernel operator: bad arguments");
+  BK_REQUIRE(ldx >= n, "kernel operator: leading dimension of X too small");
   BK_REQUIRE(sigma > 0.0, "kernel operator: sigma must be > 0");
   void *px = nullptr, *pn = nullptr, *psh = nullptr;
   BK_TRY(ws_get(ctx, SLOT_KOP_X, n * p * (int64_t)sizeof(double), &px));

@@ -336,7 +336,14 @@ int bigkrls_dev_multdiag(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t k
  * vecs (n x n_vecs, ldv) receives the eigenvectors of the n_vecs largest.
  * If h_keep_thresh >= 0, n_vecs is determined on the device side as
  * lastkeeper = #{k : vals[k] >= h_keep_thresh * vals[0]} capped at n_vecs_max,
- * exactly bEigen's rule (R/bigKRLS_Rcpp_functions.R:190); *h_n_vecs returns it. */
+ * exactly bEigen's rule (R/bigKRLS_Rcpp_functions.R:190); *h_n_vecs returns it.
+ *
+ * Leading dimensions, for this entry and for bigkrls_dev_eigen_part, bigkrls_dev_eigen_implicit and
+ * bigkrls_dev_eigen_auto: lda, ldx and ldv are ordinary column-major strides in doubles, each >= n (a shorter one is
+ * BIGKRLS_EINVAL, named in the message, and nothing is launched or written). A, X and vecs may be blocks of larger
+ * matrices: no alignment beyond that of a double (8 bytes) is required, only the n x n (A), n x p (X) block is read, and
+ * nothing outside the n x n_vecs block of vecs is written (n_vecs = *h_n_vecs <= n_vecs_max; in the partition form the
+ * other parts' columns are zeroed over their n rows only). */
 int bigkrls_dev_eigen(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t lda,
                       int64_t n_vals, double* vals,
                       int64_t n_vecs_max, double h_keep_thresh, double* vecs, int64_t ldv,
