@@ -1076,6 +1076,131 @@ def partial_dependence(object: BigKRLS, which=None, grid=20, newdata=None, se: b
             "se.first.difference": sefd, "newdata": nd_init}
 
 
+def _ale_bins(z, edges):
+    """The bin of every reference value z under the edges z_0 < ... < z_B: b(i) = the smallest b >= 1 with z <= z_b (a row
+    equal to z_0 goes to bin 1), 0-based; and the rows per bin."""
+    lab = np.maximum(np.searchsorted(edges, z, side="left"), 1) - 1
+    return lab, np.bincount(lab, minlength=edges.size - 1)
+
+
+def accumulated_effects(object: BigKRLS, which=None, bins=20, newdata=None, se: bool = True, correct_SE: bool = True,
+                        vcov: Optional[str] = None, ctx: Optional[Context] = None) -> dict:
+    """Accumulated local effects (ALE, Apley & Zhu) of the fitted outcome on one predictor at a time, with standard
+    errors: for every column j of `which` (1-based; default: the object's which.derivatives, else all columns) and every
+    bin of x_j, the mean change of the prediction over the reference rows that fall into the bin when x_j moves from
+    the bin's lower to its upper edge ("local"), accumulated over the bins and centred ("ale", at the edges). Unlike
+    partial_dependence() no prediction is taken at a combination of values the data do not contain, which matters with
+    correlated predictors. No counterpart in the reference. The numeric body is ONE call into the C ABI,
+    `bigkrls_accumulated_effects`: the Gaussian kernel factorises over the columns, so all curves are linear in the
+    coefficients and come, with their covariance, from one fused O(u n) pass (`bigkrls_dev_kernel_loo_binsums`) instead of
+    two predict() calls per bin.
+
+    bins: an int B >= 1 -- the edges are the distinct inverted-CDF quantiles of the reference column at k/B, k = 0..B, so
+    every edge is a sample value, no bin is empty and ties merge bins -- or a list of edge arrays aligned with `which`
+    (strictly increasing, covering the reference column, no bin empty). A binary training column has one bin between its
+    two training values (lo, hi): ale = (-d/2, +d/2) with d = partial_dependence()'s "first.difference"; explicit edges
+    for it must be those two values. newdata: the reference rows (u x p); None: the training rows. se / vcov: as in
+    marginal_effects(); correct_SE: as in predict(). Returns a dict: "which", "xlabs", "binaryindicator", "edges",
+    "counts" (rows per bin), "ale", "se.ale", "vcov.ale" (lists over the columns, at the edges; the last two None without
+    a variance), "local", "se.local" (per bin: the differences of "ale" and their standard errors from "vcov.ale"),
+    "first.difference", "se.first.difference" (1 x |J|, NaN for continuous columns) and "newdata"."""
+    Xh, n, p, nd_init, nd, u, isbin, form = _effects_open("accumulated_effects", object, newdata, vcov, se, gated=True,
+                                                         default="null")
+    if which is None:
+        which = object.get("which.derivatives")
+    if which is None:
+        which = list(range(1, p + 1))
+    else:
+        which = [int(i) for i in np.atleast_1d(which)]
+        if not which or not all(1 <= i <= p for i in which):
+            raise ValueError("which.derivatives must index columns of X")
+    explicit = not isinstance(bins, (int, np.integer)) or isinstance(bins, (bool, np.bool_))
+    if explicit:
+        try:
+            bins = [np.asarray(e, dtype=np.float64) for e in bins]
+        except (TypeError, ValueError):
+            bins = None
+        if isinstance(bins, list) and any(e.ndim == 0 for e in bins):
+            bins = None
+        if bins is None or len(bins) != len(which):
+            raise ValueError("bins must be an integer or a list with one array of edges per column of which")
+    elif bins < 1:
+        raise ValueError("bins must be at least 1")
+    ref = Xh if nd is None else nd
+    edges, counts = [], []
+    for idx, i in enumerate(which):
+        j = i - 1
+        z = ref[:, j]
+        lo, hi = Xh[:, j].min(), Xh[:, j].max()
+        if explicit:
+            e = np.ascontiguousarray(np.asarray(bins[idx], dtype=np.float64).ravel())
+            if e.size < 2:
+                raise ValueError(f"the edges of column {i} must hold at least 2 values")
+            if not np.all(np.isfinite(e)):
+                raise ValueError(f"the edges of column {i} contain missing or infinite values")
+            if not np.all(np.diff(e) > 0):
+                raise ValueError(f"the edges of column {i} must be strictly increasing")
+            if isbin[j] and not (e.size == 2 and e[0] == lo and e[1] == hi):
+                raise ValueError(f"column {i} is binary in the training data; its edges must be "
+                                 f"its two training values ({lo:g}, {hi:g})")
+        if isbin[j]:
+            e = np.array([lo, hi])
+        else:
+            if np.unique(z).size < 2:
+                raise ValueError(f"the reference rows hold one distinct value in column {i}: no accumulated effect")
+            if not explicit:
+                e = np.unique(np.quantile(z, np.arange(int(bins) + 1) / int(bins), method="inverted_cdf"))
+        if z.min() < e[0] or z.max() > e[-1]:
+            raise ValueError(f"the edges of column {i} do not cover the reference rows: [{e[0]:g}, {e[-1]:g}] against "
+                             f"[{z.min():g}, {z.max():g}]")
+        _, cnt = _ale_bins(z, e)
+        if np.any(cnt == 0):
+            raise ValueError(f"bin {int(np.argmin(cnt != 0)) + 1} of column {i} holds no reference row")
+        edges.append(e)
+        counts.append(cnt)
+    ctx, Vd, Qd, wv, yv, coeffs, vcov_args, xlabs = _effects_device(object, form, ctx, p)
+    which_arr = np.ascontiguousarray(which, dtype=np.int64)
+    nj = which_arr.size
+    sizes = np.array([e.size for e in edges], dtype=np.int64)
+    off = np.ascontiguousarray(np.concatenate([[0], np.cumsum(sizes)]), dtype=np.int64)
+    cov_off = np.concatenate([[0], np.cumsum(sizes * sizes)])
+    flat = np.ascontiguousarray(np.concatenate(edges))
+    total = int(off[-1])
+    ale = np.empty(total)
+    sev = np.empty(total) if se else None
+    cov = np.empty(int(cov_off[-1])) if se else None
+    neff = -1.0
+    if se and correct_SE and object.get("Neffective") is not None:                # predict(): R/bigKRLS.R:610-611
+        neff = float(object["Neffective"])
+    _call_native("bigkrls_accumulated_effects", ctx.handle, Xh.ctypes.data, n, p, yv.ctypes.data, coeffs.ctypes.data,
+                 float(object["sigma"]), which_arr.ctypes.data, nj, nd.ctypes.data if nd is not None else None, u,
+                 flat.ctypes.data, off.ctypes.data, *vcov_args, neff, ale.ctypes.data,
+                 sev.ctypes.data if se else None, cov.ctypes.data if se else None)
+    cut = lambda v: [v[off[i]:off[i + 1]] for i in range(nj)]
+    ales = cut(ale)
+    covs = None
+    if se:
+        covs = [cov[cov_off[i]:cov_off[i + 1]].reshape(sizes[i], sizes[i], order="F") for i in range(nj)]
+    local = [np.diff(a) for a in ales]
+    selocal = None
+    if se:                                                                        # var(ale_b - ale_{b-1}) from vcov.ale
+        selocal = []
+        for c in covs:
+            d = np.diag(c)
+            selocal.append(np.sqrt(np.maximum(d[1:] + d[:-1] - 2.0 * np.diag(c, 1), 0.0)))
+    bin_sel = isbin[which_arr - 1]
+    fd = np.full((1, nj), np.nan)
+    sefd = np.full((1, nj), np.nan) if se else None
+    for i in range(nj):
+        if bin_sel[i]:
+            fd[0, i] = local[i][0]
+            if se:
+                sefd[0, i] = selocal[i][0]
+    return {"which": which, "xlabs": [xlabs[i - 1] for i in which], "binaryindicator": bin_sel, "edges": edges,
+            "counts": counts, "ale": ales, "se.ale": cut(sev) if se else None, "vcov.ale": covs, "local": local,
+            "se.local": selocal, "first.difference": fd, "se.first.difference": sefd, "newdata": nd_init}
+
+
 def conditional_effects(object: BigKRLS, effect, along, grid=20, newdata=None, se: bool = True,
                         vcov: Optional[str] = None, ctx: Optional[Context] = None) -> dict:
     """Marginal effects along a moderator: how does the effect of x_j change with x_k? For every pair (j, k) of `effect`

@@ -540,6 +540,14 @@ int bigkrls_dev_kernel_loo_colsums(bigkrls_ctx* ctx, const double* A, int64_t u,
   return kernel_loo_colsums(ctx, A, u, lda, B, v, ldb, p, sigma, h_cols, n_cols, out, ldo);
 }
 
+int bigkrls_dev_kernel_loo_binsums(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B,
+                                   int64_t v, int64_t ldb, int64_t p, double sigma, const int64_t* h_cols,
+                                   int64_t n_cols, const int64_t* h_labels, const int64_t* h_nbins, double* out,
+                                   int64_t ldo) {
+  BK_TRY(check_ctx(ctx));
+  return kernel_loo_binsums(ctx, A, u, lda, B, v, ldb, p, sigma, h_cols, n_cols, h_labels, h_nbins, out, ldo);
+}
+
 int bigkrls_dev_kernel_loo_moments(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B,
                                    int64_t v, int64_t ldb, int64_t p, double sigma, const int64_t* h_entries,
                                    int64_t n_entries, double* out, int64_t ldo) {

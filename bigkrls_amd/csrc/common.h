@@ -66,7 +66,7 @@ struct bigkrls_ctx {
   bool side_is_main = false;   // BIGKRLS_NO_SIDE (diagnostics): side_stream is the main stream itself
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_pq = nullptr;
   // workspace slots: slot i is grown on demand and reused across calls
-  static constexpr int kSlots = 62;
+  static constexpr int kSlots = 64;
   void* ws[kSlots] = {nullptr};
   int64_t ws_bytes[kSlots] = {0};
   // pinned host scratch for small scalar read-backs
@@ -222,6 +222,8 @@ enum Slot {
   SLOT_CS_INDEX = 59,      // ... the sort permutation, the rows' pieces, the pieces' destinations, the multi-piece clusters
   SLOT_KCG_PART = 60,      // kernel_contract_grouped: partial sums of the groups that are cut into several segments
   SLOT_KCG_GATHER = 61,    // ... the segment table, the sort permutation and the copies of A's rows, their norms and W in group order
+  SLOT_KLB_INDEX = 62,     // kernel_loo_binsums: every selected column's row index list, the launches' segment tables and multi triples
+  SLOT_KLB_PART = 63,      // ... partial sums of the bins that are cut into several segments
 };
 
 // BIGKRLS_VERBOSE: progress and timing lines on stderr (read at every call: it may be switched while the process runs)
@@ -343,6 +345,13 @@ int kernel_contract_grouped_centred(bigkrls_ctx* ctx, const double* S, int64_t v
 int kernel_loo_colsums(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
                        int64_t ldb, int64_t p, double sigma, const int64_t* h_cols, int64_t n_cols, double* out,
                        int64_t ldo);
+
+// out (v x sum_jj h_nbins[jj], ldo): kernel_loo_colsums' sums per bin of the left-out column: h_labels (host, u x n_cols
+// column-major) holds the bin of row i under selected column jj, in [0, h_nbins[jj]); the bins of column jj are
+// consecutive columns of out, the columns in the caller's order. One fused pass; an empty bin gives zeros; deterministic.
+int kernel_loo_binsums(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
+                       int64_t ldb, int64_t p, double sigma, const int64_t* h_cols, int64_t n_cols,
+                       const int64_t* h_labels, const int64_t* h_nbins, double* out, int64_t ldo);
 
 // out (v x n_entries, ldo): out[l, e] = sum_i wgt exp(-max(d2(i,l) - dc^2 - [kind = 2] dj^2, 0) / sigma) for the entries
 // (kind, c, j) of h_entries (host, 3 x n_entries column-major, 0-based columns): kind 0: wgt = 1 (kernel_loo_colsums'

@@ -2757,6 +2757,30 @@ struct KcgDevice {
   double *Lg, *ng, *Wg;      // the loop rows, their norms and W in group order (u x p, u, u x q; ld u): likewise
   double* part;
 };
+// The pinned buffer the tables of the grouped passes (kernel_contract_grouped, kernel_loo_binsums) are uploaded from, at
+// least `bytes` long, with its event: the previous upload has left the buffer before the caller overwrites it. A buffer
+// of these passes' own, guarded by an event behind the upload: waiting for the STREAM here (the context's shared pinned
+// buffer would need it) leaves the device idle between the centring kernels and the pass, 4 % of the whole call at
+// u = v = 20 000. kcg_stage_send copies the buffer's bytes [from, to) to the same offsets of dbase and records the event.
+static int kcg_stage(bigkrls_ctx* ctx, int64_t bytes, char** hb) {
+  if (ctx->ev_kcg) BK_HIP(hipEventSynchronize(ctx->ev_kcg));   // (the previous call's upload has left the buffer)
+  else BK_HIP(hipEventCreateWithFlags(&ctx->ev_kcg, hipEventDisableTiming));
+  if (ctx->h_kcg_bytes < bytes) {
+    if (ctx->h_kcg) BK_HIP(hipHostFree(ctx->h_kcg));
+    ctx->h_kcg = nullptr;
+    ctx->h_kcg_bytes = 0;
+    BK_HIP(hipHostMalloc((void**)&ctx->h_kcg, (size_t)bytes + 4096, hipHostMallocDefault));
+    ctx->h_kcg_bytes = bytes + 4096;
+  }
+  *hb = ctx->h_kcg;
+  return BIGKRLS_OK;
+}
+static int kcg_stage_send(bigkrls_ctx* ctx, char* dbase, int64_t from, int64_t to) {
+  BK_HIP(hipMemcpyAsync(dbase + from, ctx->h_kcg + from, (size_t)(to - from), hipMemcpyHostToDevice, ctx->stream));
+  BK_HIP(hipEventRecord(ctx->ev_kcg, ctx->stream));
+  return BIGKRLS_OK;
+}
+
 // Carves the buffers and sends the table and, if there is one, the permutation (perm: group_order's).
 static int kcg_upload(bigkrls_ctx* ctx, const GroupedPlan& pl, const std::vector<int32_t>& perm, int64_t u, int64_t v,
                       int64_t p, int64_t q, KcgDevice* d) {
@@ -2788,28 +2812,15 @@ static int kcg_upload(bigkrls_ctx* ctx, const GroupedPlan& pl, const std::vector
     BK_CHECK_LAUNCH();
   }
   if (inline_table && identity) return BIGKRLS_OK;
-  // a pinned buffer of this function's own, guarded by an event behind the upload: waiting for the STREAM here (the
-  // context's shared pinned buffer would need it) leaves the device idle between the centring kernels and the pass,
-  // 4 % of the whole call at u = v = 20 000
-  if (ctx->ev_kcg) BK_HIP(hipEventSynchronize(ctx->ev_kcg));   // (the previous call's upload has left the buffer)
-  else BK_HIP(hipEventCreateWithFlags(&ctx->ev_kcg, hipEventDisableTiming));
-  if (ctx->h_kcg_bytes < b_idx) {
-    if (ctx->h_kcg) BK_HIP(hipHostFree(ctx->h_kcg));
-    ctx->h_kcg = nullptr;
-    ctx->h_kcg_bytes = 0;
-    BK_HIP(hipHostMalloc((void**)&ctx->h_kcg, (size_t)b_idx + 4096, hipHostMallocDefault));
-    ctx->h_kcg_bytes = b_idx + 4096;
-  }
-  char* hb = ctx->h_kcg;
+  char* hb = nullptr;
+  BK_TRY(kcg_stage(ctx, b_idx, &hb));
   const int64_t from = inline_table ? b_seg + b_mu : 0;      // (the table is already there: the permutation alone)
   if (!inline_table) {
     std::memcpy(hb, pl.segs.data(), (size_t)b_seg);
     if (nmulti > 0) std::memcpy(hb + b_seg, pl.multi.data(), (size_t)nmulti * 12);
   }
   if (!identity) std::memcpy(hb + b_seg + b_mu, perm.data(), (size_t)u * 4);
-  BK_HIP(hipMemcpyAsync(dbase + from, hb + from, (size_t)(b_idx - from), hipMemcpyHostToDevice, st));
-  BK_HIP(hipEventRecord(ctx->ev_kcg, st));
-  return BIGKRLS_OK;
+  return kcg_stage_send(ctx, dbase, from, b_idx);
 }
 
 // For operands that are already centred and come with their squared row norms (kernel_contract_centred's contract): S the
@@ -3269,6 +3280,187 @@ int kernel_loo_moments(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda
       BK_CHECK_LAUNCH();
     }
     BK_TRY(prof_end(ctx, "kernel_loo_moments"));
+  }
+  return BIGKRLS_OK;
+}
+
+// ---------------------------------------------------------------------------
+// fused binned leave-one-column-out column sums (accumulated local effects, csrc/ale.hip)
+// ---------------------------------------------------------------------------
+// out[l, bin0(jj) + b] = sum over the rows i of A with label[i, jj] = b of exp(-(||A_i - B_l||^2 - (A[i,c] - B[l,c])^2) / sigma),
+// c = cols[jj]: kernel_loo_colsums' quantity summed per bin of the left-out column, and the grouping differs per
+// column. The frame (kt_*) with 64 stationary rows per wave as kernel_loo_colsums_kernel; the task is (stationary
+// tile, segment) and a segment is a run of ONE selected column's loop rows in that column's bin order
+// (plan_loo_binsums, csrc/ktplan.h), so a wave handles one column (chunk width 1) and the Gram tile is rebuilt per
+// column. The loop rows are not gathered: the operands are column-major, so row idx[r] of column k is L[idx[r] + k ldl],
+// and the wave reads its 16 loop rows of a tile through the column's int32 index list -- p gathered copies of A would
+// cost u p^2 doubles. As in the grouped contraction the loop tiles start at l_begin (not at a multiple of 16) and are
+// masked by l < l_end; a segment that is a whole bin stores into out, the segments of a cut bin into their slots of
+// `part` (each NS long), added in segment order by contract_grouped_reduce_kernel with Q = 1, which also zeroes the
+// empty bins: no atomics, two calls are bitwise identical.
+template <int KS>
+__global__ __launch_bounds__(NT, 2) void kernel_loo_binsums_kernel(
+    const double* __restrict__ S, int64_t lds, int NS, const double* __restrict__ L, int64_t ldl, int NL, int P,
+    const double* __restrict__ nrm_s, const double* __restrict__ nrm_l, double neg_inv_sigma, LooCols cols,
+    const int* __restrict__ idx, const KcgSeg* __restrict__ segs, double* __restrict__ out, int64_t ldo,
+    double* __restrict__ part, int stiles, int64_t ntasks) {
+  __shared__ double etab[32];
+  kt_exp_table(etab);
+  KtTask k;
+  if (!kt_task(k, stiles, 1, ntasks)) return;
+  const KcgSeg sg = segs[k.part];
+  const int s0 = k.st * 16 * KL_MS;
+  const int l_end = sg.l_end, l_last = sg.l_end - 1;
+  const int col = cols.c[sg.l_begin / NL];   // (positions in idx: the launch's column jl owns [jl NL, (jl + 1) NL))
+  const int64_t coff = (int64_t)col * ldl;
+  const int lane = threadIdx.x & 63, lm = lane & 15, lk = lane >> 4;
+
+  int srow[KL_MS];
+  double ns[KL_MS], sf[KL_MS][KS > 0 ? KS : 1];
+  kt_stationary<KL_MS, KS>(srow, ns, sf, S, lds, NS, nrm_s, P, s0);
+  const int ms = KL_MS, ks = KS > 0 ? KS : 1;   // kt_gram's trip counts (by reference: see there)
+  double sc[KL_MS], acc[KL_MS][1];
+#pragma unroll
+  for (int m = 0; m < KL_MS; ++m) {
+    sc[m] = S[srow[m] + (int64_t)col * lds];
+    acc[m][0] = 0.0;
+  }
+
+  for (int l0 = sg.l_begin; l0 < l_end; l0 += 16) {
+    const int lrow = idx[min(l0 + lm, l_last)];   // this lane's row of the L operand (clamped inside the segment)
+    double nl[4], mk[4], lv[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int l = l0 + lk + 4 * r;              // this lane's loop row in accumulator register r
+      const int li = idx[min(l, l_last)];
+      nl[r] = nrm_l[li];
+      lv[r] = L[li + coff];
+      mk[r] = l < l_end ? 1.0 : 0.0;
+    }
+    d4 g[KL_MS];
+    kt_gram<KL_MS, KS>(g, srow, sf, S, lds, L, ldl, lrow, P, ms, ks);
+#pragma unroll
+    for (int m = 0; m < KL_MS; ++m) {
+      double tsum = 0.0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const double dj = lv[r] - sc[m];
+        const double x = fmax(fma(-dj, dj, kt_dist2(g[m][r], ns[m], nl[r])), 0.0);
+        tsum = fma(exp_nonpos_tab(x * neg_inv_sigma, etab), mk[r], tsum);
+      }
+      acc[m][0] += tsum;
+    }
+  }
+  double* dst = sg.slot < 0 ? out + (int64_t)sg.group * ldo : part + (int64_t)sg.slot * NS;
+  kt_store_lane_sums<KL_MS, 1>(acc, dst, 0, s0, 0, 1, NS);
+}
+
+// p = 1: out[s, blockIdx.y] = counts.v[blockIdx.y], up to KLB_FILL bins per launch (the counts as a kernel argument)
+constexpr int KLB_FILL = 256;
+struct BinCounts {
+  double v[KLB_FILL];
+};
+__global__ void loo_binsums_fill_kernel(int NS, BinCounts counts, double* __restrict__ out, int64_t ldo) {
+  const double c = counts.v[blockIdx.y];
+  double* o = out + (int64_t)blockIdx.y * ldo;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < NS; i += gridDim.x * blockDim.x) o[i] = c;
+}
+
+int kernel_loo_binsums(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B, int64_t v,
+                       int64_t ldb, int64_t p, double sigma, const int64_t* h_cols, int64_t n_cols,
+                       const int64_t* h_labels, const int64_t* h_nbins, double* out, int64_t ldo) {
+  BK_REQUIRE(u > 0 && v > 0 && p > 0, "kernel_loo_binsums: bad dimensions");
+  BK_REQUIRE(u < (1ll << 31) && v < (1ll << 31) && p < (1ll << 20), "kernel_loo_binsums: too large");
+  BK_REQUIRE(sigma > 0.0, "kernel_loo_binsums: sigma must be > 0");
+  BK_REQUIRE(A && B && h_cols && h_labels && h_nbins && out, "kernel_loo_binsums: null pointer");
+  BK_REQUIRE(lda >= u && ldb >= v, "kernel_loo_binsums: leading dimension of A or B too small");
+  BK_REQUIRE(ldo >= v, "kernel_loo_binsums: leading dimension of out too small");
+  BK_REQUIRE(n_cols >= 1 && n_cols < (1ll << 20), "kernel_loo_binsums: n_cols must be at least 1 (and below 2^20)");
+  int64_t nbt = 0;
+  for (int64_t j = 0; j < n_cols; ++j) {
+    BK_REQUIRE(h_cols[j] >= 0 && h_cols[j] < p, "kernel_loo_binsums: column index " + std::to_string(h_cols[j]) +
+                                                    " outside [0, " + std::to_string(p) + ")");
+    BK_REQUIRE(h_nbins[j] >= 1 && h_nbins[j] < (1ll << 31), "kernel_loo_binsums: selected column " + std::to_string(j + 1) +
+                                                                " must have at least 1 bin (and fewer than 2^31)");
+    nbt += h_nbins[j];
+  }
+  BK_REQUIRE(nbt < (1ll << 31) && u * n_cols < (1ll << 40), "kernel_loo_binsums: too many bins or labels");
+  hipStream_t st = ctx->stream;
+  CentredOperands co{};   // both operands moved by the column means of ALL of A, not per bin (see centre_operands)
+  if (p > 1) BK_TRY(centre_operands(ctx, A, u, lda, B, v, ldb, p, &co));
+
+  using KbFn = void (*)(const double*, int64_t, int, const double*, int64_t, int, int, const double*, const double*,
+                        double, LooCols, const int*, const KcgSeg*, double*, int64_t, double*, int, int64_t);
+  const KbFn fn = with_ks(ks_of(p), [](auto ks) -> KbFn { return kernel_loo_binsums_kernel<decltype(ks)::value>; });
+  int64_t slots = 0;
+  BK_TRY(wave_slots(ctx, (const void*)fn, &slots));
+  const int64_t stiles = (v + 16 * KL_MS - 1) / (16 * KL_MS);
+  // every column's order, the segments and the launches, on the host while the device centres the operands; the slots
+  // of the cut bins hold at most 64 MB
+  const BinPlan pl = plan_loo_binsums(h_labels, u, n_cols, h_nbins, stiles, slots, (64ll << 20) / (v * (int64_t)sizeof(double)));
+  BK_REQUIRE(pl.bad_row < 0, "kernel_loo_binsums: the label of row " + std::to_string(pl.bad_row + 1) + " of selected column " +
+                                 std::to_string(pl.bad_col + 1) + " is outside [0, " +
+                                 std::to_string(pl.bad_col >= 0 ? h_nbins[pl.bad_col] : 0) + ")");
+  if (p == 1) {   // nothing is left of the distance: every term is exp(0), the sums are the bins' counts
+    const int blocks = (int)std::min<int64_t>((v + 255) / 256, 1024);
+    for (int64_t b0 = 0; b0 < nbt; b0 += KLB_FILL) {
+      BinCounts bc;
+      const int64_t cnt = std::min<int64_t>(KLB_FILL, nbt - b0);
+      for (int64_t b = 0; b < cnt; ++b) bc.v[b] = (double)pl.counts[(size_t)(b0 + b)];
+      hipLaunchKernelGGL(loo_binsums_fill_kernel, dim3(blocks, (unsigned)cnt), dim3(256), 0, st, (int)v, bc, out + b0 * ldo, ldo);
+      BK_CHECK_LAUNCH();
+    }
+    return BIGKRLS_OK;
+  }
+
+  // ---- one upload for all launches: every column's index list, then per launch its segments and multi triples ----
+  const int64_t b_idx = (u * n_cols * 4 + 15) / 16 * 16;
+  std::vector<int64_t> seg_at, multi_at;
+  int64_t bytes = b_idx, max_slots = 1;
+  for (const BinLaunch& ln : pl.launches) {
+    BK_REQUIRE((stiles * (int64_t)ln.plan.segs.size() + 3) / 4 < (1ll << 31), "kernel_loo_binsums: too many tiles");
+    seg_at.push_back(bytes);
+    bytes += (int64_t)ln.plan.segs.size() * (int64_t)sizeof(KcgSeg);
+    multi_at.push_back(bytes);
+    bytes += ((int64_t)ln.plan.multi.size() * 4 + 15) / 16 * 16;
+    max_slots = std::max(max_slots, ln.plan.nslots);
+  }
+  void *pg = nullptr, *ppart = nullptr;
+  BK_TRY(ws_get(ctx, SLOT_KLB_INDEX, bytes + 64, &pg));
+  BK_TRY(ws_get(ctx, SLOT_KLB_PART, max_slots * v * (int64_t)sizeof(double), &ppart));
+  char* dbase = (char*)pg;
+  char* hb = nullptr;   // (kcg_upload's pinned buffer and event: the stream is never waited for)
+  BK_TRY(kcg_stage(ctx, bytes, &hb));
+  std::memcpy(hb, pl.idx.data(), (size_t)(u * n_cols) * 4);
+  for (size_t i = 0; i < pl.launches.size(); ++i) {
+    const GroupedPlan& gp = pl.launches[i].plan;
+    std::memcpy(hb + seg_at[i], gp.segs.data(), gp.segs.size() * sizeof(KcgSeg));
+    if (!gp.multi.empty()) std::memcpy(hb + multi_at[i], gp.multi.data(), gp.multi.size() * 4);
+  }
+  BK_TRY(kcg_stage_send(ctx, dbase, 0, bytes));
+
+  // the rows of B are stationary, the rows of A the loop (kernel_contract's trans = 1)
+  for (size_t i = 0; i < pl.launches.size(); ++i) {
+    const BinLaunch& ln = pl.launches[i];
+    LooCols lc;
+    for (int64_t j = 0; j < KL_GROUP; ++j) lc.c[j] = (int)h_cols[ln.col0 + std::min(j, ln.ncols - 1)];
+    const int64_t nseg = (int64_t)ln.plan.segs.size(), nmulti = (int64_t)ln.plan.multi.size() / 3;
+    const int64_t ntasks = stiles * nseg;
+    double* o = out + ln.bin0 * ldo;
+    BK_TRY(prof_begin(ctx, "kernel_loo_binsums", (double)u * (double)v * (double)ln.ncols));
+    if (ntasks > 0) {
+      hipLaunchKernelGGL(fn, dim3((unsigned)((ntasks + 3) / 4)), dim3(NT), 0, st, co.B, co.ldb, (int)v, co.A, co.lda, (int)u,
+                         (int)p, co.nb, co.na, -1.0 / sigma, lc, (const int*)dbase + ln.col0 * u,
+                         (const KcgSeg*)(dbase + seg_at[i]), o, ldo, (double*)ppart, (int)stiles, ntasks);
+      BK_CHECK_LAUNCH();
+    }
+    if (nmulti > 0) {
+      const dim3 grid((unsigned)std::min<int64_t>((v + 255) / 256, 1024), (unsigned)std::min<int64_t>(nmulti, 1024));
+      hipLaunchKernelGGL(contract_grouped_reduce_kernel, grid, dim3(256), 0, st, (int)v, 1, (int)nmulti,
+                         (const int*)(dbase + multi_at[i]), (const double*)ppart, o, ldo);
+      BK_CHECK_LAUNCH();
+    }
+    BK_TRY(prof_end(ctx, "kernel_loo_binsums"));
   }
   return BIGKRLS_OK;
 }

@@ -10,6 +10,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 namespace bk {
@@ -240,6 +241,76 @@ inline LooPlan plan_loo_moments(const int64_t* entries, int64_t n_entries, int64
     }
     for (int64_t i = ln.nchunks; i <= KL_GROUP; ++i) le.begin[i] = (int)nc;
     pl.launches.push_back(ln);
+  }
+  return pl;
+}
+
+// ---- the launches of the binned leave-out sums (kernel_loo_binsums) ------------------------------------------------
+// labels: u x n_cols column-major, the bin of every loop row under selected column jj, in [0, nbins[jj]). Every column
+// has an order of its own: idx (u x n_cols, ld u) holds group_order's stable order of column jj in its column (always
+// written out, the identity included: the kernel reads its loop rows through it), counts the rows per bin, all columns'
+// bins one after the other (bin_off[jj]: the first of column jj -- the caller's output columns).
+// A launch takes a run of selected columns: at most KL_GROUP (their numbers travel as a kernel argument), at most
+// KLB_BINS bins (a column with more goes alone) and fewer than 2^31 index entries, so that a position in the launch's
+// part of idx is an int. Its bins are the groups of ONE plan_grouped_segments call -- the slots are shared by all of
+// the launch's columns, so the split is chosen for all of them together -- over the offsets jl u + off_jl[b] (jl the
+// column's place in the launch): a segment's l_begin / l_end are positions in the launch's part of idx, l_begin / u is
+// its column's place, and its group is the output column counted from the launch's first bin.
+// bad_row >= 0: the first label outside its range, of selected column bad_col (nothing else is filled in then).
+constexpr int64_t KLB_BINS = 4096;
+struct BinLaunch {
+  int64_t col0, ncols;   // the selected columns [col0, col0 + ncols)
+  int64_t bin0, nb;      // their bins: the output columns [bin0, bin0 + nb)
+  GroupedPlan plan;
+};
+struct BinPlan {
+  int64_t bad_row = -1, bad_col = -1;
+  std::vector<int32_t> idx;
+  std::vector<int64_t> counts, bin_off;
+  std::vector<BinLaunch> launches;
+};
+inline BinPlan plan_loo_binsums(const int64_t* labels, int64_t u, int64_t n_cols, const int64_t* nbins, int64_t base,
+                                int64_t slots, int64_t slot_cap) {
+  BinPlan pl;
+  pl.bin_off.assign((size_t)n_cols + 1, 0);
+  for (int64_t jj = 0; jj < n_cols; ++jj) pl.bin_off[(size_t)jj + 1] = pl.bin_off[(size_t)jj] + nbins[jj];
+  pl.idx.resize((size_t)(u * n_cols));
+  pl.counts.resize((size_t)pl.bin_off[(size_t)n_cols]);
+  for (int64_t jj = 0; jj < n_cols; ++jj) {
+    const GroupOrder go = group_order(labels + jj * u, u, nbins[jj]);
+    if (go.bad >= 0) {
+      pl.bad_row = go.bad;
+      pl.bad_col = jj;
+      return pl;
+    }
+    int32_t* ix = pl.idx.data() + jj * u;
+    for (int64_t i = 0; i < u; ++i) ix[i] = go.perm.empty() ? (int32_t)i : go.perm[(size_t)i];
+    for (int64_t b = 0; b < nbins[jj]; ++b)
+      pl.counts[(size_t)(pl.bin_off[(size_t)jj] + b)] = go.off[(size_t)b + 1] - go.off[(size_t)b];
+  }
+  for (int64_t c0 = 0; c0 < n_cols;) {
+    int64_t c1 = c0 + 1;
+    while (c1 < n_cols && c1 - c0 < KL_GROUP && pl.bin_off[(size_t)c1 + 1] - pl.bin_off[(size_t)c0] <= KLB_BINS &&
+           (c1 - c0 + 1) * u < (1ll << 31))
+      ++c1;
+    BinLaunch ln;
+    ln.col0 = c0;
+    ln.ncols = c1 - c0;
+    ln.bin0 = pl.bin_off[(size_t)c0];
+    ln.nb = pl.bin_off[(size_t)c1] - ln.bin0;
+    std::vector<int64_t> off((size_t)ln.nb + 1);
+    int64_t g = 0;
+    for (int64_t jj = c0; jj < c1; ++jj) {
+      int64_t at = (jj - c0) * u;
+      for (int64_t b = 0; b < nbins[jj]; ++b) {
+        off[(size_t)g++] = at;
+        at += pl.counts[(size_t)(pl.bin_off[(size_t)jj] + b)];
+      }
+    }
+    off[(size_t)ln.nb] = ln.ncols * u;
+    ln.plan = plan_grouped_segments(off.data(), ln.nb, base, slots, slot_cap);
+    pl.launches.push_back(std::move(ln));
+    c0 = c1;
   }
   return pl;
 }

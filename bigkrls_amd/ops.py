@@ -112,6 +112,31 @@ def bKernelLooColsums(A: DeviceMatrix, B: DeviceMatrix, sigma: float, cols) -> D
     return out
 
 
+def bKernelLooBinsums(A: DeviceMatrix, B: DeviceMatrix, sigma: float, cols, labels, nbins) -> DeviceMatrix:
+    """out (nrow(B) x sum(nbins)): bKernelLooColsums' sums per bin of the left-out column. labels (nrow(A) x len(cols)):
+    labels[i, jj] in [0, nbins[jj]) is the bin of row i of A under selected column cols[jj] (0-based) -- every column
+    groups the rows its own way; the bins of column jj are consecutive columns of out, the columns in the caller's
+    order. All columns and bins in one fused pass (bigkrls_dev_kernel_loo_binsums); an empty bin gives zeros. No
+    counterpart in the reference."""
+    ctx = A.ctx
+    if A.ncol != B.ncol:
+        raise ValueError("bKernelLooBinsums: column counts of A and B differ")
+    h_cols = np.ascontiguousarray(cols, dtype=np.int64).ravel()
+    h_nbins = np.ascontiguousarray(nbins, dtype=np.int64).ravel()
+    if h_nbins.size != h_cols.size:
+        raise ValueError("bKernelLooBinsums: nbins must have one entry per selected column")
+    lab = np.asarray(labels, dtype=np.int64)
+    if lab.size != A.nrow * h_cols.size or (lab.ndim == 2 and lab.shape != (A.nrow, h_cols.size)):
+        raise ValueError(f"bKernelLooBinsums: labels must be {A.nrow} x {h_cols.size}")
+    lab = np.ascontiguousarray(lab.reshape(A.nrow, h_cols.size).T)         # column-major u x n_cols
+    out = ctx.empty(B.nrow, max(int(h_nbins.sum()), 1))
+    _lib.call("bigkrls_dev_kernel_loo_binsums", ctx.handle, A.ptr, A.nrow, A.ld, B.ptr, B.nrow, B.ld, A.ncol,
+              float(sigma), h_cols.ctypes.data if h_cols.size else np.zeros(1, dtype=np.int64).ctypes.data,
+              int(h_cols.size), lab.ctypes.data if lab.size else np.zeros(1, dtype=np.int64).ctypes.data,
+              h_nbins.ctypes.data if h_nbins.size else np.zeros(1, dtype=np.int64).ctypes.data, out.ptr, out.ld)
+    return out
+
+
 def bKernelLooMoments(A: DeviceMatrix, B: DeviceMatrix, sigma: float, entries) -> DeviceMatrix:
     """out (nrow(B) x len(entries)) for entries (kind, c, j) with 0-based columns: out[l, e] = sum_i wgt
     exp(-max(d2(i,l) - dc^2 - [kind = 2] dj^2, 0) / sigma) with dc = A[i,c] - B[l,c], dj = A[i,j] - B[l,j]; kind 0: wgt = 1

@@ -102,7 +102,8 @@ int bigkrls_ctx_release_workspace(bigkrls_ctx* ctx);
  * lower triangle streamed), "solveforc_probe", "deriv_rows", "yhat_gemv" (algorithmic
  * bytes: 8 N K per probe, 8 N^2, 8 N^2), "vcov_syrk" (N (N + 1) K flops per matrix),
  * "kernel_loo_colsums" (u v n_cols exponentials), "kernel_loo_moments" (u v E exponentials, E per
- * row pair: one per chunk with a kind-0 or kind-1 entry plus one per kind-2 entry). */
+ * row pair: one per chunk with a kind-0 or kind-1 entry plus one per kind-2 entry),
+ * "kernel_loo_binsums" (u v n_cols exponentials). */
 int bigkrls_ctx_set_profile(bigkrls_ctx* ctx, int enable);
 int bigkrls_ctx_get_profile(bigkrls_ctx* ctx, const char* name, double* total_ms,
                             double* total_work, int64_t* launches);
@@ -241,6 +242,24 @@ int bigkrls_dev_kernel_contract_grouped(bigkrls_ctx* ctx, const double* A, int64
 int bigkrls_dev_kernel_loo_colsums(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B,
                                    int64_t v, int64_t ldb, int64_t p, double sigma, const int64_t* h_cols,
                                    int64_t n_cols, double* out, int64_t ldo);
+
+/* Fused binned leave-one-column-out column sums: bigkrls_dev_kernel_loo_colsums' sums per bin of the left-out column.
+ * h_labels (host, u x n_cols column-major) holds the bin of row i of A under selected column jj, an integer in
+ * [0, h_nbins[jj]) -- every selected column groups the rows its own way, and a column may be selected more than once
+ * with other labels. out (v x sum_jj h_nbins[jj], ldo >= v): the bins of column jj are consecutive columns, the
+ * columns in the caller's order,
+ *   out[l, off(jj) + b] = sum over i with h_labels[i, jj] = b of exp(-(||A_i - B_l||^2 - (A[i,c] - B[l,c])^2) / sigma),
+ * c = h_cols[jj] (host, 0-based). One pass for all columns and bins: the rows of A are read in every column's bin order
+ * through an index list (no gathered copies), long bins are cut into segments whose sums are added in a fixed order; an
+ * empty bin gives zeros; at p = 1 the sums are exactly the bins' counts. Both operands are centred once, by the column
+ * means of all of A. Extra device memory O((u + v) p + u n_cols + v sum nbins), never O(u v); no atomics; deterministic:
+ * two calls give bitwise identical results. A column index outside [0, p), n_cols < 1, a column with fewer than 1 bin,
+ * or a label outside its range (naming the row and the selected column) is BIGKRLS_EINVAL. Profile name
+ * "kernel_loo_binsums". */
+int bigkrls_dev_kernel_loo_binsums(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, const double* B,
+                                   int64_t v, int64_t ldb, int64_t p, double sigma, const int64_t* h_cols,
+                                   int64_t n_cols, const int64_t* h_labels, const int64_t* h_nbins, double* out,
+                                   int64_t ldo);
 
 /* Fused leave-out moments: out (v x n_entries, ldo >= v). h_entries (host) is 3 x n_entries column-major, entry e =
  * (kind, c, j) with 0-based columns, and with dc = A[i,c] - B[l,c], dj = A[i,j] - B[l,j], d2 = ||A_i - B_l||^2:
@@ -754,6 +773,28 @@ int bigkrls_partial_dependence(bigkrls_ctx* ctx, const double* h_X, int64_t n, i
                                const double* h_newdata, int64_t u, const double* h_grid, const int64_t* h_grid_off,
                                const double* d_vcov_c, const double* d_Q, int64_t ldq, int64_t k, const double* h_w,
                                double neffective, double* h_pd, double* h_se, double* h_cov);
+
+/* Accumulated local effects (Apley & Zhu): the ALE curve of the fitted outcome on one predictor at a time, with its
+ * covariance over the bin edges (no counterpart in the reference). Arguments as bigkrls_partial_dependence, with h_grid
+ * holding the raw bin EDGES z_0 < z_1 < ... < z_B of every selected column (column i's at h_grid_off[i] ..
+ * h_grid_off[i + 1], G_i = B_i + 1 >= 2 values). Reference row i falls into bin b(i) = the smallest b >= 1 with
+ * Z[i,j] <= z_b (a row equal to z_0 goes to bin 1), n_b rows per bin. In standardised units, with
+ * M_j = bigkrls_dev_kernel_loo_binsums(Zs, Xs) (ONE fused O(u n) pass for all columns and bins) and
+ * phi_j(v, l) = exp(-(vs - Xs[l,j])^2 / sigma):
+ *   D_j[b,l]  = M_j[l,b] (phi_j(z_b, l) - phi_j(z_{b-1}, l)) / n_b          the local effect of bin b is sd(y) D_j[b,:] c
+ *   g(z_k)    = sum_{b <= k} local_b, g(z_0) = 0
+ *   ale_j(z_k) = g(z_k) - (1/u) sum_b n_b (g(z_{b-1}) + g(z_b)) / 2          (ALEPlot's centring)
+ * so ale_j = sd(y) A_j c with A_j (G_j x n) written by one elementwise kernel, and cov_j = f A_j vcov.est.c A_j' from
+ * either form of vcov.est.c, f bigkrls_predict's factor for neffective > 0:
+ *   h_ale = the curve at the edges (T = h_grid_off[n_which] values, original units of y, centred: no mean(y) is added),
+ *   h_se  = its standard errors (T values; may be NULL),   h_cov = the G_i x G_i blocks (may be NULL).
+ * BIGKRLS_EINVAL naming the column (and bin): fewer than 2 edges, edges that are not finite or not strictly increasing, a
+ * reference value outside [z_0, z_B], an empty bin, more than the cap 8 G_i n <= 2^30 bytes allows. */
+int bigkrls_accumulated_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                                const double* h_coeffs, double sigma, const int64_t* h_which, int64_t n_which,
+                                const double* h_newdata, int64_t u, const double* h_edges, const int64_t* h_grid_off,
+                                const double* d_vcov_c, const double* d_Q, int64_t ldq, int64_t k, const double* h_w,
+                                double neffective, double* h_ale, double* h_se, double* h_cov);
 
 /* Conditional effects: the marginal effect of x_j along a moderator x_k, with its covariance over the grid (no
  * counterpart in the reference). h_pairs is 2 x m column-major, 1-based: pair i = (effect j, moderator k). For every pair
