@@ -24,6 +24,7 @@
 #include "common.h"
 #include "s1sched.h"
 #include "dcplan.h"
+#include "s2plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -3000,13 +3001,14 @@ struct DenseEig : EigArgs {
   double *taus1 = nullptr, *AB = nullptr, *VV = nullptr, *TT = nullptr;
   int64_t* d_soff = nullptr;
   // ---- what is precomputed for the back-transforms beside the divide & conquer (fork_lookahead)
-  std::vector<int64_t> bt2_toff;      // T-factor slot offsets of the stage-2 back-transform's task groups
-  double* bt2_T = nullptr;
+  S2Plan plan;                        // the host plan of the back half (csrc/s2plan.h), built once, in carve_workspace
+  bool bg = false;                    // BIGKRLS_BG
+  double* bt2_T = nullptr;            // T factors of the stage-2 back-transform's tasks, their slot offsets behind them
   int64_t* bt2_dtoff = nullptr;
   int* bt2_err = nullptr;             // watchdog word of the persistent stage-2 back-transform (when it ran)
-  Bt1Plan bt1;                        // merged block reflectors of the stage-1 back-transform
-  double *bt1_V = nullptr, *bt1_T = nullptr, *bt1_G = nullptr;
-  int64_t LT1 = 0;
+  // merged block reflectors of the stage-1 back-transform: the V blocks; T, Gram matrix and scratch per group; the group table
+  double *bt1_V = nullptr, *bt1_T = nullptr, *bt1_G = nullptr, *bt1_tmp = nullptr;
+  Bt1Group* bt1_groups = nullptr;
   bool lookahead_queued = false;      // work of this call may still be running on pre_stream()
   // ---- the tridiagonal matrix and the solution (host)
   std::vector<double> hd, he, vals_desc;
@@ -3026,10 +3028,7 @@ struct DenseEig : EigArgs {
   // (BIGKRLS_BG=1, an A/B switch: what is precomputed for the back-transforms goes to a lowest-priority stream instead
   //  of the high-priority look-ahead stream. Measured slower: C3 0.4029-0.4043 vs 0.4009-0.4012 s, same box
   //  (profiles/r06/r06g_bg_stream_ab_*.log) -- the merged blocks then finish late behind the stage-2 back-transform)
-  hipStream_t pre_stream() const {
-    static const bool bg = [] { const char* e = getenv("BIGKRLS_BG"); return e && e[0] == '1'; }();
-    return bg ? ctx->bg_stream : ctx->side_stream;
-  }
+  hipStream_t pre_stream() const { return bg ? ctx->bg_stream : ctx->side_stream; }
 
   // ---- Neig << N: block Lanczos (the reference switches to eigs_sym for Neig < N, src/eigen.cpp:18-22);
   // BIGKRLS_EIGK=dense keeps the dense path, =krylov forces the iterative one when Neig <= N/4. *go_dense is set when
@@ -3089,35 +3088,37 @@ struct DenseEig : EigArgs {
     return BIGKRLS_OK;
   }
 
-  // ---- the workspace of the reduction and of the stage-2 back-transform's T factors: sizes, slots, layout, then what a
-  // fresh decomposition starts from and the two small tables the device needs
+  // The switches of the back half, as csrc/s2plan.h takes them: the variants are read at every decomposition (the tests
+  // switch them), the group size of the stage-1 back-transform and BIGKRLS_BG once per process
+  static S2Switches read_switches() {
+    static const int bt1_grp = [] { const char* e = getenv("BIGKRLS_BT1_GRP"); return e ? atoi(e) : 0; }();
+    static const bool bg = [] { const char* e = getenv("BIGKRLS_BG"); return e && e[0] == '1'; }();
+    S2Switches sw;
+    sw.eig = getenv("BIGKRLS_EIG");
+    sw.bc = getenv("BIGKRLS_BC");
+    sw.bc_t = getenv("BIGKRLS_BC_T");
+    sw.bt2 = getenv("BIGKRLS_BT2");
+    sw.bt2_seg = getenv("BIGKRLS_BT2_SEG");
+    sw.bt1 = getenv("BIGKRLS_BT1");
+    sw.bt1_grp = bt1_grp;
+    sw.bg = bg;
+    return sw;
+  }
+
+  // ---- the plan of the back half, then the workspace of the reduction and of the stage-2 back-transform's T factors:
+  // sizes, slots, layout, then what a fresh decomposition starts from and the two small tables the device needs
   int carve_workspace() {
-    // two-stage (band) reduction is the default above 4 panels; BIGKRLS_EIG=1stage forces the
-    // one-stage (symv) reduction (kept for small n and as a cross-check: the tests run both)
-    const char* eig_env = getenv("BIGKRLS_EIG");
-    two_stage = mode != EIG_FULL || (!(eig_env && std::string(eig_env) == "1stage") && n > 4 * S2_B);
+    const S2Switches env = read_switches();
+    bg = env.bg;
+    two_stage = s2_two_stage(mode == EIG_FULL, env.eig, n);
+    plan = s2_plan(n, two_stage, n_vecs_max > 0, ctx->no_resident, env);
     // ---- sizes, in doubles. The tiled-symv partial buffers live in the (later) U slot of the divide & conquer
     const int64_t sv_prow = (N / SV_CW + 2) * N, sv_pcol = 10 * N, sv_prow2 = (N / (SV_CW * 32) + 2) * N;
     const int64_t u_doubles = std::max<int64_t>(N * N, sv_prow + sv_pcol + sv_prow2 + 16 * 2 * TRD_NB);
-    const int64_t nb64 = N * S2_B;
-    const int64_t maxb = (N + 255) / 256 + 2;
-    const int64_t nmail1 = 2 * maxb * 2 * S2_B;  // pq_resident: 2 buffers x workgroups x 64 word pairs
-    const int64_t nmail = nmail1 + 2 * 16 * 2 * S2_B;   // + 2 buffers x 16 group boxes
-    const int64_t npqc = PQC_MAIL_DOUBLES;   // pq_chol mailbox
-    const int64_t npart = 2 * maxb + 2 * maxb * S2_B + S2_B + S2_B * S2_B + 2 * N + nmail;
-    const int64_t ntall = (N / S2_B + 2) * S2_B * S2_B;
-    const int64_t nfpart = (N / (S1F_CHUNKS * S2_B) + 3) * S2_B * S2_B;   // partial V'Y blocks of the fused small products
-    const int64_t bt_doubles = 8 * nb64 + S2_B * S2_B /* Vw, Tfold: the split panel factorisation */ + 8 * S2_B * S2_B + npart + ntall + nfpart + npqc + 2 * N /*taus1, scales1*/ +
-                               (int64_t)S2_LD * N /*AB*/ + N + 8 /*soff as int64*/;
-    const Stage2Plan plan = two_stage ? stage2_plan(n) : Stage2Plan();
+    const S1Regions r = s1_regions(N);
     // reflector blocks of the two panel groups whose trailing update is pending (stage1_to_band)
     const bool agg = two_stage && mode != EIG_RESUME && n >= S1_AGG_MIN_M + 4 * S2_B;
     const int64_t agg_blk = N * 4 * S2_B;
-    // T factors of the stage-2 back-transform tasks (BIGKRLS_BT2=seq: reflector-by-reflector kernel)
-    const char* bt2_env = getenv("BIGKRLS_BT2");
-    const bool bt2_wy = two_stage && n_vecs_max > 0 && n >= 3 && !(bt2_env && std::string(bt2_env) == "seq");
-    if (bt2_wy) bt2_toff = bt2_task_offsets(n);
-    const int64_t ntasks = bt2_wy ? bt2_toff.back() : 0;
     // ---- slots
     void *pW = nullptr, *pP = nullptr, *pV = nullptr, *pU = nullptr, *p2 = nullptr, *pvv = nullptr, *pt2 = nullptr, *pagg = nullptr;
     BK_TRY(ws_get(ctx, SLOT_EIG_A, N * N * sizeof(double), &pW));
@@ -3125,13 +3126,12 @@ struct DenseEig : EigArgs {
     BK_TRY(ws_get(ctx, SLOT_EIG_VEC, (5 * N + 4 * TRD_NB + 2 * ((N + 255) / 256 + 2)) * sizeof(double), &pV));
     BK_TRY(ws_get(ctx, SLOT_EIG_U, u_doubles * sizeof(double), &pU));
     if (two_stage) {
-      BK_TRY(ws_get(ctx, SLOT_EIG_BT, bt_doubles * sizeof(double), &p2));
-      BK_TRY(ws_get(ctx, SLOT_EIG_VV, (plan.nrefl * (S2_B + 1) + 16) * sizeof(double), &pvv));
+      BK_TRY(ws_get(ctx, SLOT_EIG_BT, r.doubles * sizeof(double), &p2));
+      BK_TRY(ws_get(ctx, SLOT_EIG_VV, plan.vv_bytes(), &pvv));
     }
-    if (bt2_wy)
-      BK_TRY(ws_get(ctx, SLOT_EIG_T2, (ntasks * BT2_G * BT2_G + (int64_t)bt2_toff.size() + 8) * (int64_t)sizeof(double), &pt2));
+    if (plan.have_t) BK_TRY(ws_get(ctx, SLOT_EIG_T2, plan.t2_bytes(), &pt2));
     if (agg) BK_TRY(ws_get(ctx, SLOT_EIG_AGG, (4 * agg_blk + 3 * 4 * S2_B * S2_B) * (int64_t)sizeof(double), &pagg));
-    if (bt2_wy) BK_TRY(side_stream_get(ctx));
+    if (plan.have_t) BK_TRY(side_stream_get(ctx));
     // ---- layout
     W = (double*)pW;
     P1 = (double*)pP;
@@ -3144,31 +3144,31 @@ struct DenseEig : EigArgs {
     sw = SymvWs{U, U + sv_prow, U + sv_prow + sv_pcol, U + sv_prow + sv_pcol + sv_prow2};
     if (two_stage) {
       double* q = (double*)p2;
-      s1.Vp = q; q += nb64;
-      s1.Vw = q; q += nb64;
-      s1.Tfold = q; q += S2_B * S2_B;
-      s1.Y = q; q += nb64;
-      s1.Y2 = q; q += nb64;
-      s1.PZ1 = q; q += 2 * nb64;
-      s1.PZ2 = q; q += 2 * nb64;
-      s1.small = q; q += 8 * S2_B * S2_B;
-      s1.part = q; q += npart;
-      s1.mail = s1.part + (npart - nmail);
-      s1.mail2 = s1.mail + nmail1;
+      s1.Vp = q + r.Vp.off;
+      s1.Vw = q + r.Vw.off;
+      s1.Tfold = q + r.Tfold.off;
+      s1.Y = q + r.Y.off;
+      s1.Y2 = q + r.Y2.off;
+      s1.PZ1 = q + r.PZ1.off;
+      s1.PZ2 = q + r.PZ2.off;
+      s1.small = q + r.small.off;
+      s1.part = q + r.p.part.off;
+      s1.mail = q + r.p.mail.off;
+      s1.mail2 = q + r.p.mail2.off;
       s1.err = (int*)scratch;
-      s1.Tall = q; q += ntall;
-      s1.fpart = q; q += nfpart;
-      s1.pqc = q; q += npqc;
+      s1.Tall = q + r.Tall.off;
+      s1.fpart = q + r.fpart.off;
+      s1.pqc = q + r.pqc.off;
       s1.fallback = (int*)scratch + 4;
-      taus1 = q; q += 2 * N;
-      AB = q; q += (int64_t)S2_LD * N;
-      d_soff = (int64_t*)q;
+      taus1 = q + r.taus1.off;
+      AB = q + r.AB.off;
+      d_soff = (int64_t*)(q + r.soff.off);
       VV = (double*)pvv;
-      TT = VV + plan.nrefl * S2_B;
+      TT = VV + plan.tt_off();
     }
-    if (bt2_wy) {
+    if (plan.have_t) {
       bt2_T = (double*)pt2;
-      bt2_dtoff = (int64_t*)(bt2_T + ntasks * BT2_G * BT2_G);
+      bt2_dtoff = (int64_t*)(bt2_T + plan.t2_toff_off());
     }
     if (agg) {
       double* qa = (double*)pagg;
@@ -3180,40 +3180,36 @@ struct DenseEig : EigArgs {
     if (mode == EIG_FULL) BK_TRY(copy_matrix(ctx, A, N, N, lda, W, N));
     BK_HIP(hipMemsetAsync(d, 0, 3 * N * sizeof(double), st));
     if (two_stage && mode != EIG_RESUME) {   // (a resumed decomposition keeps the watchdog word of its stage 1)
-      BK_HIP(hipMemsetAsync(s1.mail, 0, nmail * sizeof(double), st));
+      BK_HIP(hipMemsetAsync(s1.mail, 0, r.p.clear_doubles() * sizeof(double), st));
       BK_HIP(hipMemsetAsync(s1.err, 0, sizeof(int), st));
-      BK_HIP(hipMemsetAsync(s1.pqc, 0, npqc * sizeof(double), st));
+      BK_HIP(hipMemsetAsync(s1.pqc, 0, r.pqc.len * sizeof(double), st));
       BK_HIP(hipMemsetAsync(s1.fallback, 0, sizeof(int), st));
-      BK_HIP(hipMemsetAsync(taus1, 0, 2 * N * sizeof(double), st));
+      BK_HIP(hipMemsetAsync(taus1, 0, r.taus1.len * sizeof(double), st));
     }
     if (two_stage) {
       // (through the pinned upload arena, sized here for the whole decomposition so that it is not reallocated later;
       //  the task offsets are not read before bt2_build_t, which ev_fork orders behind everything queued here)
-      const size_t soff_bytes = plan.soff.size() * sizeof(int64_t), toff_bytes = bt2_toff.size() * sizeof(int64_t);
+      const size_t soff_bytes = plan.soff.size() * sizeof(int64_t), toff_bytes = plan.toff.size() * sizeof(int64_t);
       PinnedStage up(ctx);
       BK_TRY(up.reserve(std::max(dc_stage_bytes(n), soff_bytes + toff_bytes + 4096)));
       BK_TRY(up.put(d_soff, plan.soff.data(), soff_bytes));
-      BK_TRY(up.put(bt2_dtoff, bt2_toff.data(), toff_bytes));
+      BK_TRY(up.put(bt2_dtoff, plan.toff.data(), toff_bytes));
     }
     return BIGKRLS_OK;
   }
 
-  // merged block reflectors of the stage-1 back-transform (BIGKRLS_BT1=panel: one panel per step)
+  // merged block reflectors of the stage-1 back-transform (none under BIGKRLS_BT1=panel: one panel per step)
   int carve_bt1() {
-    const char* bt1_env = getenv("BIGKRLS_BT1");
-    if (!two_stage || n_vecs_max <= 0 || (bt1_env && std::string(bt1_env) == "panel")) return BIGKRLS_OK;
-    LT1 = bt1_grp_for(n) * S2_B;
-    bt1 = bt1_plan(n);
+    if (plan.bt1.groups.empty()) return BIGKRLS_OK;
+    const Bt1Plan::Tbig t = plan.bt1.tbig();
     void *pvb = nullptr, *ptb = nullptr;
-    BK_TRY(ws_get(ctx, SLOT_EIG_VBIG, (bt1.vtotal + 16) * (int64_t)sizeof(double), &pvb));
-    // per group: the merged T (LT x LT), its Gram matrix (LT x LT), the recurrence's scratch (LT x 64); then the group table
-    const int64_t ng1 = (int64_t)bt1.k0.size();
-    BK_TRY(ws_get(ctx, SLOT_EIG_TBIG,
-                  (ng1 * (2 * LT1 * LT1 + LT1 * S2_B) + 16) * (int64_t)sizeof(double) + (ng1 + 1) * (int64_t)sizeof(Bt1Group),
-                  &ptb));
+    BK_TRY(ws_get(ctx, SLOT_EIG_VBIG, plan.bt1.vbig_bytes(), &pvb));
+    BK_TRY(ws_get(ctx, SLOT_EIG_TBIG, t.slot_bytes, &ptb));
     bt1_V = (double*)pvb;
-    bt1_T = (double*)ptb;
-    bt1_G = bt1_T + ng1 * LT1 * LT1;
+    bt1_T = (double*)ptb + t.T.off;
+    bt1_G = (double*)ptb + t.G.off;
+    bt1_tmp = (double*)ptb + t.tmp.off;
+    bt1_groups = (Bt1Group*)((char*)ptb + t.table_bytes_off);
     return side_stream_get(ctx);
   }
 
@@ -3271,7 +3267,7 @@ struct DenseEig : EigArgs {
     // progress flags / error word of the persistent bulge-chasing kernel: the (unused here)
     // tau and scratch vectors of the one-stage path
     int* bc_err = (int*)scratch;
-    BK_TRY(stage2_to_tridiag(ctx, AB, n, d_soff, VV, TT, d, e, (int*)tau, bc_err));
+    BK_TRY(stage2_to_tridiag(ctx, plan, AB, d_soff, VV, TT, d, e, (int*)tau, bc_err));
     BK_TRY(fork_lookahead());
     BK_TRY(read_watchdog(bc_err, WD_STAGE2));
     tick("stage 2 (band -> tridiagonal)");
@@ -3288,11 +3284,9 @@ struct DenseEig : EigArgs {
       BK_HIP(hipEventRecord(ctx->ev_fork, st));          // the bulge chasing is done
       lookahead_queued = true;
       BK_HIP(hipStreamWaitEvent(side, ctx->ev_fork, 0));
-      const int ngroups = (int)bt2_toff.size() - 1, ntmax = (n - 2) / S2_B + 1;
       BK_TRY(ensure_dyn_smem(ctx, (const void*)bt2_build_t, BT2T_SMEM));
-      hipLaunchKernelGGL(bt2_build_t, dim3((unsigned)(((int64_t)ntmax * ngroups + 3) / 4)), dim3(256), BT2T_SMEM, side, n,
-                         (const int64_t*)d_soff, (const double*)VV, (const double*)TT, (const int64_t*)bt2_dtoff, bt2_T,
-                         ntmax, ngroups);
+      hipLaunchKernelGGL(bt2_build_t, dim3(plan.build_t_grid()), dim3(256), BT2T_SMEM, side, n, (const int64_t*)d_soff,
+                         (const double*)VV, (const double*)TT, (const int64_t*)bt2_dtoff, bt2_T, plan.ntmax, plan.ngroups);
       BK_CHECK_LAUNCH();
       BK_HIP(hipEventRecord(ctx->ev_join2, side));       // what the stage-2 back-transform waits for
     }
@@ -3304,10 +3298,7 @@ struct DenseEig : EigArgs {
       BK_HIP(hipEventRecord(ctx->ev_fork, st));
       lookahead_queued = true;
       BK_HIP(hipStreamWaitEvent(pre_stream(), ctx->ev_fork, 0));
-      const int64_t ng1 = (int64_t)bt1.k0.size();
-      double* bt1_tmp = bt1_G + ng1 * LT1 * LT1;
-      Bt1Group* d_groups = (Bt1Group*)(bt1_tmp + ng1 * LT1 * S2_B + 8);
-      BK_TRY(bt1_precompute(ctx, W, n, taus1, s1.Tall, bt1, bt1_V, bt1_T, bt1_G, bt1_tmp, d_groups, pre_stream()));
+      BK_TRY(bt1_precompute(ctx, W, n, taus1, s1.Tall, plan.bt1, bt1_V, bt1_T, bt1_G, bt1_tmp, bt1_groups, pre_stream()));
       BK_HIP(hipEventRecord(ctx->ev_join, pre_stream()));
     }
     return BIGKRLS_OK;
@@ -3377,19 +3368,16 @@ struct DenseEig : EigArgs {
     if (bt2_T != nullptr) BK_HIP(hipStreamWaitEvent(st, ctx->ev_join2, 0));
     // (the watchdog word of the bulge chasing, read back as zero above, now serves the persistent back-transform)
     bt2_err = (bt2_T != nullptr) ? (int*)scratch : nullptr;
-    BK_TRY(back_transform_stage2(ctx, n, d_soff, VV, TT, pvecs, ldv, pnv, bt2_dtoff, bt2_T,
-                                 bt2_toff.empty() ? 0 : bt2_toff.back(), bt2_err));
+    BK_TRY(back_transform_stage2(ctx, plan, d_soff, VV, TT, pvecs, ldv, pnv, bt2_dtoff, bt2_T, bt2_err));
     tick("back-transform stage 2");
     void* pw12 = nullptr;
-    const int64_t bt1_w = (int64_t)bt1_grp_for(n) * S2_B;
-    BK_TRY(ws_get(ctx, SLOT_EIG_Z, 2 * bt1_w * pnv * sizeof(double), &pw12));
+    BK_TRY(ws_get(ctx, SLOT_EIG_Z, plan.bt1.z_bytes(pnv), &pw12));
+    double *W1 = (double*)pw12, *W2 = W1 + plan.bt1.w2_off(pnv);
     if (bt1_V != nullptr) {
       BK_HIP(hipStreamWaitEvent(st, ctx->ev_join, 0));
-      BK_TRY(back_transform_stage1_grouped(ctx, n, bt1, bt1_V, bt1_T, pvecs, ldv, pnv, (double*)pw12,
-                                           (double*)pw12 + bt1_w * pnv));
+      BK_TRY(back_transform_stage1_grouped(ctx, plan.bt1, bt1_V, bt1_T, pvecs, ldv, pnv, W1, W2));
     } else {
-      BK_TRY(back_transform_stage1(ctx, W, n, taus1, pvecs, ldv, pnv, s1.Vp, s1.Tall, (double*)pw12,
-                                   (double*)pw12 + (int64_t)S2_B * pnv));
+      BK_TRY(back_transform_stage1(ctx, W, n, taus1, pvecs, ldv, pnv, s1.Vp, s1.Tall, W1, W2));
     }
     tick("back-transform stage 1");
     return BIGKRLS_OK;
@@ -3796,26 +3784,27 @@ int panel_factor(bigkrls_ctx* ctx, double* P, int64_t ld, int64_t m, double* Vw,
   BK_REQUIRE(P && Vw && V && T && Tfold && tau && h_fallback && m >= 2 * b && m <= (int64_t)PQC_MAXWG * 256 && ld >= m,
              "panel_factor: bad arguments (128 <= m <= 20 480 rows, ld >= m)");
   const int n = (int)m + b;
-  const int64_t maxb = (n + 255) / 256 + 2;
-  const int64_t nmail1 = 2 * maxb * 2 * S2_B, nmail = nmail1 + 2 * 16 * 2 * S2_B;
-  const int64_t npart = 2 * maxb + 2 * maxb * S2_B + S2_B + S2_B * S2_B + 2 * n + nmail;
+  Layout L;
+  const Region small = L.dev(8 * b * b);
+  const S1Part part = s1_part(L, n);
+  const Region pqc = L.dev(PQC_MAIL_DOUBLES), taus_r = L.dev(2 * n), words = L.dev(16);   // (err, fallback: zeroed with taus)
   void* pw = nullptr;
-  BK_TRY(ws_get(ctx, SLOT_EIG_MISC, (8 * b * b + npart + PQC_MAIL_DOUBLES + 2 * n + 16) * (int64_t)sizeof(double), &pw));
+  BK_TRY(ws_get(ctx, SLOT_EIG_MISC, L.total_doubles() * (int64_t)sizeof(double), &pw));
   hipStream_t st = ctx->stream;
   Stage1Ws ws{};
   double* q = (double*)pw;
   ws.Vp = V; ws.Vw = Vw; ws.Tfold = Tfold; ws.Tall = T;
-  ws.small = q; q += 8 * b * b;
-  ws.part = q; q += npart;
-  ws.mail = ws.part + (npart - nmail);
-  ws.mail2 = ws.mail + nmail1;
-  ws.pqc = q; q += PQC_MAIL_DOUBLES;
-  double* taus = q; q += 2 * n;
-  ws.err = (int*)q;
+  ws.small = q + small.off;
+  ws.part = q + part.part.off;
+  ws.mail = q + part.mail.off;
+  ws.mail2 = q + part.mail2.off;
+  ws.pqc = q + pqc.off;
+  double* taus = q + taus_r.off;
+  ws.err = (int*)(q + words.off);
   ws.fallback = ws.err + 4;
-  BK_HIP(hipMemsetAsync(ws.mail, 0, nmail * sizeof(double), st));
-  BK_HIP(hipMemsetAsync(ws.pqc, 0, PQC_MAIL_DOUBLES * sizeof(double), st));
-  BK_HIP(hipMemsetAsync(taus, 0, (2 * n + 16) * sizeof(double), st));
+  BK_HIP(hipMemsetAsync(ws.mail, 0, part.clear_doubles() * sizeof(double), st));
+  BK_HIP(hipMemsetAsync(ws.pqc, 0, pqc.len * sizeof(double), st));
+  BK_HIP(hipMemsetAsync(taus, 0, (taus_r.len + words.len) * sizeof(double), st));
   Stage1 ops;
   BK_TRY(ops.init(ctx, P - b, n, taus, ws));
   ops.N = ld;

@@ -19,9 +19,10 @@
 // The algebra was prototyped against dense numpy (residual/orthogonality 1e-15) before
 // being written here; tests/test_gpu_level1.py::test_eigen_* run both paths.
 
-constexpr int S2_B = 64;     // band width == stage-1 panel width
+// (S2_B = 64, the band width == stage-1 panel width, S2_LD = 2 S2_B rows of the band array and the other plain constants
+//  of the host plan: csrc/s2plan.h)
+static_assert(S2_B == 64 && S2_LD == 2 * S2_B, "the kernels below are written for a band of 64 and a band array of 128 rows");
 constexpr int S1_PROF_STRIDE = 8;   // bench.py's HIP-event sampling brackets every 8th panel (event overhead)
-constexpr int S2_LD = 2 * S2_B;  // rows of the band array (bulges reach 2b-1 below the diagonal)
 
 // ---------------------------------------------------------------------------
 // stage 1: panel QR (right-looking dgeqr2 on an m x pw panel, ld = N)
@@ -572,13 +573,12 @@ __global__ __launch_bounds__(256, 1) void pq_resident(double* __restrict__ P, in
 // (the schedule's thresholds S1_AGG_MIN_M, S1_SWAP_M, S1_QUAD_MIN_M: csrc/s1sched.h)
 static_assert(S1_B == S2_B, "the schedule's panel width is the band width");
 constexpr int PQC_LD = 66;             // LDS row stride of the 64 x 64 matrices and of the staged rows
-constexpr int PQC_NG = S2_B * S2_B;     // Gram entries
 constexpr double PQC_RATIO = 1e-5;      // min / max diagonal of the first Cholesky factor below which the panel is left
                                         // to the Householder kernel (kappa^2 eps must stay far below 1)
 #ifndef PQC_PARK
 #define PQC_PARK 1
 #endif
-constexpr int PQC_MAXWG = 80;
+static_assert(PQC_MAXWG == 80 && PQC_NG == S2_B * S2_B, "pq_chol: at most 80 workgroups, 64 x 64 Gram entries (csrc/s2plan.h)");
 constexpr size_t PQC_SMEM = (size_t)(3 * S2_B * PQC_LD + 64) * sizeof(double);   // dynamic LDS of pq_chol (sA, sM)
 
 // development builds (tools/pqc_bench.sh): -DPQC_STOP=n compiles the kernel up to phase n only (a build per phase: a
@@ -758,16 +758,7 @@ __device__ __forceinline__ bool pqc_wait_flags(const unsigned long long* flag, i
 #define PQC_RELEASE() do { if (PQC_FENCES & 1) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); pqc_drain(); } } while (0)
 #define PQC_ACQUIRE() do { if ((PQC_FENCES & 2) && threadIdx.x == 0) { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); pqc_drain(); } } while (0)
 
-// layout of the pq_chol mailbox (doubles): PQC_MAXWG partial matrices, the summed matrix (+ padding), the top block
-// of Q, then the flag words (partials, slices, top block)
-constexpr int64_t PQC_OFF_SLICES = (int64_t)PQC_MAXWG * PQC_NG;
-constexpr int64_t PQC_OFF_QTOP = PQC_OFF_SLICES + PQC_NG + 256;
-constexpr int64_t PQC_OFF_FLAGS = PQC_OFF_QTOP + PQC_NG;
-// ... and what the head of the split factorisation leaves for its tail (pq_tail): L \ U of Q1 - S in the top-block area,
-// the product R2 R1, then S and the reciprocals of U's diagonal
-constexpr int64_t PQC_OFF_RPROD = PQC_OFF_FLAGS + 2 * PQC_MAXWG + 16;
-constexpr int64_t PQC_OFF_SINV = PQC_OFF_RPROD + PQC_NG;
-constexpr int64_t PQC_MAIL_DOUBLES = PQC_OFF_SINV + 2 * S2_B;
+// (layout of the pq_chol mailbox, PQC_OFF_* and PQC_MAIL_DOUBLES: csrc/s2plan.h)
 
 // The T factor of the block reflector from the reconstruction itself: with Q1 - S = L U and V1 = L one has
 // (I - V T V')[I; 0] = Q S  <=>  Q1 S - I = -L T L'  <=>  T = -U S L^-T (same paper). Row i of X = T solves X L' = -U S on
@@ -1581,7 +1572,7 @@ __global__ void s1_build_vz(const double* __restrict__ Vp, const double* __restr
 //   s1_fused_z : Z = Y - 1/2 V S, written straight into [V | Z] and [Z | V].
 typedef double s1_d4 __attribute__((ext_vector_type(4)));
 constexpr int S1F_LD = S2_B + 2;   // LDS row stride 66 = 2 mod 32: conflict-free MFMA fragment reads
-constexpr int S1F_CHUNKS = 2;      // 64-row chunks per workgroup of s1_fused_yt
+static_assert(S1F_CHUNKS == 2, "s1_fused_yt: two 64-row chunks per workgroup (csrc/s2plan.h sizes fpart by it)");
 
 __global__ __launch_bounds__(256) void s1_fused_yt(const double* __restrict__ Y2, const double* __restrict__ T,
                                                    const double* __restrict__ Vp, int m,
@@ -2880,7 +2871,7 @@ __device__ unsigned long long bc_trace[BC_TR_LOCS * BC_TR_SW * BC_TR_EV];
 #define BC_TRACE(ev, cond)
 #endif
 constexpr int RB_LDC = 2 * S2_B + 9;   // window column stride; mod 32 == 9 keeps the 4-lanes-per-row matvec reads conflict-free
-constexpr int RB_BOX = 2 * (S2_B + 1);  // 8-byte words per message: (value, value ^ key(sweep)) pairs
+static_assert(RB_BOX == 2 * (S2_B + 1), "a message of the resident bulge chasing: 65 (value, value ^ key(sweep)) pairs");
 
 // NTH threads (256 or 512): the matvecs use NTH / 64 lanes per row, the update NTH / 64 column groups. With 512 a SIMD
 // holds two waves of the workgroup, which hides the LDS round trips a single wave per SIMD waits out (the kernel is
@@ -3552,103 +3543,65 @@ __global__ void s2_extract_de(const double* __restrict__ AB, int n, double* __re
   }
 }
 
-struct Stage2Plan {
-  std::vector<int64_t> soff;  // reflector slot offset of sweep s
-  int64_t nrefl = 0;
-};
-
-static Stage2Plan stage2_plan(int n) {
-  Stage2Plan p;
-  const int nsweep = std::max(0, n - 2);
-  p.soff.resize(nsweep + 1);
-  int64_t o = 0;
-  for (int s = 0; s < nsweep; ++s) {
-    p.soff[s] = o;
-    o += (n - 1 - (s + 1)) / S2_B + 1;   // steps t with s+1+t*b <= n-1
-  }
-  p.soff[nsweep] = o;
-  p.nrefl = o;
-  return p;
-}
-
-int stage2_to_tridiag(bigkrls_ctx* ctx, double* AB, int n, const int64_t* d_soff, double* VV, double* TT,
+// (sweep offsets, arm, grid, mailbox and wavefront ranges: S2Plan of csrc/s2plan.h)
+int stage2_to_tridiag(bigkrls_ctx* ctx, const S2Plan& plan, double* AB, const int64_t* d_soff, double* VV, double* TT,
                       double* d, double* e, int* progress, int* err) {
   hipStream_t st = ctx->stream;
-  const int b = S2_B;
-  const int nsweep = n - 2;
-  const char* bc_env = getenv("BIGKRLS_BC");
-  const std::string mode = ctx->no_resident ? std::string("wavefront")
-                                            : (bc_env ? std::string(bc_env) : std::string("resident"));
-  bool persistent = (mode == "persistent");
-  if (nsweep > 0 && (mode == "resident" || mode == "lds")) {
-    // the window in registers (bc_regwin) unless BIGKRLS_BC=lds: the LDS-window kernel, 512 threads per location
-    // unless BIGKRLS_BC_T=256 (A/B: 88 -> ~65 ms at n = 20 000)
-    const bool regwin = (mode == "resident");
-    const char* bct = getenv("BIGKRLS_BC_T");
-    const bool wide = !(bct && atoi(bct) == 256);
+  const int b = S2_B, n = plan.n;
+  BcArm arm = plan.bc_request;
+  const void* resident = arm == BcArm::Regwin ? (const void*)bc_regwin
+                                              : arm == BcArm::Lds512 ? (const void*)bc_resident<512> : (const void*)bc_resident<256>;
+  const int threads = arm == BcArm::Lds256 ? 256 : 512;
+  if (plan.nsweep > 0 && bc_is_resident(arm)) {
     int rcap = 1;
-    if (regwin) BK_TRY(resident_capacity(ctx, (const void*)bc_regwin, &rcap, 512));
-    else if (wide) BK_TRY(resident_capacity(ctx, (const void*)bc_resident<512>, &rcap, 512));
-    else BK_TRY(resident_capacity(ctx, (const void*)bc_resident<256>, &rcap, 256));
-    const int nloc = (n - 2) / b + 1;   // locations of sweep 0
-    if (nloc <= rcap) {
-      void* pm = nullptr;
-      const int64_t mail_doubles = (int64_t)(nloc + 1) * 3 * RB_BOX;   // (bc_regwin: three boxes per location)
-      BK_TRY(ws_get(ctx, SLOT_EIG_Z, mail_doubles * sizeof(double), &pm));
-      double* mail = (double*)pm;
-      BK_HIP(hipMemsetAsync(mail, 0, (size_t)mail_doubles * sizeof(double), st));   // A ^ B == 0: no valid message
-      // algorithmic HBM bytes: the band read once (16 n b) + the stored reflectors (8 b per task)
-      BK_TRY(prof_begin(ctx, "bulge_chase", 16.0 * (double)n * b + 8.0 * b * ((double)n * n / (2.0 * b))));
-      if (regwin)
-        hipLaunchKernelGGL(bc_regwin, dim3(nloc), dim3(512), 0, st, (const double*)AB, n, d_soff, VV, TT, d, e,
-                           mail, err);
-      else if (wide)
-        hipLaunchKernelGGL(bc_resident<512>, dim3(nloc), dim3(512), 0, st, (const double*)AB, n, d_soff, VV, TT, d, e,
-                           mail, err);
-      else
-        hipLaunchKernelGGL(bc_resident<256>, dim3(nloc), dim3(256), 0, st, (const double*)AB, n, d_soff, VV, TT, d, e,
-                           mail, err);
-      BK_TRY(prof_end(ctx, "bulge_chase"));
-      BK_CHECK_LAUNCH();
-      return BIGKRLS_OK;
-    }
-    persistent = false;   // too many locations to keep resident: wavefront launches
+    BK_TRY(resident_capacity(ctx, resident, &rcap, threads));
+    arm = plan.bc_arm(rcap);
   }
-  if (nsweep > 0 && persistent) {
-    // grid = min(sweeps in flight, co-resident capacity)
+  if (plan.nsweep > 0 && bc_is_resident(arm)) {
+    void* pm = nullptr;
+    const int64_t mail_doubles = plan.bc_mail_doubles();
+    BK_TRY(ws_get(ctx, SLOT_EIG_Z, mail_doubles * sizeof(double), &pm));
+    double* mail = (double*)pm;
+    BK_HIP(hipMemsetAsync(mail, 0, (size_t)mail_doubles * sizeof(double), st));   // A ^ B == 0: no valid message
+    // algorithmic HBM bytes: the band read once (16 n b) + the stored reflectors (8 b per task)
+    BK_TRY(prof_begin(ctx, "bulge_chase", 16.0 * (double)n * b + 8.0 * b * ((double)n * n / (2.0 * b))));
+    if (arm == BcArm::Regwin)
+      hipLaunchKernelGGL(bc_regwin, dim3(plan.nloc), dim3(512), 0, st, (const double*)AB, n, d_soff, VV, TT, d, e,
+                         mail, err);
+    else if (arm == BcArm::Lds512)
+      hipLaunchKernelGGL(bc_resident<512>, dim3(plan.nloc), dim3(512), 0, st, (const double*)AB, n, d_soff, VV, TT, d, e,
+                         mail, err);
+    else
+      hipLaunchKernelGGL(bc_resident<256>, dim3(plan.nloc), dim3(256), 0, st, (const double*)AB, n, d_soff, VV, TT, d, e,
+                         mail, err);
+    BK_TRY(prof_end(ctx, "bulge_chase"));
+    BK_CHECK_LAUNCH();
+    return BIGKRLS_OK;
+  }
+  if (plan.nsweep > 0 && arm == BcArm::Persistent) {
     int cap = 1;
     BK_TRY(resident_capacity(ctx, (const void*)bc_persistent, &cap));
-    const int t0 = (n - 2) / b + 1;                 // tasks of sweep 0
-    int grid = std::min(std::min(nsweep, t0 / 2 + 2), cap);
-    BK_HIP(hipMemsetAsync(progress, 0, (size_t)nsweep * sizeof(int), st));
-    hipLaunchKernelGGL(bc_persistent, dim3(grid), dim3(256), 0, st, AB, n, d_soff, VV, TT, progress, err,
-                       nsweep);
+    BK_HIP(hipMemsetAsync(progress, 0, (size_t)plan.nsweep * sizeof(int), st));
+    hipLaunchKernelGGL(bc_persistent, dim3(plan.bc_persistent_grid(cap)), dim3(256), 0, st, AB, n, d_soff, VV, TT, progress,
+                       err, plan.nsweep);
     BK_CHECK_LAUNCH();
-  } else if (nsweep > 0) {
-    // last wavefront: s = n-3, t = 0 (lo = n-2 <= n-1; t = 1 would need lo = n-2+b > n-1 unless b == 1)
-    const int64_t tmax = 2ll * (nsweep - 1) + ((n - 1) - (nsweep - 1 + 1)) / b;
-    for (int64_t w = 0; w <= tmax; ++w) {
-      // tasks (s,t), t = w - 2s >= 0, lo = s+1+t b <= n-1, s <= n-3
-      int64_t smax = std::min<int64_t>(w / 2, nsweep - 1);
-      // s + 1 + (w - 2s) b <= n - 1  <=>  s (2b - 1) >= w b - n + 2
-      int64_t num = w * b - n + 2;
-      int64_t smin = 0;
-      if (num > 0) smin = (num + (2 * b - 2)) / (2 * b - 1);
-      if (smin > smax) continue;
-      const int cnt = (int)(smax - smin + 1);
+  } else if (plan.nsweep > 0) {
+    for (int64_t w = 0; w <= plan.bc_tmax(); ++w) {
+      const S2Range r = plan.bc_wavefront(w);
+      if (r.count == 0) continue;
       const bool sample = ctx->profile && (w % 64) == 32;
       if (sample) {
         // algorithmic bytes of this launch: every task reads and writes its len x b off-diagonal
         // block (t > 0) and the lower triangle of its len x len diagonal block
         double bytes = 0.0;
-        for (int64_t s = smin; s <= smax; ++s) {
+        for (int64_t s = r.lo; s < r.lo + r.count; ++s) {
           const int64_t t = w - 2 * s, lo = s + 1 + t * b;
           const double len = (double)(std::min<int64_t>(s + (t + 1) * b, n - 1) - lo + 1);
           bytes += 16.0 * (len * (len + 1.0) * 0.5 + (t > 0 ? len * b : len));
         }
         BK_TRY(prof_begin(ctx, "bulge_chase", bytes));
       }
-      hipLaunchKernelGGL(bc_wavefront, dim3(cnt), dim3(256), 0, st, AB, n, (int)w, (int)smin, d_soff, VV, TT);
+      hipLaunchKernelGGL(bc_wavefront, dim3(r.count), dim3(256), 0, st, AB, n, (int)w, (int)r.lo, d_soff, VV, TT);
       if (sample) BK_TRY(prof_end(ctx, "bulge_chase"));
     }
     BK_CHECK_LAUNCH();
@@ -3709,7 +3662,7 @@ __global__ __launch_bounds__(256) void bt2_sweep(double* __restrict__ Z, int64_t
 // 64-column slab of Z held in LDS, so Z moves through HBM once per GROUP instead of once
 // per sweep. Reordering is legal because reflectors with disjoint rows commute:
 //   (g,t) needs (g,t-1) and (g-1,t) done; tasks with equal g + t are independent.
-constexpr int BT2_G = 32;
+static_assert(BT2_G == 32, "the stage-2 back-transform's tasks: 32 sweeps (csrc/s2plan.h)");
 __global__ __launch_bounds__(256) void bt2_block(double* __restrict__ Z, int64_t ldz, int n, int nv,
                                                  int wave_idx, int g_min, const int64_t* __restrict__ soff,
                                                  const double* __restrict__ VV,
@@ -3810,19 +3763,7 @@ __global__ __launch_bounds__(256) void bt2_block(double* __restrict__ Z, int64_t
 constexpr int BT2_LDW = BT2_G + S2_B + 2;   // 98: LDS stride of window columns / reflector rows, = 2 mod 32
 typedef double d4 __attribute__((ext_vector_type(4)));
 
-// slot of task (g, t)'s T factor: toff[g] + t
-static std::vector<int64_t> bt2_task_offsets(int n) {
-  const int nsweep = std::max(0, n - 2);
-  const int ngroups = (nsweep + BT2_G - 1) / BT2_G;
-  std::vector<int64_t> toff(ngroups + 1, 0);
-  for (int g = 0; g < ngroups; ++g) {
-    const int s_hi = (n - 3) - g * BT2_G;
-    const int s_lo = std::max(0, s_hi - BT2_G + 1);
-    toff[g + 1] = toff[g] + ((n - 2 - s_lo) / S2_B + 1);   // steps t with s_lo + 1 + t b <= n - 1
-  }
-  return toff;
-}
-
+// (slot of task (g, t)'s T factor, toff[g] + t: S2Plan::toff of csrc/s2plan.h)
 // One WAVE per task (round 6; it was one workgroup per task, whose 32-step recurrence ran on at most 32 of its 256
 // threads between two workgroup barriers per step: 6 ms at N = 20 000 for 97 000 tasks, on the stream that shares the GPU
 // with the divide & conquer). The Gram products V_k' V_j of the task's 32 reflectors (length 64, shifted by one window
@@ -4166,7 +4107,6 @@ __global__ __launch_bounds__(256, 2) void bt2_persistent(double* __restrict__ Z,
 // handed out in the order in which the segments become runnable (see below): its predecessors -- (g, t-1) for every step, (g-1, t) for its
 // first step -- belong to tickets with smaller numbers, so the progress argument of bt2_persistent holds unchanged.
 // The per-task flags stay: the chain at t follows the chain at t - 1 one step behind.
-constexpr int BT2_CHAIN_MIN_N = 8000;      // below, the back-transform is bound by its dependency chain, not by traffic
 __device__ __forceinline__ int bt2_rot(int i, int base) {
   const int x = i + base;
   return x >= 96 ? x - 96 : x;
@@ -4428,101 +4368,58 @@ __global__ __launch_bounds__(256, 2) void bt2_chain(double* __restrict__ Z, int6
   }
 }
 
-int back_transform_stage2(bigkrls_ctx* ctx, int n, const int64_t* d_soff, const double* VV,
-                          const double* TT, double* Z, int64_t ldz, int nv,
-                          const int64_t* d_toff = nullptr, const double* Tst = nullptr,
-                          int64_t ntasks = 0, int* err = nullptr) {
+// (arm, task geometry, flag layout, grid and anti-diagonal ranges: S2Plan of csrc/s2plan.h. d_toff, Tst and err exist
+//  on every arm but Seq)
+int back_transform_stage2(bigkrls_ctx* ctx, const S2Plan& plan, const int64_t* d_soff, const double* VV,
+                          const double* TT, double* Z, int64_t ldz, int nv, const int64_t* d_toff, const double* Tst,
+                          int* err) {
   hipStream_t st = ctx->stream;
+  const int n = plan.n;
   if (n < 3 || nv <= 0) return BIGKRLS_OK;
-  const int nsweep = n - 2;
-  const int ngroups = (nsweep + BT2_G - 1) / BT2_G;
-  const int ntmax = (n - 2) / S2_B + 1;  // steps of sweep 0
   const dim3 block(256);
   const size_t wy_smem = (size_t)(64 + BT2_G) * BT2_LDW * sizeof(double);
-  if (Tst != nullptr) BK_TRY(ensure_dyn_smem(ctx, (const void*)bt2_wy, wy_smem));
-  const char* bt2_env = getenv("BIGKRLS_BT2");
-  const bool want_persistent = Tst != nullptr && err != nullptr && ntasks > 0 && !ctx->no_resident &&
-                               !(bt2_env && std::string(bt2_env) == "wavefront");
-  if (want_persistent) {
-    // BIGKRLS_BT2=tasks: one ticket per task (bt2_persistent); default: chains of BIGKRLS_BT2_SEG groups (bt2_chain)
-    const bool chain = bt2_env ? std::string(bt2_env) == "chain" : n > BT2_CHAIN_MIN_N;
-    const char* seg_env = getenv("BIGKRLS_BT2_SEG");             // (read per call: the tests switch it)
-    const int seg = (seg_env && atoi(seg_env) > 0) ? atoi(seg_env) : 32;
+  if (plan.have_t) BK_TRY(ensure_dyn_smem(ctx, (const void*)bt2_wy, wy_smem));
+  if (plan.bt2_arm == Bt2Arm::Tasks || plan.bt2_arm == Bt2Arm::Chain) {
+    const bool chain = plan.bt2_arm == Bt2Arm::Chain;
     const void* fn = chain ? (const void*)bt2_chain : (const void*)bt2_persistent;
     BK_TRY(ensure_dyn_smem(ctx, fn, wy_smem));
     int per_cu = 0, ncu = 0;
     BK_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, wy_smem));
     BK_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    const int nslab = (nv + 63) / 64;
-    const int64_t total = ntasks * nslab;
-    const int grid = (int)std::min<int64_t>((int64_t)std::max(1, per_cu) * ncu, total);
+    const Bt2Flags fl = plan.bt2_flags(nv);
+    const int grid = S2Plan::bt2_persistent_grid(per_cu, ncu, fl.total);
     void* pf = nullptr;
-    const int64_t ticket_off = (total + 3) / 2 * 2;      // (8-byte aligned) the ticket counter behind the flags
-    BK_TRY(ws_get(ctx, SLOT_EIG_FLAGS, (ticket_off + 16) * (int64_t)sizeof(int), &pf));
-    BK_HIP(hipMemsetAsync(pf, 0, (size_t)(ticket_off + 4) * sizeof(int), st));
+    BK_TRY(ws_get(ctx, SLOT_EIG_FLAGS, fl.slot_bytes, &pf));
+    BK_HIP(hipMemsetAsync(pf, 0, (size_t)fl.clear_bytes, st));
     if (chain)
-      hipLaunchKernelGGL(bt2_chain, dim3(grid), block, wy_smem, st, Z, ldz, n, nv, ngroups, ntmax, seg, d_soff, VV,
-                         d_toff, Tst, (int*)pf, (long long)ticket_off, err);
+      hipLaunchKernelGGL(bt2_chain, dim3(grid), block, wy_smem, st, Z, ldz, n, nv, plan.ngroups, plan.ntmax, plan.seg, d_soff,
+                         VV, d_toff, Tst, (int*)pf, (long long)fl.ticket_off, err);
     else
-      hipLaunchKernelGGL(bt2_persistent, dim3(grid), block, wy_smem, st, Z, ldz, n, nv, ngroups, ntmax, d_soff, VV,
-                         d_toff, Tst, (int*)pf, (long long)ticket_off, err);
+      hipLaunchKernelGGL(bt2_persistent, dim3(grid), block, wy_smem, st, Z, ldz, n, nv, plan.ngroups, plan.ntmax, d_soff, VV,
+                         d_toff, Tst, (int*)pf, (long long)fl.ticket_off, err);
     BK_CHECK_LAUNCH();
     return BIGKRLS_OK;
   }
-  for (int w = 0; w <= (ngroups - 1) + (ntmax - 1); ++w) {
-    // tasks (g, t = w - g): 0 <= g < ngroups, t >= 0, first row of the window <= n-1
-    const int g_hi = std::min(w, ngroups - 1);
-    int g_lo = std::max(0, w - (ntmax - 1));
-    if (g_lo > g_hi) continue;
-    if (Tst != nullptr)
-      hipLaunchKernelGGL(bt2_wy, dim3(g_hi - g_lo + 1, (nv + 63) / 64), block, wy_smem, st, Z, ldz, n, nv, w,
-                         g_lo, d_soff, VV, d_toff, Tst);
+  for (int w = 0; w < plan.bt2_diagonals(); ++w) {
+    const S2Range r = plan.bt2_diagonal(w);
+    if (r.count == 0) continue;
+    if (plan.bt2_arm == Bt2Arm::WyWavefront)
+      hipLaunchKernelGGL(bt2_wy, dim3(r.count, plan.slabs(nv)), block, wy_smem, st, Z, ldz, n, nv, w, (int)r.lo, d_soff, VV,
+                         d_toff, Tst);
     else
-      hipLaunchKernelGGL(bt2_block, dim3(g_hi - g_lo + 1, (nv + 63) / 64), block, 0, st, Z, ldz, n, nv, w,
-                         g_lo, d_soff, VV, TT);
+      hipLaunchKernelGGL(bt2_block, dim3(r.count, plan.slabs(nv)), block, 0, st, Z, ldz, n, nv, w, (int)r.lo, d_soff, VV, TT);
   }
   BK_CHECK_LAUNCH();
   return BIGKRLS_OK;
 }
 
-// ---- stage-1 back-transform with bt1_grp_for(n) panels per step --------------------------------------
+// ---- stage-1 back-transform with Bt1Plan::grp panels per step (csrc/s2plan.h) ---------------------------
 // Q1 = H(0) H(1) ... with one 64-column block reflector per panel. Consecutive panels are merged:
 //   H(p) ... H(p+g-1) = I - Vb Tb Vb',  Vb = [V_p | V_{p+1} | ...] (later panels zero-padded on top),
 //   Tb(0:64j, j-th block) = -Tb(0:64j, 0:64j) (V_{0:j}' V_j) T_j   (block form of dlarft),
 // so that the n/64 dependent steps of three thin GEMMs become n/256 steps of GEMMs with a 256-deep
 // inner dimension. Vb and Tb depend only on stage 1: they are built on the look-ahead stream while
 // the main stream does the bulge chasing and the divide & conquer.
-// panels per merged block reflector: eight (until round 6 four above n = 10 000, where the precomputation of the wider
-// blocks on the look-ahead stream cost what the faster steps saved). BIGKRLS_BT1_GRP = 2, 4 or 8 overrides.
-static int bt1_grp_for(int n) {
-  static const int env = [] { const char* e = getenv("BIGKRLS_BT1_GRP"); return e ? atoi(e) : 0; }();
-  if (env == 2 || env == 4 || env == 8) return env;
-  // eight panels per merged block at every size since round 6 (four above n = 10 000 before): the steps are faster
-  // (N = 20 000: 13.0 -> 10.9 ms) and the blocks, now built in batched launches, no longer cost what that saves
-  // (C3 0.4008-0.4012 -> 0.3991-0.4001 s, N = 14 000 0.1970-0.1985 -> 0.1955-0.1971 s: profiles/r06/r06j_*)
-  (void)n;
-  return 8;
-}
-struct Bt1Plan {
-  std::vector<int> k0, g;          // first panel column and number of panels of every group
-  std::vector<int64_t> voff;       // offset of the group's Vb in the store
-  int64_t vtotal = 0;
-};
-static Bt1Plan bt1_plan(int n) {
-  Bt1Plan p;
-  const int b = S2_B;
-  int npan = 0;
-  for (int k = 0; k + b < n && n - k - b > 1; k += b) ++npan;
-  const int grp = bt1_grp_for(n);
-  for (int q = 0; q < npan; q += grp) {
-    const int g = std::min(grp, npan - q), k0 = q * b;
-    p.k0.push_back(k0);
-    p.g.push_back(g);
-    p.voff.push_back(p.vtotal);
-    p.vtotal += (int64_t)(n - k0 - b) * b * g;
-  }
-  return p;
-}
 
 // Vb (m0 x 64 g, ld m0): panel i's unit-lower-trapezoidal reflector block in rows >= 64 i
 __global__ void s1_extract_vbig(const double* __restrict__ W, int64_t N, int k0, int g, int m0,
@@ -4548,7 +4445,8 @@ __global__ void s1_extract_vbig(const double* __restrict__ W, int64_t N, int k0,
 // back-transform waited 5 ms for them. Now: ONE launch builds every group's V block and the block diagonal of its T,
 // the Gram products stay one GEMM per group (they are the flops), and every step of the T recurrence is two launches
 // over all groups: 1 + 2 ngroups + 2 (g - 1) launches.
-struct Bt1Group { int k0, g, m0, pad; long long voff; };
+// (the group record Bt1Group { k0, g, m0, pad, voff }: csrc/s2plan.h)
+static_assert(sizeof(Bt1Group) == 24, "the group table as the kernels read it");
 
 // grid (blocks, ngroups): Vb_q (m0 x 64 g, ld m0) as s1_extract_vbig builds it, and Tb_q = blockdiag(T_{q,0} ... T_{q,g-1})
 // in an LT x LT matrix that is zero elsewhere
@@ -4656,9 +4554,8 @@ int bt1_precompute(bigkrls_ctx* ctx, const double* W, int n, const double* taus1
                    const Bt1Plan& plan, double* Vstore, double* Tstore, double* Gstore, double* tmpstore,
                    Bt1Group* d_groups, hipStream_t ps) {
   const int64_t N = n;
-  const int b = S2_B;
-  const int LT = bt1_grp_for(n) * S2_B;
-  const int ng = (int)plan.k0.size();
+  const int LT = plan.LT;
+  const int ng = (int)plan.ng();
   if (ng == 0) return BIGKRLS_OK;
   // the group table through a pinned buffer of its own (the upload arena belongs to the divide & conquer, which runs
   // on the host while this is still queued)
@@ -4672,26 +4569,20 @@ int bt1_precompute(bigkrls_ctx* ctx, const double* W, int n, const double* taus1
     BK_HIP(hipHostMalloc((void**)&ctx->h_plan, tbytes + 4096, hipHostMallocDefault));
     ctx->h_plan_bytes = (int64_t)tbytes + 4096;
   }
-  Bt1Group* hg = (Bt1Group*)ctx->h_plan;
-  int gmax = 0;
-  int64_t maxwork = (int64_t)LT * LT;
-  for (int q = 0; q < ng; ++q) {
-    hg[q].k0 = plan.k0[q]; hg[q].g = plan.g[q]; hg[q].m0 = n - plan.k0[q] - b; hg[q].pad = 0; hg[q].voff = plan.voff[q];
-    gmax = std::max(gmax, plan.g[q]);
-    maxwork = std::max<int64_t>(maxwork, (int64_t)hg[q].m0 * b * hg[q].g);
-  }
-  BK_HIP(hipMemcpyAsync(d_groups, hg, tbytes, hipMemcpyHostToDevice, ps));
-  const int blocks = (int)std::min<int64_t>((maxwork + 255) / 256, 1024);
+  memcpy(ctx->h_plan, plan.groups.data(), tbytes);
+  BK_HIP(hipMemcpyAsync(d_groups, ctx->h_plan, tbytes, hipMemcpyHostToDevice, ps));
+  const int blocks = (int)std::min<int64_t>((plan.maxwork + 255) / 256, 1024);
   hipLaunchKernelGGL(bt1_extract_all, dim3(blocks, ng), dim3(256), 0, ps, (const Bt1Group*)d_groups, W, N,
                      (const double*)(taus1 + n), Tall, LT, Vstore, Tstore);
   BK_CHECK_LAUNCH();
   for (int q = 0; q < ng; ++q) {
     StreamScope on(ctx, ps);   // gemm() launches on ctx->stream
-    const int g = plan.g[q], m0 = n - plan.k0[q] - b, w = b * g;
-    const double* Vb = Vstore + plan.voff[q];
-    if (g > 1) BK_TRY(gemm(ctx, 1, 0, w, w, m0, 1.0, Vb, m0, Vb, m0, 0.0, Gstore + (int64_t)q * LT * LT, LT));   // Gb = Vb' Vb
+    const Bt1Group& gr = plan.groups[q];
+    const int w = S2_B * gr.g;
+    const double* Vb = Vstore + gr.voff;
+    if (gr.g > 1) BK_TRY(gemm(ctx, 1, 0, w, w, gr.m0, 1.0, Vb, gr.m0, Vb, gr.m0, 0.0, Gstore + (int64_t)q * LT * LT, LT));   // Gb = Vb' Vb
   }
-  for (int j = 1; j < gmax; ++j)
+  for (int j = 1; j < plan.gmax; ++j)
     for (int mode = 0; mode < 2; ++mode)
       hipLaunchKernelGGL(bt1_merge_step, dim3(j, ng), dim3(256), 0, ps, (const Bt1Group*)d_groups, j, mode, LT, Tall,
                          Tstore, (const double*)Gstore, tmpstore);
@@ -4699,20 +4590,19 @@ int bt1_precompute(bigkrls_ctx* ctx, const double* W, int n, const double* taus1
   return BIGKRLS_OK;
 }
 
-// Z <- Q1 Z with the merged block reflectors (W1, W2: 256 x nv scratch each)
-int back_transform_stage1_grouped(bigkrls_ctx* ctx, int n, const Bt1Plan& plan, const double* Vstore,
-                                  const double* Tstore, double* Z, int64_t ldz, int nv, double* W1,
-                                  double* W2) {
-  const int b = S2_B;
-  const int LT = bt1_grp_for(n) * S2_B;
-  for (int q = (int)plan.k0.size() - 1; q >= 0; --q) {
-    const int k0 = plan.k0[q], g = plan.g[q], m0 = n - k0 - b, w = b * g;
-    const double* Vb = Vstore + plan.voff[q];
+// Z <- Q1 Z with the merged block reflectors (W1, W2: LT x nv scratch each)
+int back_transform_stage1_grouped(bigkrls_ctx* ctx, const Bt1Plan& plan, const double* Vstore, const double* Tstore,
+                                  double* Z, int64_t ldz, int nv, double* W1, double* W2) {
+  const int LT = plan.LT;
+  for (int q = (int)plan.ng() - 1; q >= 0; --q) {
+    const Bt1Group& gr = plan.groups[q];
+    const int w = S2_B * gr.g;
+    const double* Vb = Vstore + gr.voff;
     const double* Tb = Tstore + (int64_t)q * LT * LT;
-    double* Zs = Z + (k0 + b);
-    BK_TRY(gemm(ctx, 1, 0, w, nv, m0, 1.0, Vb, m0, Zs, ldz, 0.0, W1, LT));
+    double* Zs = Z + (gr.k0 + S2_B);
+    BK_TRY(gemm(ctx, 1, 0, w, nv, gr.m0, 1.0, Vb, gr.m0, Zs, ldz, 0.0, W1, LT));
     BK_TRY(gemm(ctx, 0, 0, w, nv, w, 1.0, Tb, LT, W1, LT, 0.0, W2, LT));
-    BK_TRY(gemm(ctx, 0, 0, m0, nv, w, -1.0, Vb, m0, W2, LT, 1.0, Zs, ldz));
+    BK_TRY(gemm(ctx, 0, 0, gr.m0, nv, w, -1.0, Vb, gr.m0, W2, LT, 1.0, Zs, ldz));
   }
   return BIGKRLS_OK;
 }

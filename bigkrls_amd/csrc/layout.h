@@ -40,6 +40,7 @@ class Layout {
   int64_t down_doubles() const { return down_; }
   int64_t down_off() const { return down_off_; }
   int64_t slot_doubles() const { return total_ + 64; }   // (the slack every entry has always asked for)
+  int64_t total_doubles() const { return total_; }       // the regions alone (csrc/s2plan.h: slots sized without slack)
   bool valid() const { return ok_; }
   bool down_adjacent() const { return adjacent_; }
 
