@@ -106,6 +106,7 @@ SIGNATURES = {
     "bigkrls_dev_gemm_modulated2": [vp, i64, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, f64, vp, i64, vp, i64],
     "bigkrls_dev_gram_weighted": [vp, i64, i64, vp, i64, vp, vp, i64],
     "bigkrls_dev_cluster_scores": [vp, i64, i64, vp, i64, vp, vp, i64, vp, i64],
+    "bigkrls_dev_deletion_residuals": [vp, i64, i64, vp, i64, vp, vp, vp, i64, i32, vp, vp, vp, i64],
     "bigkrls_dev_multdiag": [vp, vp, i64, i64, i64, vp, vp, i64],
     "bigkrls_dev_eigen": [vp, vp, i64, i64, i64, vp, i64, f64, vp, i64, pi64],
     "bigkrls_dev_eigen_part": [vp, vp, i64, i64, i64, vp, i64, f64, vp, i64, pi64, i32, i32],
@@ -153,6 +154,8 @@ SIGNATURES = {
     "bigkrls_group_effects": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, vp, i64, vp, vp, i64, i64, vp, vp, vp,
                               vp],
     "bigkrls_vcov_robust": [vp, i64, i64, vp, i64, vp, f64, vp, f64, f64, i32, vp, i64, vp, i64, vp],
+    "bigkrls_influence": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, vp, i64, i64, vp, f64, vp, vp, i64, vp, vp, vp,
+                          vp, vp, vp, vp, vp],
     # multi-GPU
     "bigkrls_comm_unique_id": [vp],
     "bigkrls_comm_create": [vp, i32, i32, vp, C.POINTER(vp)],

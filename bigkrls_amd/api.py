@@ -887,7 +887,7 @@ def interaction_effects(object: BigKRLS, newdata=None, pairs=None, which=None, s
     return out
 
 
-ROBUST_TYPES = {"classical": 0, "HC0": 1, "HC1": 2, "HC2": 3, "HC3": 4, "CR0": 1, "CR1": 2}
+ROBUST_TYPES = {"classical": 0, "HC0": 1, "HC1": 2, "HC2": 3, "HC3": 4, "CR0": 1, "CR1": 2, "CR3": 5}
 
 
 def _robust_plan(object, type, cluster):
@@ -896,14 +896,15 @@ def _robust_plan(object, type, cluster):
     if not isinstance(object, BigKRLS):
         raise TypeError("Object not of class 'bigKRLS'")
     if type not in ROBUST_TYPES:
-        raise ValueError('type must be one of "classical", "HC0", "HC1", "HC2", "HC3", or "CR0", "CR1" with cluster')
+        raise ValueError('type must be one of "classical", "HC0", "HC1", "HC2", "HC3", or "CR0", "CR1", "CR3" with '
+                         'cluster')
     if object.get("vcov.est.Q") is None or object.get("vcov.est.w") is None:
         raise ValueError('the object has no vcov.est.Q / vcov.est.w: refit with vcov_form="factors" or "both"')
     clustered = type.startswith("CR")
     if clustered and cluster is None:
         raise ValueError(f'type="{type}" needs cluster (one label per row)')
     if cluster is not None and not clustered:
-        raise ValueError(f'cluster goes with type="CR0" or "CR1", not "{type}"')
+        raise ValueError(f'cluster goes with type="CR0", "CR1" or "CR3", not "{type}"')
     n = np.asarray(object["X"]).shape[0]
     k = len(np.asarray(object["vcov.est.w"]).ravel())
     d = np.asarray(object["K.eigenvalues"], dtype=np.float64).ravel()
@@ -916,22 +917,16 @@ def _robust_plan(object, type, cluster):
             raise ValueError(f"the object has no {key}")
     labels = G = None
     if clustered:
-        raw = list(cluster.tolist() if isinstance(cluster, np.ndarray) else cluster)
-        if len(raw) != n:
-            raise ValueError(f"cluster must have one label per row: {len(raw)} labels for N = {n}")
-        index = {}
-        labels = np.empty(n, dtype=np.int64)
-        for i, lab in enumerate(raw):                        # any hashable labels, numbered in order of appearance
-            labels[i] = index.setdefault(lab, len(index))
-        G = len(index)
-        if G < 2:
-            raise ValueError("cluster must hold at least 2 distinct labels")
+        labels, names = _unit_labels(cluster, n)             # any hashable labels, numbered in order of appearance
+        G = len(names)
     if type == "classical":
         scale = float(object["sigmasq"])
     elif type == "HC1":
         scale = n / float(object["Neffective"])
     elif type == "CR1":
         scale = G / (G - 1.0)
+    elif type == "CR3":
+        scale = (G - 1.0) / G
     else:
         scale = 1.0
     yv = np.asarray(object["y"], dtype=np.float64).ravel()
@@ -951,7 +946,9 @@ def robust_vcov(object: BigKRLS, type: str = "HC1", cluster=None, ctx: Optional[
     type: "classical" (omega = sigmasq: the fit's own variance, rotated), "HC0" (e_i^2), "HC1" (HC0 times
     N / Neffective, the package's degrees of freedom), "HC2" (e_i^2 / (1 - h_i)), "HC3" (e_i^2 / (1 - h_i)^2) with h the
     leverages of the smoother K (K + lambda I)^-1; "CR0" / "CR1" with `cluster` (N hashable labels, at least 2 distinct):
-    the clustered middle sum_g s_g s_g', s_g the score sum of cluster g, CR1 times G / (G - 1).
+    the clustered middle sum_g s_g s_g', s_g the score sum of cluster g, CR1 times G / (G - 1); "CR3": the cluster jackknife,
+    recommended when the clusters are few -- the same middle on the deletion residuals (I - H_SS)^-1 e_S of every
+    cluster (see influence()), times (G - 1) / G.
 
     The object must carry the factors (a fit with vcov_form="factors" or "both"; kernel="implicit", Neig="auto" and
     multi-GPU objects do). The numeric body is ONE call into the C ABI, `bigkrls_vcov_robust`. In the result
@@ -974,6 +971,8 @@ def robust_vcov(object: BigKRLS, type: str = "HC1", cluster=None, ctx: Optional[
     for key in ("vcov.est.c.cols", "vcov.est.fitted.cols", "path", "model_subfolder_name"):
         out.pop(key, None)
     out["vcov.est.Q"], out["vcov.est.w"] = Qout, wout
+    if out.get("vcov.fit.Q") is None:                          # the fit's own eigenvectors (no copy): influence() needs them
+        out["vcov.fit.Q"] = Qd
     out["vcov.est.c"] = out["vcov.est.fitted"] = None
     out["vcov.type"], out["vcov.clusters"] = type, plan["G"]
     out["_ctx"] = ctx
@@ -986,6 +985,121 @@ def robust_vcov(object: BigKRLS, type: str = "HC1", cluster=None, ctx: Optional[
             g = plan["y_sd"] / np.array([_sd(Xh[:, j - 1]) for j in me["which.derivatives"]])
             out["var.avgderivatives.std"] = var.ravel() / (g * g)
     return out
+
+
+def _unit_labels(cluster, n):
+    """cluster labels as _robust_plan maps them: any hashable labels numbered 0 .. G - 1 in order of appearance, at least
+    2 distinct. Returns (labels int64, the distinct labels in that order)."""
+    raw = list(cluster.tolist() if isinstance(cluster, np.ndarray) else cluster)
+    if len(raw) != n:
+        raise ValueError(f"cluster must have one label per row: {len(raw)} labels for N = {n}")
+    index = {}
+    labels = np.empty(n, dtype=np.int64)
+    for i, lab in enumerate(raw):
+        labels[i] = index.setdefault(lab, len(index))
+    if len(index) < 2:
+        raise ValueError("cluster must hold at least 2 distinct labels")
+    return labels, list(index)
+
+
+def _influence_plan(object, cluster, which_derivatives, newdata):
+    """Everything influence() decides before it touches the library: the class check, the factors and what goes with them
+    (robust_vcov's messages), the multi-GPU refusal, the units, the selected columns and newdata."""
+    if not isinstance(object, BigKRLS):
+        raise TypeError("Object not of class 'bigKRLS'")
+    if object.get("vcov.est.Q") is None or object.get("vcov.est.w") is None:
+        raise ValueError('the object has no vcov.est.Q / vcov.est.w: refit with vcov_form="factors" or "both"')
+    if "vcov.est.c.cols" in object or "rows" in object:
+        raise NotImplementedError("influence of a multi-GPU fit (sharded vcov.est.c.cols) is not supported; refit on one GPU")
+    rotated = object.get("vcov.type") is not None        # a robust_vcov() object: vcov.est.Q is the fit's Q times a rotation
+    Q = object.get("vcov.fit.Q") if rotated else object["vcov.est.Q"]
+    if Q is None:
+        raise ValueError("the object is a robust_vcov() result that no longer carries the fit's own eigenvectors "
+                         "(vcov.fit.Q): call influence() on the fit it was made from")
+    Xh = np.asfortranarray(np.asarray(object["X"], dtype=np.float64))
+    n, p = Xh.shape
+    k = len(np.asarray(object["vcov.est.w"]).ravel())
+    d = np.asarray(object["K.eigenvalues"], dtype=np.float64).ravel()
+    if tuple(getattr(Q, "shape", ())) != (n, k):
+        raise ValueError("vcov.est.Q must be nrow(X) x length(vcov.est.w)")
+    if k < 1 or d.size < k:
+        raise ValueError("the object's K.eigenvalues do not cover its vcov.est.w")
+    for key in ("lambda", "y", "yfitted.std", "coeffs", "sigma"):
+        if object.get(key) is None:
+            raise ValueError(f"the object has no {key}")
+    labels = names = None
+    if cluster is not None:
+        labels, names = _unit_labels(cluster, n)
+    if which_derivatives is None:
+        which_derivatives = object.get("which.derivatives")
+    if which_derivatives is None:
+        which = list(range(1, p + 1))
+    else:
+        which = [int(i) for i in np.atleast_1d(which_derivatives)]
+        if not which or not all(1 <= i <= p for i in which):
+            raise ValueError("which.derivatives must index columns of X")
+    nd = None
+    if newdata is not None:
+        nd = np.array(_as_host_matrix(newdata), dtype=np.float64, order="F")
+        if nd.ndim != 2 or nd.shape[1] != p:
+            raise ValueError("ncol(newdata) differs from ncol(X) from fitted bigKRLS object")
+        if nd.shape[0] < 1:
+            raise ValueError("newdata has no rows")
+        if not np.all(np.isfinite(nd)):
+            raise ValueError("newdata contains missing or infinite values")
+        isbin = np.array([np.unique(Xh[:, j]).size == 2 for j in range(p)])
+        _check_binary_newdata(Xh, nd, isbin, sorted(set(i - 1 for i in which)))
+    yv = np.ascontiguousarray(np.asarray(object["y"], dtype=np.float64).ravel())
+    resid = np.ascontiguousarray((yv - yv.mean()) / _sd(yv) - np.asarray(object["yfitted.std"], dtype=np.float64).ravel())
+    return {"Q": Q, "Xh": Xh, "n": n, "p": p, "k": k, "d": np.ascontiguousarray(d[:k]), "labels": labels, "names": names,
+            "G": None if labels is None else len(names), "which": which, "newdata": nd, "y": yv, "resid": resid}
+
+
+def influence(object: BigKRLS, cluster=None, which_derivatives=None, newdata=None, ctx: Optional[Context] = None) -> dict:
+    """Case- and cluster-deletion diagnostics of a fitted model, without refitting: which observations -- or, with
+    `cluster` (N hashable labels, at least 2 distinct), which clusters -- the result rests on. A unit is one observation,
+    or one cluster. Deleting a unit HOLDS THE BASIS (the kept eigenvectors of the full kernel), sigma, lambda AND THE
+    STANDARDISATION AT THEIR FULL-SAMPLE VALUES: with every eigenpair kept that is the refit on the remaining rows at the
+    same lambda; with a truncated basis it is the penalised least-squares refit on the same basis. The closed form is
+    et_S = (I - H_SS)^-1 e_S on the smoother H = Q diag(d / (d + lambda)) Q', one small system per unit, solved on the GPU
+    (`bigkrls_dev_deletion_residuals`); the numeric body is ONE call into the C ABI, `bigkrls_influence`. No counterpart
+    in the reference.
+
+    Returns a dict: "hat" (N leverages), "resid.deleted" and "fitted.deleted" (N: y minus / the prediction of every row
+    by the fit without its unit), "cooks" (U: ||yhat - yhat(-u)||^2 / (tr(H) e'e / (N - tr(H))) in standardised units),
+    "dfame" (U x |J|: AME_j of the full fit minus AME_j without unit u, in marginal_effects' units, on `newdata` --
+    default the training rows), "ame" (1 x |J|), "var.avgderivatives.jack" (1 x |J|: ((U - 1) / U) sum_u dfame^2, the
+    jackknife variance, times the reference's factor 2 for a binary column as in every var.avgderivatives; with clusters
+    it equals robust_vcov(type="CR3")'s var.avgderivatives), "R2.loo"
+    (1 - sum et^2 / sum ys^2), "units" (U), "unit.labels" (the distinct labels in order of appearance, or None),
+    "unit.sizes" and "which.derivatives".
+
+    The object must carry the factors (vcov_form="factors" or "both"; kernel="implicit" and Neig="auto" objects do). A
+    robust_vcov() object is accepted and uses the fit's ORIGINAL eigenvectors, which it carries as `vcov.fit.Q`. A
+    multi-GPU sharded object is refused. A unit whose block leverage reaches 1 raises a ValueError naming it."""
+    plan = _influence_plan(object, cluster, which_derivatives, newdata)
+    ctx = ctx or object.get("_ctx") or default_context()
+    n, p, k, G = plan["n"], plan["p"], plan["k"], plan["G"]
+    Q = plan["Q"]
+    Qd = Q if is_device_matrix(Q) else ctx.from_numpy(np.asarray(Q, dtype=np.float64))
+    U = n if G is None else G
+    which_arr = np.ascontiguousarray(plan["which"], dtype=np.int64)
+    nj = which_arr.size
+    nd, labels = plan["newdata"], plan["labels"]
+    coeffs = np.ascontiguousarray(np.asarray(object["coeffs"], dtype=np.float64).ravel())
+    hat, rdel, fdel, cooks = np.empty(n), np.empty(n), np.empty(n), np.empty(U)
+    dfame = np.empty((U, nj), dtype=np.float64, order="F")
+    ame, vjack, r2 = np.empty(nj), np.empty(nj), np.empty(1)
+    _call_native("bigkrls_influence", ctx.handle, plan["Xh"].ctypes.data, n, p, plan["y"].ctypes.data, coeffs.ctypes.data,
+                 float(object["sigma"]), which_arr.ctypes.data, nj, nd.ctypes.data if nd is not None else None,
+                 nd.shape[0] if nd is not None else n, Qd.ptr, Qd.ld, k, plan["d"].ctypes.data, float(object["lambda"]),
+                 plan["resid"].ctypes.data, labels.ctypes.data if labels is not None else None, G or 0,
+                 hat.ctypes.data, rdel.ctypes.data, fdel.ctypes.data, cooks.ctypes.data, dfame.ctypes.data,
+                 ame.ctypes.data, vjack.ctypes.data, r2.ctypes.data)
+    sizes = np.ones(n, dtype=np.int64) if labels is None else np.bincount(labels, minlength=G).astype(np.int64)
+    return {"hat": hat, "resid.deleted": rdel, "fitted.deleted": fdel, "cooks": cooks, "dfame": dfame, "ame": ame[None, :],
+            "var.avgderivatives.jack": vjack[None, :], "R2.loo": float(r2[0]), "units": U, "unit.labels": plan["names"],
+            "unit.sizes": sizes, "which.derivatives": plan["which"]}
 
 
 def partial_dependence(object: BigKRLS, which=None, grid=20, newdata=None, se: bool = True, correct_SE: bool = True,

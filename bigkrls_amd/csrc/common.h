@@ -66,7 +66,7 @@ struct bigkrls_ctx {
   bool side_is_main = false;   // BIGKRLS_NO_SIDE (diagnostics): side_stream is the main stream itself
   hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr, ev_pq = nullptr;
   // workspace slots: slot i is grown on demand and reused across calls
-  static constexpr int kSlots = 64;
+  static constexpr int kSlots = 72;
   void* ws[kSlots] = {nullptr};
   int64_t ws_bytes[kSlots] = {0};
   // pinned host scratch for small scalar read-backs
@@ -224,6 +224,13 @@ enum Slot {
   SLOT_KCG_GATHER = 61,    // ... the segment table, the sort permutation and the copies of A's rows, their norms and W in group order
   SLOT_KLB_INDEX = 62,     // kernel_loo_binsums: every selected column's row index list, the launches' segment tables and multi triples
   SLOT_KLB_PART = 63,      // ... partial sums of the bins that are cut into several segments
+  SLOT_DEL_INDEX = 64,     // deletion_residuals: the sorted rows, the per-class unit lists, the flag word, the leverages when the
+                           //     caller does not want them
+  SLOT_DEL_GENERAL = 65,   // ... the general route's unit: Q_S, Q_S diag(w), I - H_SS, its eigenvectors, four vectors
+  SLOT_DEL_W = 66,         // bigkrls_dev_deletion_residuals: the weights on the device
+  SLOT_INF_SMALL = 67,     // bigkrls_influence: standardised X and newdata, operands, g, w, w^2, e, et, the leverages, Cook's numerators
+  SLOT_INF_BIG = 68,       // ... C, S, Q'S, B = Q diag(g) Q'S, the units' sums of et B and their scores (k x G)
+  SLOT_DEL_WIDE = 69,      // deletion_residuals: I - H_SS of the units of 129 .. 256 rows of one launch (at most 128 x 514 KiB)
 };
 
 // BIGKRLS_VERBOSE: progress and timing lines on stderr (read at every call: it may be switched while the process runs)
@@ -443,6 +450,15 @@ int copy_matrix(bigkrls_ctx* ctx, const double* A, int64_t m, int64_t n, int64_t
 // e (n) on the device, the labels on the host. Deterministic (fixed-order segmented sums, no atomics).
 int cluster_scores(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* A, int64_t lda, const double* e,
                    const int64_t* h_cluster, int64_t G, double* S, int64_t lds);
+
+// ---- influence.hip ------------------------------------------------------------
+// d_et[S] = (I - H_SS)^-1 e[S] for the rows S of every unit, H = Q diag(w) Q': Q n x k (ldq), w (k) and e (n) on the
+// device, h_unit n host labels in [0, G) (nullptr: every row is its own unit). route 0: units of up to 256 rows in one
+// fused launch per size class, larger ones through eigen(); 1: every unit of two rows or more through eigen(). d_hat (n)
+// receives the leverages, d_S (k x G, lds) the scores Q_S' et_S; both may be null. Deterministic.
+int deletion_residuals(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* d_Q, int64_t ldq, const double* d_w,
+                       const double* d_e, const int64_t* h_unit, int64_t G, int route, double* d_et, double* d_hat,
+                       double* d_S, int64_t lds);
 
 // ---- solveforc.hip ------------------------------------------------------------
 int qty(bigkrls_ctx* ctx, const double* Q, int64_t n, int64_t k, int64_t ldq, const double* y,

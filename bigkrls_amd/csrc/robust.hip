@@ -8,6 +8,8 @@
 // the (vcov.est.Q, vcov.est.w) form everything after the fit already consumes. Clustered: M = S_c S_c' with
 // S_c[j, c] = sum_{i in cluster c} e_i Q_ij, the per-cluster score sums. The O(n) work is the weighted Gram matrix
 // (gram_weighted, csrc/gemm.hip) or the cluster scores (cluster_scores, below), the leverages and the rotation Q U.
+// Type 5, CR3 (the cluster jackknife): the same clustered middle on the deletion residuals (I - H_SS)^-1 e_S of every
+// cluster (deletion_residuals, csrc/influence.hip) in place of e.
 //
 // cluster_scores: the host makes a stable counting sort of the labels (rows of one cluster in their original order)
 // and cuts the sorted rows into pieces: maximal runs of one cluster inside one 64-row chunk. One wave takes a chunk
@@ -282,9 +284,11 @@ int bigkrls_vcov_robust(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* d_
     const char* b1 = b0 + ((k - 1) * ldqo + n) * (int64_t)sizeof(double);
     BK_REQUIRE(a1 <= b0 || b1 <= a0, "vcov_robust: Qout must not alias Q");
   }
-  BK_REQUIRE(type >= 0 && type <= 4, "vcov_robust: type must be 0 (classical), 1 (HC0), 2 (HC1), 3 (HC2) or 4 (HC3)");
+  BK_REQUIRE(type >= 0 && type <= 5 && (type != 5 || h_cluster),
+             "vcov_robust: type must be 0 (classical), 1 (HC0), 2 (HC1), 3 (HC2) or 4 (HC3), or 5 (CR3) with clusters");
   BK_REQUIRE(type == 0 || h_resid, "vcov_robust: the residuals are required for every type but 0");
-  BK_REQUIRE(!h_cluster || type == 1 || type == 2, "vcov_robust: clusters go with type 1 or 2 (the scale is the caller's)");
+  BK_REQUIRE(!h_cluster || type == 1 || type == 2 || type == 5,
+             "vcov_robust: clusters go with type 1 or 2 (the scale is the caller's) or 5");
   BK_REQUIRE(std::isfinite(lambda) && std::isfinite(scale) && scale >= 0.0, "vcov_robust: lambda and scale must be finite, scale >= 0");
   BK_REQUIRE(y_sd > 0.0 && std::isfinite(y_sd), "vcov_robust: y_sd must be positive");
   for (int64_t j = 0; j < k; ++j)
@@ -329,7 +333,9 @@ int bigkrls_vcov_robust(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* d_
 
   // ---- M --------------------------------------------------------------------------------------------------------
   if (h_cluster) {
-    BK_TRY(cluster_scores(ctx, n, k, d_Q, ldq, de, h_cluster, G, dSc, k));
+    // CR3, the cluster jackknife: CR0's machinery on the deletion residuals (csrc/influence.hip; dh is free here)
+    if (type == 5) BK_TRY(deletion_residuals(ctx, n, k, d_Q, ldq, ddg, de, h_cluster, G, 0, dh, nullptr, nullptr, 0));
+    BK_TRY(cluster_scores(ctx, n, k, d_Q, ldq, type == 5 ? dh : de, h_cluster, G, dSc, k));
     BK_TRY(gemm(ctx, 0, 1, k, k, G, 1.0, dSc, k, dSc, k, 0.0, dM, k));
   } else {
     if (lev) {

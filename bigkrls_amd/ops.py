@@ -250,6 +250,39 @@ def bClusterScores(A: DeviceMatrix, e, labels, G: int) -> DeviceMatrix:
     return out
 
 
+def bDeletionResiduals(Q: DeviceMatrix, w, e, labels=None, G: int = 0, route: int = 0, hat: bool = False,
+                       scores: bool = False):
+    """et (n, host): for the rows S of every unit, et[S] = (I - H_SS)^-1 e[S] with H = Q diag(w) Q' (Q n x k on the
+    device, w k weights, e n entries); labels: n integers in [0, G), or None: every row is its own unit. route 0: units of
+    up to 256 rows in the fused kernel, 1: the general route through the eigensolver (bigkrls_dev_deletion_residuals).
+    hat / scores: also the leverages (n, host) and the scores Q_S' et_S (a k x G DeviceMatrix). Returns et, or the tuple
+    (et, hat, scores) with None for what was not asked for. No counterpart in the reference."""
+    ctx = Q.ctx
+    n, k = Q.nrow, Q.ncol
+    wv = np.ascontiguousarray(w, dtype=np.float64).ravel()
+    if wv.size != k:
+        raise ValueError(f"bDeletionResiduals: w must have {k} entries")
+    de = e if isinstance(e, DeviceMatrix) else ctx.from_numpy(np.asarray(e, dtype=np.float64).ravel())
+    if de.nrow * de.ncol != n:
+        raise ValueError(f"bDeletionResiduals: e must be a vector with {n} entries")
+    lab = None
+    if labels is not None:
+        lab = np.ascontiguousarray(labels, dtype=np.int64).ravel()
+        if lab.size != n:
+            raise ValueError(f"bDeletionResiduals: labels must have {n} entries")
+    U = int(G) if lab is not None else n
+    det = ctx.empty(n, 1)
+    dhat = ctx.empty(n, 1) if hat else None
+    dS = ctx.empty(k, max(U, 1)) if scores else None
+    _lib.call("bigkrls_dev_deletion_residuals", ctx.handle, n, k, Q.ptr, Q.ld, wv.ctypes.data, de.ptr,
+              lab.ctypes.data if lab is not None else None, int(G), int(route), det.ptr,
+              dhat.ptr if hat else None, dS.ptr if scores else None, dS.ld if scores else 0)
+    et = det.to_numpy().ravel()
+    if not hat and not scores:
+        return et
+    return et, (dhat.to_numpy().ravel() if hat else None), dS
+
+
 # ---------------------------------------------------------------------------
 # eigen   (R/bigKRLS_Rcpp_functions.R:173-199)
 # ---------------------------------------------------------------------------

@@ -68,7 +68,9 @@ def read_big_matrix_text(path: str) -> np.ndarray:
         return np.asarray(m).reshape(-1, ncol)     # a single column or a single row is still a matrix
 
 _BIGKRLS_MATRICES = ["K", "X", "derivatives", "vcov.est.c", "vcov.est.fitted"]             # bLoad :337
-_FACTOR_MATRICES = ["vcov.est.Q"]      # bigKRLS(vcov_form="factors" / "both"): loaded when present, no NOTE when absent
+# bigKRLS(vcov_form="factors" / "both"), and the fit's own eigenvectors in a robust_vcov() object: loaded when present, no
+# NOTE when absent
+_FACTOR_MATRICES = ["vcov.est.Q", "vcov.fit.Q"]
 _PREDICTED_MATRICES = ["predicted", "se.pred", "vcov.est.pred", "newdata", "newdataK", "ytest"]   # :340
 _CLASSES = {"bigKRLS": BigKRLS, "bigKRLS_predicted": BigKRLSPredicted, "bigKRLS_CV": BigKRLSCV}
 

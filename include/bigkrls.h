@@ -103,7 +103,8 @@ int bigkrls_ctx_release_workspace(bigkrls_ctx* ctx);
  * bytes: 8 N K per probe, 8 N^2, 8 N^2), "vcov_syrk" (N (N + 1) K flops per matrix),
  * "kernel_loo_colsums" (u v n_cols exponentials), "kernel_loo_moments" (u v E exponentials, E per
  * row pair: one per chunk with a kind-0 or kind-1 entry plus one per kind-2 entry),
- * "kernel_loo_binsums" (u v n_cols exponentials). */
+ * "kernel_loo_binsums" (u v n_cols exponentials), "deletion_residuals" (one call of
+ * bigkrls_dev_deletion_residuals, 2 k sum_g m_g^2 flops over the units' sizes m_g). */
 int bigkrls_ctx_set_profile(bigkrls_ctx* ctx, int enable);
 int bigkrls_ctx_get_profile(bigkrls_ctx* ctx, const char* name, double* total_ms,
                             double* total_work, int64_t* launches);
@@ -344,6 +345,25 @@ int bigkrls_dev_gram_weighted(bigkrls_ctx* ctx, int64_t n, int64_t k, const doub
  * a cluster that spans several 64-row chunks (at most n / 64 + G pieces). */
 int bigkrls_dev_cluster_scores(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* A, int64_t lda, const double* e,
                                const int64_t* h_cluster, int64_t G, double* S, int64_t lds);
+
+/* Deletion residuals of a linear smoother H = Q diag(w) Q' (Q n x k column-major on the device, ldq >= n; h_w the k
+ * weights on the host): for the rows S of every unit, d_et[S] = (I - H_SS)^-1 d_e[S] -- the residuals of the rows of S
+ * under the fit without them, basis and weights held fixed. h_unit: n host labels in [0, G), any order (a label outside
+ * is BIGKRLS_EINVAL naming the row; an empty unit is allowed); NULL: every row is its own unit, d_et = d_e / (1 - h) on
+ * the leverages h_i = sum_j Q_ij^2 w_j (no solve; G is ignored). Units of one row take that formula with labels too,
+ * bitwise the NULL call's values. route 0: a unit of 2 .. 256 rows is one workgroup of a fused kernel (gather of the
+ * unit's rows, H_SS by the f64 MFMA, Cholesky and both triangular solves in place; four size classes, one launch each:
+ * up to 16, 64 and 128 rows with I - H_SS in LDS, up to 256 rows with it in 514 KiB of workspace per unit, at most 128
+ * units per launch), a larger one takes the general route: I - H_SS by bigkrls_dev_gemm, its eigenpairs by
+ * bigkrls_dev_eigen, et_S = V diag(1 / theta) V' e_S; 8 m^2 bytes per unit, at most 2^30, else BIGKRLS_EINVAL naming the unit before anything is allocated. route 1: every unit of two rows or more takes
+ * the general route. A pivot (smallest eigenvalue, leverage of a single row) that is not positive means a block
+ * leverage of 1 or more: BIGKRLS_EINVAL naming the first such unit, its size and the pivot column; nothing is written
+ * for that unit. d_hat (n, may be NULL): the leverages. d_S (k x G -- k x n without labels --, lds >= k, may be NULL):
+ * the scores S[:, g] = Q_S' et_S, by bigkrls_dev_cluster_scores. Fixed summation orders, no floating-point atomics: two
+ * calls give bitwise identical results. Profile name "deletion_residuals". */
+int bigkrls_dev_deletion_residuals(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* d_Q, int64_t ldq,
+                                   const double* h_w, const double* d_e, const int64_t* h_unit, int64_t G, int32_t route,
+                                   double* d_et, double* d_hat, double* d_S, int64_t lds);
 
 /* out[:,i] = A[:,i]*diag[i] (diag on device). */
 int bigkrls_dev_multdiag(bigkrls_ctx* ctx, const double* A, int64_t n, int64_t k, int64_t lda,
@@ -860,6 +880,9 @@ int bigkrls_group_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_
  *   3 HC2: e_i^2 / (1 - h_i),   4 HC3: e_i^2 / (1 - h_i)^2; a leverage >= 1 is BIGKRLS_EINVAL naming the row.
  * With h_cluster (n labels in [0, G), host; types 1 and 2 only) the middle is the clustered one,
  * Q' diag(omega) Q -> S S' with S = bigkrls_dev_cluster_scores(Q, e); scale carries the caller's G / (G - 1).
+ *   5 CR3 (h_cluster required): the cluster jackknife -- the clustered middle on the deletion residuals
+ *     et_S = (I - H_SS)^-1 e_S of every cluster (bigkrls_dev_deletion_residuals) in place of e; the caller passes
+ *     scale = (G - 1) / G. A cluster with a block leverage of 1 or more is BIGKRLS_EINVAL naming it.
  * Steps: M = Q' diag(omega) Q (bigkrls_dev_gram_weighted) or S S'; S = diag(g) M diag(g), symmetrised; its k
  * eigenpairs (theta, U) by bigkrls_dev_eigen, theta < 0 (rounding, or rank G < k) set to 0; Qout = Q U, wout =
  * sd(y)^2 scale theta (the scalar stays outside the eigenproblem, so Qout does not depend on it). Workspace beyond the outputs: 3 k^2 + 3 n + k G doubles; bigkrls_dev_gram_weighted's slabs
@@ -870,6 +893,33 @@ int bigkrls_group_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_
 int bigkrls_vcov_robust(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* d_Q, int64_t ldq, const double* h_d,
                         double lambda, const double* h_resid, double y_sd, double scale, int32_t type,
                         const int64_t* h_cluster, int64_t G, double* d_Qout, int64_t ldqo, double* h_wout);
+
+/* Case- and cluster-deletion diagnostics of a fitted model (no counterpart in the reference): which observations, or
+ * which clusters, the result rests on, without refitting. X, y, coeffs, sigma, h_which, newdata and u as in
+ * bigkrls_marginal_effects (validation, standardisation, binary columns and error messages are its own; h_newdata NULL:
+ * the training rows); d_Q (n x k, ldq >= n, device) and h_d (k, host) the kept eigenpairs of the fit, lambda its ridge
+ * parameter, h_resid (n, host) the residuals in standardised units; h_unit: n labels in [0, G) (host), or NULL: every row
+ * is its own unit. U = G, or n. With g = 1 / (d + lambda), w = d g, H = Q diag(w) Q': deleting the rows S of a unit with
+ * the basis Q, sigma, lambda and the standardisation HELD AT THEIR FULL-SAMPLE VALUES gives
+ *   et_S = (I - H_SS)^-1 e_S,   c - c(-S) = Q diag(g) (Q_S' et_S),   yhat - yhat(-S) = Q diag(w) (Q_S' et_S).
+ * Outputs (host; any may be NULL):
+ *   h_hat (n): the leverages h_i = sum_m Q_im^2 w_m;
+ *   h_resid_deleted, h_fitted_deleted (n): sd(y) et, and y - sd(y) et: every row's prediction by the fit without its unit;
+ *   h_cooks (U): sum_m (w_m s_mu)^2 / (tr(H) e'e / (n - tr(H))), s_u = Q_S' et_S, tr(H) = sum w;
+ *   h_dfame (U x |J| column-major): AME_j(full) - AME_j(without unit u) in bigkrls_marginal_effects' units, on newdata;
+ *   h_ame (|J|): AME_j of the full fit as s_j' c, s_j bigkrls_marginal_effects' column side;
+ *   h_var_jack (|J|): ((U - 1) / U) sum_u dfame[u, j]^2, the jackknife variance of the AME -- times the reference's
+ *         factor 2 for a binary column (src/bigderiv_v3.cpp:85), as bigkrls_marginal_effects' h_var: with clusters it is
+ *         the var.avgderivatives of bigkrls_vcov_robust's type 5;
+ *   h_r2_loo (scalar): 1 - sum et^2 / sum ys^2.
+ * Steps: bigkrls_dev_deletion_residuals (route 0) with the leverages and, for Cook's distances of clusters, the scores;
+ * S by bigkrls_dev_kernel_contract and the marginal effects' finalise, B = Q diag(g) (Q' S) by two bigkrls_dev_gemm,
+ * dfame = bigkrls_dev_cluster_scores(B, et)' (single rows: diag(et) B). Device memory O(n (p + |J|) + k U). */
+int bigkrls_influence(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y, const double* h_coeffs,
+                      double sigma, const int64_t* h_which, int64_t n_which, const double* h_newdata, int64_t u,
+                      const double* d_Q, int64_t ldq, int64_t k, const double* h_d, double lambda, const double* h_resid,
+                      const int64_t* h_unit, int64_t G, double* h_hat, double* h_resid_deleted, double* h_fitted_deleted,
+                      double* h_cooks, double* h_dfame, double* h_ame, double* h_var_jack, double* h_r2_loo);
 
 /* =============================================================================
  * Multi-GPU: one process per GPU, the collectives inside the library (the context's
