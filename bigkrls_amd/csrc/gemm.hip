@@ -2141,6 +2141,7 @@ int kernel_block(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda, cons
   if (u == 0 || v == 0) return BIGKRLS_OK;
   BK_REQUIRE(A && B && out, "kernel_block: null pointer");
   BK_REQUIRE(lda >= u && ldb >= v, "kernel_block: leading dimension of A or B too small");
+  BK_REQUIRE(ldo >= u, "kernel_block: leading dimension of out too small");
   const bool sym = A == B && u == v && lda == ldb && diag_shift == 0;
   // from here on A and B are the centred copies (the same buffer when they were the same buffer)
   CentredOperands co;

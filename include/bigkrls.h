@@ -199,7 +199,8 @@ int bigkrls_neffective(const double* X, int64_t n, int64_t p, double* neff);
  * set to exactly 1 (column block [c0,c1) of the symmetric n x n kernel:
  * A = X, B = X + c0, diag_shift = c0). Pass diag_shift = -1 for predict.
  * A and B need not be centred: both are copied with the column means of A subtracted (extra device memory
- * O((u + v) p), no host synchronisation) before |a|^2 + |b|^2 - 2 a.b is formed; lda >= u and ldb >= v. A block B
+ * O((u + v) p), no host synchronisation) before |a|^2 + |b|^2 - 2 a.b is formed; lda >= u, ldb >= v and ldo >= u, else
+ * BIGKRLS_EINVAL. A block B
  * that lies inside A (same leading dimension) reads the copy of A, so every column block of one X sees the same rows. */
 int bigkrls_dev_kernel_block(bigkrls_ctx* ctx, const double* A, int64_t u, int64_t lda,
                              const double* B, int64_t v, int64_t ldb, int64_t p, double sigma,
