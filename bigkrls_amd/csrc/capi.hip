@@ -574,6 +574,14 @@ int bigkrls_dev_gemm(bigkrls_ctx* ctx, int ta, int tb, int64_t m, int64_t n, int
   return gemm(ctx, ta, tb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc);
 }
 
+// Test entry of gemm_thin (bigkrls_dev_gemm's arguments and force_bn = 32, 64, 128 or 0: the rule). Development only:
+// exported, but not part of include/bigkrls.h; tests/test_gpu_gemm_thin.py declares its arguments itself.
+int bigkrls_dev_gemm_thin(bigkrls_ctx* ctx, int ta, int tb, int64_t m, int64_t n, int64_t k, double alpha, const double* A,
+                          int64_t lda, const double* B, int64_t ldb, double beta, double* C, int64_t ldc, int force_bn) {
+  BK_TRY(check_ctx(ctx));
+  return gemm_thin(ctx, ta, tb, m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, force_bn);
+}
+
 int bigkrls_dev_gemm_modulated(bigkrls_ctx* ctx, int64_t m, int64_t n, int64_t k, const double* A, int64_t lda,
                                const double* r, const double* t, const double* s, const double* B, int64_t ldb,
                                double* C, int64_t ldc) {

@@ -299,6 +299,10 @@ class PinnedStage {
 int gemm(bigkrls_ctx* ctx, int ta, int tb, int64_t m, int64_t n, int64_t k, double alpha,
          const double* A, int64_t lda, const double* B, int64_t ldb, double beta, double* C,
          int64_t ldc);
+// gemm() bit for bit -- the same kernels over the same k slabs -- with the tile width chosen from the shape for products
+// of few tiles and a long contraction (thin_plan, csrc/splitplan.h). force_bn = 32, 64 or 128: that width (development).
+int gemm_thin(bigkrls_ctx* ctx, int ta, int tb, int64_t m, int64_t n, int64_t k, double alpha, const double* A, int64_t lda,
+              const double* B, int64_t ldb, double beta, double* C, int64_t ldc, int force_bn = 0);
 // C (m x n, ldc) = (A o (r 1' + t s')) B: A m x k (lda) and B k x n (ldb) not transposed, r and t m entries, s k entries,
 // all on the device; C is overwritten. A is modulated in registers on its way to LDS, the modulated copy never stored.
 // gemm()'s tiles and deterministic split-K choice; with r = 1, t = 0 bitwise gemm(0, 0, .., 1.0, .., 0.0, ..).

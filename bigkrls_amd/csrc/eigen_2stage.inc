@@ -4590,19 +4590,23 @@ int bt1_precompute(bigkrls_ctx* ctx, const double* W, int n, const double* taus1
   return BIGKRLS_OK;
 }
 
-// Z <- Q1 Z with the merged block reflectors (W1, W2: LT x nv scratch each)
+// Z <- Q1 Z with the merged block reflectors (W1, W2: LT x nv scratch each). The three products of a step have few
+// tiles and long k loops: gemm_thin runs them with the tile width its plan chooses from the shape, bitwise as gemm().
+// (development: BIGKRLS_BT1_TILE=128|64|32 fixes the width, read per call)
 int back_transform_stage1_grouped(bigkrls_ctx* ctx, const Bt1Plan& plan, const double* Vstore, const double* Tstore,
                                   double* Z, int64_t ldz, int nv, double* W1, double* W2) {
   const int LT = plan.LT;
+  const char* tile_env = getenv("BIGKRLS_BT1_TILE");
+  const int bn = tile_env ? atoi(tile_env) : 0;
   for (int q = (int)plan.ng() - 1; q >= 0; --q) {
     const Bt1Group& gr = plan.groups[q];
     const int w = S2_B * gr.g;
     const double* Vb = Vstore + gr.voff;
     const double* Tb = Tstore + (int64_t)q * LT * LT;
     double* Zs = Z + (gr.k0 + S2_B);
-    BK_TRY(gemm(ctx, 1, 0, w, nv, gr.m0, 1.0, Vb, gr.m0, Zs, ldz, 0.0, W1, LT));
-    BK_TRY(gemm(ctx, 0, 0, w, nv, w, 1.0, Tb, LT, W1, LT, 0.0, W2, LT));
-    BK_TRY(gemm(ctx, 0, 0, gr.m0, nv, w, -1.0, Vb, gr.m0, W2, LT, 1.0, Zs, ldz));
+    BK_TRY(gemm_thin(ctx, 1, 0, w, nv, gr.m0, 1.0, Vb, gr.m0, Zs, ldz, 0.0, W1, LT, bn));
+    BK_TRY(gemm_thin(ctx, 0, 0, w, nv, w, 1.0, Tb, LT, W1, LT, 0.0, W2, LT, bn));
+    BK_TRY(gemm_thin(ctx, 0, 0, gr.m0, nv, w, -1.0, Vb, gr.m0, W2, LT, 1.0, Zs, ldz, bn));
   }
   return BIGKRLS_OK;
 }

@@ -650,9 +650,12 @@ __global__ void splitk_reduce_kernel(const double* __restrict__ partial, int spl
 // The deterministic split-K choice (csrc/splitplan.h) of a launch of ntile tiles under one of the three models.
 // (development: BIGKRLS_GEMM_SPLITS=<n> overrides the count for products with K >= 16384 under the plain model,
 //  tools/kb_shape_probe.hip)
-static SplitPlan gemm_split_plan(const SplitModel& md, const GemmOperands& g, int ntile) {
+static int gemm_env_splits() {
   static const int env_splits = [] { const char* e = getenv("BIGKRLS_GEMM_SPLITS"); return e ? atoi(e) : 0; }();
-  return split_plan(md, ntile, g.M, g.N, g.K, BK, env_splits);
+  return env_splits;
+}
+static SplitPlan gemm_split_plan(const SplitModel& md, const GemmOperands& g, int ntile) {
+  return split_plan(md, ntile, g.M, g.N, g.K, BK, gemm_env_splits());
 }
 
 // GEMMs issued on the look-ahead stream run concurrently with main-stream GEMMs: own partial buffer
@@ -706,13 +709,23 @@ static int launch_splitk_reduce(bigkrls_ctx* ctx, const double* partial, int spl
 // One launch of a plain kernel of tile width BN -- gemm_kernel<TA, TB, BN> (pre: alpha, beta) or a modulated kernel
 // (TA = TB = false; pre: GemmMod, or GemmMod and GemmMod2) -- over the split plan's (tiles, splits) grid, and for more than
 // one split the slabs' reduction C = alpha (sum) + beta C.
+// (launch_gemm_planned: the same under a plan made elsewhere -- gemm_thin's, whose slabs are those of another width)
+template <bool TA, bool TB, int BN, class Kern, class... Pre>
+static int launch_gemm_planned(bigkrls_ctx* ctx, const GemmOperands& g, Kern kern, const SplitPlan& plan, double alpha,
+                               double beta, double* C, int64_t ldc, const Pre&... pre);
 template <bool TA, bool TB, int BN, class Kern, class... Pre>
 static int launch_gemm_splitk(bigkrls_ctx* ctx, const GemmOperands& g, Kern kern, double alpha, double beta, double* C,
                               int64_t ldc, const Pre&... pre) {
+  const int ntile = ((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
+  const SplitPlan plan = gemm_split_plan(split_model_gemm(gemm_occ<TA, TB, BN>()), g, ntile);
+  return launch_gemm_planned<TA, TB, BN>(ctx, g, kern, plan, alpha, beta, C, ldc, pre...);
+}
+template <bool TA, bool TB, int BN, class Kern, class... Pre>
+static int launch_gemm_planned(bigkrls_ctx* ctx, const GemmOperands& g, Kern kern, const SplitPlan& plan, double alpha,
+                               double beta, double* C, int64_t ldc, const Pre&... pre) {
   const int tiles_m = (g.M + BM - 1) / BM;
   const int tiles_n = (g.N + BN - 1) / BN;
   const int ntile = tiles_m * tiles_n;
-  const SplitPlan plan = gemm_split_plan(split_model_gemm(gemm_occ<TA, TB, BN>()), g, ntile);
   double* partial = nullptr;   // the slabs of the split-K partials (splits x M x N doubles); nullptr for a single split
   if (plan.splits > 1) {
     void* p = nullptr;
@@ -748,6 +761,34 @@ int gemm(bigkrls_ctx* ctx, int ta, int tb, int64_t m, int64_t n, int64_t k, doub
     if (ta && !tb) return launch_gemm<true, false, BN>(ctx, g, alpha, beta, C, ldc);
     return launch_gemm<true, true, BN>(ctx, g, alpha, beta, C, ldc);
   });
+}
+
+// gemm() for a product of few tiles and a long contraction (the stage-1 back-transform's): the same kernels over the same
+// k slabs -- thin_plan() (csrc/splitplan.h) keeps gemm()'s (splits, k_chunk) -- with the tile width thin_plan chooses from
+// the shape, so that more and shorter workgroups share the arithmetic. Same partial slot, same reduction; bitwise gemm().
+// force_bn = 32, 64 or 128: that width (development and tests), else the rule.
+template <bool TA, bool TB>
+static int launch_gemm_thin(bigkrls_ctx* ctx, const GemmOperands& g, int force_bn, double alpha, double beta, double* C,
+                            int64_t ldc) {
+  const int occ = with_bn(g.N, [](auto bn) { return gemm_occ<TA, TB, decltype(bn)::value>(); });
+  const ThinPlan tp = thin_plan(TA, TB, g.M, g.N, g.K, BM, BK, occ, gemm_env_splits(), force_bn);
+  const SplitPlan plan{tp.splits, tp.k_chunk};
+  if (tp.bn_exec == 32) return launch_gemm_planned<TA, TB, 32>(ctx, g, gemm_kernel<TA, TB, 32>, plan, alpha, beta, C, ldc, alpha, beta);
+  if (tp.bn_exec == 64) return launch_gemm_planned<TA, TB, 64>(ctx, g, gemm_kernel<TA, TB, 64>, plan, alpha, beta, C, ldc, alpha, beta);
+  return launch_gemm_planned<TA, TB, 128>(ctx, g, gemm_kernel<TA, TB, 128>, plan, alpha, beta, C, ldc, alpha, beta);
+}
+
+int gemm_thin(bigkrls_ctx* ctx, int ta, int tb, int64_t m, int64_t n, int64_t k, double alpha, const double* A, int64_t lda,
+              const double* B, int64_t ldb, double beta, double* C, int64_t ldc, int force_bn) {
+  BK_TRY(require_dims("gemm_thin", m, n, k));
+  if (m == 0 || n == 0) return BIGKRLS_OK;
+  if (k == 0 || alpha == 0.0) return beta == 1.0 ? BIGKRLS_OK : scale_matrix(ctx, C, ldc, m, n, beta);
+  BK_REQUIRE(A && B && C, "gemm_thin: null pointer");
+  GemmOperands g{A, B, lda, ldb, (int)m, (int)n, (int)k, nullptr, ctx->gemm_run_if};
+  if (!ta && !tb) return launch_gemm_thin<false, false>(ctx, g, force_bn, alpha, beta, C, ldc);
+  if (!ta && tb) return launch_gemm_thin<false, true>(ctx, g, force_bn, alpha, beta, C, ldc);
+  if (ta && !tb) return launch_gemm_thin<true, false>(ctx, g, force_bn, alpha, beta, C, ldc);
+  return launch_gemm_thin<true, true>(ctx, g, force_bn, alpha, beta, C, ldc);
 }
 
 // ---------------------------------------------------------------------------

@@ -56,4 +56,48 @@ inline SplitPlan split_plan(const SplitModel& md, int ntile, int M, int N, int K
   return SplitPlan{splits, k_chunk};
 }
 
+// ---- thin products: the executed tile width apart from the split plan ------------------------------------------------
+// gemm() ties the tile width to the column count (N <= 32: 32, N <= 64: 64, else 128). A product of few tiles and a long
+// contraction per tile -- the three products of a step of the stage-1 back-transform: (512 x m0)(m0 x 250) split over K,
+// 512 x 512 x 250 and m0 x 512 x 250 -- then runs as a handful of workgroups that each walk a long k loop while most of
+// the GPU stands empty. gemm_thin() (csrc/gemm.hip) runs such a product with narrower tiles: every accumulator receives
+// the same MFMA sequence over k whatever the width, and the slabs of a split product stay those of gemm(), so the result
+// is gemm()'s bit for bit.
+struct ThinPlan { int bn_exec, splits, k_chunk; };
+
+// gemm()'s tile width of an N-column result
+inline int thin_base_bn(int N) { return N <= 32 ? 32 : (N <= 64 ? 64 : 128); }
+
+// The width rule, a function of the shape alone: a launch that at gemm()'s width has fewer workgroups (tiles * splits)
+// than the GPU holds at once (`resident`) runs 32 wide, provided the k loop of a workgroup (K per split) is at least
+// thin_min_k long; every other launch keeps gemm()'s width. Measured alone on the GPU (tools/bt1_thin_bench.py,
+// profiles/bt1/sweep.txt; us at 128 / 64 / 32 wide): Tb W1 (8 workgroups at 128) 84 / 47 / 33 at every m0;
+// Zs -= Vb W2, m0 = 20 000 (314): 151 / 124 / 116, 10 000: 93 / 79 / 67, 2 000: 89 / 49 / 34; Vb' Zs with its reduction,
+// m0 = 20 000: 143 / 138 / 146, 5 000: 58 / 56 / 51, 2 000: 56 / 36 / 29; the three in order 371 / 300 / 288,
+// 243 / 193 / 177 (10 000), 228 / 132 / 93 (2 000). A 32-wide workgroup alone on a CU is bound by latency (33 us against the
+// 22 us a quarter of the 128-wide tile's 89 us would be) and two of them on a CU overlap, so 32 also wins where it makes
+// several rounds; 64 wins single shapes by a few us (m0 = 15 000: 81 against 93) and is left to the development switch.
+// thin_min_k is split_plan's own floor of a slab (it never cuts K below 256): shorter loops were not measured.
+constexpr int thin_min_k = 256;
+inline int thin_width(int base_bn, int tiles_m, int N, int splits, int k_per_split, int resident) {
+  const long long wgs = (long long)tiles_m * ((N + base_bn - 1) / base_bn) * splits;
+  return (k_per_split >= thin_min_k && wgs < resident) ? 32 : base_bn;
+}
+
+// (splits, k_chunk): split_plan() under the plain model over gemm()'s own tiling of the M x N result, whatever width
+// executes -- the slab boundaries decide the bits (that tiling is the 128-wide one: up to N = 64 either has one tile
+// column). occ: workgroups per CU of gemm()'s kernel for this shape; bm: the
+// tile height; force_bn = 32, 64 or 128 sets the executed width (development), anything else: the rule.
+inline ThinPlan thin_plan(bool /*ta*/, bool /*tb*/, int M, int N, int K, int bm, int bk, int occ, int override_splits,
+                          int force_bn = 0) {
+  const int base = thin_base_bn(N);
+  const int tiles_m = (M + bm - 1) / bm;
+  const SplitModel md = split_model_gemm(occ);
+  const SplitPlan sp = split_plan(md, tiles_m * ((N + base - 1) / base), M, N, K, bk, override_splits);
+  const int bn = (force_bn == 32 || force_bn == 64 || force_bn == 128)
+               ? force_bn
+               : thin_width(base, tiles_m, N, sp.splits, std::min(K, sp.k_chunk), md.resident);
+  return ThinPlan{bn, sp.splits, sp.k_chunk};
+}
+
 }  // namespace bk
