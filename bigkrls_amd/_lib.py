@@ -99,6 +99,7 @@ SIGNATURES = {
     "bigkrls_dev_kernel_loo_colsums": [vp, vp, i64, i64, vp, i64, i64, i64, f64, vp, i64, vp, i64],
     "bigkrls_dev_kernel_loo_moments": [vp, vp, i64, i64, vp, i64, i64, i64, f64, vp, i64, vp, i64],
     "bigkrls_dev_kernel_loo_binsums": [vp, vp, i64, i64, vp, i64, i64, i64, f64, vp, i64, vp, vp, vp, i64],
+    "bigkrls_dev_shapley_weights": [vp, vp, i64, vp, i64, vp, i64, i64, f64, vp, i64, vp],
     "bigkrls_dev_quadform_diag": [vp, i64, i64, vp, i64, vp, i64, vp],
     "bigkrls_dev_rowsumsq_weighted": [vp, i64, i64, vp, i64, vp, vp],
     "bigkrls_dev_gemm": [vp, C.c_int, C.c_int, i64, i64, i64, f64, vp, i64, vp, i64, f64, vp, i64],
@@ -149,6 +150,8 @@ SIGNATURES = {
                                    vp, vp, vp],
     "bigkrls_accumulated_effects": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, vp, vp, vp, vp, i64, i64, vp, f64,
                                     vp, vp, vp],
+    "bigkrls_shapley_effects": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, vp, i64, vp, vp, i64, i64, vp, f64, i64,
+                                vp, vp, vp],
     "bigkrls_conditional_effects": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp,
                                     vp],
     "bigkrls_group_effects": [vp, vp, i64, i64, vp, vp, f64, vp, i64, vp, i64, vp, i64, vp, vp, i64, i64, vp, vp, vp,

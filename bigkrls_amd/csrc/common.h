@@ -231,6 +231,9 @@ enum Slot {
   SLOT_INF_SMALL = 67,     // bigkrls_influence: standardised X and newdata, operands, g, w, w^2, e, et, the leverages, Cook's numerators
   SLOT_INF_BIG = 68,       // ... C, S, Q'S, B = Q diag(g) Q'S, the units' sums of et B and their scores (k x G)
   SLOT_DEL_WIDE = 69,      // deletion_residuals: I - H_SS of the units of 129 .. 256 rows of one launch (at most 128 x 514 KiB)
+  SLOT_SHAP_TABLE = 70,    // shapley_weights: the columns in player order
+  SLOT_SHAP_SMALL = 71,    // bigkrls_shapley_effects: standardised X, newdata and background, c, w, the values, variances, background
+                           //     fits; behind them one row block of W (at most 1 GiB) and its product with Q (variance from the factors)
 };
 
 // BIGKRLS_VERBOSE: progress and timing lines on stderr (read at every call: it may be switched while the process runs)
@@ -463,6 +466,14 @@ int cluster_scores(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* A, int6
 int deletion_residuals(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* d_Q, int64_t ldq, const double* d_w,
                        const double* d_e, const int64_t* h_unit, int64_t G, int route, double* d_et, double* d_hat,
                        double* d_S, int64_t lds);
+
+// ---- shapley.hip --------------------------------------------------------------
+// W (u M x n, ldw): the weights of the exact interventional Shapley values on the coefficients, row r M + m = explained
+// row r of Z (u x p), player m; X (n x p) the training rows, Bg (B x p) the background rows, h_players (host, p labels in
+// [0, M); nullptr: one player per column). All in the same (standardised) units; see include/bigkrls.h. Deterministic.
+int shapley_weights(bigkrls_ctx* ctx, const double* Z, int64_t u, int64_t ldz, const double* X, int64_t n, int64_t ldx,
+                    const double* Bg, int64_t B, int64_t ldb, int64_t p, double sigma, const int64_t* h_players,
+                    int64_t M, double* W, int64_t ldw);
 
 // ---- solveforc.hip ------------------------------------------------------------
 int qty(bigkrls_ctx* ctx, const double* Q, int64_t n, int64_t k, int64_t ldq, const double* y,

@@ -137,6 +137,29 @@ def bKernelLooBinsums(A: DeviceMatrix, B: DeviceMatrix, sigma: float, cols, labe
     return out
 
 
+def bShapleyWeights(Z: DeviceMatrix, X: DeviceMatrix, Bg: DeviceMatrix, sigma: float, players=None) -> DeviceMatrix:
+    """W (nrow(Z) M x nrow(X)): the weights of the exact interventional Shapley values on the coefficients of a Gaussian-
+    kernel fit, W[r M + m, i] for explained row r of Z, player m and training row i of X, against the background rows Bg
+    (bigkrls_dev_shapley_weights; all three in the same units): W[r M + m, :] c is the Shapley value of player m at Z[r, :]
+    for the function x -> sum_i c_i K(x, X_i). players: ncol labels in [0, M), the player of every column (every player
+    owns at least one column, M <= 128); None: one player per column. No counterpart in the reference."""
+    ctx = Z.ctx
+    if Z.ncol != X.ncol or Bg.ncol != X.ncol:
+        raise ValueError("bShapleyWeights: column counts of Z, X and Bg differ")
+    p = X.ncol
+    if players is None:
+        lab, M = None, p
+    else:
+        lab = np.ascontiguousarray(players, dtype=np.int64).ravel()
+        if lab.size != p:
+            raise ValueError(f"bShapleyWeights: players must have {p} entries")
+        M = int(lab.max()) + 1 if lab.size else 0
+    out = ctx.empty(Z.nrow * max(M, 1), X.nrow)
+    _lib.call("bigkrls_dev_shapley_weights", ctx.handle, Z.ptr, Z.nrow, X.ptr, X.nrow, Bg.ptr, Bg.nrow, p, float(sigma),
+              lab.ctypes.data if lab is not None else None, M, out.ptr)      # packed: a DeviceMatrix has ld == nrow
+    return out
+
+
 def bKernelLooMoments(A: DeviceMatrix, B: DeviceMatrix, sigma: float, entries) -> DeviceMatrix:
     """out (nrow(B) x len(entries)) for entries (kind, c, j) with 0-based columns: out[l, e] = sum_i wgt
     exp(-max(d2(i,l) - dc^2 - [kind = 2] dj^2, 0) / sigma) with dc = A[i,c] - B[l,c], dj = A[i,j] - B[l,j]; kind 0: wgt = 1

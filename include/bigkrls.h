@@ -263,6 +263,31 @@ int bigkrls_dev_kernel_loo_binsums(bigkrls_ctx* ctx, const double* A, int64_t u,
                                    int64_t n_cols, const int64_t* h_labels, const int64_t* h_nbins, double* out,
                                    int64_t ldo);
 
+/* The weights of exact interventional Shapley values on the coefficients of a Gaussian-kernel fit. The p columns are
+ * partitioned into M players: h_players (host) holds the player of column l, an integer in [0, M); NULL: one player per
+ * column (M must equal p). Every player owns at least one column and M <= 128. Z (u x p) holds the explained rows,
+ * X (n x p) the training rows, Bg (B x p) the background rows, all on the device, in the same units and PACKED: column-
+ * major matrices of their own, a column every `rows` doubles (this entry takes no leading dimensions). For a
+ * triple (r, b, i) player m has the factors A_m = exp(-sum_{l in m} (Z[r,l] - X[i,l])^2 / sigma) inside a coalition and
+ * B_m = exp(-sum_{l in m} (Bg[b,l] - X[i,l])^2 / sigma) outside it, and
+ *   W[r M + m, i] = (1/B) sum_b (A_m - B_m) sum_g w_g prod_{l != m} (B_l + t_g (A_l - B_l)),
+ * (t_g, w_g) the Gauss-Legendre rule on [0,1] with ceil(M/2) nodes, which integrates the Shapley weights of this product
+ * game exactly: W[r M + m, :] c is the Shapley value of player m for the function x -> sum_i c_i K(x, X_i) at Z[r,:],
+ * its value function the mean over the background rows of the function at "Z[r,:] on the coalition's columns, the
+ * background row elsewhere". W is (u M) x n, column-major and packed as well; its ROW ORDER is explained row by explained
+ * row, the M players of a row adjacent (row r M + m), a training row per column. The products without player m are
+ * prefix times suffix products, never quotients: factors that underflow to 0 give finite weights. A player whose columns
+ * agree between Z[r,:] and every background row has the weight exactly 0.0. One thread per training row and a few
+ * explained rows, the per-player arrays in registers for M <= 32 (buckets 8, 16, 20, 24, 32) and in LDS above (64, 128); the
+ * background rows pass through LDS in chunks, so p <= 2048. Sums over the background rows and the nodes run in a fixed
+ * order inside one thread: no atomics, no partial sums, and an entry depends on its own explained row, its training row
+ * and the background only -- a row block of Z gives bitwise the rows of the whole call, and two calls give bitwise
+ * identical results. Extra device memory: 4 p bytes. BIGKRLS_EINVAL naming the argument: a player index out of
+ * range, a player without a column, M over the cap, B < 1. Profile name
+ * "shapley_weights". */
+int bigkrls_dev_shapley_weights(bigkrls_ctx* ctx, const double* Z, int64_t u, const double* X, int64_t n, const double* Bg,
+                                int64_t B, int64_t p, double sigma, const int64_t* h_players, int64_t M, double* W);
+
 /* Fused leave-out moments: out (v x n_entries, ldo >= v). h_entries (host) is 3 x n_entries column-major, entry e =
  * (kind, c, j) with 0-based columns, and with dc = A[i,c] - B[l,c], dj = A[i,j] - B[l,j], d2 = ||A_i - B_l||^2:
  *   out[l, e] = sum_i wgt exp(-max(d2 - dc^2 - [kind = 2] dj^2, 0) / sigma)
@@ -816,6 +841,41 @@ int bigkrls_accumulated_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, 
                                 const double* h_newdata, int64_t u, const double* h_edges, const int64_t* h_grid_off,
                                 const double* d_vcov_c, const double* d_Q, int64_t ldq, int64_t k, const double* h_w,
                                 double neffective, double* h_ale, double* h_se, double* h_cov);
+
+/* Shapley effects: how much of one row's prediction is due to each predictor -- exact interventional Shapley values of
+ * the fitted prediction, with standard errors (no counterpart in the reference).
+ * Players: the columns of X are partitioned into M players, h_players[l] in {0 .. M-1} the player of column l (host, p
+ * labels; NULL: one player per column, M = p); every player owns at least one column, M <= 128. Grouping makes a set of
+ * dummies count as one feature.
+ * Value function: against the background sample h_background (B x p, host, column-major),
+ *   v(S; x) = (1/B) sum_b f(x on the columns of the players in S, b elsewhere),
+ * f the fitted prediction in original units; all rows are standardised with the TRAINING means and sds, as
+ * bigkrls_predict does. The explained rows are h_newdata (u x p); NULL: the training rows (u is then ignored).
+ * Result: with A_m / B_m the factors of bigkrls_dev_shapley_weights in standardised units,
+ *   phi_m(x_r) = (sd(y)/B) sum_b sum_i c_i (A_m - B_m) sum_g w_g prod_{l != m} (B_l + t_g (A_l - B_l)) = sd(y) W[r M + m, :] c
+ *   h_phi      = phi, u x M with the players of a row adjacent (h_phi[r M + m]), original units of y,
+ *   h_baseline = the mean over b of bigkrls_predict at the background rows (one value),
+ *   h_se       = the standard errors of phi in h_phi's order (may be NULL).
+ * Efficiency: sum_m phi_m(x_r) = bigkrls_predict(x_r) - baseline.
+ * Variance: Var phi_m(x_r) = f sd(y)^2 W[r M + m, :] V W[r M + m, :]' with V = vcov.est.c / sd(y)^2, the covariance of the
+ * coefficients in standardised units -- d_vcov_c and the factors are the fit's vcov.est.c itself, which carries sd(y)^2 --
+ * and f bigkrls_predict's factor for neffective > 0 (the correct_SE convention of bigkrls_partial_dependence). It is
+ * conditional on X and on the background rows. vcov.est.c comes as the n x n matrix or as its factors, at most one of
+ * them (else BIGKRLS_EINVAL); with neither, h_se must be NULL. The kernel matrix is never needed.
+ * The explained rows are taken in blocks of b rows: the largest b with 8 b M n <= 2^30 bytes, at least 1; block_rows > 0
+ * overrides it. Per block: bigkrls_dev_shapley_weights, phi = W c (bigkrls_dev_gemv), and T = W Q
+ * (bigkrls_dev_gemm) with bigkrls_dev_rowsumsq_weighted, or bigkrls_dev_quadform_diag from the matrix. Every entry of W
+ * is bitwise independent of b. h_phi and h_se of a row are bitwise independent of b as long as the products split alike
+ * for both block shapes (bigkrls_dev_gemv's column splits, bigkrls_dev_gemm's k splits: one each for n <= 64), and agree
+ * to rounding otherwise. Two calls with the same b are bitwise identical.
+ * BIGKRLS_EINVAL naming the argument: a player index out of range, an empty player, M over the cap of 128, B < 1,
+ * newdata or background with missing or infinite values, p > 2048. Extra device memory: the block and T, and
+ * 8 ((n + u + B) p + n + k + 2 u M + B) bytes of vectors. */
+int bigkrls_shapley_effects(bigkrls_ctx* ctx, const double* h_X, int64_t n, int64_t p, const double* h_y,
+                            const double* h_coeffs, double sigma, const int64_t* h_players, int64_t M,
+                            const double* h_newdata, int64_t u, const double* h_background, int64_t B,
+                            const double* d_vcov_c, const double* d_Q, int64_t ldq, int64_t k, const double* h_w,
+                            double neffective, int64_t block_rows, double* h_phi, double* h_se, double* h_baseline);
 
 /* Conditional effects: the marginal effect of x_j along a moderator x_k, with its covariance over the grid (no
  * counterpart in the reference). h_pairs is 2 x m column-major, 1-based: pair i = (effect j, moderator k). For every pair
