@@ -3775,14 +3775,20 @@ int dist_s1_put(bigkrls_ctx* ctx, int64_t n, int64_t k, const double* strip, int
   return copy_matrix(ctx, strip, n - k, ncols, n - k, ds->ops.W + k + k * n, n);
 }
 
-// One stage-1 panel factorisation on its own (exposed for tests): Stage1::panel_qr and build_T, i.e. head -> Householder
-// kernel's slot -> tail (the one-kernel form under BIGKRLS_PQ=fused), on the context's otherwise idle stream with a
-// workspace of its own. The panel is block column 0 of an imagined (m + 64)-row matrix whose sub-diagonal block is P.
+// One stage-1 panel factorisation on its own (exposed for tests): Stage1::panel_qr and build_T, whichever route they take
+// for a panel of m rows under the current BIGKRLS_PQ and BIGKRLS_S1_TPQ -- head -> Householder kernel's slot -> tail, the
+// one-kernel form, the Householder kernel alone (every panel of fewer than 128 rows), one launch per column -- on the
+// context's otherwise idle stream with a workspace of its own. The panel is block column 0 of an imagined (m + 64)-row
+// matrix with leading dimension ld whose sub-diagonal block is P: the kernels address P + (row >= 0) + column * ld only.
 int panel_factor(bigkrls_ctx* ctx, double* P, int64_t ld, int64_t m, double* Vw, double* V, double* T, double* Tfold,
                  double* tau, int32_t* h_fallback) {
   const int b = S2_B;
-  BK_REQUIRE(P && Vw && V && T && Tfold && tau && h_fallback && m >= 2 * b && m <= (int64_t)PQC_MAXWG * 256 && ld >= m,
-             "panel_factor: bad arguments (128 <= m <= 20 480 rows, ld >= m)");
+  BK_REQUIRE(P && Vw && V && T && Tfold && tau, "panel_factor: null pointer (P, Vw, V, T, Tfold, tau)");
+  BK_REQUIRE(h_fallback, "panel_factor: null pointer (h_fallback)");
+  // S1Sched::has_panel: a panel has more than one row. Above: the kernels take m, n = m + 64 and the row index of a
+  // thread -- up to 64 + m rounded up to whole workgroups of 256 -- as int; the workspace (Layout, 64-bit) sets no limit
+  BK_REQUIRE(m >= 2 && m <= (int64_t)INT32_MAX - b - 512, "panel_factor: m out of range (2 <= m <= 2^31 - 577 rows)");
+  BK_REQUIRE(ld >= m, "panel_factor: ld too small (ld >= m)");
   const int n = (int)m + b;
   Layout L;
   const Region small = L.dev(8 * b * b);
@@ -3808,7 +3814,9 @@ int panel_factor(bigkrls_ctx* ctx, double* P, int64_t ld, int64_t m, double* Vw,
   Stage1 ops;
   BK_TRY(ops.init(ctx, P - b, n, taus, ws));
   ops.N = ld;
-  BK_REQUIRE(ops.chol_panel(0), "panel_factor: the register-resident factorisation is not available (BIGKRLS_PQ, co-residency)");
+  // pq_chol and pq_tail address row r of column c of the panel at the 32-bit byte offset 8 r + c * (8 ld), r < m, c < 64
+  BK_REQUIRE(!ops.chol_panel(0) || 63 * ld + m <= ((int64_t)1 << 29),
+             "panel_factor: ld too large for the 32-bit offsets of pq_chol (63 ld + m <= 2^29)");
   BK_TRY(ops.panel_qr(0, st));
   BK_TRY(ops.build_T(0, st));
   if (!ops.split_panel(0)) {     // the one-kernel form: W-space is V-space

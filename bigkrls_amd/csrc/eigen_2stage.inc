@@ -575,6 +575,14 @@ static_assert(S1_B == S2_B, "the schedule's panel width is the band width");
 constexpr int PQC_LD = 66;             // LDS row stride of the 64 x 64 matrices and of the staged rows
 constexpr double PQC_RATIO = 1e-5;      // min / max diagonal of the first Cholesky factor below which the panel is left
                                         // to the Householder kernel (kappa^2 eps must stay far below 1)
+// ... and the largest entry of E = Q1'Q1 - I after the first pass from which it is left to that kernel as well. The diagonal
+// of a Cholesky factor does not show its condition number (Kahan's matrix: diagonal >= 0.004, condition 1e12): a first
+// factor of a numerically singular Gram matrix that happens to go through passes the ratio, and the second factor of
+// the Q1 it gives (condition 30 ... 2000 measured) has its diagonal in [0.65, 1] -- the panel then came back with
+// |H'H - I| up to 1e-9 (tests/test_gpu_panel_routes.py). |E|_2 <= 64 max |E| < 1/2 bounds the singular values of Q1 to
+// (0.70, 1.23): its condition number is below sqrt(3) and the second pass leaves Q orthonormal to rounding. Kernel
+// matrices are far inside (max |E| ~ kappa^2 eps: 1e-6 at kappa = 1e5); panels up to kappa ~ 2e7 still pass.
+constexpr double PQC_E2MAX = 0x1p-7;
 #ifndef PQC_PARK
 #define PQC_PARK 1
 #endif
@@ -1127,15 +1135,18 @@ __global__ __launch_bounds__(256, 2) void pq_chol(double* __restrict__ P, int64_
         // Second pass on a well-conditioned panel: G = I + E with max |E| < 1e-8 (E ~ kappa^2 eps), and the Cholesky
         // factor of I + E is I + triu(E, 1) + diag(E) / 2 up to O(E^2) < 1e-16: no factorisation steps at all
         int nsteps = B / 4;
+        bool far = false;                       // second pass: max |E| >= PQC_E2MAX (uniform)
         if (stage == 1) {
           double emax = 0.0;
 #pragma unroll
           for (int a = 0; a < 4; ++a)
 #pragma unroll
             for (int b2 = 0; b2 < 4; ++b2) emax = fmax(emax, fabs(blkv[a][b2] - ((bi == bj && a == b2) ? 1.0 : 0.0)));
-          if (!(emax < 1e-8)) s_bad = 2;        // (every writer stores the same value; a NaN lands here too)
+          // (2: factorise; 3: too far from I for this method -- the largest wins; a NaN lands at 3)
+          if (!(emax < 1e-8)) atomicMax(&s_bad, (emax < PQC_E2MAX) ? 2 : 3);
           __syncthreads();
           const bool near_identity = (s_bad == 0);
+          far = (s_bad == 3);
           __syncthreads();
           if (tid == 0) s_bad = 0;
           if (near_identity) {
@@ -1206,7 +1217,7 @@ __global__ __launch_bounds__(256, 2) void pq_chol(double* __restrict__ P, int64_
         }
         // the first factor decides whether the panel is safe for this method; the second Gram matrix must be near I
         if (!bad && stage == 0 && dmin < PQC_RATIO * dmax) bad = 1;
-        if (!bad && stage == 1 && (dmin < 0.5 || dmax > 2.0)) bad = 1;
+        if (!bad && stage == 1 && (far || dmin < 0.5 || dmax > 2.0)) bad = 1;
         if (tid == 0) s_bad = bad;
         if (tid == 0 && blk == 0) {     // (diagnostics of the decision, read by the host in debug mode)
           double* dbg = mail + PQC_OFF_SLICES + PQC_NG + 8 * stage;

@@ -462,12 +462,19 @@ int bigkrls_dev_fill_random(bigkrls_ctx* ctx, double* p, int64_t count, uint32_t
 int bigkrls_dev_cholqr2(bigkrls_ctx* ctx, double* W, double* tmp, int64_t n, int64_t b, double* h_R,
                         int32_t* h_breakdown, double* d_R);
 /* One panel factorisation of the dense eigensolver's stage 1 (exposed for tests): the m x 64 panel P (device,
- * column-major, ld; 128 <= m <= 20 480) is factorised by CholeskyQR2 + Householder reconstruction as the reduction does
- * it -- head, the Householder kernel's slot, tail; the one-kernel form under BIGKRLS_PQ=fused. On return P holds R on
- * and above the diagonal of its top block and V below it; V (m x 64, ld m) the unit lower trapezoidal reflector block;
- * T (64 x 64) the upper triangular factor of H = I - V T V'; tau (64) its diagonal; Vw (m x 64, ld m) the operand
- * W = V U of the big product of stage 1 and Tfold (64 x 64) = U^-1 T, so that W Tfold = V T (Vw = V and Tfold = T for
- * the one-kernel form and for a panel left to the Householder kernel, which *h_fallback = 1 reports). */
+ * column-major, ld >= m; m >= 2) is factorised by the route the reduction takes for a panel of m rows under the current
+ * BIGKRLS_PQ and BIGKRLS_S1_TPQ. 128 <= m <= 20 480: CholeskyQR2 + Householder reconstruction -- head, the Householder
+ * kernel's slot, tail; the one-kernel form under BIGKRLS_PQ=fused; the Householder kernel alone under
+ * BIGKRLS_PQ=householder. m < 128 (the last panels of a decomposition): the Householder kernel. m > 20 480,
+ * BIGKRLS_PQ=steps or a context whose watchdog has fired: one launch per column. On return P holds R on and above the
+ * diagonal of its top block and below it V (CholeskyQR2) or V's columns before their scaling, x_c = V[:, c] / scale_c with
+ * the scales the reduction keeps beside tau (the Householder kernels and the per-column path); V (m x 64, ld m) the unit lower trapezoidal reflector block; T (64 x 64)
+ * the upper triangular factor of H = I - V T V'; tau (64) its diagonal; Vw (m x 64, ld m) the operand W = V U of the
+ * big product of stage 1 and Tfold (64 x 64) = U^-1 T, so that W Tfold = V T (Vw = V and Tfold = T wherever the split
+ * form did not run, and for a panel CholeskyQR2 left to the Householder kernel, which alone *h_fallback = 1 reports).
+ * m < 64: min(64, m) reflectors; columns m ... of V, entries m - 1 ... of tau and rows and columns m - 1 ... of T are
+ * zero, and all of P is R. BIGKRLS_EINVAL: a null pointer, m < 2, ld < m, or -- where CholeskyQR2 would run, whose
+ * kernels address the panel through 32-bit byte offsets -- 63 ld + m > 2^29. */
 int bigkrls_dev_panel_factor(bigkrls_ctx* ctx, double* P, int64_t ld, int64_t m, double* Vw, double* V, double* T,
                              double* Tfold, double* tau, int32_t* h_fallback);
 /* The symmetric rank-2k family of the MFMA GEMM core (exposed for tests): one unchanged call of the internal function

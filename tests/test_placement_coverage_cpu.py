@@ -39,11 +39,10 @@ COVERED = {
     "bigkrls_dev_gemv": "test_gpu_level2_helpers.py",
     "bigkrls_dev_diag": "test_gpu_level2_helpers.py",
     "bigkrls_dev_neffective": "test_gpu_neffective_exact.py",
+    "bigkrls_dev_panel_factor": "test_gpu_panel_routes.py",
 }
 
 NOT_YET = {
-    "bigkrls_dev_panel_factor": "tests/test_gpu_panel_split.py, its only direct caller, passes ld == m; with ld > m (the panel in "
-                                "place inside the n x n matrix) it runs only end to end through the dense eigensolver",
 }
 
 MUST_BE_COVERED = [name for name in COVERED if name.startswith("bigkrls_dev_kernel_")] + ["bigkrls_dev_deletion_residuals"]
